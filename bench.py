@@ -2,7 +2,7 @@
 """Headline benchmark: training meshes/s of the plain spiral autoencoder at 6890 vertices,
 batch 64 per GPU, fp32 (BASELINE.json configs[1]); synthetic meshes resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype f32|bf16]
+    python bench.py --gpus N --steps K --warmup W [--dtype f32|bf16] [--dump-outputs DIR] [--full]
     N > 1: one rank per GPU, RCCL gradient all-reduce.  Either launched by torch.distributed.run
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or - when WORLD_SIZE is not set -
     bench.py starts the N rank processes itself (fresh children, before this process touches the GPU),
@@ -10,9 +10,10 @@ batch 64 per GPU, fp32 (BASELINE.json configs[1]); synthetic meshes resident in 
 
 One "step" = the reference's training iteration (train_funcs.py:495-510): zero_grad, forward,
 L1 + 1e-2 * edge-ratio loss, backward, [gradient all-reduce], Adam(lr 1e-3, wd 5e-5) step.
-Prints ONE JSON line (rank 0) with the whole-job throughput, the roofline of the dominant HIP
-kernel (HIP events recorded by the library on the launch stream) and a CPU baseline (the
-oracle = the reference's formulation, on this box's host cores; a reported number, not a
+Prints ONE JSON line (rank 0) with the whole-job throughput and the time of one step; --dump-outputs
+writes what the last timed step computed.  --full adds, after the timed steps, the roofline of the
+dominant HIP kernel (HIP events recorded by the library on the launch stream), the other BASELINE
+configurations and a CPU baseline (the oracle = the reference's formulation, on the host cores; a reported number, not a
 target).  Nothing here reads /root/reference.
 """
 from __future__ import annotations
@@ -1150,6 +1151,37 @@ def injected_rank_failure(rank):
         time.sleep(3600)
 
 
+DUMP_MAX_ELEMS = 1 << 22          # arrays larger than this are written as a fixed, seeded sample of DUMP_SAMPLE_ELEMS elements
+DUMP_SAMPLE_ELEMS = 1 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, last):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy - the step's `loss`, its reconstruction
+    `x_hat` and latent codes `z`, and every parameter after the step's Adam update as `param.<name>`.  An array of more than
+    DUMP_MAX_ELEMS elements (at the headline's sizes: the two latent FCs' weights, 14.2M each) is written flat as the
+    DUMP_SAMPLE_ELEMS elements at numpy default_rng(0)'s sorted choice of indices - the same ones in every run with the same
+    shapes, so two builds compare output for output."""
+    import numpy as np
+    arrays = {"loss": last["loss"], "x_hat": last["x_hat"], "z": last["z"]}
+    arrays.update(("param." + n, p.detach()) for n, p in model.named_parameters())
+    host = {}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            host[name] = flat.float().cpu().numpy()
+        else:
+            host[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def dry_run(args, world, rank):
     """SH_BENCH_DRYRUN=1: the launch / rendezvous / timing / reporting skeleton of this script over gloo with no GPU work
     (the CPU container has no device): rendezvous, warm-up, K barrier-bracketed empty steps, MAX over ranks, one JSON
@@ -1172,7 +1204,7 @@ def dry_run(args, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     coll = None
-    if world > 1:                                       # the `collective` block of an N > 1 line, exercised end to end over gloo
+    if args.full and world > 1:                         # the `collective` block of an N > 1 line, exercised end to end over gloo
         import types
         stand_in = types.SimpleNamespace(buckets=[types.SimpleNamespace(numel=1 << 16, inplace=True), types.SimpleNamespace(numel=1 << 12, inplace=False)],
                                          large_dtype=None, avg=False, overlap=True)
@@ -1222,6 +1254,15 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=8, help="timed CPU-baseline steps (8 steps at batch 64 = ~13 s of host work)")
     ap.add_argument("--template", default=os.path.join("tests", "golden", "template6890.npz"),
                     help="mesh hierarchy fixture; tests/golden/template27554.npz + --batch 32 is BASELINE config 4")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline after its timed steps: the held-out L2 of the trained "
+                         "model, the roofline of the dominant kernel, the CPU baseline with its matched L2, the other BASELINE "
+                         "configurations (`secondary`) and, N > 1, the gradient messages timed alone (`collective`).  The --no-* "
+                         "switches above leave out parts of it.  Without --full a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): its loss, "
+                         "reconstruction and latent codes, and the parameters it left (see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1323,17 +1364,19 @@ def main():
 
     mark_phase("built")
     xin = torch.empty((B, h.sizes[0] + 1, 3), dtype=torch.float32, device=dev)
-    last = {}                                     # the step's loss tensor (a fixed address inside the graph's pool when captured)
+    last = {}                                     # the step's loss and outputs (fixed addresses inside the graph's pool when captured)
     unit = torch.ones((), dtype=torch.float32, device=dev)   # d loss / d loss, made once instead of one fill launch per step
 
     def fwd_bwd():
         optim.zero_grad(set_to_none=True)
-        x_hat, _ = model(xin)
+        x_hat, z = model(xin)
         loss, _ = sh.recon_loss(x_hat, xin, ft, 1e-2)     # l1 + 1e-2 * edge (train_funcs.py:501-508, traincfg.yaml:41), fused
         if reducer:
             reducer.prepare()
         loss.backward(unit)
         last["loss"] = loss.detach()
+        last["x_hat"] = x_hat.detach()
+        last["z"] = z.detach()
 
     def one_step():
         fwd_bwd()
@@ -1437,10 +1480,8 @@ def main():
         elapsed = float(t.item())
     mark_phase("timed")
     final_loss = float(last["loss"].item())
-
-    with torch.no_grad():
-        xh, _ = model(test)
-        l2mm = float(sh.vertex_l2_mm(xh, test).item())
+    if args.dump_outputs and rank == 0:           # before anything below runs the model again
+        dump_outputs(args.dump_outputs, model, last)
 
     result = {
         "metric": "training meshes/sec at %d verts, batch=%d" % (h.sizes[0], B),
@@ -1468,18 +1509,22 @@ def main():
                        sum(b.numel * (2 if (b.inplace and args.grad_comm == "bf16") else 4) for b in reducer.buckets) / 1e6,
                        "bf16 (large) + fp32" if args.grad_comm == "bf16" else "fp32")} if reducer else {})},
         "train_loss_last": final_loss,
-        "recon_l2_mm_after_run": l2mm,
     }
 
     result["whole_step"] = whole_step_block(model, B, args.dtype, elapsed / args.steps, args.f32_mma if args.dtype == "f32" else None)
 
+    if args.full:
+        with torch.no_grad():
+            xh, _ = model(test)
+            result["recon_l2_mm_after_run"] = float(sh.vertex_l2_mm(xh, test).item())
+
     # ---- the data-parallel job as RCCL saw it: ranks, devices, and the gradient messages timed alone (HIP events on this
     # rank's stream around blocking all-reduces of the step's own message sizes, MAX over ranks)
-    if reducer is not None and dist.is_initialized():
+    if args.full and reducer is not None and dist.is_initialized():
         result["collective"] = collective_block(reducer, world, rank, dev, backend)
 
     # ---- roofline of the dominant kernel: HIP events recorded by the library around every launch
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # EVERY rank runs these steps (the gradient all-reduce inside them is a collective); only rank 0 records
         nprof = 5
         from semantichuman_amd import stack as _stack
@@ -1499,14 +1544,14 @@ def main():
                 reducer.gather_weights()
         torch.cuda.synchronize()
         _stack.OVERLAP_WGRAD = overlap_was
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         recs = _lib.profile_records_by_kernel()
         _lib.profile_enable(False)
         result.update((roofline_bf16 if args.dtype == "bf16" else roofline_f32)(recs, model, B, nprof, h.sizes[0]))
 
     cpu_l2_ref = {}
     # ---- CPU baseline: the oracle (reference formulation) on this box's host cores, rank 0, N=1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import ref_cpu
         S, D, U = h.dense_constants()
         om = ref_cpu.SpiralAEOracle(FE, FD, 256, h.sizes, h.spiral_sizes, S, D, U)
@@ -1565,7 +1610,7 @@ def main():
 
     # ---- the other BASELINE configurations, measured in the same run (each a few hundred ms of GPU time): what README /
     # DESIGN quote for them is traceable to this line
-    if rank == 0 and world == 1 and not args.no_secondary and h.sizes[0] == 6890 and args.dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and h.sizes[0] == 6890 and args.dtype == "f32":
         result["secondary"] = secondary_block(sh, h, B, dev, init_state, data, test, ft, cpu_l2_ref.get("mm"), args)
 
     if rank == 0:

@@ -24,13 +24,13 @@ def _one_json_line(out):
 
 
 def test_self_launch_two_ranks():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     res = _one_json_line(r.stdout)
     assert res["n_gpus"] == 2 and res["steps"] == 3 and res["config"]["global_batch"] == 128 and res["dry_run"]
-    # the N > 1 line's `collective` block: world size as the process group sees it, one entry per rank, every gradient message timed
-    # with its ring bus bandwidth (the same code path an RCCL run takes, here over gloo with host tensors)
+    # the N > 1 line's `collective` block (--full): world size as the process group sees it, one entry per rank, every gradient message
+    # timed with its ring bus bandwidth (the same code path an RCCL run takes, here over gloo with host tensors)
     c = res["collective"]
     assert c["world_size"] == 2 and sorted(r["rank"] for r in c["ranks"]) == [0, 1] and len({r["pid"] for r in c["ranks"]}) == 2
     assert len(c["messages"]) == 2 and all(m["ms"] > 0 and m["bus_gbps"] > 0 and m["bytes"] > 0 for m in c["messages"])
@@ -44,7 +44,9 @@ def test_under_torch_distributed_run():
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
                         "--warmup", "0"], env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    assert _one_json_line(r.stdout)["n_gpus"] == 2
+    res = _one_json_line(r.stdout)
+    assert res["n_gpus"] == 2
+    assert res["collective"] is None                     # timing the gradient messages alone is a --full leg
 
 
 def test_failing_rank_propagates_exit_status():

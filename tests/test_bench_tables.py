@@ -77,3 +77,47 @@ def test_streaming_launches_are_priced(model):
     assert bench.parse_tag_linear("linear_fwd_x3_kernel<4>", "M=64 N=256 K=55296 split=247")[0] == 2.0 * 64 * 256 * 55296
     assert bench.parse_tag_f32("conv_p3s_kernel<2, true, 6, 4>", "R=863 B=64 K=512 N=128 grid=256x512") == ("bwd", 863, 512, 128)
     assert bench.parse_tag_f32("wgrad_stream_kernel<2, 4, 3, true, ilv>", "R=3446 B=64 K=352 N=32 grid=256 presum=4495") == ("wgt", 3446, 352, 32)
+
+
+def test_dump_outputs_sample_cast_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs without a GPU: loss, x_hat, z and every parameter as float32 .npy (bf16 widened); an array above
+    DUMP_MAX_ELEMS is written as the same seeded sample of DUMP_SAMPLE_ELEMS elements in every call, so two builds compare
+    output for output; a dump above DUMP_MAX_BYTES raises before anything is written."""
+    import torch
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Module()
+    m.big = torch.nn.Parameter(torch.randn(bench.DUMP_MAX_ELEMS + 5))
+    m.small = torch.nn.Parameter(torch.randn(4, 3))
+    last = {"loss": torch.tensor(0.25), "x_hat": torch.randn(2, 5, 3).to(torch.bfloat16), "z": torch.randn(2, 8)}
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(str(a), m, last)
+    bench.dump_outputs(str(b), m, last)
+    names = sorted(os.listdir(a))
+    assert names == ["loss.npy", "param.big.npy", "param.small.npy", "x_hat.npy", "z.npy"]
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+    idx = np.sort(np.random.default_rng(0).choice(bench.DUMP_MAX_ELEMS + 5, bench.DUMP_SAMPLE_ELEMS, replace=False))
+    assert np.array_equal(np.load(a / "param.big.npy"), m.big.detach().numpy()[idx])
+    assert np.array_equal(np.load(a / "param.small.npy"), m.small.detach().numpy())
+    assert np.array_equal(np.load(a / "x_hat.npy"), last["x_hat"].float().numpy())
+    assert np.load(a / "loss.npy") == np.float32(0.25)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000)
+    with pytest.raises(RuntimeError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "c"), m, last)
+    assert not (tmp_path / "c").exists()
+
+
+def test_dump_outputs_fit_at_the_benchmark_sizes(model, tmp_path):
+    """The dump of the headline (6890 vertices, batch 64) and of BASELINE config 4 (27 554 vertices, batch 32) stays under
+    DUMP_MAX_BYTES with the model's real parameter shapes."""
+    import torch
+    import bench
+    m, h = model
+    B = 64 if h.sizes[0] == 6890 else 32
+    last = {"loss": torch.zeros(()), "x_hat": torch.zeros(B, h.sizes[0] + 1, 3), "z": torch.zeros(B, 256)}
+    bench.dump_outputs(str(tmp_path), m, last)
+    files = os.listdir(tmp_path)
+    assert len(files) == 3 + len(list(m.parameters()))
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= bench.DUMP_MAX_BYTES

@@ -7,7 +7,7 @@ grep -h "wgrad\|total" $O/lr_s3.txt | cut -c1-110
 grep -h "wgrad\|total" $O/lr_s3_cot4.txt | cut -c1-110
 timeout 1200 python -m pytest tests -q -m gpu > $O/tests_all.txt 2>&1
 grep -n "passed\|failed\|FAILED" $O/tests_all.txt | tail -12
-timeout 300 python bench.py --steps 30 --warmup 5 --no-secondary > $O/bench_s3.json 2>$O/bench_s3.err
+timeout 300 python bench.py --full --steps 30 --warmup 5 --no-secondary > $O/bench_s3.json 2>$O/bench_s3.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r03e10/bench_s3.json").read().splitlines() if l.startswith("{")][-1])

@@ -9,8 +9,8 @@ SH_WS_TAIL_BLOCKS=256 timeout 300 python tools/layer_report.py 64 > $O/lr_tail25
 grep -h "total library" $O/lr_*.txt
 grep -h "wgrad_stream\|spmm" $O/lr_tail.txt | cut -c1-120
 for i in 1 2; do
-timeout 300 python bench.py --steps 30 --warmup 5 --no-secondary --no-cpu-baseline --no-roofline > $O/bench_tail_$i.json 2>/dev/null
-SH_WS_TAIL=0 timeout 300 python bench.py --steps 30 --warmup 5 --no-secondary --no-cpu-baseline --no-roofline > $O/bench_notail_$i.json 2>/dev/null
+timeout 300 python bench.py --full --steps 30 --warmup 5 --no-secondary --no-cpu-baseline --no-roofline > $O/bench_tail_$i.json 2>/dev/null
+SH_WS_TAIL=0 timeout 300 python bench.py --full --steps 30 --warmup 5 --no-secondary --no-cpu-baseline --no-roofline > $O/bench_notail_$i.json 2>/dev/null
 done
 python - <<'PY'
 import json,glob

@@ -5,10 +5,10 @@ O=gpurun_out/r03e19; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "conv_kernels_vs_oracle or launch_table or golden or stack" > $O/tests_parity.txt 2>&1
 tail -3 $O/tests_parity.txt
 for g in 1 0; do
-  SH_GG_OUT3=$g timeout 300 python bench.py --steps 200 --warmup 20 --no-secondary > $O/bench_out3_$g.json 2> $O/bench_out3_$g.err
+  SH_GG_OUT3=$g timeout 300 python bench.py --full --steps 200 --warmup 20 --no-secondary > $O/bench_out3_$g.json 2> $O/bench_out3_$g.err
 done
 for w in 32 96 128; do
-  SH_OUT3_WG_PER_XCD=$w timeout 300 python bench.py --steps 200 --warmup 20 --no-secondary --no-roofline > $O/bench_wg_$w.json 2> $O/bench_wg_$w.err
+  SH_OUT3_WG_PER_XCD=$w timeout 300 python bench.py --full --steps 200 --warmup 20 --no-secondary --no-roofline > $O/bench_wg_$w.json 2> $O/bench_wg_$w.err
 done
 python - <<'PY'
 import json,glob

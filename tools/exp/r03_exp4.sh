@@ -7,11 +7,11 @@ tail -n 4 $O/tests_all.txt
 timeout 300 python tools/layer_report.py 64 > $O/lr_skip.txt 2>$O/lr_skip.err
 SH_GG_SKIP=0 timeout 300 python tools/layer_report.py 64 > $O/lr_noskip.txt 2>$O/lr_noskip.err
 grep -h "total library" $O/lr_*.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_full.json 2>$O/bench_full.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2>$O/bench_full.err
 tail -c 600 $O/bench_full.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_reducer_graph.json 2>$O/bench_reducer_graph.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-graph > $O/bench_reducer_eager.json 2>$O/bench_reducer_eager.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype bf16 > $O/bench_reducer_graph_bf16.json 2>$O/bench_reducer_graph_bf16.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_reducer_graph.json 2>$O/bench_reducer_graph.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-graph > $O/bench_reducer_eager.json 2>$O/bench_reducer_eager.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype bf16 > $O/bench_reducer_graph_bf16.json 2>$O/bench_reducer_graph_bf16.err
 python - <<'PY'
 import json
 for f in ("bench_full","bench_reducer_graph","bench_reducer_eager","bench_reducer_graph_bf16"):

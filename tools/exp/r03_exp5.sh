@@ -6,9 +6,9 @@ grep -n "passed\|failed" $O/tests_all.txt | tail -2
 timeout 300 python tools/layer_report.py 64 > $O/lr_f32.txt 2>$O/lr_f32.err
 for co in 0 1 2; do
   SH_BC_CO=$co timeout 300 python tools/layer_report.py 64 tests/golden/template6890.npz bf16 > $O/lr_bf16_co$co.txt 2>$O/lr_bf16_co$co.err
-  SH_BC_CO=$co timeout 300 python bench.py --dtype bf16 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_co$co.json 2>$O/bench_bf16_co$co.err
+  SH_BC_CO=$co timeout 300 python bench.py --full --dtype bf16 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_co$co.json 2>$O/bench_bf16_co$co.err
 done
-timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32.json 2>$O/bench_f32.err
+timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32.json 2>$O/bench_f32.err
 grep -h "total library" $O/lr_*.txt
 python - <<'PY'
 import json,glob

@@ -7,8 +7,8 @@ SH_F32_MMA=split3 SH_S3_ALL9=1 timeout 900 python -m pytest tests -q -m gpu -k "
 grep -n "passed\|failed\|FAILED" $O/tests_s3_all9.txt | tail -8
 SH_F32_MMA=split3 timeout 300 python tools/layer_report.py 64 > $O/lr_s3.txt 2>$O/lr_s3.err
 SH_F32_MMA=split3 SH_S3_ALL9=1 timeout 300 python tools/layer_report.py 64 > $O/lr_s3_all9.txt 2>$O/lr_s3_all9.err
-SH_F32_MMA=split3 timeout 300 python bench.py --steps 30 --warmup 5 --no-secondary --no-roofline > $O/bench_s3.json 2>$O/bench_s3.err
-SH_F32_MMA=split3 SH_S3_ALL9=1 timeout 300 python bench.py --steps 30 --warmup 5 --no-secondary --no-roofline > $O/bench_s3_all9.json 2>$O/bench_s3_all9.err
+SH_F32_MMA=split3 timeout 300 python bench.py --full --steps 30 --warmup 5 --no-secondary --no-roofline > $O/bench_s3.json 2>$O/bench_s3.err
+SH_F32_MMA=split3 SH_S3_ALL9=1 timeout 300 python bench.py --full --steps 30 --warmup 5 --no-secondary --no-roofline > $O/bench_s3_all9.json 2>$O/bench_s3_all9.err
 grep -h "total library" $O/lr_*.txt
 python - <<'PY'
 import json,glob

@@ -4,7 +4,7 @@ O=gpurun_out/r03e7; mkdir -p $O
 timeout 1200 python -m pytest tests -q -m gpu > $O/tests_all.txt 2>&1
 grep -n "passed\|failed\|FAILED" $O/tests_all.txt | tail -12
 SH_F32_MMA=split3 timeout 300 python tools/layer_report.py 64 > $O/lr_s3.txt 2>$O/lr_s3.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_full.json 2>$O/bench_full.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2>$O/bench_full.err
 tail -c 400 $O/bench_full.err
 grep -h "total library\|linear\|tgemm\|reduce" $O/lr_s3.txt
 python - <<'PY'

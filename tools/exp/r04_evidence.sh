@@ -24,11 +24,11 @@ pmc 27554v_b32_f32_planes3 SH_F32_MMA=planes3 32 tests/golden/template27554.npz 
 for w in 6890v_b64_f32 6890v_b64_f32_planes3 6890v_b64_bf16 27554v_b32_f32_planes3; do
   cp $O/pmc_traffic_$w.json profiles/r04_pmc_traffic_$w.json; cp $O/pmc_traffic_$w.txt profiles/r04_pmc_traffic_$w.txt
 done
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err
-timeout 600 python bench.py --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16.json 2>$O/bench_bf16.err
-timeout 600 python bench.py --steps 20 --warmup 5 --f32-mma exact --no-secondary > $O/bench_f32_exact.json 2>$O/bench_f32_exact.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_f32.json 2>$O/bench_reducer_graph_f32.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --shard-optimizer > $O/bench_reducer_graph_f32_sharded.json 2>$O/bench_reducer_graph_f32_sharded.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16.json 2>$O/bench_bf16.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --f32-mma exact --no-secondary > $O/bench_f32_exact.json 2>$O/bench_f32_exact.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_f32.json 2>$O/bench_reducer_graph_f32.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --shard-optimizer > $O/bench_reducer_graph_f32_sharded.json 2>$O/bench_reducer_graph_f32_sharded.err
 bash tools/exp/r04_two_rank.sh > $O/two_rank_gloo.txt 2>&1
 cp gpurun_out/r04_two_rank_gloo.json gpurun_out/r04_two_rank_retry.json $O/ 2>/dev/null
 SH_F32_MMA=exact timeout 300 python tools/layer_report.py 64 > $O/layer_report_f32_exact.txt 2>/dev/null
@@ -41,9 +41,9 @@ timeout 600 python tools/p3_probe.py 64 --both > $O/p3_probe.txt 2>/dev/null
 timeout 600 python tools/p3_probe.py 64 --both --adversarial > $O/p3_probe_adversarial.txt 2>/dev/null
 SH_F32_MMA=planes3 timeout 600 python tools/bench_decode.py > $O/decode_config5.json 2>/dev/null
 # rocprofv3 kernel statistics of the bench command itself
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_f32 -o f32 --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_f32_rocprof_run.json 2>$O/prof_f32.err
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_ex -o ex --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --f32-mma exact > $O/bench_f32_exact_rocprof_run.json 2>$O/prof_ex.err
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_bf16 -o bf16 --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype bf16 > $O/bench_bf16_rocprof_run.json 2>$O/prof_bf16.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_f32 -o f32 --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/bench_f32_rocprof_run.json 2>$O/prof_f32.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_ex -o ex --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --f32-mma exact > $O/bench_f32_exact_rocprof_run.json 2>$O/prof_ex.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_bf16 -o bf16 --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --dtype bf16 > $O/bench_bf16_rocprof_run.json 2>$O/prof_bf16.err
 cp $(find $O/prof_f32 -name "*kernel_stats.csv" | head -1) $O/rocprof_kernel_stats_f32_planes3.csv 2>/dev/null
 cp $(find $O/prof_ex -name "*kernel_stats.csv" | head -1) $O/rocprof_kernel_stats_f32_exact.csv 2>/dev/null
 cp $(find $O/prof_bf16 -name "*kernel_stats.csv" | head -1) $O/rocprof_kernel_stats_bf16.csv 2>/dev/null

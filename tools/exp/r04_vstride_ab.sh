@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 python -m pytest tests/test_gpu_parity.py tests/test_configs.py tests/test_train_loop.py -m gpu -x -q 2>&1 | grep -E "passed|failed|rror" | tail -2
 for v in 0 1 0 1; do
   for m in exact planes3; do
-    SH_WS_VSTRIDE=$v python bench.py --f32-mma $m --no-cpu-baseline --no-secondary --steps 100 --warmup 10 2>/dev/null | python -c "import sys,json; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('vstride=$v $m', round(r['ms_per_step'],4), round(r.get('hip_kernel_ms_per_step'),4), r['roofline']['kernel'][:44], round(r['roofline']['frac'],3))"
+    SH_WS_VSTRIDE=$v python bench.py --full --f32-mma $m --no-cpu-baseline --no-secondary --steps 100 --warmup 10 2>/dev/null | python -c "import sys,json; r=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('vstride=$v $m', round(r['ms_per_step'],4), round(r.get('hip_kernel_ms_per_step'),4), r['roofline']['kernel'][:44], round(r['roofline']['frac'],3))"
   done
 done
 for v in 0 1; do

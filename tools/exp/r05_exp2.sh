@@ -8,8 +8,8 @@ for rep in 1 2; do for x in 0 1; do
   grep -h "wgrad_stream" $O/layer_planes3_xg${x}_$rep.txt | awk -v x=$x '{s+=$(NF-1)} END {print "xg" x " wgrad_stream sum", s}'
   grep -h total $O/layer_planes3_xg${x}_$rep.txt
 done; done
-timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_xg1.json 2>$O/bench_xg1.err
-SH_WS_XCD_RANGES=0 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_xg0.json 2>$O/bench_xg0.err
+timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_xg1.json 2>$O/bench_xg1.err
+SH_WS_XCD_RANGES=0 timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary > $O/bench_xg0.json 2>$O/bench_xg0.err
 python - <<'PY'
 import json
 for f in ("xg1","xg0"):

@@ -5,7 +5,7 @@ timeout 2400 python -m pytest tests -q -m gpu > $O/tests_all.txt 2>&1; tail -4 $
 SH_F32_MMA=planes3 timeout 300 python tools/layer_report.py 64 > $O/layer_planes3.txt 2>&1
 SH_F32_MMA=planes3 timeout 300 python tools/layer_report.py 32 tests/golden/template27554.npz f32 > $O/layer_c4.txt 2>&1
 grep -h "wgrad_stream\|total" $O/layer_planes3.txt $O/layer_c4.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err; tail -3 $O/bench_f32.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err; tail -3 $O/bench_f32.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/r05e5/bench_f32.json").read().splitlines() if l.startswith("{")][-1])

@@ -3,8 +3,8 @@ cd "$(dirname "$0")/../.."
 O=gpurun_out/r05fa; rm -rf $O; mkdir -p $O
 timeout 900 python -m pytest tests/test_optim.py tests/test_bf16.py -q -m gpu -x 2>&1 | tail -5
 for d in f32 bf16; do
-timeout 900 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --dtype $d > $O/bench_fused_$d.json 2>$O/bench_fused_$d.err
-timeout 900 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-fused-update --dtype $d > $O/bench_unfused_$d.json 2>$O/bench_unfused_$d.err
+timeout 900 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --dtype $d > $O/bench_fused_$d.json 2>$O/bench_fused_$d.err
+timeout 900 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-secondary --no-fused-update --dtype $d > $O/bench_unfused_$d.json 2>$O/bench_unfused_$d.err
 done
 python - <<'PY'
 import json

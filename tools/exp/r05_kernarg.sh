@@ -3,7 +3,7 @@ cd "$(dirname "$0")/../.."
 O=gpurun_out/r05ka; rm -rf $O; mkdir -p $O
 run() {  # label, env assignments...
   lbl=$1; shift
-  env "$@" timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/b.json 2>$O/b.err
+  env "$@" timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/b.json 2>$O/b.err
   python - "$lbl" <<'PY'
 import json,sys
 try:

@@ -2,8 +2,8 @@
 cd "$(dirname "$0")/../.."
 O=gpurun_out/r05soak; rm -rf $O; mkdir -p $O
 for d in f32 bf16; do
-timeout 900 python bench.py --steps 4000 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d > $O/soak_$d.json 2>$O/soak_$d.err
-timeout 900 python bench.py --steps 4000 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d --no-fused-update > $O/soak_two_$d.json 2>$O/soak_two_$d.err
+timeout 900 python bench.py --full --steps 4000 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d > $O/soak_$d.json 2>$O/soak_$d.err
+timeout 900 python bench.py --full --steps 4000 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d --no-fused-update > $O/soak_two_$d.json 2>$O/soak_two_$d.err
 done
 python - <<'PY'
 import json

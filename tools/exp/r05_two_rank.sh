@@ -3,12 +3,12 @@
 # its GPU-free supervisor; then the same with an injected rank failure in the first attempt (the retry must produce the line)
 cd "$(dirname "$0")/../.."
 O=gpurun_out; mkdir -p $O
-SH_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/r05_two_rank_gloo.json 2> $O/r05_two_rank_gloo.err
+SH_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary > $O/r05_two_rank_gloo.json 2> $O/r05_two_rank_gloo.err
 echo "rc=$?"
-SH_BENCH_BACKEND=gloo SH_BENCH_TEST_RANK_FAIL=0:1 SH_BENCH_FAIL_GRACE=3 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline > $O/r05_two_rank_retry.json 2> $O/r05_two_rank_retry.err
+SH_BENCH_BACKEND=gloo SH_BENCH_TEST_RANK_FAIL=0:1 SH_BENCH_FAIL_GRACE=3 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline > $O/r05_two_rank_retry.json 2> $O/r05_two_rank_retry.err
 echo "rc=$?"
 # ... and with a rank that HANGS after the rendezvous in the first attempt: the progress watchdog ends it, the next attempt reports
-SH_BENCH_BACKEND=gloo SH_BENCH_TEST_RANK_HANG=0:1 SH_BENCH_PHASE_TIMEOUT=20 SH_BENCH_FAIL_GRACE=3 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline > $O/r05_two_rank_hang.json 2> $O/r05_two_rank_hang.err
+SH_BENCH_BACKEND=gloo SH_BENCH_TEST_RANK_HANG=0:1 SH_BENCH_PHASE_TIMEOUT=20 SH_BENCH_FAIL_GRACE=3 python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-roofline > $O/r05_two_rank_hang.json 2> $O/r05_two_rank_hang.err
 echo "rc=$?"
 python - <<'PY'
 import json

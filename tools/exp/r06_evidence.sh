@@ -35,18 +35,18 @@ python3 tools/pmc_table.py $O/sq_wp3_table.txt $O/sq_wp3_1 $O/sq_wp3_2 $O/sq_wp3
 i=0; for set in "$A" "$B"; do i=$((i+1)); SH_F32_MMA=planes3 timeout 300 rocprofv3 --pmc $set --kernel-trace -d $O/sq_sem_$i -o p --output-format csv -- python3 tools/bench_semantic.py --steps 5 > $O/sq_sem_$i.log 2>&1; done
 python3 tools/pmc_table.py $O/sq_sem_table.txt $O/sq_sem_1 $O/sq_sem_2 > /dev/null 2>&1; grep -A1 -E "^pairdist|^grouped|^part_|^joint" $O/sq_sem_table.txt > $P/r06_pmc_sq_semantic.txt; rm -rf $O/sq_sem_1 $O/sq_sem_2
 # bench lines
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err
-timeout 600 python bench.py --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16.json 2>$O/bench_bf16.err
-timeout 600 python bench.py --steps 20 --warmup 5 --f32-mma exact --no-secondary > $O/bench_f32_exact.json 2>$O/bench_f32_exact.err
-SH_P3_WGRAD=0 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_exact_wgrad.json 2>/dev/null
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_f32.json 2>$O/bench_f32.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype bf16 > $O/bench_bf16.json 2>$O/bench_bf16.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --f32-mma exact --no-secondary > $O/bench_f32_exact.json 2>$O/bench_f32_exact.err
+SH_P3_WGRAD=0 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_exact_wgrad.json 2>/dev/null
 # the same box with round 5's launches (exact weight gradients with their riders, dense transposed tables, one-row lists, every fp32 row written) ...
-SH_P3_WGRAD=0 SH_P3_RAGGED=0 SH_P3_GROUPED=0 SH_P3_DROP_FP32=0 SH_P3_YPREV_IMG=0 timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_round5_launches.json 2>/dev/null
+SH_P3_WGRAD=0 SH_P3_RAGGED=0 SH_P3_GROUPED=0 SH_P3_DROP_FP32=0 SH_P3_YPREV_IMG=0 timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_round5_launches.json 2>/dev/null
 # ... and this round's, measured the same way (100 steps); bf16 with the dense backward-data tables next to the ragged default
-timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_100steps.json 2>/dev/null
-SH_BF16_RAGGED=0 timeout 600 python bench.py --steps 100 --warmup 10 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_dense_tables.json 2>/dev/null
-timeout 600 python bench.py --steps 100 --warmup 10 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_100steps.json 2>/dev/null
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_f32.json 2>$O/bench_reducer_graph_f32.err
-SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_bf16_sharded.json 2>$O/bench_reducer_graph_bf16_sharded.err
+timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_f32_100steps.json 2>/dev/null
+SH_BF16_RAGGED=0 timeout 600 python bench.py --full --steps 100 --warmup 10 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_dense_tables.json 2>/dev/null
+timeout 600 python bench.py --full --steps 100 --warmup 10 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_bf16_100steps.json 2>/dev/null
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_f32.json 2>$O/bench_reducer_graph_f32.err
+SH_BENCH_FORCE_REDUCER=1 timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype bf16 --no-cpu-baseline --no-secondary --no-roofline > $O/bench_reducer_graph_bf16_sharded.json 2>$O/bench_reducer_graph_bf16_sharded.err
 for f in bench_f32 bench_bf16 bench_f32_exact bench_f32_exact_wgrad bench_f32_round5_launches bench_f32_100steps bench_bf16_dense_tables bench_bf16_100steps bench_reducer_graph_f32 bench_reducer_graph_bf16_sharded; do grep "^{" $O/$f.json | tail -1 > $P/r06_$f.json; done
 # layer reports
 SH_F32_MMA=exact timeout 300 python tools/layer_report.py 64 > $P/r06_layer_report_f32_exact.txt 2>/dev/null
@@ -67,7 +67,7 @@ SH_F32_MMA=planes3 timeout 600 python tools/bench_decode.py > $O/decode_config5.
 # rocprofv3 kernel statistics of the bench command itself
 for v in "f32:" "f32_exact:--f32-mma exact" "bf16:--dtype bf16"; do
   n=${v%%:*}; a=${v#*:}
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o p --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $a > $O/bench_${n}_rocprof_run.json 2>$O/prof_$n.err
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o p --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $a > $O/bench_${n}_rocprof_run.json 2>$O/prof_$n.err
   cp $(find $O/prof_$n -name "*kernel_stats.csv" | head -1) $P/r06_rocprof_kernel_stats_$n.csv 2>/dev/null
   grep "^{" $O/bench_${n}_rocprof_run.json | tail -1 > $P/r06_bench_${n}_rocprof_run.json
   rm -rf $O/prof_$n
@@ -76,7 +76,7 @@ timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_sem -o p --output-format
 cp $(find $O/prof_sem -name "*kernel_stats.csv" | head -1) $P/r06_rocprof_kernel_stats_semantic.csv 2>/dev/null; rm -rf $O/prof_sem
 # one replayed step as a timeline
 for d in f32 bf16; do
-  timeout 600 rocprofv3 --kernel-trace -d $O/tr_$d -o t --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d > $O/bench_${d}_trace_run.json 2>/dev/null
+  timeout 600 rocprofv3 --kernel-trace -d $O/tr_$d -o t --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-roofline --dtype $d > $O/bench_${d}_trace_run.json 2>/dev/null
   python3 tools/timeline.py $(find $O/tr_$d -name "*kernel_trace.csv" | head -1) > $P/r06_timeline_$d.txt
   rm -rf $O/tr_$d
 done

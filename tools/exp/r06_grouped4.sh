@@ -7,10 +7,10 @@ timeout 600 python tools/p3_probe.py 64 --both > $O/p3_probe.txt 2>&1; grep -E "
 SH_F32_MMA=planes3 timeout 300 python tools/layer_report.py 64 tests/golden/template6890.npz f32 > $O/layer_rule.txt 2>&1; grep -E "conv_p3g|conv_p3r|conv_p3<|total" $O/layer_rule.txt | cut -c1-170
 SH_P3_GRP_MIN_ITEMS_PER_CU=0 SH_F32_MMA=planes3 timeout 300 python tools/layer_report.py 64 tests/golden/template6890.npz f32 > $O/layer_all.txt 2>&1; grep -E "conv_p3g|total" $O/layer_all.txt | cut -c1-170
 for rep in 1 2; do for cfg in "SH_P3_GROUPED=1" "SH_P3_GROUPED=0" "SH_P3_GRP_MIN_ITEMS_PER_CU=0"; do
-  env $cfg timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench.json 2>$O/bench.err
+  env $cfg timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-roofline > $O/bench.json 2>$O/bench.err
   echo "== f32 $cfg rep $rep: $(python -c "import json; d=json.loads([l for l in open('$O/bench.json') if l.startswith('{')][-1]); print(d['ms_per_step'], d['value'])" 2>&1 | tail -1)"
 done; done
 for cfg in "SH_P3_GROUPED=1" "SH_P3_GROUPED=0"; do
-  env $cfg timeout 400 python bench.py --steps 40 --warmup 10 --batch 32 --template tests/golden/template27554.npz --no-cpu-baseline --no-secondary --no-roofline > $O/bench_c4.json 2>$O/bench_c4.err
+  env $cfg timeout 400 python bench.py --full --steps 40 --warmup 10 --batch 32 --template tests/golden/template27554.npz --no-cpu-baseline --no-secondary --no-roofline > $O/bench_c4.json 2>$O/bench_c4.err
   echo "== config 4 $cfg: $(python -c "import json; d=json.loads([l for l in open('$O/bench_c4.json') if l.startswith('{')][-1]); print(d['ms_per_step'])" 2>&1 | tail -1)"
 done

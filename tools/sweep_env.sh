@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for setting in "$@"; do
-    out=$(env $setting python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1)
+    out=$(env $setting python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1)
     python - "$setting" "$out" <<'EOF'
 import json, sys
 setting, line = sys.argv[1], sys.argv[2]
