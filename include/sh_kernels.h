@@ -289,7 +289,13 @@ SH_API int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float
  * 2).  With 2 a step whose input was left as its image alone must run on the images: SH_ERR_INVALID_ARG when the buffers given
  * do not allow it (never a read of unwritten rows); and the gradient rows this pass itself hands from step to step are written
  * as their image alone where the step that takes them reads nothing else (ragged source lists or a table without
- * multiplicities, plane weight gradient). */
+ * multiplicities, plane weight gradient).
+ * dW[p] == NULL (the dW array itself is required) means: do not compute the weight gradient of the conv step(s) of parameter p
+ * (a frozen layer; dbias[p] must then be NULL too).  Such a step launches no weight-gradient kernel and has no job in the slab
+ * reduction; what used to ride in that launch runs on its own: the last pre-sum level as the standalone sh_spmm_p3 launch, the
+ * role-swapped 16 -> 3 layer's input gradient as the ordinary backward-data kernel.  Weight transposes / fragments are still
+ * made (backward-data reads them).  A forward pass whose backward pass will skip a step must run with keep_fp32 == 1 (the
+ * skipped step reads fp32 rows), and this call then gets acts_fp32 == 1. */
 SH_API int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, int x_layout, int rows0, int c0, int B,
                              const float* const* acts, const float* g, int out_layout, const float* const* weights,
                              float* const* gin, float* dpre_last, float* const* weight_t, void* const* workspace,
@@ -456,6 +462,24 @@ SH_API int sh_part_pairdist_loss_bwd_scale(const float* grad_raw, const int32_t*
 SH_API int sh_measure_girth(const float* v, int64_t v_sb, const int32_t* ring_ptr, const int32_t* ring_a,
                      const int32_t* ring_b, const float* ring_f, int B, int P, float* girth, sh_stream_t stream);
 SH_API int sh_bone_length(const float* kps, const int32_t* bones, int B, int K, int P, float* length, sh_stream_t stream);
+/* Their gradients (fp32, deterministic: gather form over transposed lists the host builds once - measure.py GirthRings / Bones;
+ * every term of an output row is summed in list order, no atomics; plain stores of every element of the output).
+ *  - sh_measure_girth_bwd: g_girth [B][P] -> g_v contiguous [B][rows][3] (OVERWRITTEN).  pt_ring [n_points] = ring of each ring
+ *    point; vt_ptr [n_vt + 1] / vt_pt / vt_w: CSR over vertex rows of (ring point k, weight) with weight 1 - ring_f[k] for
+ *    ring_a[k] and ring_f[k] for ring_b[k], entries of a row ordered by k (a before b); n_vt <= rows, rows >= n_vt get 0.
+ *    Segment k joins point k and point (k+1) mod n as in sh_measure_girth (n == 1: length 0; n == 2: the two points twice); a
+ *    zero-length segment has subgradient 0.  v / v_sb as for sh_measure_girth.
+ *  - sh_bone_length_bwd: g_len [B][P] -> g_kps contiguous [B][K][3] (OVERWRITTEN).  jt_ptr [n_jt + 1] / jt_bone / jt_w: CSR over
+ *    joints of (bone, signed weight): +1 for the head, -1 for a 2-joint bone's tail, -1/2 for each tail joint of a 3-joint bone;
+ *    entries ordered by bone.  Joints >= n_jt get 0; a zero-length bone has subgradient 0.
+ *  - sh_joint_regress_bwd: g_kps contiguous [B][K][3] -> g_x contiguous [B][rows][3] = J^T g_kps for rows < N (J dense [K][N],
+ *    joints summed in order), 0 for N <= row < rows (the dummy row). */
+SH_API int sh_measure_girth_bwd(const float* v, int64_t v_sb, const int32_t* ring_ptr, const int32_t* ring_a, const int32_t* ring_b,
+                                const float* ring_f, const int32_t* pt_ring, const int32_t* vt_ptr, const int32_t* vt_pt,
+                                const float* vt_w, int n_vt, const float* g_girth, int B, int P, int rows, float* g_v, sh_stream_t stream);
+SH_API int sh_bone_length_bwd(const float* kps, const int32_t* bones, const int32_t* jt_ptr, const int32_t* jt_bone, const float* jt_w,
+                              int n_jt, const float* g_len, int B, int K, int P, float* g_kps, sh_stream_t stream);
+SH_API int sh_joint_regress_bwd(const float* g_kps, const float* J, int B, int N, int K, int rows, float* g_x, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
@@ -635,7 +659,8 @@ SH_API int sh_adam_step_bf16(int n_tensors, float* const* params, const float* c
  * sh_conv_wfrag_bytes(S, cin, cout) / (S, cout, cin) bytes which the call fills from the fp32 master `weights` (one
  * conversion launch per pass) - unless wfrag_ready != 0: then they already hold the converted CURRENT weights (the caller
  * ran sh_conv_wfrag_prep_multi itself, e.g. once for both stacks and both orientations of a training step) and no
- * conversion is launched.  workspace[i] >= sh_spiral_conv_bwd_wgt_workspace_bf16.  Everything else as above. */
+ * conversion is launched.  workspace[i] >= sh_spiral_conv_bwd_wgt_workspace_bf16.  Everything else as above, dW[p] == NULL
+ * included (no weight gradient for parameter p: no bf16 weight-gradient launch, no reduction job, no role-swapped 16 -> 3 kernel). */
 SH_API int sh_stack_forward_bf16(int n_steps, const sh_stack_step* steps, const void* x, int x_dtype, int x_layout, int rows0,
                                  int c0, int B, const float* const* weights, const float* const* biases, void* const* wfrag,
                                  int wfrag_ready, void* const* outs, int out_dtype, int out_layout, sh_stream_t stream);

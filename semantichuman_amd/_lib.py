@@ -67,6 +67,9 @@ SIGNATURES = {
     "sh_part_pairdist_loss_bwd_scale": (c_int, [_P] * 6 + [_I] * 4 + [_P, _P]),
     "sh_measure_girth": (c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _P, _P]),
     "sh_bone_length": (c_int, [_P, _P, _I, _I, _I, _P, _P]),
+    "sh_measure_girth_bwd": (c_int, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "sh_bone_length_bwd": (c_int, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
+    "sh_joint_regress_bwd": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "sh_dataset_normalize": (c_int, [_P, _P, _I, _I, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P]),
     "sh_gather_meshes": (c_int, [_P, _L, _P, _I, _P, _P]),
     "sh_adam_step": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P] + [ctypes.c_double] * 4 + [_P]),

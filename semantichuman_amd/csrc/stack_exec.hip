@@ -276,9 +276,14 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
         bool gi_img_done = false;
         if (s.kind == 0) {
             SH_REQUIRE(workspace && workspace[i], SH_ERR_INVALID_ARG, "sh_stack_backward: no workspace for step %d", i);
+            // dW[param] == NULL: a frozen layer - no weight gradient; what rides in that launch (the last pre-sum level, the thin
+            // layer's input gradient) runs in the launches the step takes without it
+            const bool wgrad = dW[s.param] != nullptr;
+            SH_REQUIRE(wgrad || !dbias || !dbias[s.param], SH_ERR_INVALID_ARG,
+                       "sh_stack_backward: parameter %d has a dbias buffer but no dW buffer", s.param);
             // a 16 -> 3 channel layer takes its weight gradient in role-swapped form (wgrad_thin.hip): it reads the extended
             // gradient buffer through the transposed table, so it runs after the pre-sum launches below
-            const bool thin = want_in && s.table_t && s.R == s.n_in && il.sb == s.cin && il.sv == (long)B * s.cin && cl.sb == s.cout &&
+            const bool thin = wgrad && want_in && s.table_t && s.R == s.n_in && il.sb == s.cin && il.sv == (long)B * s.cin && cl.sb == s.cout &&
                               cl.sv == (long)B * s.cout && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32);
             const bool p3 = !thin && cur_img && cl.sb == s.cout && cl.sv == (long)B * s.cout;
             // backward-data over ragged source lists (round 6): every source an image row, no pre-summed rows - neither the launches
@@ -292,7 +297,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
             const bool rag = grp_b || (p3 && rag_on && want_in && s.rag_rows && s.rag_pos && sh_spiral_conv_p3_rag_ok(B, s.S, s.cout, s.cin, s.rag_L));
             // the last pre-sum level of this layer rides in the weight-gradient launch (sh_spiral_conv_bwd_wgt_presum); an
             // earlier level (very long lists: two levels) runs first, on its own
-            const bool ride = !thin && !rag && want_in && s.table_t && (s.n1 || s.n2);
+            const bool ride = wgrad && !thin && !rag && want_in && s.table_t && (s.n1 || s.n2);
             // SH_P3_PRESUM_IMG=1: the riders / pre-sum launches write the image of their rows; default 0: they stay plain and the
             // backward-data kernel splits those rows itself from the fp32 buffer (they are ~6 % of what it gathers)
             // pre-summed rows: imaged by their producers (the riders / pre-sum launches), or - LDS-resident plane kernel and at
@@ -308,7 +313,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                                 pimg0 ? pimg0 + sh_p3_bytes(s.R, B, s.cout) : nullptr, nullptr, 0, 0, 0, -1, B, s.n1, s.cout, stream);
                 if (rc != SH_OK) return rc;
             }
-            const bool p3w = p3 && p3_wgrad_on && i > 0 && in_planes && in_planes[i] && il.sb == s.cin && il.sv == (long)B * s.cin &&
+            const bool p3w = wgrad && p3 && p3_wgrad_on && i > 0 && in_planes && in_planes[i] && il.sb == s.cin && il.sv == (long)B * s.cin &&
                              sh_spiral_conv_bwd_wgt_p3_ok(B, s.R, s.S, s.cin, s.cout) && (((long)s.R * (B / 16)) % 2 == 0 || s.zero_row >= 0) &&
                              workspace_bytes[i] >= sh_spiral_conv_bwd_wgt_p3_workspace(B, s.R, s.S, s.cin, s.cout);
             // the forward pass left the fp32 rows of this step's input unwritten (keep_fp32 == 2) when this much was known from the
@@ -317,7 +322,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
             SH_REQUIRE(!in_dropped || (p3w && (!yprev || (in_planes[i] && yl.sb == s.cin && yl.sv == (long)B * s.cin))), SH_ERR_INVALID_ARG,
                        "sh_stack_backward: step %d: the forward pass kept only the image of its input (keep_fp32 == 2) but this pass cannot run "
                        "the step on images (gin_planes / wfrag3_t / in_planes / workspace of sh_spiral_conv_bwd_wgt_p3_workspace bytes)", i);
-            if (!thin) {
+            if (wgrad && !thin) {
                 const sh_csr_ref& lm = s.n2 ? s.sum2 : s.sum1;
                 const int ln = ride ? (s.n2 ? s.n2 : s.n1) : 0;
                 float* lout = mut0 + (long)(s.R + (s.n2 ? s.n1 : 0)) * cl.sv;
@@ -339,10 +344,11 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                 }
                 if (rc != SH_OK) return rc;
             }
-            job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
-            jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout; jK[njobs] = p3w ? 2 : 0;
-            SH_REQUIRE(job_dW[njobs], SH_ERR_INVALID_ARG, "sh_stack_backward: no dW buffer for parameter %d", s.param);
-            ++njobs;
+            if (wgrad) {
+                job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
+                jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout; jK[njobs] = p3w ? 2 : 0;
+                ++njobs;
+            }
             if (want_in) {
                 SH_REQUIRE(s.table_t, SH_ERR_INVALID_ARG, "sh_stack_backward: step %d has no transposed table", i);
                 float* mut = const_cast<float*>(cur);          // the extra rows behind the R real ones of this step's own buffer
@@ -555,19 +561,23 @@ int sh_stack_backward_bf16(int n_steps, const sh_stack_step* steps, const void* 
         }
         if (s.kind == 0) {
             SH_REQUIRE(workspace && workspace[i], SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: no workspace for step %d", i);
+            const bool wgrad = dW[s.param] != nullptr;                 // NULL: frozen layer, no weight gradient (see sh_stack_backward)
+            SH_REQUIRE(wgrad || !dbias || !dbias[s.param], SH_ERR_INVALID_ARG,
+                       "sh_stack_backward_bf16: parameter %d has a dbias buffer but no dW buffer", s.param);
             // role-swapped weight gradient of a 16 -> 3 channel layer (see sh_stack_backward)
-            const bool thin = want_in && s.table_t && cd == SH_DTYPE_F32 && ind == SH_DTYPE_BF16 && s.R == s.n_in && il.sb == s.cin &&
+            const bool thin = wgrad && want_in && s.table_t && cd == SH_DTYPE_F32 && ind == SH_DTYPE_BF16 && s.R == s.n_in && il.sb == s.cin &&
                               il.sv == (long)B * s.cin && cl.sb == s.cout && cl.sv == (long)B * s.cout &&
                               sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_BF16);
-            if (!thin) {
+            if (wgrad && !thin) {
                 rc = sh_spiral_conv_bwd_wgt_bf16(cur, cd, cl.sv, cl.sb, inp, ind, il.sv, il.sb, s.table, workspace[i], workspace_bytes[i], B,
                                                  s.R, s.S, s.cin, s.cout, stream);
                 if (rc != SH_OK) return rc;
             }
-            job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
-            jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout;
-            SH_REQUIRE(job_dW[njobs], SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: no dW buffer for parameter %d", s.param);
-            ++njobs;
+            if (wgrad) {
+                job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
+                jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout;
+                ++njobs;
+            }
             if (want_in) {
                 SH_REQUIRE(s.table_t, SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: step %d has no transposed table", i);
                 // backward-data over ragged source lists (round 6): every source a real row of dpre - neither the pre-sum launches nor

@@ -3,13 +3,17 @@ and utils_SH.edit_skl (:412-440) as functions, plus the OBJ writer the demo uses
 
 All edits are small tensor manipulations on latents / joints; the heavy part is `model.decode`, which runs the
 HIP decoder stack.  `decode_edits` reproduces the demo's seven decodes for a (shape, skeleton, style) triple.
+
+Measurement-targeted editing: `fit_latents` optimises part latents through the frozen decoder against any per-body objective
+(the decoder's backward pass then computes no weight gradient); `fit_part_girths` asks for girths ("chest +4 %, waist unchanged")
+through the differentiable measurements of measure.py.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import constants
+from . import constants, measure, optim
 from .part_losses import kps2skl, skl2kps
 
 # utils_SH.py:21-24 (SMPL-style kinematic tree of the 24 body joints)
@@ -104,3 +108,101 @@ def save_obj(obj_path, v, f, partcolor_list=None, vert_part_index=None):
             fp.write("v %f %f %f %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
         for t in f + 1:
             fp.write("f %d %d %d\n" % (t[0], t[1], t[2]))
+
+
+# ------------------------------------------------------------------------------------------------ fitting
+def _default_dummy(model, z):
+    """The decoder's dummy row as demo.py:74 makes it: zeros as wide as the decoder stack's input (its first conv's in_c)."""
+    return torch.zeros((z.shape[0], 1, model.dconv[0].in_c), device=z.device)
+
+
+def _decode(model, z, z_kps, dummy):
+    if hasattr(model, "kps_encode"):                                   # SemanticHuman: decode(z, z_part_kps, dummy)
+        return model.decode(z, z_kps, dummy)
+    return model.decode(z)                                             # plain SpiralAutoencoder: decode(z)
+
+
+def fit_latents(model, z, z_kps, objective, parts, *, steps, lr, dummy=None):
+    """Optimise the latents `z[:, parts]` so that `objective(model.decode(...))` falls; returns (new z, loss per step).
+
+    objective(x_hat) -> one scalar per body [B]; each step minimises their sum (bodies are independent).  Per step: decode ->
+    objective -> backward to the moving latents -> the library's Adam (lr) on them; no host synchronisation.  Only z[:, parts]
+    moves: the rest of z and z_kps are returned / left bitwise as given.  The model's parameters are frozen for the call (the
+    decoder's backward pass computes no weight gradient) and their requires_grad flags restored afterwards; their .grad are not
+    touched.  SemanticHuman: z [B, P, d], z_kps [B, P, d_kps], parts = part indices (None: all), dummy = the decoder's dummy row
+    (None: zeros, as demo.py).  Plain SpiralAutoencoder: z [B, nz], z_kps ignored, parts = latent indices (None: all).
+    The loss tensor [steps] stays on the device."""
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    semantic = hasattr(model, "kps_encode")
+    z0 = z.detach()
+    if not (z0.is_cuda and z0.dtype == torch.float32):
+        raise RuntimeError("fit_latents: z must be an fp32 HIP tensor (got %s %s)" % (z0.device, z0.dtype))
+    idx = torch.arange(z0.shape[1], device=z0.device) if parts is None else \
+        torch.as_tensor(np.asarray(parts, dtype=np.int64).reshape(-1), device=z0.device)
+    zk = z_kps.detach() if (semantic and z_kps is not None) else None
+    if semantic and dummy is None:
+        dummy = _default_dummy(model, z0)
+    dummy = dummy.detach() if dummy is not None else None
+    var = z0.index_select(1, idx).contiguous().requires_grad_(True)
+    opt = optim.Adam([var], lr=lr)
+    losses = torch.empty(steps, dtype=torch.float32, device=z0.device)
+    params = list(model.parameters())
+    flags = [p.requires_grad for p in params]
+    try:
+        for p in params:
+            p.requires_grad_(False)
+        for t in range(steps):
+            x_hat = _decode(model, z0.index_copy(1, idx, var), zk, dummy)
+            loss = objective(x_hat).sum()
+            var.grad = None
+            loss.backward()
+            opt.step()
+            losses[t] = loss.detach()
+    finally:
+        for p, f in zip(params, flags):
+            p.requires_grad_(f)
+    return z0.index_copy(1, idx, var.detach()), losses
+
+
+def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, bones=None, J=None, hold_lengths=False, *,
+                    steps=200, lr=1e-2, dummy=None):
+    """Edit bodies by their girths: ring `edit[i]` of body b should measure target[b, i]; the rings in `hold` keep the girth they
+    have on decode(z); with hold_lengths, the lengths of `bones` (a measure.Bones or a bone list) on the joints J @ x_hat
+    (measure.joints, J [K, N] on the device) keep theirs too.  The objective per body is the sum of squared relative errors.
+    Batched: B bodies, each with its own targets, in one loop (fit_latents moves z[:, parts]).
+    rings: a measure.GirthRings; target [B, len(edit)].  Returns (new z, girths [B, P] of the result, loss per step [steps])."""
+    edit = [int(i) for i in np.asarray(edit).reshape(-1)]
+    hold = [int(i) for i in np.asarray(hold, dtype=np.int64).reshape(-1)]
+    dev = z.device
+    target = torch.as_tensor(target, dtype=torch.float32, device=dev).reshape(z.shape[0], len(edit))
+    if hold_lengths and (bones is None or J is None):
+        raise ValueError("hold_lengths needs bones and J")
+    if hold_lengths and not isinstance(bones, measure.Bones):
+        bones = measure.Bones(bones, dev)
+    if hold_lengths:
+        J = torch.as_tensor(J, dtype=torch.float32, device=dev).contiguous()
+    semantic = hasattr(model, "kps_encode")
+    if semantic and dummy is None:
+        dummy = _default_dummy(model, z)
+    e_idx = torch.tensor(edit, dtype=torch.int64, device=dev)
+    h_idx = torch.tensor(hold, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        x0 = _decode(model, z.detach(), z_kps, dummy)
+        g_hold = measure.girths(x0, rings).index_select(1, h_idx)
+        l_hold = measure.bone_lengths(measure.joints(x0, J), bones) if hold_lengths else None
+
+    def objective(x_hat):
+        g = measure.girths(x_hat, rings)
+        err = ((g.index_select(1, e_idx) - target) / target).pow(2).sum(1)
+        if hold:
+            err = err + ((g.index_select(1, h_idx) - g_hold) / g_hold).pow(2).sum(1)
+        if hold_lengths:
+            ln = measure.bone_lengths(measure.joints(x_hat, J), bones)
+            err = err + ((ln - l_hold) / l_hold).pow(2).sum(1)
+        return err
+
+    z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
+    with torch.no_grad():
+        g_final = measure.girths(_decode(model, z_new, z_kps, dummy), rings)
+    return z_new, g_final, losses

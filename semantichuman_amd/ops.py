@@ -370,6 +370,37 @@ def bone_length(kps, bones):
     return out
 
 
+def measure_girth_bwd(v, rings, g_girth):
+    """Gradient of measure_girth w.r.t. v: -> contiguous [B, rows, 3] (rows no ring touches: 0).  rings: a measure.GirthRings."""
+    ptr_, a, b, f = rings.tables()
+    pt_ring, vt_ptr, vt_pt, vt_w, n_vt = rings.transposed()
+    B, rows, P = v.shape[0], v.shape[1], ptr_.numel() - 1
+    out = torch.empty((B, rows, 3), dtype=torch.float32, device=v.device)
+    check(_lib.load().sh_measure_girth_bwd(ptr(v), v.stride(0) if B > 1 else rows * 3, ptr(ptr_), ptr(a), ptr(b), ptr(f), ptr(pt_ring),
+                                           ptr(vt_ptr), ptr(vt_pt), ptr(vt_w), n_vt, ptr(g_girth), B, P, rows, ptr(out), stream_ptr()),
+          "sh_measure_girth_bwd")
+    return out
+
+
+def bone_length_bwd(kps, bones, g_len):
+    """Gradient of bone_length w.r.t. kps: -> [B, K, 3].  bones: a measure.Bones."""
+    jt_ptr, jt_bone, jt_w, n_jt = bones.transposed()
+    B, K, P = kps.shape[0], kps.shape[1], bones.n_bones
+    out = torch.empty((B, K, 3), dtype=torch.float32, device=kps.device)
+    check(_lib.load().sh_bone_length_bwd(ptr(kps), ptr(bones.table), ptr(jt_ptr), ptr(jt_bone), ptr(jt_w), n_jt, ptr(g_len), B, K, P,
+                                         ptr(out), stream_ptr()), "sh_bone_length_bwd")
+    return out
+
+
+def joint_regress_bwd(g_kps, J, rows):
+    """g_x = J^T g_kps for the first N rows, 0 for the rows behind them: g_kps contiguous [B, K, 3], J [K, N] -> [B, rows, 3]."""
+    K, N = J.shape
+    B = g_kps.shape[0]
+    out = torch.empty((B, rows, 3), dtype=torch.float32, device=g_kps.device)
+    check(_lib.load().sh_joint_regress_bwd(ptr(g_kps), ptr(J), B, N, K, rows, ptr(out), stream_ptr()), "sh_joint_regress_bwd")
+    return out
+
+
 NORM_FLAGS = {"zeromean": 1, "zeroroot": 2, "onelength": 4, "small": 8, "gass": 16, "normal": 32}
 
 

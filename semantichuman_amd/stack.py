@@ -61,6 +61,10 @@ OVERLAP_WGRAD = os.environ.get("SH_OVERLAP_WGRAD", "0") != "0"
 # run the small list pre-sum kernels of backward-data on a side stream, underneath the weight-gradient kernel of the
 # same layer (both only read dpre_i; the pre-sums are memory-bound and tiny, the weight gradient is MFMA-bound)
 OVERLAP_PRESUM = os.environ.get("SH_OVERLAP_PRESUM", "0") != "0"     # measured on MI355X: 2.03 vs 1.93 ms/step - off
+# A conv layer whose weight AND bias are both frozen (requires_grad False when the forward pass ran) gets no weight gradient: the
+# backward pass hands the sequencer a NULL dW for it (include/sh_kernels.h, sh_stack_backward).  SH_FULL_WGRAD=1 (or FULL_WGRAD =
+# True at run time): the old behaviour - every layer's weight gradient is computed and frozen ones are discarded (A/B switch).
+FULL_WGRAD = os.environ.get("SH_FULL_WGRAD", "0").strip() == "1"
 
 
 def _dev(a: np.ndarray, device):
@@ -419,8 +423,9 @@ class Stack:
         convert_p3_frags([(self, plan, weights, wf3, 0)], with_backward)
         return planes, wf3, 0
 
-    def native_forward(self, x, in_layout, out_layout, weights, biases, mma: str = "exact", with_backward: bool = False):
-        """-> (output, arena holding the outputs of the inner steps, three-plane state or None)."""
+    def native_forward(self, x, in_layout, out_layout, weights, biases, mma: str = "exact", with_backward: bool = False, frozen=None):
+        """-> (output, arena holding the outputs of the inner steps, three-plane state or None).
+        frozen: per parameter index, True = the backward pass will not compute that layer's weight gradient (None: none)."""
         B = x.shape[0] if in_layout == "bm" else x.shape[1]
         rows0 = x.shape[1] if in_layout == "bm" else x.shape[0]
         c0 = x.shape[2]
@@ -439,16 +444,20 @@ class Stack:
         outs[n - 1] = out.data_ptr()
         p3 = None
         keep = 1 if with_backward else 0
+        # a frozen layer's backward pass reads the fp32 rows of its input (no plane weight gradient): keep_fp32 == 1, and the image
+        # arena only when some layer still takes its weight gradient from it
+        any_frozen = bool(frozen) and any(frozen)
+        any_trained = not frozen or not all(frozen)
         planes_p = wf3_p = None
         if mma == "planes3" and B % 16 == 0 and plan["wf3_total"]:
             planes, wf3, wbase = self._p3_prepare(plan, weights, with_backward, x.device)
             # what the backward pass needs of this: the weight fragments - and, since round 6, the image arena of the forward
             # activations (6 bytes per element): the three-plane weight gradient (csrc/wgrad_p3.hip) reads a step's gathered input
             # through it.  SH_P3_WGRAD=0 (the exact weight-gradient kernels): not kept, as before.
-            p3 = (planes if (with_backward and _P3_WGRAD) else None, wf3, wbase)
+            p3 = (planes if (with_backward and _P3_WGRAD and any_trained) else None, wf3, wbase)
             # ... and with the images kept, the fp32 rows that neither pass reads are not written (sh_stack_forward keep_fp32 == 2;
             # SH_P3_DROP_FP32=0: every row, as before)
-            if p3[0] is not None:
+            if p3[0] is not None and not any_frozen:
                 keep = 2
             pl = (plan["pl_off"] + np.uint64(planes.data_ptr())) * plan["pl_mask"]
             wf = (plan["wf3_off"] + np.uint64(wf3.data_ptr() + wbase)) * plan["wf3_mask"]
@@ -459,8 +468,9 @@ class Stack:
                    "sh_stack_forward")
         return out, arena, p3
 
-    def native_backward(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, mma: str = "exact", p3=None):
-        """-> (grad_x or None, {param: (dW, db)})"""
+    def native_backward(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, mma: str = "exact", p3=None,
+                        frozen=None):
+        """-> (grad_x or None, {param: (dW, db)}); frozen: as for native_forward (the same list), those parameters get (None, None)."""
         B = x.shape[0] if in_layout == "bm" else x.shape[1]
         rows0 = x.shape[1] if in_layout == "bm" else x.shape[0]
         c0 = x.shape[2]
@@ -479,8 +489,10 @@ class Stack:
         gin[0] = gx.data_ptr() if need_x_grad else 0
         wt = (plan["wt_off"] + wbase) * plan["wt_mask"]
         ws = (plan["ws_off"] + wbase) * plan["ws_mask"]
-        dW = plan["dW_off"] + fbase
         assert len(need_bias) == plan["npar"] == len(weights)
+        frozen = list(frozen) if frozen else [False] * plan["npar"]
+        assert not any(f and nb for f, nb in zip(frozen, need_bias))
+        dW = (plan["dW_off"] + fbase) * np.array([0 if f else 1 for f in frozen], dtype=np.uint64)
         db = (plan["db_off"] + fbase) * np.array([1 if nb else 0 for nb in need_bias], dtype=np.uint64)
         gpl_p = wf3t_p = inpl_p = None
         dpl = ctypes.c_void_p(0)
@@ -500,10 +512,11 @@ class Stack:
             n, self._native_steps(), _lib.ptr(x), _LAYOUT_ID[in_layout], rows0, c0, B, acts.ctypes.data, _lib.ptr(g),
             _LAYOUT_ID[out_layout], self._ptr_array(weights), gin.ctypes.data, ctypes.c_void_p(int(wbase) + 4 * plan["dpre_last_off"]),
             wt.ctypes.data, ws.ctypes.data, plan["ws_bytes"].ctypes.data, dW.ctypes.data, db.ctypes.data, 1 if need_x_grad else 0,
-            _lib.mma_id(mma), gpl_p, dpl, wf3t_p, inpl_p, 2 if inpl_p is not None else 1, _lib.stream_ptr()), "sh_stack_backward")
+            _lib.mma_id(mma), gpl_p, dpl, wf3t_p, inpl_p, 2 if (inpl_p is not None and not any(frozen)) else 1, _lib.stream_ptr()),
+            "sh_stack_backward")
         grads = {}
         for j, shp in enumerate(plan["shapes"]):
-            if shp is None:
+            if shp is None or frozen[j]:
                 continue
             o = int(plan["dW_off_f"][j])
             dWj = flat[o:o + shp[0] * shp[1]].view(shp)
@@ -613,7 +626,7 @@ class Stack:
             _LAYOUT_ID[out_layout], _lib.stream_ptr()), "sh_stack_forward_bf16")
         return out, arena
 
-    def native_backward_bf16(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, wf=None):
+    def native_backward_bf16(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, wf=None, frozen=None):
         B, rows0, c0 = self._io_dims(x, in_layout)
         plan = self._plan_bf16(B, c0, x.dtype == torch.float32, out.dtype == torch.float32)
         n = len(self.steps)
@@ -629,8 +642,10 @@ class Stack:
         ready = wf is not None and wf.bwd is not None
         wt = wf.bwd[id(self)] if ready else (plan["wt_off"] + wbase) * plan["wt_mask"]
         ws = (plan["ws_off"] + wbase) * plan["ws_mask"]
-        dW = plan["dW_off"] + fbase
         assert len(need_bias) == plan["npar"] == len(weights)
+        frozen = list(frozen) if frozen else [False] * plan["npar"]
+        assert not any(f and nb for f, nb in zip(frozen, need_bias))
+        dW = (plan["dW_off"] + fbase) * np.array([0 if f else 1 for f in frozen], dtype=np.uint64)
         db = (plan["db_off"] + fbase) * np.array([1 if nb else 0 for nb in need_bias], dtype=np.uint64)
         _lib.check(_lib.load().sh_stack_backward_bf16(
             n, self._native_steps(), _lib.ptr(x), ops.dtype_id(x), _LAYOUT_ID[in_layout], rows0, c0, B, acts.ctypes.data, _lib.ptr(g),
@@ -639,7 +654,7 @@ class Stack:
             db.ctypes.data, 1 if need_x_grad else 0, _lib.stream_ptr()), "sh_stack_backward_bf16")
         grads = {}
         for j, shp in enumerate(plan["shapes"]):
-            if shp is None:
+            if shp is None or frozen[j]:
                 continue
             o = int(plan["dW_off_f"][j])
             dWj = flat[o:o + shp[0] * shp[1]].view(shp)
@@ -679,9 +694,10 @@ class Stack:
         return cur, acts
 
     # ------------------------------------------------------------------ backward
-    def run_backward(self, x, in_layout, out_layout, acts, g, weights, need_x_grad: bool, need_bias):
-        """g: gradient w.r.t. the stack output (layout out_layout).
-        -> (grad_x or None, {param: (dW, db)})"""
+    def run_backward(self, x, in_layout, out_layout, acts, g, weights, need_x_grad: bool, need_bias, frozen=None):
+        """g: gradient w.r.t. the stack output (layout out_layout); frozen: per parameter index, no weight gradient (as
+        native_backward).  -> (grad_x or None, {param: (dW, db)})"""
+        frozen = list(frozen) if frozen else [False] * len(weights)
         steps = self.steps
         last = len(steps) - 1
         B = x.shape[0] if in_layout == "bm" else x.shape[1]
@@ -753,7 +769,8 @@ class Stack:
                         presum()                               # writes rows >= R; the weight gradient reads rows < R
                 # a 16 -> 3 channel layer takes the role-swapped weight gradient (wgrad_thin.hip), which reads the
                 # pre-summed rows: same order as sh_stack_backward
-                thin = (want_in and side is None and not presum_side and cur_layout == "vm" and inp_layout == "vm"
+                fz = frozen[st.param]
+                thin = (not fz and want_in and side is None and not presum_side and cur_layout == "vm" and inp_layout == "vm"
                         and st.R == st.n_in and ops.wgrad_thin_ok(B, st.n_in, st.S, st.cin, st.cout, cur.dtype))
                 thin_dx = thin and g_layout == "vm" and (ep["yprev"] is None or ep["yprev"] is inp)
                 if thin:
@@ -762,15 +779,16 @@ class Stack:
                         cur, inp, st.dev["table_t"], st.R, st.S, st.cin, st.cout, want_bias=need_bias[st.param],
                         weight=weights[st.param], dx=g_in if thin_dx else None,
                         act_prev=ep["act_prev"] if ep["yprev"] is not None else 0, zero_prev=ep["zero_row"])
-                else:
+                elif not fz:
                     if side is not None:
                         side.wait_stream(main)                 # dpre_i (and input_i) are complete on main
                         keep_alive.append(cur)
                     with torch.cuda.stream(side if side is not None else main):
                         job = ops.spiral_conv_bwd_wgt_deferred(cur, cur_layout, inp, inp_layout, st.dev["table"], st.R, st.S,
                                                                st.cin, st.cout, want_bias=need_bias[st.param])
-                jobs.append(job)
-                grads[st.param] = (job["dW"], job["db"])
+                if not fz:
+                    jobs.append(job)
+                    grads[st.param] = (job["dW"], job["db"])
                 if want_in:
                     if presum_side:
                         main.wait_stream(ps)
@@ -844,6 +862,14 @@ def prepare_p3_frags(stacks_convs_c0, B: int, with_backward: bool):
         st._p3_next = (buf, off, id(pl), with_backward)
 
 
+def _frozen_mask(needs_input_grad, first: int, n: int):
+    """Per conv parameter: True when neither its weight (input first + 2j) nor its bias (first + 2j + 1) wants a gradient.
+    All False under FULL_WGRAD."""
+    if FULL_WGRAD:
+        return [False] * n
+    return [not (needs_input_grad[first + 2 * j] or needs_input_grad[first + 2 * j + 1]) for j in range(n)]
+
+
 class StackFunction(torch.autograd.Function):
     """autograd node for a whole Stack.  params = (w_0, b_0, w_1, b_1, ...) for the SpiralConv
     modules in ModuleList order (b_j may be None)."""
@@ -859,8 +885,11 @@ class StackFunction(torch.autograd.Function):
         # the arithmetic form of the node: what the caller's default says NOW; the backward pass (autograd's thread, later)
         # runs in the same form whatever the default is by then
         ctx.mma = _lib.get_f32_mma_mode()
+        # layers whose weight and bias are both frozen: no weight gradient (params start at input 4: w_j = 4 + 2j, b_j = 5 + 2j)
+        ctx.frozen = _frozen_mask(ctx.needs_input_grad, 4, len(weights))
         if ctx.native:
-            out, arena, ctx.p3 = stack.native_forward(x, in_layout, out_layout, weights, biases, ctx.mma, with_backward=need or ctx.needs_input_grad[3])
+            out, arena, ctx.p3 = stack.native_forward(x, in_layout, out_layout, weights, biases, ctx.mma, with_backward=need or ctx.needs_input_grad[3],
+                                                      frozen=ctx.frozen)
             ctx.save_for_backward(x, out, arena, *weights)
             return out
         out, acts = stack.run_forward(x, in_layout, out_layout, weights, biases, keep=need)
@@ -878,7 +907,7 @@ class StackFunction(torch.autograd.Function):
         if ctx.native:
             x, out, arena, *weights = ctx.saved_tensors
             gx, grads = stack.native_backward(x, in_layout, out_layout, arena, out, g, weights, ctx.needs_input_grad[3], need_bias,
-                                              ctx.mma, ctx.p3)
+                                              ctx.mma, ctx.p3, ctx.frozen)
             ctx.p3 = None
         else:
             x, out, *weights = ctx.saved_tensors
@@ -886,7 +915,7 @@ class StackFunction(torch.autograd.Function):
             _lib.set_f32_mma_mode(ctx.mma)
             try:
                 gx, grads = stack.run_backward(x, in_layout, out_layout, ctx.acts + [out], g, weights,
-                                               ctx.needs_input_grad[3], need_bias)
+                                               ctx.needs_input_grad[3], need_bias, ctx.frozen)
             finally:
                 _lib.set_f32_mma_mode(was)
             ctx.acts = None
@@ -951,6 +980,7 @@ class StackFunctionBF16(torch.autograd.Function):
         x = x.contiguous()
         ctx.stack, ctx.layouts, ctx.wf = stack, (in_layout, out_layout), wf
         ctx.has_bias = [b is not None for b in biases]
+        ctx.frozen = _frozen_mask(ctx.needs_input_grad, 6, len(weights))
         out, arena = stack.native_forward_bf16(x, in_layout, out_layout, out_dtype, weights, biases, wf)
         ctx.save_for_backward(x, out, arena, *weights)
         return out
@@ -963,7 +993,7 @@ class StackFunctionBF16(torch.autograd.Function):
         # forward args: (stack, in_layout, out_layout, out_dtype, wf, x, w_0, b_0, ...)
         need_bias = [hb and ctx.needs_input_grad[7 + 2 * j] for j, hb in enumerate(ctx.has_bias)]
         gx, grads = ctx.stack.native_backward_bf16(x, in_layout, out_layout, arena, out, g, weights, ctx.needs_input_grad[5], need_bias,
-                                                   ctx.wf)
+                                                   ctx.wf, ctx.frozen)
         res = [None, None, None, None, None, gx]
         for j in range(len(weights)):
             dW, db = grads.get(j, (None, None))
