@@ -253,20 +253,42 @@ typedef struct sh_stack_step {
     const int32_t* bg_rows; const uint32_t* bg_pos; const int32_t* bg_out; int bg_n, bg_L;
 } sh_stack_step;
 
+/* The kernel forms of an fp32 stack (sh_stack_forward / sh_stack_backward), decided in one place for both passes: from the steps, c0,
+ * B, x_layout, mma_mode, keep_fp32 (the forward pass's; the backward pass's acts_fp32), need_x_grad and the switches SH_P3_N16_MAXB,
+ * SH_P3_BWD, SH_P3_WGRAD, SH_P3_YPREV_IMG, SH_P3_DROP_FP32, SH_P3_RAGGED, SH_P3_GROUPED, SH_P3_PRESUM_IMG, SH_TR_RIDE.
+ * sh_stack_plan_f32 writes per step an OR of SH_FORM_* flags (backward flags as a layer with a weight gradient runs them).  Both
+ * sequencers compute this plan and require the per-step buffers it names (SH_ERR_INVALID_ARG when one is NULL); a caller sizes its
+ * buffers from it. */
+enum sh_stack_form {
+    SH_FORM_FWD_P3 = 1,                /* conv: forward on the plane image of its input (planes[i - 1], wfrag3[i]) */
+    SH_FORM_FWD_GRP = 2,               /* ... over grouped lists */
+    SH_FORM_FWD_IMG = 4,               /* the step writes the plane image of its output (planes[i]) */
+    SH_FORM_FWD_IMG_ONLY = 8,          /* ... and leaves its fp32 rows unwritten */
+    SH_FORM_BWD_GIMG = 16,             /* the pre-activation gradient gets an image (gin_planes[i + 1] / dpre_last_planes, wfrag3_t[i]) */
+    SH_FORM_BWD_THIN = 32,             /* role-swapped weight gradient, which computes the input gradient too */
+    SH_FORM_BWD_P3 = 64,               /* backward-data on planes */
+    SH_FORM_BWD_RAG = 128,             /* ... over ragged source lists */
+    SH_FORM_BWD_GRP = 256,             /* ... over grouped lists */
+    SH_FORM_BWD_RIDE = 512,            /* the last pre-sum level rides in the weight-gradient launch */
+    SH_FORM_BWD_PRESUM_IMG = 1024,     /* the pre-summed gradient rows get an image */
+    SH_FORM_BWD_P3W = 2048,            /* weight gradient from the two images (in_planes[i]) */
+    SH_FORM_BWD_YIMG = 4096,           /* plane backward-data takes the activation derivative from the input's image (in_planes[i]) */
+    SH_FORM_BWD_IN_IMG_ONLY = 8192,    /* keep_fp32 == 2: the step's input may be its image alone */
+    SH_FORM_BWD_GRAD_IMG_ONLY = 16384  /* keep_fp32 == 2: its pre-activation gradient is handed over as the image alone */
+};
+SH_API int sh_stack_plan_f32(int n_steps, const sh_stack_step* steps, int c0, int B, int x_layout, int mma_mode, int keep_fp32,
+                             int need_x_grad, int* forms);
+
 /* outs[i]: output of step i, vertex-major, except outs[n_steps-1] which has layout out_layout.
  * x: [rows0] rows of c0 channels in layout x_layout. */
-/* Three-plane form (mma_mode == SH_MMA_PLANES3; ignored otherwise, may be NULL): planes[i] = buffer for the plane image of
- * outs[i] (sh_p3_bytes of the buffer's rows - a step that appends shares its predecessor's buffer AND image - or NULL: the
- * step that gathers it keeps the SPLIT3 kernels); wfrag3[i] = three-plane weight fragments of conv step i, forward operand
- * (sh_conv_wfrag3_prep_multi, transpose 0), already converted from the CURRENT weights.  A conv step whose input has an
- * image and whose shape sh_spiral_conv_p3_ok() takes runs sh_spiral_conv_fwd_p3; images are written by their producers.
+/* Three-plane form (mma_mode == SH_MMA_PLANES3 and both arrays given; NULL arrays: no plane form): planes[i] = buffer for the plane
+ * image of outs[i] (sh_p3_bytes of the buffer's rows - a step that appends shares its predecessor's buffer AND image), required where
+ * the plan says SH_FORM_FWD_IMG; wfrag3[i] = three-plane weight fragments of conv step i, forward operand
+ * (sh_conv_wfrag3_prep_multi, transpose 0), already converted from the CURRENT weights, required where it says SH_FORM_FWD_P3.
  * keep_fp32: 1 = every step writes its fp32 output (a backward pass reads them); 0 = forward only: rows that the next plane
- * conv gathers through their image alone are written as the image alone (outs[i] of such a step is then partly or wholly
- * unwritten; the last step's output is always fp32); 2 (round 6) = training on the images: the same rows, where the BACKWARD
- * pass of the conv that gathers them leaves their fp32 form unread as well - its weight gradient runs on the two images
- * (sh_spiral_conv_bwd_wgt_p3) and the activation derivative is evaluated from the image.  What is known of that from the steps
- * alone decides (shapes, tables, the switches SH_P3_BWD / SH_P3_WGRAD / SH_P3_YPREV_IMG / SH_P3_DROP_FP32); the caller of 2 owes
- * sh_stack_backward the plane buffers (gin_planes, wfrag3_t, in_planes, plane-sized workspaces) and acts_fp32 == 2. */
+ * conv gathers through their image alone are written as the image alone (SH_FORM_FWD_IMG_ONLY; the last step's output is always
+ * fp32); 2 (round 6) = training on the images: the same rows, where the BACKWARD pass of the conv that gathers them leaves their fp32
+ * form unread as well (SH_FORM_BWD_IN_IMG_ONLY); the caller of 2 owes sh_stack_backward the plane buffers and acts_fp32 == 2. */
 SH_API int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float* x, int x_layout, int rows0, int c0, int B,
                             const float* const* weights, const float* const* biases, float* const* outs, int out_layout,
                             int mma_mode, void* const* planes, const void* const* wfrag3, int keep_fp32, sh_stream_t stream);
@@ -278,18 +300,17 @@ SH_API int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float
  * output of the last step when that is a conv ([R + n1 + n2][B][cout]), else unused.  Per conv step i:
  * weight_t[i] ([cin][S*cout], needed when i > 0 or need_x_grad), workspace[i] / workspace_bytes[i]
  * (>= sh_spiral_conv_bwd_wgt_workspace); per parameter index: dW[p], dbias[p] (may be NULL).
- * Three-plane form (SH_MMA_PLANES3; otherwise ignored, may be NULL): gin_planes[i] / dpre_last_planes = buffers for the plane
- * images of gin[i] / dpre_last (all rows, the pre-summed ones included; NULL = that conv step's backward-data pass keeps the
- * SPLIT3 kernels), wfrag3_t[i] = fragments of conv step i's backward-data operand (transpose 1); weight_t[i] may be NULL for
- * a step that runs sh_spiral_conv_bwd_data_p3.  in_planes (round 6; may be NULL): in_planes[i] = the plane image of the INPUT
- * of conv step i - what sh_stack_forward wrote to planes[i - 1], kept alive by the caller - or NULL; with it, the image of its
- * gradient rows and a workspace of at least sh_spiral_conv_bwd_wgt_p3_workspace() bytes, a step whose shape
- * sh_spiral_conv_bwd_wgt_p3_ok() takes computes its WEIGHT gradient from the two images (sh_spiral_conv_bwd_wgt_p3_presum)
- * instead of from the fp32 tensors (sh_spiral_conv_bwd_wgt_presum).  acts_fp32: the keep_fp32 sh_stack_forward ran with (1 or
- * 2).  With 2 a step whose input was left as its image alone must run on the images: SH_ERR_INVALID_ARG when the buffers given
- * do not allow it (never a read of unwritten rows); and the gradient rows this pass itself hands from step to step are written
- * as their image alone where the step that takes them reads nothing else (ragged source lists or a table without
- * multiplicities, plane weight gradient).
+ * Three-plane form (SH_MMA_PLANES3 with gin_planes and wfrag3_t; NULL arrays: no plane form): where the plan says SH_FORM_BWD_GIMG,
+ * gin_planes[i + 1] / dpre_last_planes = buffer for the plane image of the step's pre-activation gradient (all rows, the pre-summed
+ * ones included) and wfrag3_t[i] = fragments of its backward-data operand (transpose 1); weight_t[i] may then be NULL unless the
+ * step is SH_FORM_BWD_THIN.  in_planes (round 6; NULL: the forward images were not kept): in_planes[i] = the plane image of the
+ * INPUT of conv step i - what sh_stack_forward wrote to planes[i - 1], kept alive by the caller - required where the plan says
+ * SH_FORM_BWD_P3W or SH_FORM_BWD_YIMG; the plan names only images the forward pass wrote.  SH_FORM_BWD_P3W computes the step's
+ * WEIGHT gradient from the two images (sh_spiral_conv_bwd_wgt_p3_presum) when its workspace has at least
+ * sh_spiral_conv_bwd_wgt_p3_workspace() bytes, else from the fp32 tensors (sh_spiral_conv_bwd_wgt_presum).  acts_fp32: the
+ * keep_fp32 sh_stack_forward ran with (1 or 2).  With 2 (plane form and in_planes required) a step whose input was left as its
+ * image alone must run on the images: SH_ERR_INVALID_ARG when it cannot (never a read of unwritten rows); and the gradient rows
+ * this pass hands from step to step are written as their image alone where the plan says SH_FORM_BWD_GRAD_IMG_ONLY.
  * dW[p] == NULL (the dW array itself is required) means: do not compute the weight gradient of the conv step(s) of parameter p
  * (a frozen layer; dbias[p] must then be NULL too).  Such a step launches no weight-gradient kernel and has no job in the slab
  * reduction; what used to ride in that launch runs on its own: the last pre-sum level as the standalone sh_spmm_p3 launch, the

@@ -37,6 +37,7 @@ SIGNATURES = {
     "sh_act_backward": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
     "sh_act_backward_tr": (c_int, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sh_spmm": (c_int, [_P, _P, _P, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _P]),
+    "sh_stack_plan_f32": (c_int, [_I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sh_stack_forward": (c_int, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P]),
     "sh_stack_backward": (c_int, [_I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
     "sh_linear_workspace": (c_size_t, [_I, _I, _I]),
@@ -128,6 +129,10 @@ SIGNATURES = {
     "sh_spiral_conv_bwd_wgt_reduce_multi_kinds": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 DTYPE_IDS = {"float32": 0, "bfloat16": 1}
+# sh_stack_plan_f32: the per-step flags (enum sh_stack_form)
+FORM = {name: 1 << k for k, name in enumerate(["fwd_p3", "fwd_grp", "fwd_img", "fwd_img_only", "bwd_gimg", "bwd_thin", "bwd_p3", "bwd_rag",
+                                                "bwd_grp", "bwd_ride", "bwd_presum_img", "bwd_p3w", "bwd_yimg", "bwd_in_img_only",
+                                                "bwd_grad_img_only"])}
 
 
 

@@ -971,10 +971,13 @@ inline bool p3s_shape_ok(int S, int Cg, int Nout) {
     const ShFragGeom g = sh_frag_geom(S, Cg, Nout);
     return (pad_on || g.nks % P3S_KC == 0) && (Nout == 32 || g.nt_tot % P3S_NT == 0);
 }
+// (dispatch_p3_nt builds 1, 2, 4 and 8 channel tiles per workgroup, and only 1 and 2 for 16 gathered channels; the list kernels
+// check their own, fewer, tile counts)
 inline bool p3_resident_ok(int S, int Cg, int Nout) {
     const P3Geom g = p3_geom(S, Cg, Nout);
     static const int max_split = sh_env_int("SH_P3_MAX_SPLIT", 1, 1, 8);      // output-channel slices re-gather the input
-    return (long)g.nks * g.nt * 3 <= 150 && g.nsplit <= max_split;
+    const bool built = Cg == 16 ? g.nt <= 2 : (g.nt == 1 || g.nt == 2 || g.nt == 4 || g.nt == 8);
+    return (long)g.nks * g.nt * 3 <= 150 && g.nsplit <= max_split && built;
 }
 // k-steps of a layer's three-plane fragment buffer: sh_frag_geom's, rounded up to whole chunks where the weight is streamed
 inline int p3_nks(int S, int Cg, int Nout) {

@@ -55,65 +55,133 @@ int check_steps(int n, const sh_stack_step* st, int c0, const char* what) {
 
 namespace {
 
-// ---- three-plane form (SH_MMA_PLANES3): which steps run the ..._p3 kernels.  A conv step's forward takes the plane image of
-// its input when the caller supplied the buffers (planes of the producing step's output buffer, three-plane weight fragments)
-// and the kernels take the shape; its backward-data pass likewise with the image of its pre-activation gradient.
-struct P3Ctx {
-    int n, B, mode;
-    const sh_stack_step* st;
-    void* const* planes;              // forward: per step, image buffer of outs[i] (NULL: none)
-    const void* const* wfrag3;        // per conv step: forward operand (sh_stack_forward) / backward-data operand (sh_stack_backward)
+// ---- The kernel forms of an fp32 stack (sh_stack_plan_f32).  plan_f32 decides, for every step and both passes, which kernels run:
+// from the steps, the batch, the input layout, whether the three-plane form (SH_MMA_PLANES3) is on, keep_fp32 and the switches
+// below.  sh_stack_forward and sh_stack_backward compute the same plan and only carry it out, so the backward pass reads a forward
+// image exactly where the forward pass wrote one and leaves unread exactly the fp32 rows the forward pass left unwritten.  Buffers
+// follow the plan (a per-step pointer the plan needs and the caller left NULL is an error); two things stay outside it: a frozen
+// layer (dW[p] == NULL drops what lives in the weight-gradient launch) and the size of the caller's workspace.
+// the switches, read once: SH_P3_N16_MAXB (the rule in plan_f32); SH_P3_BWD, SH_P3_WGRAD, SH_P3_YPREV_IMG, SH_P3_DROP_FP32, SH_P3_RAGGED,
+// SH_P3_GROUPED = 0: that plane form off (with SH_P3_WGRAD=0 the backward pass reads no forward image); SH_P3_PRESUM_IMG: 0 / 1 force,
+// 2 = the rule in plan_f32; SH_TR_RIDE=0: the weight transposes get a launch of their own
+struct Switches { int n16_maxb, bwd, wgrad, yprev_img, drop_fp32, ragged, grouped, presum_img, tr_ride; };
+const Switches& switches() {
+    static const Switches s{sh_env_int("SH_P3_N16_MAXB", 256, 0, 1 << 30), sh_env_int("SH_P3_BWD", 1, 0, 1), sh_env_int("SH_P3_WGRAD", 1, 0, 1),
+                            sh_env_int("SH_P3_YPREV_IMG", 1, 0, 1),        sh_env_int("SH_P3_DROP_FP32", 1, 0, 1),
+                            sh_env_int("SH_P3_RAGGED", 1, 0, 1),           sh_env_int("SH_P3_GROUPED", 1, 0, 1),
+                            sh_env_int("SH_P3_PRESUM_IMG", 2, 0, 2),       sh_env_int("SH_TR_RIDE", 1, 0, 1)};
+    return s;
+}
+
+enum { BD_F32 = 0, BD_TABLE, BD_RAG, BD_GRP };      // backward-data: fp32 kernels; plane kernel over table_t / ragged / grouped lists
+struct Forms {
+    // forward
+    bool f_p3;              // conv: the plane kernel, on the image of its input (sh_spiral_conv_fwd_p3)
+    bool f_grp;             // ... over grouped lists (sh_spiral_conv_p3_grp)
+    bool f_img;             // the step writes the image of its output, because the conv that gathers it takes f_p3
+    bool f_img_only;        // ... and leaves the fp32 rows unwritten
+    // backward, for a trained layer
+    bool b_gimg;            // the step's pre-activation gradient gets an image (gin_planes[i + 1] / dpre_last_planes)
+    bool b_thin;            // role-swapped weight gradient, which computes the input gradient too (wgrad_thin.hip)
+    int b_data;             // backward-data form (BD_*) wherever b_thin does not run (a frozen layer)
+    bool b_ride;            // the last pre-sum level rides in the weight-gradient launch
+    bool b_presum_img;      // the pre-summed rows get an image (else the plane kernel splits them from the fp32 rows)
+    bool b_p3w;             // weight gradient from the two images (wgrad_p3.hip)
+    bool b_yimg;            // the plane backward-data kernel takes the activation derivative from the forward image
+    bool b_in_img_only;     // keep_fp32 == 2: the fp32 rows of the step's input may be unwritten - the step must run on images
+    bool b_grad_img_only;   // keep_fp32 == 2: its pre-activation gradient is handed over as the image alone
 };
-// does conv step j's FORWARD pass take the plane kernel for this batch?  The kernels' shape test, and one measured rule: a layer with
-// <= 16 output channels (one channel tile: 6 MFMAs per gathered 3-KiB fragment) loses to the exact staged kernel once the batch is
-// large - per 64 meshes, dec3 (6891 rows, K = 320 -> 16): plane 50.6 / 58.1 / 63.4 / 65.4 / 67.9 us at batch 64 / 128 / 256 / 512 / 1024,
-// exact 68.8 / 66.6 / 63.4 / 60.4 / 56.5 (profiles/r05_decode_batch_sweep.txt).  SH_P3_N16_MAXB: the largest batch at which such a layer
-// still runs the plane kernel.
-inline bool p3_step_shape_ok(int B, const sh_stack_step& s) {
-    static const int n16_maxb = sh_env_int("SH_P3_N16_MAXB", 256, 0, 1 << 30);
-    if (s.cout <= 16 && B > n16_maxb) return false;
-    return sh_spiral_conv_p3_ok(B, s.S, s.cin, s.cout) != 0;
-}
-inline bool p3_fwd(const P3Ctx& c, int i, bool in_vm) {
-    const sh_stack_step& s = c.st[i];
-    return c.mode == SH_MMA_PLANES3 && s.kind == 0 && i > 0 && in_vm && c.planes && c.planes[i - 1] && c.wfrag3 && c.wfrag3[i] &&
-           p3_step_shape_ok(c.B, s);
-}
-// Training on the plane images (round 6, keep_fp32 == 2): does the BACKWARD pass of conv step j leave the fp32 rows of the step's
-// gathered input (acts[j - 1]) unread?  Yes when its weight gradient runs on the images (wgrad_p3.hip) and the activation
-// derivative its backward-data pass applies is evaluated from the image.  This is the part of sh_stack_backward's decisions that is
-// known from the steps alone; sh_stack_forward drops fp32 rows by it and sh_stack_backward, told so (acts_fp32 == 2), refuses to
-// run such a step in any other form.
-inline bool bwd_plane_static(const sh_stack_step* st, int j, int B) {
-    static const int on = sh_env_int("SH_P3_BWD", 1, 0, 1) && sh_env_int("SH_P3_WGRAD", 1, 0, 1) && sh_env_int("SH_P3_YPREV_IMG", 1, 0, 1) &&
-                          sh_env_int("SH_P3_DROP_FP32", 1, 0, 1);
-    const sh_stack_step& s = st[j];
-    if (!on || j == 0 || s.kind != 0 || !s.table_t) return false;
-    if (!sh_spiral_conv_p3_ok(B, s.S, s.cout, s.cin)) return false;                  // its backward-data pass gathers the image of dpre
-    if (s.R == s.n_in && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32)) return false;
-    if (!sh_spiral_conv_bwd_wgt_p3_ok(B, s.R, s.S, s.cin, s.cout)) return false;
-    if (((long)s.R * (B / 16)) % 2 != 0 && s.zero_row < 0) return false;
-    return sh_p3_bytes(1, B, s.cin) != 0;
-}
-// ... and does it leave the fp32 rows of its pre-activation gradient (what the step behind it writes to gin[j + 1]) unread?  When,
-// besides, no pre-sum launch or rider reads them: ragged source lists, or a table without multiplicities.
-inline bool bwd_grad_plane_static(const sh_stack_step* st, int j, int B) {
-    static const int rag_on = sh_env_int("SH_P3_RAGGED", 1, 0, 1);
-    const sh_stack_step& s = st[j];
-    if (!bwd_plane_static(st, j, B)) return false;
-    const bool rag = rag_on && s.rag_rows && s.rag_pos && sh_spiral_conv_p3_rag_ok(B, s.S, s.cout, s.cin, s.rag_L);
-    return rag || (s.n1 == 0 && s.n2 == 0);
-}
+
 // the conv step that gathers the buffer step i writes (through a folded up-sampling that appends to it), or -1
-inline int consumer_conv(const P3Ctx& c, int i) {
+inline int consumer_conv(int n, const sh_stack_step* st, int i) {
     int j = i + 1;
-    if (j < c.n && c.st[j].kind == 1 && c.st[j].extend) ++j;
-    return (j < c.n && c.st[j].kind == 0) ? j : -1;
+    if (j < n && st[j].kind == 1 && st[j].extend) ++j;
+    return (j < n && st[j].kind == 0) ? j : -1;
+}
+
+void plan_f32(int n, const sh_stack_step* st, int B, int x_layout, bool planes3, int keep_fp32, bool need_x_grad, Forms* f) {
+    const Switches& sw = switches();
+    for (int i = 0; i < n; ++i) f[i] = Forms{};
+    for (int i = 1; i < n && planes3; ++i) {
+        const sh_stack_step& s = st[i];
+        if (s.kind != 0) continue;
+        // the kernels' shape test, and one measured rule: a layer with <= 16 output channels (one channel tile: 6 MFMAs per gathered 3-KiB
+        // fragment) loses to the exact staged kernel once the batch is large - per 64 meshes, dec3 (6891 rows, K = 320 -> 16): plane
+        // 50.6 / 58.1 / 63.4 / 65.4 / 67.9 us at batch 64 / 128 / 256 / 512 / 1024, exact 68.8 / 66.6 / 63.4 / 60.4 / 56.5
+        // (profiles/r05_decode_batch_sweep.txt)
+        f[i].f_p3 = !(s.cout <= 16 && B > sw.n16_maxb) && sh_spiral_conv_p3_ok(B, s.S, s.cin, s.cout);
+        // grouped lists (round 6): output rows with overlapping spirals share one list of the union - every row gathered once
+        f[i].f_grp = f[i].f_p3 && sw.grouped && s.fg_rows && s.fg_pos && s.fg_out && s.fg_n > 0 &&
+                     sh_spiral_conv_p3_grp_ok(B, s.S, s.cin, s.cout, s.fg_L) && sh_spiral_conv_p3_grp_pays(B, s.fg_n);
+    }
+    for (int i = 0; i + 1 < n; ++i) {
+        const int c = consumer_conv(n, st, i);
+        f[i].f_img = c >= 0 && f[c].f_p3;
+    }
+    for (int i = 0; i < n; ++i) {
+        const sh_stack_step& s = st[i];
+        Forms& q = f[i];
+        if (s.kind != 0 || !(i > 0 || need_x_grad) || !s.table_t) continue;
+        // backward-data on the image of the pre-activation gradient where the kernels take the transposed shape
+        q.b_gimg = planes3 && sw.bwd && sh_spiral_conv_p3_ok(B, s.S, s.cout, s.cin);
+        // a 16 -> 3 channel layer takes its weight gradient in role-swapped form (wgrad_thin.hip), on a plain vertex-major input
+        q.b_thin = s.R == s.n_in && (i > 0 || x_layout == 0) && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32);
+        if (q.b_gimg) {
+            // ragged source lists (round 6): every source an image row, no pre-summed rows - neither the launches that fill them nor the
+            // rider; as GROUPS of input rows sharing one list where the launch has groups enough (also the layers that gather 16
+            // channels, which the one-row list kernel does not take)
+            const bool grp = sw.ragged && sw.grouped && s.bg_rows && s.bg_pos && s.bg_out && s.bg_n > 0 &&
+                             sh_spiral_conv_p3_grp_ok(B, s.S, s.cout, s.cin, s.bg_L) && sh_spiral_conv_p3_grp_pays(B, s.bg_n);
+            const bool rag = sw.ragged && s.rag_rows && s.rag_pos && sh_spiral_conv_p3_rag_ok(B, s.S, s.cout, s.cin, s.rag_L);
+            q.b_data = grp ? BD_GRP : rag ? BD_RAG : BD_TABLE;
+            // pre-summed rows: imaged by their producers (the riders / pre-sum launches), or - LDS-resident plane kernel and at least
+            // half as many of them as real rows - left fp32 and split by the backward-data kernel itself (they are ~6 % of what it
+            // gathers; the riders' image stores cost their hosts more)
+            q.b_presum_img = sw.presum_img == 1 ||
+                             !(sh_spiral_conv_p3_kind(B, s.S, s.cout, s.cin) == 1 && (sw.presum_img == 0 || 2 * (s.n1 + s.n2) >= s.R));
+        }
+        const bool p3 = q.b_data != BD_F32 && !q.b_thin;
+        q.b_ride = !q.b_thin && q.b_data < BD_RAG && (s.n1 || s.n2);
+        // the weight gradient from the two images: the image of the step's input exists (the forward pass wrote it) and the kernel
+        // takes the shape
+        q.b_p3w = p3 && sw.wgrad && i > 0 && f[i - 1].f_img && sh_spiral_conv_bwd_wgt_p3_ok(B, s.R, s.S, s.cin, s.cout) &&
+                  (((long)s.R * (B / 16)) % 2 == 0 || s.zero_row >= 0);
+        q.b_yimg = q.b_data != BD_F32 && sw.wgrad && sw.yprev_img && i > 0 && st[i - 1].kind == 0 && f[i - 1].f_img;
+        q.b_in_img_only = keep_fp32 == 2 && sw.drop_fp32 && sw.yprev_img && q.b_p3w;
+        // ... and its gradient rows, when besides no pre-sum launch or rider reads them: list forms, or a table without multiplicities
+        q.b_grad_img_only = q.b_in_img_only && (q.b_data >= BD_RAG || (s.n1 == 0 && s.n2 == 0));
+    }
+    // forward only (keep_fp32 == 0), or training on the images where the backward pass of the consumer leaves them unread too
+    // (keep_fp32 == 2): rows that are gathered through their plane image alone are written as the image alone - a re-sampling step in
+    // front of a plane conv, a plane conv directly in front of another (through a folded up-sampling its fp32 rows feed the blend)
+    for (int i = 0; i + 1 < n; ++i) {
+        const int c = consumer_conv(n, st, i);
+        f[i].f_img_only = f[i].f_img && (keep_fp32 == 0 || f[c].b_in_img_only) && (st[i].kind == 1 || (f[i].f_p3 && c == i + 1));
+    }
 }
 
 }  // namespace
 
 extern "C" {
+
+int sh_stack_plan_f32(int n_steps, const sh_stack_step* steps, int c0, int B, int x_layout, int mma_mode, int keep_fp32, int need_x_grad,
+                      int* forms) {
+    int rc = check_steps(n_steps, steps, c0, "sh_stack_plan_f32");
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(forms && B > 0 && n_steps <= 64 && sh_mma_mode_valid(mma_mode) && keep_fp32 >= 0 && keep_fp32 <= 2, SH_ERR_INVALID_ARG,
+               "sh_stack_plan_f32: null pointer, empty batch, more than 64 steps, mma_mode %d or keep_fp32 %d", mma_mode, keep_fp32);
+    Forms f[64];
+    plan_f32(n_steps, steps, B, x_layout, mma_mode == SH_MMA_PLANES3, keep_fp32, need_x_grad != 0, f);
+    for (int i = 0; i < n_steps; ++i) {
+        const Forms& q = f[i];
+        const int bd = q.b_thin ? BD_F32 : q.b_data;
+        const bool on[15] = {q.f_p3, q.f_grp, q.f_img, q.f_img_only, q.b_gimg, q.b_thin, bd != BD_F32, bd == BD_RAG, bd == BD_GRP, q.b_ride,
+                             bd != BD_F32 && q.b_presum_img, q.b_p3w, q.b_yimg, q.b_in_img_only, q.b_grad_img_only};      // enum sh_stack_form
+        forms[i] = 0;
+        for (int k = 0; k < 15; ++k) forms[i] |= on[k] ? 1 << k : 0;
+    }
+    return SH_OK;
+}
 
 int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float* x, int x_layout, int rows0, int c0, int B,
                      const float* const* weights, const float* const* biases, float* const* outs, int out_layout, int mma_mode,
@@ -122,54 +190,47 @@ int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float* x, in
     if (rc != SH_OK) return rc;
     if (B > 0 && (rc = check_tensor_sizes(n_steps, steps, rows0, c0, B, "sh_stack_forward")) != SH_OK) return rc;
     SH_REQUIRE(x && weights && outs && B > 0, SH_ERR_INVALID_ARG, "sh_stack_forward: null pointer or empty batch");
+    SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_forward: more than 64 steps");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_stack_forward: unknown mma_mode %d", mma_mode);
     SH_REQUIRE(keep_fp32 >= 0 && keep_fp32 <= 2, SH_ERR_INVALID_ARG, "sh_stack_forward: keep_fp32 = %d (0, 1 or 2)", keep_fp32);
-    const P3Ctx pc{n_steps, B, mma_mode, steps, planes, wfrag3};
+    Forms f[64];
+    plan_f32(n_steps, steps, B, x_layout, mma_mode == SH_MMA_PLANES3 && planes && wfrag3, keep_fp32, false, f);
+    for (int i = 0; i < n_steps; ++i) {
+        SH_REQUIRE(outs[i], SH_ERR_INVALID_ARG, "sh_stack_forward: no output buffer for step %d", i);
+        SH_REQUIRE(!f[i].f_img || planes[i], SH_ERR_INVALID_ARG, "sh_stack_forward: step %d writes the image of its output: planes[%d] is NULL", i, i);
+        SH_REQUIRE(!f[i].f_p3 || wfrag3[i], SH_ERR_INVALID_ARG, "sh_stack_forward: step %d runs on planes: wfrag3[%d] is NULL", i, i);
+    }
     const float* cur = x;
     Lay cl = lay(x_layout, rows0, B, c0);
     int c = c0;
     for (int i = 0; i < n_steps; ++i) {
         const sh_stack_step& s = steps[i];
+        const Forms& q = f[i];
         const int co = s.kind == 0 ? s.cout : c;
         const Lay ol = lay(i == n_steps - 1 ? out_layout : 0, out_rows(s), B, co);
-        SH_REQUIRE(outs[i], SH_ERR_INVALID_ARG, "sh_stack_forward: no output buffer for step %d", i);
-        // does a three-plane conv gather the buffer this step writes?  then its image is written with it
-        const int cons = i < n_steps - 1 ? consumer_conv(pc, i) : -1;
-        void* img = (cons >= 0 && planes && planes[i] && mma_mode == SH_MMA_PLANES3 && wfrag3 && wfrag3[cons] &&
-                     p3_step_shape_ok(B, steps[cons]) && sh_p3_bytes(1, B, co)) ? planes[i] : nullptr;
-        // forward only (keep_fp32 == 0: no backward pass will read this pass's activations): rows that are gathered through
-        // their plane image alone are written as the image alone - a re-sampling step in front of a plane conv, a plane conv
-        // directly in front of another (6 instead of 10 bytes per element; BASELINE config 5's decode)
-        // training on the images (keep_fp32 == 2): the same rows, when the backward pass of the consumer leaves them unread too
-        const bool img_only = (keep_fp32 == 0 || (keep_fp32 == 2 && cons >= 0 && bwd_plane_static(steps, cons, B))) && img && cons >= 0 &&
-                              p3_fwd(pc, cons, true);
+        void* img = q.f_img ? planes[i] : nullptr;
         if (s.kind == 0) {
-            if (p3_fwd(pc, i, cl.sb == c && cl.sv == (long)B * c)) {
-                const bool direct = img_only && cons == i + 1;      // (through a folded up-sampling the fp32 rows feed the blend)
-                // grouped lists (round 6): output rows with overlapping spirals share one list of the union - every row gathered once
-                static const int grp_on = sh_env_int("SH_P3_GROUPED", 1, 0, 1);
-                if (grp_on && s.fg_rows && s.fg_pos && s.fg_out && s.fg_n > 0 && sh_spiral_conv_p3_grp_ok(B, s.S, s.cin, s.cout, s.fg_L) &&
-                    sh_spiral_conv_p3_grp_pays(B, s.fg_n))
-                    rc = sh_spiral_conv_p3_grp(planes[i - 1], s.fg_rows, s.fg_pos, s.fg_out, s.fg_n, s.fg_L, wfrag3[i], biases ? biases[s.param] : nullptr,
-                                               direct ? nullptr : outs[i], ol.sv, ol.sb, img, nullptr, 0, 0, nullptr, s.act, s.zero_row, 0, B, s.R, s.S,
-                                               s.cin, s.cout, stream);
-                else
-                rc = sh_spiral_conv_fwd_p3(planes[i - 1], s.table, wfrag3[i], biases ? biases[s.param] : nullptr, direct ? nullptr : outs[i], ol.sv,
-                                           ol.sb, img, B, s.R, s.S, s.cin, s.cout, s.act, s.zero_row, stream);
-            } else {
-                rc = sh_spiral_conv_fwd_img(cur, cl.sv, cl.sb, s.table, weights[s.param], biases ? biases[s.param] : nullptr, outs[i],
-                                            ol.sv, ol.sb, img, B, s.R, s.S, s.cin, s.cout, s.act, s.zero_row, mma_mode, stream);
-            }
+            const float* bias = biases ? biases[s.param] : nullptr;
+            float* y = q.f_img_only ? nullptr : outs[i];
+            if (q.f_grp)
+                rc = sh_spiral_conv_p3_grp(planes[i - 1], s.fg_rows, s.fg_pos, s.fg_out, s.fg_n, s.fg_L, wfrag3[i], bias, y, ol.sv, ol.sb, img, nullptr,
+                                           0, 0, nullptr, s.act, s.zero_row, 0, B, s.R, s.S, s.cin, s.cout, stream);
+            else if (q.f_p3)
+                rc = sh_spiral_conv_fwd_p3(planes[i - 1], s.table, wfrag3[i], bias, y, ol.sv, ol.sb, img, B, s.R, s.S, s.cin, s.cout, s.act,
+                                           s.zero_row, stream);
+            else
+                rc = sh_spiral_conv_fwd_img(cur, cl.sv, cl.sb, s.table, weights[s.param], bias, outs[i], ol.sv, ol.sb, img, B, s.R, s.S, s.cin,
+                                            s.cout, s.act, s.zero_row, mma_mode, stream);
         } else if (s.extend) {
             SH_REQUIRE(i > 0 && !is_last_step(i, n_steps) && outs[i] == outs[i - 1] && cl.sb == c, SH_ERR_INVALID_ARG,
                        "sh_stack_forward: step %d appends to its input, which must be the vertex-major output buffer of step %d", i, i - 1);
-            SH_REQUIRE(!planes || planes[i] == planes[i - 1], SH_ERR_INVALID_ARG, "sh_stack_forward: step %d appends to its input: same image buffer", i);
-            float* dst = img_only ? nullptr : outs[i] + (long)s.m_cols * cl.sv;
+            SH_REQUIRE(!img || planes[i] == planes[i - 1], SH_ERR_INVALID_ARG, "sh_stack_forward: step %d appends to its input: same image buffer", i);
+            float* dst = q.f_img_only ? nullptr : outs[i] + (long)s.m_cols * cl.sv;
             rc = sh_spmm_p3(s.m.rowptr, s.m.col, s.m.val, cur, cl.sv, cl.sb, dst, cl.sv, cl.sb,
                             img ? static_cast<char*>(img) + sh_p3_bytes(s.m_cols, B, c) : nullptr, nullptr, 0, 0, 0, -1, B, s.m_rows, c, stream);
         } else {
-            rc = sh_spmm_p3(s.m.rowptr, s.m.col, s.m.val, cur, cl.sv, cl.sb, img_only ? nullptr : outs[i], ol.sv, ol.sb, img, nullptr, 0, 0, 0, -1, B,
-                            s.m_rows, c, stream);
+            rc = sh_spmm_p3(s.m.rowptr, s.m.col, s.m.val, cur, cl.sv, cl.sb, q.f_img_only ? nullptr : outs[i], ol.sv, ol.sb, img, nullptr, 0, 0, 0,
+                            -1, B, s.m_rows, c, stream);
         }
         if (rc != SH_OK) return rc;
         cur = outs[i]; cl = ol; c = co;
@@ -189,44 +250,38 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
     SH_REQUIRE(x && acts && g && weights && gin && dW && B > 0, SH_ERR_INVALID_ARG, "sh_stack_backward: null pointer or empty batch");
     SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_backward: more than 64 steps");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_stack_backward: unknown mma_mode %d", mma_mode);
-    SH_REQUIRE(acts_fp32 == 1 || (acts_fp32 == 2 && mma_mode == SH_MMA_PLANES3 && in_planes), SH_ERR_INVALID_ARG,
-               "sh_stack_backward: acts_fp32 = %d (1: every activation has its fp32 rows; 2, three-plane form with in_planes: the forward pass "
-               "ran with keep_fp32 == 2)", acts_fp32);
+    const bool planes3 = mma_mode == SH_MMA_PLANES3 && gin_planes && wfrag3_t;
+    SH_REQUIRE(acts_fp32 == 1 || (acts_fp32 == 2 && planes3 && in_planes), SH_ERR_INVALID_ARG,
+               "sh_stack_backward: acts_fp32 = %d (1: every activation has its fp32 rows; 2, three-plane form with gin_planes, wfrag3_t and "
+               "in_planes: the forward pass ran with keep_fp32 == 2)", acts_fp32);
     const int last = n_steps - 1;
+    Forms f[64];
+    plan_f32(n_steps, steps, B, x_layout, planes3, acts_fp32, need_x_grad != 0, f);
+    for (int i = 0; i < n_steps; ++i) {
+        SH_REQUIRE(!f[i].b_gimg || (wfrag3_t[i] && (i == last ? dpre_last_planes : gin_planes[i + 1])), SH_ERR_INVALID_ARG,
+                   "sh_stack_backward: step %d runs backward-data on planes: wfrag3_t[%d] and the image buffer of its gradient (%s) are required",
+                   i, i, i == last ? "dpre_last_planes" : "gin_planes[i + 1]");
+        SH_REQUIRE(!in_planes || !(f[i].b_p3w || f[i].b_yimg) || in_planes[i], SH_ERR_INVALID_ARG,
+                   "sh_stack_backward: step %d reads the image of its input: in_planes[%d] is NULL", i, i);
+    }
+    const Switches& sw = switches();
     int cin_of[64];                                            // channels entering step i
     {
         int c = c0;
         for (int i = 0; i < n_steps; ++i) { cin_of[i] = c; if (steps[i].kind == 0) c = steps[i].cout; }
     }
-    // three-plane form: conv step i's backward-data pass gathers the IMAGE of its pre-activation gradient when the caller gave
-    // a buffer for it (gin_planes[i + 1], or dpre_last_planes for the last step) and the fragments of the transposed weight
-    // SH_P3_BWD: 0 = the backward pass keeps the SPLIT3 kernels everywhere, 1 = three-plane backward-data wherever it can run
-    static const int p3_bwd_on = sh_env_int("SH_P3_BWD", 1, 0, 1);
-    auto bwd_p3 = [&](int i) -> void* {
-        const sh_stack_step& s = steps[i];
-        if (!p3_bwd_on) return nullptr;
-        if (mma_mode != SH_MMA_PLANES3 || s.kind != 0 || !(i > 0 || need_x_grad) || !s.table_t || !wfrag3_t || !wfrag3_t[i]) return nullptr;
-        if (!sh_spiral_conv_p3_ok(B, s.S, s.cout, s.cin)) return nullptr;
-        return i == last ? dpre_last_planes : (gin_planes ? gin_planes[i + 1] : nullptr);
-    };
-    // all weight transposes of the stack: workgroups of the launch that opens the pass (the last step's activation backward),
-    // or a launch of their own when the pass opens with a re-sampling step
+    // all weight transposes of the stack (backward-data on planes reads fragments instead): workgroups of the launch that opens the
+    // pass (the last step's activation backward), or a launch of their own when the pass opens with a re-sampling step
     const float* tr_w[32]; float* tr_wt[32]; int tr_S[32], tr_Ci[32], tr_Co[32];
     int n_tr = 0;
     for (int i = 0; i < n_steps; ++i) {
-        if (steps[i].kind != 0 || !(i > 0 || need_x_grad)) continue;
-        if (bwd_p3(i)) {                                       // reads fragments, not the transposed weight
-            const sh_stack_step& s = steps[i];
-            const bool thin = s.R == s.n_in && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32);
-            if (!thin) continue;
-        }
+        if (steps[i].kind != 0 || !(i > 0 || need_x_grad) || (f[i].b_gimg && !f[i].b_thin)) continue;
         SH_REQUIRE(weight_t && weight_t[i], SH_ERR_INVALID_ARG, "sh_stack_backward: no weight_t buffer for step %d", i);
         SH_REQUIRE(n_tr < 32, SH_ERR_UNSUPPORTED, "sh_stack_backward: more than 32 conv steps");
         tr_w[n_tr] = weights[steps[i].param]; tr_wt[n_tr] = weight_t[i]; tr_S[n_tr] = steps[i].S; tr_Ci[n_tr] = steps[i].cin; tr_Co[n_tr] = steps[i].cout;
         ++n_tr;
     }
-    static const int tr_ride = sh_env_int("SH_TR_RIDE", 1, 0, 1);
-    if (n_tr && !(tr_ride && steps[last].kind == 0)) {
+    if (n_tr && !(sw.tr_ride && steps[last].kind == 0)) {
         rc = sh_weight_transpose_multi(n_tr, tr_w, tr_wt, tr_S, tr_Ci, tr_Co, stream);
         if (rc != SH_OK) return rc;
         n_tr = 0;
@@ -240,9 +295,9 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
         if (s.kind == 0) {
             SH_REQUIRE(dpre_last, SH_ERR_INVALID_ARG, "sh_stack_backward: no dpre_last buffer");
             const Lay ol = lay(out_layout, s.R, B, s.cout), dl = lay(0, 0, B, s.cout);
-            cur_img = bwd_p3(last);
+            cur_img = f[last].b_gimg ? dpre_last_planes : nullptr;
             // the image of dpre rides in the launch when that is the plain element-wise form (16-byte quads, no tile turning)
-            const bool img_in = cur_img && s.cout % 4 == 0 && s.cout > 8 && ((ol.sv | ol.sb) % 4 == 0);
+            const bool img_in = cur_img && s.cout % 4 == 0 && s.cout > 8;
             rc = sh_act_backward_tr_img(g, ol.sv, ol.sb, acts[last], ol.sv, ol.sb, dpre_last, dl.sv, dl.sb, img_in ? cur_img : nullptr, B, s.R,
                                         s.cout, s.act, s.zero_row, n_tr, tr_w, tr_wt, tr_S, tr_Ci, tr_Co, stream);
             if (rc != SH_OK) return rc;
@@ -254,25 +309,24 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
     }
     const void* job_ws[64]; float* job_dW[64]; float* job_db[64]; int jB[64], jR[64], jS[64], jCi[64], jCo[64], jK[64];
     int njobs = 0;
-    // three-plane WEIGHT GRADIENT (csrc/wgrad_p3.hip, round 6): conv step i takes it when the caller kept the image of the step's
-    // input alive (in_planes[i] = what sh_stack_forward wrote to planes[i - 1]), the image of its pre-activation gradient exists
-    // (the step's backward-data pass gathers it) and the kernel takes the shape; SH_P3_WGRAD=0: the exact fp32 MFMA kernels everywhere
-    static const int p3_wgrad_on = sh_env_int("SH_P3_WGRAD", 1, 0, 1);
     for (int i = last; i >= 0; --i) {
         const sh_stack_step& s = steps[i];
+        const Forms& q = f[i];
         const bool want_in = i > 0 || need_x_grad;
         const float* inp = i == 0 ? x : acts[i - 1];
         const Lay il = i == 0 ? lay(x_layout, rows0, B, c0) : lay(0, 0, B, cin_of[i]);
         float* gi = want_in ? gin[i] : nullptr;
         SH_REQUIRE(!want_in || gi, SH_ERR_INVALID_ARG, "sh_stack_backward: no gradient buffer for the input of step %d", i);
-        const Lay gl = i == 0 ? lay(x_layout, rows0, B, c0) : lay(0, 0, B, cin_of[i]);
+        const Lay gl = il;
         // the activation derivative of the layer that produced this step's input is applied by whoever writes gin[i]
         const float* yprev = nullptr; Lay yl{0, 0}; int act_prev = 0, zero_prev = -1;
         if (i > 0 && steps[i - 1].kind == 0) {
             yprev = acts[i - 1]; yl = lay(0, 0, B, steps[i - 1].cout); act_prev = steps[i - 1].act; zero_prev = steps[i - 1].zero_row;
         }
-        // gin[i] is the pre-activation gradient of conv step i - 1: does that step's backward-data pass want its image?
-        void* gi_img = (want_in && i > 0 && steps[i - 1].kind == 0) ? bwd_p3(i - 1) : nullptr;
+        // gin[i] is the pre-activation gradient of conv step i - 1: its image when that step's backward-data pass gathers planes;
+        // written as the image alone when that step reads nothing else (acts_fp32 == 2)
+        void* gi_img = (i > 0 && steps[i - 1].kind == 0 && f[i - 1].b_gimg) ? gin_planes[i] : nullptr;
+        float* gi_f = (gi_img && f[i - 1].b_grad_img_only) ? nullptr : gi;
         bool gi_img_done = false;
         if (s.kind == 0) {
             SH_REQUIRE(workspace && workspace[i], SH_ERR_INVALID_ARG, "sh_stack_backward: no workspace for step %d", i);
@@ -281,47 +335,23 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
             const bool wgrad = dW[s.param] != nullptr;
             SH_REQUIRE(wgrad || !dbias || !dbias[s.param], SH_ERR_INVALID_ARG,
                        "sh_stack_backward: parameter %d has a dbias buffer but no dW buffer", s.param);
-            // a 16 -> 3 channel layer takes its weight gradient in role-swapped form (wgrad_thin.hip): it reads the extended
-            // gradient buffer through the transposed table, so it runs after the pre-sum launches below
-            const bool thin = wgrad && want_in && s.table_t && s.R == s.n_in && il.sb == s.cin && il.sv == (long)B * s.cin && cl.sb == s.cout &&
-                              cl.sv == (long)B * s.cout && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32);
-            const bool p3 = !thin && cur_img && cl.sb == s.cout && cl.sv == (long)B * s.cout;
-            // backward-data over ragged source lists (round 6): every source an image row, no pre-summed rows - neither the launches
-            // that fill them nor the rider in the weight gradient (SH_P3_RAGGED=0: the dense table with its pre-sums)
-            static const int rag_on = sh_env_int("SH_P3_RAGGED", 1, 0, 1);
-            static const int grp_on = sh_env_int("SH_P3_GROUPED", 1, 0, 1);
-            // ... as GROUPS of input rows sharing one list where the launch has groups enough (also the layers that gather 16 channels,
-            // which the one-row list kernel does not take)
-            const bool grp_b = p3 && rag_on && grp_on && want_in && s.bg_rows && s.bg_pos && s.bg_out && s.bg_n > 0 &&
-                               sh_spiral_conv_p3_grp_ok(B, s.S, s.cout, s.cin, s.bg_L) && sh_spiral_conv_p3_grp_pays(B, s.bg_n);
-            const bool rag = grp_b || (p3 && rag_on && want_in && s.rag_rows && s.rag_pos && sh_spiral_conv_p3_rag_ok(B, s.S, s.cout, s.cin, s.rag_L));
-            // the last pre-sum level of this layer rides in the weight-gradient launch (sh_spiral_conv_bwd_wgt_presum); an
-            // earlier level (very long lists: two levels) runs first, on its own
-            const bool ride = wgrad && !thin && !rag && want_in && s.table_t && (s.n1 || s.n2);
-            // SH_P3_PRESUM_IMG=1: the riders / pre-sum launches write the image of their rows; default 0: they stay plain and the
-            // backward-data kernel splits those rows itself from the fp32 buffer (they are ~6 % of what it gathers)
-            // pre-summed rows: imaged by their producers (the riders / pre-sum launches), or - LDS-resident plane kernel and at
-            // least half as many of them as real rows - left fp32 and split by the backward-data kernel itself (they are ~6 % of
-            // what it gathers; the riders' image stores cost their hosts more).  SH_P3_PRESUM_IMG: 0 / 1 force, 2 = that rule
-            static const int presum_mode = sh_env_int("SH_P3_PRESUM_IMG", 2, 0, 2);
-            const bool presum_img = !p3 ? false : presum_mode == 1 ? true
-                                    : !(sh_spiral_conv_p3_kind(B, s.S, s.cout, s.cin) == 1 && (presum_mode == 0 || 2 * (s.n1 + s.n2) >= s.R));
-            char* pimg0 = (p3 && presum_img) ? static_cast<char*>(cur_img) : nullptr;
+            // the role-swapped weight gradient reads the extended gradient buffer through the transposed table, so it runs after the
+            // pre-sum launches below
+            const bool thin = wgrad && q.b_thin;
+            const int bd = thin ? BD_F32 : q.b_data;
+            const bool p3 = bd != BD_F32, rag = bd >= BD_RAG;
+            const bool ride = wgrad && q.b_ride;
+            char* pimg0 = (p3 && q.b_presum_img) ? static_cast<char*>(cur_img) : nullptr;
             float* mut0 = const_cast<float*>(cur);
             if (ride && s.n1 && s.n2) {
                 rc = sh_spmm_p3(s.sum1.rowptr, s.sum1.col, s.sum1.val, cur, cl.sv, cl.sb, mut0 + (long)s.R * cl.sv, cl.sv, cl.sb,
                                 pimg0 ? pimg0 + sh_p3_bytes(s.R, B, s.cout) : nullptr, nullptr, 0, 0, 0, -1, B, s.n1, s.cout, stream);
                 if (rc != SH_OK) return rc;
             }
-            const bool p3w = wgrad && p3 && p3_wgrad_on && i > 0 && in_planes && in_planes[i] && il.sb == s.cin && il.sv == (long)B * s.cin &&
-                             sh_spiral_conv_bwd_wgt_p3_ok(B, s.R, s.S, s.cin, s.cout) && (((long)s.R * (B / 16)) % 2 == 0 || s.zero_row >= 0) &&
-                             workspace_bytes[i] >= sh_spiral_conv_bwd_wgt_p3_workspace(B, s.R, s.S, s.cin, s.cout);
-            // the forward pass left the fp32 rows of this step's input unwritten (keep_fp32 == 2) when this much was known from the
-            // steps alone: then the step must run on the images, whatever the buffers the caller gave this pass
-            const bool in_dropped = acts_fp32 == 2 && bwd_plane_static(steps, i, B);
-            SH_REQUIRE(!in_dropped || (p3w && (!yprev || (in_planes[i] && yl.sb == s.cin && yl.sv == (long)B * s.cin))), SH_ERR_INVALID_ARG,
+            const bool p3w = wgrad && q.b_p3w && in_planes && workspace_bytes[i] >= sh_spiral_conv_bwd_wgt_p3_workspace(B, s.R, s.S, s.cin, s.cout);
+            SH_REQUIRE(!q.b_in_img_only || p3w, SH_ERR_INVALID_ARG,
                        "sh_stack_backward: step %d: the forward pass kept only the image of its input (keep_fp32 == 2) but this pass cannot run "
-                       "the step on images (gin_planes / wfrag3_t / in_planes / workspace of sh_spiral_conv_bwd_wgt_p3_workspace bytes)", i);
+                       "the step on images (a frozen layer, or a workspace smaller than sh_spiral_conv_bwd_wgt_p3_workspace)", i);
             if (wgrad && !thin) {
                 const sh_csr_ref& lm = s.n2 ? s.sum2 : s.sum1;
                 const int ln = ride ? (s.n2 ? s.n2 : s.n1) : 0;
@@ -364,63 +394,46 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                                     s.cout, stream);
                     if (rc != SH_OK) return rc;
                 }
-                // ... and computes the input gradient from the same staged gradient rows when that buffer is plain vertex-major
-                // and the activation to differentiate (if any) produced the layer input itself
-                const bool thin_dx = thin && gl.sb == s.cin && gl.sv == (long)B * s.cin && (!yprev || yprev == inp);
                 if (thin) {
-                    const bool img_out = thin_dx && gi_img && sh_p3_bytes(1, B, s.cin);
+                    // ... and computes the input gradient from the same staged gradient rows
                     rc = sh_spiral_conv_bwd_wgt_thin(cur, cl.sv, cl.sb, inp, SH_DTYPE_F32, il.sv, il.sb, s.table_t, workspace[i],
-                                                     workspace_bytes[i], weights[s.param], thin_dx ? gi : nullptr, gl.sv, gl.sb,
-                                                     img_out ? gi_img : nullptr, yprev ? act_prev : SH_ACT_IDENTITY, zero_prev, B, s.R, s.n_in,
-                                                     s.S, s.cin, s.cout, SH_DTYPE_F32, stream);
-                    if (rc != SH_OK) return rc;
-                    gi_img_done = img_out;
-                }
-                if (!thin_dx) {
-                    if (p3) {
-                        // image of the gradient rows this pass gathers: the R real rows unless their producer wrote them, and
-                        // the pre-summed rows behind them
-                        const int r0 = 0, r1 = cur_img_done ? 0 : s.R;          // (the pre-sum launches wrote the image of their rows)
-                        if (r1 > r0) {
-                            rc = sh_to_p3(cur + (long)r0 * cl.sv, cl.sv, cl.sb, static_cast<char*>(cur_img) + sh_p3_bytes(r0, B, s.cout), B, r1 - r0,
-                                          s.cout, stream);
-                            if (rc != SH_OK) return rc;
-                        }
-                        const bool img_out = gi_img && gl.sb == s.cin && gl.sv == (long)B * s.cin && sh_p3_bytes(1, B, s.cin);
-                        // the step that takes this gradient reads it through the image alone (acts_fp32 == 2 holds it to that): image only
-                        float* gi_f = (acts_fp32 == 2 && img_out && i > 0 && bwd_grad_plane_static(steps, i - 1, B)) ? nullptr : gi;
-                        // the activation to differentiate, from its image when the caller kept the forward images (SH_P3_YPREV_IMG=0: fp32)
-                        static const int yimg_on = sh_env_int("SH_P3_YPREV_IMG", 1, 0, 1);
-                        const void* yimg = (yimg_on && yprev && in_planes && in_planes[i] && yl.sb == s.cin && yl.sv == (long)B * s.cin &&
-                                            sh_p3_bytes(1, B, s.cin)) ? in_planes[i] : nullptr;
-                        if (grp_b)
-                            rc = sh_spiral_conv_p3_grp(cur_img, s.bg_rows, s.bg_pos, s.bg_out, s.bg_n, s.bg_L, wfrag3_t[i], nullptr, gi_f, gl.sv, gl.sb,
-                                                       img_out ? gi_img : nullptr, yprev, yl.sv, yl.sb, yimg, act_prev, zero_prev, 1, B, s.n_in, s.S, s.cout,
-                                                       s.cin, stream);
-                        else if (rag)
-                            rc = sh_spiral_conv_bwd_data_p3_rag(cur_img, s.rag_rows, s.rag_pos, s.rag_L, wfrag3_t[i], gi_f, gl.sv, gl.sb, img_out ? gi_img : nullptr,
-                                                                yprev, yl.sv, yl.sb, yimg, act_prev, zero_prev, B, s.n_in, s.S, s.cin, s.cout, stream);
-                        else
-                        rc = sh_spiral_conv_bwd_data_p3(cur_img, s.zero_row, presum_img ? nullptr : cur, cl.sv, cl.sb, s.R, s.table_t, wfrag3_t[i], gi_f, gl.sv, gl.sb, img_out ? gi_img : nullptr, yprev, yl.sv,
-                                                        yl.sb, yimg, act_prev, zero_prev, B, s.n_in, s.S, s.cin, s.cout, stream);
-                        gi_img_done = img_out;
-                    } else {
-                        // the "no source" entries of table_t point at this step's own dummy row of dpre (stack.py ConvStep.finalize),
-                        // which its producer forced to zero
-                        rc = sh_spiral_conv_bwd_data_z(cur, cl.sv, cl.sb, s.zero_row, s.table_t, weight_t[i], gi, gl.sv, gl.sb, yprev, yl.sv,
-                                                       yl.sb, act_prev, zero_prev, B, s.n_in, s.S, s.cin, s.cout, mma_mode, stream);
+                                                     workspace_bytes[i], weights[s.param], gi, gl.sv, gl.sb, gi_img, yprev ? act_prev : SH_ACT_IDENTITY,
+                                                     zero_prev, B, s.R, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32, stream);
+                    gi_img_done = gi_img != nullptr;
+                } else if (p3) {
+                    // image of the gradient rows this pass gathers: the R real rows unless their producer wrote them (the pre-sum
+                    // launches wrote the image of their rows)
+                    if (!cur_img_done) {
+                        rc = sh_to_p3(cur, cl.sv, cl.sb, cur_img, B, s.R, s.cout, stream);
+                        if (rc != SH_OK) return rc;
                     }
-                    if (rc != SH_OK) return rc;
+                    // the activation to differentiate, from its image when the plan says so (SH_P3_YPREV_IMG=0: fp32)
+                    const void* yimg = (q.b_yimg && in_planes) ? in_planes[i] : nullptr;
+                    if (bd == BD_GRP)
+                        rc = sh_spiral_conv_p3_grp(cur_img, s.bg_rows, s.bg_pos, s.bg_out, s.bg_n, s.bg_L, wfrag3_t[i], nullptr, gi_f, gl.sv, gl.sb,
+                                                   gi_img, yprev, yl.sv, yl.sb, yimg, act_prev, zero_prev, 1, B, s.n_in, s.S, s.cout, s.cin, stream);
+                    else if (bd == BD_RAG)
+                        rc = sh_spiral_conv_bwd_data_p3_rag(cur_img, s.rag_rows, s.rag_pos, s.rag_L, wfrag3_t[i], gi_f, gl.sv, gl.sb, gi_img, yprev,
+                                                            yl.sv, yl.sb, yimg, act_prev, zero_prev, B, s.n_in, s.S, s.cin, s.cout, stream);
+                    else
+                        rc = sh_spiral_conv_bwd_data_p3(cur_img, s.zero_row, q.b_presum_img ? nullptr : cur, cl.sv, cl.sb, s.R, s.table_t, wfrag3_t[i],
+                                                        gi_f, gl.sv, gl.sb, gi_img, yprev, yl.sv, yl.sb, yimg, act_prev, zero_prev, B, s.n_in, s.S,
+                                                        s.cin, s.cout, stream);
+                    gi_img_done = gi_img != nullptr;
+                } else {
+                    // the "no source" entries of table_t point at this step's own dummy row of dpre (stack.py ConvStep.finalize),
+                    // which its producer forced to zero
+                    rc = sh_spiral_conv_bwd_data_z(cur, cl.sv, cl.sb, s.zero_row, s.table_t, weight_t[i], gi, gl.sv, gl.sb, yprev, yl.sv,
+                                                   yl.sb, act_prev, zero_prev, B, s.n_in, s.S, s.cin, s.cout, mma_mode, stream);
                 }
+                if (rc != SH_OK) return rc;
             }
         } else if (want_in) {
             SH_REQUIRE(s.mt.rowptr && s.mt.col && s.mt.val, SH_ERR_INVALID_ARG, "sh_stack_backward: step %d has no transposed matrix", i);
-            const bool img_out = gi_img && gl.sb == cin_of[i] && gl.sv == (long)B * cin_of[i] && sh_p3_bytes(1, B, cin_of[i]);
-            float* gi_f = (acts_fp32 == 2 && img_out && i > 0 && bwd_grad_plane_static(steps, i - 1, B)) ? nullptr : gi;
-            rc = sh_spmm_p3(s.mt.rowptr, s.mt.col, s.mt.val, cur, cl.sv, cl.sb, gi_f, gl.sv, gl.sb, img_out ? gi_img : nullptr, yprev, yl.sv, yl.sb,
+            rc = sh_spmm_p3(s.mt.rowptr, s.mt.col, s.mt.val, cur, cl.sv, cl.sb, gi_f, gl.sv, gl.sb, gi_img, yprev, yl.sv, yl.sb,
                             act_prev, zero_prev, B, s.m_cols, cin_of[i], stream);
             if (rc != SH_OK) return rc;
-            gi_img_done = img_out;
+            gi_img_done = gi_img != nullptr;
         }
         if (want_in) { cur = gi; cl = gl; cur_img = gi_img; cur_img_done = gi_img_done; }
     }
@@ -431,7 +444,6 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
     }
     return SH_OK;
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same two sequencers for the bf16 compute path (BASELINE config 3).  Tensors between steps are bf16 vertex-major;

@@ -39,9 +39,6 @@ from .mesh_ops import CSR, TransposedTable
 # one library call per stack and direction (csrc/stack_exec.hip); 0 = the call-by-call Python sequencing below
 NATIVE = os.environ.get("SH_STACK_NATIVE", "1") != "0"
 _LAYOUT_ID = {"vm": 0, "bm": 1}
-# the library's own switch (csrc/stack_exec.hip reads it once): with the exact weight-gradient kernels nothing reads the forward
-# images during the backward pass, so they are not kept
-_P3_WGRAD = os.environ.get("SH_P3_WGRAD", "1").strip() != "0"
 _P3_RAGGED = os.environ.get("SH_P3_RAGGED", "1").strip() != "0"
 # Test switch: fill the activation / gradient arenas with NaN when they are allocated.  A training pass on the images (keep_fp32 == 2)
 # leaves fp32 rows unwritten; a kernel that read one would otherwise see whatever the allocator's block held before - possibly the same
@@ -288,6 +285,13 @@ class Stack:
         self._nsteps = arr
         return arr
 
+    def forms(self, B: int, c0: int, mma: str, x_layout: str = "vm", keep_fp32: int = 1, need_x_grad: bool = True):
+        """The kernel forms sh_stack_forward / sh_stack_backward take for every step: per step an OR of _lib.FORM flags."""
+        out = np.zeros(len(self.steps), dtype=np.int32)
+        _lib.check(_lib.load().sh_stack_plan_f32(len(self.steps), self._native_steps(), c0, B, _LAYOUT_ID[x_layout], _lib.mma_id(mma),
+                                                 keep_fp32, 1 if need_x_grad else 0, out.ctypes.data), "sh_stack_plan_f32")
+        return out
+
     def _plan(self, B: int, c0: int):
         """Buffer sizes / arena offsets (in floats) for batch B; cached."""
         key = (B, c0)
@@ -355,50 +359,46 @@ class Stack:
             shapes[st.param] = (st.cout, st.S * st.cin)
         # three-plane form (SH_MMA_PLANES3): byte offsets of the plane images of the forward buffers (one arena), of the gradient
         # buffers (another; no aliasing - 288 GB) and of the weight fragments (forward and backward-data operand, one buffer
-        # filled by ONE conversion launch per forward pass); a zero mask = no image (shape outside the plane kernels)
+        # filled by ONE conversion launch per forward pass) - where the library's plan of the stack's kernel forms has them
+        # (sh_stack_plan_f32; planned for a pass that wants the input gradient, which needs a superset of the buffers)
+        forms = self.forms(B, c0, "planes3")
+        has = lambda i, name: bool(forms[i] & _lib.FORM[name])         # noqa: E731
         al = lambda nbytes: (int(nbytes) + 255) // 256 * 256          # noqa: E731
         pl_off, pl_mask, o3 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), 0
         for i in range(n - 1):
             if self._extends(i):
                 pl_off[i], pl_mask[i] = pl_off[i - 1], pl_mask[i - 1]
-                continue
-            nb = int(lib.sh_p3_bytes(self._buffer_rows(i), B, out_ch[i]))
-            if nb:
+            elif has(i, "fwd_img"):
                 pl_off[i], pl_mask[i] = o3, 1
-                o3 += al(nb)
+                o3 += al(lib.sh_p3_bytes(self._buffer_rows(i), B, out_ch[i]))
         pl_total = o3
+        # the images of step inputs the backward pass reads (in_planes)
+        in_img = np.array([1 if forms[i] & (_lib.FORM["bwd_p3w"] | _lib.FORM["bwd_yimg"]) else 0 for i in range(n)], dtype=np.uint64)
         gpl_off, gpl_mask, o3 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), 0
         for i in range(1, n):
             prev = self.steps[i - 1]
-            if prev.kind != "conv":
-                continue
-            nb = int(lib.sh_p3_bytes(prev.R + prev.n_extra, B, prev.cout))
-            if nb and lib.sh_spiral_conv_p3_ok(B, prev.S, prev.cout, prev.cin):
+            if has(i - 1, "bwd_gimg"):
                 gpl_off[i], gpl_mask[i] = o3, 1
-                o3 += al(nb)
+                o3 += al(lib.sh_p3_bytes(prev.R + prev.n_extra, B, prev.cout))
         dpl_off, dpl_mask = 0, 0
-        if last.kind == "conv" and lib.sh_spiral_conv_p3_ok(B, last.S, last.cout, last.cin):
-            nb = int(lib.sh_p3_bytes(last.R + last.n_extra, B, last.cout))
-            if nb:
-                dpl_off, dpl_mask = o3, 1
-                o3 += al(nb)
+        if has(n - 1, "bwd_gimg"):
+            dpl_off, dpl_mask = o3, 1
+            o3 += al(lib.sh_p3_bytes(last.R + last.n_extra, B, last.cout))
         gpl_total = o3
         wf3_off, wf3_mask, wf3t_off, wf3t_mask = (np.zeros(n, dtype=np.uint64) for _ in range(4))
         o3 = 0
         wf3_jobs = []                                                  # (step index, transpose, byte offset)
         for i, st in enumerate(self.steps):
-            if st.kind != "conv":
-                continue
-            if i > 0 and lib.sh_spiral_conv_p3_ok(B, st.S, st.cin, st.cout):
+            if has(i, "fwd_p3"):
                 wf3_off[i], wf3_mask[i] = o3, 1
                 wf3_jobs.append((i, 0, o3))
                 o3 += al(lib.sh_conv_wfrag3_bytes(st.S, st.cin, st.cout))
-            if lib.sh_spiral_conv_p3_ok(B, st.S, st.cout, st.cin):
+            if has(i, "bwd_gimg"):
                 wf3t_off[i], wf3t_mask[i] = o3, 1
                 wf3_jobs.append((i, 1, o3))
                 o3 += al(lib.sh_conv_wfrag3_bytes(st.S, st.cout, st.cin))
         wf3_total = o3
-        plan = dict(pl_off=pl_off, pl_mask=pl_mask, pl_total=pl_total, gpl_off=gpl_off, gpl_mask=gpl_mask, dpl_off=dpl_off,
+        plan = dict(pl_off=pl_off, pl_mask=pl_mask, pl_total=pl_total, in_img=in_img, gpl_off=gpl_off, gpl_mask=gpl_mask, dpl_off=dpl_off,
                     dpl_mask=dpl_mask, gpl_total=gpl_total, wf3_off=wf3_off, wf3_mask=wf3_mask, wf3t_off=wf3t_off,
                     wf3t_mask=wf3t_mask, wf3_jobs=wf3_jobs, wf3_total=wf3_total,
                     f_off=f_off * 4, f_total=f_total, dpre_last_off=dpre_last_off, g_off=g_off * 4, g_mask=g_mask,
@@ -449,12 +449,12 @@ class Stack:
         any_frozen = bool(frozen) and any(frozen)
         any_trained = not frozen or not all(frozen)
         planes_p = wf3_p = None
-        if mma == "planes3" and B % 16 == 0 and plan["wf3_total"]:
+        if mma == "planes3" and plan["wf3_total"]:
             planes, wf3, wbase = self._p3_prepare(plan, weights, with_backward, x.device)
             # what the backward pass needs of this: the weight fragments - and, since round 6, the image arena of the forward
-            # activations (6 bytes per element): the three-plane weight gradient (csrc/wgrad_p3.hip) reads a step's gathered input
-            # through it.  SH_P3_WGRAD=0 (the exact weight-gradient kernels): not kept, as before.
-            p3 = (planes if (with_backward and _P3_WGRAD and any_trained) else None, wf3, wbase)
+            # activations (6 bytes per element) where the plan has the backward pass read a step's input through its image (the
+            # three-plane weight gradient, csrc/wgrad_p3.hip; none with SH_P3_WGRAD=0)
+            p3 = (planes if (with_backward and any_trained and plan["in_img"].any()) else None, wf3, wbase)
             # ... and with the images kept, the fp32 rows that neither pass reads are not written (sh_stack_forward keep_fp32 == 2;
             # SH_P3_DROP_FP32=0: every row, as before)
             if p3[0] is not None and not any_frozen:
@@ -499,7 +499,7 @@ class Stack:
         if mma == "planes3" and p3 is not None and p3[0] is not None:
             # image of the INPUT of step i = image of the buffer step i - 1 wrote
             inpl = np.zeros(n, dtype=np.uint64)
-            inpl[1:] = ((plan["pl_off"] + np.uint64(p3[0].data_ptr())) * plan["pl_mask"])[:n - 1]
+            inpl[1:] = (plan["pl_off"][:n - 1] + np.uint64(p3[0].data_ptr())) * plan["in_img"][1:]
             inpl_p = inpl.ctypes.data
         if mma == "planes3" and p3 is not None:
             gimg = torch.empty(max(256, plan["gpl_total"]), dtype=torch.uint8, device=dev)

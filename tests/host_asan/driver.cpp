@@ -31,6 +31,47 @@ static std::vector<int32_t> make_table(int rows, int S, int limit) {
 }
 template <class T> static T* alloc(size_t n) { return static_cast<T*>(calloc(n ? n : 1, sizeof(T))); }      // exact size: ASan guards the end
 
+// SH_ASAN_DISAGREE: a stack of two convs (8 -> 32, 32 -> 64) at batch 16 in the three-plane form, whose second conv the stub
+// predicates refuse in its forward form and take in its backward form.  The caller hands over every image buffer, the one of step
+// 0's output included (in_planes[1]): the backward pass must not read it, the forward pass did not write it.
+static int disagree_pass() {
+    const int S = 3, B = 16, n = 6, ci[2] = {8, 32}, co[2] = {32, 64};
+    std::vector<int32_t> t[2] = {make_table(n, S, n), make_table(n, S, n)}, tt[2] = {make_table(n, S, n), make_table(n, S, n)};
+    sh_stack_step st[2];
+    memset(st, 0, sizeof st);
+    float* W[2]; float* bias[2]; float* dW[2]; float* db[2]; float* wt[2]; void* ws[2]; size_t wsb[2]; const void* wf3[2]; const void* wf3t[2];
+    for (int i = 0; i < 2; ++i) {
+        sh_stack_step& s = st[i];
+        s.kind = 0; s.param = i; s.table = t[i].data(); s.table_t = tt[i].data(); s.R = n; s.S = S; s.n_in = n; s.cin = ci[i]; s.cout = co[i];
+        s.act = i ? SH_ACT_IDENTITY : SH_ACT_ELU; s.zero_row = n - 1;
+        const size_t nw = (size_t)co[i] * S * ci[i];
+        W[i] = alloc<float>(nw); bias[i] = alloc<float>(co[i]); dW[i] = alloc<float>(nw); db[i] = alloc<float>(co[i]); wt[i] = alloc<float>(nw);
+        const size_t a = sh_spiral_conv_bwd_wgt_workspace(B, n, S, ci[i], co[i]), b = sh_spiral_conv_bwd_wgt_p3_workspace(B, n, S, ci[i], co[i]);
+        wsb[i] = a > b ? a : b; ws[i] = alloc<char>(wsb[i]);
+        wf3[i] = i ? alloc<char>(sh_conv_wfrag3_bytes(S, ci[i], co[i])) : nullptr; wf3t[i] = alloc<char>(sh_conv_wfrag3_bytes(S, co[i], ci[i]));
+    }
+    float* x = alloc<float>((size_t)n * B * 8); float* o0 = alloc<float>((size_t)n * B * 32); float* out = alloc<float>((size_t)B * n * 64);
+    char* img0 = alloc<char>(sh_p3_bytes(n, B, 32));
+    void* planes[2] = {img0, nullptr};
+    float* outs[2] = {o0, out};
+    g_calls.push_back("disagree pass");
+    int rc = sh_stack_forward(2, st, x, 0, n, 8, B, W, bias, outs, 1, SH_MMA_PLANES3, planes, wf3, 1, nullptr);
+    float* g = alloc<float>((size_t)B * n * 64); float* gx = alloc<float>((size_t)n * B * 8); float* g1 = alloc<float>((size_t)n * B * 32);
+    float* dpre_last = alloc<float>((size_t)n * B * 64);
+    char* gimg1 = alloc<char>(sh_p3_bytes(n, B, 32)); char* dimg = alloc<char>(sh_p3_bytes(n, B, 64));
+    float* gin[2] = {gx, g1};
+    void* gpl[2] = {nullptr, gimg1};
+    const void* inpl[2] = {nullptr, img0};
+    if (rc == 0)
+        rc = sh_stack_backward(2, st, x, 0, n, 8, B, outs, g, 1, W, gin, dpre_last, wt, ws, wsb, dW, db, 1, SH_MMA_PLANES3, gpl, dimg, wf3t, inpl, 1,
+                               nullptr);
+    for (int i = 0; i < 2; ++i) {
+        free(W[i]); free(bias[i]); free(dW[i]); free(db[i]); free(wt[i]); free(ws[i]); free(const_cast<void*>(wf3[i])); free(const_cast<void*>(wf3t[i]));
+    }
+    free(x); free(o0); free(out); free(img0); free(g); free(gx); free(g1); free(dpre_last); free(gimg1); free(dimg);
+    return rc;
+}
+
 int main() {
     const int S = 3;
     // step 0: conv 8 -> 16, 6 rows out of 7 in; pre-sums 1 + 2.  step 1: extend, 4 blended rows behind the 6.  step 2: conv 16 -> 8 over
@@ -119,6 +160,7 @@ int main() {
         for (int i = 0; i < 4; ++i) { free(ws[i]); free(wt[i]); free(wf[i]); free(wft[i]); free(const_cast<void*>(wf3[i])); free(const_cast<void*>(wf3t[i])); }
         free(img0); free(imgg);
     }
+    if (rc == 0 && getenv("SH_ASAN_DISAGREE")) rc = disagree_pass();
     for (const auto& c : g_calls) printf("%s\n", c.c_str());
     printf(rc == 0 ? "SEQUENCERS OK %zu calls\n" : "SEQUENCERS FAILED\n", g_calls.size());
     return rc;

@@ -4,6 +4,7 @@
 // sequencer derived past the end of a buffer, and logs the call for the order check.  No GPU, no launches.
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 #include <vector>
@@ -269,7 +270,11 @@ size_t sh_p3_bytes(int rows, int B, int C) {
 }
 size_t sh_conv_wfrag3_bytes(int S, int Cg, int Nout) { return 3 * sh_conv_wfrag_bytes(S, Cg, Nout); }
 int sh_spiral_conv_p3_kind(int B, int S, int Cg, int Nout) { return (B % 16 == 0 && (Cg == 16 || (Cg > 0 && Cg % 32 == 0)) && Nout % 4 == 0) ? 1 : 0; }
-int sh_spiral_conv_p3_ok(int B, int S, int Cg, int Nout) { return B % 16 == 0 && (Cg == 16 || (Cg > 0 && Cg % 32 == 0)) && Nout % 4 == 0; }
+int sh_spiral_conv_p3_ok(int B, int S, int Cg, int Nout) {
+    // SH_ASAN_DISAGREE: refuse the forward form of the driver's 32 -> 64 conv, take its backward form
+    if (getenv("SH_ASAN_DISAGREE") && Cg == 32 && Nout == 64) return 0;
+    return B % 16 == 0 && (Cg == 16 || (Cg > 0 && Cg % 32 == 0)) && Nout % 4 == 0;
+}
 int sh_to_p3(const float* x, int64_t x_sv, int64_t x_sb, void* planes, int B, int rows, int C, sh_stream_t) {
     touch_r(x, span(x_sv, x_sb, rows, B, C, 4)); touch_w(planes, sh_p3_bytes(rows, B, C));
     log("to_p3 rows=%d C=%d", rows, C);
@@ -297,6 +302,7 @@ int sh_spiral_conv_bwd_data_p3(const void* dprep, int, const float* dpre_f32, in
     if (yprev_planes) touch_r(yprev_planes, sh_p3_bytes(n_in, B, Cin));
     else if (yprev) touch_r(yprev, span(yp_sv, yp_sb, n_in, B, Cin, 4));
     log("bwd_data_p3 n_in=%d Cin=%d Cout=%d", n_in, Cin, Cout);
+    if (yprev_planes) log("yprev_planes n_in=%d Cin=%d", n_in, Cin);
     return 0;
 }
 int sh_spiral_conv_p3_rag_ok(int B, int S, int Cg, int Nout, int rag_L) { return sh_spiral_conv_p3_ok(B, S, Cg, Nout) && Cg % 32 == 0 && rag_L > 0 && rag_L <= 64; }

@@ -57,3 +57,16 @@ def test_the_harness_sees_an_undersized_buffer(driver):
     buffer - AddressSanitizer must report it (otherwise the clean run above proves nothing)."""
     r = subprocess.run([driver], capture_output=True, text=True, timeout=120, env=dict(os.environ, SH_ASAN_NEGATIVE="1"))
     assert r.returncode != 0 and "AddressSanitizer" in r.stderr
+
+
+def test_backward_reads_only_the_images_the_forward_pass_wrote(driver):
+    """SH_ASAN_DISAGREE: the stub predicates refuse a conv's forward plane form and take its backward one (driver.cpp
+    disagree_pass).  The forward pass then writes no image of that step's input - so, although the caller hands over a buffer for
+    it, the backward pass must neither run the step's weight gradient on images nor take its activation derivative from one."""
+    r = subprocess.run([driver], capture_output=True, text=True, timeout=120, env=dict(os.environ, SH_ASAN_DISAGREE="1"))
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    calls = r.stdout.strip().splitlines()
+    d = calls[calls.index("disagree pass") + 1:-1]
+    assert d[:2] == ["conv_fwd R=6 Cin=8 Cout=32", "conv_fwd R=6 Cin=32 Cout=64"]            # no image of step 0's output
+    assert "bwd_wgt R=6 Cin=32 Cout=64" in d and not any(c.startswith("bwd_wgt_p3") for c in d)
+    assert "bwd_data_p3 n_in=6 Cin=32 Cout=64" in d and not any(c.startswith("yprev_planes") for c in d)
