@@ -503,6 +503,55 @@ SH_API int sh_bone_length_bwd(const float* kps, const int32_t* bones, const int3
 SH_API int sh_joint_regress_bwd(const float* g_kps, const float* J, int B, int N, int K, int rows, float* g_x, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest points and Chamfer loss: the objective of fitting the model to an unregistered point cloud (no reference
+ * counterpart).  All of it fp32, deterministic (no float atomics), plain stores of every output element.
+ *
+ * sh_nearest_points.  q: [B] bodies of [*][3] query points, batch stride q_sb floats, nq rows searched; t: the same for the
+ * targets (t_sb, nt).  q_count / t_count: int32 [B] live rows per body, or NULL (= nq / nt); a count is clamped to [0, rows].
+ * t_mask: uint8 [nt] (mask_sb == 0: one mask for all bodies) or [B] masks with stride mask_sb >= nt, 0 = target not allowed;
+ * NULL = all allowed.  For body b and query j < q_count[b], over the allowed targets i < t_count[b]:
+ *     dx = qx - tx;  dy = qy - ty;  dz = qz - tz          (each rounded to fp32)
+ *     d2(i) = fma(dz, dz, fma(dy, dy, dx * dx))           (fp32, two fused multiply-adds on the rounded product dx * dx)
+ *     d2[b][j] = min_i d2(i);   idx[b][j] = the lowest i that attains it
+ * i.e. the minimum of (d2, i) in lexicographic order - never the expanded |q|^2 + |t|^2 - 2 q.t form, and no other form is used
+ * to discard candidates.  A body with no allowed target gets idx = -1, d2 = +inf (so does a query all of whose distances
+ * overflow to +inf); queries j >= q_count[b] get idx = -1, d2 = 0.  idx / d2: contiguous [B][nq].
+ * The targets may be split into `chunks` contiguous ranges searched by different workgroups and merged by a second kernel
+ * (chunks = 0: chosen from B, nq, nt so that the chip is filled - sh_nearest_points_chunks tells; a request is rounded to whole
+ * LDS tiles).  The lexicographic minimum is associative and commutative: every split returns the same bits.  A split into more
+ * than one chunk needs sh_nearest_points_workspace(B, nq, nt, chunks) bytes.
+ * B == 0 or nq == 0: SH_OK, nothing launched.  Negative B, nq, nt or chunks: SH_ERR_INVALID_ARG.
+ *
+ * sh_chamfer_fwd.  d2_sm [B][M] (scan -> model: queries = scan points, targets = model vertices), s_count [B] or NULL = m_b;
+ * d2_ms [B][rows] (model -> scan; read only when w_ms > 0, may be NULL otherwise); v_mask over the first n <= rows model
+ * vertices as t_mask above, active = unmasked.  With n_act = active vertices among the first n and tau2 = squared truncation
+ * distance (+inf: none):
+ *     L[b] = (1/m_b) sum_{j < m_b} min(d2_sm[b][j], tau2)  +  w_ms (1/n_act) sum_{i < n active} min(d2_ms[b][i], tau2)
+ * (m_b == 0: L[b] = 0; n_act == 0: no second term).  Sums in fp64 in a fixed order (thread t: terms t, t + 256, ...; then the
+ * 256 thread sums in a fixed tree).  counts [B][2] int32 receives (m_b, n_act) for the backward pass.
+ *
+ * sh_chamfer_bwd.  Gradient w.r.t. the model points x [B][*][3] (stride x_sb, `rows` rows) through the recorded indices; the
+ * scan s [B][*][3] (stride s_sb, M rows) takes none.  For i < n active, with k = idx_ms[b][i]:
+ *     acc   = sum over j < m_b with idx_sm[b][j] == i and d2_sm[b][j] < tau2, in ascending j, of (x_i - s_j)      (fp32)
+ *     g_x[b][i] = gL[b] * ( (2/m_b) acc + [w_ms > 0, d2_ms[b][i] < tau2] (w_ms 2/n_act) (x_i - s_k) )
+ * and 0 for every other row (rows >= n, masked vertices, vertices nothing points at, m_b == 0).  g_x: contiguous [B][rows][3],
+ * every element stored.  idx_ms / d2_ms may both be NULL when w_ms == 0.  Gather form: a workgroup owns 256 rows, sweeps the
+ * indices of the body once and sums its rows' terms in ascending j.
+ */
+SH_API int sh_nearest_points_chunks(int B, int nq, int nt);
+SH_API size_t sh_nearest_points_workspace(int B, int nq, int nt, int chunks);
+SH_API int sh_nearest_points(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* t, int64_t t_sb, int nt,
+                             const int32_t* t_count, const uint8_t* t_mask, int64_t mask_sb, int B, int chunks, int32_t* idx,
+                             float* d2, void* workspace, size_t workspace_bytes, sh_stream_t stream);
+SH_API int sh_chamfer_fwd(const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n,
+                          const uint8_t* v_mask, int64_t mask_sb, float tau2, float w_ms, int B, float* loss, int32_t* counts,
+                          sh_stream_t stream);
+SH_API int sh_chamfer_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
+                          const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
+                          int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x,
+                          sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

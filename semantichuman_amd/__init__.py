@@ -5,7 +5,7 @@ hand-written HIP kernels for gfx950 behind a C ABI (include/sh_kernels.h), wrapp
 reference's own nn.Module interface.  Importing the package works without a GPU; running a
 model does not (no CPU fallback).
 """
-from . import dataset, measure, optim  # noqa: F401
+from . import dataset, measure, optim, scan  # noqa: F401
 from .losses import FaceTables, edge_ratio_loss, eval_l1, l1_loss, recon_loss, vertex_l2_mm  # noqa: F401
 from .models import SpiralAutoencoder, SpiralAutoencoder_multiz_partkps, SpiralConv  # noqa: F401
 

@@ -71,6 +71,11 @@ SIGNATURES = {
     "sh_measure_girth_bwd": (c_int, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "sh_bone_length_bwd": (c_int, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P]),
     "sh_joint_regress_bwd": (c_int, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "sh_nearest_points_chunks": (c_int, [_I, _I, _I]),
+    "sh_nearest_points_workspace": (c_size_t, [_I, _I, _I, _I]),
+    "sh_nearest_points": (c_int, [_P, _L, _I, _P, _P, _L, _I, _P, _P, _L, _I, _I, _P, _P, _P, c_size_t, _P]),
+    "sh_chamfer_fwd": (c_int, [_P, _I, _P, _P, _I, _I, _P, _L, c_float, c_float, _I, _P, _P, _P]),
+    "sh_chamfer_bwd": (c_int, [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _L, _P, c_float, c_float, _P, _I, _P, _P]),
     "sh_dataset_normalize": (c_int, [_P, _P, _I, _I, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P]),
     "sh_gather_meshes": (c_int, [_P, _L, _P, _I, _P, _P]),
     "sh_adam_step": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P] + [ctypes.c_double] * 4 + [_P]),

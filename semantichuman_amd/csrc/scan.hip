@@ -1,0 +1,364 @@
+// Fitting to unregistered point clouds: brute-force nearest-point search and the Chamfer loss built on it
+// (include/sh_kernels.h, "Nearest points and Chamfer loss").  The reference has no counterpart; the search follows the part
+// pair-distance sweep of part_loss.hip: queries in registers, targets streamed through LDS, every lane reading the same LDS
+// address (broadcast).  No float atomics: the search keeps (d2, index) under the lexicographic minimum, which is associative and
+// commutative, and the loss / gradient sums run in a fixed order - the same bits on every call and for every split of the targets.
+#include "sh_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;          // threads per workgroup
+constexpr int QPT = 4;           // queries a thread keeps in registers
+constexpr int QT = NT * QPT;     // queries per workgroup
+constexpr int TT = 256;          // targets per LDS tile: one global load per thread and tile
+constexpr int WG_SLOTS = 2048;   // workgroups the chip holds at once (256 CUs x 8): the automatic split aims at this many
+
+struct NNParams {
+    const float* q; long q_sb; int nq; const int32_t* q_count;
+    const float* t; long t_sb; int nt; const int32_t* t_count;
+    const unsigned char* mask; long mask_sb;
+    int tiles_per_chunk, chunks;
+};
+
+__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
+    if (!cnt) return rows;
+    const int c = cnt[b];
+    return c < 0 ? 0 : (c > rows ? rows : c);
+}
+
+// The distance of the header, in its one fixed form.
+__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
+    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
+    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+
+// grid (query tile, target chunk, body).  final != 0: the one chunk's result is the result (idx / d2 [B][nq]); otherwise the
+// chunk's (d2, idx) go to part_d2 / part_idx [B][chunks][nq] for nearest_merge_kernel.
+// A target that is masked, or lies beyond the body's count, enters LDS as (+inf, +inf, +inf): its distance is +inf, which the
+// strict `<` never selects, so the inner loop carries no index test.  Targets are visited in ascending order and a candidate
+// replaces the best only when strictly closer: the lowest index wins an exact tie.
+__global__ __launch_bounds__(NT) void nearest_search_kernel(const NNParams p, int32_t* __restrict__ idx, float* __restrict__ d2,
+                                                           int final) {
+    __shared__ __attribute__((aligned(16))) float sx[2][TT];
+    __shared__ __attribute__((aligned(16))) float sy[2][TT];
+    __shared__ __attribute__((aligned(16))) float sz[2][TT];
+    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
+    const int nqb = clamp_count(p.q_count, b, p.nq), ntb = clamp_count(p.t_count, b, p.nt);
+    const int j0 = blockIdx.x * QT;
+    if (j0 >= nqb) {                                                     // uniform: no query of this tile is live
+        if (final)
+            for (int k = 0; k < QPT; ++k) {
+                const int j = j0 + k * NT + tid;
+                if (j < p.nq) { idx[(long)b * p.nq + j] = -1; d2[(long)b * p.nq + j] = 0.f; }
+            }
+        return;
+    }
+    const float* qb = p.q + (long)b * p.q_sb;
+    const float* tb = p.t + (long)b * p.t_sb;
+    const unsigned char* mb = p.mask ? p.mask + (long)b * p.mask_sb : nullptr;
+    float qx[QPT], qy[QPT], qz[QPT], best[QPT];
+    int bi[QPT];
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + k * NT + tid;
+        const bool live = j < nqb;
+        qx[k] = live ? qb[3L * j] : 0.f; qy[k] = live ? qb[3L * j + 1] : 0.f; qz[k] = live ? qb[3L * j + 2] : 0.f;
+        best[k] = INFINITY; bi[k] = -1;
+    }
+    const int tiles = (ntb + TT - 1) / TT;
+    const int tile_lo = c * p.tiles_per_chunk;
+    const int tile_hi = min(tile_lo + p.tiles_per_chunk, tiles);
+    if (tile_lo < tile_hi) {                                             // uniform
+        float lx, ly, lz;
+        auto fetch = [&](int tile) {
+            const int i = tile * TT + tid;
+            const bool ok = i < ntb && (!mb || mb[i] != 0);
+            lx = ok ? tb[3L * i] : INFINITY; ly = ok ? tb[3L * i + 1] : INFINITY; lz = ok ? tb[3L * i + 2] : INFINITY;
+        };
+        fetch(tile_lo);
+        sx[0][tid] = lx; sy[0][tid] = ly; sz[0][tid] = lz;
+        __syncthreads();
+        for (int tile = tile_lo; tile < tile_hi; ++tile) {
+            const int cur = (tile - tile_lo) & 1;
+            const bool more = tile + 1 < tile_hi;
+            if (more) fetch(tile + 1);                                   // in flight under this tile's arithmetic
+            const int base = tile * TT;
+#pragma unroll 2
+            for (int u = 0; u < TT; u += 4) {
+                const f32x4 X = *reinterpret_cast<const f32x4*>(&sx[cur][u]);
+                const f32x4 Y = *reinterpret_cast<const f32x4*>(&sy[cur][u]);
+                const f32x4 Z = *reinterpret_cast<const f32x4*>(&sz[cur][u]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int k = 0; k < QPT; ++k) {
+                        const float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
+                        const bool closer = d < best[k];
+                        best[k] = closer ? d : best[k];
+                        bi[k] = closer ? base + u + e : bi[k];
+                    }
+                }
+            }
+            if (more) { sx[cur ^ 1][tid] = lx; sy[cur ^ 1][tid] = ly; sz[cur ^ 1][tid] = lz; }
+            __syncthreads();                                             // one barrier per tile: the other buffer was last read before the previous one
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + k * NT + tid;
+        if (j >= p.nq) continue;
+        if (final) {
+            const long o = (long)b * p.nq + j;
+            idx[o] = j < nqb ? bi[k] : -1;
+            d2[o] = j < nqb ? best[k] : 0.f;
+        } else if (j < nqb) {
+            const long o = ((long)b * p.chunks + c) * p.nq + j;
+            idx[o] = bi[k]; d2[o] = best[k];
+        }
+    }
+}
+
+// (d2, idx) of a query = lexicographic minimum over its chunks.  Chunk c holds lower indices than chunk c + 1, so walking the
+// chunks in order with a strict `<` is that minimum.  One thread per (body, query).
+__global__ __launch_bounds__(256) void nearest_merge_kernel(const int32_t* __restrict__ part_idx, const float* __restrict__ part_d2,
+                                                           const int32_t* __restrict__ q_count, int B, int nq, int chunks,
+                                                           int32_t* __restrict__ idx, float* __restrict__ d2) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)B * nq) return;
+    const int b = (int)(t / nq), j = (int)(t - (long)b * nq);
+    if (j >= clamp_count(q_count, b, nq)) { idx[t] = -1; d2[t] = 0.f; return; }
+    float best = INFINITY;
+    int bi = -1;
+    for (int c = 0; c < chunks; ++c) {
+        const long o = ((long)b * chunks + c) * nq + j;
+        const float d = part_d2[o];
+        if (d < best) { best = d; bi = part_idx[o]; }
+    }
+    idx[t] = bi; d2[t] = best;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One workgroup per body.  Stage 1: thread t sums the terms t, t + 256, ... in order (fp64); stage 2: the 256 sums through the
+// wave butterfly and the four wave sums in order.  counts[b] = (m_b, n_act).
+__global__ __launch_bounds__(256) void chamfer_fwd_kernel(const float* __restrict__ d2_sm, int M, const int32_t* __restrict__ s_count,
+                                                         const float* __restrict__ d2_ms, int rows, int n,
+                                                         const unsigned char* __restrict__ v_mask, long mask_sb, float tau2, float w_ms,
+                                                         float* __restrict__ loss, int32_t* __restrict__ counts) {
+    __shared__ double red[3][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int m = clamp_count(s_count, b, M);
+    const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
+    double s1 = 0.0, s2 = 0.0, na = 0.0;
+    for (int j = tid; j < m; j += 256) s1 += (double)fminf(d2_sm[(long)b * M + j], tau2);
+    for (int i = tid; i < n; i += 256) {
+        if (mb && mb[i] == 0) continue;
+        na += 1.0;
+        if (d2_ms) s2 += (double)fminf(d2_ms[(long)b * rows + i], tau2);
+    }
+    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); na = wave_sum_d(na);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; red[2][tid >> 6] = na; }
+    __syncthreads();
+    if (tid == 0) {
+        double a = 0.0, c = 0.0, k = 0.0;
+        for (int w = 0; w < 4; ++w) { a += red[0][w]; c += red[1][w]; k += red[2][w]; }
+        double L = 0.0;
+        if (m > 0) {
+            L = a / (double)m;
+            if (d2_ms && w_ms > 0.f && k > 0.0) L += (double)w_ms * c / k;
+        }
+        loss[b] = (float)L;
+        counts[2 * b] = m; counts[2 * b + 1] = (int)k;
+    }
+}
+
+// Gradient w.r.t. the model points, gather form.  grid (row tile of 256, body), thread = one row i.  The scan -> model indices are
+// swept in tiles of 256: thread t looks at entry j = base + t and keeps it when its (untruncated) index lies in this workgroup's
+// row range; the kept entries are compacted into LDS in ascending j (wave ballot, waves in order), and every thread then walks
+// that short list and adds the terms whose row is its own - ascending j, the order the header states, whatever the scheduling.
+__global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restrict__ x, long x_sb, int rows, int n,
+                                                         const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
+                                                         const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
+                                                         const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms,
+                                                         const unsigned char* __restrict__ v_mask, long mask_sb,
+                                                         const int32_t* __restrict__ counts, float tau2, float w_ms,
+                                                         const float* __restrict__ gL, float* __restrict__ g_x) {
+    __shared__ int wave_n[4];
+    __shared__ int list_j[256];
+    __shared__ int list_r[256];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int i_lo = blockIdx.x * 256, i = i_lo + tid;
+    const int m = min(clamp_count(s_count, b, M), counts[2 * b]);
+    const int n_act = counts[2 * b + 1];
+    const float* xb = x + (long)b * x_sb;
+    const float* sb = s + (long)b * s_sb;
+    const bool mine = i < n;
+    const float xi0 = mine ? xb[3L * i] : 0.f, xi1 = mine ? xb[3L * i + 1] : 0.f, xi2 = mine ? xb[3L * i + 2] : 0.f;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    auto fetch = [&](int base) {
+        const int j = base + tid;
+        if (j >= m) return -1;
+        return d2_sm[(long)b * M + j] < tau2 ? idx_sm[(long)b * M + j] : -1;
+    };
+    int id = m > 0 ? fetch(0) : -1;
+    for (int base = 0; base < m; base += 256) {                         // m is uniform over the workgroup
+        const int id_next = base + 256 < m ? fetch(base + 256) : -1;     // in flight under this tile's compaction
+        const bool hit = (unsigned)(id - i_lo) < 256u;
+        const unsigned long long bal = __ballot(hit);
+        if (lane == 0) wave_n[wv] = __popcll(bal);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int w = 0; w < 4; ++w) { off += w < wv ? wave_n[w] : 0; total += wave_n[w]; }
+        if (hit) {
+            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+            list_j[pos] = base + tid; list_r[pos] = id - i_lo;
+        }
+        __syncthreads();
+        for (int k = 0; k < total; ++k)
+            if (list_r[k] == tid && mine) {
+                const long j = list_j[k];
+                a0 += xi0 - sb[3 * j]; a1 += xi1 - sb[3 * j + 1]; a2 += xi2 - sb[3 * j + 2];
+            }
+        __syncthreads();                                                 // the lists are rewritten by the next tile
+        id = id_next;
+    }
+    if (i >= rows) return;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    const bool active = mine && !(v_mask && v_mask[(long)b * mask_sb + i] == 0);
+    if (active && m > 0) {
+        const float g = gL[b];
+        const float c1 = 2.f / (float)m;
+        g0 = c1 * a0; g1 = c1 * a1; g2 = c1 * a2;
+        if (idx_ms && w_ms > 0.f && n_act > 0) {
+            const int k = idx_ms[(long)b * rows + i];
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) {
+                const float c2 = w_ms * 2.f / (float)n_act;
+                g0 += c2 * (xi0 - sb[3L * k]); g1 += c2 * (xi1 - sb[3L * k + 1]); g2 += c2 * (xi2 - sb[3L * k + 2]);
+            }
+        }
+        g0 *= g; g1 *= g; g2 *= g;
+    }
+    float* o = g_x + ((long)b * rows + i) * 3;
+    o[0] = g0; o[1] = g1; o[2] = g2;
+}
+
+int nn_tiles(int nt) { return (nt + TT - 1) / TT; }
+
+int nn_auto_chunks(int B, int nq, int nt) {
+    if (B <= 0 || nq <= 0 || nt <= 0) return 1;
+    const long wgs = (long)sh_cdiv(nq, QT) * B;
+    long want = (WG_SLOTS + wgs - 1) / wgs;
+    const int tiles = nn_tiles(nt);
+    if (want > tiles) want = tiles;
+    if (want < 1) want = 1;
+    const int tpc = sh_cdiv(tiles, (int)want);
+    return sh_cdiv(tiles, tpc);
+}
+
+// the split actually run for a request of `chunks` (0 = automatic): whole tiles per chunk, no empty chunk
+int nn_resolve_chunks(int B, int nq, int nt, int chunks, int* tiles_per_chunk) {
+    const int tiles = nn_tiles(nt) > 0 ? nn_tiles(nt) : 1;
+    int c = chunks > 0 ? chunks : nn_auto_chunks(B, nq, nt);
+    if (c > tiles) c = tiles;
+    const int tpc = sh_cdiv(tiles, c);
+    *tiles_per_chunk = tpc;
+    return sh_cdiv(tiles, tpc);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sh_nearest_points_chunks(int B, int nq, int nt) {
+    int tpc;
+    return nn_resolve_chunks(B, nq, nt, 0, &tpc);
+}
+
+size_t sh_nearest_points_workspace(int B, int nq, int nt, int chunks) {
+    if (B <= 0 || nq <= 0 || nt < 0 || chunks < 0) return 0;
+    int tpc;
+    const int c = nn_resolve_chunks(B, nq, nt, chunks, &tpc);
+    return c <= 1 ? 0 : (size_t)B * c * nq * (sizeof(float) + sizeof(int32_t));
+}
+
+int sh_nearest_points(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* t, int64_t t_sb, int nt,
+                      const int32_t* t_count, const uint8_t* t_mask, int64_t mask_sb, int B, int chunks, int32_t* idx, float* d2,
+                      void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    SH_REQUIRE(q && t && idx && d2, SH_ERR_INVALID_ARG, "sh_nearest_points: null pointer");
+    SH_REQUIRE(B >= 0 && nq >= 0 && nt >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "sh_nearest_points: negative size (B %d, nq %d, nt %d, chunks %d)",
+               B, nq, nt, chunks);
+    if (B == 0 || nq == 0) return SH_OK;
+    SH_REQUIRE(q_sb >= 3L * nq && t_sb >= 3L * nt && (!t_mask || mask_sb == 0 || mask_sb >= nt), SH_ERR_INVALID_ARG,
+               "sh_nearest_points: batch stride shorter than a body (q_sb %ld, t_sb %ld, mask_sb %ld)", (long)q_sb, (long)t_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && nt < (1 << 30), SH_ERR_UNSUPPORTED, "sh_nearest_points: B, B*nq or nt too large");
+    NNParams p{};
+    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
+    p.t = t; p.t_sb = (long)t_sb; p.nt = nt; p.t_count = t_count;
+    p.mask = t_mask; p.mask_sb = (long)mask_sb;
+    p.chunks = nn_resolve_chunks(B, nq, nt, chunks, &p.tiles_per_chunk);
+    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_points: %d target chunks", p.chunks);
+    const size_t need = p.chunks <= 1 ? 0 : (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
+               "sh_nearest_points: workspace too small (%zu bytes needed for %d chunks)", need, p.chunks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
+    if (p.chunks <= 1) {
+        ShProfScope ps(st, "nearest_search_kernel|B=%d nq=%d nt=%d chunks=1", B, nq, nt);
+        SH_LAUNCH_PS(ps, nearest_search_kernel, grid, dim3(NT), 0, st, p, idx, d2, 1);
+    } else {
+        float* part_d2 = static_cast<float*>(workspace);
+        int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
+        {
+            ShProfScope ps(st, "nearest_search_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
+            SH_LAUNCH_PS(ps, nearest_search_kernel, grid, dim3(NT), 0, st, p, part_idx, part_d2, 0);
+        }
+        ShProfScope ps(st, "nearest_merge_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
+        SH_LAUNCH_PS(ps, nearest_merge_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, part_idx, part_d2, q_count, B, nq,
+                     p.chunks, idx, d2);
+    }
+    SH_CHECK_LAUNCH("nearest_points");
+    return SH_OK;
+}
+
+int sh_chamfer_fwd(const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n, const uint8_t* v_mask,
+                   int64_t mask_sb, float tau2, float w_ms, int B, float* loss, int32_t* counts, sh_stream_t stream) {
+    SH_REQUIRE(d2_sm && loss && counts, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: null pointer");
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: bad size (B %d, M %d, rows %d, n %d)",
+               B, M, rows, n);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: w_ms and tau2 must be >= 0 (and not NaN)");
+    SH_REQUIRE(!v_mask || mask_sb == 0 || mask_sb >= n, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: mask stride %ld shorter than n", (long)mask_sb);
+    if (B == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "chamfer_fwd_kernel|B=%d M=%d n=%d", B, M, n);
+    SH_LAUNCH_PS(ps, chamfer_fwd_kernel, dim3((unsigned)B), dim3(256), 0, st, d2_sm, M, s_count, w_ms > 0.f ? d2_ms : nullptr, rows, n, v_mask,
+                 (long)mask_sb, tau2, w_ms, loss, counts);
+    SH_CHECK_LAUNCH("chamfer_fwd");
+    return SH_OK;
+}
+
+int sh_chamfer_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
+                   const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
+                   int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x, sh_stream_t stream) {
+    SH_REQUIRE(x && s && idx_sm && d2_sm && counts && gL && g_x, SH_ERR_INVALID_ARG, "sh_chamfer_bwd: null pointer");
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "sh_chamfer_bwd: bad size (B %d, M %d, rows %d, n %d)",
+               B, M, rows, n);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_chamfer_bwd: w_ms and tau2 must be >= 0 (and not NaN)");
+    SH_REQUIRE((idx_ms != nullptr) == (d2_ms != nullptr), SH_ERR_INVALID_ARG, "sh_chamfer_bwd: idx_ms and d2_ms come together");
+    if (B == 0 || rows == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * rows && s_sb >= 3L * M && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_chamfer_bwd: batch stride shorter than a body (x_sb %ld, s_sb %ld, mask_sb %ld)", (long)x_sb, (long)s_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * rows < (1L << 30), SH_ERR_UNSUPPORTED, "sh_chamfer_bwd: B or B*rows too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "chamfer_bwd_kernel|B=%d M=%d rows=%d", B, M, rows);
+    SH_LAUNCH_PS(ps, chamfer_bwd_kernel, dim3((unsigned)sh_cdiv(rows, 256), (unsigned)B), dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M,
+                 s_count, idx_sm, d2_sm, w_ms > 0.f ? idx_ms : nullptr, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, gL, g_x);
+    SH_CHECK_LAUNCH("chamfer_bwd");
+    return SH_OK;
+}
+
+}  // extern "C"

@@ -6,14 +6,15 @@ HIP decoder stack.  `decode_edits` reproduces the demo's seven decodes for a (sh
 
 Measurement-targeted editing: `fit_latents` optimises part latents through the frozen decoder against any per-body objective
 (the decoder's backward pass then computes no weight gradient); `fit_part_girths` asks for girths ("chest +4 %, waist unchanged")
-through the differentiable measurements of measure.py.
+through the differentiable measurements of measure.py; `fit_scan` fits the latents to unregistered point clouds (scans, depth
+clouds, meshes of another topology) with the Chamfer objective of scan.py.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import constants, measure, optim
+from . import constants, measure, optim, scan
 from .part_losses import kps2skl, skl2kps
 
 # utils_SH.py:21-24 (SMPL-style kinematic tree of the 24 body joints)
@@ -206,3 +207,27 @@ def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, b
     with torch.no_grad():
         g_final = measure.girths(_decode(model, z_new, z_kps, dummy), rings)
     return z_new, g_final, losses
+
+
+def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None):
+    """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
+    own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
+    The scans must be in the model's normalised frame - nothing here aligns them (no rotation, translation or scale is solved
+    for).  trunc / w_model_to_scan / vertex_mask as in scan.chamfer (w_model_to_scan = 0: scan -> model only, for partial scans);
+    the decoder's dummy row is never matched.  Works for both model classes (plain SpiralAutoencoder: z [B, nz], z_kps ignored);
+    no host synchronisation in the loop.  Returns (new z, chamfer [B] of the result, loss per step [steps])."""
+    if not isinstance(scans, scan.ScanBatch):
+        scans = scan.ScanBatch(scans, z.device)
+    if len(scans) != z.shape[0]:
+        raise ValueError("fit_scan: %d bodies, %d scans" % (z.shape[0], len(scans)))
+    semantic = hasattr(model, "kps_encode")
+    if semantic and dummy is None:
+        dummy = _default_dummy(model, z)
+
+    def objective(x_hat):
+        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan)
+
+    z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
+    with torch.no_grad():
+        final = objective(_decode(model, z_new, z_kps, dummy))
+    return z_new, final, losses

@@ -401,6 +401,83 @@ def joint_regress_bwd(g_kps, J, rows):
     return out
 
 
+def _points(t, what):
+    """[B, rows, 3] fp32 HIP points with packed rows (the batch stride is free) -> (B, rows, batch stride in elements)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[2] == 3
+            and (t.shape[1] == 0 or (t.stride(2) == 1 and t.stride(1) == 3))):
+        raise RuntimeError("semantichuman_amd.%s needs fp32 HIP points [B, rows, 3] (got %s %s %s); there is no CPU path"
+                           % (what, getattr(t, "device", None), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    B, rows = t.shape[0], t.shape[1]
+    if B > 1 and t.stride(0) < 3 * rows:
+        raise RuntimeError("semantichuman_amd.%s: bodies overlap in memory (batch stride %d < %d)" % (what, t.stride(0), 3 * rows))
+    return B, rows, (t.stride(0) if B > 1 else rows * 3)
+
+
+def _mask_arg(mask, B, rows, device):
+    """None | bool/uint8 [rows] | [B, rows] -> (uint8 tensor or None, batch stride)."""
+    if mask is None:
+        return None, 0
+    m = torch.as_tensor(mask, device=device)
+    m = (m != 0).to(torch.uint8).contiguous()
+    if m.dim() == 1 and m.shape[0] == rows:
+        return m, 0
+    if m.dim() == 2 and tuple(m.shape) == (B, rows):
+        return m, rows
+    raise ValueError("mask must be [%d] or [%d, %d], got %s" % (rows, B, rows, tuple(m.shape)))
+
+
+def _count_arg(cnt, B, device):
+    if cnt is None:
+        return None
+    c = torch.as_tensor(cnt, device=device).to(torch.int32).contiguous()
+    if tuple(c.shape) != (B,):
+        raise ValueError("per-body counts must be [%d], got %s" % (B, tuple(c.shape)))
+    return c
+
+
+def nearest_points(q, t, q_count=None, t_count=None, t_mask=None, nq=None, nt=None, chunks=0, out=None):
+    """sh_nearest_points: q [B, *, 3] (the first nq rows are queries), t [B, *, 3] (the first nt rows are targets) ->
+    (idx int32 [B, nq], d2 fp32 [B, nq]).  chunks: 0 = the library's split of the target range, k = that many ranges."""
+    B, q_rows, q_sb = _points(q, "nearest_points")
+    Bt, t_rows, t_sb = _points(t, "nearest_points")
+    if Bt != B:
+        raise ValueError("nearest_points: %d query bodies, %d target bodies" % (B, Bt))
+    nq = q_rows if nq is None else int(nq)
+    nt = t_rows if nt is None else int(nt)
+    if not (0 <= nq <= q_rows and 0 <= nt <= t_rows):
+        raise ValueError("nearest_points: nq / nt exceed the tensors' rows")
+    q_count, t_count = _count_arg(q_count, B, q.device), _count_arg(t_count, B, q.device)
+    mask, mask_sb = _mask_arg(t_mask, B, nt, q.device)
+    lib = _lib.load()
+    idx, d2 = out if out is not None else (torch.empty((B, nq), dtype=torch.int32, device=q.device),
+                                          torch.empty((B, nq), dtype=torch.float32, device=q.device))
+    nbytes = lib.sh_nearest_points_workspace(B, nq, nt, chunks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    check(lib.sh_nearest_points(ptr(q), q_sb, nq, ptr(q_count), ptr(t), t_sb, nt, ptr(t_count), ptr(mask), mask_sb, B, chunks, ptr(idx),
+                                ptr(d2), ptr(ws), nbytes, stream_ptr()), "sh_nearest_points")
+    return idx, d2
+
+
+def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None):
+    """sh_chamfer_fwd -> (loss [B], counts int32 [B, 2])."""
+    B, M = d2_sm.shape
+    loss, counts = out if out is not None else (torch.empty(B, dtype=torch.float32, device=d2_sm.device),
+                                                torch.empty((B, 2), dtype=torch.int32, device=d2_sm.device))
+    check(_lib.load().sh_chamfer_fwd(ptr(d2_sm), M, ptr(s_count), ptr(d2_ms), rows, n, ptr(v_mask), mask_sb, tau2, w_ms, B, ptr(loss),
+                                     ptr(counts), stream_ptr()), "sh_chamfer_fwd")
+    return loss, counts
+
+
+def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
+    """sh_chamfer_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
+    B, rows, x_sb = _points(x, "chamfer_bwd")
+    _, M, s_sb = _points(s, "chamfer_bwd")
+    g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_chamfer_bwd(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), ptr(idx_sm), ptr(d2_sm), ptr(idx_ms), ptr(d2_ms),
+                                     ptr(v_mask), mask_sb, ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g), stream_ptr()), "sh_chamfer_bwd")
+    return g
+
+
 NORM_FLAGS = {"zeromean": 1, "zeroroot": 2, "onelength": 4, "small": 8, "gass": 16, "normal": 32}
 
 
