@@ -552,6 +552,61 @@ SH_API int sh_chamfer_bwd(const float* x, int64_t x_sb, int rows, int n, const f
                           sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
+ * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
+ * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.
+ *
+ * sh_align_moments.  s [B][*][3] the (aligned) scan, stride s_sb, M rows, s_count [B] or NULL = m_b; x [B][*][3] the model
+ * points, stride x_sb, `rows` rows, the first n of them vertices; v_mask, idx_sm / d2_sm [B][M], idx_ms / d2_ms [B][rows], tau2,
+ * w_ms as sh_chamfer_bwd takes them (idx_ms / d2_ms may be NULL when w_ms == 0).  The pairs (p = scan side, q = model side) and
+ * weights are those of the Chamfer loss:
+ *     scan -> model:  (s_j, x[idx_sm[j]])  for j < m_b with 0 <= idx_sm[j] < n and d2_sm[j] < tau2,             weight 1 / m_b
+ *     model -> scan:  (s[idx_ms[i]], x_i)  for active i < n with 0 <= idx_ms[i] < m_b and d2_ms[i] < tau2,  weight w_ms / n_act
+ * (the second only when w_ms > 0).  Stage 1, this call: one workgroup per range of SH_ALIGN_RANGE consecutive j (then i); thread
+ * t takes t, t + 256, ... of its range, fp64 products of the fp32 coordinates, fp64 sums, then a fixed tree over the 256
+ * threads.  partials: fp64 [B][sh_align_ranges(M, n, w_ms)][SH_ALIGN_PARTIAL], per range the UNWEIGHTED sums
+ *     [0] pairs kept  [1..3] sum p  [4..6] sum q  [7..15] sum q p^T (row-major: q_r p_c at 7 + 3 r + c)  [16] sum |p|^2
+ *     [17] sum |q|^2  [18] active vertices of the range (model -> scan ranges only)
+ * every element stored (a range beyond m_b holds zeros).  The order depends on M and n only, never on B or the grid.
+ *
+ * sh_align_solve.  Stage 2 and the closed form, one wave per body.  The ranges' sums are added in range order per direction and
+ * joined with the weights above into the moments, mom fp64 [B][SH_ALIGN_MOMENTS] (optional output):
+ *     [0] W = sum w  [1..3] sum w p  [4..6] sum w q  [7..15] sum w q p^T  [16] sum w |p|^2  [17] sum w |q|^2  [18] pairs kept
+ *     [19] 0
+ * Then, in fp64: p_bar = sum w p / W, q_bar likewise, H = sum w q p^T / W - q_bar p_bar^T; R = the rotation of Horn's closed form
+ * (the eigenvector of the largest eigenvalue of the symmetric 4 x 4 matrix built from H, cyclic Jacobi, SH_ALIGN_JACOBI_SWEEPS
+ * sweeps, no convergence test), a proper rotation for every H; c = trace(R^T H) / var_p with var_p = sum w |p|^2 / W - |p_bar|^2
+ * for SH_ALIGN_SIMILARITY (c = 1 when var_p <= 0 or the numerator <= 0, and in the other modes); R = I for SH_ALIGN_TRANSLATION;
+ * t = q_bar - c R p_bar.  W == 0: the increment is the identity.  inc (optional) fp32 [B][13] receives the increment (c R
+ * row-major, t, c).  The pose so far (pose_in [B][12], scale_in [B]) is composed with it, A_new = c R A_old,
+ * t_new = c R t_old + t, scale_new = c scale_old, each rounded to fp32 once, into pose_out / scale_out (may alias the inputs;
+ * pose_out NULL: only mom is written).  M, n, s_count and w_ms must be those of the sh_align_moments call.
+ *
+ * sh_transform_points.  dst contiguous [B][M][3]; for j < count[b] (NULL = M), with p = src[b][j] (stride src_sb) and the pose:
+ *     dst[b][j][r] = fma(A[r][2], p_z, fma(A[r][1], p_y, fma(A[r][0], p_x, t[r])))          (fp32, three fused multiply-adds)
+ * and 0 for rows j >= count[b].
+ *
+ * All three: B == 0 is SH_OK with nothing launched; null pointers and negative sizes are SH_ERR_INVALID_ARG before the device is
+ * touched; nothing allocates or synchronises.
+ */
+enum sh_align_mode { SH_ALIGN_TRANSLATION = 0, SH_ALIGN_RIGID = 1, SH_ALIGN_SIMILARITY = 2 };
+#define SH_ALIGN_RANGE 2048
+#define SH_ALIGN_PARTIAL 19
+#define SH_ALIGN_MOMENTS 20
+#define SH_ALIGN_JACOBI_SWEEPS 12
+SH_API int sh_align_ranges(int M, int n, float w_ms);
+SH_API size_t sh_align_partials_bytes(int B, int M, int n, float w_ms);
+SH_API int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                            const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
+                            const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                            sh_stream_t stream);
+SH_API int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B,
+                          const float* pose_in, const float* scale_in, float* pose_out, float* scale_out, float* inc, double* mom,
+                          sh_stream_t stream);
+SH_API int sh_transform_points(const float* src, int64_t src_sb, int M, const int32_t* count, const float* pose, int B, float* dst,
+                               sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

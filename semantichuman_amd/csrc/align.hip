@@ -1,0 +1,315 @@
+// Aligning scans to the model: the weighted moments of the matched pairs, the closed-form similarity from them, and the
+// transform of the scan (include/sh_kernels.h, "Scan alignment").  The matches are the ones scan.hip's search has recorded for
+// the Chamfer loss, so a pose update costs no search.  No atomics of any kind: every sum runs in a fixed order that depends on
+// M and n only - the same bits on every call, for every batch size and for a body alone or inside a batch.
+#include "sh_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;                       // threads per workgroup of the moments kernel
+constexpr int RANGE = SH_ALIGN_RANGE;         // pairs per workgroup: thread t takes t, t + 256, ... of its range (8 each)
+constexpr int NP = SH_ALIGN_PARTIAL;          // sums per range
+constexpr int NM = SH_ALIGN_MOMENTS;          // doubles per body of the finished moments
+
+__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
+    if (!cnt) return rows;
+    const int c = cnt[b];
+    return c < 0 ? 0 : (c > rows ? rows : c);
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+int ranges_of(int rows) { return (rows + RANGE - 1) / RANGE; }
+
+// grid (range, body).  Ranges [0, r_sm) walk the scan -> model pairs j, ranges [r_sm, r_sm + r_ms) the model -> scan pairs i.
+// The sums are unweighted (the weight of a direction is one factor per body, applied by align_solve_kernel); a range beyond the
+// body's count stores zeros, which change nothing when the second stage adds them.
+__global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
+                                                           const float* __restrict__ x, long x_sb, int rows, int n,
+                                                           const unsigned char* __restrict__ v_mask, long mask_sb,
+                                                           const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
+                                                           const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms, float tau2,
+                                                           int r_sm, double* __restrict__ partials) {
+    __shared__ double red[NP][4];
+    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int R = gridDim.x;
+    const int m = clamp_count(s_count, b, M);
+    const float* sb = s + (long)b * s_sb;
+    const float* xb = x + (long)b * x_sb;
+    double a[NP];
+#pragma unroll
+    for (int c = 0; c < NP; ++c) a[c] = 0.0;
+    auto add = [&](long ip, long iq) {
+        const double p0 = sb[3 * ip], p1 = sb[3 * ip + 1], p2 = sb[3 * ip + 2];
+        const double q0 = xb[3 * iq], q1 = xb[3 * iq + 1], q2 = xb[3 * iq + 2];
+        a[0] += 1.0;
+        a[1] += p0; a[2] += p1; a[3] += p2;
+        a[4] += q0; a[5] += q1; a[6] += q2;
+        a[7] += q0 * p0; a[8] += q0 * p1; a[9] += q0 * p2;
+        a[10] += q1 * p0; a[11] += q1 * p1; a[12] += q1 * p2;
+        a[13] += q2 * p0; a[14] += q2 * p1; a[15] += q2 * p2;
+        a[16] += p0 * p0 + p1 * p1 + p2 * p2;
+        a[17] += q0 * q0 + q1 * q1 + q2 * q2;
+    };
+    if (r < r_sm) {                                                      // uniform over the workgroup
+        const int lo = r * RANGE, hi = min(lo + RANGE, m);
+        for (int j = lo + tid; j < hi; j += NT) {
+            const int i = idx_sm[(long)b * M + j];
+            if (i >= 0 && i < n && d2_sm[(long)b * M + j] < tau2) add(j, i);
+        }
+    } else {
+        const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
+        const int lo = (r - r_sm) * RANGE, hi = min(lo + RANGE, n);
+        for (int i = lo + tid; i < hi; i += NT) {
+            if (mb && mb[i] == 0) continue;
+            a[18] += 1.0;                                                // n_act
+            const int k = idx_ms[(long)b * rows + i];
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add(k, i);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        const double v = wave_sum_d(a[c]);
+        if ((tid & 63) == 0) red[c][tid >> 6] = v;
+    }
+    __syncthreads();
+    if (tid < NP) partials[((long)b * R + r) * NP + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// One Jacobi rotation of the symmetric 4 x 4 matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.
+// Select form: a zero off-diagonal element gives the identity rotation, no branch.
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4]) {
+    const double apq = a[P][Q];
+    const double tau = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+    double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+    t = (apq != 0.0 && t == t) ? t : 0.0;                                // apq == 0, or tau = +-inf / NaN: nothing to rotate
+    const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                        // columns P, Q
+        const double akp = a[k][P], akq = a[k][Q];
+        a[k][P] = c * akp - sn * akq; a[k][Q] = sn * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                        // rows P, Q
+        const double apk = a[P][k], aqk = a[Q][k];
+        a[P][k] = c * apk - sn * aqk; a[Q][k] = sn * apk + c * aqk;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = v[k][P], vkq = v[k][Q];
+        v[k][P] = c * vkp - sn * vkq; v[k][Q] = sn * vkp + c * vkq;
+    }
+}
+
+// One wave per body.  Lane c < NP adds the ranges' partial sums of component c in range order (scan -> model ranges, then
+// model -> scan ranges) and the two directions are joined with their weights; lane 0 then solves for the pose.
+__global__ __launch_bounds__(64) void align_solve_kernel(const double* __restrict__ partials, int M, int n, const int32_t* __restrict__ s_count,
+                                                        float w_ms, int r_sm, int r_ms, int mode, const float* __restrict__ pose_in,
+                                                        const float* __restrict__ scale_in, float* __restrict__ pose_out,
+                                                        float* __restrict__ scale_out, float* __restrict__ inc, double* __restrict__ mom) {
+    __shared__ double sum[2][NP];
+    __shared__ double mo[NM];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int R = r_sm + r_ms;
+    if (lane < NP) {
+        double u = 0.0, w = 0.0;
+        for (int r = 0; r < r_sm; ++r) u += partials[((long)b * R + r) * NP + lane];
+        for (int r = r_sm; r < R; ++r) w += partials[((long)b * R + r) * NP + lane];
+        sum[0][lane] = u; sum[1][lane] = w;
+    }
+    __syncthreads();
+    const int m = clamp_count(s_count, b, M);
+    const double n_act = sum[1][18];
+    const double w1 = m > 0 ? 1.0 / (double)m : 0.0;
+    const double w2 = (m > 0 && r_ms > 0 && n_act > 0.0) ? (double)w_ms / n_act : 0.0;
+    if (lane < 18) mo[lane] = w1 * sum[0][lane] + w2 * sum[1][lane];
+    if (lane == 18) mo[18] = (w1 > 0.0 ? sum[0][0] : 0.0) + (w2 > 0.0 ? sum[1][0] : 0.0);       // kept pairs, exact
+    if (lane == 19) mo[19] = 0.0;
+    __syncthreads();
+    if (mom && lane < NM) mom[(long)b * NM + lane] = mo[lane];
+    if (lane != 0 || !pose_out) return;
+
+    const double W = mo[0];
+    double Rm[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    double c = 1.0, t[3] = {0.0, 0.0, 0.0};
+    if (W > 0.0) {
+        const double iw = 1.0 / W;
+        double pb[3], qb[3], H[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pb[k] = mo[1 + k] * iw; qb[k] = mo[4 + k] * iw; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) H[i][j] = mo[7 + 3 * i + j] * iw - qb[i] * pb[j];      // H[i][j] = cov(q_i, p_j)
+        if (mode != SH_ALIGN_TRANSLATION) {
+            // Horn's matrix: with S_ab = sum p_a q_b = H[b][a], its largest eigenvector is the quaternion (w, x, y, z) of the
+            // rotation that maximises trace(R^T H).  Scaled to unit size first: the eigenvectors do not change.
+            const double Sxx = H[0][0], Sxy = H[1][0], Sxz = H[2][0], Syx = H[0][1], Syy = H[1][1], Syz = H[2][1], Szx = H[0][2],
+                         Szy = H[1][2], Szz = H[2][2];
+            double a[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                              {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                              {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                              {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+            double big = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) big = fmax(big, fabs(a[i][j]));
+            const double inv = big > 0.0 ? 1.0 / big : 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[i][j] *= inv;
+            double v[4][4] = {{1.0, 0.0, 0.0, 0.0}, {0.0, 1.0, 0.0, 0.0}, {0.0, 0.0, 1.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};
+            for (int sweep = 0; sweep < SH_ALIGN_JACOBI_SWEEPS; ++sweep) {       // fixed count: no convergence test
+                jacobi_rotate<0, 1>(a, v); jacobi_rotate<0, 2>(a, v); jacobi_rotate<0, 3>(a, v);
+                jacobi_rotate<1, 2>(a, v); jacobi_rotate<1, 3>(a, v); jacobi_rotate<2, 3>(a, v);
+            }
+            double best = a[0][0], q0 = v[0][0], q1 = v[1][0], q2 = v[2][0], q3 = v[3][0];   // lowest index on a tie
+#pragma unroll
+            for (int k = 1; k < 4; ++k) {
+                const bool up = a[k][k] > best;
+                best = up ? a[k][k] : best;
+                q0 = up ? v[0][k] : q0; q1 = up ? v[1][k] : q1; q2 = up ? v[2][k] : q2; q3 = up ? v[3][k] : q3;
+            }
+            const double qn = 1.0 / sqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+            q0 *= qn; q1 *= qn; q2 *= qn; q3 *= qn;
+            Rm[0][0] = 1.0 - 2.0 * (q2 * q2 + q3 * q3); Rm[0][1] = 2.0 * (q1 * q2 - q0 * q3); Rm[0][2] = 2.0 * (q1 * q3 + q0 * q2);
+            Rm[1][0] = 2.0 * (q1 * q2 + q0 * q3); Rm[1][1] = 1.0 - 2.0 * (q1 * q1 + q3 * q3); Rm[1][2] = 2.0 * (q2 * q3 - q0 * q1);
+            Rm[2][0] = 2.0 * (q1 * q3 - q0 * q2); Rm[2][1] = 2.0 * (q2 * q3 + q0 * q1); Rm[2][2] = 1.0 - 2.0 * (q1 * q1 + q2 * q2);
+        }
+        if (mode == SH_ALIGN_SIMILARITY) {
+            const double var_p = mo[16] * iw - (pb[0] * pb[0] + pb[1] * pb[1] + pb[2] * pb[2]);
+            double num = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) num += Rm[i][j] * H[i][j];
+            c = (var_p > 0.0 && num > 0.0) ? num / var_p : 1.0;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = qb[i] - c * (Rm[i][0] * pb[0] + Rm[i][1] * pb[1] + Rm[i][2] * pb[2]);
+    }
+    if (inc) {
+        float* o = inc + (long)b * 13;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) o[3 * i + j] = (float)(c * Rm[i][j]);
+            o[9 + i] = (float)t[i];
+        }
+        o[12] = (float)c;
+    }
+    const float* pi = pose_in + (long)b * 12;
+    double A0[3][3], t0[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A0[i][j] = pi[3 * i + j];
+        t0[i] = pi[9 + i];
+    }
+    const double s0 = scale_in[b];
+    float* po = pose_out + (long)b * 12;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) po[3 * i + j] = (float)(c * (Rm[i][0] * A0[0][j] + Rm[i][1] * A0[1][j] + Rm[i][2] * A0[2][j]));
+        po[9 + i] = (float)(c * (Rm[i][0] * t0[0] + Rm[i][1] * t0[1] + Rm[i][2] * t0[2]) + t[i]);
+    }
+    scale_out[b] = (float)(c * s0);
+}
+
+// grid (tile of 256 points, body); the expression of the header, one fma chain per coordinate.
+__global__ __launch_bounds__(256) void transform_points_kernel(const float* __restrict__ src, long src_sb, int M, const int32_t* __restrict__ count,
+                                                              const float* __restrict__ pose, float* __restrict__ dst) {
+    const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    if (j < clamp_count(count, b, M)) {
+        const float* A = pose + (long)b * 12;
+        const float* p = src + (long)b * src_sb + 3L * j;
+        const float px = p[0], py = p[1], pz = p[2];
+        o0 = __builtin_fmaf(A[2], pz, __builtin_fmaf(A[1], py, __builtin_fmaf(A[0], px, A[9])));
+        o1 = __builtin_fmaf(A[5], pz, __builtin_fmaf(A[4], py, __builtin_fmaf(A[3], px, A[10])));
+        o2 = __builtin_fmaf(A[8], pz, __builtin_fmaf(A[7], py, __builtin_fmaf(A[6], px, A[11])));
+    }
+    float* o = dst + ((long)b * M + j) * 3;
+    o[0] = o0; o[1] = o1; o[2] = o2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sh_align_ranges(int M, int n, float w_ms) {
+    if (M < 0 || n < 0) return 0;
+    return ranges_of(M) + (w_ms > 0.f ? ranges_of(n) : 0);
+}
+
+size_t sh_align_partials_bytes(int B, int M, int n, float w_ms) {
+    if (B <= 0) return 0;
+    return (size_t)B * sh_align_ranges(M, n, w_ms) * NP * sizeof(double);
+}
+
+int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                     const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
+                     const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes, sh_stream_t stream) {
+    SH_REQUIRE(s && x && idx_sm && d2_sm && partials, SH_ERR_INVALID_ARG, "sh_align_moments: null pointer");
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "sh_align_moments: bad size (B %d, M %d, rows %d, n %d)",
+               B, M, rows, n);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_align_moments: w_ms and tau2 must be >= 0 (and not NaN)");
+    SH_REQUIRE(!(w_ms > 0.f) || (idx_ms && d2_ms), SH_ERR_INVALID_ARG, "sh_align_moments: w_ms > 0 needs idx_ms and d2_ms");
+    if (B == 0) return SH_OK;
+    SH_REQUIRE(s_sb >= 3L * M && x_sb >= 3L * rows && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_align_moments: batch stride shorter than a body (s_sb %ld, x_sb %ld, mask_sb %ld)", (long)s_sb, (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * M < (1L << 30) && (long)B * rows < (1L << 30), SH_ERR_UNSUPPORTED, "sh_align_moments: B, B*M or B*rows too large");
+    const int r_sm = ranges_of(M), R = sh_align_ranges(M, n, w_ms);
+    SH_REQUIRE(partials_bytes >= sh_align_partials_bytes(B, M, n, w_ms), SH_ERR_WORKSPACE, "sh_align_moments: partials too small (%zu bytes needed)",
+               sh_align_partials_bytes(B, M, n, w_ms));
+    if (R == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "align_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
+    SH_LAUNCH_PS(ps, align_moments_kernel, dim3((unsigned)R, (unsigned)B), dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                 (long)mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, partials);
+    SH_CHECK_LAUNCH("align_moments");
+    return SH_OK;
+}
+
+int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,
+                   const float* scale_in, float* pose_out, float* scale_out, float* inc, double* mom, sh_stream_t stream) {
+    SH_REQUIRE(partials && (mom || pose_out), SH_ERR_INVALID_ARG, "sh_align_solve: null pointer");
+    SH_REQUIRE(!pose_out || (pose_in && scale_in && scale_out), SH_ERR_INVALID_ARG, "sh_align_solve: pose_out needs pose_in, scale_in and scale_out");
+    SH_REQUIRE(B >= 0 && M >= 0 && n >= 0, SH_ERR_INVALID_ARG, "sh_align_solve: bad size (B %d, M %d, n %d)", B, M, n);
+    SH_REQUIRE(w_ms >= 0.f, SH_ERR_INVALID_ARG, "sh_align_solve: w_ms must be >= 0 (and not NaN)");
+    SH_REQUIRE(mode == SH_ALIGN_TRANSLATION || mode == SH_ALIGN_RIGID || mode == SH_ALIGN_SIMILARITY, SH_ERR_INVALID_ARG,
+               "sh_align_solve: unknown mode %d", mode);
+    if (B == 0) return SH_OK;
+    const int r_sm = ranges_of(M), r_ms = w_ms > 0.f ? ranges_of(n) : 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "align_solve_kernel|B=%d ranges=%d mode=%d", B, r_sm + r_ms, mode);
+    SH_LAUNCH_PS(ps, align_solve_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, M, n, s_count, w_ms, r_sm, r_ms, mode, pose_in, scale_in, pose_out,
+                 scale_out, inc, mom);
+    SH_CHECK_LAUNCH("align_solve");
+    return SH_OK;
+}
+
+int sh_transform_points(const float* src, int64_t src_sb, int M, const int32_t* count, const float* pose, int B, float* dst, sh_stream_t stream) {
+    SH_REQUIRE(src && pose && dst, SH_ERR_INVALID_ARG, "sh_transform_points: null pointer");
+    SH_REQUIRE(B >= 0 && M >= 0, SH_ERR_INVALID_ARG, "sh_transform_points: negative size (B %d, M %d)", B, M);
+    if (B == 0 || M == 0) return SH_OK;
+    SH_REQUIRE(src_sb >= 3L * M, SH_ERR_INVALID_ARG, "sh_transform_points: batch stride %ld shorter than a body", (long)src_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * M < (1L << 30), SH_ERR_UNSUPPORTED, "sh_transform_points: B or B*M too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "transform_points_kernel|B=%d M=%d", B, M);
+    SH_LAUNCH_PS(ps, transform_points_kernel, dim3((unsigned)sh_cdiv(M, 256), (unsigned)B), dim3(256), 0, st, src, (long)src_sb, M, count, pose, dst);
+    SH_CHECK_LAUNCH("transform_points");
+    return SH_OK;
+}
+
+}  // extern "C"

@@ -7,7 +7,8 @@ HIP decoder stack.  `decode_edits` reproduces the demo's seven decodes for a (sh
 Measurement-targeted editing: `fit_latents` optimises part latents through the frozen decoder against any per-body objective
 (the decoder's backward pass then computes no weight gradient); `fit_part_girths` asks for girths ("chest +4 %, waist unchanged")
 through the differentiable measurements of measure.py; `fit_scan` fits the latents to unregistered point clouds (scans, depth
-clouds, meshes of another topology) with the Chamfer objective of scan.py.
+clouds, meshes of another topology) with the Chamfer objective of scan.py; `register_scan` does the same for scans that arrive
+in their own frame and units, solving for the pose (scan.align) before and during the fit.
 """
 from __future__ import annotations
 
@@ -123,7 +124,7 @@ def _decode(model, z, z_kps, dummy):
     return model.decode(z)                                             # plain SpiralAutoencoder: decode(z)
 
 
-def fit_latents(model, z, z_kps, objective, parts, *, steps, lr, dummy=None):
+def fit_latents(model, z, z_kps, objective, parts, *, steps, lr, dummy=None, after_step=None):
     """Optimise the latents `z[:, parts]` so that `objective(model.decode(...))` falls; returns (new z, loss per step).
 
     objective(x_hat) -> one scalar per body [B]; each step minimises their sum (bodies are independent).  Per step: decode ->
@@ -132,7 +133,8 @@ def fit_latents(model, z, z_kps, objective, parts, *, steps, lr, dummy=None):
     decoder's backward pass computes no weight gradient) and their requires_grad flags restored afterwards; their .grad are not
     touched.  SemanticHuman: z [B, P, d], z_kps [B, P, d_kps], parts = part indices (None: all), dummy = the decoder's dummy row
     (None: zeros, as demo.py).  Plain SpiralAutoencoder: z [B, nz], z_kps ignored, parts = latent indices (None: all).
-    The loss tensor [steps] stays on the device."""
+    The loss tensor [steps] stays on the device.  after_step(t), if given, is called after the optimiser step t (register_scan
+    updates its pose there); it must not synchronise."""
     if steps < 1:
         raise ValueError("steps must be >= 1")
     semantic = hasattr(model, "kps_encode")
@@ -160,6 +162,8 @@ def fit_latents(model, z, z_kps, objective, parts, *, steps, lr, dummy=None):
             loss.backward()
             opt.step()
             losses[t] = loss.detach()
+            if after_step is not None:
+                after_step(t)
     finally:
         for p, f in zip(params, flags):
             p.requires_grad_(f)
@@ -212,8 +216,8 @@ def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, b
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
-    The scans must be in the model's normalised frame - nothing here aligns them (no rotation, translation or scale is solved
-    for).  trunc / w_model_to_scan / vertex_mask as in scan.chamfer (w_model_to_scan = 0: scan -> model only, for partial scans);
+    The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
+    solves for rotation, translation and scale.  trunc / w_model_to_scan / vertex_mask as in scan.chamfer (w_model_to_scan = 0: scan -> model only, for partial scans);
     the decoder's dummy row is never matched.  Works for both model classes (plain SpiralAutoencoder: z [B, nz], z_kps ignored);
     no host synchronisation in the loop.  Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
@@ -231,3 +235,57 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     with torch.no_grad():
         final = objective(_decode(model, z_new, z_kps, dummy))
     return z_new, final, losses
+
+
+def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
+                  lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None):
+    """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
+    with the latents.
+
+    1. scan.align of the scans against decode(z): `align_iters` ICP iterations in `mode` from the start `init`, with
+       align_w_model_to_scan (None: 1.0 for mode "similarity", else the fit's own w_model_to_scan).  align_iters = 0 keeps the
+       start pose as it is.
+    2. The fit_latents loop with the Chamfer objective on the aligned scans (trunc / w_model_to_scan / vertex_mask as in
+       fit_scan).  After every `align_every`-th step the pose is updated from the matches that step's forward pass has just found
+       (moments -> closed-form increment -> the ORIGINAL scan under the new pose: three launches, no search); align_every = 0
+       keeps the pose of stage 1.  No host synchronisation in the loop.
+
+    Returns (new z, pose, chamfer [B] of the result in the model's frame, loss per step [steps]).  `pose.apply(scans)` are the
+    scans in the model's frame, `pose.to_scan_frame(decode(z_new))` the fitted body in the scan's.
+
+    Limits: those of scan.align - ICP is local (the moment start fixes translation and scale, not rotation; beyond about 45
+    degrees pass a start Pose), a similarity with w_model_to_scan = 0 from the identity can shrink the scan into the model (the
+    defaults of stage 1 avoid it), partial scans want mode="rigid" with scan -> model only, and only the normalisations that are
+    similarities (zeromean, zeroroot, onelength, small) can be undone by a pose.  No point-to-triangle distance, no file reader."""
+    if not isinstance(scans, scan.ScanBatch):
+        scans = scan.ScanBatch(scans, z.device)
+    if len(scans) != z.shape[0]:
+        raise ValueError("register_scan: %d bodies, %d scans" % (z.shape[0], len(scans)))
+    if mode not in ("translation", "rigid", "similarity"):
+        raise ValueError("register_scan: mode must be 'translation', 'rigid' or 'similarity'")
+    align_iters, align_every = int(align_iters), int(align_every)
+    if align_iters < 0 or align_every < 0:
+        raise ValueError("register_scan: align_iters and align_every must be >= 0")
+    semantic = hasattr(model, "kps_encode")
+    if semantic and dummy is None:
+        dummy = _default_dummy(model, z)
+    w_align = (1.0 if mode == "similarity" else w_model_to_scan) if align_w_model_to_scan is None else align_w_model_to_scan
+    with torch.no_grad():
+        x0 = _decode(model, z.detach(), z_kps, dummy)
+    pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
+                                  vertex_mask=vertex_mask)
+    matches = {} if align_every > 0 else None
+    state = {"partials": None}
+
+    def objective(x_hat):
+        return scan.chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches=matches)
+
+    def after_step(t):
+        if (t + 1) % align_every == 0:
+            state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"])
+
+    z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
+                                after_step=after_step if align_every > 0 else None)
+    with torch.no_grad():
+        final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan)
+    return z_new, pose, final, losses

@@ -478,6 +478,39 @@ def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb,
     return g
 
 
+ALIGN_MODES = {"translation": 0, "rigid": 1, "similarity": 2}   # enum sh_align_mode
+ALIGN_PARTIAL, ALIGN_MOMENTS = 19, 20                           # SH_ALIGN_PARTIAL, SH_ALIGN_MOMENTS
+
+
+def align_moments(s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
+    """sh_align_moments -> the ranges' partial sums, fp64 [B, ranges, 19] (stage 1; sh_align_solve finishes them)."""
+    B, M, s_sb = _points(s, "align_moments")
+    _, rows, x_sb = _points(x, "align_moments")
+    lib = _lib.load()
+    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PARTIAL), dtype=torch.float64, device=s.device)
+    check(lib.sh_align_moments(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(idx_sm), ptr(d2_sm), ptr(idx_ms),
+                               ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), "sh_align_moments")
+    return part
+
+
+def align_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, inc=None, mom=None):
+    """sh_align_solve: partial sums -> moments (mom fp64 [B, 20], optional), the pose increment (inc fp32 [B, 13], optional) and
+    the pose (pose fp32 [B, 12], scale [B]) composed with it into pose_out / scale_out (which may be pose / scale themselves)."""
+    B = part.shape[0]
+    check(_lib.load().sh_align_solve(ptr(part), M, n, ptr(s_count), w_ms, ALIGN_MODES[mode], B, ptr(pose), ptr(scale), ptr(pose_out), ptr(scale_out),
+                                     ptr(inc), ptr(mom), stream_ptr()), "sh_align_solve")
+
+
+def transform_points(src, count, pose, out=None):
+    """sh_transform_points: dst[b, j] = A_b src[b, j] + t_b for j < count[b], zero rows beyond; pose fp32 contiguous [B, 12]."""
+    B, M, src_sb = _points(src, "transform_points")
+    if not (pose.is_cuda and pose.dtype == torch.float32 and pose.is_contiguous() and tuple(pose.shape) == (B, 12)):
+        raise RuntimeError("semantichuman_amd.transform_points needs a contiguous fp32 HIP pose [%d, 12]" % B)
+    dst = out if out is not None else torch.empty((B, M, 3), dtype=torch.float32, device=src.device)
+    check(_lib.load().sh_transform_points(ptr(src), src_sb, M, ptr(count), ptr(pose), B, ptr(dst), stream_ptr()), "sh_transform_points")
+    return dst
+
+
 NORM_FLAGS = {"zeromean": 1, "zeroroot": 2, "onelength": 4, "small": 8, "gass": 16, "normal": 32}
 
 

@@ -4,11 +4,14 @@
   * `nearest(q, t, ...)`          -> sh_nearest_points: index and squared distance of each query's nearest target
   * `chamfer(x_hat, scans, ...)`  -> sh_nearest_points (one or both directions) + sh_chamfer_fwd / sh_chamfer_bwd, differentiable
                                      w.r.t. x_hat through the recorded indices
+  * `Pose`, `moment_pose(...)`, `align(x, scans, ...)`  scan frame -> model frame: batched similarity ICP on the same matches
+                                     (sh_transform_points, sh_align_moments, sh_align_solve)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
-|a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  Scans are expected in the
-model's normalised frame: there is no rigid or similarity alignment here, no point-to-triangle distance and no file reader.
-The search and the loss have no CPU path: tensors must live on the GPU.
+|a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
+model's normalised frame; `align` (and editing.register_scan, which alternates it with the fit) brings a scan there by a
+translation, a rigid motion or a similarity.  There is no point-to-triangle distance and no file reader.
+The search, the loss and the alignment have no CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -76,7 +79,7 @@ def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
 
 class _Chamfer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms):
+    def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms, matches=None):
         s, cnt = scans.points, scans.counts
         rows = x.shape[1]
         idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)
@@ -86,6 +89,9 @@ class _Chamfer(torch.autograd.Function):
         loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
         ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
         ctx.save_for_backward(x, idx_sm, d2_sm, idx_ms, d2_ms, counts)
+        if matches is not None:
+            matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_sm, idx_ms=idx_ms,
+                           d2_ms=d2_ms)
         return loss
 
     @staticmethod
@@ -93,10 +99,10 @@ class _Chamfer(torch.autograd.Function):
         x, idx_sm, d2_sm, idx_ms, d2_ms, counts = ctx.saved_tensors
         g = ops.chamfer_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, idx_sm, d2_sm, idx_ms, d2_ms, ctx.v_mask, ctx.mask_sb, counts,
                             ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None
 
 
-def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0):
+def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -107,7 +113,8 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     Rows >= n are never matched and get no gradient - do not slice x_hat instead.  vertex_mask [n] or [B, n]: False = vertex
     takes no part (not a target, no term of its own).  trunc: distances beyond it are cut to it and stop pulling (None: none).
     w_model_to_scan = 0 skips the model -> scan search altogether - the setting for a partial scan.  The gradient flows through
-    the nearest indices found in the forward pass; the scan takes none."""
+    the nearest indices found in the forward pass; the scan takes none.  matches: a dict that receives what the forward pass
+    found (indices, distances, the arguments they belong to) for `pose_update`; None (the default) records nothing."""
     if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
         raise RuntimeError("semantichuman_amd.scan.chamfer needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
                            % getattr(x_hat, "device", type(x_hat)))
@@ -126,4 +133,200 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
         raise ValueError("chamfer: trunc must be > 0")
     tau2 = math.inf if trunc is None else float(trunc) ** 2
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
-    return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w)
+    return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches)
+
+
+# ------------------------------------------------------------------------------------------------ alignment
+class Pose:
+    """B similarities scan frame -> model frame, s' = A s + t with A = scale * R (R a proper rotation, scale > 0).  One fp32
+    buffer `packed` [B, 12] (A row-major, then t - the layout of include/sh_kernels.h) of which `A` [B, 3, 3] and `t` [B, 3] are
+    views, plus `scale` [B].  Lives wherever its tensors live; `apply` runs on the GPU only."""
+
+    def __init__(self, A, t, scale=None):
+        A = torch.as_tensor(A, dtype=torch.float32)
+        t = torch.as_tensor(t, dtype=torch.float32, device=A.device)
+        if A.dim() != 3 or tuple(A.shape[1:]) != (3, 3) or tuple(t.shape) != (A.shape[0], 3):
+            raise ValueError("Pose: A must be [B, 3, 3] and t [B, 3], got %s and %s" % (tuple(A.shape), tuple(t.shape)))
+        if scale is None:
+            scale = torch.linalg.det(A.double().cpu()).abs().pow(1.0 / 3.0)
+        scale = torch.as_tensor(scale, dtype=torch.float32).to(A.device).reshape(-1).contiguous()
+        if tuple(scale.shape) != (A.shape[0],):
+            raise ValueError("Pose: scale must be [%d]" % A.shape[0])
+        self.packed = torch.cat([A.reshape(-1, 9), t], 1).contiguous()
+        self.scale = scale
+
+    @classmethod
+    def from_packed(cls, packed, scale):
+        out = cls.__new__(cls)
+        out.packed, out.scale = packed, scale
+        return out
+
+    @classmethod
+    def identity(cls, B, device):
+        packed = torch.zeros((int(B), 12), dtype=torch.float32, device=device)
+        packed[:, 0] = packed[:, 4] = packed[:, 8] = 1.0
+        return cls.from_packed(packed, torch.ones(int(B), dtype=torch.float32, device=device))
+
+    @property
+    def A(self):
+        return self.packed[:, :9].view(-1, 3, 3)
+
+    @property
+    def t(self):
+        return self.packed[:, 9:]
+
+    def __len__(self):
+        return self.packed.shape[0]
+
+    def clone(self):
+        return Pose.from_packed(self.packed.clone(), self.scale.clone())
+
+    def select(self, sl):
+        return Pose.from_packed(self.packed[sl].contiguous(), self.scale[sl].contiguous())
+
+    def apply(self, points, counts=None):
+        """A p + t for every point, in the one fp32 expression of sh_transform_points.  points: a ScanBatch (-> ScanBatch, rows
+        beyond the counts zero) or fp32 HIP points [B, M, 3] with optional live counts [B] (-> tensor)."""
+        if isinstance(points, ScanBatch):
+            out = ScanBatch.__new__(ScanBatch)
+            out.host_counts, out.counts = points.host_counts, points.counts
+            out.points = ops.transform_points(points.points, points.counts, self.packed)
+            return out
+        B = ops._points(points, "scan.Pose.apply")[0]
+        return ops.transform_points(points, ops._count_arg(counts, B, points.device), self.packed)
+
+    def compose(self, first):
+        """The pose that applies `first` and then this one (float64 inside, rounded to fp32 once)."""
+        A1, A0 = self.A.double(), first.A.double()
+        A = torch.matmul(A1, A0)
+        t = torch.matmul(A1, first.t.double()[:, :, None])[:, :, 0] + self.t.double()
+        return Pose(A.float(), t.float(), (self.scale.double() * first.scale.double()).float())
+
+    def inverse(self):
+        """Model frame -> scan frame (float64 adjugate of A, rounded to fp32 once)."""
+        a = self.A.double()
+        c0 = torch.linalg.cross(a[:, 1], a[:, 2])
+        c1 = torch.linalg.cross(a[:, 2], a[:, 0])
+        c2 = torch.linalg.cross(a[:, 0], a[:, 1])
+        det = (a[:, 0] * c0).sum(-1)
+        inv = torch.stack([c0, c1, c2], dim=2) / det[:, None, None]
+        t = -(inv * self.t.double()[:, None, :]).sum(-1)
+        return Pose(inv.float(), t.float(), (1.0 / self.scale.double()).float())
+
+    def to_scan_frame(self, x_hat):
+        """Model-frame points [B, rows, 3] (decoded vertices) carried back into the scan's frame; plain tensor operations."""
+        inv = self.inverse()
+        return (x_hat[:, :, None, :] * inv.A[:, None, :, :]).sum(-1) + inv.t[:, None, :]
+
+
+def _check_pair(x, scans, n, what):
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise RuntimeError("semantichuman_amd.scan.%s needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
+                           % (what, getattr(x, "device", type(x))))
+    if not isinstance(scans, ScanBatch):
+        scans = ScanBatch(scans, x.device)
+    B, rows, _ = ops._points(x, "scan." + what)
+    ops._points(scans.points, "scan." + what)
+    if len(scans) != B:
+        raise ValueError("%s: %d bodies, %d scans" % (what, B, len(scans)))
+    n = rows - 1 if n is None else int(n)
+    if not 0 < n <= rows:
+        raise ValueError("%s: n = %d outside (0, %d]" % (what, n, rows))
+    return scans, B, rows, n
+
+
+def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
+    """The start pose that needs no matches: the scan's centroid onto the centroid of the (unmasked) model vertices and, with
+    scale=True, its RMS radius onto theirs; the rotation is the identity.  x [B, rows, 3] on the GPU, n / vertex_mask as in
+    `chamfer`.  A one-off in torch (float64 sums), outside every loop."""
+    scans, B, rows, n = _check_pair(x, scans, n, "moment_pose")
+    v_mask, _ = ops._mask_arg(vertex_mask, B, n, x.device)
+    s = scans.points.double()
+    ws = (torch.arange(s.shape[1], device=x.device)[None, :] < scans.counts[:, None]).double()
+    wx = torch.ones((B, n), dtype=torch.float64, device=x.device) if v_mask is None else v_mask.double().expand(B, n)
+    xv = x.detach()[:, :n].double()
+
+    def stats(p, w):
+        tot = w.sum(1).clamp_min(1.0)
+        c = (p * w[:, :, None]).sum(1) / tot[:, None]
+        r2 = (((p - c[:, None, :]) ** 2).sum(-1) * w).sum(1) / tot
+        return c, r2
+
+    cs, rs = stats(s, ws)
+    cx, rx = stats(xv, wx)
+    c = torch.sqrt(rx / rs) if scale else torch.ones_like(rs)
+    c = torch.where(torch.isfinite(c) & (c > 0), c, torch.ones_like(c))
+    A = torch.eye(3, dtype=torch.float64, device=x.device)[None] * c[:, None, None]
+    return Pose(A.float(), (cx - c[:, None] * cs).float(), c.float())
+
+
+def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None):
+    """One closed-form pose step from recorded matches, no search: moments of the matched pairs (`matches`, as `chamfer(...,
+    matches=)` or `align` fill it, found on `aligned`), the pose increment that minimises the same weighted squared distances,
+    composed into `pose` in place, and `aligned.points` overwritten with the ORIGINAL `scans` under the new pose.  Three
+    launches."""
+    m = matches
+    part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
+                             m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+    ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
+    ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
+    return part
+
+
+def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0):
+    """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
+    nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
+    trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
+
+    mode: "translation", "rigid" or "similarity".  init: "moments" (`moment_pose`; without scale unless mode is "similarity"),
+    "identity", or a Pose.  Per iteration: the ORIGINAL scan under the pose so far -> search -> the logged Chamfer value ->
+    moments -> solve; rounding therefore does not build up in the points.  No host synchronisation.  chunks: the search's split
+    (every value gives the same bits).  Returns (pose, the aligned scans as a ScanBatch, chamfer [iters, B] - row k is the value
+    BEFORE the k-th update).  Not differentiable.
+
+    Limits.  ICP is local: the moment start fixes translation and scale, not rotation - a scan rotated by more than about 45
+    degrees against the model needs a caller-supplied start pose (no principal-axes or multi-start search here).  mode
+    "similarity" with w_model_to_scan = 0 and init="identity" can shrink the scan into the model; the defaults avoid it.
+    Partial scans: mode="rigid", w_model_to_scan=0.  A similarity reaches the model's frame only under the normalisations that
+    are similarities (zeromean, zeroroot, onelength, small), not under gass or normal."""
+    scans, B, rows, n = _check_pair(x, scans, n, "align")
+    if mode not in ops.ALIGN_MODES:
+        raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("align: iters must be >= 0")
+    w = float(w_model_to_scan)
+    if not w >= 0.0:
+        raise ValueError("align: w_model_to_scan must be >= 0")
+    if trunc is not None and not float(trunc) > 0.0:
+        raise ValueError("align: trunc must be > 0")
+    tau2 = math.inf if trunc is None else float(trunc) ** 2
+    v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
+    x = x.detach()
+    if isinstance(init, Pose):
+        if len(init) != B:
+            raise ValueError("align: %d bodies, start pose for %d" % (B, len(init)))
+        pose = Pose.from_packed(init.packed.to(x.device).contiguous().clone(), init.scale.to(x.device).contiguous().clone())
+    elif init == "moments":
+        pose = moment_pose(scans, x, n, vertex_mask, scale=(mode == "similarity"))
+    elif init == "identity":
+        pose = Pose.identity(B, x.device)
+    else:
+        raise ValueError("align: init must be 'moments', 'identity' or a Pose")
+    aligned = pose.apply(scans)
+    log = torch.empty((iters, B), dtype=torch.float32, device=x.device)
+    cnt = scans.counts
+    M = scans.points.shape[1]
+    sm = (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device))
+    ms = (torch.empty((B, rows), dtype=torch.int32, device=x.device), torch.empty((B, rows), dtype=torch.float32, device=x.device)) if w > 0.0 \
+        else (None, None)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
+    matches = dict(x=x, n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w, idx_sm=sm[0], d2_sm=sm[1], idx_ms=ms[0], d2_ms=ms[1])
+    part = None
+    for k in range(iters):
+        ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm)
+        if w > 0.0:
+            ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms)
+        ops.chamfer_fwd(sm[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
+        part = pose_update(pose, scans, aligned, matches, mode, partials=part)
+    return pose, aligned, log
