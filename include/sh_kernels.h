@@ -552,6 +552,80 @@ SH_API int sh_chamfer_bwd(const float* x, int64_t x_sb, int rows, int n, const f
                           sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest surface points: the scan -> model term measured to the model's SURFACE instead of to its vertices (no reference
+ * counterpart).  fp32, deterministic, plain stores of every output element.
+ *
+ * sh_nearest_surface.  q: [B] bodies of [*][3] scan points, batch stride q_sb floats, nq rows searched, q_count int32 [B] live
+ * rows per body or NULL (= nq).  x: [B] bodies of model points, batch stride x_sb, the first n rows are vertices.  faces: int32
+ * [nF][3], ONE table for the whole batch, indices into the first n rows.  v_mask as t_mask of sh_nearest_points, over n rows.  A
+ * triangle is a target only if its three indices lie in [0, n) and all three vertices are active; the others are skipped.
+ * For scan point s and target triangle f with corners a = x[f0], b = x[f1], c = x[f2], everything in fp32, every operation
+ * rounded on its own except the fused multiply-adds written out (no other contraction):
+ *     ab = b - a;  ac = c - a;  ap = s - a                               (component-wise: the differences from a come first)
+ *     dot(u, v) = fma(u.z, v.z, fma(u.y, v.y, u.x * v.x))
+ *     e11 = dot(ab, ab);  e12 = dot(ab, ac);  e22 = dot(ac, ac);  d1 = dot(ab, ap);  d2 = dot(ac, ap)
+ *     d3 = d1 - e11;  d4 = d2 - e12;  d5 = d1 - e12;  d6 = d2 - e22      (Ericson's ab.bp, ac.bp, ab.cp, ac.cp, in a's frame)
+ *     vc = d1 * d4 - d3 * d2;  vb = d5 * d2 - d1 * d6;  va = d3 * d6 - d5 * d4
+ * The region test of Ericson, Real-Time Collision Detection 5.1.5; the FIRST rule that applies gives the weights (v, w) of b, c:
+ *     1. d1 <= 0 and d2 <= 0                               (0, 0)                                vertex a
+ *     2. d3 >= 0 and d4 <= d3                              (1, 0)                                vertex b
+ *     3. vc <= 0 and d1 >= 0 and d3 <= 0                   (d1 / (d1 - d3), 0)                   edge ab
+ *     4. d6 >= 0 and d5 <= d6                              (0, 1)                                vertex c
+ *     5. vb <= 0 and d2 >= 0 and d6 <= 0                   (0, d2 / (d2 - d6))                   edge ca
+ *     6. va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0         w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w      edge bc
+ *     7. otherwise, with sum = (va + vb) + vc              (vb * (1 / sum), vc * (1 / sum))      interior
+ * An edge rule (3, 5, 6) applies only if its quotient's denominator is > 0, and 1 / sum is replaced by 0 when sum is not > 0.
+ * That is the rule for a degenerate triangle (two or three equal corners, or collinear): an edge of length 0 is passed over,
+ * the other vertex and edge rules cover the triangle, and where rounding lets a point reach rule 7 it falls to vertex a.  Then v = min(max(v, 0), 1), w = min(max(w, 0), 1 - v): every result is a valid convex
+ * combination, l1 = v, l2 = w, l0 = fl(fl(1 - v) - w) >= 0, and every d2 is finite.
+ *     r = ap - fma(w, ac, v * ab)   (component-wise);    d2(f) = fma(r.z, r.z, fma(r.y, r.y, r.x * r.x))
+ * The answer for the point is the minimum of (d2, f) in lexicographic order: face [B][nq] int32, d2 [B][nq], uv [B][nq][2] =
+ * (l1, l2) of that face.  No target triangle: face -1, d2 +inf, uv 0; points j >= q_count[b]: face -1, d2 0, uv 0.
+ *
+ * How it is computed.  Three launches.  (1) Per body and triangle, the record (a, ab, ac, e11, e12, e22) and a bounding sphere:
+ * centre m = a + (ab + ac) / 3, radius SH_SURFACE_MARGIN * sqrt(max |corner - m|^2).  (2) The sweep: scan points in registers
+ * (a wave owns 256 consecutive ones), spheres streamed through LDS.  With cull != 0 a triangle is skipped for a point when
+ *     |s - m|^2 > (rb + radius)^2,      rb = SH_SURFACE_MARGIN * sqrt(min(bound[b][j], best d2 found so far))
+ * all in the difference form above; the region test runs, for the lanes that cannot skip, when any lane of the wave cannot.
+ * bound [B][nq] (or NULL = none) is an upper bound of the answer supplied by the caller - the squared distance to the nearest
+ * vertex, which sh_nearest_points gives.  Why a skip never changes the result: the computed foot point is a convex combination
+ * of the rounded ab, ac, so sqrt(d2(f)) >= dist(s, triangle) (1 - 5 u) - 12 u radius with u = 2^-24, dist(s, triangle) >=
+ * |s - m| - radius, and the computed sphere test carries another 4 u: about 30 u in all against the margin's 2^-10 = 16384 u.
+ * A skipped triangle is therefore strictly farther than SH_SURFACE_MARGIN times the bound in force.  (3) Per point: the minimum
+ * over the chunks; if it exceeds SH_SURFACE_MARGIN * bound[b][j] (the bound was no upper bound after all: a vertex mask can
+ * leave the nearest vertex without a target triangle; the factor admits a foot point on the nearest vertex itself, whose
+ * distance differs from the vertex search's by rounding) the point is swept again without any bound; then the weights of the
+ * chosen face.  cull == 0 runs every (point, triangle) pair through the region test and ignores bound: the
+ * yardstick, same bits.  The triangles may be split into `chunks` ranges (0: chosen to fill the chip;
+ * sh_nearest_surface_chunks tells) - every split gives the same bits.  workspace: sh_nearest_surface_workspace(B, nq, nF,
+ * chunks) bytes, 16-byte aligned, always needed; nothing allocates.  stats: NULL, or two zeroed uint64 that receive [0] the
+ * number of (point, triangle) region tests the sweep ran and [1] the number of points swept again in step (3) - a diagnostic
+ * for benchmarks, served by a separate instantiation of the sweep (integer atomics, one per wave; the instantiation a NULL
+ * selects has no counter and no atomic; results are the same).  B == 0 or nq == 0: SH_OK, nothing launched.
+ *
+ * sh_chamfer_surface_bwd.  The gradient of sh_chamfer_fwd fed with the d2 above, w.r.t. x, the weights taken as constants
+ * (at the minimiser the derivative through them vanishes or is blocked by the active constraint).  For row i < n active:
+ *     acc = sum over j < m_b with face[b][j] >= 0, d2[b][j] < tau2 and corner k of that face == i, in ascending j and corner
+ *           order 0, 1, 2 within a j, of  fl(l_k * e),   e = fma(w, ac, v * ab) - ap  (= q_j - s_j, from x and uv as above),
+ *           (l_0, l_1, l_2) = (fl(fl(1 - v) - w), v, w);          acc = fl(acc + term), no contraction
+ *     g_x[b][i] = gL[b] * ( (2/m_b) acc + [w_ms > 0, d2_ms[b][i] < tau2] (w_ms 2/n_act) (x_i - s_k) ),   k = idx_ms[b][i]
+ * and 0 for every other row; the model -> scan term is the vertex term of sh_chamfer_bwd, unchanged.  Gather form, a workgroup
+ * owns 256 rows; no atomics of any kind.  counts as sh_chamfer_fwd wrote them.
+ */
+#define SH_SURFACE_MARGIN (1.0f + 0x1p-10f)
+SH_API int sh_nearest_surface_chunks(int B, int nq, int nF);
+SH_API size_t sh_nearest_surface_workspace(int B, int nq, int nF, int chunks);
+SH_API int sh_nearest_surface(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* x, int64_t x_sb, int n,
+                              const int32_t* faces, int nF, const uint8_t* v_mask, int64_t mask_sb, const float* bound, int B,
+                              int chunks, int cull, int32_t* face, float* d2, float* uv, uint64_t* stats, void* workspace,
+                              size_t workspace_bytes, sh_stream_t stream);
+SH_API int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M,
+                                  const int32_t* s_count, const int32_t* faces, int nF, const int32_t* face, const float* d2,
+                                  const float* uv, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask, int64_t mask_sb,
+                                  const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x,
+                                  sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.

@@ -1,0 +1,461 @@
+// Point-to-surface distance for scan fitting: the exact closest point of a triangle mesh to every scan point, and the gradient
+// of the Chamfer term built on it (include/sh_kernels.h, "Nearest surface points").  The reference has no counterpart.  The
+// sweep follows nearest_search_kernel of scan.hip: queries in registers, one record per triangle streamed through LDS, every
+// lane reading the same LDS address (broadcast).  What is streamed is the triangle's bounding sphere; the region test of the
+// header runs for a triangle only when the wave's ballot says that some lane cannot rule it out.  The cull only ever skips a
+// triangle whose fp32 distance is provably larger than the query's best so far, so the result equals the unculled sweep's bit
+// for bit; the unculled sweep is kept (cull = 0) as its yardstick.  No atomics of any kind in the kernels a fit runs (the
+// only atomics are two counters of the diagnostic instantiation the benchmark asks for with `stats`): (d2, face) is kept under the lexicographic minimum, the gradient sums run in a fixed order.
+#include "sh_common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int NT = 256;          // threads per workgroup
+constexpr int QPT = 4;           // queries a thread keeps in registers
+constexpr int QT = NT * QPT;     // queries per workgroup; a wave owns 256 CONSECUTIVE ones (a spatially sorted scan keeps them close)
+constexpr int FT = 256;          // triangles per LDS tile: one global load per thread and tile
+constexpr int WG_SLOTS = 2048;   // workgroups the chip holds at once: the automatic split aims at this many
+constexpr int TRI = 12;          // floats per triangle record: a, ab, ac, |ab|^2, ab.ac, |ac|^2
+// Safety factor of the cull, applied to sqrt(best) and to the sphere's radius.  The rounding it has to cover is about 30 units
+// of 2^-24 (include/sh_kernels.h derives it); 2^-10 is 500 times that and costs no measurable number of extra region tests.
+constexpr float MARGIN = SH_SURFACE_MARGIN;
+
+__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
+    if (!cnt) return rows;
+    const int c = cnt[b];
+    return c < 0 ? 0 : (c > rows ? rows : c);
+}
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+}
+
+struct Foot { float v, w, d2; };
+
+// The header's expression, in its one fixed form: no contraction beyond the fused multiply-adds written out, so that every
+// kernel that inlines it (sweep, finish, gradient) and the numpy transcription of tests/surface_ref.py round alike.
+__device__ __forceinline__ Foot surf_foot(const float* __restrict__ T, float sx, float sy, float sz) {
+#pragma clang fp contract(off)
+    const float ax = T[0], ay = T[1], az = T[2], abx = T[3], aby = T[4], abz = T[5], acx = T[6], acy = T[7], acz = T[8];
+    const float e11 = T[9], e12 = T[10], e22 = T[11];
+    const float apx = sx - ax, apy = sy - ay, apz = sz - az;
+    const float d1 = dot3(abx, aby, abz, apx, apy, apz), d2 = dot3(acx, acy, acz, apx, apy, apz);
+    const float d3 = d1 - e11, d4 = d2 - e12, d5 = d1 - e12, d6 = d2 - e22;
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    // interior first, then the regions in REVERSE order of the header's list, so that the first region that applies wins
+    const float sum = (va + vb) + vc;
+    const float den = sum > 0.f ? 1.0f / sum : 0.f;                       // degenerate triangle: falls to vertex a
+    float v = vb * den, w = vc * den;
+    const float den_bc = e43 + e56, den_ac = d2 - d6, den_ab = d1 - d3;
+    if (va <= 0.f && e43 >= 0.f && e56 >= 0.f && den_bc > 0.f) { w = e43 / den_bc; v = 1.0f - w; }          // edge bc
+    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f && den_ac > 0.f) { v = 0.f; w = d2 / den_ac; }                  // edge ca
+    if (d6 >= 0.f && d5 <= d6) { v = 0.f; w = 1.f; }                                                       // vertex c
+    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f && den_ab > 0.f) { v = d1 / den_ab; w = 0.f; }                  // edge ab
+    if (d3 >= 0.f && d4 <= d3) { v = 1.f; w = 0.f; }                                                       // vertex b
+    if (d1 <= 0.f && d2 <= 0.f) { v = 0.f; w = 0.f; }                                                      // vertex a
+    v = fminf(fmaxf(v, 0.f), 1.f);                                        // a valid convex combination whatever the rounding did
+    w = fminf(fmaxf(w, 0.f), 1.0f - v);
+    const float rx = apx - __builtin_fmaf(w, acx, v * abx), ry = apy - __builtin_fmaf(w, acy, v * aby),
+                rz = apz - __builtin_fmaf(w, acz, v * abz);
+    Foot o;
+    o.v = v; o.w = w;
+    o.d2 = __builtin_fmaf(rz, rz, __builtin_fmaf(ry, ry, rx * rx));
+    return o;
+}
+
+// One thread per (body, triangle): the triangle's record and bounding sphere for this step's vertices.  A triangle that is
+// not a target (a masked corner, or an index outside [0, n)) gets the centre (+inf, +inf, +inf): the sweep never tests it.
+__global__ __launch_bounds__(256) void surface_prep_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
+                                                          int nF, const unsigned char* __restrict__ v_mask, long mask_sb, int B,
+                                                          float* __restrict__ tri, f32x4* __restrict__ sphere) {
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)B * nF) return;
+    const int b = (int)(t / nF), f = (int)(t - (long)b * nF);
+    const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
+    bool ok = (unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n;
+    if (ok && v_mask) {
+        const unsigned char* mb = v_mask + (long)b * mask_sb;
+        ok = mb[i0] != 0 && mb[i1] != 0 && mb[i2] != 0;
+    }
+    float* T = tri + t * TRI;
+    if (!ok) {
+#pragma unroll
+        for (int k = 0; k < TRI; ++k) T[k] = 0.f;
+        sphere[t] = f32x4{INFINITY, INFINITY, INFINITY, 0.f};
+        return;
+    }
+    const float* xb = x + (long)b * x_sb;
+    const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
+    const float bx = xb[3L * i1], by = xb[3L * i1 + 1], bz = xb[3L * i1 + 2];
+    const float cx = xb[3L * i2], cy = xb[3L * i2 + 1], cz = xb[3L * i2 + 2];
+    const float abx = bx - ax, aby = by - ay, abz = bz - az, acx = cx - ax, acy = cy - ay, acz = cz - az;
+    T[0] = ax; T[1] = ay; T[2] = az; T[3] = abx; T[4] = aby; T[5] = abz; T[6] = acx; T[7] = acy; T[8] = acz;
+    T[9] = dot3(abx, aby, abz, abx, aby, abz); T[10] = dot3(abx, aby, abz, acx, acy, acz); T[11] = dot3(acx, acy, acz, acx, acy, acz);
+    const float third = 1.0f / 3.0f;
+    float mx = ax + (abx + acx) * third, my = ay + (aby + acy) * third, mz = az + (abz + acz) * third;
+    const float ra = dot3(ax - mx, ay - my, az - mz, ax - mx, ay - my, az - mz);
+    const float rb = dot3(bx - mx, by - my, bz - mz, bx - mx, by - my, bz - mz);
+    const float rc = dot3(cx - mx, cy - my, cz - mz, cx - mx, cy - my, cz - mz);
+    float r = sqrtf(fmaxf(ra, fmaxf(rb, rc))) * MARGIN;
+    if (!(mx < INFINITY && mx > -INFINITY && my < INFINITY && my > -INFINITY && mz < INFINITY && mz > -INFINITY && r < INFINITY)) {
+        mx = my = mz = 0.f; r = INFINITY;                                 // overflow or NaN in the vertices: never culled
+    }
+    sphere[t] = f32x4{mx, my, mz, r};
+}
+
+struct SurfParams {
+    const float* q; long q_sb; int nq; const int32_t* q_count;
+    const float* tri; const f32x4* sphere; int nF;
+    const float* bound;
+    int tiles_per_chunk, chunks, cull;
+    unsigned long long* stats;
+};
+
+// grid (query tile, triangle chunk, body).  The chunk's (d2, face) go to part_d2 / part_idx [B][chunks][nq] for
+// surface_finish_kernel.  Triangles are visited in ascending order and a candidate replaces the best only when strictly
+// closer: the lowest face wins an exact tie.  A triangle is skipped for a query when
+//     d2(s, centre) > (rb + r)^2,      rb = MARGIN * sqrt(the query's bound),  r = MARGIN * the sphere's radius
+// where the bound is the smaller of the caller's upper bound and the best distance found so far (cull = 0: rb = +inf, nothing is
+// skipped).  The region test runs, for the lanes that need it, when any lane of the wave does.
+template <bool STATS>
+__global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, int32_t* __restrict__ part_idx, float* __restrict__ part_d2) {
+    __shared__ __attribute__((aligned(16))) float sx[2][FT];
+    __shared__ __attribute__((aligned(16))) float sy[2][FT];
+    __shared__ __attribute__((aligned(16))) float sz[2][FT];
+    __shared__ __attribute__((aligned(16))) float sr[2][FT];
+    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nqb = clamp_count(p.q_count, b, p.nq);
+    const int j0 = blockIdx.x * QT;
+    if (j0 >= nqb) return;                                               // uniform: no query of this tile is live (finish writes them)
+    const float* qb = p.q + (long)b * p.q_sb;
+    const f32x4* sph = p.sphere + (long)b * p.nF;
+    const float* trib = p.tri + (long)b * p.nF * TRI;
+    float qx[QPT], qy[QPT], qz[QPT], best[QPT], rb[QPT];
+    int bi[QPT];
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + wv * (64 * QPT) + k * 64 + lane;
+        const bool live = j < nqb;
+        // a dead query sits at +inf with a bound of 0: infinitely far from every sphere, it never asks for a region test
+        qx[k] = live ? qb[3L * j] : INFINITY; qy[k] = live ? qb[3L * j + 1] : INFINITY; qz[k] = live ? qb[3L * j + 2] : INFINITY;
+        best[k] = INFINITY; bi[k] = -1;
+        const float bnd = (p.cull && p.bound && live) ? p.bound[(long)b * p.nq + j] : INFINITY;
+        rb[k] = live ? sqrtf(fmaxf(bnd, 0.f)) * MARGIN : 0.f;
+        if (!(rb[k] == rb[k])) rb[k] = INFINITY;                         // NaN bound: no bound
+    }
+    const int tiles = (p.nF + FT - 1) / FT;
+    const int tile_lo = c * p.tiles_per_chunk;
+    const int tile_hi = min(tile_lo + p.tiles_per_chunk, tiles);
+    unsigned long long tested = 0;                                       // STATS only: the shipped instantiation has no counter
+    if (tile_lo < tile_hi) {                                             // uniform
+        f32x4 ld;
+        auto fetch = [&](int tile) {
+            const int f = tile * FT + tid;
+            ld = f < p.nF ? sph[f] : f32x4{INFINITY, INFINITY, INFINITY, 0.f};
+        };
+        fetch(tile_lo);
+        sx[0][tid] = ld[0]; sy[0][tid] = ld[1]; sz[0][tid] = ld[2]; sr[0][tid] = ld[3];
+        __syncthreads();
+        for (int tile = tile_lo; tile < tile_hi; ++tile) {
+            const int cur = (tile - tile_lo) & 1;
+            const bool more = tile + 1 < tile_hi;
+            if (more) fetch(tile + 1);                                   // in flight under this tile's arithmetic
+            const int base = tile * FT;
+            for (int u = 0; u < FT; u += 4) {
+                const f32x4 X = *reinterpret_cast<const f32x4*>(&sx[cur][u]);
+                const f32x4 Y = *reinterpret_cast<const f32x4*>(&sy[cur][u]);
+                const f32x4 Z = *reinterpret_cast<const f32x4*>(&sz[cur][u]);
+                const f32x4 R = *reinterpret_cast<const f32x4*>(&sr[cur][u]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    bool need[QPT];
+                    bool any = false;
+#pragma unroll
+                    for (int k = 0; k < QPT; ++k) {
+                        const float dx = qx[k] - X[e], dy = qy[k] - Y[e], dz = qz[k] - Z[e];
+                        const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                        const float t = rb[k] + R[e];
+                        need[k] = !(d > t * t);                          // written so that a NaN asks for the test
+                        any = any || need[k];
+                    }
+                    if (X[e] < INFINITY && __ballot(any) != 0ull) {      // uniform: the triangle is a target and some lane needs it
+                        const int f = base + u + e;
+                        const float* T = trib + (long)f * TRI;
+#pragma unroll
+                        for (int k = 0; k < QPT; ++k) {
+                            if (need[k]) {
+                                const Foot ft = surf_foot(T, qx[k], qy[k], qz[k]);
+                                if (ft.d2 < best[k]) {
+                                    best[k] = ft.d2; bi[k] = f;
+                                    if (p.cull) rb[k] = fminf(rb[k], sqrtf(ft.d2) * MARGIN);
+                                }
+                                if (STATS) ++tested;
+                            }
+                        }
+                    }
+                }
+            }
+            if (more) { sx[cur ^ 1][tid] = ld[0]; sy[cur ^ 1][tid] = ld[1]; sz[cur ^ 1][tid] = ld[2]; sr[cur ^ 1][tid] = ld[3]; }
+            __syncthreads();                                             // one barrier per tile: the other buffer was last read before the previous one
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + wv * (64 * QPT) + k * 64 + lane;
+        if (j < nqb) {
+            const long o = ((long)b * p.chunks + c) * p.nq + j;
+            part_idx[o] = bi[k]; part_d2[o] = best[k];
+        }
+    }
+    if (STATS) {                                                         // diagnostic instantiation only (tools/bench_surface.py)
+        for (int o = 32; o > 0; o >>= 1) tested += __shfl_xor(tested, o, 64);
+        if (lane == 0) atomicAdd(p.stats, tested);
+    }
+}
+
+// One thread per (body, query).  (d2, face) = lexicographic minimum over the chunks: chunk c holds lower faces than chunk
+// c + 1, so walking the chunks in order with a strict `<` is that minimum.  With the cull on, the result is the unculled
+// sweep's whenever it does not exceed MARGIN times the caller's bound (every skipped triangle is farther than that, or than a
+// distance found; the factor lets a foot point ON the nearest vertex pass, whose distance differs from the vertex search's by
+// rounding).  When it does - the bound was no upper bound of the fp32 surface distance, which a vertex mask can cause - the
+// query is swept again here without a bound.  Then the weights of the chosen face are formed once more.
+__global__ __launch_bounds__(256) void surface_finish_kernel(const SurfParams p, int B, const int32_t* __restrict__ part_idx,
+                                                            const float* __restrict__ part_d2, int32_t* __restrict__ face,
+                                                            float* __restrict__ d2, float* __restrict__ uv) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)B * p.nq) return;
+    const int b = (int)(t / p.nq), j = (int)(t - (long)b * p.nq);
+    if (j >= clamp_count(p.q_count, b, p.nq)) { face[t] = -1; d2[t] = 0.f; uv[2 * t] = 0.f; uv[2 * t + 1] = 0.f; return; }
+    float best = INFINITY;
+    int bi = -1;
+    for (int c = 0; c < p.chunks; ++c) {
+        const long o = ((long)b * p.chunks + c) * p.nq + j;
+        const float d = part_d2[o];
+        if (d < best) { best = d; bi = part_idx[o]; }
+    }
+    const float* qb = p.q + (long)b * p.q_sb;
+    const float sx = qb[3L * j], sy = qb[3L * j + 1], sz = qb[3L * j + 2];
+    const float* trib = p.tri + (long)b * p.nF * TRI;
+    if (p.cull) {
+        const float bnd = p.bound ? p.bound[t] : INFINITY;
+        if (bi < 0 || !(best <= bnd * MARGIN)) {                          // a skipped triangle is farther than MARGIN^2 * bnd
+            const f32x4* sph = p.sphere + (long)b * p.nF;
+            best = INFINITY; bi = -1;
+            if (p.stats) atomicAdd(p.stats + 1, 1ull);                   // diagnostic: points that took this path
+            for (int f = 0; f < p.nF; ++f) {
+                if (!(sph[f][0] < INFINITY)) continue;
+                const Foot ft = surf_foot(trib + (long)f * TRI, sx, sy, sz);
+                if (ft.d2 < best) { best = ft.d2; bi = f; }
+            }
+        }
+    }
+    float v = 0.f, w = 0.f;
+    if (bi >= 0) {
+        const Foot ft = surf_foot(trib + (long)bi * TRI, sx, sy, sz);
+        v = ft.v; w = ft.w;
+    }
+    face[t] = bi; d2[t] = best; uv[2 * t] = v; uv[2 * t + 1] = w;
+}
+
+// Gradient w.r.t. the model points, gather form, the discipline of chamfer_bwd_kernel.  grid (row tile of 256, body), thread =
+// one row i.  The recorded faces are swept in tiles of 256 scan points: thread t looks at entry j = base + t and keeps the
+// corners of its face that lie in this workgroup's row range; the kept (row, weight, q - s) entries are compacted into LDS in
+// ascending j and corner order 0, 1, 2 within a j (wave ballots, waves in order), and every thread then walks that short list
+// and adds the terms whose row is its own - the order the header states, whatever the scheduling.
+__global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restrict__ x, long x_sb, int rows, int n,
+                                                         const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
+                                                         const int32_t* __restrict__ faces, int nF, const int32_t* __restrict__ face,
+                                                         const float* __restrict__ d2, const float* __restrict__ uv,
+                                                         const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms,
+                                                         const unsigned char* __restrict__ v_mask, long mask_sb,
+                                                         const int32_t* __restrict__ counts, float tau2, float w_ms,
+                                                         const float* __restrict__ gL, float* __restrict__ g_x) {
+#pragma clang fp contract(off)
+    __shared__ int wave_n[4];
+    __shared__ int list_r[768];
+    __shared__ float list_l[768];
+    __shared__ float list_x[768];
+    __shared__ float list_y[768];
+    __shared__ float list_z[768];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int i_lo = blockIdx.x * 256, i = i_lo + tid;
+    const int m = min(clamp_count(s_count, b, M), counts[2 * b]);
+    const int n_act = counts[2 * b + 1];
+    const float* xb = x + (long)b * x_sb;
+    const float* sb = s + (long)b * s_sb;
+    const bool mine = i < n;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int base = 0; base < m; base += 256) {                         // m is uniform over the workgroup
+        const int j = base + tid;
+        int r[3] = {-1, -1, -1};
+        float l[3] = {0.f, 0.f, 0.f}, ex = 0.f, ey = 0.f, ez = 0.f;
+        if (j < m) {
+            const long o = (long)b * M + j;
+            const int f = face[o];
+            if (f >= 0 && f < nF && d2[o] < tau2) {
+                const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
+                const bool ok = (unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n;
+                const bool h0 = (unsigned)(i0 - i_lo) < 256u, h1 = (unsigned)(i1 - i_lo) < 256u, h2 = (unsigned)(i2 - i_lo) < 256u;
+                if (ok && (h0 || h1 || h2)) {
+                    const float v = uv[2 * o], w = uv[2 * o + 1];
+                    const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
+                    const float abx = xb[3L * i1] - ax, aby = xb[3L * i1 + 1] - ay, abz = xb[3L * i1 + 2] - az;
+                    const float acx = xb[3L * i2] - ax, acy = xb[3L * i2 + 1] - ay, acz = xb[3L * i2 + 2] - az;
+                    const float apx = sb[3L * j] - ax, apy = sb[3L * j + 1] - ay, apz = sb[3L * j + 2] - az;
+                    ex = __builtin_fmaf(w, acx, v * abx) - apx;          // q - s, the exact negative of the forward pass's residual
+                    ey = __builtin_fmaf(w, acy, v * aby) - apy;
+                    ez = __builtin_fmaf(w, acz, v * abz) - apz;
+                    l[0] = (1.0f - v) - w; l[1] = v; l[2] = w;
+                    r[0] = h0 ? i0 - i_lo : -1; r[1] = h1 ? i1 - i_lo : -1; r[2] = h2 ? i2 - i_lo : -1;
+                }
+            }
+        }
+        const unsigned long long b0 = __ballot(r[0] >= 0), b1 = __ballot(r[1] >= 0), b2 = __ballot(r[2] >= 0);
+        if (lane == 0) wave_n[wv] = __popcll(b0) + __popcll(b1) + __popcll(b2);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int w_ = 0; w_ < 4; ++w_) { off += w_ < wv ? wave_n[w_] : 0; total += wave_n[w_]; }
+        int pos = off + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (r[k] >= 0) { list_r[pos] = r[k]; list_l[pos] = l[k]; list_x[pos] = ex; list_y[pos] = ey; list_z[pos] = ez; ++pos; }
+        __syncthreads();
+        for (int k = 0; k < total; ++k)
+            if (list_r[k] == tid && mine) {
+                const float lk = list_l[k];
+                a0 = a0 + lk * list_x[k]; a1 = a1 + lk * list_y[k]; a2 = a2 + lk * list_z[k];
+            }
+        __syncthreads();                                                 // the lists are rewritten by the next tile
+    }
+    if (i >= rows) return;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    const bool active = mine && !(v_mask && v_mask[(long)b * mask_sb + i] == 0);
+    if (active && m > 0) {
+        const float g = gL[b];
+        const float c1 = 2.f / (float)m;
+        g0 = c1 * a0; g1 = c1 * a1; g2 = c1 * a2;
+        if (idx_ms && w_ms > 0.f && n_act > 0) {
+            const int k = idx_ms[(long)b * rows + i];
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) {
+                const float c2 = w_ms * 2.f / (float)n_act;
+                const float xi0 = xb[3L * i], xi1 = xb[3L * i + 1], xi2 = xb[3L * i + 2];
+                g0 = g0 + c2 * (xi0 - sb[3L * k]); g1 = g1 + c2 * (xi1 - sb[3L * k + 1]); g2 = g2 + c2 * (xi2 - sb[3L * k + 2]);
+            }
+        }
+        g0 *= g; g1 *= g; g2 *= g;
+    }
+    float* o = g_x + ((long)b * rows + i) * 3;
+    o[0] = g0; o[1] = g1; o[2] = g2;
+}
+
+int sf_tiles(int nF) { return (nF + FT - 1) / FT; }
+
+// the split actually run for a request of `chunks` (0 = automatic: fill the chip): whole tiles per chunk, no empty chunk
+int sf_resolve_chunks(int B, int nq, int nF, int chunks, int* tiles_per_chunk) {
+    const int tiles = sf_tiles(nF) > 0 ? sf_tiles(nF) : 1;
+    long c = chunks;
+    if (c <= 0) {
+        const long wgs = (long)sh_cdiv(nq > 0 ? nq : 1, QT) * (B > 0 ? B : 1);
+        c = (WG_SLOTS + wgs - 1) / wgs;
+    }
+    if (c > tiles) c = tiles;
+    if (c < 1) c = 1;
+    const int tpc = sh_cdiv(tiles, (int)c);
+    *tiles_per_chunk = tpc;
+    return sh_cdiv(tiles, tpc);
+}
+
+size_t sf_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+int sh_nearest_surface_chunks(int B, int nq, int nF) {
+    int tpc;
+    return sf_resolve_chunks(B, nq, nF, 0, &tpc);
+}
+
+size_t sh_nearest_surface_workspace(int B, int nq, int nF, int chunks) {
+    if (B <= 0 || nq <= 0 || nF < 0 || chunks < 0) return 0;
+    int tpc;
+    const int c = sf_resolve_chunks(B, nq, nF, chunks, &tpc);
+    return sf_align16((size_t)B * nF * sizeof(f32x4)) + sf_align16((size_t)B * nF * TRI * sizeof(float)) +
+           (size_t)B * c * nq * (sizeof(float) + sizeof(int32_t));
+}
+
+int sh_nearest_surface(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* x, int64_t x_sb, int n,
+                       const int32_t* faces, int nF, const uint8_t* v_mask, int64_t mask_sb, const float* bound, int B, int chunks,
+                       int cull, int32_t* face, float* d2, float* uv, uint64_t* stats, void* workspace, size_t workspace_bytes,
+                       sh_stream_t stream) {
+    SH_REQUIRE(q && x && face && d2 && uv && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_nearest_surface: null pointer");
+    SH_REQUIRE(B >= 0 && nq >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
+               "sh_nearest_surface: negative size (B %d, nq %d, n %d, nF %d, chunks %d)", B, nq, n, nF, chunks);
+    if (B == 0 || nq == 0) return SH_OK;
+    SH_REQUIRE(q_sb >= 3L * nq && x_sb >= 3L * n && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_nearest_surface: batch stride shorter than a body (q_sb %ld, x_sb %ld, mask_sb %ld)", (long)q_sb, (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && (long)B * nF < (1L << 27), SH_ERR_UNSUPPORTED,
+               "sh_nearest_surface: B, B*nq or B*nF too large");
+    SurfParams p{};
+    p.chunks = sf_resolve_chunks(B, nq, nF, chunks, &p.tiles_per_chunk);
+    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_surface: %d triangle chunks", p.chunks);
+    const size_t sph_bytes = sf_align16((size_t)B * nF * sizeof(f32x4)), tri_bytes = sf_align16((size_t)B * nF * TRI * sizeof(float));
+    const size_t need = sph_bytes + tri_bytes + (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
+    SH_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, SH_ERR_WORKSPACE,
+               "sh_nearest_surface: workspace too small or not 16-byte aligned (%zu bytes needed for %d chunks)", need, p.chunks);
+    char* wsb = static_cast<char*>(workspace);
+    f32x4* sphere = reinterpret_cast<f32x4*>(wsb);
+    float* tri = reinterpret_cast<float*>(wsb + sph_bytes);
+    float* part_d2 = reinterpret_cast<float*>(wsb + sph_bytes + tri_bytes);
+    int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
+    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
+    p.tri = tri; p.sphere = sphere; p.nF = nF; p.bound = bound; p.cull = cull ? 1 : 0;
+    p.stats = reinterpret_cast<unsigned long long*>(stats);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (nF > 0) {
+        ShProfScope ps(st, "surface_prep_kernel|B=%d nF=%d", B, nF);
+        SH_LAUNCH_PS(ps, surface_prep_kernel, dim3((unsigned)(((long)B * nF + 255) / 256)), dim3(256), 0, st, x, (long)x_sb, n, faces, nF, v_mask,
+                     (long)mask_sb, B, tri, sphere);
+    }
+    {
+        ShProfScope ps(st, "surface_search_kernel|B=%d nq=%d nF=%d chunks=%d cull=%d", B, nq, nF, p.chunks, p.cull);
+        const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
+        if (p.stats) SH_LAUNCH_PS(ps, surface_search_kernel<true>, grid, dim3(NT), 0, st, p, part_idx, part_d2);
+        else SH_LAUNCH_PS(ps, surface_search_kernel<false>, grid, dim3(NT), 0, st, p, part_idx, part_d2);
+    }
+    {
+        ShProfScope ps(st, "surface_finish_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
+        SH_LAUNCH_PS(ps, surface_finish_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, p, B, part_idx, part_d2, face, d2,
+                     uv);
+    }
+    SH_CHECK_LAUNCH("nearest_surface");
+    return SH_OK;
+}
+
+int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
+                           const int32_t* faces, int nF, const int32_t* face, const float* d2, const float* uv, const int32_t* idx_ms,
+                           const float* d2_ms, const uint8_t* v_mask, int64_t mask_sb, const int32_t* counts, float tau2, float w_ms,
+                           const float* gL, int B, float* g_x, sh_stream_t stream) {
+    SH_REQUIRE(x && s && face && d2 && uv && counts && gL && g_x && (faces || nF == 0), SH_ERR_INVALID_ARG,
+               "sh_chamfer_surface_bwd: null pointer");
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows && nF >= 0, SH_ERR_INVALID_ARG,
+               "sh_chamfer_surface_bwd: bad size (B %d, M %d, rows %d, n %d, nF %d)", B, M, rows, n, nF);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_chamfer_surface_bwd: w_ms and tau2 must be >= 0 (and not NaN)");
+    SH_REQUIRE((idx_ms != nullptr) == (d2_ms != nullptr), SH_ERR_INVALID_ARG, "sh_chamfer_surface_bwd: idx_ms and d2_ms come together");
+    if (B == 0 || rows == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * rows && s_sb >= 3L * M && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_chamfer_surface_bwd: batch stride shorter than a body (x_sb %ld, s_sb %ld, mask_sb %ld)", (long)x_sb, (long)s_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * rows < (1L << 30), SH_ERR_UNSUPPORTED, "sh_chamfer_surface_bwd: B or B*rows too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "surface_bwd_kernel|B=%d M=%d rows=%d", B, M, rows);
+    SH_LAUNCH_PS(ps, surface_bwd_kernel, dim3((unsigned)sh_cdiv(rows, 256), (unsigned)B), dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M,
+                 s_count, faces, nF, face, d2, uv, w_ms > 0.f ? idx_ms : nullptr, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, gL, g_x);
+    SH_CHECK_LAUNCH("chamfer_surface_bwd");
+    return SH_OK;
+}
+
+}  // extern "C"

@@ -478,6 +478,48 @@ def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb,
     return g
 
 
+def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunks=0, cull=True, out=None, stats=None):
+    """sh_nearest_surface: q [B, *, 3] scan points, x [B, *, 3] model points of which the first n are vertices, faces int32 HIP
+    [nF, 3] (one table for the batch) -> (face int32 [B, nq], d2 fp32 [B, nq], uv fp32 [B, nq, 2]).  bound [B, nq]: an upper
+    bound of each answer (the squared distance to the nearest vertex), None = none; cull=False runs every pair through the region
+    test (the yardstick: same bits).  stats: None or a zeroed int64 HIP tensor [2] that receives (region tests run, points swept again without a bound)."""
+    B, nq, q_sb = _points(q, "nearest_surface")
+    Bx, x_rows, x_sb = _points(x, "nearest_surface")
+    if Bx != B:
+        raise ValueError("nearest_surface: %d scan bodies, %d model bodies" % (B, Bx))
+    n = int(n)
+    if not 0 <= n <= x_rows:
+        raise ValueError("nearest_surface: n = %d exceeds the model's %d rows" % (n, x_rows))
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.nearest_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
+    nF = faces.shape[0]
+    q_count = _count_arg(q_count, B, q.device)
+    mask, mask_sb = _mask_arg(v_mask, B, n, q.device)
+    if bound is not None and not (bound.is_cuda and bound.dtype == torch.float32 and bound.is_contiguous() and tuple(bound.shape) == (B, nq)):
+        raise RuntimeError("semantichuman_amd.nearest_surface: bound must be a contiguous fp32 HIP tensor [%d, %d]" % (B, nq))
+    lib = _lib.load()
+    face, d2, uv = out if out is not None else (torch.empty((B, nq), dtype=torch.int32, device=q.device),
+                                                torch.empty((B, nq), dtype=torch.float32, device=q.device),
+                                                torch.empty((B, nq, 2), dtype=torch.float32, device=q.device))
+    nbytes = lib.sh_nearest_surface_workspace(B, nq, nF, chunks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    check(lib.sh_nearest_surface(ptr(q), q_sb, nq, ptr(q_count), ptr(x), x_sb, n, ptr(faces), nF, ptr(mask), mask_sb, ptr(bound), B, chunks,
+                                 1 if cull else 0, ptr(face), ptr(d2), ptr(uv), ptr(stats), ptr(ws), nbytes, stream_ptr()), "sh_nearest_surface")
+    return face, d2, uv
+
+
+def chamfer_surface_bwd(x, n, s, s_count, faces, face, d2, uv, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
+    """sh_chamfer_surface_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
+    B, rows, x_sb = _points(x, "chamfer_surface_bwd")
+    _, M, s_sb = _points(s, "chamfer_surface_bwd")
+    g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_chamfer_surface_bwd(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), ptr(faces), faces.shape[0], ptr(face), ptr(d2),
+                                             ptr(uv), ptr(idx_ms), ptr(d2_ms), ptr(v_mask), mask_sb, ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g),
+                                             stream_ptr()), "sh_chamfer_surface_bwd")
+    return g
+
+
 ALIGN_MODES = {"translation": 0, "rigid": 1, "similarity": 2}   # enum sh_align_mode
 ALIGN_PARTIAL, ALIGN_MOMENTS = 19, 20                           # SH_ALIGN_PARTIAL, SH_ALIGN_MOMENTS
 

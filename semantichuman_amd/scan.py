@@ -2,15 +2,19 @@
 
   * `ScanBatch(clouds, device)`   ragged clouds -> one resident padded [B, Mmax, 3] tensor + counts (host packing, numpy)
   * `nearest(q, t, ...)`          -> sh_nearest_points: index and squared distance of each query's nearest target
+  * `FaceTable`, `nearest_surface(q, x, faces, ...)`, `closest_points(...)`  -> sh_nearest_surface: the exact closest point of the
+                                     model's triangles to each scan point (face, squared distance, barycentric weights)
   * `chamfer(x_hat, scans, ...)`  -> sh_nearest_points (one or both directions) + sh_chamfer_fwd / sh_chamfer_bwd, differentiable
-                                     w.r.t. x_hat through the recorded indices
+                                     w.r.t. x_hat through the recorded indices; with `faces=` the scan -> model term is measured
+                                     to the surface (sh_nearest_surface, sh_chamfer_surface_bwd)
   * `Pose`, `moment_pose(...)`, `align(x, scans, ...)`  scan frame -> model frame: batched similarity ICP on the same matches
                                      (sh_transform_points, sh_align_moments, sh_align_solve)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
 model's normalised frame; `align` (and editing.register_scan, which alternates it with the fit) brings a scan there by a
-translation, a rigid motion or a similarity.  There is no point-to-triangle distance and no file reader.
+translation, a rigid motion or a similarity.  The alignment works on vertex pairs (no point-to-surface ICP); there is no file
+reader.
 The search, the loss and the alignment have no CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
@@ -45,12 +49,42 @@ def pack_clouds(clouds):
     return pts, counts
 
 
+def morton_order(points, bits=10):
+    """The permutation that sorts an [m, 3] cloud along the Morton (Z-order) curve of its own bounding box, `bits` bits per axis;
+    a stable sort, so equal codes keep their order.  Host side, numpy only."""
+    p = np.asarray(points, dtype=np.float64)
+    if p.shape[0] == 0:
+        return np.zeros(0, dtype=np.int64)
+    lo, hi = p.min(0), p.max(0)
+    cell = np.where(hi > lo, hi - lo, 1.0)
+    g = np.minimum(((p - lo) / cell * (1 << bits)).astype(np.int64), (1 << bits) - 1)
+    code = np.zeros(p.shape[0], dtype=np.int64)
+    for k in range(bits):
+        for a in range(3):
+            code |= ((g[:, a] >> k) & 1) << (3 * k + a)
+    return np.argsort(code, kind="stable")
+
+
 class ScanBatch:
     """B point clouds resident on the device: `points` fp32 [B, Mmax, 3] (rows >= counts[b] are zero padding the kernels never
-    read as points), `counts` int32 [B].  `host_counts` keeps the counts on the host."""
+    read as points), `counts` int32 [B].  `host_counts` keeps the counts on the host.
 
-    def __init__(self, clouds, device):
+    order=None keeps every cloud's points in the order given.  order="morton" sorts each cloud along a space-filling curve at
+    packing time (`morton_order`), so that points next to each other in memory are next to each other in space - what the
+    surface search's cull lives on.  The permutation is kept on the host as `perm`, int64 [B, Mmax]: points[b, k] is the given
+    cloud's point perm[b, k] (k < counts[b]; -1 in the padding); `perm` is None when nothing was sorted.  A Chamfer value does
+    not depend on the order beyond the rounding of its sum."""
+
+    def __init__(self, clouds, device, order=None):
+        if order not in (None, "morton"):
+            raise ValueError("ScanBatch: order must be None or 'morton'")
         pts, counts = pack_clouds(clouds)
+        self.perm = None
+        if order == "morton":
+            self.perm = np.full(pts.shape[:2], -1, dtype=np.int64)
+            for b, m in enumerate(counts):
+                self.perm[b, :m] = morton_order(pts[b, :m])
+                pts[b, :m] = pts[b, :m][self.perm[b, :m]]
         dev = torch.device(device)
         self.host_counts = counts
         self.points = torch.from_numpy(pts).to(dev)
@@ -62,6 +96,7 @@ class ScanBatch:
     def select(self, sl):
         """The bodies `sl` (a slice) as a ScanBatch sharing this one's memory."""
         out = ScanBatch.__new__(ScanBatch)
+        out.perm = None if self.perm is None else self.perm[sl]
         out.host_counts = self.host_counts[sl]
         out.points = self.points[sl]
         out.counts = self.counts[sl].contiguous()
@@ -75,6 +110,96 @@ def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
     idx -1, d2 0.  chunks: how many ranges the targets are split into (0 = chosen by the library; every split gives the same
     bits).  Not differentiable."""
     return ops.nearest_points(q.detach(), t.detach(), q_count, t_count, t_mask, chunks=chunks)
+
+
+class FaceTable:
+    """The model's triangles for the surface search: `faces` int32 [nF, 3] on the device, one table for every body of a batch;
+    `n` is the number of model vertices the indices may address (the decoder's dummy row, row n, is not among them).
+    ValueError unless the table is an integer array [nF, 3] with 0 <= index < n and no face that names a vertex twice."""
+
+    def __init__(self, faces, n, device):
+        f = faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)
+        if f.dtype.kind not in "iu":
+            raise ValueError("FaceTable: faces must be integers, got %s" % f.dtype)
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("FaceTable: faces must be [nF, 3], got %s" % (f.shape,))
+        n = int(n)
+        f = f.astype(np.int64)
+        if f.size and (f.min() < 0 or f.max() >= n):
+            raise ValueError("FaceTable: face indices must lie in [0, %d) (the dummy row is not a vertex); got [%d, %d]"
+                             % (n, f.min(), f.max()))
+        if ((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])).any():
+            raise ValueError("FaceTable: a face names the same vertex twice")
+        self.n = n
+        self.faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(torch.device(device))
+
+    def __len__(self):
+        return self.faces.shape[0]
+
+
+def _face_table(faces, n, device):
+    if isinstance(faces, FaceTable):
+        if faces.n > n:
+            raise ValueError("face table made for %d vertices, the model has %d" % (faces.n, n))
+        return faces
+    return FaceTable(faces, n, device)
+
+
+def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=True, n=None):
+    """For every scan point q[b, j] the closest point of body b's triangles: (face int32 [B, nq], d2 fp32 [B, nq], uv fp32
+    [B, nq, 2]), exact in the fp32 expression of sh_kernels.h - the lexicographic minimum of (d2, face) over all target
+    triangles, uv the barycentric weights (l1, l2) of the foot point on that face (l0 = 1 - l1 - l2).  x [B, rows, 3]; faces: a
+    FaceTable (its n says how many leading rows of x are vertices) or an integer array [nF, 3], validated against n - as in
+    `chamfer`, n=None means rows - 1 (the decoder's dummy row is no vertex); pass n=rows for a bare vertex tensor.  vertex_mask [n]
+    or [B, n]: a triangle with a masked corner is no target.  No target: face -1, d2 +inf; points beyond q_count: face -1, d2 0.
+    cull=True starts from the nearest vertex (one sh_nearest_points search) and tests only the triangles whose bounding sphere
+    reaches inside the best distance so far; cull=False tests every pair - same bits, many times the work.  chunks: the split of
+    the triangle range (0 = chosen by the library; every split gives the same bits).  Not differentiable."""
+    q, x = q.detach(), x.detach()
+    rows = ops._points(x, "scan.nearest_surface")[1]
+    ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
+    bound = None
+    if cull:
+        bound = ops.nearest_points(q, x, q_count=q_count, t_mask=vertex_mask, nt=ft.n)[1]
+    return ops.nearest_surface(q, x, ft.faces, ft.n, q_count, vertex_mask, bound, chunks=chunks, cull=cull)
+
+
+def closest_points(x, faces, face, uv):
+    """The foot points [B, M, 3] that `nearest_surface` found, rebuilt from (face, uv) in plain torch: a + l1 (b - a) + l2 (c - a)
+    on the face's corners; rows with face -1 give zeros.  Differentiable w.r.t. x (the weights are constants)."""
+    f = faces.faces if isinstance(faces, FaceTable) else torch.as_tensor(faces, device=x.device)
+    B = x.shape[0]
+    corners = f.long()[face.clamp_min(0).long()]                            # [B, M, 3]
+    ar = torch.arange(B, device=x.device)[:, None]
+    a, b, c = (x[ar, corners[:, :, k]] for k in range(3))
+    p = a + uv[:, :, 0:1] * (b - a) + uv[:, :, 1:2] * (c - a)
+    return torch.where((face >= 0)[:, :, None], p, torch.zeros_like(p))
+
+
+class _ChamferSurface(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, scans, faces, n, v_mask, mask_sb, tau2, w_ms, matches=None):
+        s, cnt = scans.points, scans.counts
+        rows = x.shape[1]
+        idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)    # the vertex search: the bound, and `matches`
+        face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, d2_v)
+        idx_ms = d2_ms = None
+        if w_ms > 0.0:
+            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt)
+        loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
+        ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
+        ctx.save_for_backward(x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts)
+        if matches is not None:
+            matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_v, idx_ms=idx_ms,
+                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gL):
+        x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts = ctx.saved_tensors
+        g = ops.chamfer_surface_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, faces, face, d2_sm, uv, idx_ms, d2_ms, ctx.v_mask,
+                                    ctx.mask_sb, counts, ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
+        return g, None, None, None, None, None, None, None, None
 
 
 class _Chamfer(torch.autograd.Function):
@@ -102,7 +227,7 @@ class _Chamfer(torch.autograd.Function):
         return g, None, None, None, None, None, None, None
 
 
-def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None):
+def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -114,7 +239,14 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     takes no part (not a target, no term of its own).  trunc: distances beyond it are cut to it and stop pulling (None: none).
     w_model_to_scan = 0 skips the model -> scan search altogether - the setting for a partial scan.  The gradient flows through
     the nearest indices found in the forward pass; the scan takes none.  matches: a dict that receives what the forward pass
-    found (indices, distances, the arguments they belong to) for `pose_update`; None (the default) records nothing."""
+    found (indices, distances, the arguments they belong to) for `pose_update`; None (the default) records nothing.
+
+    faces: None (the default: everything above, bit for bit), or a FaceTable / integer array [nF, 3] of the model's triangles.
+    Then the scan -> model term is the squared distance to the closest point of the SURFACE (`nearest_surface`), nn_x(s_j) being
+    that point, and its gradient reaches the three corners of the face with the foot point's barycentric weights.  The model ->
+    scan term (vertex to scan point), trunc, vertex_mask (a triangle with a masked corner is no target) and n keep their meaning.
+    `matches` receives what it receives without faces - the VERTEX matches, which were computed for the search's bound - plus
+    `face`, `uv` and `d2_surface`; `pose_update` and `align` go on working on the vertex pairs."""
     if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
         raise RuntimeError("semantichuman_amd.scan.chamfer needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
                            % getattr(x_hat, "device", type(x_hat)))
@@ -133,6 +265,8 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
         raise ValueError("chamfer: trunc must be > 0")
     tau2 = math.inf if trunc is None else float(trunc) ** 2
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
+    if faces is not None:
+        return _ChamferSurface.apply(x_hat, scans, _face_table(faces, n, x_hat.device).faces, n, v_mask, mask_sb, tau2, w, matches)
     return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches)
 
 
@@ -189,6 +323,7 @@ class Pose:
         beyond the counts zero) or fp32 HIP points [B, M, 3] with optional live counts [B] (-> tensor)."""
         if isinstance(points, ScanBatch):
             out = ScanBatch.__new__(ScanBatch)
+            out.perm = getattr(points, "perm", None)
             out.host_counts, out.counts = points.host_counts, points.counts
             out.points = ops.transform_points(points.points, points.counts, self.packed)
             return out
