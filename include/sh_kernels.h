@@ -626,6 +626,40 @@ SH_API int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n,
                                   sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Vertex normals: the two normal fields a scan match is gated by, and the gated search (no reference counterpart).  fp32,
+ * deterministic (no atomics of any kind), plain stores of every output element.
+ *
+ * sh_vertex_normals.  x: [B] bodies of model points, batch stride x_sb floats, the first n rows are vertices.  faces int32
+ * [nF][3], ONE table for the batch, indices in [0, n).  The vertex-to-face incidence is CSR: vf_ptr int32 [n + 1], vf_idx int32
+ * [3 nF]; vf_idx[vf_ptr[v] .. vf_ptr[v + 1]) are the faces that name vertex v, in ascending face order.  For vertex v, one
+ * thread walks its faces in that order; for face f with corners a = x[f0], b = x[f1], c = x[f2] in the face's own corner order,
+ * everything in fp32, every operation rounded on its own except the fused multiply-adds written out (no other contraction):
+ *     ab = b - a;  ac = c - a                                             (component-wise)
+ *     cx = fma(ab.y, ac.z, -(ab.z * ac.y));  cy = fma(ab.z, ac.x, -(ab.x * ac.z));  cz = fma(ab.x, ac.y, -(ab.y * ac.x))
+ *     s = fl(s + c)                          (component-wise, starting from 0: the cross products carry the area weights)
+ *     len2 = fma(s.z, s.z, fma(s.y, s.y, s.x * s.x))
+ *     normal[b][v] = s / sqrtf(len2)  (three divisions) when 0 < len2 < +inf, otherwise (0, 0, 0)
+ * The zero vector means "unknown": a vertex in no face, a fan of zero-area faces, an overflow.  normals: contiguous [B][n][3],
+ * every element stored; no vertex mask takes part (normals belong to the whole mesh).  A table entry outside its range (face
+ * >= nF, corner >= n) is passed over.  B == 0 or n == 0: SH_OK, nothing launched.
+ *
+ * sh_nearest_points_gated.  sh_nearest_points with a gate on the pair: qn [B] bodies of [*][3] query normals (stride qn_sb, row
+ * j belongs to query j), tn the same for the targets (tn_sb), cos_min the gate.  Target i is COMPATIBLE with query j iff
+ *     fma(qn.z, tn.z, fma(qn.y, tn.y, qn.x * tn.x)) >= cos_min            (fp32; a NaN compares false)
+ * A zero normal on either side gives 0: compatible only when cos_min <= 0.  The answer is the minimum of (d2, i) in
+ * lexicographic order over the allowed AND compatible targets, d2(i) the expression of sh_nearest_points, unchanged.  A live
+ * query with no such target gets idx = -1, d2 = +inf; queries j >= q_count[b] get idx = -1, d2 = 0.  cos_min = -inf opens the
+ * gate: the result is sh_nearest_points' bits (for normals free of NaN).  Chunks, workspace (sh_nearest_points_workspace) and
+ * the merge are those of sh_nearest_points; every split returns the same bits.  cos_min NaN: SH_ERR_INVALID_ARG.
+ */
+SH_API int sh_vertex_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const int32_t* vf_ptr,
+                             const int32_t* vf_idx, int B, float* normals, sh_stream_t stream);
+SH_API int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* qn, int64_t qn_sb,
+                                   const float* t, int64_t t_sb, int nt, const int32_t* t_count, const float* tn, int64_t tn_sb,
+                                   const uint8_t* t_mask, int64_t mask_sb, float cos_min, int B, int chunks, int32_t* idx, float* d2,
+                                   void* workspace, size_t workspace_bytes, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.

@@ -247,6 +247,150 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
     o[0] = g0; o[1] = g1; o[2] = g2;
 }
 
+// ------------------------------------------------------------------------------------------------ normals (header: "Vertex normals")
+struct NNGate {
+    const float* qn; long qn_sb;
+    const float* tn; long tn_sb;
+    float cos_min;
+};
+
+// nearest_search_kernel with the normal gate of the header: a target is a candidate only when the fp32 dot product of the two
+// normals reaches cos_min.  Same grid, tiles, chunks and outputs; six LDS arrays instead of three, six query registers instead of
+// three.  The gate is one compare and one select on the candidate distance (d = ok ? d : +inf), so a gated-out target loses
+// exactly as a masked one does and the (d2, index) minimum stays the lexicographic one.  Target normals of masked / out-of-count
+// targets enter as zeros: their distance is +inf whatever the gate says.
+__global__ __launch_bounds__(NT) void nearest_search_gated_kernel(const NNParams p, const NNGate g, int32_t* __restrict__ idx,
+                                                                 float* __restrict__ d2, int final) {
+    __shared__ __attribute__((aligned(16))) float sx[2][TT];
+    __shared__ __attribute__((aligned(16))) float sy[2][TT];
+    __shared__ __attribute__((aligned(16))) float sz[2][TT];
+    __shared__ __attribute__((aligned(16))) float su[2][TT];
+    __shared__ __attribute__((aligned(16))) float sv[2][TT];
+    __shared__ __attribute__((aligned(16))) float sw[2][TT];
+    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
+    const int nqb = clamp_count(p.q_count, b, p.nq), ntb = clamp_count(p.t_count, b, p.nt);
+    const int j0 = blockIdx.x * QT;
+    if (j0 >= nqb) {                                                     // uniform: no query of this tile is live
+        if (final)
+            for (int k = 0; k < QPT; ++k) {
+                const int j = j0 + k * NT + tid;
+                if (j < p.nq) { idx[(long)b * p.nq + j] = -1; d2[(long)b * p.nq + j] = 0.f; }
+            }
+        return;
+    }
+    const float* qb = p.q + (long)b * p.q_sb;
+    const float* tb = p.t + (long)b * p.t_sb;
+    const float* qnb = g.qn + (long)b * g.qn_sb;
+    const float* tnb = g.tn + (long)b * g.tn_sb;
+    const unsigned char* mb = p.mask ? p.mask + (long)b * p.mask_sb : nullptr;
+    const float cos_min = g.cos_min;
+    float qx[QPT], qy[QPT], qz[QPT], qu[QPT], qv[QPT], qw[QPT], best[QPT];
+    int bi[QPT];
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + k * NT + tid;
+        const bool live = j < nqb;
+        qx[k] = live ? qb[3L * j] : 0.f; qy[k] = live ? qb[3L * j + 1] : 0.f; qz[k] = live ? qb[3L * j + 2] : 0.f;
+        qu[k] = live ? qnb[3L * j] : 0.f; qv[k] = live ? qnb[3L * j + 1] : 0.f; qw[k] = live ? qnb[3L * j + 2] : 0.f;
+        best[k] = INFINITY; bi[k] = -1;
+    }
+    const int tiles = (ntb + TT - 1) / TT;
+    const int tile_lo = c * p.tiles_per_chunk;
+    const int tile_hi = min(tile_lo + p.tiles_per_chunk, tiles);
+    if (tile_lo < tile_hi) {                                             // uniform
+        float lx, ly, lz, lu, lv, lw;
+        auto fetch = [&](int tile) {
+            const int i = tile * TT + tid;
+            const bool ok = i < ntb && (!mb || mb[i] != 0);
+            lx = ok ? tb[3L * i] : INFINITY; ly = ok ? tb[3L * i + 1] : INFINITY; lz = ok ? tb[3L * i + 2] : INFINITY;
+            lu = ok ? tnb[3L * i] : 0.f; lv = ok ? tnb[3L * i + 1] : 0.f; lw = ok ? tnb[3L * i + 2] : 0.f;
+        };
+        fetch(tile_lo);
+        sx[0][tid] = lx; sy[0][tid] = ly; sz[0][tid] = lz; su[0][tid] = lu; sv[0][tid] = lv; sw[0][tid] = lw;
+        __syncthreads();
+        for (int tile = tile_lo; tile < tile_hi; ++tile) {
+            const int cur = (tile - tile_lo) & 1;
+            const bool more = tile + 1 < tile_hi;
+            if (more) fetch(tile + 1);                                   // in flight under this tile's arithmetic
+            const int base = tile * TT;
+#pragma unroll 2
+            for (int u = 0; u < TT; u += 4) {
+                const f32x4 X = *reinterpret_cast<const f32x4*>(&sx[cur][u]);
+                const f32x4 Y = *reinterpret_cast<const f32x4*>(&sy[cur][u]);
+                const f32x4 Z = *reinterpret_cast<const f32x4*>(&sz[cur][u]);
+                const f32x4 U = *reinterpret_cast<const f32x4*>(&su[cur][u]);
+                const f32x4 V = *reinterpret_cast<const f32x4*>(&sv[cur][u]);
+                const f32x4 W = *reinterpret_cast<const f32x4*>(&sw[cur][u]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int k = 0; k < QPT; ++k) {
+                        const float dot = __builtin_fmaf(qw[k], W[e], __builtin_fmaf(qv[k], V[e], qu[k] * U[e]));
+                        float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
+                        d = dot >= cos_min ? d : INFINITY;                // a NaN compares false: not compatible
+                        const bool closer = d < best[k];
+                        best[k] = closer ? d : best[k];
+                        bi[k] = closer ? base + u + e : bi[k];
+                    }
+                }
+            }
+            if (more) {
+                sx[cur ^ 1][tid] = lx; sy[cur ^ 1][tid] = ly; sz[cur ^ 1][tid] = lz;
+                su[cur ^ 1][tid] = lu; sv[cur ^ 1][tid] = lv; sw[cur ^ 1][tid] = lw;
+            }
+            __syncthreads();                                             // one barrier per tile, as in nearest_search_kernel
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < QPT; ++k) {
+        const int j = j0 + k * NT + tid;
+        if (j >= p.nq) continue;
+        if (final) {
+            const long o = (long)b * p.nq + j;
+            idx[o] = j < nqb ? bi[k] : -1;
+            d2[o] = j < nqb ? best[k] : 0.f;
+        } else if (j < nqb) {
+            const long o = ((long)b * p.chunks + c) * p.nq + j;
+            idx[o] = bi[k]; d2[o] = best[k];
+        }
+    }
+}
+
+// Area-weighted vertex normals, gather form: one thread per (body, vertex) walks the vertex's incident faces in the order of the
+// incidence table (ascending face) and sums the faces' cross products in fp32 - the header's expression, no contraction beyond
+// the fused multiply-adds written out, so the numpy transcription of tests/normals_ref.py rounds alike.  An entry of either table
+// outside its range is passed over (scan.FaceTable never builds one).
+__global__ __launch_bounds__(256) void vertex_normals_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
+                                                            int nF, const int32_t* __restrict__ vf_ptr, const int32_t* __restrict__ vf_idx,
+                                                            int B, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)B * n) return;
+    const int b = (int)(t / n), v = (int)(t - (long)b * n);
+    const float* xb = x + (long)b * x_sb;
+    int lo = vf_ptr[v], hi = vf_ptr[v + 1];
+    lo = max(lo, 0); hi = min(hi, 3 * nF);
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int e = lo; e < hi; ++e) {
+        const int f = vf_idx[e];
+        if ((unsigned)f >= (unsigned)nF) continue;
+        const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
+        if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
+        const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
+        const float abx = xb[3L * i1] - ax, aby = xb[3L * i1 + 1] - ay, abz = xb[3L * i1 + 2] - az;
+        const float acx = xb[3L * i2] - ax, acy = xb[3L * i2 + 1] - ay, acz = xb[3L * i2 + 2] - az;
+        const float cx = __builtin_fmaf(aby, acz, -(abz * acy));
+        const float cy = __builtin_fmaf(abz, acx, -(abx * acz));
+        const float cz = __builtin_fmaf(abx, acy, -(aby * acx));
+        sx = sx + cx; sy = sy + cy; sz = sz + cz;
+    }
+    const float len2 = __builtin_fmaf(sz, sz, __builtin_fmaf(sy, sy, sx * sx));
+    const bool ok = len2 > 0.f && len2 < INFINITY;
+    const float len = sqrtf(len2);
+    float* o = out + t * 3;
+    o[0] = ok ? sx / len : 0.f; o[1] = ok ? sy / len : 0.f; o[2] = ok ? sz / len : 0.f;
+}
+
 int nn_tiles(int nt) { return (nt + TT - 1) / TT; }
 
 int nn_auto_chunks(int B, int nq, int nt) {
@@ -322,6 +466,64 @@ int sh_nearest_points(const float* q, int64_t q_sb, int nq, const int32_t* q_cou
                      p.chunks, idx, d2);
     }
     SH_CHECK_LAUNCH("nearest_points");
+    return SH_OK;
+}
+
+int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* qn, int64_t qn_sb, const float* t,
+                            int64_t t_sb, int nt, const int32_t* t_count, const float* tn, int64_t tn_sb, const uint8_t* t_mask,
+                            int64_t mask_sb, float cos_min, int B, int chunks, int32_t* idx, float* d2, void* workspace,
+                            size_t workspace_bytes, sh_stream_t stream) {
+    SH_REQUIRE(q && t && qn && tn && idx && d2, SH_ERR_INVALID_ARG, "sh_nearest_points_gated: null pointer");
+    SH_REQUIRE(B >= 0 && nq >= 0 && nt >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
+               "sh_nearest_points_gated: negative size (B %d, nq %d, nt %d, chunks %d)", B, nq, nt, chunks);
+    SH_REQUIRE(cos_min == cos_min, SH_ERR_INVALID_ARG, "sh_nearest_points_gated: cos_min is NaN");
+    if (B == 0 || nq == 0) return SH_OK;
+    SH_REQUIRE(q_sb >= 3L * nq && t_sb >= 3L * nt && qn_sb >= 3L * nq && tn_sb >= 3L * nt && (!t_mask || mask_sb == 0 || mask_sb >= nt),
+               SH_ERR_INVALID_ARG, "sh_nearest_points_gated: batch stride shorter than a body (q_sb %ld, qn_sb %ld, t_sb %ld, tn_sb %ld, mask_sb %ld)",
+               (long)q_sb, (long)qn_sb, (long)t_sb, (long)tn_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && nt < (1 << 30), SH_ERR_UNSUPPORTED, "sh_nearest_points_gated: B, B*nq or nt too large");
+    NNParams p{};
+    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
+    p.t = t; p.t_sb = (long)t_sb; p.nt = nt; p.t_count = t_count;
+    p.mask = t_mask; p.mask_sb = (long)mask_sb;
+    p.chunks = nn_resolve_chunks(B, nq, nt, chunks, &p.tiles_per_chunk);
+    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_points_gated: %d target chunks", p.chunks);
+    NNGate g{qn, (long)qn_sb, tn, (long)tn_sb, cos_min};
+    const size_t need = p.chunks <= 1 ? 0 : (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
+               "sh_nearest_points_gated: workspace too small (%zu bytes needed for %d chunks)", need, p.chunks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
+    if (p.chunks <= 1) {
+        ShProfScope ps(st, "nearest_search_gated_kernel|B=%d nq=%d nt=%d chunks=1", B, nq, nt);
+        SH_LAUNCH_PS(ps, nearest_search_gated_kernel, grid, dim3(NT), 0, st, p, g, idx, d2, 1);
+    } else {
+        float* part_d2 = static_cast<float*>(workspace);
+        int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
+        {
+            ShProfScope ps(st, "nearest_search_gated_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
+            SH_LAUNCH_PS(ps, nearest_search_gated_kernel, grid, dim3(NT), 0, st, p, g, part_idx, part_d2, 0);
+        }
+        ShProfScope ps(st, "nearest_merge_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
+        SH_LAUNCH_PS(ps, nearest_merge_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, part_idx, part_d2, q_count, B, nq,
+                     p.chunks, idx, d2);
+    }
+    SH_CHECK_LAUNCH("nearest_points_gated");
+    return SH_OK;
+}
+
+int sh_vertex_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const int32_t* vf_ptr, const int32_t* vf_idx, int B,
+                      float* normals, sh_stream_t stream) {
+    SH_REQUIRE(x && normals && vf_ptr && (nF == 0 || (faces && vf_idx)), SH_ERR_INVALID_ARG, "sh_vertex_normals: null pointer");
+    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0, SH_ERR_INVALID_ARG, "sh_vertex_normals: negative size (B %d, n %d, nF %d)", B, n, nF);
+    if (B == 0 || n == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * n, SH_ERR_INVALID_ARG, "sh_vertex_normals: batch stride %ld shorter than a body", (long)x_sb);
+    SH_REQUIRE((long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "sh_vertex_normals: B*n or nF too large");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "vertex_normals_kernel|B=%d n=%d nF=%d", B, n, nF);
+    SH_LAUNCH_PS(ps, vertex_normals_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, st, x, (long)x_sb, n, faces, nF, vf_ptr,
+                 vf_idx, B, normals);
+    SH_CHECK_LAUNCH("vertex_normals");
     return SH_OK;
 }
 

@@ -214,7 +214,7 @@ def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, b
 
 
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None,
-             faces=None):
+             faces=None, normal_angle=None, normal_faces=None):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
     The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
@@ -222,7 +222,9 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     the decoder's dummy row is never matched.  Works for both model classes (plain SpiralAutoencoder: z [B, nz], z_kps ignored);
     no host synchronisation in the loop.  faces: the model's triangles (a scan.FaceTable or an integer array [nF, 3]) - the scan
     -> model term is then the distance to the model's surface, not to its nearest vertex (scan.chamfer); a scan packed with
-    order="morton" makes that search 2 - 3 times cheaper (DESIGN 4j has the measurement).  Returns (new z, chamfer [B] of the result, loss per step [steps])."""
+    order="morton" makes that search 2 - 3 times cheaper (DESIGN 4j has the measurement).  normal_angle / normal_faces: the normal
+    gate of scan.chamfer (degrees; needs scans.normals, the model's triangles and trunc; None: none, the same bits as ever).
+    Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -230,9 +232,14 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
-    state = {"faces": faces}
+    state = {"faces": faces, "normal_faces": normal_faces}
 
     def objective(x_hat):
+        if normal_angle is not None:
+            if state["normal_faces"] is not None and not isinstance(state["normal_faces"], scan.FaceTable):
+                state["normal_faces"] = scan.FaceTable(state["normal_faces"], x_hat.shape[1] - 1, x_hat.device)
+            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=state["faces"], normal_angle=normal_angle,
+                                normal_faces=state["normal_faces"])
         if state["faces"] is None:
             return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan)
         if not isinstance(state["faces"], scan.FaceTable):                # validated and uploaded once, at the first decode
@@ -246,7 +253,8 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
 
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
-                  lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None):
+                  lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
+                  normal_angle=None, normal_faces=None):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -265,7 +273,9 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     degrees pass a start Pose), a similarity with w_model_to_scan = 0 from the identity can shrink the scan into the model (the
     defaults of stage 1 avoid it), partial scans want mode="rigid" with scan -> model only, and only the normalisations that are
     similarities (zeromean, zeroroot, onelength, small) can be undone by a pose.  faces (as in fit_scan) makes the FIT's scan ->
-    model term point-to-surface; both pose stages keep working on vertex pairs (no point-to-surface ICP).  No file reader."""
+    model term point-to-surface; both pose stages keep working on vertex pairs (no point-to-surface ICP).  normal_angle /
+    normal_faces: the normal gate of scan.chamfer on every search of both stages (needs scans.normals, the model's triangles and
+    trunc; the scan's normals follow the pose's rotation; None: none, the same bits as ever).  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -281,15 +291,21 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     w_align = (1.0 if mode == "similarity" else w_model_to_scan) if align_w_model_to_scan is None else align_w_model_to_scan
     with torch.no_grad():
         x0 = _decode(model, z.detach(), z_kps, dummy)
+    if normal_angle is not None:
+        if faces is not None:
+            raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built")
+        if normal_faces is not None and not isinstance(normal_faces, scan.FaceTable):
+            normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
-                                  vertex_mask=vertex_mask)
+                                  vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces)
     matches = {} if align_every > 0 else None
     state = {"partials": None}
     if faces is not None and not isinstance(faces, scan.FaceTable):
         faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
 
     def objective(x_hat):
-        return scan.chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches=matches, faces=faces)
+        return scan.chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches=matches, faces=faces,
+                            normal_angle=normal_angle, normal_faces=normal_faces)
 
     def after_step(t):
         if (t + 1) % align_every == 0:
@@ -298,5 +314,6 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
                                 after_step=after_step if align_every > 0 else None)
     with torch.no_grad():
-        final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan, faces=faces)
+        final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan, faces=faces,
+                             normal_angle=normal_angle, normal_faces=normal_faces)
     return z_new, pose, final, losses

@@ -435,9 +435,11 @@ def _count_arg(cnt, B, device):
     return c
 
 
-def nearest_points(q, t, q_count=None, t_count=None, t_mask=None, nq=None, nt=None, chunks=0, out=None):
+def nearest_points(q, t, q_count=None, t_count=None, t_mask=None, nq=None, nt=None, chunks=0, out=None, gate=None):
     """sh_nearest_points: q [B, *, 3] (the first nq rows are queries), t [B, *, 3] (the first nt rows are targets) ->
-    (idx int32 [B, nq], d2 fp32 [B, nq]).  chunks: 0 = the library's split of the target range, k = that many ranges."""
+    (idx int32 [B, nq], d2 fp32 [B, nq]).  chunks: 0 = the library's split of the target range, k = that many ranges.
+    gate: None, or (qn [B, >= nq, 3], tn [B, >= nt, 3], cos_min) - then sh_nearest_points_gated: only targets whose normal's fp32
+    dot product with the query's reaches cos_min are candidates."""
     B, q_rows, q_sb = _points(q, "nearest_points")
     Bt, t_rows, t_sb = _points(t, "nearest_points")
     if Bt != B:
@@ -453,9 +455,36 @@ def nearest_points(q, t, q_count=None, t_count=None, t_mask=None, nq=None, nt=No
                                           torch.empty((B, nq), dtype=torch.float32, device=q.device))
     nbytes = lib.sh_nearest_points_workspace(B, nq, nt, chunks)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+    if gate is not None:
+        qn, tn, cos_min = gate
+        (Bq, qn_rows, qn_sb), (Bn, tn_rows, tn_sb) = _points(qn, "nearest_points (query normals)"), _points(tn, "nearest_points (target normals)")
+        if Bq != B or Bn != B or qn_rows < nq or tn_rows < nt:
+            raise ValueError("nearest_points: normals must be [%d, >= %d, 3] and [%d, >= %d, 3], got %s and %s"
+                             % (B, nq, B, nt, tuple(qn.shape), tuple(tn.shape)))
+        check(lib.sh_nearest_points_gated(ptr(q), q_sb, nq, ptr(q_count), ptr(qn), qn_sb, ptr(t), t_sb, nt, ptr(t_count), ptr(tn), tn_sb, ptr(mask),
+                                          mask_sb, float(cos_min), B, chunks, ptr(idx), ptr(d2), ptr(ws), nbytes, stream_ptr()),
+              "sh_nearest_points_gated")
+        return idx, d2
     check(lib.sh_nearest_points(ptr(q), q_sb, nq, ptr(q_count), ptr(t), t_sb, nt, ptr(t_count), ptr(mask), mask_sb, B, chunks, ptr(idx),
                                 ptr(d2), ptr(ws), nbytes, stream_ptr()), "sh_nearest_points")
     return idx, d2
+
+
+def vertex_normals(x, faces, vf_ptr, vf_idx, n, out=None):
+    """sh_vertex_normals: x [B, *, 3] of which the first n rows are vertices, faces int32 HIP [nF, 3] with its incidence (vf_ptr
+    int32 [n + 1], vf_idx int32 [3 nF]; scan.FaceTable builds all three) -> unit normals, contiguous fp32 [B, n, 3]."""
+    B, rows, x_sb = _points(x, "vertex_normals")
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("vertex_normals: n = %d exceeds the model's %d rows" % (n, rows))
+    for t, shape, what in ((faces, (faces.shape[0], 3), "faces [nF, 3]"), (vf_ptr, (n + 1,), "vf_ptr [n + 1]"),
+                           (vf_idx, (3 * faces.shape[0],), "vf_idx [3 nF]")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("semantichuman_amd.vertex_normals needs a contiguous int32 HIP table %s (scan.FaceTable makes one)" % what)
+    nrm = out if out is not None else torch.empty((B, n, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_vertex_normals(ptr(x), x_sb, n, ptr(faces), faces.shape[0], ptr(vf_ptr), ptr(vf_idx), B, ptr(nrm), stream_ptr()),
+          "sh_vertex_normals")
+    return nrm
 
 
 def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None):

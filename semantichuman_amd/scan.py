@@ -9,12 +9,16 @@
                                      to the surface (sh_nearest_surface, sh_chamfer_surface_bwd)
   * `Pose`, `moment_pose(...)`, `align(x, scans, ...)`  scan frame -> model frame: batched similarity ICP on the same matches
                                      (sh_transform_points, sh_align_moments, sh_align_solve)
+  * `ScanBatch(..., normals=)`, `vertex_normals(x, faces)`, `normal_angle=` on chamfer / align  matching by normal: the scan's
+                                     normals and the model's area-weighted vertex normals (sh_vertex_normals) gate every pair of
+                                     the vertex search (sh_nearest_points_gated) - off unless `normal_angle` is given
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
 model's normalised frame; `align` (and editing.register_scan, which alternates it with the fit) brings a scan there by a
 translation, a rigid motion or a similarity.  The alignment works on vertex pairs (no point-to-surface ICP); there is no file
-reader.
+reader.  With `normal_angle` a pair is a match only when its two normals agree to within that angle (a point with no compatible
+partner counts as truncated, so a gate needs `trunc`); the gate applies to vertex pairs, not to the surface distance of `faces=`.
 The search, the loss and the alignment have no CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
@@ -49,6 +53,30 @@ def pack_clouds(clouds):
     return pts, counts
 
 
+def pack_normals(normals, counts, width):
+    """Normals matching packed clouds row for row: a list of [m_b, 3] arrays (or one [B, M, 3] array) -> float32 [B, width, 3],
+    every row normalised in float64 and rounded to fp32 once; a row of exact zeros stays zero ("unknown"), the padding is zero.
+    ValueError on a shape that does not match the clouds, NaN or inf."""
+    if isinstance(normals, np.ndarray) and normals.ndim == 3:
+        normals = list(normals)
+    elif torch.is_tensor(normals) and normals.dim() == 3:
+        normals = list(normals.detach().cpu().numpy())
+    normals = [c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c) for c in normals]
+    if len(normals) != len(counts):
+        raise ValueError("ScanBatch: %d clouds, normals for %d" % (len(counts), len(normals)))
+    out = np.zeros((len(counts), int(width), 3), dtype=np.float32)
+    for b, (c, m) in enumerate(zip(normals, counts)):
+        if c.ndim != 2 or c.shape[1] != 3 or c.shape[0] != m:
+            raise ValueError("ScanBatch: normals %d have shape %s, the cloud has [%d, 3]" % (b, c.shape, m))
+        c = c.astype(np.float64)
+        if not np.isfinite(c).all():
+            raise ValueError("ScanBatch: normals %d hold NaN or inf" % b)
+        big = np.abs(c).max(1, keepdims=True)                              # scaled first: no overflow or underflow in the squares
+        c = c / np.where(big > 0, big, 1.0)
+        out[b, :m] = c / np.where(big > 0, np.sqrt((c * c).sum(1, keepdims=True)), 1.0)
+    return out
+
+
 def morton_order(points, bits=10):
     """The permutation that sorts an [m, 3] cloud along the Morton (Z-order) curve of its own bounding box, `bits` bits per axis;
     a stable sort, so equal codes keep their order.  Host side, numpy only."""
@@ -73,22 +101,30 @@ class ScanBatch:
     packing time (`morton_order`), so that points next to each other in memory are next to each other in space - what the
     surface search's cull lives on.  The permutation is kept on the host as `perm`, int64 [B, Mmax]: points[b, k] is the given
     cloud's point perm[b, k] (k < counts[b]; -1 in the padding); `perm` is None when nothing was sorted.  A Chamfer value does
-    not depend on the order beyond the rounding of its sum."""
+    not depend on the order beyond the rounding of its sum.
 
-    def __init__(self, clouds, device, order=None):
+    normals: None, or the clouds' normals row for row (a list of [m_b, 3] arrays or one [B, M, 3] array; `pack_normals`): kept as
+    `normals`, fp32 [B, Mmax, 3] unit rows on the device, sorted with their points; a zero row means "unknown".  They are used
+    only where a `normal_angle` is asked for."""
+
+    def __init__(self, clouds, device, order=None, normals=None):
         if order not in (None, "morton"):
             raise ValueError("ScanBatch: order must be None or 'morton'")
         pts, counts = pack_clouds(clouds)
+        nrm = None if normals is None else pack_normals(normals, counts, pts.shape[1])
         self.perm = None
         if order == "morton":
             self.perm = np.full(pts.shape[:2], -1, dtype=np.int64)
             for b, m in enumerate(counts):
                 self.perm[b, :m] = morton_order(pts[b, :m])
                 pts[b, :m] = pts[b, :m][self.perm[b, :m]]
+                if nrm is not None:
+                    nrm[b, :m] = nrm[b, :m][self.perm[b, :m]]
         dev = torch.device(device)
         self.host_counts = counts
         self.points = torch.from_numpy(pts).to(dev)
         self.counts = torch.from_numpy(counts).to(dev)
+        self.normals = None if nrm is None else torch.from_numpy(nrm).to(dev)
 
     def __len__(self):
         return self.points.shape[0]
@@ -100,6 +136,7 @@ class ScanBatch:
         out.host_counts = self.host_counts[sl]
         out.points = self.points[sl]
         out.counts = self.counts[sl].contiguous()
+        out.normals = None if getattr(self, "normals", None) is None else self.normals[sl]
         return out
 
 
@@ -115,6 +152,8 @@ def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
 class FaceTable:
     """The model's triangles for the surface search: `faces` int32 [nF, 3] on the device, one table for every body of a batch;
     `n` is the number of model vertices the indices may address (the decoder's dummy row, row n, is not among them).
+    `vf_ptr` int32 [n + 1] / `vf_idx` int32 [3 nF] are the vertex-to-face incidence (CSR, built once here on the host): the faces
+    that name vertex v are vf_idx[vf_ptr[v]:vf_ptr[v + 1]], in ascending face order - what `vertex_normals` walks.
     ValueError unless the table is an integer array [nF, 3] with 0 <= index < n and no face that names a vertex twice."""
 
     def __init__(self, faces, n, device):
@@ -132,6 +171,12 @@ class FaceTable:
             raise ValueError("FaceTable: a face names the same vertex twice")
         self.n = n
         self.faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(torch.device(device))
+        flat = f.reshape(-1)
+        order = np.argsort(flat, kind="stable")                            # stable: a vertex's faces stay in ascending face order
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(flat, minlength=n), out=ptr[1:])
+        self.vf_ptr = torch.from_numpy(ptr.astype(np.int32)).to(self.faces.device)
+        self.vf_idx = torch.from_numpy((order // 3).astype(np.int32)).to(self.faces.device)
 
     def __len__(self):
         return self.faces.shape[0]
@@ -143,6 +188,46 @@ def _face_table(faces, n, device):
             raise ValueError("face table made for %d vertices, the model has %d" % (faces.n, n))
         return faces
     return FaceTable(faces, n, device)
+
+
+def vertex_normals(x, faces, n=None):
+    """Area-weighted unit vertex normals of every body, fp32 [B, n, 3] (sh_vertex_normals: the fp32 expression of sh_kernels.h,
+    one thread per vertex over its incident faces in ascending face order; deterministic).  x [B, rows, 3]; faces: a FaceTable or
+    an integer array [nF, 3], oriented counter-clockwise seen from outside for outward normals; n as in `chamfer` (None = rows -
+    1).  A vertex in no face, or whose faces' cross products cancel, gets the zero vector.  The vertex mask plays no part.  Not
+    differentiable."""
+    x = x.detach()
+    rows = ops._points(x, "scan.vertex_normals")[1]
+    ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
+    return ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
+
+
+def _normal_gate(what, normal_angle, normal_faces, scans, n, trunc, faces, device):
+    """Validates the arguments of a normal gate -> None (no gate) or (cos_min, FaceTable)."""
+    if normal_angle is None:
+        return None
+    a = float(normal_angle)
+    if not 0.0 < a <= 180.0:
+        raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
+    if faces is not None:
+        raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built" % what)
+    if getattr(scans, "normals", None) is None:
+        raise ValueError("%s: normal_angle needs scan normals (ScanBatch(..., normals=))" % what)
+    if normal_faces is None:
+        raise ValueError("%s: normal_angle needs the model's triangles (normal_faces=, a FaceTable or an integer array)" % what)
+    if trunc is None:
+        raise ValueError("%s: normal_angle needs trunc (a point with no compatible partner counts as truncated; without trunc "
+                         "the loss would be infinite)" % what)
+    ft = _face_table(normal_faces, n, device)
+    if ft.n != n:
+        raise ValueError("%s: normal_faces was made for %d vertices, the model has %d" % (what, ft.n, n))
+    return (-math.inf if a == 180.0 else math.cos(math.radians(a))), ft
+
+
+def _query_normals(tn, rows):
+    """Vertex normals [B, n, 3] as the model -> scan search takes them, [B, rows, 3]: every row of the model is a query there, and
+    the rows behind the vertices (the decoder's dummy row) carry the zero normal."""
+    return tn if rows == tn.shape[1] else torch.nn.functional.pad(tn, (0, 0, 0, rows - tn.shape[1]))
 
 
 def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=True, n=None):
@@ -204,13 +289,19 @@ class _ChamferSurface(torch.autograd.Function):
 
 class _Chamfer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms, matches=None):
+    def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms, matches=None, gate=None):
         s, cnt = scans.points, scans.counts
         rows = x.shape[1]
-        idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)
+        g_sm = g_ms = None
+        if gate is not None:                                                        # (cos_min, FaceTable): both directions gated
+            cos_min, ft = gate
+            tn = ops.vertex_normals(x.detach(), ft.faces, ft.vf_ptr, ft.vf_idx, n)  # once per forward pass
+            g_sm = (scans.normals, tn, cos_min)
+            g_ms = (_query_normals(tn, rows), scans.normals, cos_min) if w_ms > 0.0 else None
+        idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, gate=g_sm)
         idx_ms = d2_ms = None
         if w_ms > 0.0:
-            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt)                   # all rows are queries: [B, rows] as the kernels index it
+            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt, gate=g_ms)        # all rows are queries: [B, rows] as the kernels index it
         loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
         ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
         ctx.save_for_backward(x, idx_sm, d2_sm, idx_ms, d2_ms, counts)
@@ -224,10 +315,11 @@ class _Chamfer(torch.autograd.Function):
         x, idx_sm, d2_sm, idx_ms, d2_ms, counts = ctx.saved_tensors
         g = ops.chamfer_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, idx_sm, d2_sm, idx_ms, d2_ms, ctx.v_mask, ctx.mask_sb, counts,
                             ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
-def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None):
+def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None, normal_angle=None,
+            normal_faces=None):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -246,7 +338,15 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     that point, and its gradient reaches the three corners of the face with the foot point's barycentric weights.  The model ->
     scan term (vertex to scan point), trunc, vertex_mask (a triangle with a masked corner is no target) and n keep their meaning.
     `matches` receives what it receives without faces - the VERTEX matches, which were computed for the search's bound - plus
-    `face`, `uv` and `d2_surface`; `pose_update` and `align` go on working on the vertex pairs."""
+    `face`, `uv` and `d2_surface`; `pose_update` and `align` go on working on the vertex pairs.
+
+    normal_angle: None (the default: everything above, bit for bit, whether or not the scans carry normals), or an angle in
+    degrees in (0, 180].  Then a scan point and a vertex are a pair only when their normals - `scans.normals` and
+    `vertex_normals(x_hat)`, computed once per forward pass from `normal_faces` (a FaceTable or an integer array) - differ by at
+    most that angle, in both directions (sh_nearest_points_gated; the test is cos(angle) against the fp32 dot product; 180 opens
+    the gate and gives the ungated bits).  A zero ("unknown") normal is compatible only for angles >= 90.  A point with no
+    compatible partner is recorded as idx -1, d2 +inf and counts as truncated: it adds trunc^2 and takes no part in the
+    gradient or in `pose_update` - which is why a gate needs `trunc`.  Not built together with `faces=`."""
     if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
         raise RuntimeError("semantichuman_amd.scan.chamfer needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
                            % getattr(x_hat, "device", type(x_hat)))
@@ -265,9 +365,10 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
         raise ValueError("chamfer: trunc must be > 0")
     tau2 = math.inf if trunc is None else float(trunc) ** 2
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
+    gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device)
     if faces is not None:
         return _ChamferSurface.apply(x_hat, scans, _face_table(faces, n, x_hat.device).faces, n, v_mask, mask_sb, tau2, w, matches)
-    return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches)
+    return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches, gate)
 
 
 # ------------------------------------------------------------------------------------------------ alignment
@@ -320,15 +421,22 @@ class Pose:
 
     def apply(self, points, counts=None):
         """A p + t for every point, in the one fp32 expression of sh_transform_points.  points: a ScanBatch (-> ScanBatch, rows
-        beyond the counts zero) or fp32 HIP points [B, M, 3] with optional live counts [B] (-> tensor)."""
+        beyond the counts zero; its normals, if any, rotated by R = A / scale through the same kernel) or fp32 HIP points
+        [B, M, 3] with optional live counts [B] (-> tensor)."""
         if isinstance(points, ScanBatch):
             out = ScanBatch.__new__(ScanBatch)
             out.perm = getattr(points, "perm", None)
             out.host_counts, out.counts = points.host_counts, points.counts
             out.points = ops.transform_points(points.points, points.counts, self.packed)
+            nrm = getattr(points, "normals", None)
+            out.normals = None if nrm is None else ops.transform_points(nrm, points.counts, self.rotation_packed())
             return out
         B = ops._points(points, "scan.Pose.apply")[0]
         return ops.transform_points(points, ops._count_arg(counts, B, points.device), self.packed)
+
+    def rotation_packed(self):
+        """The packed pose of the rotation alone, [B, 12]: R = A / scale row-major, t = 0 - what carries a normal."""
+        return torch.nn.functional.pad(self.packed[:, :9] / self.scale[:, None], (0, 3))
 
     def compose(self, first):
         """The pose that applies `first` and then this one (float64 inside, rounded to fp32 once)."""
@@ -399,16 +507,20 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None)
     """One closed-form pose step from recorded matches, no search: moments of the matched pairs (`matches`, as `chamfer(...,
     matches=)` or `align` fill it, found on `aligned`), the pose increment that minimises the same weighted squared distances,
     composed into `pose` in place, and `aligned.points` overwritten with the ORIGINAL `scans` under the new pose.  Three
-    launches."""
+    launches; when both batches carry normals, `aligned.normals` is overwritten with the ORIGINAL normals under the new pose's
+    rotation (one more sh_transform_points)."""
     m = matches
     part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
                              m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
     ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
+    if getattr(scans, "normals", None) is not None and getattr(aligned, "normals", None) is not None:
+        ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)
     return part
 
 
-def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0):
+def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
+          normal_angle=None, normal_faces=None):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -417,7 +529,9 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     "identity", or a Pose.  Per iteration: the ORIGINAL scan under the pose so far -> search -> the logged Chamfer value ->
     moments -> solve; rounding therefore does not build up in the points.  No host synchronisation.  chunks: the search's split
     (every value gives the same bits).  Returns (pose, the aligned scans as a ScanBatch, chamfer [iters, B] - row k is the value
-    BEFORE the k-th update).  Not differentiable.
+    BEFORE the k-th update).  Not differentiable.  normal_angle / normal_faces: the normal gate of `chamfer` on both searches of
+    every iteration (None: none, the same bits as ever); the model's normals are computed once, the scan's are carried by the
+    pose's rotation from the ORIGINAL normals each iteration.  Needs scans.normals, normal_faces and trunc.
 
     Limits.  ICP is local: the moment start fixes translation and scale, not rotation - a scan rotated by more than about 45
     degrees against the model needs a caller-supplied start pose (no principal-axes or multi-start search here).  mode
@@ -438,6 +552,7 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     tau2 = math.inf if trunc is None else float(trunc) ** 2
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
     x = x.detach()
+    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, None, x.device)
     if isinstance(init, Pose):
         if len(init) != B:
             raise ValueError("align: %d bodies, start pose for %d" % (B, len(init)))
@@ -458,10 +573,16 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
     matches = dict(x=x, n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w, idx_sm=sm[0], d2_sm=sm[1], idx_ms=ms[0], d2_ms=ms[1])
     part = None
+    tn = qn = None
+    if gate is not None and iters > 0:
+        tn = ops.vertex_normals(x, gate[1].faces, gate[1].vf_ptr, gate[1].vf_idx, n)    # x is fixed: once
+        qn = _query_normals(tn, rows) if w > 0.0 else None
     for k in range(iters):
-        ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm)
+        g_sm = None if gate is None else (aligned.normals, tn, gate[0])
+        g_ms = None if gate is None else (qn, aligned.normals, gate[0])
+        ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=g_sm)
         if w > 0.0:
-            ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms)
+            ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms, gate=g_ms)
         ops.chamfer_fwd(sm[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
         part = pose_update(pose, scans, aligned, matches, mode, partials=part)
     return pose, aligned, log
