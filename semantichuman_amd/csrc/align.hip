@@ -2,8 +2,7 @@
 // transform of the scan (include/sh_kernels.h, "Scan alignment").  The matches are the ones scan.hip's search has recorded for
 // the Chamfer loss, so a pose update costs no search.  No atomics of any kind: every sum runs in a fixed order that depends on
 // M and n only - the same bits on every call, for every batch size and for a body alone or inside a batch.
-#include "sh_common.h"
-#include <math.h>
+#include "sh_nn.h"
 
 namespace {
 
@@ -11,18 +10,6 @@ constexpr int NT = 256;                       // threads per workgroup of the mo
 constexpr int RANGE = SH_ALIGN_RANGE;         // pairs per workgroup: thread t takes t, t + 256, ... of its range (8 each)
 constexpr int NP = SH_ALIGN_PARTIAL;          // sums per range
 constexpr int NM = SH_ALIGN_MOMENTS;          // doubles per body of the finished moments
-
-__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
-    if (!cnt) return rows;
-    const int c = cnt[b];
-    return c < 0 ? 0 : (c > rows ? rows : c);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 int ranges_of(int rows) { return (rows + RANGE - 1) / RANGE; }
 

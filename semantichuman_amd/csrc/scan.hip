@@ -3,8 +3,7 @@
 // pair-distance sweep of part_loss.hip: queries in registers, targets streamed through LDS, every lane reading the same LDS
 // address (broadcast).  No float atomics: the search keeps (d2, index) under the lexicographic minimum, which is associative and
 // commutative, and the loss / gradient sums run in a fixed order - the same bits on every call and for every split of the targets.
-#include "sh_common.h"
-#include <math.h>
+#include "sh_nn.h"
 
 namespace {
 
@@ -12,7 +11,6 @@ constexpr int NT = 256;          // threads per workgroup
 constexpr int QPT = 4;           // queries a thread keeps in registers
 constexpr int QT = NT * QPT;     // queries per workgroup
 constexpr int TT = 256;          // targets per LDS tile: one global load per thread and tile
-constexpr int WG_SLOTS = 2048;   // workgroups the chip holds at once (256 CUs x 8): the automatic split aims at this many
 
 struct NNParams {
     const float* q; long q_sb; int nq; const int32_t* q_count;
@@ -21,28 +19,32 @@ struct NNParams {
     int tiles_per_chunk, chunks;
 };
 
-__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
-    if (!cnt) return rows;
-    const int c = cnt[b];
-    return c < 0 ? 0 : (c > rows ? rows : c);
-}
-
-// The distance of the header, in its one fixed form.
-__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
-    const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-    return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-}
+// The normal gate of the header ("Vertex normals"): the queries' and the targets' normals and the smallest cosine that pairs them.
+struct NNGate {
+    const float* qn; long qn_sb;
+    const float* tn; long tn_sb;
+    float cos_min;
+};
 
 // grid (query tile, target chunk, body).  final != 0: the one chunk's result is the result (idx / d2 [B][nq]); otherwise the
 // chunk's (d2, idx) go to part_d2 / part_idx [B][chunks][nq] for nearest_merge_kernel.
 // A target that is masked, or lies beyond the body's count, enters LDS as (+inf, +inf, +inf): its distance is +inf, which the
 // strict `<` never selects, so the inner loop carries no index test.  Targets are visited in ascending order and a candidate
 // replaces the best only when strictly closer: the lowest index wins an exact tie.
-__global__ __launch_bounds__(NT) void nearest_search_kernel(const NNParams p, int32_t* __restrict__ idx, float* __restrict__ d2,
-                                                           int final) {
+// GATED: a target is a candidate only when the fp32 dot product of the two normals reaches g.cos_min - three more LDS arrays,
+// three more query registers.  The gate is one compare and one select on the candidate distance (d = ok ? d : +inf), so a
+// gated-out target loses exactly as a masked one does and the (d2, index) minimum stays the lexicographic one.  Target normals
+// of masked / out-of-count targets enter as zeros: their distance is +inf whatever the gate says.  Without GATED, g is not read
+// and the gate's arrays and registers do not exist.
+template <bool GATED>
+__global__ __launch_bounds__(NT) void nearest_search_kernel(const NNParams p, int32_t* __restrict__ idx, float* __restrict__ d2, int final,
+                                                           const NNGate g) {
     __shared__ __attribute__((aligned(16))) float sx[2][TT];
     __shared__ __attribute__((aligned(16))) float sy[2][TT];
     __shared__ __attribute__((aligned(16))) float sz[2][TT];
+    __shared__ __attribute__((aligned(16))) float su[GATED ? 2 : 1][GATED ? TT : 4];
+    __shared__ __attribute__((aligned(16))) float sv[GATED ? 2 : 1][GATED ? TT : 4];
+    __shared__ __attribute__((aligned(16))) float sw[GATED ? 2 : 1][GATED ? TT : 4];
     const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
     const int nqb = clamp_count(p.q_count, b, p.nq), ntb = clamp_count(p.t_count, b, p.nt);
     const int j0 = blockIdx.x * QT;
@@ -56,28 +58,37 @@ __global__ __launch_bounds__(NT) void nearest_search_kernel(const NNParams p, in
     }
     const float* qb = p.q + (long)b * p.q_sb;
     const float* tb = p.t + (long)b * p.t_sb;
+    const float* qnb = GATED ? g.qn + (long)b * g.qn_sb : nullptr;
+    const float* tnb = GATED ? g.tn + (long)b * g.tn_sb : nullptr;
     const unsigned char* mb = p.mask ? p.mask + (long)b * p.mask_sb : nullptr;
-    float qx[QPT], qy[QPT], qz[QPT], best[QPT];
+    const float cos_min = g.cos_min;
+    float qx[QPT], qy[QPT], qz[QPT], qu[QPT], qv[QPT], qw[QPT], best[QPT];
     int bi[QPT];
 #pragma unroll
     for (int k = 0; k < QPT; ++k) {
         const int j = j0 + k * NT + tid;
         const bool live = j < nqb;
         qx[k] = live ? qb[3L * j] : 0.f; qy[k] = live ? qb[3L * j + 1] : 0.f; qz[k] = live ? qb[3L * j + 2] : 0.f;
+        if constexpr (GATED) { qu[k] = live ? qnb[3L * j] : 0.f; qv[k] = live ? qnb[3L * j + 1] : 0.f; qw[k] = live ? qnb[3L * j + 2] : 0.f; }
         best[k] = INFINITY; bi[k] = -1;
     }
     const int tiles = (ntb + TT - 1) / TT;
     const int tile_lo = c * p.tiles_per_chunk;
     const int tile_hi = min(tile_lo + p.tiles_per_chunk, tiles);
     if (tile_lo < tile_hi) {                                             // uniform
-        float lx, ly, lz;
+        float lx, ly, lz, lu, lv, lw;
         auto fetch = [&](int tile) {
             const int i = tile * TT + tid;
             const bool ok = i < ntb && (!mb || mb[i] != 0);
             lx = ok ? tb[3L * i] : INFINITY; ly = ok ? tb[3L * i + 1] : INFINITY; lz = ok ? tb[3L * i + 2] : INFINITY;
+            if constexpr (GATED) { lu = ok ? tnb[3L * i] : 0.f; lv = ok ? tnb[3L * i + 1] : 0.f; lw = ok ? tnb[3L * i + 2] : 0.f; }
+        };
+        auto stage = [&](int buf) {
+            sx[buf][tid] = lx; sy[buf][tid] = ly; sz[buf][tid] = lz;
+            if constexpr (GATED) { su[buf][tid] = lu; sv[buf][tid] = lv; sw[buf][tid] = lw; }
         };
         fetch(tile_lo);
-        sx[0][tid] = lx; sy[0][tid] = ly; sz[0][tid] = lz;
+        stage(0);
         __syncthreads();
         for (int tile = tile_lo; tile < tile_hi; ++tile) {
             const int cur = (tile - tile_lo) & 1;
@@ -89,18 +100,28 @@ __global__ __launch_bounds__(NT) void nearest_search_kernel(const NNParams p, in
                 const f32x4 X = *reinterpret_cast<const f32x4*>(&sx[cur][u]);
                 const f32x4 Y = *reinterpret_cast<const f32x4*>(&sy[cur][u]);
                 const f32x4 Z = *reinterpret_cast<const f32x4*>(&sz[cur][u]);
+                f32x4 U, V, W;
+                if constexpr (GATED) {
+                    U = *reinterpret_cast<const f32x4*>(&su[cur][u]);
+                    V = *reinterpret_cast<const f32x4*>(&sv[cur][u]);
+                    W = *reinterpret_cast<const f32x4*>(&sw[cur][u]);
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
 #pragma unroll
                     for (int k = 0; k < QPT; ++k) {
-                        const float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
+                        float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
+                        if constexpr (GATED) {
+                            const float dot = __builtin_fmaf(qw[k], W[e], __builtin_fmaf(qv[k], V[e], qu[k] * U[e]));
+                            d = dot >= cos_min ? d : INFINITY;            // a NaN compares false: not compatible
+                        }
                         const bool closer = d < best[k];
                         best[k] = closer ? d : best[k];
                         bi[k] = closer ? base + u + e : bi[k];
                     }
                 }
             }
-            if (more) { sx[cur ^ 1][tid] = lx; sy[cur ^ 1][tid] = ly; sz[cur ^ 1][tid] = lz; }
+            if (more) stage(cur ^ 1);
             __syncthreads();                                             // one barrier per tile: the other buffer was last read before the previous one
         }
     }
@@ -136,12 +157,6 @@ __global__ __launch_bounds__(256) void nearest_merge_kernel(const int32_t* __res
         if (d < best) { best = d; bi = part_idx[o]; }
     }
     idx[t] = bi; d2[t] = best;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // One workgroup per body.  Stage 1: thread t sums the terms t, t + 256, ... in order (fp64); stage 2: the 256 sums through the
@@ -248,114 +263,6 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ normals (header: "Vertex normals")
-struct NNGate {
-    const float* qn; long qn_sb;
-    const float* tn; long tn_sb;
-    float cos_min;
-};
-
-// nearest_search_kernel with the normal gate of the header: a target is a candidate only when the fp32 dot product of the two
-// normals reaches cos_min.  Same grid, tiles, chunks and outputs; six LDS arrays instead of three, six query registers instead of
-// three.  The gate is one compare and one select on the candidate distance (d = ok ? d : +inf), so a gated-out target loses
-// exactly as a masked one does and the (d2, index) minimum stays the lexicographic one.  Target normals of masked / out-of-count
-// targets enter as zeros: their distance is +inf whatever the gate says.
-__global__ __launch_bounds__(NT) void nearest_search_gated_kernel(const NNParams p, const NNGate g, int32_t* __restrict__ idx,
-                                                                 float* __restrict__ d2, int final) {
-    __shared__ __attribute__((aligned(16))) float sx[2][TT];
-    __shared__ __attribute__((aligned(16))) float sy[2][TT];
-    __shared__ __attribute__((aligned(16))) float sz[2][TT];
-    __shared__ __attribute__((aligned(16))) float su[2][TT];
-    __shared__ __attribute__((aligned(16))) float sv[2][TT];
-    __shared__ __attribute__((aligned(16))) float sw[2][TT];
-    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
-    const int nqb = clamp_count(p.q_count, b, p.nq), ntb = clamp_count(p.t_count, b, p.nt);
-    const int j0 = blockIdx.x * QT;
-    if (j0 >= nqb) {                                                     // uniform: no query of this tile is live
-        if (final)
-            for (int k = 0; k < QPT; ++k) {
-                const int j = j0 + k * NT + tid;
-                if (j < p.nq) { idx[(long)b * p.nq + j] = -1; d2[(long)b * p.nq + j] = 0.f; }
-            }
-        return;
-    }
-    const float* qb = p.q + (long)b * p.q_sb;
-    const float* tb = p.t + (long)b * p.t_sb;
-    const float* qnb = g.qn + (long)b * g.qn_sb;
-    const float* tnb = g.tn + (long)b * g.tn_sb;
-    const unsigned char* mb = p.mask ? p.mask + (long)b * p.mask_sb : nullptr;
-    const float cos_min = g.cos_min;
-    float qx[QPT], qy[QPT], qz[QPT], qu[QPT], qv[QPT], qw[QPT], best[QPT];
-    int bi[QPT];
-#pragma unroll
-    for (int k = 0; k < QPT; ++k) {
-        const int j = j0 + k * NT + tid;
-        const bool live = j < nqb;
-        qx[k] = live ? qb[3L * j] : 0.f; qy[k] = live ? qb[3L * j + 1] : 0.f; qz[k] = live ? qb[3L * j + 2] : 0.f;
-        qu[k] = live ? qnb[3L * j] : 0.f; qv[k] = live ? qnb[3L * j + 1] : 0.f; qw[k] = live ? qnb[3L * j + 2] : 0.f;
-        best[k] = INFINITY; bi[k] = -1;
-    }
-    const int tiles = (ntb + TT - 1) / TT;
-    const int tile_lo = c * p.tiles_per_chunk;
-    const int tile_hi = min(tile_lo + p.tiles_per_chunk, tiles);
-    if (tile_lo < tile_hi) {                                             // uniform
-        float lx, ly, lz, lu, lv, lw;
-        auto fetch = [&](int tile) {
-            const int i = tile * TT + tid;
-            const bool ok = i < ntb && (!mb || mb[i] != 0);
-            lx = ok ? tb[3L * i] : INFINITY; ly = ok ? tb[3L * i + 1] : INFINITY; lz = ok ? tb[3L * i + 2] : INFINITY;
-            lu = ok ? tnb[3L * i] : 0.f; lv = ok ? tnb[3L * i + 1] : 0.f; lw = ok ? tnb[3L * i + 2] : 0.f;
-        };
-        fetch(tile_lo);
-        sx[0][tid] = lx; sy[0][tid] = ly; sz[0][tid] = lz; su[0][tid] = lu; sv[0][tid] = lv; sw[0][tid] = lw;
-        __syncthreads();
-        for (int tile = tile_lo; tile < tile_hi; ++tile) {
-            const int cur = (tile - tile_lo) & 1;
-            const bool more = tile + 1 < tile_hi;
-            if (more) fetch(tile + 1);                                   // in flight under this tile's arithmetic
-            const int base = tile * TT;
-#pragma unroll 2
-            for (int u = 0; u < TT; u += 4) {
-                const f32x4 X = *reinterpret_cast<const f32x4*>(&sx[cur][u]);
-                const f32x4 Y = *reinterpret_cast<const f32x4*>(&sy[cur][u]);
-                const f32x4 Z = *reinterpret_cast<const f32x4*>(&sz[cur][u]);
-                const f32x4 U = *reinterpret_cast<const f32x4*>(&su[cur][u]);
-                const f32x4 V = *reinterpret_cast<const f32x4*>(&sv[cur][u]);
-                const f32x4 W = *reinterpret_cast<const f32x4*>(&sw[cur][u]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int k = 0; k < QPT; ++k) {
-                        const float dot = __builtin_fmaf(qw[k], W[e], __builtin_fmaf(qv[k], V[e], qu[k] * U[e]));
-                        float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
-                        d = dot >= cos_min ? d : INFINITY;                // a NaN compares false: not compatible
-                        const bool closer = d < best[k];
-                        best[k] = closer ? d : best[k];
-                        bi[k] = closer ? base + u + e : bi[k];
-                    }
-                }
-            }
-            if (more) {
-                sx[cur ^ 1][tid] = lx; sy[cur ^ 1][tid] = ly; sz[cur ^ 1][tid] = lz;
-                su[cur ^ 1][tid] = lu; sv[cur ^ 1][tid] = lv; sw[cur ^ 1][tid] = lw;
-            }
-            __syncthreads();                                             // one barrier per tile, as in nearest_search_kernel
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < QPT; ++k) {
-        const int j = j0 + k * NT + tid;
-        if (j >= p.nq) continue;
-        if (final) {
-            const long o = (long)b * p.nq + j;
-            idx[o] = j < nqb ? bi[k] : -1;
-            d2[o] = j < nqb ? best[k] : 0.f;
-        } else if (j < nqb) {
-            const long o = ((long)b * p.chunks + c) * p.nq + j;
-            idx[o] = bi[k]; d2[o] = best[k];
-        }
-    }
-}
-
 // Area-weighted vertex normals, gather form: one thread per (body, vertex) walks the vertex's incident faces in the order of the
 // incidence table (ascending face) and sums the faces' cross products in fp32 - the header's expression, no contraction beyond
 // the fused multiply-adds written out, so the numpy transcription of tests/normals_ref.py rounds alike.  An entry of either table
@@ -391,27 +298,45 @@ __global__ __launch_bounds__(256) void vertex_normals_kernel(const float* __rest
     o[0] = ok ? sx / len : 0.f; o[1] = ok ? sy / len : 0.f; o[2] = ok ? sz / len : 0.f;
 }
 
-int nn_tiles(int nt) { return (nt + TT - 1) / TT; }
-
-int nn_auto_chunks(int B, int nq, int nt) {
-    if (B <= 0 || nq <= 0 || nt <= 0) return 1;
-    const long wgs = (long)sh_cdiv(nq, QT) * B;
-    long want = (WG_SLOTS + wgs - 1) / wgs;
-    const int tiles = nn_tiles(nt);
-    if (want > tiles) want = tiles;
-    if (want < 1) want = 1;
-    const int tpc = sh_cdiv(tiles, (int)want);
-    return sh_cdiv(tiles, tpc);
-}
-
-// the split actually run for a request of `chunks` (0 = automatic): whole tiles per chunk, no empty chunk
-int nn_resolve_chunks(int B, int nq, int nt, int chunks, int* tiles_per_chunk) {
-    const int tiles = nn_tiles(nt) > 0 ? nn_tiles(nt) : 1;
-    int c = chunks > 0 ? chunks : nn_auto_chunks(B, nq, nt);
-    if (c > tiles) c = tiles;
-    const int tpc = sh_cdiv(tiles, c);
-    *tiles_per_chunk = tpc;
-    return sh_cdiv(tiles, tpc);
+// sh_nearest_points (g == nullptr) and sh_nearest_points_gated: the checks both make, in the order the header states, the split,
+// the workspace and the launches.  `who` is the entry point's name in every error text.
+int nn_search(const char* who, NNParams p, const NNGate* g, int B, int chunks, int32_t* idx, float* d2, void* workspace,
+              size_t workspace_bytes, sh_stream_t stream) {
+    const int nq = p.nq, nt = p.nt;
+    SH_REQUIRE(p.q && p.t && idx && d2, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(B >= 0 && nq >= 0 && nt >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, nq %d, nt %d, chunks %d)", who, B, nq,
+               nt, chunks);
+    SH_REQUIRE(!g || g->cos_min == g->cos_min, SH_ERR_INVALID_ARG, "%s: cos_min is NaN", who);
+    if (B == 0 || nq == 0) return SH_OK;
+    SH_REQUIRE(p.q_sb >= 3L * nq && p.t_sb >= 3L * nt && (!p.mask || p.mask_sb == 0 || p.mask_sb >= nt), SH_ERR_INVALID_ARG,
+               "%s: batch stride shorter than a body (q_sb %ld, t_sb %ld, mask_sb %ld)", who, p.q_sb, p.t_sb, p.mask_sb);
+    SH_REQUIRE(!g || (g->qn_sb >= 3L * nq && g->tn_sb >= 3L * nt), SH_ERR_INVALID_ARG,
+               "%s: batch stride shorter than a body (qn_sb %ld, tn_sb %ld)", who, g ? g->qn_sb : 0L, g ? g->tn_sb : 0L);
+    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && nt < (1 << 30), SH_ERR_UNSUPPORTED, "%s: B, B*nq or nt too large", who);
+    p.chunks = nn_resolve_chunks(B, nq, nt, TT, QT, chunks, &p.tiles_per_chunk);
+    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "%s: %d target chunks", who, p.chunks);
+    const size_t need = p.chunks <= 1 ? 0 : (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes needed for %d chunks)",
+               who, need, p.chunks);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
+    const int final = p.chunks <= 1;
+    float* part_d2 = final ? d2 : static_cast<float*>(workspace);
+    int32_t* part_idx = final ? idx : reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
+    if (g) {
+        ShProfScope ps(st, "nearest_search_gated_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
+        SH_LAUNCH_PS(ps, nearest_search_kernel<true>, grid, dim3(NT), 0, st, p, part_idx, part_d2, final, *g);
+    } else {
+        ShProfScope ps(st, "nearest_search_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
+        SH_LAUNCH_PS(ps, nearest_search_kernel<false>, grid, dim3(NT), 0, st, p, part_idx, part_d2, final, NNGate{});
+    }
+    if (!final) {
+        ShProfScope ps(st, "nearest_merge_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
+        SH_LAUNCH_PS(ps, nearest_merge_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, part_idx, part_d2, p.q_count, B, nq,
+                     p.chunks, idx, d2);
+    }
+    SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
 }
 
 }  // namespace
@@ -419,97 +344,33 @@ int nn_resolve_chunks(int B, int nq, int nt, int chunks, int* tiles_per_chunk) {
 extern "C" {
 
 int sh_nearest_points_chunks(int B, int nq, int nt) {
+    if (B <= 0 || nq <= 0) return 1;                                     // nothing to search: not split
     int tpc;
-    return nn_resolve_chunks(B, nq, nt, 0, &tpc);
+    return nn_resolve_chunks(B, nq, nt, TT, QT, 0, &tpc);
 }
 
 size_t sh_nearest_points_workspace(int B, int nq, int nt, int chunks) {
     if (B <= 0 || nq <= 0 || nt < 0 || chunks < 0) return 0;
     int tpc;
-    const int c = nn_resolve_chunks(B, nq, nt, chunks, &tpc);
+    const int c = nn_resolve_chunks(B, nq, nt, TT, QT, chunks, &tpc);
     return c <= 1 ? 0 : (size_t)B * c * nq * (sizeof(float) + sizeof(int32_t));
 }
 
 int sh_nearest_points(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* t, int64_t t_sb, int nt,
                       const int32_t* t_count, const uint8_t* t_mask, int64_t mask_sb, int B, int chunks, int32_t* idx, float* d2,
                       void* workspace, size_t workspace_bytes, sh_stream_t stream) {
-    SH_REQUIRE(q && t && idx && d2, SH_ERR_INVALID_ARG, "sh_nearest_points: null pointer");
-    SH_REQUIRE(B >= 0 && nq >= 0 && nt >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "sh_nearest_points: negative size (B %d, nq %d, nt %d, chunks %d)",
-               B, nq, nt, chunks);
-    if (B == 0 || nq == 0) return SH_OK;
-    SH_REQUIRE(q_sb >= 3L * nq && t_sb >= 3L * nt && (!t_mask || mask_sb == 0 || mask_sb >= nt), SH_ERR_INVALID_ARG,
-               "sh_nearest_points: batch stride shorter than a body (q_sb %ld, t_sb %ld, mask_sb %ld)", (long)q_sb, (long)t_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && nt < (1 << 30), SH_ERR_UNSUPPORTED, "sh_nearest_points: B, B*nq or nt too large");
-    NNParams p{};
-    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
-    p.t = t; p.t_sb = (long)t_sb; p.nt = nt; p.t_count = t_count;
-    p.mask = t_mask; p.mask_sb = (long)mask_sb;
-    p.chunks = nn_resolve_chunks(B, nq, nt, chunks, &p.tiles_per_chunk);
-    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_points: %d target chunks", p.chunks);
-    const size_t need = p.chunks <= 1 ? 0 : (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
-    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
-               "sh_nearest_points: workspace too small (%zu bytes needed for %d chunks)", need, p.chunks);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
-    if (p.chunks <= 1) {
-        ShProfScope ps(st, "nearest_search_kernel|B=%d nq=%d nt=%d chunks=1", B, nq, nt);
-        SH_LAUNCH_PS(ps, nearest_search_kernel, grid, dim3(NT), 0, st, p, idx, d2, 1);
-    } else {
-        float* part_d2 = static_cast<float*>(workspace);
-        int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
-        {
-            ShProfScope ps(st, "nearest_search_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
-            SH_LAUNCH_PS(ps, nearest_search_kernel, grid, dim3(NT), 0, st, p, part_idx, part_d2, 0);
-        }
-        ShProfScope ps(st, "nearest_merge_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
-        SH_LAUNCH_PS(ps, nearest_merge_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, part_idx, part_d2, q_count, B, nq,
-                     p.chunks, idx, d2);
-    }
-    SH_CHECK_LAUNCH("nearest_points");
-    return SH_OK;
+    const NNParams p{q, (long)q_sb, nq, q_count, t, (long)t_sb, nt, t_count, t_mask, (long)mask_sb, 0, 0};
+    return nn_search("sh_nearest_points", p, nullptr, B, chunks, idx, d2, workspace, workspace_bytes, stream);
 }
 
 int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* qn, int64_t qn_sb, const float* t,
                             int64_t t_sb, int nt, const int32_t* t_count, const float* tn, int64_t tn_sb, const uint8_t* t_mask,
                             int64_t mask_sb, float cos_min, int B, int chunks, int32_t* idx, float* d2, void* workspace,
                             size_t workspace_bytes, sh_stream_t stream) {
-    SH_REQUIRE(q && t && qn && tn && idx && d2, SH_ERR_INVALID_ARG, "sh_nearest_points_gated: null pointer");
-    SH_REQUIRE(B >= 0 && nq >= 0 && nt >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
-               "sh_nearest_points_gated: negative size (B %d, nq %d, nt %d, chunks %d)", B, nq, nt, chunks);
-    SH_REQUIRE(cos_min == cos_min, SH_ERR_INVALID_ARG, "sh_nearest_points_gated: cos_min is NaN");
-    if (B == 0 || nq == 0) return SH_OK;
-    SH_REQUIRE(q_sb >= 3L * nq && t_sb >= 3L * nt && qn_sb >= 3L * nq && tn_sb >= 3L * nt && (!t_mask || mask_sb == 0 || mask_sb >= nt),
-               SH_ERR_INVALID_ARG, "sh_nearest_points_gated: batch stride shorter than a body (q_sb %ld, qn_sb %ld, t_sb %ld, tn_sb %ld, mask_sb %ld)",
-               (long)q_sb, (long)qn_sb, (long)t_sb, (long)tn_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && nt < (1 << 30), SH_ERR_UNSUPPORTED, "sh_nearest_points_gated: B, B*nq or nt too large");
-    NNParams p{};
-    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
-    p.t = t; p.t_sb = (long)t_sb; p.nt = nt; p.t_count = t_count;
-    p.mask = t_mask; p.mask_sb = (long)mask_sb;
-    p.chunks = nn_resolve_chunks(B, nq, nt, chunks, &p.tiles_per_chunk);
-    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_points_gated: %d target chunks", p.chunks);
-    NNGate g{qn, (long)qn_sb, tn, (long)tn_sb, cos_min};
-    const size_t need = p.chunks <= 1 ? 0 : (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
-    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
-               "sh_nearest_points_gated: workspace too small (%zu bytes needed for %d chunks)", need, p.chunks);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
-    if (p.chunks <= 1) {
-        ShProfScope ps(st, "nearest_search_gated_kernel|B=%d nq=%d nt=%d chunks=1", B, nq, nt);
-        SH_LAUNCH_PS(ps, nearest_search_gated_kernel, grid, dim3(NT), 0, st, p, g, idx, d2, 1);
-    } else {
-        float* part_d2 = static_cast<float*>(workspace);
-        int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
-        {
-            ShProfScope ps(st, "nearest_search_gated_kernel|B=%d nq=%d nt=%d chunks=%d", B, nq, nt, p.chunks);
-            SH_LAUNCH_PS(ps, nearest_search_gated_kernel, grid, dim3(NT), 0, st, p, g, part_idx, part_d2, 0);
-        }
-        ShProfScope ps(st, "nearest_merge_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
-        SH_LAUNCH_PS(ps, nearest_merge_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, part_idx, part_d2, q_count, B, nq,
-                     p.chunks, idx, d2);
-    }
-    SH_CHECK_LAUNCH("nearest_points_gated");
-    return SH_OK;
+    SH_REQUIRE(qn && tn, SH_ERR_INVALID_ARG, "sh_nearest_points_gated: null pointer");
+    const NNParams p{q, (long)q_sb, nq, q_count, t, (long)t_sb, nt, t_count, t_mask, (long)mask_sb, 0, 0};
+    const NNGate g{qn, (long)qn_sb, tn, (long)tn_sb, cos_min};
+    return nn_search("sh_nearest_points_gated", p, &g, B, chunks, idx, d2, workspace, workspace_bytes, stream);
 }
 
 int sh_vertex_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const int32_t* vf_ptr, const int32_t* vf_idx, int B,

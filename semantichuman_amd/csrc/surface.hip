@@ -6,8 +6,7 @@
 // triangle whose fp32 distance is provably larger than the query's best so far, so the result equals the unculled sweep's bit
 // for bit; the unculled sweep is kept (cull = 0) as its yardstick.  No atomics of any kind in the kernels a fit runs (the
 // only atomics are two counters of the diagnostic instantiation the benchmark asks for with `stats`): (d2, face) is kept under the lexicographic minimum, the gradient sums run in a fixed order.
-#include "sh_common.h"
-#include <math.h>
+#include "sh_nn.h"
 
 namespace {
 
@@ -15,17 +14,10 @@ constexpr int NT = 256;          // threads per workgroup
 constexpr int QPT = 4;           // queries a thread keeps in registers
 constexpr int QT = NT * QPT;     // queries per workgroup; a wave owns 256 CONSECUTIVE ones (a spatially sorted scan keeps them close)
 constexpr int FT = 256;          // triangles per LDS tile: one global load per thread and tile
-constexpr int WG_SLOTS = 2048;   // workgroups the chip holds at once: the automatic split aims at this many
 constexpr int TRI = 12;          // floats per triangle record: a, ab, ac, |ab|^2, ab.ac, |ac|^2
 // Safety factor of the cull, applied to sqrt(best) and to the sphere's radius.  The rounding it has to cover is about 30 units
 // of 2^-24 (include/sh_kernels.h derives it); 2^-10 is 500 times that and costs no measurable number of extra region tests.
 constexpr float MARGIN = SH_SURFACE_MARGIN;
-
-__device__ __forceinline__ int clamp_count(const int32_t* cnt, int b, int rows) {
-    if (!cnt) return rows;
-    const int c = cnt[b];
-    return c < 0 ? 0 : (c > rows ? rows : c);
-}
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
     return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
@@ -175,8 +167,7 @@ __global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, 
                     bool any = false;
 #pragma unroll
                     for (int k = 0; k < QPT; ++k) {
-                        const float dx = qx[k] - X[e], dy = qy[k] - Y[e], dz = qz[k] - Z[e];
-                        const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+                        const float d = nn_d2(qx[k], qy[k], qz[k], X[e], Y[e], Z[e]);
                         const float t = rb[k] + R[e];
                         need[k] = !(d > t * t);                          // written so that a NaN asks for the test
                         any = any || need[k];
@@ -352,23 +343,6 @@ __global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restric
     o[0] = g0; o[1] = g1; o[2] = g2;
 }
 
-int sf_tiles(int nF) { return (nF + FT - 1) / FT; }
-
-// the split actually run for a request of `chunks` (0 = automatic: fill the chip): whole tiles per chunk, no empty chunk
-int sf_resolve_chunks(int B, int nq, int nF, int chunks, int* tiles_per_chunk) {
-    const int tiles = sf_tiles(nF) > 0 ? sf_tiles(nF) : 1;
-    long c = chunks;
-    if (c <= 0) {
-        const long wgs = (long)sh_cdiv(nq > 0 ? nq : 1, QT) * (B > 0 ? B : 1);
-        c = (WG_SLOTS + wgs - 1) / wgs;
-    }
-    if (c > tiles) c = tiles;
-    if (c < 1) c = 1;
-    const int tpc = sh_cdiv(tiles, (int)c);
-    *tiles_per_chunk = tpc;
-    return sh_cdiv(tiles, tpc);
-}
-
 size_t sf_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -377,13 +351,13 @@ extern "C" {
 
 int sh_nearest_surface_chunks(int B, int nq, int nF) {
     int tpc;
-    return sf_resolve_chunks(B, nq, nF, 0, &tpc);
+    return nn_resolve_chunks(B, nq, nF, FT, QT, 0, &tpc);
 }
 
 size_t sh_nearest_surface_workspace(int B, int nq, int nF, int chunks) {
     if (B <= 0 || nq <= 0 || nF < 0 || chunks < 0) return 0;
     int tpc;
-    const int c = sf_resolve_chunks(B, nq, nF, chunks, &tpc);
+    const int c = nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &tpc);
     return sf_align16((size_t)B * nF * sizeof(f32x4)) + sf_align16((size_t)B * nF * TRI * sizeof(float)) +
            (size_t)B * c * nq * (sizeof(float) + sizeof(int32_t));
 }
@@ -401,7 +375,7 @@ int sh_nearest_surface(const float* q, int64_t q_sb, int nq, const int32_t* q_co
     SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && (long)B * nF < (1L << 27), SH_ERR_UNSUPPORTED,
                "sh_nearest_surface: B, B*nq or B*nF too large");
     SurfParams p{};
-    p.chunks = sf_resolve_chunks(B, nq, nF, chunks, &p.tiles_per_chunk);
+    p.chunks = nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &p.tiles_per_chunk);
     SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_surface: %d triangle chunks", p.chunks);
     const size_t sph_bytes = sf_align16((size_t)B * nF * sizeof(f32x4)), tri_bytes = sf_align16((size_t)B * nF * TRI * sizeof(float));
     const size_t need = sph_bytes + tri_bytes + (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));

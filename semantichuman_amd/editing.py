@@ -232,19 +232,15 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
-    state = {"faces": faces, "normal_faces": normal_faces}
+    # one face table at most: a gate reads normal_faces (and scan.chamfer refuses faces= next to it), no gate reads faces alone
+    gated = normal_angle is not None
+    state = {"table": normal_faces if gated else faces}
 
     def objective(x_hat):
-        if normal_angle is not None:
-            if state["normal_faces"] is not None and not isinstance(state["normal_faces"], scan.FaceTable):
-                state["normal_faces"] = scan.FaceTable(state["normal_faces"], x_hat.shape[1] - 1, x_hat.device)
-            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=state["faces"], normal_angle=normal_angle,
-                                normal_faces=state["normal_faces"])
-        if state["faces"] is None:
-            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan)
-        if not isinstance(state["faces"], scan.FaceTable):                # validated and uploaded once, at the first decode
-            state["faces"] = scan.FaceTable(state["faces"], x_hat.shape[1] - 1, x_hat.device)
-        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=state["faces"])
+        if state["table"] is not None and not isinstance(state["table"], scan.FaceTable):    # validated and uploaded once, at the first decode
+            state["table"] = scan.FaceTable(state["table"], x_hat.shape[1] - 1, x_hat.device)
+        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=faces if gated else state["table"],
+                            normal_angle=normal_angle, normal_faces=state["table"] if gated else None)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():

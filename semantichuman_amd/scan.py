@@ -129,15 +129,17 @@ class ScanBatch:
     def __len__(self):
         return self.points.shape[0]
 
+    @classmethod
+    def _from_parts(cls, points, counts, host_counts, perm, normals):
+        """A ScanBatch around tensors that are already packed and resident: every field, nothing copied or checked."""
+        out = cls.__new__(cls)
+        out.points, out.counts, out.host_counts, out.perm, out.normals = points, counts, host_counts, perm, normals
+        return out
+
     def select(self, sl):
         """The bodies `sl` (a slice) as a ScanBatch sharing this one's memory."""
-        out = ScanBatch.__new__(ScanBatch)
-        out.perm = None if self.perm is None else self.perm[sl]
-        out.host_counts = self.host_counts[sl]
-        out.points = self.points[sl]
-        out.counts = self.counts[sl].contiguous()
-        out.normals = None if getattr(self, "normals", None) is None else self.normals[sl]
-        return out
+        return ScanBatch._from_parts(self.points[sl], self.counts[sl].contiguous(), self.host_counts[sl],
+                                     None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl])
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
@@ -211,7 +213,7 @@ def _normal_gate(what, normal_angle, normal_faces, scans, n, trunc, faces, devic
         raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
     if faces is not None:
         raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built" % what)
-    if getattr(scans, "normals", None) is None:
+    if scans.normals is None:
         raise ValueError("%s: normal_angle needs scan normals (ScanBatch(..., normals=))" % what)
     if normal_faces is None:
         raise ValueError("%s: normal_angle needs the model's triangles (normal_faces=, a FaceTable or an integer array)" % what)
@@ -347,23 +349,8 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     the gate and gives the ungated bits).  A zero ("unknown") normal is compatible only for angles >= 90.  A point with no
     compatible partner is recorded as idx -1, d2 +inf and counts as truncated: it adds trunc^2 and takes no part in the
     gradient or in `pose_update` - which is why a gate needs `trunc`.  Not built together with `faces=`."""
-    if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
-        raise RuntimeError("semantichuman_amd.scan.chamfer needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
-                           % getattr(x_hat, "device", type(x_hat)))
-    if not isinstance(scans, ScanBatch):
-        scans = ScanBatch(scans, x_hat.device)
-    B, rows, _ = ops._points(x_hat, "scan.chamfer")
-    if len(scans) != B:
-        raise ValueError("chamfer: %d bodies, %d scans" % (B, len(scans)))
-    n = rows - 1 if n is None else int(n)
-    if not 0 < n <= rows:
-        raise ValueError("chamfer: n = %d outside (0, %d]" % (n, rows))
-    w = float(w_model_to_scan)
-    if not w >= 0.0:
-        raise ValueError("chamfer: w_model_to_scan must be >= 0")
-    if trunc is not None and not float(trunc) > 0.0:
-        raise ValueError("chamfer: trunc must be > 0")
-    tau2 = math.inf if trunc is None else float(trunc) ** 2
+    scans, B, rows, n = _check_pair(x_hat, scans, n, "chamfer")
+    w, tau2 = _check_weights(w_model_to_scan, trunc, "chamfer")
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
     gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device)
     if faces is not None:
@@ -424,13 +411,9 @@ class Pose:
         beyond the counts zero; its normals, if any, rotated by R = A / scale through the same kernel) or fp32 HIP points
         [B, M, 3] with optional live counts [B] (-> tensor)."""
         if isinstance(points, ScanBatch):
-            out = ScanBatch.__new__(ScanBatch)
-            out.perm = getattr(points, "perm", None)
-            out.host_counts, out.counts = points.host_counts, points.counts
-            out.points = ops.transform_points(points.points, points.counts, self.packed)
-            nrm = getattr(points, "normals", None)
-            out.normals = None if nrm is None else ops.transform_points(nrm, points.counts, self.rotation_packed())
-            return out
+            nrm = None if points.normals is None else ops.transform_points(points.normals, points.counts, self.rotation_packed())
+            return ScanBatch._from_parts(ops.transform_points(points.points, points.counts, self.packed), points.counts, points.host_counts,
+                                         points.perm, nrm)
         B = ops._points(points, "scan.Pose.apply")[0]
         return ops.transform_points(points, ops._count_arg(counts, B, points.device), self.packed)
 
@@ -478,6 +461,16 @@ def _check_pair(x, scans, n, what):
     return scans, B, rows, n
 
 
+def _check_weights(w_model_to_scan, trunc, what):
+    """w_model_to_scan / trunc as `chamfer` and `align` take them -> (w, tau2)."""
+    w = float(w_model_to_scan)
+    if not w >= 0.0:
+        raise ValueError("%s: w_model_to_scan must be >= 0" % what)
+    if trunc is not None and not float(trunc) > 0.0:
+        raise ValueError("%s: trunc must be > 0" % what)
+    return w, (math.inf if trunc is None else float(trunc) ** 2)
+
+
 def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
     """The start pose that needs no matches: the scan's centroid onto the centroid of the (unmasked) model vertices and, with
     scale=True, its RMS radius onto theirs; the rotation is the identity.  x [B, rows, 3] on the GPU, n / vertex_mask as in
@@ -514,7 +507,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None)
                              m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
     ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
-    if getattr(scans, "normals", None) is not None and getattr(aligned, "normals", None) is not None:
+    if scans.normals is not None and aligned.normals is not None:
         ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)
     return part
 
@@ -544,12 +537,7 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     iters = int(iters)
     if iters < 0:
         raise ValueError("align: iters must be >= 0")
-    w = float(w_model_to_scan)
-    if not w >= 0.0:
-        raise ValueError("align: w_model_to_scan must be >= 0")
-    if trunc is not None and not float(trunc) > 0.0:
-        raise ValueError("align: trunc must be > 0")
-    tau2 = math.inf if trunc is None else float(trunc) ** 2
+    w, tau2 = _check_weights(w_model_to_scan, trunc, "align")
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
     x = x.detach()
     gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, None, x.device)
