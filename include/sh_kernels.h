@@ -677,6 +677,19 @@ SH_API int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const i
  *     [17] sum |q|^2  [18] active vertices of the range (model -> scan ranges only)
  * every element stored (a range beyond m_b holds zeros).  The order depends on M and n only, never on B or the grid.
  *
+ * sh_align_moments_surface.  sh_align_moments with the scan -> model partner on the model's SURFACE: idx_sm / d2_sm give way to
+ * what sh_nearest_surface recorded - faces int32 [nF][3] (one table for the batch), face [B][M], uv [B][M][2], d2 [B][M] (the
+ * surface distance).  A scan -> model pair j < m_b is kept iff 0 <= face[j] < nF, the face's three corner indices lie in [0, n)
+ * and d2[j] < tau2 (strict; the vertex mask is not consulted: the search has already refused a triangle with a masked corner).
+ * Its pair is (p, q) = (s_j, q_j), weight 1 / m_b, q_j the foot point: with a, b, c the corners x[f0], x[f1], x[f2] in the
+ * face's order and (v, w) = uv[j], per coordinate k
+ *     ab_k = fl32(b_k - a_k);  ac_k = fl32(c_k - a_k)                                (fp32, the differences of the search)
+ *     q_k = (double)a_k + ((double)v * (double)ab_k + (double)w * (double)ac_k)      (fp64, no contraction: two exact products,
+ *                                                                                     two rounded additions)
+ * The sums, the partials' layout, the ranges, the grid and the order are those of sh_align_moments; so are the model -> scan
+ * ranges (vertex x_i to scan point s[idx_ms[i]], as the model -> scan term of the surface Chamfer loss), and sh_align_solve
+ * finishes either call's partials.  nF >= 0; nF == 0 keeps no scan -> model pair.  One kernel template serves both calls.
+ *
  * sh_align_solve.  Stage 2 and the closed form, one wave per body.  The ranges' sums are added in range order per direction and
  * joined with the weights above into the moments, mom fp64 [B][SH_ALIGN_MOMENTS] (optional output):
  *     [0] W = sum w  [1..3] sum w p  [4..6] sum w q  [7..15] sum w q p^T  [16] sum w |p|^2  [17] sum w |q|^2  [18] pairs kept
@@ -694,7 +707,7 @@ SH_API int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const i
  *     dst[b][j][r] = fma(A[r][2], p_z, fma(A[r][1], p_y, fma(A[r][0], p_x, t[r])))          (fp32, three fused multiply-adds)
  * and 0 for rows j >= count[b].
  *
- * All three: B == 0 is SH_OK with nothing launched; null pointers and negative sizes are SH_ERR_INVALID_ARG before the device is
+ * All four: B == 0 is SH_OK with nothing launched; null pointers and negative sizes are SH_ERR_INVALID_ARG before the device is
  * touched; nothing allocates or synchronises.
  */
 enum sh_align_mode { SH_ALIGN_TRANSLATION = 0, SH_ALIGN_RIGID = 1, SH_ALIGN_SIMILARITY = 2 };
@@ -708,6 +721,10 @@ SH_API int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* 
                             const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
                             const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
                             sh_stream_t stream);
+SH_API int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows,
+                                    int n, const uint8_t* v_mask, int64_t mask_sb, const int32_t* faces, int nF, const int32_t* face,
+                                    const float* uv, const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms,
+                                    int B, double* partials, size_t partials_bytes, sh_stream_t stream);
 SH_API int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B,
                           const float* pose_in, const float* scale_in, float* pose_out, float* scale_out, float* inc, double* mom,
                           sh_stream_t stream);

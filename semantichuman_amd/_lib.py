@@ -85,6 +85,7 @@ SIGNATURES = {
     "sh_align_ranges": (c_int, [_I, _I, c_float]),
     "sh_align_partials_bytes": (c_size_t, [_I, _I, _I, c_float]),
     "sh_align_moments": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),
+    "sh_align_moments_surface": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),
     "sh_align_solve": (c_int, [_P, _I, _I, _P, c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sh_transform_points": (c_int, [_P, _L, _I, _P, _P, _I, _P, _P]),
     "sh_dataset_normalize": (c_int, [_P, _P, _I, _I, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P]),

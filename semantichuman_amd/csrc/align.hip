@@ -13,15 +13,32 @@ constexpr int NM = SH_ALIGN_MOMENTS;          // doubles per body of the finishe
 
 int ranges_of(int rows) { return (rows + RANGE - 1) / RANGE; }
 
+// The scan -> model partner of the surface form: which table the recorded face indexes, and the foot point's weights.  Empty
+// (all null) for the vertex form, which never reads it.
+struct AlignSurface {
+    const int32_t* faces;   // [nF][3]
+    int nF;
+    const float* uv;        // [B][M][2]
+};
+
+// One coordinate of the foot point, the header's expression: fp32 differences from corner a, then fp64 with no contraction.
+__device__ __forceinline__ double foot_coord(float a, float b, float c, float v, float w) {
+#pragma clang fp contract(off)
+    const float ab = b - a, ac = c - a;
+    return (double)a + ((double)v * (double)ab + (double)w * (double)ac);
+}
+
 // grid (range, body).  Ranges [0, r_sm) walk the scan -> model pairs j, ranges [r_sm, r_sm + r_ms) the model -> scan pairs i.
 // The sums are unweighted (the weight of a direction is one factor per body, applied by align_solve_kernel); a range beyond the
-// body's count stores zeros, which change nothing when the second stage adds them.
+// body's count stores zeros, which change nothing when the second stage adds them.  SURFACE: idx_sm / d2_sm are the recorded face
+// and the surface distance, and the partner of s_j is the foot point on that face instead of a vertex; nothing else differs.
+template <bool SURFACE>
 __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
                                                            const float* __restrict__ x, long x_sb, int rows, int n,
                                                            const unsigned char* __restrict__ v_mask, long mask_sb,
                                                            const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
                                                            const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms, float tau2,
-                                                           int r_sm, double* __restrict__ partials) {
+                                                           int r_sm, AlignSurface sf, double* __restrict__ partials) {
     __shared__ double red[NP][4];
     const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int R = gridDim.x;
@@ -31,9 +48,8 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
     double a[NP];
 #pragma unroll
     for (int c = 0; c < NP; ++c) a[c] = 0.0;
-    auto add = [&](long ip, long iq) {
+    auto add = [&](long ip, double q0, double q1, double q2) {
         const double p0 = sb[3 * ip], p1 = sb[3 * ip + 1], p2 = sb[3 * ip + 2];
-        const double q0 = xb[3 * iq], q1 = xb[3 * iq + 1], q2 = xb[3 * iq + 2];
         a[0] += 1.0;
         a[1] += p0; a[2] += p1; a[3] += p2;
         a[4] += q0; a[5] += q1; a[6] += q2;
@@ -47,7 +63,17 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
         const int lo = r * RANGE, hi = min(lo + RANGE, m);
         for (int j = lo + tid; j < hi; j += NT) {
             const int i = idx_sm[(long)b * M + j];
-            if (i >= 0 && i < n && d2_sm[(long)b * M + j] < tau2) add(j, i);
+            if (!(d2_sm[(long)b * M + j] < tau2)) continue;
+            if constexpr (SURFACE) {
+                if ((unsigned)i >= (unsigned)sf.nF) continue;
+                const int i0 = sf.faces[3L * i], i1 = sf.faces[3L * i + 1], i2 = sf.faces[3L * i + 2];
+                if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
+                const float v = sf.uv[2 * ((long)b * M + j)], w = sf.uv[2 * ((long)b * M + j) + 1];
+                const float *ca = xb + 3L * i0, *cb = xb + 3L * i1, *cc = xb + 3L * i2;
+                add(j, foot_coord(ca[0], cb[0], cc[0], v, w), foot_coord(ca[1], cb[1], cc[1], v, w), foot_coord(ca[2], cb[2], cc[2], v, w));
+            } else {
+                if (i >= 0 && i < n) add(j, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2]);
+            }
         }
     } else {
         const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
@@ -56,7 +82,7 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
             if (mb && mb[i] == 0) continue;
             a[18] += 1.0;                                                // n_act
             const int k = idx_ms[(long)b * rows + i];
-            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add(k, i);
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add(k, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2]);
         }
     }
 #pragma unroll
@@ -230,6 +256,42 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const float* __re
     o[0] = o0; o[1] = o1; o[2] = o2;
 }
 
+// sh_align_moments (sf == nullptr) and sh_align_moments_surface: the checks both make, the range arithmetic and the launch.
+// idx_sm / d2_sm are the surface form's face / d2.  `who` is the entry point's name in every error text.
+int align_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                  const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
+                  const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                  sh_stream_t stream) {
+    SH_REQUIRE(s && x && idx_sm && d2_sm && partials && (!sf || sf->uv) && (!sf || sf->faces || sf->nF == 0), SH_ERR_INVALID_ARG,
+               "%s: null pointer", who);
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows && (!sf || sf->nF >= 0), SH_ERR_INVALID_ARG,
+               "%s: bad size (B %d, M %d, rows %d, n %d, nF %d)", who, B, M, rows, n, sf ? sf->nF : 0);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "%s: w_ms and tau2 must be >= 0 (and not NaN)", who);
+    SH_REQUIRE(!(w_ms > 0.f) || (idx_ms && d2_ms), SH_ERR_INVALID_ARG, "%s: w_ms > 0 needs idx_ms and d2_ms", who);
+    if (B == 0) return SH_OK;
+    SH_REQUIRE(s_sb >= 3L * M && x_sb >= 3L * rows && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "%s: batch stride shorter than a body (s_sb %ld, x_sb %ld, mask_sb %ld)", who, (long)s_sb, (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * M < (1L << 30) && (long)B * rows < (1L << 30) && (!sf || sf->nF < (1 << 30)), SH_ERR_UNSUPPORTED,
+               "%s: B, B*M, B*rows or nF too large", who);
+    const int r_sm = ranges_of(M), R = sh_align_ranges(M, n, w_ms);
+    SH_REQUIRE(partials_bytes >= sh_align_partials_bytes(B, M, n, w_ms), SH_ERR_WORKSPACE, "%s: partials too small (%zu bytes needed)", who,
+               sh_align_partials_bytes(B, M, n, w_ms));
+    if (R == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)R, (unsigned)B);
+    if (sf) {
+        ShProfScope ps(st, "align_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d", B, M, n, sf->nF, R);
+        SH_LAUNCH_PS(ps, align_moments_kernel<true>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask, (long)mask_sb,
+                     idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
+    } else {
+        ShProfScope ps(st, "align_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
+        SH_LAUNCH_PS(ps, align_moments_kernel<false>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask, (long)mask_sb,
+                     idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
+    }
+    SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -247,25 +309,17 @@ size_t sh_align_partials_bytes(int B, int M, int n, float w_ms) {
 int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
                      const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
                      const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes, sh_stream_t stream) {
-    SH_REQUIRE(s && x && idx_sm && d2_sm && partials, SH_ERR_INVALID_ARG, "sh_align_moments: null pointer");
-    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "sh_align_moments: bad size (B %d, M %d, rows %d, n %d)",
-               B, M, rows, n);
-    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_align_moments: w_ms and tau2 must be >= 0 (and not NaN)");
-    SH_REQUIRE(!(w_ms > 0.f) || (idx_ms && d2_ms), SH_ERR_INVALID_ARG, "sh_align_moments: w_ms > 0 needs idx_ms and d2_ms");
-    if (B == 0) return SH_OK;
-    SH_REQUIRE(s_sb >= 3L * M && x_sb >= 3L * rows && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
-               "sh_align_moments: batch stride shorter than a body (s_sb %ld, x_sb %ld, mask_sb %ld)", (long)s_sb, (long)x_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * M < (1L << 30) && (long)B * rows < (1L << 30), SH_ERR_UNSUPPORTED, "sh_align_moments: B, B*M or B*rows too large");
-    const int r_sm = ranges_of(M), R = sh_align_ranges(M, n, w_ms);
-    SH_REQUIRE(partials_bytes >= sh_align_partials_bytes(B, M, n, w_ms), SH_ERR_WORKSPACE, "sh_align_moments: partials too small (%zu bytes needed)",
-               sh_align_partials_bytes(B, M, n, w_ms));
-    if (R == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ShProfScope ps(st, "align_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
-    SH_LAUNCH_PS(ps, align_moments_kernel, dim3((unsigned)R, (unsigned)B), dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
-                 (long)mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, partials);
-    SH_CHECK_LAUNCH("align_moments");
-    return SH_OK;
+    return align_moments("sh_align_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, nullptr, idx_ms, d2_ms, tau2,
+                         w_ms, B, partials, partials_bytes, stream);
+}
+
+int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                             const uint8_t* v_mask, int64_t mask_sb, const int32_t* faces, int nF, const int32_t* face, const float* uv,
+                             const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials,
+                             size_t partials_bytes, sh_stream_t stream) {
+    const AlignSurface sf{faces, nF, uv};
+    return align_moments("sh_align_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, face, d2, &sf, idx_ms, d2_ms, tau2,
+                         w_ms, B, partials, partials_bytes, stream);
 }
 
 int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,

@@ -250,7 +250,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
-                  normal_angle=None, normal_faces=None):
+                  normal_angle=None, normal_faces=None, align_on="vertices"):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -269,7 +269,10 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     degrees pass a start Pose), a similarity with w_model_to_scan = 0 from the identity can shrink the scan into the model (the
     defaults of stage 1 avoid it), partial scans want mode="rigid" with scan -> model only, and only the normalisations that are
     similarities (zeromean, zeroroot, onelength, small) can be undone by a pose.  faces (as in fit_scan) makes the FIT's scan ->
-    model term point-to-surface; both pose stages keep working on vertex pairs (no point-to-surface ICP).  normal_angle /
+    model term point-to-surface.  align_on: "vertices" (the default) - both pose stages work on vertex pairs, whatever the fit
+    measures; "surface" (needs faces) - both work on (scan point, foot point on the surface) pairs: stage 1 is
+    scan.align(..., faces=) and the in-loop update is scan.pose_update(..., surface=True) on the foot points the step's forward
+    pass has just found, so fit and pose lower one and the same surface Chamfer value.  normal_angle /
     normal_faces: the normal gate of scan.chamfer on every search of both stages (needs scans.normals, the model's triangles and
     trunc; the scan's normals follow the pose's rotation; None: none, the same bits as ever).  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
@@ -281,6 +284,11 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     align_iters, align_every = int(align_iters), int(align_every)
     if align_iters < 0 or align_every < 0:
         raise ValueError("register_scan: align_iters and align_every must be >= 0")
+    if align_on not in ("vertices", "surface"):
+        raise ValueError("register_scan: align_on must be 'vertices' or 'surface'")
+    on_surface = align_on == "surface"
+    if on_surface and faces is None:
+        raise ValueError("register_scan: align_on='surface' needs faces (the model's triangles)")
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -292,8 +300,11 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
             raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built")
         if normal_faces is not None and not isinstance(normal_faces, scan.FaceTable):
             normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
+    if on_surface and not isinstance(faces, scan.FaceTable):
+        faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
-                                  vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces)
+                                  vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
+                                  faces=faces if on_surface else None)
     matches = {} if align_every > 0 else None
     state = {"partials": None}
     if faces is not None and not isinstance(faces, scan.FaceTable):
@@ -305,7 +316,7 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
 
     def after_step(t):
         if (t + 1) % align_every == 0:
-            state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"])
+            state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"], surface=on_surface)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
                                 after_step=after_step if align_every > 0 else None)

@@ -564,6 +564,26 @@ def align_moments(s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_m
     return part
 
 
+def align_moments_surface(s, s_count, x, n, v_mask, mask_sb, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
+    """sh_align_moments_surface -> the ranges' partial sums, fp64 [B, ranges, 19]: sh_align_moments with the scan -> model partner
+    the foot point (face, uv) that sh_nearest_surface recorded on the table `faces` (int32 HIP [nF, 3]); d2 is the surface
+    distance."""
+    B, M, s_sb = _points(s, "align_moments_surface")
+    _, rows, x_sb = _points(x, "align_moments_surface")
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.align_moments_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
+    for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("semantichuman_amd.align_moments_surface: %s must be a contiguous %s HIP tensor %s" % (what, dtype, list(shape)))
+    lib = _lib.load()
+    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PARTIAL), dtype=torch.float64, device=s.device)
+    check(lib.sh_align_moments_surface(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(faces), faces.shape[0],
+                                       ptr(face), ptr(uv), ptr(d2), ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8,
+                                       stream_ptr()), "sh_align_moments_surface")
+    return part
+
+
 def align_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, inc=None, mom=None):
     """sh_align_solve: partial sums -> moments (mom fp64 [B, 20], optional), the pose increment (inc fp32 [B, 13], optional) and
     the pose (pose fp32 [B, 12], scale [B]) composed with it into pose_out / scale_out (which may be pose / scale themselves)."""

@@ -8,7 +8,8 @@
                                      w.r.t. x_hat through the recorded indices; with `faces=` the scan -> model term is measured
                                      to the surface (sh_nearest_surface, sh_chamfer_surface_bwd)
   * `Pose`, `moment_pose(...)`, `align(x, scans, ...)`  scan frame -> model frame: batched similarity ICP on the same matches
-                                     (sh_transform_points, sh_align_moments, sh_align_solve)
+                                     (sh_transform_points, sh_align_moments, sh_align_solve); with `faces=` the scan -> model
+                                     partner is the foot point on the surface (sh_nearest_surface, sh_align_moments_surface)
   * `ScanBatch(..., normals=)`, `vertex_normals(x, faces)`, `normal_angle=` on chamfer / align  matching by normal: the scan's
                                      normals and the model's area-weighted vertex normals (sh_vertex_normals) gate every pair of
                                      the vertex search (sh_nearest_points_gated) - off unless `normal_angle` is given
@@ -16,8 +17,8 @@
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
 model's normalised frame; `align` (and editing.register_scan, which alternates it with the fit) brings a scan there by a
-translation, a rigid motion or a similarity.  The alignment works on vertex pairs (no point-to-surface ICP); there is no file
-reader.  With `normal_angle` a pair is a match only when its two normals agree to within that angle (a point with no compatible
+translation, a rigid motion or a similarity.  The alignment works on vertex pairs, or with `faces=` on (scan point, foot point on
+the surface) pairs - point-to-surface ICP in the same closed form (sh_align_moments_surface); there is no file reader.  With `normal_angle` a pair is a match only when its two normals agree to within that angle (a point with no compatible
 partner counts as truncated, so a gate needs `trunc`); the gate applies to vertex pairs, not to the surface distance of `faces=`.
 The search, the loss and the alignment have no CPU path: tensors must live on the GPU.
 """
@@ -278,7 +279,7 @@ class _ChamferSurface(torch.autograd.Function):
         ctx.save_for_backward(x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts)
         if matches is not None:
             matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_v, idx_ms=idx_ms,
-                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm)
+                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces)
         return loss
 
     @staticmethod
@@ -340,7 +341,8 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     that point, and its gradient reaches the three corners of the face with the foot point's barycentric weights.  The model ->
     scan term (vertex to scan point), trunc, vertex_mask (a triangle with a masked corner is no target) and n keep their meaning.
     `matches` receives what it receives without faces - the VERTEX matches, which were computed for the search's bound - plus
-    `face`, `uv` and `d2_surface`; `pose_update` and `align` go on working on the vertex pairs.
+    `face`, `uv`, `d2_surface` and the table `faces`; `pose_update` works on the vertex pairs unless it is called with
+    surface=True, which takes the foot points instead.
 
     normal_angle: None (the default: everything above, bit for bit, whether or not the scans carry normals), or an angle in
     degrees in (0, 180].  Then a scan point and a vertex are a pair only when their normals - `scans.normals` and
@@ -496,15 +498,25 @@ def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
     return Pose(A.float(), (cx - c[:, None] * cs).float(), c.float())
 
 
-def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None):
+def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None, surface=False):
     """One closed-form pose step from recorded matches, no search: moments of the matched pairs (`matches`, as `chamfer(...,
     matches=)` or `align` fill it, found on `aligned`), the pose increment that minimises the same weighted squared distances,
     composed into `pose` in place, and `aligned.points` overwritten with the ORIGINAL `scans` under the new pose.  Three
     launches; when both batches carry normals, `aligned.normals` is overwritten with the ORIGINAL normals under the new pose's
-    rotation (one more sh_transform_points)."""
+    rotation (one more sh_transform_points).  surface=True: the scan -> model partner of a scan point is its foot point on the
+    model's surface (`face`, `uv`, `d2_surface` and `faces` of the matches, as `chamfer(..., faces=, matches=)` or
+    `align(..., faces=)` record them) instead of its nearest vertex - the step then lowers the surface Chamfer value; still three
+    launches.  ValueError if the matches carry no surface result."""
     m = matches
-    part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
-                             m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+    if surface:
+        if any(m.get(k) is None for k in ("face", "uv", "d2_surface", "faces")):
+            raise ValueError("pose_update: surface=True needs the matches of a surface search (chamfer(..., faces=, matches=) or "
+                             "align(..., faces=)); these carry none")
+        part = ops.align_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["faces"], m["face"], m["uv"],
+                                         m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+    else:
+        part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
+                                 m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
     ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
     if scans.normals is not None and aligned.normals is not None:
@@ -513,7 +525,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None)
 
 
 def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
-          normal_angle=None, normal_faces=None):
+          normal_angle=None, normal_faces=None, faces=None, cull=True):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -526,11 +538,22 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     every iteration (None: none, the same bits as ever); the model's normals are computed once, the scan's are carried by the
     pose's rotation from the ORIGINAL normals each iteration.  Needs scans.normals, normal_faces and trunc.
 
+    faces: None (the default: everything above, bit for bit), or the model's triangles (a FaceTable or an integer array [nF, 3]) -
+    point-to-surface ICP.  The scan -> model partner of a scan point is then the closest point of the SURFACE, the pairs and
+    weights are those of `chamfer(..., faces=)`, and it is that surface Chamfer value that the log holds and that every iteration
+    lowers.  Per iteration: the vertex search (its distance bounds the surface search; recorded as ever), `nearest_surface` into
+    buffers allocated once, the model -> scan search if w_model_to_scan > 0 (vertex to scan point, unchanged), the logged value,
+    then the surface moments (sh_align_moments_surface), the solve and the transform.  The face table is built once.  cull=False
+    makes the surface search test every (point, triangle) pair - same bits, many times the work.  A scan packed with
+    order="morton" makes the culled search cheaper.
+
     Limits.  ICP is local: the moment start fixes translation and scale, not rotation - a scan rotated by more than about 45
     degrees against the model needs a caller-supplied start pose (no principal-axes or multi-start search here).  mode
     "similarity" with w_model_to_scan = 0 and init="identity" can shrink the scan into the model; the defaults avoid it.
     Partial scans: mode="rigid", w_model_to_scan=0.  A similarity reaches the model's frame only under the normalisations that
-    are similarities (zeromean, zeroroot, onelength, small), not under gass or normal."""
+    are similarities (zeromean, zeroroot, onelength, small), not under gass or normal.  With faces= the closed form is still
+    point-to-point (on foot points), not the linearised point-to-plane step: along the surface it slides slowly.  faces= together
+    with normal_angle is not built, and the model -> scan term stays vertex to scan point."""
     scans, B, rows, n = _check_pair(x, scans, n, "align")
     if mode not in ops.ALIGN_MODES:
         raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
@@ -540,7 +563,8 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     w, tau2 = _check_weights(w_model_to_scan, trunc, "align")
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
     x = x.detach()
-    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, None, x.device)
+    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, faces, x.device)
+    ft = None if faces is None else _face_table(faces, n, x.device)                     # x is fixed: once
     if isinstance(init, Pose):
         if len(init) != B:
             raise ValueError("align: %d bodies, start pose for %d" % (B, len(init)))
@@ -560,6 +584,10 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         else (None, None)
     counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
     matches = dict(x=x, n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w, idx_sm=sm[0], d2_sm=sm[1], idx_ms=ms[0], d2_ms=ms[1])
+    if ft is not None:
+        sf = (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device),
+              torch.empty((B, M, 2), dtype=torch.float32, device=x.device))
+        matches.update(face=sf[0], d2_surface=sf[1], uv=sf[2], faces=ft.faces)
     part = None
     tn = qn = None
     if gate is not None and iters > 0:
@@ -569,8 +597,10 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         g_sm = None if gate is None else (aligned.normals, tn, gate[0])
         g_ms = None if gate is None else (qn, aligned.normals, gate[0])
         ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=g_sm)
+        if ft is not None:
+            ops.nearest_surface(aligned.points, x, ft.faces, n, cnt, v_mask, sm[1] if cull else None, chunks=chunks, cull=cull, out=sf)
         if w > 0.0:
             ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms, gate=g_ms)
-        ops.chamfer_fwd(sm[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
-        part = pose_update(pose, scans, aligned, matches, mode, partials=part)
+        ops.chamfer_fwd(sm[1] if ft is None else sf[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
+        part = pose_update(pose, scans, aligned, matches, mode, partials=part, surface=ft is not None)
     return pose, aligned, log
