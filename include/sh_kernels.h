@@ -707,8 +707,46 @@ SH_API int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const i
  *     dst[b][j][r] = fma(A[r][2], p_z, fma(A[r][1], p_y, fma(A[r][0], p_x, t[r])))          (fp32, three fused multiply-adds)
  * and 0 for rows j >= count[b].
  *
- * All four: B == 0 is SH_OK with nothing launched; null pointers and negative sizes are SH_ERR_INVALID_ARG before the device is
- * touched; nothing allocates or synchronises.
+ * Point-to-plane step.  sh_align_plane_moments / sh_align_plane_moments_surface / sh_align_plane_solve are the Gauss-Newton
+ * counterpart of the three calls above: the same pairs, kept rule, weights, ranges, grid and order (sh_align_ranges), but the
+ * residual of a kept pair is measured along the unit normal at the model-side partner.  Everything below is fp64, every
+ * operation rounded on its own (no contraction).  For a kept pair with p the (aligned) scan point (fp32, widened), q its
+ * partner and nrm the normal there:
+ *     r   = (nrm_0 (p_0 - q_0) + nrm_1 (p_1 - q_1)) + nrm_2 (p_2 - q_2)
+ *     J   = [ nrm_0, nrm_1, nrm_2,  p_1 nrm_2 - p_2 nrm_1,  p_2 nrm_0 - p_0 nrm_2,  p_0 nrm_1 - p_1 nrm_0,
+ *             (nrm_0 p_0 + nrm_1 p_1) + nrm_2 p_2 ]                                              (order: t, omega, sigma)
+ * J is the derivative of r under the linearised increment p' = p + omega x p + sigma p + t.  Partner and normal:
+ *     scan -> model, surface form:  q = the foot point of sh_align_moments_surface, unchanged; nrm = the normal of the recorded
+ *         face: ab = b - a, ac = c - a, c = (cx, cy, cz) the fp32 cross product of "Vertex normals" (fma(u, v, -(w * z))), then
+ *         fp64 len = sqrt((cx cx + cy cy) + cz cz), nrm = c / len (three divisions), the zero vector unless 0 < len < +inf
+ *     scan -> model, vertex form:   q = x[idx_sm[j]], nrm = tn[idx_sm[j]]
+ *     model -> scan, both forms:    q = x_i, p = s[idx_ms[i]], nrm = tn[i]
+ * tn fp32 contiguous [B][n][3] as sh_vertex_normals writes it (may be NULL for the surface form with w_ms == 0).  A zero
+ * normal contributes zeros to every sum; the pair still counts as kept.  partials: fp64
+ * [B][sh_align_ranges(M, n, w_ms)][SH_ALIGN_PLANE_PARTIAL], per range the UNWEIGHTED sums
+ *     [0] pairs kept  [1..28] sum J J^T, the upper triangle row-major ((0,0) (0,1) .. (0,6) (1,1) .. (6,6))  [29..35] sum J r
+ *     [36] sum r^2  [37] active vertices of the range (model -> scan ranges only)
+ * every element stored (a range beyond m_b holds zeros); thread t takes t, t + 256, ... of its range, then the fixed tree of
+ * sh_align_moments.  One kernel template serves both calls.
+ *
+ * sh_align_plane_solve.  One wave per body.  The ranges' sums are added in range order per direction and joined with the
+ * weights of sh_align_solve (1 / m_b, w_ms / n_act) into the system, sys fp64 [B][SH_ALIGN_PLANE_SYSTEM] (optional output):
+ *     [0] W = sum w  [1..28] H = sum w J J^T (upper triangle)  [29..35] g = sum w J r  [36] sum w r^2
+ * Lane 0 takes the leading k x k block, k = 3 (SH_ALIGN_TRANSLATION: t), 6 (SH_ALIGN_RIGID: t, omega) or 7; d_i = H_ii;
+ * Hs_ij = H_ij / (sqrt(d_i) sqrt(d_j)) (unit diagonal), gs_i = g_i / sqrt(d_i); Cholesky Hs = L L^T column by column with the
+ * pivot piv_j = Hs_jj - sum_{c<j} L_jc^2 (sums in ascending c), L_jj = sqrt(piv_j), L_ij = (Hs_ij - sum_{c<j} L_ic L_jc) / L_jj;
+ * L y = -gs, L^T z = y, delta_i = z_i / sqrt(d_i), delta_i = 0 for i >= k.  Fixed loop counts, no data-dependent branch.  Then
+ * c = exp(sigma); R = I + a K + b K^2 with K the cross-product matrix of omega, th2 = |omega|^2, a = sin(th) / th and
+ * b = (1 - cos(th)) / th2, or a = 1 - th2 / 6, b = 1/2 - th2 / 24 when th2 < 1e-8; t = delta_t.  The pose so far is composed
+ * with (c R, t) exactly as sh_align_solve composes, each value rounded to fp32 once, into pose_out / scale_out (may alias the
+ * inputs).  solved int32 [B]: 1, or 0 when W == 0, a d_i (i < k) is not positive and finite, a pivot is not >
+ * SH_ALIGN_PLANE_PIVOT_MIN (the block is singular to fp64 working precision: planar or parallel normals, too few pairs) or a
+ * delta_i is not finite - then the increment is the identity, bitwise, and the pose passes through.  The step is Gauss-Newton:
+ * it minimises the linearised sum w (r + J delta)^2, so the true weighted residual is not guaranteed to fall.  M, n, s_count
+ * and w_ms must be those of the moments call.
+ *
+ * All of them: B == 0 is SH_OK with nothing launched; null pointers and negative sizes are SH_ERR_INVALID_ARG before the device
+ * is touched; nothing allocates or synchronises.
  */
 enum sh_align_mode { SH_ALIGN_TRANSLATION = 0, SH_ALIGN_RIGID = 1, SH_ALIGN_SIMILARITY = 2 };
 #define SH_ALIGN_RANGE 2048
@@ -730,6 +768,22 @@ SH_API int sh_align_solve(const double* partials, int M, int n, const int32_t* s
                           sh_stream_t stream);
 SH_API int sh_transform_points(const float* src, int64_t src_sb, int M, const int32_t* count, const float* pose, int B, float* dst,
                                sh_stream_t stream);
+#define SH_ALIGN_PLANE_PARTIAL 38
+#define SH_ALIGN_PLANE_SYSTEM 37
+#define SH_ALIGN_PLANE_PIVOT_MIN 1e-12
+SH_API size_t sh_align_plane_partials_bytes(int B, int M, int n, float w_ms);
+SH_API int sh_align_plane_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows,
+                                  int n, const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm,
+                                  const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
+                                  double* partials, size_t partials_bytes, sh_stream_t stream);
+SH_API int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb,
+                                          int rows, int n, const uint8_t* v_mask, int64_t mask_sb, const float* tn,
+                                          const int32_t* faces, int nF, const int32_t* face, const float* uv, const float* d2,
+                                          const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials,
+                                          size_t partials_bytes, sh_stream_t stream);
+SH_API int sh_align_plane_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B,
+                                const float* pose_in, const float* scale_in, float* pose_out, float* scale_out, double* sys,
+                                int32_t* solved, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and

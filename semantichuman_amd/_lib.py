@@ -88,6 +88,11 @@ SIGNATURES = {
     "sh_align_moments_surface": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),
     "sh_align_solve": (c_int, [_P, _I, _I, _P, c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sh_transform_points": (c_int, [_P, _L, _I, _P, _P, _I, _P, _P]),
+    "sh_align_plane_partials_bytes": (c_size_t, [_I, _I, _I, c_float]),
+    "sh_align_plane_moments": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),
+    "sh_align_plane_moments_surface": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P,
+                                               c_size_t, _P]),
+    "sh_align_plane_solve": (c_int, [_P, _I, _I, _P, c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "sh_dataset_normalize": (c_int, [_P, _P, _I, _I, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P]),
     "sh_gather_meshes": (c_int, [_P, _L, _P, _I, _P, _P]),
     "sh_adam_step": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P] + [ctypes.c_double] * 4 + [_P]),

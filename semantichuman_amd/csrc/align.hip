@@ -10,6 +10,8 @@ constexpr int NT = 256;                       // threads per workgroup of the mo
 constexpr int RANGE = SH_ALIGN_RANGE;         // pairs per workgroup: thread t takes t, t + 256, ... of its range (8 each)
 constexpr int NP = SH_ALIGN_PARTIAL;          // sums per range
 constexpr int NM = SH_ALIGN_MOMENTS;          // doubles per body of the finished moments
+constexpr int NPP = SH_ALIGN_PLANE_PARTIAL;   // sums per range of the point-to-plane step
+constexpr int NPS = SH_ALIGN_PLANE_SYSTEM;    // doubles per body of its joined system
 
 int ranges_of(int rows) { return (rows + RANGE - 1) / RANGE; }
 
@@ -26,6 +28,20 @@ __device__ __forceinline__ double foot_coord(float a, float b, float c, float v,
 #pragma clang fp contract(off)
     const float ab = b - a, ac = c - a;
     return (double)a + ((double)v * (double)ab + (double)w * (double)ac);
+}
+
+// The unit normal of the face (a, b, c), the header's expression: the fp32 cross product of "Vertex normals", normalised in fp64;
+// the zero vector when its length is zero or not finite.
+__device__ __forceinline__ void face_normal(const float* a, const float* b, const float* c, double& n0, double& n1, double& n2) {
+#pragma clang fp contract(off)
+    const float abx = b[0] - a[0], aby = b[1] - a[1], abz = b[2] - a[2];
+    const float acx = c[0] - a[0], acy = c[1] - a[1], acz = c[2] - a[2];
+    const double cx = __builtin_fmaf(aby, acz, -(abz * acy)), cy = __builtin_fmaf(abz, acx, -(abx * acz)),
+                 cz = __builtin_fmaf(abx, acy, -(aby * acx));
+    const double len = sqrt((cx * cx + cy * cy) + cz * cz);
+    const bool ok = len > 0.0 && len < __builtin_inf();
+    const double d = ok ? len : 1.0;
+    n0 = ok ? cx / d : 0.0; n1 = ok ? cy / d : 0.0; n2 = ok ? cz / d : 0.0;
 }
 
 // grid (range, body).  Ranges [0, r_sm) walk the scan -> model pairs j, ranges [r_sm, r_sm + r_ms) the model -> scan pairs i.
@@ -92,6 +108,27 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
     }
     __syncthreads();
     if (tid < NP) partials[((long)b * R + r) * NP + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// The pose so far composed with the increment (c R, t): A_new = c R A_old, t_new = c R t_old + t, scale_new = c scale_old, each
+// rounded to fp32 once.  Everything is read before anything is written, so the outputs may alias the inputs.  Both solve kernels
+// end here.
+__device__ __forceinline__ void compose_pose(double c, const double (&Rm)[3][3], const double (&t)[3], const float* pi, double s0, float* po,
+                                             float* so) {
+    double A0[3][3], t0[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) A0[i][j] = pi[3 * i + j];
+        t0[i] = pi[9 + i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) po[3 * i + j] = (float)(c * (Rm[i][0] * A0[0][j] + Rm[i][1] * A0[1][j] + Rm[i][2] * A0[2][j]));
+        po[9 + i] = (float)(c * (Rm[i][0] * t0[0] + Rm[i][1] * t0[1] + Rm[i][2] * t0[2]) + t[i]);
+    }
+    *so = (float)(c * s0);
 }
 
 // One Jacobi rotation of the symmetric 4 x 4 matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.
@@ -219,23 +256,195 @@ __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restric
         }
         o[12] = (float)c;
     }
-    const float* pi = pose_in + (long)b * 12;
-    double A0[3][3], t0[3];
+    compose_pose(c, Rm, t, pose_in + (long)b * 12, scale_in[b], pose_out + (long)b * 12, scale_out + b);
+}
+
+// The point-to-plane step's stage 1: align_moments_kernel's grid, ranges, kept rule and tree, with the sums of the header's
+// "Point-to-plane step" - per kept pair the Jacobian row J (7) of the residual r along the partner's normal, J J^T (upper
+// triangle), J r and r^2.  fp64, contraction off.  SURFACE: the partner is the foot point and the normal that of the recorded
+// face, formed from the three corners the foot point needs anyway; otherwise partner and normal are gathered by idx_sm.
+template <bool SURFACE>
+__global__ __launch_bounds__(NT) void align_plane_moments_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
+                                                                 const float* __restrict__ x, long x_sb, int rows, int n,
+                                                                 const unsigned char* __restrict__ v_mask, long mask_sb,
+                                                                 const float* __restrict__ tn, const int32_t* __restrict__ idx_sm,
+                                                                 const float* __restrict__ d2_sm, const int32_t* __restrict__ idx_ms,
+                                                                 const float* __restrict__ d2_ms, float tau2, int r_sm, AlignSurface sf,
+                                                                 double* __restrict__ partials) {
+    __shared__ double red[NPP][4];
+    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int R = gridDim.x;
+    const int m = clamp_count(s_count, b, M);
+    const float* sb = s + (long)b * s_sb;
+    const float* xb = x + (long)b * x_sb;
+    const float* tb = tn ? tn + (long)b * n * 3 : nullptr;
+    double a[NPP];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int c = 0; c < NPP; ++c) a[c] = 0.0;
+    auto add = [&](long ip, double q0, double q1, double q2, double n0, double n1, double n2) {
+#pragma clang fp contract(off)
+        const double p0 = sb[3 * ip], p1 = sb[3 * ip + 1], p2 = sb[3 * ip + 2];
+        const double res = (n0 * (p0 - q0) + n1 * (p1 - q1)) + n2 * (p2 - q2);
+        const double J[7] = {n0, n1, n2, p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, (n0 * p0 + n1 * p1) + n2 * p2};
+        a[0] += 1.0;
+        int c = 1;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) A0[i][j] = pi[3 * i + j];
-        t0[i] = pi[9 + i];
+        for (int i = 0; i < 7; ++i)
+#pragma unroll
+            for (int j = i; j < 7; ++j) a[c++] += J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) a[29 + i] += J[i] * res;
+        a[36] += res * res;
+    };
+    if (r < r_sm) {                                                      // uniform over the workgroup
+        const int lo = r * RANGE, hi = min(lo + RANGE, m);
+        for (int j = lo + tid; j < hi; j += NT) {
+            const int i = idx_sm[(long)b * M + j];
+            if (!(d2_sm[(long)b * M + j] < tau2)) continue;
+            if constexpr (SURFACE) {
+                if ((unsigned)i >= (unsigned)sf.nF) continue;
+                const int i0 = sf.faces[3L * i], i1 = sf.faces[3L * i + 1], i2 = sf.faces[3L * i + 2];
+                if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
+                const float v = sf.uv[2 * ((long)b * M + j)], w = sf.uv[2 * ((long)b * M + j) + 1];
+                const float *ca = xb + 3L * i0, *cb = xb + 3L * i1, *cc = xb + 3L * i2;
+                double n0, n1, n2;
+                face_normal(ca, cb, cc, n0, n1, n2);
+                add(j, foot_coord(ca[0], cb[0], cc[0], v, w), foot_coord(ca[1], cb[1], cc[1], v, w), foot_coord(ca[2], cb[2], cc[2], v, w), n0, n1,
+                    n2);
+            } else {
+                if (i >= 0 && i < n) add(j, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
+            }
+        }
+    } else {
+        const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
+        const int lo = (r - r_sm) * RANGE, hi = min(lo + RANGE, n);
+        for (int i = lo + tid; i < hi; i += NT) {
+            if (mb && mb[i] == 0) continue;
+            a[37] += 1.0;                                                // n_act
+            const int k = idx_ms[(long)b * rows + i];
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2)
+                add(k, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
+        }
     }
-    const double s0 = scale_in[b];
-    float* po = pose_out + (long)b * 12;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) po[3 * i + j] = (float)(c * (Rm[i][0] * A0[0][j] + Rm[i][1] * A0[1][j] + Rm[i][2] * A0[2][j]));
-        po[9 + i] = (float)(c * (Rm[i][0] * t0[0] + Rm[i][1] * t0[1] + Rm[i][2] * t0[2]) + t[i]);
+    for (int c = 0; c < NPP; ++c) {
+        const double v = wave_sum_d(a[c]);
+        if ((tid & 63) == 0) red[c][tid >> 6] = v;
     }
-    scale_out[b] = (float)(c * s0);
+    __syncthreads();
+    if (tid < NPP) partials[((long)b * R + r) * NPP + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+}
+
+// The point-to-plane step's stage 2, one wave per body: lane c < NPP adds the ranges' sums of component c in range order per
+// direction, the two directions are joined with align_solve_kernel's weights, and lane 0 solves the leading k x k block of
+// H delta = -g (diagonal scaling, Cholesky; fixed loop counts, selects instead of branches: the rows and columns >= k are those of
+// the identity, so every mode runs the same 7 x 7 code), turns delta into (c R, t) and composes it with the pose so far.
+__global__ __launch_bounds__(64) void align_plane_solve_kernel(const double* __restrict__ partials, int M, int n, const int32_t* __restrict__ s_count,
+                                                              float w_ms, int r_sm, int r_ms, int k, const float* __restrict__ pose_in,
+                                                              const float* __restrict__ scale_in, float* __restrict__ pose_out,
+                                                              float* __restrict__ scale_out, double* __restrict__ sys,
+                                                              int32_t* __restrict__ solved) {
+#pragma clang fp contract(off)
+    __shared__ double sum[2][NPP];
+    __shared__ double sy[NPS];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int R = r_sm + r_ms;
+    if (lane < NPP) {
+        double u = 0.0, w = 0.0;
+        for (int r = 0; r < r_sm; ++r) u += partials[((long)b * R + r) * NPP + lane];
+        for (int r = r_sm; r < R; ++r) w += partials[((long)b * R + r) * NPP + lane];
+        sum[0][lane] = u; sum[1][lane] = w;
+    }
+    __syncthreads();
+    const int m = clamp_count(s_count, b, M);
+    const double n_act = sum[1][37];
+    const double w1 = m > 0 ? 1.0 / (double)m : 0.0;
+    const double w2 = (m > 0 && r_ms > 0 && n_act > 0.0) ? (double)w_ms / n_act : 0.0;
+    if (lane < NPS) sy[lane] = w1 * sum[0][lane] + w2 * sum[1][lane];
+    __syncthreads();
+    if (sys && lane < NPS) sys[(long)b * NPS + lane] = sy[lane];
+    if (lane != 0 || !pose_out) return;
+
+    bool ok = sy[0] > 0.0;
+    double H[7][7], sd[7], gs[7];
+    {
+        int c = 1;
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+#pragma unroll
+            for (int j = i; j < 7; ++j) { H[i][j] = sy[c]; H[j][i] = sy[c]; ++c; }
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const double d = H[i][i];
+        const bool good = d > 0.0 && d < __builtin_inf();
+        ok = ok && (i >= k || good);
+        sd[i] = (i < k && good) ? sqrt(d) : 1.0;
+        gs[i] = i < k ? sy[29 + i] / sd[i] : 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+#pragma unroll
+        for (int j = 0; j < 7; ++j) H[i][j] = (i < k && j < k) ? H[i][j] / (sd[i] * sd[j]) : (i == j ? 1.0 : 0.0);
+    double L[7][7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < j; ++c) acc += L[j][c] * L[j][c];
+        const double piv = H[j][j] - acc;
+        const bool pos = piv > SH_ALIGN_PLANE_PIVOT_MIN;                 // false for NaN
+        ok = ok && pos;
+        L[j][j] = sqrt(pos ? piv : 1.0);
+#pragma unroll
+        for (int i = j + 1; i < 7; ++i) {
+            double dot = 0.0;
+#pragma unroll
+            for (int c = 0; c < j; ++c) dot += L[i][c] * L[j][c];
+            L[i][j] = (H[i][j] - dot) / L[j][j];
+        }
+    }
+    double y[7], z[7], delta[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        double dot = 0.0;
+#pragma unroll
+        for (int c = 0; c < i; ++c) dot += L[i][c] * y[c];
+        y[i] = (-gs[i] - dot) / L[i][i];
+    }
+#pragma unroll
+    for (int i = 6; i >= 0; --i) {
+        double dot = 0.0;
+#pragma unroll
+        for (int c = i + 1; c < 7; ++c) dot += L[c][i] * z[c];
+        z[i] = (y[i] - dot) / L[i][i];
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        delta[i] = z[i] / sd[i];
+        ok = ok && fabs(delta[i]) < __builtin_inf();                     // false for NaN
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) delta[i] = (ok && i < k) ? delta[i] : 0.0;
+    const double c = exp(delta[6]);
+    const double o0 = delta[3], o1 = delta[4], o2 = delta[5];
+    const double th2 = (o0 * o0 + o1 * o1) + o2 * o2;
+    const bool tiny = th2 < 1e-8;
+    const double th = sqrt(tiny ? 1.0 : th2);
+    const double fa = tiny ? 1.0 - th2 / 6.0 : sin(th) / th;
+    const double fb = tiny ? 0.5 - th2 / 24.0 : (1.0 - cos(th)) / (tiny ? 1.0 : th2);
+    const double K[3][3] = {{0.0, -o2, o1}, {o2, 0.0, -o0}, {-o1, o0, 0.0}};
+    double Rm[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double k2 = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+            Rm[i][j] = (i == j ? 1.0 : 0.0) + (fa * K[i][j] + fb * k2);
+        }
+    const double t[3] = {delta[0], delta[1], delta[2]};
+    solved[b] = ok ? 1 : 0;
+    compose_pose(c, Rm, t, pose_in + (long)b * 12, scale_in[b], pose_out + (long)b * 12, scale_out + b);
 }
 
 // grid (tile of 256 points, body); the expression of the header, one fma chain per coordinate.
@@ -256,12 +465,13 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const float* __re
     o[0] = o0; o[1] = o1; o[2] = o2;
 }
 
-// sh_align_moments (sf == nullptr) and sh_align_moments_surface: the checks both make, the range arithmetic and the launch.
-// idx_sm / d2_sm are the surface form's face / d2.  `who` is the entry point's name in every error text.
-int align_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
-                  const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
-                  const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
-                  sh_stream_t stream) {
+// The checks every moments entry point makes, and the range arithmetic.  `per_range`: doubles a range stores.  *ranges: the grid's
+// first dimension, 0 when there is nothing to launch.  `who` is the entry point's name in every error text.
+int align_moments_check(const char* who, const float* s, int64_t s_sb, int M, const float* x, int64_t x_sb, int rows, int n, const uint8_t* v_mask,
+                        int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf, const int32_t* idx_ms,
+                        const float* d2_ms, float tau2, float w_ms, int B, const double* partials, size_t partials_bytes, int per_range,
+                        int* ranges) {
+    *ranges = 0;
     SH_REQUIRE(s && x && idx_sm && d2_sm && partials && (!sf || sf->uv) && (!sf || sf->faces || sf->nF == 0), SH_ERR_INVALID_ARG,
                "%s: null pointer", who);
     SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows && (!sf || sf->nF >= 0), SH_ERR_INVALID_ARG,
@@ -273,10 +483,24 @@ int align_moments(const char* who, const float* s, int64_t s_sb, int M, const in
                "%s: batch stride shorter than a body (s_sb %ld, x_sb %ld, mask_sb %ld)", who, (long)s_sb, (long)x_sb, (long)mask_sb);
     SH_REQUIRE(B <= 65535 && (long)B * M < (1L << 30) && (long)B * rows < (1L << 30) && (!sf || sf->nF < (1 << 30)), SH_ERR_UNSUPPORTED,
                "%s: B, B*M, B*rows or nF too large", who);
-    const int r_sm = ranges_of(M), R = sh_align_ranges(M, n, w_ms);
-    SH_REQUIRE(partials_bytes >= sh_align_partials_bytes(B, M, n, w_ms), SH_ERR_WORKSPACE, "%s: partials too small (%zu bytes needed)", who,
-               sh_align_partials_bytes(B, M, n, w_ms));
-    if (R == 0) return SH_OK;
+    const int R = sh_align_ranges(M, n, w_ms);
+    const size_t need = (size_t)B * R * per_range * sizeof(double);
+    SH_REQUIRE(partials_bytes >= need, SH_ERR_WORKSPACE, "%s: partials too small (%zu bytes needed)", who, need);
+    *ranges = R;
+    return SH_OK;
+}
+
+// sh_align_moments (sf == nullptr) and sh_align_moments_surface: the checks, then the launch.  idx_sm / d2_sm are the surface
+// form's face / d2.
+int align_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                  const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
+                  const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                  sh_stream_t stream) {
+    int R = 0;
+    const int rc = align_moments_check(who, s, s_sb, M, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, sf, idx_ms, d2_ms, tau2, w_ms, B, partials,
+                                       partials_bytes, NP, &R);
+    if (rc != SH_OK || R == 0) return rc;
+    const int r_sm = ranges_of(M);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)R, (unsigned)B);
     if (sf) {
@@ -289,6 +513,35 @@ int align_moments(const char* who, const float* s, int64_t s_sb, int M, const in
                      idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
     }
     SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
+
+// sh_align_plane_moments (sf == nullptr) and sh_align_plane_moments_surface: the same checks, the normals', then the launch.
+int align_plane_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                        const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
+                        const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                        sh_stream_t stream) {
+    int R = 0;
+    const int rc = align_moments_check(who, s, s_sb, M, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, sf, idx_ms, d2_ms, tau2, w_ms, B, partials,
+                                       partials_bytes, NPP, &R);
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(tn || (sf && !(w_ms > 0.f)), SH_ERR_INVALID_ARG, "%s: null pointer (tn: only the surface form with w_ms == 0 needs no vertex normals)",
+               who);
+    if (R == 0) return SH_OK;
+    SH_REQUIRE((long)B * n < (1L << 30), SH_ERR_UNSUPPORTED, "%s: B*n too large", who);
+    const int r_sm = ranges_of(M);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)R, (unsigned)B);
+    if (sf) {
+        ShProfScope ps(st, "align_plane_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d", B, M, n, sf->nF, R);
+        SH_LAUNCH_PS(ps, align_plane_moments_kernel<true>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
+    } else {
+        ShProfScope ps(st, "align_plane_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
+        SH_LAUNCH_PS(ps, align_plane_moments_kernel<false>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
+    }
+    SH_CHECK_LAUNCH(who + 3);
     return SH_OK;
 }
 
@@ -320,6 +573,48 @@ int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t*
     const AlignSurface sf{faces, nF, uv};
     return align_moments("sh_align_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, face, d2, &sf, idx_ms, d2_ms, tau2,
                          w_ms, B, partials, partials_bytes, stream);
+}
+
+size_t sh_align_plane_partials_bytes(int B, int M, int n, float w_ms) {
+    if (B <= 0) return 0;
+    return (size_t)B * sh_align_ranges(M, n, w_ms) * NPP * sizeof(double);
+}
+
+int sh_align_plane_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                           const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm,
+                           const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                           sh_stream_t stream) {
+    return align_plane_moments("sh_align_plane_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, idx_sm, d2_sm, nullptr, idx_ms,
+                               d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+}
+
+int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                                   const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* faces, int nF, const int32_t* face,
+                                   const float* uv, const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
+                                   double* partials, size_t partials_bytes, sh_stream_t stream) {
+    const AlignSurface sf{faces, nF, uv};
+    return align_plane_moments("sh_align_plane_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, face, d2, &sf, idx_ms,
+                               d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+}
+
+int sh_align_plane_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,
+                         const float* scale_in, float* pose_out, float* scale_out, double* sys, int32_t* solved, sh_stream_t stream) {
+    SH_REQUIRE(partials && (sys || pose_out), SH_ERR_INVALID_ARG, "sh_align_plane_solve: null pointer");
+    SH_REQUIRE(!pose_out || (pose_in && scale_in && scale_out && solved), SH_ERR_INVALID_ARG,
+               "sh_align_plane_solve: pose_out needs pose_in, scale_in, scale_out and solved");
+    SH_REQUIRE(B >= 0 && M >= 0 && n >= 0, SH_ERR_INVALID_ARG, "sh_align_plane_solve: bad size (B %d, M %d, n %d)", B, M, n);
+    SH_REQUIRE(w_ms >= 0.f, SH_ERR_INVALID_ARG, "sh_align_plane_solve: w_ms must be >= 0 (and not NaN)");
+    SH_REQUIRE(mode == SH_ALIGN_TRANSLATION || mode == SH_ALIGN_RIGID || mode == SH_ALIGN_SIMILARITY, SH_ERR_INVALID_ARG,
+               "sh_align_plane_solve: unknown mode %d", mode);
+    if (B == 0) return SH_OK;
+    const int r_sm = ranges_of(M), r_ms = w_ms > 0.f ? ranges_of(n) : 0;
+    const int k = mode == SH_ALIGN_TRANSLATION ? 3 : (mode == SH_ALIGN_RIGID ? 6 : 7);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, "align_plane_solve_kernel|B=%d ranges=%d mode=%d", B, r_sm + r_ms, mode);
+    SH_LAUNCH_PS(ps, align_plane_solve_kernel, dim3((unsigned)B), dim3(64), 0, st, partials, M, n, s_count, w_ms, r_sm, r_ms, k, pose_in, scale_in,
+                 pose_out, scale_out, sys, solved);
+    SH_CHECK_LAUNCH("align_plane_solve");
+    return SH_OK;
 }
 
 int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,

@@ -250,7 +250,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
-                  normal_angle=None, normal_faces=None, align_on="vertices"):
+                  normal_angle=None, normal_faces=None, align_on="vertices", align_step="point"):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -274,7 +274,11 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     scan.align(..., faces=) and the in-loop update is scan.pose_update(..., surface=True) on the foot points the step's forward
     pass has just found, so fit and pose lower one and the same surface Chamfer value.  normal_angle /
     normal_faces: the normal gate of scan.chamfer on every search of both stages (needs scans.normals, the model's triangles and
-    trunc; the scan's normals follow the pose's rotation; None: none, the same bits as ever).  No file reader."""
+    trunc; the scan's normals follow the pose's rotation; None: none, the same bits as ever).  align_step: "point" (the default:
+    everything above, bit for bit) or "plane" - both pose stages take the linearised point-to-plane step (scan.align(...,
+    step="plane") and scan.pose_update(..., step="plane")) on the pairs `align_on` selects; it needs the model's triangles for the
+    normals (faces, or normal_faces).  That step is Gauss-Newton, so a pose update is not guaranteed to lower the Chamfer value, and
+    a body whose system is singular (too few or parallel normals) keeps its pose for that update.  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -286,6 +290,10 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
         raise ValueError("register_scan: align_iters and align_every must be >= 0")
     if align_on not in ("vertices", "surface"):
         raise ValueError("register_scan: align_on must be 'vertices' or 'surface'")
+    if align_step not in ("point", "plane"):
+        raise ValueError("register_scan: align_step must be 'point' or 'plane'")
+    if align_step == "plane" and faces is None and normal_faces is None:
+        raise ValueError("register_scan: align_step='plane' needs the model's triangles (faces or normal_faces)")
     on_surface = align_on == "surface"
     if on_surface and faces is None:
         raise ValueError("register_scan: align_on='surface' needs faces (the model's triangles)")
@@ -300,11 +308,16 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
             raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built")
         if normal_faces is not None and not isinstance(normal_faces, scan.FaceTable):
             normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
-    if on_surface and not isinstance(faces, scan.FaceTable):
+    if (on_surface or align_step == "plane") and faces is not None and not isinstance(faces, scan.FaceTable):
         faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
+    if align_step == "plane":                                                           # the table the vertex normals come from
+        if normal_faces is None:
+            normal_faces = faces
+        elif not isinstance(normal_faces, scan.FaceTable):
+            normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
                                   vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
-                                  faces=faces if on_surface else None)
+                                  faces=faces if on_surface else None, step=align_step)
     matches = {} if align_every > 0 else None
     state = {"partials": None}
     if faces is not None and not isinstance(faces, scan.FaceTable):
@@ -316,7 +329,8 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
 
     def after_step(t):
         if (t + 1) % align_every == 0:
-            state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"], surface=on_surface)
+            state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"], surface=on_surface,
+                                                 step=align_step)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
                                 after_step=after_step if align_every > 0 else None)

@@ -592,6 +592,66 @@ def align_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out
                                      ptr(inc), ptr(mom), stream_ptr()), "sh_align_solve")
 
 
+ALIGN_PLANE_PARTIAL, ALIGN_PLANE_SYSTEM = 38, 37                # SH_ALIGN_PLANE_PARTIAL, SH_ALIGN_PLANE_SYSTEM
+
+
+def _plane_normals(tn, B, n, what, needed):
+    """The vertex normals a point-to-plane call takes: None (allowed only where none are read) or contiguous fp32 HIP [B, n, 3]."""
+    if tn is None:
+        if needed:
+            raise RuntimeError("semantichuman_amd.%s needs the vertex normals tn [%d, %d, 3] (sh_vertex_normals)" % (what, B, n))
+        return None
+    if not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous() and tuple(tn.shape) == (B, n, 3)):
+        raise RuntimeError("semantichuman_amd.%s: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (what, B, n))
+    return tn
+
+
+def align_plane_moments(s, s_count, x, n, v_mask, mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
+    """sh_align_plane_moments -> the ranges' partial sums of the point-to-plane step, fp64 [B, ranges, 38] (stage 1;
+    sh_align_plane_solve finishes them).  tn: the vertex normals, contiguous fp32 [B, n, 3]."""
+    B, M, s_sb = _points(s, "align_plane_moments")
+    _, rows, x_sb = _points(x, "align_plane_moments")
+    tn = _plane_normals(tn, B, n, "align_plane_moments", True)
+    lib = _lib.load()
+    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PLANE_PARTIAL), dtype=torch.float64, device=s.device)
+    check(lib.sh_align_plane_moments(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(tn), ptr(idx_sm), ptr(d2_sm),
+                                     ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), "sh_align_plane_moments")
+    return part
+
+
+def align_plane_moments_surface(s, s_count, x, n, v_mask, mask_sb, tn, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
+    """sh_align_plane_moments_surface -> fp64 [B, ranges, 38]: sh_align_plane_moments with the scan -> model partner the foot point
+    (face, uv) that sh_nearest_surface recorded on the table `faces` and the normal that face's; tn (the model -> scan pairs'
+    normals) may be None when w_ms == 0."""
+    B, M, s_sb = _points(s, "align_plane_moments_surface")
+    _, rows, x_sb = _points(x, "align_plane_moments_surface")
+    tn = _plane_normals(tn, B, n, "align_plane_moments_surface", w_ms > 0)
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.align_plane_moments_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
+    for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("semantichuman_amd.align_plane_moments_surface: %s must be a contiguous %s HIP tensor %s" % (what, dtype, list(shape)))
+    lib = _lib.load()
+    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PLANE_PARTIAL), dtype=torch.float64, device=s.device)
+    check(lib.sh_align_plane_moments_surface(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(tn), ptr(faces),
+                                             faces.shape[0], ptr(face), ptr(uv), ptr(d2), ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part),
+                                             part.numel() * 8, stream_ptr()), "sh_align_plane_moments_surface")
+    return part
+
+
+def align_plane_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, sys=None, solved=None):
+    """sh_align_plane_solve: partial sums -> the joined system (sys fp64 [B, 37], optional), its Gauss-Newton increment composed
+    with the pose (pose fp32 [B, 12], scale [B]) into pose_out / scale_out (which may be pose / scale themselves), and solved int32
+    [B] (0: the system was singular and the pose passed through); returns solved."""
+    B = part.shape[0]
+    if pose_out is not None and solved is None:
+        solved = torch.empty(B, dtype=torch.int32, device=part.device)
+    check(_lib.load().sh_align_plane_solve(ptr(part), M, n, ptr(s_count), w_ms, ALIGN_MODES[mode], B, ptr(pose), ptr(scale), ptr(pose_out),
+                                           ptr(scale_out), ptr(sys), ptr(solved), stream_ptr()), "sh_align_plane_solve")
+    return solved
+
+
 def transform_points(src, count, pose, out=None):
     """sh_transform_points: dst[b, j] = A_b src[b, j] + t_b for j < count[b], zero rows beyond; pose fp32 contiguous [B, 12]."""
     B, M, src_sb = _points(src, "transform_points")

@@ -9,7 +9,9 @@
                                      to the surface (sh_nearest_surface, sh_chamfer_surface_bwd)
   * `Pose`, `moment_pose(...)`, `align(x, scans, ...)`  scan frame -> model frame: batched similarity ICP on the same matches
                                      (sh_transform_points, sh_align_moments, sh_align_solve); with `faces=` the scan -> model
-                                     partner is the foot point on the surface (sh_nearest_surface, sh_align_moments_surface)
+                                     partner is the foot point on the surface (sh_nearest_surface, sh_align_moments_surface);
+                                     with `step="plane"` the pose step is the linearised point-to-plane (Gauss-Newton) step along
+                                     the model's normals (sh_align_plane_moments, sh_align_plane_solve) instead of the closed form
   * `ScanBatch(..., normals=)`, `vertex_normals(x, faces)`, `normal_angle=` on chamfer / align  matching by normal: the scan's
                                      normals and the model's area-weighted vertex normals (sh_vertex_normals) gate every pair of
                                      the vertex search (sh_nearest_points_gated) - off unless `normal_angle` is given
@@ -279,7 +281,7 @@ class _ChamferSurface(torch.autograd.Function):
         ctx.save_for_backward(x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts)
         if matches is not None:
             matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_v, idx_ms=idx_ms,
-                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces)
+                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces, tn=None)
         return loss
 
     @staticmethod
@@ -295,7 +297,7 @@ class _Chamfer(torch.autograd.Function):
     def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms, matches=None, gate=None):
         s, cnt = scans.points, scans.counts
         rows = x.shape[1]
-        g_sm = g_ms = None
+        g_sm = g_ms = tn = None
         if gate is not None:                                                        # (cos_min, FaceTable): both directions gated
             cos_min, ft = gate
             tn = ops.vertex_normals(x.detach(), ft.faces, ft.vf_ptr, ft.vf_idx, n)  # once per forward pass
@@ -310,7 +312,7 @@ class _Chamfer(torch.autograd.Function):
         ctx.save_for_backward(x, idx_sm, d2_sm, idx_ms, d2_ms, counts)
         if matches is not None:
             matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_sm, idx_ms=idx_ms,
-                           d2_ms=d2_ms)
+                           d2_ms=d2_ms, tn=tn)
         return loss
 
     @staticmethod
@@ -342,7 +344,9 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     scan term (vertex to scan point), trunc, vertex_mask (a triangle with a masked corner is no target) and n keep their meaning.
     `matches` receives what it receives without faces - the VERTEX matches, which were computed for the search's bound - plus
     `face`, `uv`, `d2_surface` and the table `faces`; `pose_update` works on the vertex pairs unless it is called with
-    surface=True, which takes the foot points instead.
+    surface=True, which takes the foot points instead.  Whenever a face table is at hand (`faces`, or `normal_faces` with or
+    without a gate) `matches` also receives it as `normal_faces`, a FaceTable (else None) - what `pose_update(..., step="plane")`
+    computes the model's normals from - and a gated pass records the normals it has computed as `tn` (else None).
 
     normal_angle: None (the default: everything above, bit for bit, whether or not the scans carry normals), or an angle in
     degrees in (0, 180].  Then a scan point and a vertex are a pair only when their normals - `scans.normals` and
@@ -356,15 +360,25 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
     gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device)
     if faces is not None:
-        return _ChamferSurface.apply(x_hat, scans, _face_table(faces, n, x_hat.device).faces, n, v_mask, mask_sb, tau2, w, matches)
-    return _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches, gate)
+        ft = _face_table(faces, n, x_hat.device)
+        loss = _ChamferSurface.apply(x_hat, scans, ft.faces, n, v_mask, mask_sb, tau2, w, matches)
+    else:
+        ft = gate[1] if gate is not None else (None if normal_faces is None or matches is None else _face_table(normal_faces, n, x_hat.device))
+        loss = _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches, gate)
+    if matches is not None:
+        matches.update(normal_faces=ft)
+    return loss
 
 
 # ------------------------------------------------------------------------------------------------ alignment
 class Pose:
     """B similarities scan frame -> model frame, s' = A s + t with A = scale * R (R a proper rotation, scale > 0).  One fp32
     buffer `packed` [B, 12] (A row-major, then t - the layout of include/sh_kernels.h) of which `A` [B, 3, 3] and `t` [B, 3] are
-    views, plus `scale` [B].  Lives wherever its tensors live; `apply` runs on the GPU only."""
+    views, plus `scale` [B].  Lives wherever its tensors live; `apply` runs on the GPU only.  `solved` is None except on the pose
+    `align(..., step="plane")` returns, where it is int32 [iters, B]: row k tells which bodies' k-th point-to-plane system was
+    solved (0: singular, that step left the pose as it was)."""
+
+    solved = None
 
     def __init__(self, A, t, scale=None):
         A = torch.as_tensor(A, dtype=torch.float32)
@@ -498,7 +512,24 @@ def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
     return Pose(A.float(), (cx - c[:, None] * cs).float(), c.float())
 
 
-def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None, surface=False):
+def _plane_normals(what, m, surface):
+    """The vertex normals a point-to-plane step on the matches m reads: None when it reads none (surface form, scan -> model only),
+    m["tn"] when the matches carry them, else computed from the FaceTable m["normal_faces"] (one sh_vertex_normals)."""
+    if surface and not m["w_ms"] > 0.0:
+        return None
+    tn = m.get("tn")
+    if tn is None:
+        ft = m.get("normal_faces")
+        if not isinstance(ft, FaceTable):
+            raise ValueError("%s: step='plane' needs the model's normals - matches recorded with a face table (faces= or normal_faces=), or a "
+                             "'normal_faces' FaceTable / 'tn' entry put into them" % what)
+        if ft.n != m["n"]:
+            raise ValueError("%s: the face table was made for %d vertices, the model has %d" % (what, ft.n, m["n"]))
+        tn = ops.vertex_normals(m["x"], ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
+    return tn
+
+
+def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None, surface=False, step="point", solved=None):
     """One closed-form pose step from recorded matches, no search: moments of the matched pairs (`matches`, as `chamfer(...,
     matches=)` or `align` fill it, found on `aligned`), the pose increment that minimises the same weighted squared distances,
     composed into `pose` in place, and `aligned.points` overwritten with the ORIGINAL `scans` under the new pose.  Three
@@ -506,18 +537,41 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     rotation (one more sh_transform_points).  surface=True: the scan -> model partner of a scan point is its foot point on the
     model's surface (`face`, `uv`, `d2_surface` and `faces` of the matches, as `chamfer(..., faces=, matches=)` or
     `align(..., faces=)` record them) instead of its nearest vertex - the step then lowers the surface Chamfer value; still three
-    launches.  ValueError if the matches carry no surface result."""
+    launches.  ValueError if the matches carry no surface result.
+
+    step: "point" (the default: everything above, bit for bit) or "plane" - the linearised point-to-plane step on the same pairs
+    (sh_align_plane_moments / _surface, sh_align_plane_solve): the residual of a pair is measured along the model's normal at the
+    partner (the recorded face's normal for a foot point, the vertex normal otherwise), and the increment solves the 3 / 6 / 7
+    normal equations of `mode`.  Still three launches, plus one sh_vertex_normals when vertex normals are read (vertex form, or
+    w_model_to_scan > 0) and the matches carry none as `tn`; they are then computed from the matches' `normal_faces` FaceTable
+    (recorded by `chamfer` whenever it was given faces= or normal_faces=).  The step is Gauss-Newton: it minimises the linearised
+    residual, so the Chamfer value is not guaranteed to fall.  solved: None, or an int32 HIP tensor [B] that receives 1 per body
+    whose system was solved and 0 where it was singular to working precision (no pairs, too few, planar or parallel normals) -
+    that body's pose is left exactly as it was.  ValueError when the normals are needed and cannot be had."""
     m = matches
-    if surface:
-        if any(m.get(k) is None for k in ("face", "uv", "d2_surface", "faces")):
-            raise ValueError("pose_update: surface=True needs the matches of a surface search (chamfer(..., faces=, matches=) or "
-                             "align(..., faces=)); these carry none")
-        part = ops.align_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["faces"], m["face"], m["uv"],
-                                         m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+    if step not in ("point", "plane"):
+        raise ValueError("pose_update: step must be 'point' or 'plane'")
+    if surface and any(m.get(k) is None for k in ("face", "uv", "d2_surface", "faces")):
+        raise ValueError("pose_update: surface=True needs the matches of a surface search (chamfer(..., faces=, matches=) or "
+                         "align(..., faces=)); these carry none")
+    if step == "plane":
+        tn = _plane_normals("pose_update", m, surface)
+        if surface:
+            part = ops.align_plane_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], tn, m["faces"], m["face"],
+                                                   m["uv"], m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+        else:
+            part = ops.align_plane_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], tn, m["idx_sm"], m["d2_sm"],
+                                           m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+        ops.align_plane_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale,
+                              solved=solved)
     else:
-        part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
-                                 m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
-    ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
+        if surface:
+            part = ops.align_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["faces"], m["face"], m["uv"],
+                                             m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+        else:
+            part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
+                                     m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
+        ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
     if scans.normals is not None and aligned.normals is not None:
         ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)
@@ -525,7 +579,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
 
 
 def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
-          normal_angle=None, normal_faces=None, faces=None, cull=True):
+          normal_angle=None, normal_faces=None, faces=None, cull=True, step="point"):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -552,8 +606,18 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     "similarity" with w_model_to_scan = 0 and init="identity" can shrink the scan into the model; the defaults avoid it.
     Partial scans: mode="rigid", w_model_to_scan=0.  A similarity reaches the model's frame only under the normalisations that
     are similarities (zeromean, zeroroot, onelength, small), not under gass or normal.  With faces= the closed form is still
-    point-to-point (on foot points), not the linearised point-to-plane step: along the surface it slides slowly.  faces= together
-    with normal_angle is not built, and the model -> scan term stays vertex to scan point."""
+    point-to-point (on foot points): along the surface it slides slowly - step="plane" is the remedy.  faces= together
+    with normal_angle is not built, and the model -> scan term stays vertex to scan point.
+
+    step: "point" (the default: everything above, bit for bit) or "plane" - every iteration's pose step is the linearised
+    point-to-plane step of `pose_update(..., step="plane")` on the same pairs: a scan point may slide along the model's surface
+    and is pulled along the normal only.  On noise-free surface samples of the 170-vertex model, float64, it is within 1e-3 of the
+    extent after 3 to 5 iterations where the closed form needs more than 20 (tests/align_plane_ref.py).  The model's vertex
+    normals are needed in vertex form and whenever w_model_to_scan > 0; x is fixed, so they are computed once before the loop
+    (shared with the gate's when normal_angle is given) from `faces`, or in vertex form from `normal_faces` - ValueError when
+    neither is given.  The step is Gauss-Newton, without damping or line search: the logged value is not guaranteed to fall.  The
+    returned pose carries `solved`, int32 [iters, B]: 0 where a body's system was singular to working precision (no kept pair, too
+    few, planar or parallel normals) - that iteration left that body's pose exactly as it was."""
     scans, B, rows, n = _check_pair(x, scans, n, "align")
     if mode not in ops.ALIGN_MODES:
         raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
@@ -565,6 +629,15 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     x = x.detach()
     gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, faces, x.device)
     ft = None if faces is None else _face_table(faces, n, x.device)                     # x is fixed: once
+    if step not in ("point", "plane"):
+        raise ValueError("align: step must be 'point' or 'plane'")
+    nt = gate[1] if gate is not None else None                                          # the table the vertex normals come from
+    if step == "plane" and nt is None and (ft is None or w > 0.0):
+        if ft is None and normal_faces is None:
+            raise ValueError("align: step='plane' on vertex pairs needs the model's triangles (normal_faces=, a FaceTable or an integer array)")
+        nt = ft if ft is not None else _face_table(normal_faces, n, x.device)
+        if nt.n != n:
+            raise ValueError("align: the face table was made for %d vertices, the model has %d" % (nt.n, n))
     if isinstance(init, Pose):
         if len(init) != B:
             raise ValueError("align: %d bodies, start pose for %d" % (B, len(init)))
@@ -590,9 +663,13 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         matches.update(face=sf[0], d2_surface=sf[1], uv=sf[2], faces=ft.faces)
     part = None
     tn = qn = None
-    if gate is not None and iters > 0:
-        tn = ops.vertex_normals(x, gate[1].faces, gate[1].vf_ptr, gate[1].vf_idx, n)    # x is fixed: once
-        qn = _query_normals(tn, rows) if w > 0.0 else None
+    if nt is not None and iters > 0:
+        tn = ops.vertex_normals(x, nt.faces, nt.vf_ptr, nt.vf_idx, n)                   # x is fixed: once
+        qn = _query_normals(tn, rows) if gate is not None and w > 0.0 else None
+    solved = None
+    if step == "plane":
+        matches.update(tn=tn)
+        solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=x.device)
     for k in range(iters):
         g_sm = None if gate is None else (aligned.normals, tn, gate[0])
         g_ms = None if gate is None else (qn, aligned.normals, gate[0])
@@ -602,5 +679,6 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         if w > 0.0:
             ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms, gate=g_ms)
         ops.chamfer_fwd(sm[1] if ft is None else sf[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
-        part = pose_update(pose, scans, aligned, matches, mode, partials=part, surface=ft is not None)
+        part = pose_update(pose, scans, aligned, matches, mode, partials=part, surface=ft is not None, step=step,
+                           solved=None if solved is None else solved[k])
     return pose, aligned, log
