@@ -660,6 +660,57 @@ SH_API int sh_nearest_points_gated(const float* q, int64_t q_sb, int nq, const i
                                    void* workspace, size_t workspace_bytes, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Nearest surface points under a normal gate: sh_nearest_surface restricted, per (point, triangle) pair, to the triangles
+ * whose FACE normal agrees with the scan point's normal (no reference counterpart).  fp32, deterministic, plain stores of every
+ * output element.
+ *
+ * Face normals.  sh_face_normals: x, x_sb, n, faces, nF as sh_nearest_surface takes them; one thread per (body, face).  For face
+ * f with corners a = x[f0], b = x[f1], c = x[f2] in the face's own corner order, everything in fp32, every operation rounded on
+ * its own except the fused multiply-adds written out (no other contraction):
+ *     ab = b - a;  ac = c - a                                             (component-wise)
+ *     cx = fma(ab.y, ac.z, -(ab.z * ac.y));  cy = fma(ab.z, ac.x, -(ab.x * ac.z));  cz = fma(ab.x, ac.y, -(ab.y * ac.x))
+ *     len2 = fma(cz, cz, fma(cy, cy, cx * cx))
+ *     normal[b][f] = (cx, cy, cz) / sqrtf(len2)  (three divisions) when 0 < len2 < +inf, otherwise (0, 0, 0)
+ * - the cross product is the one "Vertex normals" sums.  A face with a corner outside [0, n) gets (0, 0, 0); no vertex mask
+ * takes part.  normals: contiguous [B][nF][3], every element stored; no LDS, no atomics.  B == 0 or nF == 0: SH_OK, nothing
+ * launched.  (The fp64-normalised face normal of the point-to-plane step below is a different quantity and is left as it is.)
+ *
+ * sh_nearest_surface_gated.  sh_nearest_surface's arguments, plus qn [B] bodies of [*][3] scan normals (stride qn_sb, row j
+ * belongs to point j), fn contiguous [B][nF][3] face normals (sh_face_normals of the same x and faces) and cos_min.  Face f is
+ * COMPATIBLE with point j iff
+ *     fma(qn.z, fn.z, fma(qn.y, fn.y, qn.x * fn.x)) >= cos_min            (fp32; a NaN compares false)
+ * A zero normal on either side gives 0: compatible only when cos_min <= 0.  The answer is the minimum of (d2, f) in
+ * lexicographic order over the triangles that are targets (sh_nearest_surface's rule) AND compatible; d2(f) and uv are
+ * sh_nearest_surface's, unchanged.  A live point with no such triangle gets face -1, d2 +inf, uv 0 (sh_chamfer_fwd counts it as
+ * truncated, sh_chamfer_surface_bwd and the alignment moments drop it); points j >= q_count[b]: face -1, d2 0, uv 0.  cos_min =
+ * -inf opens the gate: sh_nearest_surface's bits (for normals free of NaN).  cos_min NaN: SH_ERR_INVALID_ARG.
+ *
+ * How it is computed.  The three launches of sh_nearest_surface in their gated instantiations, and between the first and the
+ * second the search that supplies the bound.  (1) also writes every target triangle's sphere centre m on its own, [B][nF][3],
+ * with a flag that is 0 for a triangle that is no target (or whose centre overflowed).  (1b) bound == NULL and cull != 0:
+ * sh_nearest_points_gated over those centres with fn as the targets' normals and the flags as the mask gives bound[b][j] = the
+ * squared distance to the nearest centre of a compatible target, +inf when there is none.  The nearest-vertex distance is no
+ * bound here: the nearest vertex may belong to incompatible faces only.  A centre lies on its face (to rounding), so its
+ * distance bounds the gated answer from above.  A caller's bound (non-NULL) is used as it is instead; whatever it holds, step
+ * (3) keeps the result exact.  (2) The sphere test is sh_nearest_surface's; a triangle that passes it is region-tested by a lane
+ * only if it is compatible with that lane's point, so an incompatible pair neither becomes the best nor tightens rb.  (3) The
+ * minimum over the chunks; a result above SH_SURFACE_MARGIN * bound[b][j] is swept again over the compatible targets without a
+ * bound.  A point WITHOUT a face whose bound is +inf is not swept again: nothing was skipped because of the bound, so "no
+ * compatible target" is exact.  cull == 0: every compatible (point, target) pair is region-tested, bound is ignored and (1b) is
+ * not run - the yardstick, same bits.  chunks, stats and the alignment of the workspace as sh_nearest_surface;
+ * workspace: sh_nearest_surface_gated_workspace(B, nq, nF, chunks) bytes (it holds the centres, the flags, the bound and the
+ * bounding search's own workspace as well).  The split is sh_nearest_surface_chunks'.  No atomics outside the stats counters.
+ */
+SH_API int sh_face_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, int B, float* normals,
+                           sh_stream_t stream);
+SH_API size_t sh_nearest_surface_gated_workspace(int B, int nq, int nF, int chunks);
+SH_API int sh_nearest_surface_gated(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* qn, int64_t qn_sb,
+                                    const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* fn,
+                                    const uint8_t* v_mask, int64_t mask_sb, float cos_min, const float* bound, int B, int chunks,
+                                    int cull, int32_t* face, float* d2, float* uv, uint64_t* stats, void* workspace,
+                                    size_t workspace_bytes, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.

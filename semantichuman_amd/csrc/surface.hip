@@ -59,9 +59,14 @@ __device__ __forceinline__ Foot surf_foot(const float* __restrict__ T, float sx,
 
 // One thread per (body, triangle): the triangle's record and bounding sphere for this step's vertices.  A triangle that is
 // not a target (a masked corner, or an index outside [0, n)) gets the centre (+inf, +inf, +inf): the sweep never tests it.
+// GATED: the centre is also written on its own, contiguous [B][nF][3], with a flag [B][nF] that is 1 for a target whose centre
+// is finite - the targets and the mask of the gated search that bounds the sweep (header, "Nearest surface points under a
+// normal gate").  Without GATED neither pointer is read.
+template <bool GATED>
 __global__ __launch_bounds__(256) void surface_prep_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
                                                           int nF, const unsigned char* __restrict__ v_mask, long mask_sb, int B,
-                                                          float* __restrict__ tri, f32x4* __restrict__ sphere) {
+                                                          float* __restrict__ tri, f32x4* __restrict__ sphere, float* __restrict__ cen,
+                                                          unsigned char* __restrict__ fvalid) {
 #pragma clang fp contract(off)
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)B * nF) return;
@@ -77,6 +82,7 @@ __global__ __launch_bounds__(256) void surface_prep_kernel(const float* __restri
 #pragma unroll
         for (int k = 0; k < TRI; ++k) T[k] = 0.f;
         sphere[t] = f32x4{INFINITY, INFINITY, INFINITY, 0.f};
+        if constexpr (GATED) { cen[3 * t] = 0.f; cen[3 * t + 1] = 0.f; cen[3 * t + 2] = 0.f; fvalid[t] = 0; }
         return;
     }
     const float* xb = x + (long)b * x_sb;
@@ -92,6 +98,10 @@ __global__ __launch_bounds__(256) void surface_prep_kernel(const float* __restri
     const float rb = dot3(bx - mx, by - my, bz - mz, bx - mx, by - my, bz - mz);
     const float rc = dot3(cx - mx, cy - my, cz - mz, cx - mx, cy - my, cz - mz);
     float r = sqrtf(fmaxf(ra, fmaxf(rb, rc))) * MARGIN;
+    if constexpr (GATED) {
+        const bool fin = mx < INFINITY && mx > -INFINITY && my < INFINITY && my > -INFINITY && mz < INFINITY && mz > -INFINITY;
+        cen[3 * t] = fin ? mx : 0.f; cen[3 * t + 1] = fin ? my : 0.f; cen[3 * t + 2] = fin ? mz : 0.f; fvalid[t] = fin ? 1 : 0;
+    }
     if (!(mx < INFINITY && mx > -INFINITY && my < INFINITY && my > -INFINITY && mz < INFINITY && mz > -INFINITY && r < INFINITY)) {
         mx = my = mz = 0.f; r = INFINITY;                                 // overflow or NaN in the vertices: never culled
     }
@@ -106,14 +116,32 @@ struct SurfParams {
     unsigned long long* stats;
 };
 
+// The face-normal gate of the header ("Nearest surface points under a normal gate"): the queries' normals, the faces' normals
+// (contiguous [B][nF][3]) and the smallest cosine that pairs them.
+struct SurfGate {
+    const float* qn; long qn_sb;
+    const float* fn;
+    float cos_min;
+};
+
+__device__ __forceinline__ bool surf_compatible(float qu, float qv, float qw, const float* __restrict__ N, float cos_min) {
+    return __builtin_fmaf(qw, N[2], __builtin_fmaf(qv, N[1], qu * N[0])) >= cos_min;   // a NaN compares false: not compatible
+}
+
 // grid (query tile, triangle chunk, body).  The chunk's (d2, face) go to part_d2 / part_idx [B][chunks][nq] for
 // surface_finish_kernel.  Triangles are visited in ascending order and a candidate replaces the best only when strictly
 // closer: the lowest face wins an exact tie.  A triangle is skipped for a query when
 //     d2(s, centre) > (rb + r)^2,      rb = MARGIN * sqrt(the query's bound),  r = MARGIN * the sphere's radius
 // where the bound is the smaller of the caller's upper bound and the best distance found so far (cull = 0: rb = +inf, nothing is
 // skipped).  The region test runs, for the lanes that need it, when any lane of the wave does.
-template <bool STATS>
-__global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, int32_t* __restrict__ part_idx, float* __restrict__ part_d2) {
+// GATED: inside that branch, a lane that needs the triangle runs the region test only when the triangle's normal (one record
+// per triangle, the address uniform over the wave like the triangle's own) is compatible with its query's - three more query
+// registers, one dot product and one compare per lane and tested triangle; the sphere loop is untouched.  An incompatible pair
+// therefore neither becomes `best` nor shrinks rb, and what the sphere test skips is still farther than the bound in force.
+// Without GATED, g is not read and the gate's registers do not exist.
+template <bool STATS, bool GATED>
+__global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, int32_t* __restrict__ part_idx, float* __restrict__ part_d2,
+                                                           const SurfGate g) {
     __shared__ __attribute__((aligned(16))) float sx[2][FT];
     __shared__ __attribute__((aligned(16))) float sy[2][FT];
     __shared__ __attribute__((aligned(16))) float sz[2][FT];
@@ -125,7 +153,10 @@ __global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, 
     const float* qb = p.q + (long)b * p.q_sb;
     const f32x4* sph = p.sphere + (long)b * p.nF;
     const float* trib = p.tri + (long)b * p.nF * TRI;
-    float qx[QPT], qy[QPT], qz[QPT], best[QPT], rb[QPT];
+    const float* qnb = GATED ? g.qn + (long)b * g.qn_sb : nullptr;
+    const float* fnb = GATED ? g.fn + (long)b * p.nF * 3 : nullptr;
+    const float cos_min = g.cos_min;
+    float qx[QPT], qy[QPT], qz[QPT], qu[QPT], qv[QPT], qw[QPT], best[QPT], rb[QPT];
     int bi[QPT];
 #pragma unroll
     for (int k = 0; k < QPT; ++k) {
@@ -133,6 +164,7 @@ __global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, 
         const bool live = j < nqb;
         // a dead query sits at +inf with a bound of 0: infinitely far from every sphere, it never asks for a region test
         qx[k] = live ? qb[3L * j] : INFINITY; qy[k] = live ? qb[3L * j + 1] : INFINITY; qz[k] = live ? qb[3L * j + 2] : INFINITY;
+        if constexpr (GATED) { qu[k] = live ? qnb[3L * j] : 0.f; qv[k] = live ? qnb[3L * j + 1] : 0.f; qw[k] = live ? qnb[3L * j + 2] : 0.f; }
         best[k] = INFINITY; bi[k] = -1;
         const float bnd = (p.cull && p.bound && live) ? p.bound[(long)b * p.nq + j] : INFINITY;
         rb[k] = live ? sqrtf(fmaxf(bnd, 0.f)) * MARGIN : 0.f;
@@ -175,8 +207,10 @@ __global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, 
                     if (X[e] < INFINITY && __ballot(any) != 0ull) {      // uniform: the triangle is a target and some lane needs it
                         const int f = base + u + e;
                         const float* T = trib + (long)f * TRI;
+                        const float* N = GATED ? fnb + 3L * f : nullptr;
 #pragma unroll
                         for (int k = 0; k < QPT; ++k) {
+                            if constexpr (GATED) need[k] = need[k] && surf_compatible(qu[k], qv[k], qw[k], N, cos_min);
                             if (need[k]) {
                                 const Foot ft = surf_foot(T, qx[k], qy[k], qz[k]);
                                 if (ft.d2 < best[k]) {
@@ -213,9 +247,14 @@ __global__ __launch_bounds__(NT) void surface_search_kernel(const SurfParams p, 
 // distance found; the factor lets a foot point ON the nearest vertex pass, whose distance differs from the vertex search's by
 // rounding).  When it does - the bound was no upper bound of the fp32 surface distance, which a vertex mask can cause - the
 // query is swept again here without a bound.  Then the weights of the chosen face are formed once more.
+// GATED: the sweep here tests the compatible targets only (the same expression), and a query without a face is NOT swept again
+// when its bound was +inf: nothing was culled by the bound then, so "no compatible target" is the sweep's exact answer (a scan
+// whose normals all point inward would otherwise walk every triangle here, one thread per point).  With a finite bound and no
+// face the comparison below fails (+inf is not <= it) and the query is swept again, as without the gate.
+template <bool GATED>
 __global__ __launch_bounds__(256) void surface_finish_kernel(const SurfParams p, int B, const int32_t* __restrict__ part_idx,
                                                             const float* __restrict__ part_d2, int32_t* __restrict__ face,
-                                                            float* __restrict__ d2, float* __restrict__ uv) {
+                                                            float* __restrict__ d2, float* __restrict__ uv, const SurfGate g) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)B * p.nq) return;
     const int b = (int)(t / p.nq), j = (int)(t - (long)b * p.nq);
@@ -232,12 +271,19 @@ __global__ __launch_bounds__(256) void surface_finish_kernel(const SurfParams p,
     const float* trib = p.tri + (long)b * p.nF * TRI;
     if (p.cull) {
         const float bnd = p.bound ? p.bound[t] : INFINITY;
-        if (bi < 0 || !(best <= bnd * MARGIN)) {                          // a skipped triangle is farther than MARGIN^2 * bnd
+        if ((!GATED && bi < 0) || !(best <= bnd * MARGIN)) {              // a skipped triangle is farther than MARGIN^2 * bnd
             const f32x4* sph = p.sphere + (long)b * p.nF;
             best = INFINITY; bi = -1;
             if (p.stats) atomicAdd(p.stats + 1, 1ull);                   // diagnostic: points that took this path
+            float qu = 0.f, qv = 0.f, qw = 0.f;
+            if constexpr (GATED) {
+                const float* qnb = g.qn + (long)b * g.qn_sb;
+                qu = qnb[3L * j]; qv = qnb[3L * j + 1]; qw = qnb[3L * j + 2];
+            }
             for (int f = 0; f < p.nF; ++f) {
                 if (!(sph[f][0] < INFINITY)) continue;
+                if constexpr (GATED)
+                    if (!surf_compatible(qu, qv, qw, g.fn + ((long)b * p.nF + f) * 3, g.cos_min)) continue;
                 const Foot ft = surf_foot(trib + (long)f * TRI, sx, sy, sz);
                 if (ft.d2 < best) { best = ft.d2; bi = f; }
             }
@@ -343,7 +389,134 @@ __global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restric
     o[0] = g0; o[1] = g1; o[2] = g2;
 }
 
+// One thread per (body, face): the unit normal of the header ("Face normals"), in its one fixed form - the cross product as
+// vertex_normals_kernel forms a face's contribution, no contraction beyond the fused multiply-adds written out, so the numpy
+// transcription of tests/surface_gated_ref.py rounds alike.  A face with a corner outside [0, n), no area or an overflow gets
+// the zero vector.  No LDS, no atomics; every element stored.
+__global__ __launch_bounds__(256) void face_normals_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
+                                                          int nF, int B, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)B * nF) return;
+    const int b = (int)(t / nF), f = (int)(t - (long)b * nF);
+    const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if ((unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n) {
+        const float* xb = x + (long)b * x_sb;
+        const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
+        const float abx = xb[3L * i1] - ax, aby = xb[3L * i1 + 1] - ay, abz = xb[3L * i1 + 2] - az;
+        const float acx = xb[3L * i2] - ax, acy = xb[3L * i2 + 1] - ay, acz = xb[3L * i2 + 2] - az;
+        const float cx = __builtin_fmaf(aby, acz, -(abz * acy));
+        const float cy = __builtin_fmaf(abz, acx, -(abx * acz));
+        const float cz = __builtin_fmaf(abx, acy, -(aby * acx));
+        const float len2 = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, cx * cx));
+        if (len2 > 0.f && len2 < INFINITY) {
+            const float len = sqrtf(len2);
+            nx = cx / len; ny = cy / len; nz = cz / len;
+        }
+    }
+    float* o = out + t * 3;
+    o[0] = nx; o[1] = ny; o[2] = nz;
+}
+
 size_t sf_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// Where the pieces of the workspace lie.  Ungated: spheres, records, the chunks' partial results - the layout it has always had.
+// Gated: after the records come the centres [B][nF][3], their flags [B][nF], the bound [B][nq] and the index [B][nq] the bounding
+// search writes, and that search's own workspace; the partial results stay last.
+struct SurfLayout {
+    size_t sphere, tri, cen, fvalid, bound, bidx, nn, nn_bytes, part, total;
+};
+
+SurfLayout surf_layout(int B, int nq, int nF, int chunks, bool gated) {
+    SurfLayout L{};
+    size_t o = 0;
+    L.sphere = o; o += sf_align16((size_t)B * nF * sizeof(f32x4));
+    L.tri = o; o += sf_align16((size_t)B * nF * TRI * sizeof(float));
+    if (gated) {
+        L.cen = o; o += sf_align16((size_t)B * nF * 3 * sizeof(float));
+        L.fvalid = o; o += sf_align16((size_t)B * nF);
+        L.bound = o; o += sf_align16((size_t)B * nq * sizeof(float));
+        L.bidx = o; o += sf_align16((size_t)B * nq * sizeof(int32_t));
+        L.nn_bytes = sh_nearest_points_workspace(B, nq, nF, 0);
+        L.nn = o; o += sf_align16(L.nn_bytes);
+    }
+    L.part = o; o += (size_t)B * chunks * nq * (sizeof(float) + sizeof(int32_t));
+    L.total = o;
+    return L;
+}
+
+// sh_nearest_surface (g == nullptr) and sh_nearest_surface_gated: the checks both make, the split, the workspace and the
+// launches.  `who` is the entry point's name in every error text.
+int surf_search(const char* who, const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* x, int64_t x_sb, int n,
+                const int32_t* faces, int nF, const uint8_t* v_mask, int64_t mask_sb, const float* bound, const SurfGate* g, int B, int chunks,
+                int cull, int32_t* face, float* d2, float* uv, uint64_t* stats, void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    SH_REQUIRE(q && x && face && d2 && uv && (faces || nF == 0) && (!g || (g->qn && (g->fn || nF == 0))), SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(B >= 0 && nq >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, nq %d, n %d, nF %d, chunks %d)", who,
+               B, nq, n, nF, chunks);
+    SH_REQUIRE(!g || g->cos_min == g->cos_min, SH_ERR_INVALID_ARG, "%s: cos_min is NaN", who);
+    if (B == 0 || nq == 0) return SH_OK;
+    SH_REQUIRE(q_sb >= 3L * nq && x_sb >= 3L * n && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "%s: batch stride shorter than a body (q_sb %ld, x_sb %ld, mask_sb %ld)", who, (long)q_sb, (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(!g || g->qn_sb >= 3L * nq, SH_ERR_INVALID_ARG, "%s: batch stride shorter than a body (qn_sb %ld)", who, g ? g->qn_sb : 0L);
+    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && (long)B * nF < (1L << 27), SH_ERR_UNSUPPORTED, "%s: B, B*nq or B*nF too large", who);
+    SurfParams p{};
+    p.chunks = nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &p.tiles_per_chunk);
+    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "%s: %d triangle chunks", who, p.chunks);
+    const SurfLayout L = surf_layout(B, nq, nF, p.chunks, g != nullptr);
+    SH_REQUIRE(workspace && workspace_bytes >= L.total && ((uintptr_t)workspace & 15) == 0, SH_ERR_WORKSPACE,
+               "%s: workspace too small or not 16-byte aligned (%zu bytes needed for %d chunks)", who, L.total, p.chunks);
+    char* wsb = static_cast<char*>(workspace);
+    f32x4* sphere = reinterpret_cast<f32x4*>(wsb + L.sphere);
+    float* tri = reinterpret_cast<float*>(wsb + L.tri);
+    float* part_d2 = reinterpret_cast<float*>(wsb + L.part);
+    int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
+    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
+    p.tri = tri; p.sphere = sphere; p.nF = nF; p.bound = bound; p.cull = cull ? 1 : 0;
+    p.stats = reinterpret_cast<unsigned long long*>(stats);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 prep_grid((unsigned)(((long)B * nF + 255) / 256));
+    if (nF > 0 && !g) {
+        ShProfScope ps(st, "surface_prep_kernel|B=%d nF=%d", B, nF);
+        SH_LAUNCH_PS(ps, surface_prep_kernel<false>, prep_grid, dim3(256), 0, st, x, (long)x_sb, n, faces, nF, v_mask, (long)mask_sb, B, tri, sphere,
+                     (float*)nullptr, (unsigned char*)nullptr);
+    }
+    if (g) {
+        float* cen = reinterpret_cast<float*>(wsb + L.cen);
+        unsigned char* fvalid = reinterpret_cast<unsigned char*>(wsb + L.fvalid);
+        if (nF > 0) {
+            ShProfScope ps(st, "surface_prep_gated_kernel|B=%d nF=%d", B, nF);
+            SH_LAUNCH_PS(ps, surface_prep_kernel<true>, prep_grid, dim3(256), 0, st, x, (long)x_sb, n, faces, nF, v_mask, (long)mask_sb, B, tri, sphere,
+                         cen, fvalid);
+        }
+        if (p.cull && !bound && nF > 0) {
+            // The bound that holds under the gate: the gated nearest search over the targets' centres, the faces' normals as the
+            // targets' normals.  A centre lies on its face, so its distance bounds that face's; no compatible target: +inf.
+            float* bnd = reinterpret_cast<float*>(wsb + L.bound);
+            const int rc = sh_nearest_points_gated(q, q_sb, nq, q_count, g->qn, g->qn_sb, cen, 3L * nF, nF, nullptr, g->fn, 3L * nF, fvalid, nF,
+                                                   g->cos_min, B, 0, reinterpret_cast<int32_t*>(wsb + L.bidx), bnd, L.nn_bytes ? wsb + L.nn : nullptr,
+                                                   L.nn_bytes, stream);
+            if (rc != SH_OK) return rc;
+            p.bound = bnd;
+        }
+    }
+    const SurfGate gate = g ? *g : SurfGate{};
+    {
+        ShProfScope ps(st, "%s|B=%d nq=%d nF=%d chunks=%d cull=%d", g ? "surface_search_gated_kernel" : "surface_search_kernel", B, nq, nF, p.chunks,
+                       p.cull);
+        const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
+        auto kern = g ? (p.stats ? surface_search_kernel<true, true> : surface_search_kernel<false, true>)
+                      : (p.stats ? surface_search_kernel<true, false> : surface_search_kernel<false, false>);
+        SH_LAUNCH_PS(ps, kern, grid, dim3(NT), 0, st, p, part_idx, part_d2, gate);
+    }
+    {
+        ShProfScope ps(st, "%s|B=%d nq=%d chunks=%d", g ? "surface_finish_gated_kernel" : "surface_finish_kernel", B, nq, p.chunks);
+        auto kern = g ? surface_finish_kernel<true> : surface_finish_kernel<false>;
+        SH_LAUNCH_PS(ps, kern, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, p, B, part_idx, part_d2, face, d2, uv, gate);
+    }
+    SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
 
 }  // namespace
 
@@ -357,56 +530,42 @@ int sh_nearest_surface_chunks(int B, int nq, int nF) {
 size_t sh_nearest_surface_workspace(int B, int nq, int nF, int chunks) {
     if (B <= 0 || nq <= 0 || nF < 0 || chunks < 0) return 0;
     int tpc;
-    const int c = nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &tpc);
-    return sf_align16((size_t)B * nF * sizeof(f32x4)) + sf_align16((size_t)B * nF * TRI * sizeof(float)) +
-           (size_t)B * c * nq * (sizeof(float) + sizeof(int32_t));
+    return surf_layout(B, nq, nF, nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &tpc), false).total;
+}
+
+size_t sh_nearest_surface_gated_workspace(int B, int nq, int nF, int chunks) {
+    if (B <= 0 || nq <= 0 || nF < 0 || chunks < 0) return 0;
+    int tpc;
+    return surf_layout(B, nq, nF, nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &tpc), true).total;
 }
 
 int sh_nearest_surface(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* x, int64_t x_sb, int n,
                        const int32_t* faces, int nF, const uint8_t* v_mask, int64_t mask_sb, const float* bound, int B, int chunks,
                        int cull, int32_t* face, float* d2, float* uv, uint64_t* stats, void* workspace, size_t workspace_bytes,
                        sh_stream_t stream) {
-    SH_REQUIRE(q && x && face && d2 && uv && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_nearest_surface: null pointer");
-    SH_REQUIRE(B >= 0 && nq >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
-               "sh_nearest_surface: negative size (B %d, nq %d, n %d, nF %d, chunks %d)", B, nq, n, nF, chunks);
-    if (B == 0 || nq == 0) return SH_OK;
-    SH_REQUIRE(q_sb >= 3L * nq && x_sb >= 3L * n && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
-               "sh_nearest_surface: batch stride shorter than a body (q_sb %ld, x_sb %ld, mask_sb %ld)", (long)q_sb, (long)x_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * nq < (1L << 30) && (long)B * nF < (1L << 27), SH_ERR_UNSUPPORTED,
-               "sh_nearest_surface: B, B*nq or B*nF too large");
-    SurfParams p{};
-    p.chunks = nn_resolve_chunks(B, nq, nF, FT, QT, chunks, &p.tiles_per_chunk);
-    SH_REQUIRE(p.chunks <= 65535, SH_ERR_UNSUPPORTED, "sh_nearest_surface: %d triangle chunks", p.chunks);
-    const size_t sph_bytes = sf_align16((size_t)B * nF * sizeof(f32x4)), tri_bytes = sf_align16((size_t)B * nF * TRI * sizeof(float));
-    const size_t need = sph_bytes + tri_bytes + (size_t)B * p.chunks * nq * (sizeof(float) + sizeof(int32_t));
-    SH_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, SH_ERR_WORKSPACE,
-               "sh_nearest_surface: workspace too small or not 16-byte aligned (%zu bytes needed for %d chunks)", need, p.chunks);
-    char* wsb = static_cast<char*>(workspace);
-    f32x4* sphere = reinterpret_cast<f32x4*>(wsb);
-    float* tri = reinterpret_cast<float*>(wsb + sph_bytes);
-    float* part_d2 = reinterpret_cast<float*>(wsb + sph_bytes + tri_bytes);
-    int32_t* part_idx = reinterpret_cast<int32_t*>(part_d2 + (size_t)B * p.chunks * nq);
-    p.q = q; p.q_sb = (long)q_sb; p.nq = nq; p.q_count = q_count;
-    p.tri = tri; p.sphere = sphere; p.nF = nF; p.bound = bound; p.cull = cull ? 1 : 0;
-    p.stats = reinterpret_cast<unsigned long long*>(stats);
+    return surf_search("sh_nearest_surface", q, q_sb, nq, q_count, x, x_sb, n, faces, nF, v_mask, mask_sb, bound, nullptr, B, chunks, cull, face, d2,
+                       uv, stats, workspace, workspace_bytes, stream);
+}
+
+int sh_nearest_surface_gated(const float* q, int64_t q_sb, int nq, const int32_t* q_count, const float* qn, int64_t qn_sb, const float* x,
+                             int64_t x_sb, int n, const int32_t* faces, int nF, const float* fn, const uint8_t* v_mask, int64_t mask_sb,
+                             float cos_min, const float* bound, int B, int chunks, int cull, int32_t* face, float* d2, float* uv,
+                             uint64_t* stats, void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    const SurfGate g{qn, (long)qn_sb, fn, cos_min};
+    return surf_search("sh_nearest_surface_gated", q, q_sb, nq, q_count, x, x_sb, n, faces, nF, v_mask, mask_sb, bound, &g, B, chunks, cull, face, d2,
+                       uv, stats, workspace, workspace_bytes, stream);
+}
+
+int sh_face_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, int B, float* normals, sh_stream_t stream) {
+    SH_REQUIRE(x && normals && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_face_normals: null pointer");
+    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0, SH_ERR_INVALID_ARG, "sh_face_normals: negative size (B %d, n %d, nF %d)", B, n, nF);
+    if (B == 0 || nF == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * n, SH_ERR_INVALID_ARG, "sh_face_normals: batch stride %ld shorter than a body", (long)x_sb);
+    SH_REQUIRE((long)B * nF < (1L << 27), SH_ERR_UNSUPPORTED, "sh_face_normals: B*nF too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (nF > 0) {
-        ShProfScope ps(st, "surface_prep_kernel|B=%d nF=%d", B, nF);
-        SH_LAUNCH_PS(ps, surface_prep_kernel, dim3((unsigned)(((long)B * nF + 255) / 256)), dim3(256), 0, st, x, (long)x_sb, n, faces, nF, v_mask,
-                     (long)mask_sb, B, tri, sphere);
-    }
-    {
-        ShProfScope ps(st, "surface_search_kernel|B=%d nq=%d nF=%d chunks=%d cull=%d", B, nq, nF, p.chunks, p.cull);
-        const dim3 grid((unsigned)sh_cdiv(nq, QT), (unsigned)p.chunks, (unsigned)B);
-        if (p.stats) SH_LAUNCH_PS(ps, surface_search_kernel<true>, grid, dim3(NT), 0, st, p, part_idx, part_d2);
-        else SH_LAUNCH_PS(ps, surface_search_kernel<false>, grid, dim3(NT), 0, st, p, part_idx, part_d2);
-    }
-    {
-        ShProfScope ps(st, "surface_finish_kernel|B=%d nq=%d chunks=%d", B, nq, p.chunks);
-        SH_LAUNCH_PS(ps, surface_finish_kernel, dim3((unsigned)(((long)B * nq + 255) / 256)), dim3(256), 0, st, p, B, part_idx, part_d2, face, d2,
-                     uv);
-    }
-    SH_CHECK_LAUNCH("nearest_surface");
+    ShProfScope ps(st, "face_normals_kernel|B=%d n=%d nF=%d", B, n, nF);
+    SH_LAUNCH_PS(ps, face_normals_kernel, dim3((unsigned)(((long)B * nF + 255) / 256)), dim3(256), 0, st, x, (long)x_sb, n, faces, nF, B, normals);
+    SH_CHECK_LAUNCH("face_normals");
     return SH_OK;
 }
 

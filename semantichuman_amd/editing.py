@@ -214,7 +214,7 @@ def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, b
 
 
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None,
-             faces=None, normal_angle=None, normal_faces=None):
+             faces=None, normal_angle=None, normal_faces=None, gate_on="vertices"):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
     The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
@@ -224,21 +224,29 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     -> model term is then the distance to the model's surface, not to its nearest vertex (scan.chamfer); a scan packed with
     order="morton" makes that search 2 - 3 times cheaper (DESIGN 4j has the measurement).  normal_angle / normal_faces: the normal
     gate of scan.chamfer (degrees; needs scans.normals, the model's triangles and trunc; None: none, the same bits as ever).
+    gate_on: "vertices" (the default: that gate, on vertex normals, not built together with faces) or "surface" - the gate of the
+    surface distance, on the face's normal (scan.chamfer; needs faces, normal_angle, scan normals and trunc).
     Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
         raise ValueError("fit_scan: %d bodies, %d scans" % (z.shape[0], len(scans)))
+    scan._check_gate_on("fit_scan", gate_on, normal_angle, faces, scans, trunc)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
     # one face table at most: a gate reads normal_faces (and scan.chamfer refuses faces= next to it), no gate reads faces alone
     gated = normal_angle is not None
-    state = {"table": normal_faces if gated else faces}
+    on_surface = gate_on == "surface"
+    state = {"table": normal_faces if gated and not on_surface else faces, "normals": normal_faces if on_surface else None}
 
     def objective(x_hat):
-        if state["table"] is not None and not isinstance(state["table"], scan.FaceTable):    # validated and uploaded once, at the first decode
-            state["table"] = scan.FaceTable(state["table"], x_hat.shape[1] - 1, x_hat.device)
+        for k in ("table", "normals"):
+            if state[k] is not None and not isinstance(state[k], scan.FaceTable):            # validated and uploaded once, at the first decode
+                state[k] = scan.FaceTable(state[k], x_hat.shape[1] - 1, x_hat.device)
+        if on_surface:
+            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=state["table"], normal_angle=normal_angle,
+                                normal_faces=state["normals"], gate_on=gate_on)
         return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=faces if gated else state["table"],
                             normal_angle=normal_angle, normal_faces=state["table"] if gated else None)
 
@@ -250,7 +258,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
-                  normal_angle=None, normal_faces=None, align_on="vertices", align_step="point"):
+                  normal_angle=None, normal_faces=None, align_on="vertices", align_step="point", gate_on="vertices"):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -278,7 +286,11 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     everything above, bit for bit) or "plane" - both pose stages take the linearised point-to-plane step (scan.align(...,
     step="plane") and scan.pose_update(..., step="plane")) on the pairs `align_on` selects; it needs the model's triangles for the
     normals (faces, or normal_faces).  That step is Gauss-Newton, so a pose update is not guaranteed to lower the Chamfer value, and
-    a body whose system is singular (too few or parallel normals) keeps its pose for that update.  No file reader."""
+    a body whose system is singular (too few or parallel normals) keeps its pose for that update.  gate_on: "vertices" (the
+    default: the gate above, on vertex normals, not built together with faces) or "surface" - the fit's surface distance is gated
+    by the face's normal (scan.chamfer(..., gate_on="surface"); needs faces, normal_angle, scan normals and trunc), with either
+    align_on: "surface" gates both pose stages' foot points the same way, "vertices" runs them on vertex pairs gated by the
+    vertex normals (of normal_faces, or of faces when that is omitted).  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -297,6 +309,8 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     on_surface = align_on == "surface"
     if on_surface and faces is None:
         raise ValueError("register_scan: align_on='surface' needs faces (the model's triangles)")
+    scan._check_gate_on("register_scan", gate_on, normal_angle, faces, scans, trunc)
+    gate_surface = gate_on == "surface"
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -304,11 +318,12 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     with torch.no_grad():
         x0 = _decode(model, z.detach(), z_kps, dummy)
     if normal_angle is not None:
-        if faces is not None:
-            raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built")
+        if faces is not None and not gate_surface:
+            raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built for the gate on vertex "
+                             "normals; gate_on='surface' gates the surface search by the face's normal")
         if normal_faces is not None and not isinstance(normal_faces, scan.FaceTable):
             normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
-    if (on_surface or align_step == "plane") and faces is not None and not isinstance(faces, scan.FaceTable):
+    if (on_surface or align_step == "plane" or gate_surface) and faces is not None and not isinstance(faces, scan.FaceTable):
         faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
     if align_step == "plane":                                                           # the table the vertex normals come from
         if normal_faces is None:
@@ -316,8 +331,9 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
         elif not isinstance(normal_faces, scan.FaceTable):
             normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
-                                  vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
-                                  faces=faces if on_surface else None, step=align_step)
+                                  vertex_mask=vertex_mask, normal_angle=normal_angle,
+                                  normal_faces=faces if gate_surface and not on_surface and normal_faces is None else normal_faces,
+                                  faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices")
     matches = {} if align_every > 0 else None
     state = {"partials": None}
     if faces is not None and not isinstance(faces, scan.FaceTable):
@@ -325,7 +341,8 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
 
     def objective(x_hat):
         return scan.chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches=matches, faces=faces,
-                            normal_angle=normal_angle, normal_faces=normal_faces)
+                            normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on,
+                            _vertex_matches=not (gate_surface and on_surface))
 
     def after_step(t):
         if (t + 1) % align_every == 0:
@@ -336,5 +353,5 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
                                 after_step=after_step if align_every > 0 else None)
     with torch.no_grad():
         final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan, faces=faces,
-                             normal_angle=normal_angle, normal_faces=normal_faces)
+                             normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on)
     return z_new, pose, final, losses

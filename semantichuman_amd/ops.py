@@ -507,11 +507,30 @@ def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb,
     return g
 
 
-def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunks=0, cull=True, out=None, stats=None):
+def face_normals(x, faces, n, out=None):
+    """sh_face_normals: x [B, *, 3] of which the first n rows are vertices, faces int32 HIP [nF, 3] -> unit face normals,
+    contiguous fp32 [B, nF, 3] (zero for a face without area or with a corner outside [0, n))."""
+    B, rows, x_sb = _points(x, "face_normals")
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("face_normals: n = %d exceeds the model's %d rows" % (n, rows))
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.face_normals needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
+    nF = faces.shape[0]
+    nrm = out if out is not None else torch.empty((B, nF, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_face_normals(ptr(x), x_sb, n, ptr(faces), nF, B, ptr(nrm), stream_ptr()), "sh_face_normals")
+    return nrm
+
+
+def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunks=0, cull=True, out=None, stats=None, gate=None):
     """sh_nearest_surface: q [B, *, 3] scan points, x [B, *, 3] model points of which the first n are vertices, faces int32 HIP
     [nF, 3] (one table for the batch) -> (face int32 [B, nq], d2 fp32 [B, nq], uv fp32 [B, nq, 2]).  bound [B, nq]: an upper
     bound of each answer (the squared distance to the nearest vertex), None = none; cull=False runs every pair through the region
-    test (the yardstick: same bits).  stats: None or a zeroed int64 HIP tensor [2] that receives (region tests run, points swept again without a bound)."""
+    test (the yardstick: same bits).  stats: None or a zeroed int64 HIP tensor [2] that receives (region tests run, points swept again without a bound).
+    gate: None, or (qn [B, >= nq, 3], fn contiguous [B, nF, 3] from `face_normals`, cos_min) - then sh_nearest_surface_gated: only
+    the faces whose normal's fp32 dot product with the point's reaches cos_min are candidates, and with bound=None the library
+    bounds the culled sweep itself (the gated search over the face centres)."""
     B, nq, q_sb = _points(q, "nearest_surface")
     Bx, x_rows, x_sb = _points(x, "nearest_surface")
     if Bx != B:
@@ -531,6 +550,19 @@ def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunk
     face, d2, uv = out if out is not None else (torch.empty((B, nq), dtype=torch.int32, device=q.device),
                                                 torch.empty((B, nq), dtype=torch.float32, device=q.device),
                                                 torch.empty((B, nq, 2), dtype=torch.float32, device=q.device))
+    if gate is not None:
+        qn, fn, cos_min = gate
+        Bq, qn_rows, qn_sb = _points(qn, "nearest_surface (scan normals)")
+        if Bq != B or qn_rows < nq:
+            raise ValueError("nearest_surface: scan normals must be [%d, >= %d, 3], got %s" % (B, nq, tuple(qn.shape)))
+        if not (torch.is_tensor(fn) and fn.is_cuda and fn.dtype == torch.float32 and fn.is_contiguous() and tuple(fn.shape) == (B, nF, 3)):
+            raise RuntimeError("semantichuman_amd.nearest_surface: face normals must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (B, nF))
+        nbytes = lib.sh_nearest_surface_gated_workspace(B, nq, nF, chunks)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
+        check(lib.sh_nearest_surface_gated(ptr(q), q_sb, nq, ptr(q_count), ptr(qn), qn_sb, ptr(x), x_sb, n, ptr(faces), nF, ptr(fn), ptr(mask),
+                                           mask_sb, float(cos_min), ptr(bound), B, chunks, 1 if cull else 0, ptr(face), ptr(d2), ptr(uv),
+                                           ptr(stats), ptr(ws), nbytes, stream_ptr()), "sh_nearest_surface_gated")
+        return face, d2, uv
     nbytes = lib.sh_nearest_surface_workspace(B, nq, nF, chunks)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes else None
     check(lib.sh_nearest_surface(ptr(q), q_sb, nq, ptr(q_count), ptr(x), x_sb, n, ptr(faces), nF, ptr(mask), mask_sb, ptr(bound), B, chunks,

@@ -207,15 +207,54 @@ def vertex_normals(x, faces, n=None):
     return ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
 
 
-def _normal_gate(what, normal_angle, normal_faces, scans, n, trunc, faces, device):
-    """Validates the arguments of a normal gate -> None (no gate) or (cos_min, FaceTable)."""
+def face_normals(x, faces, n=None):
+    """Unit face normals of every body, fp32 [B, nF, 3] (sh_face_normals: the fp32 expression of sh_kernels.h, one thread per
+    face; deterministic).  x, faces and n as in `vertex_normals`; faces oriented counter-clockwise seen from outside give outward
+    normals.  A face without area gets the zero vector.  The vertex mask plays no part.  Not differentiable."""
+    x = x.detach()
+    rows = ops._points(x, "scan.face_normals")[1]
+    ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
+    return ops.face_normals(x, ft.faces, ft.n)
+
+
+def _check_gate_on(what, gate_on, normal_angle, faces, scans, trunc):
+    """The checks of `gate_on` that need no device: ValueError on an unknown value, and for "surface" on whatever it needs and
+    lacks (normal_angle, faces=, scan normals, trunc - each named)."""
+    if gate_on not in ("vertices", "surface"):
+        raise ValueError("%s: gate_on must be 'vertices' or 'surface', got %r" % (what, gate_on))
+    if gate_on != "surface":
+        return
+    if normal_angle is None:
+        raise ValueError("%s: gate_on='surface' needs normal_angle (degrees)" % what)
+    if not 0.0 < float(normal_angle) <= 180.0:
+        raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
+    if faces is None:
+        raise ValueError("%s: gate_on='surface' needs faces= (the model's triangles: the gate is on the face's normal)" % what)
+    if isinstance(scans, ScanBatch) and scans.normals is None:
+        raise ValueError("%s: gate_on='surface' needs scan normals (ScanBatch(..., normals=))" % what)
+    if trunc is None:
+        raise ValueError("%s: gate_on='surface' needs trunc (a point with no compatible face counts as truncated; without trunc "
+                         "the loss would be infinite)" % what)
+
+
+def _normal_gate(what, normal_angle, normal_faces, scans, n, trunc, faces, device, gate_on="vertices"):
+    """Validates the arguments of a normal gate -> None (no gate) or (cos_min, FaceTable the vertex normals come from).  With
+    gate_on="surface" the gate is the face-normal gate of the surface search and `faces` must already be a FaceTable."""
+    _check_gate_on(what, gate_on, normal_angle, faces, scans, trunc)
+    if gate_on == "surface":
+        a = float(normal_angle)
+        ft = faces if normal_faces is None else _face_table(normal_faces, n, device)
+        if ft.n != n or faces.n != n:
+            raise ValueError("%s: the face table was made for %d vertices, the model has %d" % (what, ft.n if ft.n != n else faces.n, n))
+        return (-math.inf if a == 180.0 else math.cos(math.radians(a))), ft
     if normal_angle is None:
         return None
     a = float(normal_angle)
     if not 0.0 < a <= 180.0:
         raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
     if faces is not None:
-        raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built" % what)
+        raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built for the gate on vertex normals; "
+                         "gate_on='surface' gates the surface search by the face's normal" % what)
     if scans.normals is None:
         raise ValueError("%s: normal_angle needs scan normals (ScanBatch(..., normals=))" % what)
     if normal_faces is None:
@@ -235,7 +274,7 @@ def _query_normals(tn, rows):
     return tn if rows == tn.shape[1] else torch.nn.functional.pad(tn, (0, 0, 0, rows - tn.shape[1]))
 
 
-def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=True, n=None):
+def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=True, n=None, q_normals=None, normal_angle=None):
     """For every scan point q[b, j] the closest point of body b's triangles: (face int32 [B, nq], d2 fp32 [B, nq], uv fp32
     [B, nq, 2]), exact in the fp32 expression of sh_kernels.h - the lexicographic minimum of (d2, face) over all target
     triangles, uv the barycentric weights (l1, l2) of the foot point on that face (l0 = 1 - l1 - l2).  x [B, rows, 3]; faces: a
@@ -244,10 +283,24 @@ def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=
     or [B, n]: a triangle with a masked corner is no target.  No target: face -1, d2 +inf; points beyond q_count: face -1, d2 0.
     cull=True starts from the nearest vertex (one sh_nearest_points search) and tests only the triangles whose bounding sphere
     reaches inside the best distance so far; cull=False tests every pair - same bits, many times the work.  chunks: the split of
-    the triangle range (0 = chosen by the library; every split gives the same bits).  Not differentiable."""
+    the triangle range (0 = chosen by the library; every split gives the same bits).  Not differentiable.
+
+    q_normals [B, >= nq, 3] with normal_angle (degrees in (0, 180]; both or neither): the bare gated search
+    (sh_nearest_surface_gated) - only the triangles whose face normal (`face_normals(x, faces)`) lies within that angle of the
+    point's normal are candidates; a point with none gets face -1, d2 +inf, uv 0.  cull=True is then bounded by the gated search
+    over the face centres instead of the nearest vertex.  180 opens the gate: the ungated bits."""
     q, x = q.detach(), x.detach()
     rows = ops._points(x, "scan.nearest_surface")[1]
     ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
+    if (q_normals is None) != (normal_angle is None):
+        raise ValueError("nearest_surface: q_normals and normal_angle come together")
+    if normal_angle is not None:
+        a = float(normal_angle)
+        if not 0.0 < a <= 180.0:
+            raise ValueError("nearest_surface: normal_angle must lie in (0, 180] degrees, got %r" % (normal_angle,))
+        cos_min = -math.inf if a == 180.0 else math.cos(math.radians(a))
+        fn = ops.face_normals(x, ft.faces, ft.n)
+        return ops.nearest_surface(q, x, ft.faces, ft.n, q_count, vertex_mask, None, chunks=chunks, cull=cull, gate=(q_normals.detach(), fn, cos_min))
     bound = None
     if cull:
         bound = ops.nearest_points(q, x, q_count=q_count, t_mask=vertex_mask, nt=ft.n)[1]
@@ -268,20 +321,34 @@ def closest_points(x, faces, face, uv):
 
 class _ChamferSurface(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scans, faces, n, v_mask, mask_sb, tau2, w_ms, matches=None):
+    def forward(ctx, x, scans, faces, n, v_mask, mask_sb, tau2, w_ms, matches=None, gate=None, vertex_matches=True):
         s, cnt = scans.points, scans.counts
         rows = x.shape[1]
-        idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)    # the vertex search: the bound, and `matches`
-        face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, d2_v)
-        idx_ms = d2_ms = None
-        if w_ms > 0.0:
-            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt)
+        idx_ms = d2_ms = tn = None
+        if gate is None:
+            idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)    # the vertex search: the bound, and `matches`
+            face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, d2_v)
+            if w_ms > 0.0:
+                idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt)
+        else:                                                                       # (cos_min, FaceTable): the face-normal gate
+            cos_min, ft = gate
+            xd = x.detach()
+            fn = ops.face_normals(xd, faces, n)                                     # once per forward pass
+            face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, None, gate=(scans.normals, fn, cos_min))
+            idx_sm = d2_v = None
+            record = matches is not None and vertex_matches
+            if w_ms > 0.0 or record:
+                tn = ops.vertex_normals(xd, ft.faces, ft.vf_ptr, ft.vf_idx, n)
+            if w_ms > 0.0:                                                          # vertex to scan point, gated by vertex normals
+                idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt, gate=(_query_normals(tn, rows), scans.normals, cos_min))
+            if record:                                                              # the gated VERTEX matches, for `pose_update`
+                idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, gate=(scans.normals, tn, cos_min))
         loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
         ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
         ctx.save_for_backward(x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts)
         if matches is not None:
             matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_v, idx_ms=idx_ms,
-                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces, tn=None)
+                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces, tn=tn)
         return loss
 
     @staticmethod
@@ -289,7 +356,7 @@ class _ChamferSurface(torch.autograd.Function):
         x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts = ctx.saved_tensors
         g = ops.chamfer_surface_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, faces, face, d2_sm, uv, idx_ms, d2_ms, ctx.v_mask,
                                     ctx.mask_sb, counts, ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None, None, None
 
 
 class _Chamfer(torch.autograd.Function):
@@ -324,7 +391,7 @@ class _Chamfer(torch.autograd.Function):
 
 
 def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None, normal_angle=None,
-            normal_faces=None):
+            normal_faces=None, gate_on="vertices", _vertex_matches=True):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -354,12 +421,29 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     most that angle, in both directions (sh_nearest_points_gated; the test is cos(angle) against the fp32 dot product; 180 opens
     the gate and gives the ungated bits).  A zero ("unknown") normal is compatible only for angles >= 90.  A point with no
     compatible partner is recorded as idx -1, d2 +inf and counts as truncated: it adds trunc^2 and takes no part in the
-    gradient or in `pose_update` - which is why a gate needs `trunc`.  Not built together with `faces=`."""
+    gradient or in `pose_update` - which is why a gate needs `trunc`.  This gate, on VERTEX normals, is not built together with
+    `faces=`.
+
+    gate_on: "vertices" (the default: everything above, bit for bit, every error included) or "surface" - the gate for `faces=`,
+    on the FACE's normal (needs faces, normal_angle, scan normals and trunc; normal_faces may be omitted and is then `faces`).
+    The scan -> model term is the distance to the closest point of the faces whose normal (`face_normals(x_hat)`, once per
+    forward pass) lies within normal_angle of the point's (sh_nearest_surface_gated: exact, bounded by the gated search over the
+    face centres); a point with no compatible face is recorded as face -1, d2 +inf and counts as truncated.  The model -> scan
+    term stays vertex to scan point and is gated by the vertex normals as above.  The backward pass is that of `faces=`.
+    `matches` keeps its keys: `face`, `uv`, `d2_surface` are the gated surface results, `idx_sm` / `d2_sm` the gated VERTEX
+    matches (one more gated vertex search, run only when `matches` is given), `tn` the vertex normals when they were computed.
+    180 degrees gives the ungated `faces=` loss and gradient, bit for bit."""
     scans, B, rows, n = _check_pair(x_hat, scans, n, "chamfer")
     w, tau2 = _check_weights(w_model_to_scan, trunc, "chamfer")
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
-    gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device)
-    if faces is not None:
+    on_surface = gate_on == "surface"
+    if on_surface and faces is not None:
+        faces = _face_table(faces, n, x_hat.device)
+    gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device, gate_on)
+    if on_surface:
+        ft = gate[1]
+        loss = _ChamferSurface.apply(x_hat, scans, faces.faces, n, v_mask, mask_sb, tau2, w, matches, gate, _vertex_matches)
+    elif faces is not None:
         ft = _face_table(faces, n, x_hat.device)
         loss = _ChamferSurface.apply(x_hat, scans, ft.faces, n, v_mask, mask_sb, tau2, w, matches)
     else:
@@ -579,7 +663,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
 
 
 def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
-          normal_angle=None, normal_faces=None, faces=None, cull=True, step="point"):
+          normal_angle=None, normal_faces=None, faces=None, cull=True, step="point", gate_on="vertices"):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -607,7 +691,13 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     Partial scans: mode="rigid", w_model_to_scan=0.  A similarity reaches the model's frame only under the normalisations that
     are similarities (zeromean, zeroroot, onelength, small), not under gass or normal.  With faces= the closed form is still
     point-to-point (on foot points): along the surface it slides slowly - step="plane" is the remedy.  faces= together
-    with normal_angle is not built, and the model -> scan term stays vertex to scan point.
+    with normal_angle needs gate_on="surface" (the gate on vertex normals is not built for the surface distance), and the model
+    -> scan term stays vertex to scan point.
+
+    gate_on: "vertices" (the default: everything above, bit for bit) or "surface" - with faces=, normal_angle, scan normals and
+    trunc: every iteration's surface search is the face-normal-gated one of `chamfer(..., gate_on="surface")` (face normals
+    once, x is fixed; the scan's normals follow the pose), no vertex search is run for the scan -> model side, and the model ->
+    scan search is gated by the vertex normals.  Works with step="point" and step="plane".
 
     step: "point" (the default: everything above, bit for bit) or "plane" - every iteration's pose step is the linearised
     point-to-plane step of `pose_update(..., step="plane")` on the same pairs: a scan point may slide along the model's surface
@@ -627,7 +717,10 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     w, tau2 = _check_weights(w_model_to_scan, trunc, "align")
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
     x = x.detach()
-    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, faces, x.device)
+    if gate_on == "surface" and faces is not None:
+        faces = _face_table(faces, n, x.device)
+    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, faces, x.device, gate_on)
+    surf_gate = gate is not None and gate_on == "surface"
     ft = None if faces is None else _face_table(faces, n, x.device)                     # x is fixed: once
     if step not in ("point", "plane"):
         raise ValueError("align: step must be 'point' or 'plane'")
@@ -652,7 +745,8 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     log = torch.empty((iters, B), dtype=torch.float32, device=x.device)
     cnt = scans.counts
     M = scans.points.shape[1]
-    sm = (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device))
+    sm = (None, None) if surf_gate else \
+        (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device))   # gated surface: no vertex search on the scan -> model side
     ms = (torch.empty((B, rows), dtype=torch.int32, device=x.device), torch.empty((B, rows), dtype=torch.float32, device=x.device)) if w > 0.0 \
         else (None, None)
     counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
@@ -662,19 +756,25 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
               torch.empty((B, M, 2), dtype=torch.float32, device=x.device))
         matches.update(face=sf[0], d2_surface=sf[1], uv=sf[2], faces=ft.faces)
     part = None
-    tn = qn = None
-    if nt is not None and iters > 0:
+    tn = qn = fn = None
+    if nt is not None and iters > 0 and not (surf_gate and w == 0.0):
         tn = ops.vertex_normals(x, nt.faces, nt.vf_ptr, nt.vf_idx, n)                   # x is fixed: once
         qn = _query_normals(tn, rows) if gate is not None and w > 0.0 else None
+    if surf_gate and iters > 0:
+        fn = ops.face_normals(x, ft.faces, n)                                           # x is fixed: once
     solved = None
     if step == "plane":
         matches.update(tn=tn)
         solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=x.device)
     for k in range(iters):
-        g_sm = None if gate is None else (aligned.normals, tn, gate[0])
+        g_sm = None if gate is None or surf_gate else (aligned.normals, tn, gate[0])
         g_ms = None if gate is None else (qn, aligned.normals, gate[0])
-        ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=g_sm)
-        if ft is not None:
+        if surf_gate:
+            ops.nearest_surface(aligned.points, x, ft.faces, n, cnt, v_mask, None, chunks=chunks, cull=cull, out=sf,
+                                gate=(aligned.normals, fn, gate[0]))
+        else:
+            ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=g_sm)
+        if ft is not None and not surf_gate:
             ops.nearest_surface(aligned.points, x, ft.faces, n, cnt, v_mask, sm[1] if cull else None, chunks=chunks, cull=cull, out=sf)
         if w > 0.0:
             ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms, gate=g_ms)
