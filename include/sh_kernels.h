@@ -711,6 +711,61 @@ SH_API int sh_nearest_surface_gated(const float* q, int64_t q_sb, int nq, const 
                                     size_t workspace_bytes, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cloud normals: the normals of a bare point cloud, estimated from the cloud itself - per point the k nearest points of its own
+ * body and the direction of least spread among them (no reference counterpart).  Deterministic: no atomics, every sum in a fixed
+ * order, plain stores of every output element; the bits depend on neither batch, padding nor launch shape.
+ *
+ * sh_cloud_normals.  s: [B] bodies of [*][3] points, batch stride s_sb floats, M rows, count int32 [B] live rows per body or NULL
+ * (= M), clamped to [0, M]; SH_CLOUD_K_MIN <= k <= SH_CLOUD_K_MAX.
+ * Neighbourhood of point j of body b with m_b live points: k_eff = min(k, m_b);
+ *     r2[j]  = the k_eff-th smallest value of d2(s_j, s_i) over all live i - d2 the expression of sh_nearest_points with q = s_j,
+ *              t = s_i; the point itself is among the i, at distance 0
+ *     member = every live i with d2(s_j, s_i) <= r2[j];        cnt[j] = the number of members (>= k_eff)
+ * Ties at the k-th distance are all members: the set depends on neither visiting order nor index.
+ * Moments.  Per member d = s_i - s_j component-wise in fp32 (the differences d2 forms, up to sign), each component widened to
+ * fp64, where products of two of them are exact.  Nine fp64 running sums per point - S1 = sum d (3), S2 = sum d d^T (6: xx xy xz
+ * yy yz zz) - each sum = fl(sum + term), members taken in ascending i, plus the count.  No contraction (none would change a bit:
+ * the products are exact).
+ * Normal, fp64, no contraction:  mean = S1 / cnt;  C_ab = S2_ab / cnt - mean_a mean_b;  C is diagonalised by cyclic Jacobi
+ * rotations in the order (0,1) (0,2) (1,2), SH_CLOUD_JACOBI_SWEEPS sweeps, no convergence test (the rotation of sh_align_solve: t
+ * = sign(tau) / (|tau| + sqrt(1 + tau^2)), tau = (a_qq - a_pp) / (2 a_pq), the identity when a_pq == 0).  Cyclic Jacobi
+ * converges quadratically once the off-diagonal mass is below the eigenvalue gaps; from any symmetric 3 x 3 start four sweeps
+ * bring it below 2^-53 of the norm in every case tried (tests/test_cloud_normals_host.py measures it on the test clouds and on
+ * random and degenerate matrices), and the count is twice that.  Eigenvalues l0 <= l1 <= l2 are the diagonal, l0 the smallest
+ * with the lowest index on a tie; the normal is the eigenvector column of l0, divided by its fp64 length.
+ * Unknown - a row of exact zeros, var 0 - when cnt < 3 or !(l1 > SH_CLOUD_RANK_MIN * l2): coincident or collinear
+ * neighbourhoods, and any NaN.
+ * Sign.  The component of largest magnitude (fp64; the lowest index on a tie) is made positive, then each component is rounded
+ * to fp32 once: canonical, UNORIENTED.  With a viewpoint v (view != NULL; for point j it is view[b * view_sb + j * view_ps ..
+ * + 3): view_ps == 0 one viewpoint per body, view_ps == 3 one per point) the rounded normal n is negated when
+ *     (n_x (v_x - s_x) + n_y (v_y - s_y)) + n_z (v_z - s_z) < 0             (fp64 from the fp32 values, no contraction)
+ * exactly 0 (or NaN) keeps the canonical sign.
+ * Surface variation: var[j] = max(l0, 0) / ((l0 + l1) + l2) in fp64, rounded to fp32: 0 on a plane, 1/3 at most.
+ * Outputs: nrm contiguous [B][M][3]; var, r2 fp32 and cnt int32, each contiguous [B][M] and each optional (NULL: not written).
+ * Rows j >= m_b hold zeros in every output.  Without r2 the k-th distances still have to live somewhere between the two
+ * launches: workspace, B * M * sizeof(float) bytes; with r2 given the workspace is not used.
+ *
+ * How it is computed.  Two launches, both in the form of the nearest search: queries in registers, the body's points streamed
+ * through LDS tiles, every lane reading the same address.  (1) cloud_kth_kernel keeps per query a sorted list of DISTANCES ONLY
+ * in registers, of capacity CAP = 8 / 16 / 32 / 64 (the first at or above k): CAP - k_eff slots are pre-filled with -inf, k_eff
+ * with +inf, and a candidate below the last slot is inserted through an unrolled median-of-three chain - the last slot is
+ * always the k_eff-th smallest value so far.  The insertion stands under a wave ballot.  1, 2 or 4 queries per thread, chosen
+ * from B and M to fill the chip; the k-th smallest of a set depends on none of it.  (2) cloud_normals_kernel sweeps the body
+ * once more in ascending i with the compare d2 <= r2[j] on every candidate and the fp64 sums under a wave ballot, never split
+ * over target ranges, and finishes each point in its own thread.  No atomics, no scratch memory.
+ * Brute force: O(m_b^2) distances per body, meant to run once per scan.  B == 0 or M == 0: SH_OK, nothing launched.  k out of
+ * range, a null s or nrm, negative sizes, strides shorter than a body or viewpoint strides that fit neither layout:
+ * SH_ERR_INVALID_ARG before the device is touched.
+ */
+#define SH_CLOUD_K_MIN 3
+#define SH_CLOUD_K_MAX 64
+#define SH_CLOUD_JACOBI_SWEEPS 8
+#define SH_CLOUD_RANK_MIN 1e-12
+SH_API int sh_cloud_normals(const float* s, int64_t s_sb, int M, const int32_t* count, int B, int k, const float* view,
+                            int64_t view_sb, int64_t view_ps, float* nrm, float* var, float* r2, int32_t* cnt, void* workspace,
+                            size_t workspace_bytes, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.

@@ -131,32 +131,6 @@ __device__ __forceinline__ void compose_pose(double c, const double (&Rm)[3][3],
     *so = (float)(c * s0);
 }
 
-// One Jacobi rotation of the symmetric 4 x 4 matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.
-// Select form: a zero off-diagonal element gives the identity rotation, no branch.
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4]) {
-    const double apq = a[P][Q];
-    const double tau = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-    double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-    t = (apq != 0.0 && t == t) ? t : 0.0;                                // apq == 0, or tau = +-inf / NaN: nothing to rotate
-    const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                        // columns P, Q
-        const double akp = a[k][P], akq = a[k][Q];
-        a[k][P] = c * akp - sn * akq; a[k][Q] = sn * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                        // rows P, Q
-        const double apk = a[P][k], aqk = a[Q][k];
-        a[P][k] = c * apk - sn * aqk; a[Q][k] = sn * apk + c * aqk;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vkp = v[k][P], vkq = v[k][Q];
-        v[k][P] = c * vkp - sn * vkq; v[k][Q] = sn * vkp + c * vkq;
-    }
-}
-
 // One wave per body.  Lane c < NP adds the ranges' partial sums of component c in range order (scan -> model ranges, then
 // model -> scan ranges) and the two directions are joined with their weights; lane 0 then solves for the pose.
 __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restrict__ partials, int M, int n, const int32_t* __restrict__ s_count,

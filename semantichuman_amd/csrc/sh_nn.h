@@ -24,6 +24,33 @@ __device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, f
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
 }
 
+// One Jacobi rotation of the symmetric N x N matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.
+// Select form: a zero off-diagonal element gives the identity rotation, no branch.  N is deduced: align.hip's 4 x 4 (Horn's
+// matrix) and cloud_normals.hip's 3 x 3 (a neighbourhood's covariance) run the same expressions.
+template <int P, int Q, int N>
+__device__ __forceinline__ void jacobi_rotate(double (&a)[N][N], double (&v)[N][N]) {
+    const double apq = a[P][Q];
+    const double tau = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+    double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+    t = (apq != 0.0 && t == t) ? t : 0.0;                                // apq == 0, or tau = +-inf / NaN: nothing to rotate
+    const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {                                        // columns P, Q
+        const double akp = a[k][P], akq = a[k][Q];
+        a[k][P] = c * akp - sn * akq; a[k][Q] = sn * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) {                                        // rows P, Q
+        const double apk = a[P][k], aqk = a[Q][k];
+        a[P][k] = c * apk - sn * aqk; a[Q][k] = sn * apk + c * aqk;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double vkp = v[k][P], vkq = v[k][Q];
+        v[k][P] = c * vkp - sn * vkq; v[k][Q] = sn * vkp + c * vkq;
+    }
+}
+
 // The split actually run for a request of `chunks` (0 = automatic: fill the chip) over nt targets in LDS tiles of `tile`, with
 // `qt` queries per workgroup: whole tiles per chunk, no empty chunk.  Rounding the result once more changes nothing.
 static inline int nn_resolve_chunks(int B, int nq, int nt, int tile, int qt, int chunks, int* tiles_per_chunk) {

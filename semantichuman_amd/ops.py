@@ -487,6 +487,34 @@ def vertex_normals(x, faces, vf_ptr, vf_idx, n, out=None):
     return nrm
 
 
+CLOUD_K_MIN, CLOUD_K_MAX = 3, 64   # SH_CLOUD_K_MIN, SH_CLOUD_K_MAX
+
+
+def cloud_normals(s, count=None, k=16, view=None, out=None):
+    """sh_cloud_normals: s [B, M, 3] clouds, count [B] live rows per body (None = all), k neighbours (the point itself counts),
+    view: None, fp32 HIP [B, 3] (one viewpoint per body) or [B, M, 3] (one per point) -> (nrm fp32 [B, M, 3], var fp32 [B, M],
+    r2 fp32 [B, M], cnt int32 [B, M]), all contiguous; rows beyond a body's count are zero in all four."""
+    B, M, s_sb = _points(s, "cloud_normals")
+    k = int(k)
+    if not CLOUD_K_MIN <= k <= CLOUD_K_MAX:
+        raise ValueError("cloud_normals: k = %d outside [%d, %d]" % (k, CLOUD_K_MIN, CLOUD_K_MAX))
+    count = _count_arg(count, B, s.device)
+    view_sb = view_ps = 0
+    if view is not None:
+        if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous()
+                and tuple(view.shape) in ((B, 3), (B, M, 3))):
+            raise ValueError("cloud_normals: view must be a contiguous fp32 HIP tensor [%d, 3] or [%d, %d, 3], got %s"
+                             % (B, B, M, tuple(getattr(view, "shape", ()))))
+        view_sb, view_ps = (3, 0) if view.dim() == 2 else (3 * M, 3)
+    nrm, var, r2, cnt = out if out is not None else (torch.empty((B, M, 3), dtype=torch.float32, device=s.device),
+                                                     torch.empty((B, M), dtype=torch.float32, device=s.device),
+                                                     torch.empty((B, M), dtype=torch.float32, device=s.device),
+                                                     torch.empty((B, M), dtype=torch.int32, device=s.device))
+    check(_lib.load().sh_cloud_normals(ptr(s), s_sb, M, ptr(count), B, k, ptr(view), view_sb, view_ps, ptr(nrm), ptr(var), ptr(r2), ptr(cnt),
+                                       None, 0, stream_ptr()), "sh_cloud_normals")
+    return nrm, var, r2, cnt
+
+
 def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None):
     """sh_chamfer_fwd -> (loss [B], counts int32 [B, 2])."""
     B, M = d2_sm.shape

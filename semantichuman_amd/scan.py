@@ -15,6 +15,9 @@
   * `ScanBatch(..., normals=)`, `vertex_normals(x, faces)`, `normal_angle=` on chamfer / align  matching by normal: the scan's
                                      normals and the model's area-weighted vertex normals (sh_vertex_normals) gate every pair of
                                      the vertex search (sh_nearest_points_gated) - off unless `normal_angle` is given
+  * `estimate_normals(points, k)`, `ScanBatch(..., normals="estimate")`  normals of a bare cloud, from the cloud: per point the k
+                                     nearest points of its own cloud and the direction of least spread among them
+                                     (sh_cloud_normals) - unoriented unless `viewpoints` are given
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -80,6 +83,44 @@ def pack_normals(normals, counts, width):
     return out
 
 
+def _check_normal_k(what, k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not ops.CLOUD_K_MIN <= int(k) <= ops.CLOUD_K_MAX:
+        raise ValueError("%s: the neighbour count must be an integer in [%d, %d], got %r" % (what, ops.CLOUD_K_MIN, ops.CLOUD_K_MAX, k))
+    return int(k)
+
+
+def pack_viewpoints(viewpoints, counts, width):
+    """Sensor positions for `estimate_normals`, host side: [3] (one for all bodies) or [B, 3] (one per body) -> float32 [B, 3]; a
+    list of [m_b, 3] arrays, one row per point (a fused multi-view scan), -> float32 [B, width, 3], zero-padded.  ValueError on
+    a shape that fits none of the three, NaN or inf."""
+    B = len(counts)
+    v = viewpoints
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    if isinstance(v, (list, tuple)) and len(v) == B and all(np.ndim(c) == 2 for c in v):
+        rows = [c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c) for c in v]
+        out = np.zeros((B, int(width), 3), dtype=np.float32)
+        for b, (c, m) in enumerate(zip(rows, counts)):
+            if c.shape != (int(m), 3):
+                raise ValueError("viewpoints: body %d has shape %s, its cloud has [%d, 3]" % (b, c.shape, m))
+            out[b, :m] = c
+    else:
+        try:
+            a = np.asarray(v, dtype=np.float32)
+        except (ValueError, TypeError):
+            a = None
+        if a is not None and a.shape == (3,):
+            out = np.array(np.broadcast_to(a, (B, 3)))                                # a copy: writable
+        elif a is not None and a.shape == (B, 3):
+            out = np.ascontiguousarray(a)
+        else:
+            raise ValueError("viewpoints must be [3], [%d, 3] or a list of %d arrays [m_b, 3], got %s"
+                             % (B, B, "shape %s" % (a.shape,) if a is not None else type(viewpoints).__name__))
+    if not np.isfinite(out).all():
+        raise ValueError("viewpoints hold NaN or inf")
+    return out
+
+
 def morton_order(points, bits=10):
     """The permutation that sorts an [m, 3] cloud along the Morton (Z-order) curve of its own bounding box, `bits` bits per axis;
     a stable sort, so equal codes keep their order.  Host side, numpy only."""
@@ -108,13 +149,29 @@ class ScanBatch:
 
     normals: None, or the clouds' normals row for row (a list of [m_b, 3] arrays or one [B, M, 3] array; `pack_normals`): kept as
     `normals`, fp32 [B, Mmax, 3] unit rows on the device, sorted with their points; a zero row means "unknown".  They are used
-    only where a `normal_angle` is asked for."""
+    only where a `normal_angle` is asked for.
 
-    def __init__(self, clouds, device, order=None, normals=None):
+    normals="estimate": the clouds carry none - a depth camera's output, a fused cloud - and they are estimated from the resident
+    points, after any sort, by `estimate_normals(self, normal_k, viewpoints)` (sh_cloud_normals: the direction of least spread of
+    each point's normal_k nearest points, the point included) and kept as `normals` exactly as given ones are: fp32 unit rows, a
+    zero row where the neighbourhood is coincident or collinear.  viewpoints: None, or where the sensor stood, in the clouds'
+    frame - [3], [B, 3] or a list of [m_b, 3] arrays (one row per point, in the order of the clouds given; sorted with them) - and
+    every normal then points into its viewpoint's half space.  Without viewpoints the normals are UNORIENTED: the sign is a
+    convention (largest component positive), so about half of them point into the body, and a gate narrower than 90 degrees
+    rejects correct partners; a gate blind to orientation (on |cos|) is not part of the library.  normal_k and viewpoints are
+    read only with normals="estimate".  ValueError for a normal_k outside [3, 64] or viewpoints of another shape."""
+
+    def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None):
         if order not in (None, "morton"):
             raise ValueError("ScanBatch: order must be None or 'morton'")
+        estimate = isinstance(normals, str)
+        if estimate:
+            if normals != "estimate":
+                raise ValueError("ScanBatch: normals must be None, arrays or 'estimate', got %r" % (normals,))
+            normal_k = _check_normal_k("ScanBatch: normal_k", normal_k)
         pts, counts = pack_clouds(clouds)
-        nrm = None if normals is None else pack_normals(normals, counts, pts.shape[1])
+        view = pack_viewpoints(viewpoints, counts, pts.shape[1]) if estimate and viewpoints is not None else None
+        nrm = None if normals is None or estimate else pack_normals(normals, counts, pts.shape[1])
         self.perm = None
         if order == "morton":
             self.perm = np.full(pts.shape[:2], -1, dtype=np.int64)
@@ -123,11 +180,15 @@ class ScanBatch:
                 pts[b, :m] = pts[b, :m][self.perm[b, :m]]
                 if nrm is not None:
                     nrm[b, :m] = nrm[b, :m][self.perm[b, :m]]
+                if view is not None and view.ndim == 3:
+                    view[b, :m] = view[b, :m][self.perm[b, :m]]
         dev = torch.device(device)
         self.host_counts = counts
         self.points = torch.from_numpy(pts).to(dev)
         self.counts = torch.from_numpy(counts).to(dev)
         self.normals = None if nrm is None else torch.from_numpy(nrm).to(dev)
+        if estimate:
+            self.normals = ops.cloud_normals(self.points, self.counts, normal_k, None if view is None else torch.from_numpy(view).to(dev))[0]
 
     def __len__(self):
         return self.points.shape[0]
@@ -143,6 +204,41 @@ class ScanBatch:
         """The bodies `sl` (a slice) as a ScanBatch sharing this one's memory."""
         return ScanBatch._from_parts(self.points[sl], self.counts[sl].contiguous(), self.host_counts[sl],
                                      None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl])
+
+
+def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
+    """Normals of bare point clouds, estimated from the clouds themselves (sh_cloud_normals; include/sh_kernels.h, "Cloud
+    normals").  points_or_scans: a ScanBatch, or fp32 HIP points [B, M, 3] with optional live counts [B].  For every point: its
+    neighbourhood is the k nearest points of its own cloud, itself included and every tie at the k-th distance with them (k is
+    cut to the cloud's size); the normal is the eigenvector of the smallest eigenvalue of the neighbourhood's covariance (fp64
+    moments of fp32 differences, a fixed-sweep Jacobi), a unit fp32 row.  -> (normals fp32 [B, M, 3], variation fp32 [B, M] =
+    l0 / (l0 + l1 + l2), 0 on a plane and large on edges and noise, radius2 fp32 [B, M] the squared k-th distance, count int32
+    [B, M] the neighbourhood's size), on the device; rows beyond a cloud's count are zero in all four.  A point whose
+    neighbourhood is coincident or collinear, or has fewer than 3 members, gets the zero normal: "unknown", as everywhere.
+
+    viewpoints: None - the sign is then a convention (the component of largest magnitude is positive) and the normals are
+    UNORIENTED - or the sensor positions: host [3] / [B, 3] / a list of [m_b, 3] arrays (`pack_viewpoints`), or an fp32 HIP
+    tensor [B, 3] / [B, M, 3], rows in the order of the points as they are resident.  A normal is then flipped when it points
+    away from its viewpoint.  Brute force, O(M^2) per cloud: meant to run once per scan.  Deterministic - the same bits for a
+    cloud alone and inside any padded batch.  Not differentiable.  ValueError for k outside [3, 64]."""
+    k = _check_normal_k("estimate_normals: k", k)
+    if isinstance(points_or_scans, ScanBatch):
+        if counts is not None:
+            raise ValueError("estimate_normals: a ScanBatch brings its own counts")
+        pts, cnt, host_counts = points_or_scans.points, points_or_scans.counts, points_or_scans.host_counts
+    else:
+        pts = points_or_scans.detach() if torch.is_tensor(points_or_scans) else points_or_scans
+        B, M, _ = ops._points(pts, "scan.estimate_normals")
+        cnt = ops._count_arg(counts, B, pts.device)
+        host_counts = None
+    view = viewpoints
+    if view is not None and not (torch.is_tensor(view) and view.is_cuda):
+        if host_counts is None:
+            host_counts = np.full(pts.shape[0], pts.shape[1], np.int64) if cnt is None else cnt.cpu().numpy()
+        view = torch.from_numpy(pack_viewpoints(view, host_counts, pts.shape[1])).to(pts.device)
+    elif view is not None:
+        view = view.detach().to(torch.float32).contiguous()
+    return ops.cloud_normals(pts, cnt, k, view)
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
