@@ -34,38 +34,28 @@ __device__ __forceinline__ double foot_coord(float a, float b, float c, float v,
 // the zero vector when its length is zero or not finite.
 __device__ __forceinline__ void face_normal(const float* a, const float* b, const float* c, double& n0, double& n1, double& n2) {
 #pragma clang fp contract(off)
-    const float abx = b[0] - a[0], aby = b[1] - a[1], abz = b[2] - a[2];
-    const float acx = c[0] - a[0], acy = c[1] - a[1], acz = c[2] - a[2];
-    const double cx = __builtin_fmaf(aby, acz, -(abz * acy)), cy = __builtin_fmaf(abz, acx, -(abx * acz)),
-                 cz = __builtin_fmaf(abx, acy, -(aby * acx));
+    float fx, fy, fz;
+    face_cross(a, b, c, fx, fy, fz);
+    const double cx = fx, cy = fy, cz = fz;
     const double len = sqrt((cx * cx + cy * cy) + cz * cz);
     const bool ok = len > 0.0 && len < __builtin_inf();
     const double d = ok ? len : 1.0;
     n0 = ok ? cx / d : 0.0; n1 = ok ? cy / d : 0.0; n2 = ok ? cz / d : 0.0;
 }
 
-// grid (range, body).  Ranges [0, r_sm) walk the scan -> model pairs j, ranges [r_sm, r_sm + r_ms) the model -> scan pairs i.
-// The sums are unweighted (the weight of a direction is one factor per body, applied by align_solve_kernel); a range beyond the
-// body's count stores zeros, which change nothing when the second stage adds them.  SURFACE: idx_sm / d2_sm are the recorded face
-// and the surface distance, and the partner of s_j is the foot point on that face instead of a vertex; nothing else differs.
-template <bool SURFACE>
-__global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
-                                                           const float* __restrict__ x, long x_sb, int rows, int n,
-                                                           const unsigned char* __restrict__ v_mask, long mask_sb,
-                                                           const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
-                                                           const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms, float tau2,
-                                                           int r_sm, AlignSurface sf, double* __restrict__ partials) {
-    __shared__ double red[NP][4];
-    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int R = gridDim.x;
-    const int m = clamp_count(s_count, b, M);
-    const float* sb = s + (long)b * s_sb;
-    const float* xb = x + (long)b * x_sb;
-    double a[NP];
-#pragma unroll
-    for (int c = 0; c < NP; ++c) a[c] = 0.0;
-    auto add = [&](long ip, double q0, double q1, double q2) {
-        const double p0 = sb[3 * ip], p1 = sb[3 * ip + 1], p2 = sb[3 * ip + 2];
+// What a kept pair adds to the sums of its range, in the two forms the walk below is instantiated with.  p: the scan point (fp32
+// [3]), q: its partner.  N: sums per range, N_ACT: the slot that counts the active vertices of a model -> scan range, NORMALS:
+// whether add() takes the model's normal at the partner as well.  SCOPE: the profile labels of the vertex and the surface form.
+
+// The closed form's sums (header, "Scan alignment").  The compiler's default contraction, as ever.
+struct PointSums {
+    static constexpr int N = NP, N_ACT = 18;
+    static constexpr bool NORMALS = false;
+    static constexpr const char* SCOPE = "align_moments_kernel|B=%d M=%d n=%d ranges=%d";
+    static constexpr const char* SCOPE_SURFACE = "align_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d";
+    double a[N];
+    __device__ __forceinline__ void add(const float* p, double q0, double q1, double q2) {
+        const double p0 = p[0], p1 = p[1], p2 = p[2];
         a[0] += 1.0;
         a[1] += p0; a[2] += p1; a[3] += p2;
         a[4] += q0; a[5] += q1; a[6] += q2;
@@ -74,6 +64,62 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
         a[13] += q2 * p0; a[14] += q2 * p1; a[15] += q2 * p2;
         a[16] += p0 * p0 + p1 * p1 + p2 * p2;
         a[17] += q0 * q0 + q1 * q1 + q2 * q2;
+    }
+};
+
+// The sums of the header's "Point-to-plane step": per kept pair the Jacobian row J (7) of the residual r along the partner's
+// normal, J J^T (upper triangle), J r and r^2.  fp64, contraction off.
+struct PlaneSums {
+    static constexpr int N = NPP, N_ACT = 37;
+    static constexpr bool NORMALS = true;
+    static constexpr const char* SCOPE = "align_plane_moments_kernel|B=%d M=%d n=%d ranges=%d";
+    static constexpr const char* SCOPE_SURFACE = "align_plane_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d";
+    double a[N];
+    __device__ __forceinline__ void add(const float* p, double q0, double q1, double q2, double n0, double n1, double n2) {
+#pragma clang fp contract(off)
+        const double p0 = p[0], p1 = p[1], p2 = p[2];
+        const double res = (n0 * (p0 - q0) + n1 * (p1 - q1)) + n2 * (p2 - q2);
+        const double J[7] = {n0, n1, n2, p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, (n0 * p0 + n1 * p1) + n2 * p2};
+        a[0] += 1.0;
+        int c = 1;
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+#pragma unroll
+            for (int j = i; j < 7; ++j) a[c++] += J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) a[29 + i] += J[i] * res;
+        a[36] += res * res;
+    }
+};
+
+// Stage 1 of both pose steps: the one walk over the matched pairs.  grid (range, body).  Ranges [0, r_sm) walk the scan -> model
+// pairs j, ranges [r_sm, r_sm + r_ms) the model -> scan pairs i.  The sums are unweighted (the weight of a direction is one factor
+// per body, applied by the solve kernel); a range beyond the body's count stores zeros, which change nothing when the second stage
+// adds them.  SURFACE: idx_sm / d2_sm are the recorded face and the surface distance, and the partner of s_j is the foot point on
+// that face instead of a vertex - with the face's normal, formed from the three corners the foot point needs anyway, where Sums
+// takes one; nothing else differs.  A vertex partner's normal is its row of tn, which no other form reads.
+template <class Sums, bool SURFACE>
+__global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
+                                                         const float* __restrict__ x, long x_sb, int rows, int n,
+                                                         const unsigned char* __restrict__ v_mask, long mask_sb, const float* __restrict__ tn,
+                                                         const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
+                                                         const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms, float tau2,
+                                                         int r_sm, AlignSurface sf, double* __restrict__ partials) {
+    constexpr int N = Sums::N;
+    __shared__ double red[N][4];
+    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int R = gridDim.x;
+    const int m = clamp_count(s_count, b, M);
+    const float* sb = s + (long)b * s_sb;
+    const float* xb = x + (long)b * x_sb;
+    const float* tb = Sums::NORMALS && tn ? tn + (long)b * n * 3 : nullptr;
+    Sums acc;
+#pragma unroll
+    for (int c = 0; c < N; ++c) acc.a[c] = 0.0;
+    auto add_vertex = [&](long ip, int i) {                              // the partner of scan point ip is vertex i
+        const float* q = xb + 3L * i;
+        if constexpr (Sums::NORMALS) acc.add(sb + 3 * ip, q[0], q[1], q[2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
+        else acc.add(sb + 3 * ip, q[0], q[1], q[2]);
     };
     if (r < r_sm) {                                                      // uniform over the workgroup
         const int lo = r * RANGE, hi = min(lo + RANGE, m);
@@ -86,9 +132,14 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
                 if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
                 const float v = sf.uv[2 * ((long)b * M + j)], w = sf.uv[2 * ((long)b * M + j) + 1];
                 const float *ca = xb + 3L * i0, *cb = xb + 3L * i1, *cc = xb + 3L * i2;
-                add(j, foot_coord(ca[0], cb[0], cc[0], v, w), foot_coord(ca[1], cb[1], cc[1], v, w), foot_coord(ca[2], cb[2], cc[2], v, w));
+                double n0, n1, n2;                                       // the face's, only where Sums takes a normal
+                if constexpr (Sums::NORMALS) face_normal(ca, cb, cc, n0, n1, n2);
+                const double q0 = foot_coord(ca[0], cb[0], cc[0], v, w), q1 = foot_coord(ca[1], cb[1], cc[1], v, w),
+                             q2 = foot_coord(ca[2], cb[2], cc[2], v, w);
+                if constexpr (Sums::NORMALS) acc.add(sb + 3L * j, q0, q1, q2, n0, n1, n2);
+                else acc.add(sb + 3L * j, q0, q1, q2);
             } else {
-                if (i >= 0 && i < n) add(j, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2]);
+                if (i >= 0 && i < n) add_vertex(j, i);
             }
         }
     } else {
@@ -96,18 +147,18 @@ __global__ __launch_bounds__(NT) void align_moments_kernel(const float* __restri
         const int lo = (r - r_sm) * RANGE, hi = min(lo + RANGE, n);
         for (int i = lo + tid; i < hi; i += NT) {
             if (mb && mb[i] == 0) continue;
-            a[18] += 1.0;                                                // n_act
+            acc.a[Sums::N_ACT] += 1.0;                                   // n_act
             const int k = idx_ms[(long)b * rows + i];
-            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add(k, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2]);
+            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add_vertex(k, i);
         }
     }
 #pragma unroll
-    for (int c = 0; c < NP; ++c) {
-        const double v = wave_sum_d(a[c]);
+    for (int c = 0; c < N; ++c) {
+        const double v = wave_sum_d(acc.a[c]);
         if ((tid & 63) == 0) red[c][tid >> 6] = v;
     }
     __syncthreads();
-    if (tid < NP) partials[((long)b * R + r) * NP + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
+    if (tid < N) partials[((long)b * R + r) * N + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
 }
 
 // The pose so far composed with the increment (c R, t): A_new = c R A_old, t_new = c R t_old + t, scale_new = c scale_old, each
@@ -131,8 +182,29 @@ __device__ __forceinline__ void compose_pose(double c, const double (&Rm)[3][3],
     *so = (float)(c * s0);
 }
 
-// One wave per body.  Lane c < NP adds the ranges' partial sums of component c in range order (scan -> model ranges, then
-// model -> scan ranges) and the two directions are joined with their weights; lane 0 then solves for the pose.
+// How both solve kernels open, one wave per body: lane c < Sums::N adds the ranges' partial sums of component c in range order,
+// the scan -> model ranges into sum[0][c] and the model -> scan ranges into sum[1][c]; w1 and w2 are the weights the two
+// directions are then joined with.
+template <class Sums>
+__device__ __forceinline__ void sum_ranges(const double* __restrict__ partials, int b, int lane, int r_sm, int r_ms, int M,
+                                           const int32_t* __restrict__ s_count, float w_ms, double (&sum)[2][Sums::N], double& w1, double& w2) {
+    constexpr int N = Sums::N;
+    const int R = r_sm + r_ms;
+    if (lane < N) {
+        double u = 0.0, w = 0.0;
+        for (int r = 0; r < r_sm; ++r) u += partials[((long)b * R + r) * N + lane];
+        for (int r = r_sm; r < R; ++r) w += partials[((long)b * R + r) * N + lane];
+        sum[0][lane] = u; sum[1][lane] = w;
+    }
+    __syncthreads();
+    const int m = clamp_count(s_count, b, M);
+    const double n_act = sum[1][Sums::N_ACT];
+    w1 = m > 0 ? 1.0 / (double)m : 0.0;
+    w2 = (m > 0 && r_ms > 0 && n_act > 0.0) ? (double)w_ms / n_act : 0.0;
+}
+
+// The closed form's stage 2, one wave per body: the ranges' sums (sum_ranges), the two directions joined with their weights - the
+// kept count exact, in a slot of its own -, and lane 0 then solves for the pose.
 __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restrict__ partials, int M, int n, const int32_t* __restrict__ s_count,
                                                         float w_ms, int r_sm, int r_ms, int mode, const float* __restrict__ pose_in,
                                                         const float* __restrict__ scale_in, float* __restrict__ pose_out,
@@ -140,18 +212,8 @@ __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restric
     __shared__ double sum[2][NP];
     __shared__ double mo[NM];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int R = r_sm + r_ms;
-    if (lane < NP) {
-        double u = 0.0, w = 0.0;
-        for (int r = 0; r < r_sm; ++r) u += partials[((long)b * R + r) * NP + lane];
-        for (int r = r_sm; r < R; ++r) w += partials[((long)b * R + r) * NP + lane];
-        sum[0][lane] = u; sum[1][lane] = w;
-    }
-    __syncthreads();
-    const int m = clamp_count(s_count, b, M);
-    const double n_act = sum[1][18];
-    const double w1 = m > 0 ? 1.0 / (double)m : 0.0;
-    const double w2 = (m > 0 && r_ms > 0 && n_act > 0.0) ? (double)w_ms / n_act : 0.0;
+    double w1, w2;
+    sum_ranges<PointSums>(partials, b, lane, r_sm, r_ms, M, s_count, w_ms, sum, w1, w2);
     if (lane < 18) mo[lane] = w1 * sum[0][lane] + w2 * sum[1][lane];
     if (lane == 18) mo[18] = (w1 > 0.0 ? sum[0][0] : 0.0) + (w2 > 0.0 ? sum[1][0] : 0.0);       // kept pairs, exact
     if (lane == 19) mo[19] = 0.0;
@@ -233,84 +295,8 @@ __global__ __launch_bounds__(64) void align_solve_kernel(const double* __restric
     compose_pose(c, Rm, t, pose_in + (long)b * 12, scale_in[b], pose_out + (long)b * 12, scale_out + b);
 }
 
-// The point-to-plane step's stage 1: align_moments_kernel's grid, ranges, kept rule and tree, with the sums of the header's
-// "Point-to-plane step" - per kept pair the Jacobian row J (7) of the residual r along the partner's normal, J J^T (upper
-// triangle), J r and r^2.  fp64, contraction off.  SURFACE: the partner is the foot point and the normal that of the recorded
-// face, formed from the three corners the foot point needs anyway; otherwise partner and normal are gathered by idx_sm.
-template <bool SURFACE>
-__global__ __launch_bounds__(NT) void align_plane_moments_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
-                                                                 const float* __restrict__ x, long x_sb, int rows, int n,
-                                                                 const unsigned char* __restrict__ v_mask, long mask_sb,
-                                                                 const float* __restrict__ tn, const int32_t* __restrict__ idx_sm,
-                                                                 const float* __restrict__ d2_sm, const int32_t* __restrict__ idx_ms,
-                                                                 const float* __restrict__ d2_ms, float tau2, int r_sm, AlignSurface sf,
-                                                                 double* __restrict__ partials) {
-    __shared__ double red[NPP][4];
-    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int R = gridDim.x;
-    const int m = clamp_count(s_count, b, M);
-    const float* sb = s + (long)b * s_sb;
-    const float* xb = x + (long)b * x_sb;
-    const float* tb = tn ? tn + (long)b * n * 3 : nullptr;
-    double a[NPP];
-#pragma unroll
-    for (int c = 0; c < NPP; ++c) a[c] = 0.0;
-    auto add = [&](long ip, double q0, double q1, double q2, double n0, double n1, double n2) {
-#pragma clang fp contract(off)
-        const double p0 = sb[3 * ip], p1 = sb[3 * ip + 1], p2 = sb[3 * ip + 2];
-        const double res = (n0 * (p0 - q0) + n1 * (p1 - q1)) + n2 * (p2 - q2);
-        const double J[7] = {n0, n1, n2, p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, (n0 * p0 + n1 * p1) + n2 * p2};
-        a[0] += 1.0;
-        int c = 1;
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-#pragma unroll
-            for (int j = i; j < 7; ++j) a[c++] += J[i] * J[j];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) a[29 + i] += J[i] * res;
-        a[36] += res * res;
-    };
-    if (r < r_sm) {                                                      // uniform over the workgroup
-        const int lo = r * RANGE, hi = min(lo + RANGE, m);
-        for (int j = lo + tid; j < hi; j += NT) {
-            const int i = idx_sm[(long)b * M + j];
-            if (!(d2_sm[(long)b * M + j] < tau2)) continue;
-            if constexpr (SURFACE) {
-                if ((unsigned)i >= (unsigned)sf.nF) continue;
-                const int i0 = sf.faces[3L * i], i1 = sf.faces[3L * i + 1], i2 = sf.faces[3L * i + 2];
-                if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
-                const float v = sf.uv[2 * ((long)b * M + j)], w = sf.uv[2 * ((long)b * M + j) + 1];
-                const float *ca = xb + 3L * i0, *cb = xb + 3L * i1, *cc = xb + 3L * i2;
-                double n0, n1, n2;
-                face_normal(ca, cb, cc, n0, n1, n2);
-                add(j, foot_coord(ca[0], cb[0], cc[0], v, w), foot_coord(ca[1], cb[1], cc[1], v, w), foot_coord(ca[2], cb[2], cc[2], v, w), n0, n1,
-                    n2);
-            } else {
-                if (i >= 0 && i < n) add(j, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
-            }
-        }
-    } else {
-        const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
-        const int lo = (r - r_sm) * RANGE, hi = min(lo + RANGE, n);
-        for (int i = lo + tid; i < hi; i += NT) {
-            if (mb && mb[i] == 0) continue;
-            a[37] += 1.0;                                                // n_act
-            const int k = idx_ms[(long)b * rows + i];
-            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2)
-                add(k, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NPP; ++c) {
-        const double v = wave_sum_d(a[c]);
-        if ((tid & 63) == 0) red[c][tid >> 6] = v;
-    }
-    __syncthreads();
-    if (tid < NPP) partials[((long)b * R + r) * NPP + tid] = ((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3];
-}
-
-// The point-to-plane step's stage 2, one wave per body: lane c < NPP adds the ranges' sums of component c in range order per
-// direction, the two directions are joined with align_solve_kernel's weights, and lane 0 solves the leading k x k block of
+// The point-to-plane step's stage 2, one wave per body: the ranges' sums (sum_ranges), the two directions joined with their
+// weights, and lane 0 solves the leading k x k block of
 // H delta = -g (diagonal scaling, Cholesky; fixed loop counts, selects instead of branches: the rows and columns >= k are those of
 // the identity, so every mode runs the same 7 x 7 code), turns delta into (c R, t) and composes it with the pose so far.
 __global__ __launch_bounds__(64) void align_plane_solve_kernel(const double* __restrict__ partials, int M, int n, const int32_t* __restrict__ s_count,
@@ -322,18 +308,8 @@ __global__ __launch_bounds__(64) void align_plane_solve_kernel(const double* __r
     __shared__ double sum[2][NPP];
     __shared__ double sy[NPS];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int R = r_sm + r_ms;
-    if (lane < NPP) {
-        double u = 0.0, w = 0.0;
-        for (int r = 0; r < r_sm; ++r) u += partials[((long)b * R + r) * NPP + lane];
-        for (int r = r_sm; r < R; ++r) w += partials[((long)b * R + r) * NPP + lane];
-        sum[0][lane] = u; sum[1][lane] = w;
-    }
-    __syncthreads();
-    const int m = clamp_count(s_count, b, M);
-    const double n_act = sum[1][37];
-    const double w1 = m > 0 ? 1.0 / (double)m : 0.0;
-    const double w2 = (m > 0 && r_ms > 0 && n_act > 0.0) ? (double)w_ms / n_act : 0.0;
+    double w1, w2;
+    sum_ranges<PlaneSums>(partials, b, lane, r_sm, r_ms, M, s_count, w_ms, sum, w1, w2);
     if (lane < NPS) sy[lane] = w1 * sum[0][lane] + w2 * sum[1][lane];
     __syncthreads();
     if (sys && lane < NPS) sys[(long)b * NPS + lane] = sy[lane];
@@ -464,58 +440,49 @@ int align_moments_check(const char* who, const float* s, int64_t s_sb, int M, co
     return SH_OK;
 }
 
-// sh_align_moments (sf == nullptr) and sh_align_moments_surface: the checks, then the launch.  idx_sm / d2_sm are the surface
-// form's face / d2.
+// The four moments entry points (sf == nullptr: the vertex forms; Sums: the closed form's or the point-to-plane step's sums): the
+// checks, the normals' for the plane step, then the launch.  idx_sm / d2_sm are the surface form's face / d2; tn is read by the
+// plane step only.
+template <class Sums>
 int align_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
-                  const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
+                  const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
                   const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
                   sh_stream_t stream) {
     int R = 0;
     const int rc = align_moments_check(who, s, s_sb, M, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, sf, idx_ms, d2_ms, tau2, w_ms, B, partials,
-                                       partials_bytes, NP, &R);
-    if (rc != SH_OK || R == 0) return rc;
+                                       partials_bytes, Sums::N, &R);
+    if (rc != SH_OK) return rc;
+    if constexpr (Sums::NORMALS)
+        SH_REQUIRE(tn || (sf && !(w_ms > 0.f)), SH_ERR_INVALID_ARG,
+                   "%s: null pointer (tn: only the surface form with w_ms == 0 needs no vertex normals)", who);
+    if (R == 0) return SH_OK;
+    if constexpr (Sums::NORMALS) SH_REQUIRE((long)B * n < (1L << 30), SH_ERR_UNSUPPORTED, "%s: B*n too large", who);
     const int r_sm = ranges_of(M);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)R, (unsigned)B);
     if (sf) {
-        ShProfScope ps(st, "align_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d", B, M, n, sf->nF, R);
-        SH_LAUNCH_PS(ps, align_moments_kernel<true>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask, (long)mask_sb,
-                     idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
+        ShProfScope ps(st, Sums::SCOPE_SURFACE, B, M, n, sf->nF, R);
+        SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, true>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
     } else {
-        ShProfScope ps(st, "align_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
-        SH_LAUNCH_PS(ps, align_moments_kernel<false>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask, (long)mask_sb,
-                     idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
+        ShProfScope ps(st, Sums::SCOPE, B, M, n, R);
+        SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, false>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
     }
     SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
     return SH_OK;
 }
 
-// sh_align_plane_moments (sf == nullptr) and sh_align_plane_moments_surface: the same checks, the normals', then the launch.
-int align_plane_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
-                        const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
-                        const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
-                        sh_stream_t stream) {
-    int R = 0;
-    const int rc = align_moments_check(who, s, s_sb, M, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, sf, idx_ms, d2_ms, tau2, w_ms, B, partials,
-                                       partials_bytes, NPP, &R);
-    if (rc != SH_OK) return rc;
-    SH_REQUIRE(tn || (sf && !(w_ms > 0.f)), SH_ERR_INVALID_ARG, "%s: null pointer (tn: only the surface form with w_ms == 0 needs no vertex normals)",
-               who);
-    if (R == 0) return SH_OK;
-    SH_REQUIRE((long)B * n < (1L << 30), SH_ERR_UNSUPPORTED, "%s: B*n too large", who);
-    const int r_sm = ranges_of(M);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)R, (unsigned)B);
-    if (sf) {
-        ShProfScope ps(st, "align_plane_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d", B, M, n, sf->nF, R);
-        SH_LAUNCH_PS(ps, align_plane_moments_kernel<true>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
-                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
-    } else {
-        ShProfScope ps(st, "align_plane_moments_kernel|B=%d M=%d n=%d ranges=%d", B, M, n, R);
-        SH_LAUNCH_PS(ps, align_plane_moments_kernel<false>, grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
-                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
-    }
-    SH_CHECK_LAUNCH(who + 3);
+// The checks both solve entry points make.  `joined`: mom or sys; `pose_args`: whether all that pose_out needs is there, and
+// `pose_needs` its names.
+int align_solve_check(const char* who, const double* partials, const void* joined, const float* pose_out, bool pose_args, const char* pose_needs,
+                      int M, int n, float w_ms, int mode, int B) {
+    SH_REQUIRE(partials && (joined || pose_out), SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(!pose_out || pose_args, SH_ERR_INVALID_ARG, "%s: pose_out needs %s", who, pose_needs);
+    SH_REQUIRE(B >= 0 && M >= 0 && n >= 0, SH_ERR_INVALID_ARG, "%s: bad size (B %d, M %d, n %d)", who, B, M, n);
+    SH_REQUIRE(w_ms >= 0.f, SH_ERR_INVALID_ARG, "%s: w_ms must be >= 0 (and not NaN)", who);
+    SH_REQUIRE(mode == SH_ALIGN_TRANSLATION || mode == SH_ALIGN_RIGID || mode == SH_ALIGN_SIMILARITY, SH_ERR_INVALID_ARG, "%s: unknown mode %d", who,
+               mode);
     return SH_OK;
 }
 
@@ -536,8 +503,8 @@ size_t sh_align_partials_bytes(int B, int M, int n, float w_ms) {
 int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
                      const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
                      const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes, sh_stream_t stream) {
-    return align_moments("sh_align_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, nullptr, idx_ms, d2_ms, tau2,
-                         w_ms, B, partials, partials_bytes, stream);
+    return align_moments<PointSums>("sh_align_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, idx_sm, d2_sm, nullptr,
+                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
 }
 
 int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
@@ -545,8 +512,8 @@ int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t*
                              const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials,
                              size_t partials_bytes, sh_stream_t stream) {
     const AlignSurface sf{faces, nF, uv};
-    return align_moments("sh_align_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, face, d2, &sf, idx_ms, d2_ms, tau2,
-                         w_ms, B, partials, partials_bytes, stream);
+    return align_moments<PointSums>("sh_align_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, face, d2, &sf,
+                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
 }
 
 size_t sh_align_plane_partials_bytes(int B, int M, int n, float w_ms) {
@@ -558,8 +525,8 @@ int sh_align_plane_moments(const float* s, int64_t s_sb, int M, const int32_t* s
                            const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm,
                            const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
                            sh_stream_t stream) {
-    return align_plane_moments("sh_align_plane_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, idx_sm, d2_sm, nullptr, idx_ms,
-                               d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+    return align_moments<PlaneSums>("sh_align_plane_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, idx_sm, d2_sm, nullptr,
+                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
 }
 
 int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
@@ -567,20 +534,15 @@ int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const in
                                    const float* uv, const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
                                    double* partials, size_t partials_bytes, sh_stream_t stream) {
     const AlignSurface sf{faces, nF, uv};
-    return align_plane_moments("sh_align_plane_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, face, d2, &sf, idx_ms,
-                               d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+    return align_moments<PlaneSums>("sh_align_plane_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, face, d2, &sf,
+                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
 }
 
 int sh_align_plane_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,
                          const float* scale_in, float* pose_out, float* scale_out, double* sys, int32_t* solved, sh_stream_t stream) {
-    SH_REQUIRE(partials && (sys || pose_out), SH_ERR_INVALID_ARG, "sh_align_plane_solve: null pointer");
-    SH_REQUIRE(!pose_out || (pose_in && scale_in && scale_out && solved), SH_ERR_INVALID_ARG,
-               "sh_align_plane_solve: pose_out needs pose_in, scale_in, scale_out and solved");
-    SH_REQUIRE(B >= 0 && M >= 0 && n >= 0, SH_ERR_INVALID_ARG, "sh_align_plane_solve: bad size (B %d, M %d, n %d)", B, M, n);
-    SH_REQUIRE(w_ms >= 0.f, SH_ERR_INVALID_ARG, "sh_align_plane_solve: w_ms must be >= 0 (and not NaN)");
-    SH_REQUIRE(mode == SH_ALIGN_TRANSLATION || mode == SH_ALIGN_RIGID || mode == SH_ALIGN_SIMILARITY, SH_ERR_INVALID_ARG,
-               "sh_align_plane_solve: unknown mode %d", mode);
-    if (B == 0) return SH_OK;
+    const int rc = align_solve_check("sh_align_plane_solve", partials, sys, pose_out, pose_in && scale_in && scale_out && solved,
+                                     "pose_in, scale_in, scale_out and solved", M, n, w_ms, mode, B);
+    if (rc != SH_OK || B == 0) return rc;
     const int r_sm = ranges_of(M), r_ms = w_ms > 0.f ? ranges_of(n) : 0;
     const int k = mode == SH_ALIGN_TRANSLATION ? 3 : (mode == SH_ALIGN_RIGID ? 6 : 7);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -593,13 +555,9 @@ int sh_align_plane_solve(const double* partials, int M, int n, const int32_t* s_
 
 int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,
                    const float* scale_in, float* pose_out, float* scale_out, float* inc, double* mom, sh_stream_t stream) {
-    SH_REQUIRE(partials && (mom || pose_out), SH_ERR_INVALID_ARG, "sh_align_solve: null pointer");
-    SH_REQUIRE(!pose_out || (pose_in && scale_in && scale_out), SH_ERR_INVALID_ARG, "sh_align_solve: pose_out needs pose_in, scale_in and scale_out");
-    SH_REQUIRE(B >= 0 && M >= 0 && n >= 0, SH_ERR_INVALID_ARG, "sh_align_solve: bad size (B %d, M %d, n %d)", B, M, n);
-    SH_REQUIRE(w_ms >= 0.f, SH_ERR_INVALID_ARG, "sh_align_solve: w_ms must be >= 0 (and not NaN)");
-    SH_REQUIRE(mode == SH_ALIGN_TRANSLATION || mode == SH_ALIGN_RIGID || mode == SH_ALIGN_SIMILARITY, SH_ERR_INVALID_ARG,
-               "sh_align_solve: unknown mode %d", mode);
-    if (B == 0) return SH_OK;
+    const int rc = align_solve_check("sh_align_solve", partials, mom, pose_out, pose_in && scale_in && scale_out, "pose_in, scale_in and scale_out", M,
+                                     n, w_ms, mode, B);
+    if (rc != SH_OK || B == 0) return rc;
     const int r_sm = ranges_of(M), r_ms = w_ms > 0.f ? ranges_of(n) : 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     ShProfScope ps(st, "align_solve_kernel|B=%d ranges=%d mode=%d", B, r_sm + r_ms, mode);
@@ -608,6 +566,7 @@ int sh_align_solve(const double* partials, int M, int n, const int32_t* s_count,
     SH_CHECK_LAUNCH("align_solve");
     return SH_OK;
 }
+
 
 int sh_transform_points(const float* src, int64_t src_sb, int M, const int32_t* count, const float* pose, int B, float* dst, sh_stream_t stream) {
     SH_REQUIRE(src && pose && dst, SH_ERR_INVALID_ARG, "sh_transform_points: null pointer");

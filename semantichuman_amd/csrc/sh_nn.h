@@ -1,5 +1,5 @@
 // What the scan-fitting sources (scan.hip, align.hip, surface.hip) share: the live-row count of a body, the fp64 wave sum, the
-// squared distance in its one fixed form and the split of a target range into chunks.
+// squared distance and a face's cross product in their one fixed form and the split of a target range into chunks.
 #pragma once
 #include "sh_common.h"
 #include <math.h>
@@ -22,6 +22,19 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 __device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+
+// The cross product (b - a) x (c - a) of a face's corners, the header's expression ("Vertex normals") in its one fixed form: fp32
+// differences from corner a, one fused multiply-add per component and no other contraction, so that every kernel that forms a
+// face's normal (vertex_normals_kernel, face_normals_kernel, align.hip's face_normal) and the numpy transcriptions round alike.
+__device__ __forceinline__ void face_cross(const float* a, const float* b, const float* c, float& cx, float& cy, float& cz) {
+#pragma clang fp contract(off)
+    const float ax = a[0], ay = a[1], az = a[2];
+    const float abx = b[0] - ax, aby = b[1] - ay, abz = b[2] - az;
+    const float acx = c[0] - ax, acy = c[1] - ay, acz = c[2] - az;
+    cx = __builtin_fmaf(aby, acz, -(abz * acy));
+    cy = __builtin_fmaf(abz, acx, -(abx * acz));
+    cz = __builtin_fmaf(abx, acy, -(aby * acx));
 }
 
 // One Jacobi rotation of the symmetric N x N matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.

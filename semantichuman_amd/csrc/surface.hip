@@ -403,12 +403,8 @@ __global__ __launch_bounds__(256) void face_normals_kernel(const float* __restri
     float nx = 0.f, ny = 0.f, nz = 0.f;
     if ((unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n) {
         const float* xb = x + (long)b * x_sb;
-        const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
-        const float abx = xb[3L * i1] - ax, aby = xb[3L * i1 + 1] - ay, abz = xb[3L * i1 + 2] - az;
-        const float acx = xb[3L * i2] - ax, acy = xb[3L * i2 + 1] - ay, acz = xb[3L * i2 + 2] - az;
-        const float cx = __builtin_fmaf(aby, acz, -(abz * acy));
-        const float cy = __builtin_fmaf(abz, acx, -(abx * acz));
-        const float cz = __builtin_fmaf(abx, acy, -(aby * acx));
+        float cx, cy, cz;
+        face_cross(xb + 3L * i0, xb + 3L * i1, xb + 3L * i2, cx, cy, cz);
         const float len2 = __builtin_fmaf(cz, cz, __builtin_fmaf(cy, cy, cx * cx));
         if (len2 > 0.f && len2 < INFINITY) {
             const float len = sqrtf(len2);

@@ -613,35 +613,44 @@ ALIGN_MODES = {"translation": 0, "rigid": 1, "similarity": 2}   # enum sh_align_
 ALIGN_PARTIAL, ALIGN_MOMENTS = 19, 20                           # SH_ALIGN_PARTIAL, SH_ALIGN_MOMENTS
 
 
+def _surface_partner(who, faces, face, uv, d2, B, M):
+    """The scan -> model partner of a surface moments call, checked: the table `faces` (int32 HIP [nF, 3]) and what
+    sh_nearest_surface recorded on it; returns the C arguments that take the place of (idx_sm, d2_sm)."""
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.%s needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)" % who)
+    for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+            raise RuntimeError("semantichuman_amd.%s: %s must be a contiguous %s HIP tensor %s" % (who, what, dtype, list(shape)))
+    return ptr(faces), faces.shape[0], ptr(face), ptr(uv), ptr(d2)
+
+
+def _align_moments(entry, per_range, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out, normals=None, surface=None):
+    """The four moments wrappers: C entry point `entry` -> the ranges' partial sums, fp64 [B, ranges, per_range].  normals: None, or
+    (tn, needed) of a point-to-plane call; surface: None, or (faces, face, uv, d2), the partner instead of (idx_sm, d2_sm)."""
+    who = entry[3:]
+    B, M, s_sb = _points(s, who)
+    _, rows, x_sb = _points(x, who)
+    tn = () if normals is None else (ptr(_plane_normals(normals[0], B, n, who, normals[1])),)
+    partner = (ptr(idx_sm), ptr(d2_sm)) if surface is None else _surface_partner(who, *surface, B, M)
+    lib = _lib.load()
+    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), per_range), dtype=torch.float64, device=s.device)
+    check(getattr(lib, entry)(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, *tn, *partner, ptr(idx_ms), ptr(d2_ms),
+                              tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), entry)
+    return part
+
+
 def align_moments(s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
     """sh_align_moments -> the ranges' partial sums, fp64 [B, ranges, 19] (stage 1; sh_align_solve finishes them)."""
-    B, M, s_sb = _points(s, "align_moments")
-    _, rows, x_sb = _points(x, "align_moments")
-    lib = _lib.load()
-    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PARTIAL), dtype=torch.float64, device=s.device)
-    check(lib.sh_align_moments(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(idx_sm), ptr(d2_sm), ptr(idx_ms),
-                               ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), "sh_align_moments")
-    return part
+    return _align_moments("sh_align_moments", ALIGN_PARTIAL, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out)
 
 
 def align_moments_surface(s, s_count, x, n, v_mask, mask_sb, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
     """sh_align_moments_surface -> the ranges' partial sums, fp64 [B, ranges, 19]: sh_align_moments with the scan -> model partner
     the foot point (face, uv) that sh_nearest_surface recorded on the table `faces` (int32 HIP [nF, 3]); d2 is the surface
     distance."""
-    B, M, s_sb = _points(s, "align_moments_surface")
-    _, rows, x_sb = _points(x, "align_moments_surface")
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
-            and faces.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.align_moments_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
-    for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-            raise RuntimeError("semantichuman_amd.align_moments_surface: %s must be a contiguous %s HIP tensor %s" % (what, dtype, list(shape)))
-    lib = _lib.load()
-    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PARTIAL), dtype=torch.float64, device=s.device)
-    check(lib.sh_align_moments_surface(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(faces), faces.shape[0],
-                                       ptr(face), ptr(uv), ptr(d2), ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8,
-                                       stream_ptr()), "sh_align_moments_surface")
-    return part
+    return _align_moments("sh_align_moments_surface", ALIGN_PARTIAL, s, s_count, x, n, v_mask, mask_sb, None, None, idx_ms, d2_ms, tau2, w_ms, out,
+                          surface=(faces, face, uv, d2))
 
 
 def align_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, inc=None, mom=None):
@@ -669,35 +678,16 @@ def _plane_normals(tn, B, n, what, needed):
 def align_plane_moments(s, s_count, x, n, v_mask, mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
     """sh_align_plane_moments -> the ranges' partial sums of the point-to-plane step, fp64 [B, ranges, 38] (stage 1;
     sh_align_plane_solve finishes them).  tn: the vertex normals, contiguous fp32 [B, n, 3]."""
-    B, M, s_sb = _points(s, "align_plane_moments")
-    _, rows, x_sb = _points(x, "align_plane_moments")
-    tn = _plane_normals(tn, B, n, "align_plane_moments", True)
-    lib = _lib.load()
-    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PLANE_PARTIAL), dtype=torch.float64, device=s.device)
-    check(lib.sh_align_plane_moments(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(tn), ptr(idx_sm), ptr(d2_sm),
-                                     ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), "sh_align_plane_moments")
-    return part
+    return _align_moments("sh_align_plane_moments", ALIGN_PLANE_PARTIAL, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms,
+                          out, normals=(tn, True))
 
 
 def align_plane_moments_surface(s, s_count, x, n, v_mask, mask_sb, tn, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
     """sh_align_plane_moments_surface -> fp64 [B, ranges, 38]: sh_align_plane_moments with the scan -> model partner the foot point
     (face, uv) that sh_nearest_surface recorded on the table `faces` and the normal that face's; tn (the model -> scan pairs'
     normals) may be None when w_ms == 0."""
-    B, M, s_sb = _points(s, "align_plane_moments_surface")
-    _, rows, x_sb = _points(x, "align_plane_moments_surface")
-    tn = _plane_normals(tn, B, n, "align_plane_moments_surface", w_ms > 0)
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
-            and faces.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.align_plane_moments_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
-    for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
-            raise RuntimeError("semantichuman_amd.align_plane_moments_surface: %s must be a contiguous %s HIP tensor %s" % (what, dtype, list(shape)))
-    lib = _lib.load()
-    part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), ALIGN_PLANE_PARTIAL), dtype=torch.float64, device=s.device)
-    check(lib.sh_align_plane_moments_surface(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, ptr(tn), ptr(faces),
-                                             faces.shape[0], ptr(face), ptr(uv), ptr(d2), ptr(idx_ms), ptr(d2_ms), tau2, w_ms, B, ptr(part),
-                                             part.numel() * 8, stream_ptr()), "sh_align_plane_moments_surface")
-    return part
+    return _align_moments("sh_align_plane_moments_surface", ALIGN_PLANE_PARTIAL, s, s_count, x, n, v_mask, mask_sb, None, None, idx_ms, d2_ms, tau2,
+                          w_ms, out, normals=(tn, w_ms > 0), surface=(faces, face, uv, d2))
 
 
 def align_plane_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, sys=None, solved=None):

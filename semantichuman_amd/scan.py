@@ -734,24 +734,17 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     if surface and any(m.get(k) is None for k in ("face", "uv", "d2_surface", "faces")):
         raise ValueError("pose_update: surface=True needs the matches of a surface search (chamfer(..., faces=, matches=) or "
                          "align(..., faces=)); these carry none")
-    if step == "plane":
-        tn = _plane_normals("pose_update", m, surface)
-        if surface:
-            part = ops.align_plane_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], tn, m["faces"], m["face"],
-                                                   m["uv"], m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
-        else:
-            part = ops.align_plane_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], tn, m["idx_sm"], m["d2_sm"],
-                                           m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
-        ops.align_plane_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale,
-                              solved=solved)
+    plane = step == "plane"
+    normals = (_plane_normals("pose_update", m, surface),) if plane else ()
+    partner = (m["faces"], m["face"], m["uv"], m["d2_surface"]) if surface else (m["idx_sm"], m["d2_sm"])
+    moments = ((ops.align_moments, ops.align_moments_surface), (ops.align_plane_moments, ops.align_plane_moments_surface))[plane][bool(surface)]
+    part = moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], *normals, *partner, m["idx_ms"], m["d2_ms"], m["tau2"],
+                   m["w_ms"], out=partials)
+    solve = (aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
+    if plane:
+        ops.align_plane_solve(part, *solve, solved=solved)
     else:
-        if surface:
-            part = ops.align_moments_surface(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["faces"], m["face"], m["uv"],
-                                             m["d2_surface"], m["idx_ms"], m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
-        else:
-            part = ops.align_moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], m["idx_sm"], m["d2_sm"], m["idx_ms"],
-                                     m["d2_ms"], m["tau2"], m["w_ms"], out=partials)
-        ops.align_solve(part, aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
+        ops.align_solve(part, *solve)
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
     if scans.normals is not None and aligned.normals is not None:
         ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)

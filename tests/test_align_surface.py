@@ -116,6 +116,45 @@ def test_a_body_with_every_vertex_masked_keeps_no_pair():
         assert mom[0, 18] == counts[0] + (n if w > 0 else 0) and not np.array_equal(inc[0], IDENTITY)
 
 
+def test_surface_form_at_a_corner_is_the_vertex_form_bit_for_bit():
+    """The two partner forms run one walk.  A foot point with uv = 0 on a face whose corner 0 is the recorded nearest vertex is
+    (double)a + (0 ab + 0 ac) = a exactly, so the surface form must return the vertex form's partial sums and pose, byte for byte."""
+    v, faces = mesh("small_ae.npz")
+    n, B, M = v.shape[0], 2, 300
+    x = scan_ref.model_points(v, B, seed=3)
+    clouds = [S.sample_surface(x[(b + 1) % B, :n], faces, m, seed=50 + b, sigma=0.01) for b, m in enumerate((300, 17))]
+    sb = scan.ScanBatch(clouds, DEV)
+    xd = torch.from_numpy(x).to(DEV)
+    # a copy of the face table in which every vertex is corner 0 of a face of its own: rows rotated, none used twice
+    table, own, used = faces.copy(), np.full(n, -1), np.zeros(len(faces), bool)
+    for i in range(n):
+        k = int(np.nonzero((faces == i).any(1) & ~used)[0][0])
+        table[k], own[i], used[k] = np.roll(faces[k], -int(np.nonzero(faces[k] == i)[0][0])), k, True
+    assert (table[own, 0] == np.arange(n)).all()
+    ft = scan.FaceTable(table, n, DEV)
+    idx, d_v = ops.nearest_points(sb.points, xd, q_count=sb.counts, nt=n)
+    ih = idx.cpu().numpy()
+    assert ((ih[0] >= 0) & (ih[0] < n)).all() and ((ih[1, :17] >= 0) & (ih[1, :17] < n)).all()
+    face = torch.from_numpy(np.where(ih >= 0, own[np.clip(ih, 0, n - 1)], -1).astype(np.int32)).to(DEV)
+    uv = torch.zeros((B, M, 2), device=DEV)
+    tau2 = float(np.float32(np.median(d_v[0].cpu().numpy())))                  # drops half of body 0's pairs
+    vm, vsb = ops._mask_arg(None, B, n, xd.device)
+    for w in (0.0, 0.5):
+        i_ms, d_ms = ops.nearest_points(xd, sb.points, t_count=sb.counts) if w > 0 else (None, None)
+        pv = ops.align_moments(sb.points, sb.counts, xd, n, vm, vsb, idx, d_v, i_ms, d_ms, tau2, w)
+        ps = ops.align_moments_surface(sb.points, sb.counts, xd, n, vm, vsb, ft.faces, face, uv, d_v, i_ms, d_ms, tau2, w)
+        kept = pv[:, 0, 0].cpu().numpy()
+        assert 0 < kept[0] < 300 and kept[1] <= 17, kept
+        assert same(pv, ps), (w, (pv != ps).nonzero().cpu().numpy())
+        poses = []
+        for part in (pv, ps):
+            out, sc = torch.full((B, 12), float("nan"), device=DEV), torch.full((B,), float("nan"), device=DEV)
+            pose = scan.Pose.identity(B, DEV)
+            ops.align_solve(part, M, n, sb.counts, w, "similarity", pose.packed, pose.scale, out, sc)
+            poses.append((out, sc))
+        assert torch.isfinite(poses[0][0]).all() and same(poses[0][0], poses[1][0]) and same(poses[0][1], poses[1][1]), w
+
+
 # ------------------------------------------------------------------------------------------------ 2. solve on surface pairs
 @pytest.mark.parametrize("mode", MODES)
 def test_solve_on_surface_pairs_against_umeyama(mode):
