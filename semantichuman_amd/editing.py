@@ -113,6 +113,12 @@ def save_obj(obj_path, v, f, partcolor_list=None, vert_part_index=None):
 
 
 # ------------------------------------------------------------------------------------------------ fitting
+def _face_table(faces, x_hat):
+    """None, a scan.FaceTable or an integer array [nF, 3] -> None or a FaceTable for the decoded bodies x_hat (their last row is the
+    dummy row), validated and uploaded here."""
+    return faces if faces is None or isinstance(faces, scan.FaceTable) else scan.FaceTable(faces, x_hat.shape[1] - 1, x_hat.device)
+
+
 def _default_dummy(model, z):
     """The decoder's dummy row as demo.py:74 makes it: zeros as wide as the decoder stack's input (its first conv's in_c)."""
     return torch.zeros((z.shape[0], 1, model.dconv[0].in_c), device=z.device)
@@ -231,24 +237,16 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
         raise ValueError("fit_scan: %d bodies, %d scans" % (z.shape[0], len(scans)))
-    scan._check_gate_on("fit_scan", gate_on, normal_angle, faces, scans, trunc)
+    scan._MatchPlan.check_gate("fit_scan", gate_on, normal_angle, faces, scans, trunc)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
-    # one face table at most: a gate reads normal_faces (and scan.chamfer refuses faces= next to it), no gate reads faces alone
-    gated = normal_angle is not None
-    on_surface = gate_on == "surface"
-    state = {"table": normal_faces if gated and not on_surface else faces, "normals": normal_faces if on_surface else None}
+    tables = {}
 
     def objective(x_hat):
-        for k in ("table", "normals"):
-            if state[k] is not None and not isinstance(state[k], scan.FaceTable):            # validated and uploaded once, at the first decode
-                state[k] = scan.FaceTable(state[k], x_hat.shape[1] - 1, x_hat.device)
-        if on_surface:
-            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=state["table"], normal_angle=normal_angle,
-                                normal_faces=state["normals"], gate_on=gate_on)
-        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, faces=faces if gated else state["table"],
-                            normal_angle=normal_angle, normal_faces=state["table"] if gated else None)
+        if not tables:                                                     # validated and uploaded once, at the first decode: n is known here
+            tables.update(faces=_face_table(faces, x_hat), normal_faces=_face_table(normal_faces, x_hat) if normal_angle is not None else None)
+        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, normal_angle=normal_angle, gate_on=gate_on, **tables)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():
@@ -309,40 +307,28 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     on_surface = align_on == "surface"
     if on_surface and faces is None:
         raise ValueError("register_scan: align_on='surface' needs faces (the model's triangles)")
-    scan._check_gate_on("register_scan", gate_on, normal_angle, faces, scans, trunc)
-    gate_surface = gate_on == "surface"
+    surface_gate = scan._MatchPlan.check_gate("register_scan", gate_on, normal_angle, faces, scans, trunc) is not None
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
     w_align = (1.0 if mode == "similarity" else w_model_to_scan) if align_w_model_to_scan is None else align_w_model_to_scan
     with torch.no_grad():
         x0 = _decode(model, z.detach(), z_kps, dummy)
-    if normal_angle is not None:
-        if faces is not None and not gate_surface:
-            raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built for the gate on vertex "
-                             "normals; gate_on='surface' gates the surface search by the face's normal")
-        if normal_faces is not None and not isinstance(normal_faces, scan.FaceTable):
-            normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
-    if (on_surface or align_step == "plane" or gate_surface) and faces is not None and not isinstance(faces, scan.FaceTable):
-        faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
-    if align_step == "plane":                                                           # the table the vertex normals come from
-        if normal_faces is None:
-            normal_faces = faces
-        elif not isinstance(normal_faces, scan.FaceTable):
-            normal_faces = scan.FaceTable(normal_faces, x0.shape[1] - 1, x0.device)
+    if normal_angle is not None and faces is not None and not surface_gate:              # stage 1 on vertex pairs would run before scan.chamfer says so
+        raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built for the gate on vertex "
+                         "normals; gate_on='surface' gates the surface search by the face's normal")
+    normal_faces, faces = _face_table(normal_faces, x0), _face_table(faces, x0)
+    if normal_faces is None:                                                            # the vertex normals' table falls back to the surface's
+        normal_faces = faces
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
-                                  vertex_mask=vertex_mask, normal_angle=normal_angle,
-                                  normal_faces=faces if gate_surface and not on_surface and normal_faces is None else normal_faces,
+                                  vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
                                   faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices")
     matches = {} if align_every > 0 else None
     state = {"partials": None}
-    if faces is not None and not isinstance(faces, scan.FaceTable):
-        faces = scan.FaceTable(faces, x0.shape[1] - 1, x0.device)
 
-    def objective(x_hat):
-        return scan.chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches=matches, faces=faces,
-                            normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on,
-                            _vertex_matches=not (gate_surface and on_surface))
+    def objective(x_hat):                                                               # foot-point pose updates read no vertex record
+        return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
+                             vertex_matches=not on_surface)
 
     def after_step(t):
         if (t + 1) % align_every == 0:

@@ -435,6 +435,14 @@ def _count_arg(cnt, B, device):
     return c
 
 
+def _face_table_arg(faces, who, what="face table"):
+    """The model's triangles as the kernels take them, a contiguous int32 HIP tensor [nF, 3], checked -> nF."""
+    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
+            and faces.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.%s needs a contiguous int32 HIP %s [nF, 3] (scan.FaceTable makes one)" % (who, what))
+    return faces.shape[0]
+
+
 def nearest_points(q, t, q_count=None, t_count=None, t_mask=None, nq=None, nt=None, chunks=0, out=None, gate=None):
     """sh_nearest_points: q [B, *, 3] (the first nq rows are queries), t [B, *, 3] (the first nt rows are targets) ->
     (idx int32 [B, nq], d2 fp32 [B, nq]).  chunks: 0 = the library's split of the target range, k = that many ranges.
@@ -477,12 +485,12 @@ def vertex_normals(x, faces, vf_ptr, vf_idx, n, out=None):
     n = int(n)
     if not 0 <= n <= rows:
         raise ValueError("vertex_normals: n = %d exceeds the model's %d rows" % (n, rows))
-    for t, shape, what in ((faces, (faces.shape[0], 3), "faces [nF, 3]"), (vf_ptr, (n + 1,), "vf_ptr [n + 1]"),
-                           (vf_idx, (3 * faces.shape[0],), "vf_idx [3 nF]")):
+    nF = _face_table_arg(faces, "vertex_normals", "table faces")
+    for t, shape, what in ((vf_ptr, (n + 1,), "vf_ptr [n + 1]"), (vf_idx, (3 * nF,), "vf_idx [3 nF]")):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == shape):
             raise RuntimeError("semantichuman_amd.vertex_normals needs a contiguous int32 HIP table %s (scan.FaceTable makes one)" % what)
     nrm = out if out is not None else torch.empty((B, n, 3), dtype=torch.float32, device=x.device)
-    check(_lib.load().sh_vertex_normals(ptr(x), x_sb, n, ptr(faces), faces.shape[0], ptr(vf_ptr), ptr(vf_idx), B, ptr(nrm), stream_ptr()),
+    check(_lib.load().sh_vertex_normals(ptr(x), x_sb, n, ptr(faces), nF, ptr(vf_ptr), ptr(vf_idx), B, ptr(nrm), stream_ptr()),
           "sh_vertex_normals")
     return nrm
 
@@ -542,10 +550,7 @@ def face_normals(x, faces, n, out=None):
     n = int(n)
     if not 0 <= n <= rows:
         raise ValueError("face_normals: n = %d exceeds the model's %d rows" % (n, rows))
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
-            and faces.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.face_normals needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
-    nF = faces.shape[0]
+    nF = _face_table_arg(faces, "face_normals")
     nrm = out if out is not None else torch.empty((B, nF, 3), dtype=torch.float32, device=x.device)
     check(_lib.load().sh_face_normals(ptr(x), x_sb, n, ptr(faces), nF, B, ptr(nrm), stream_ptr()), "sh_face_normals")
     return nrm
@@ -566,10 +571,7 @@ def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunk
     n = int(n)
     if not 0 <= n <= x_rows:
         raise ValueError("nearest_surface: n = %d exceeds the model's %d rows" % (n, x_rows))
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
-            and faces.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.nearest_surface needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)")
-    nF = faces.shape[0]
+    nF = _face_table_arg(faces, "nearest_surface")
     q_count = _count_arg(q_count, B, q.device)
     mask, mask_sb = _mask_arg(v_mask, B, n, q.device)
     if bound is not None and not (bound.is_cuda and bound.dtype == torch.float32 and bound.is_contiguous() and tuple(bound.shape) == (B, nq)):
@@ -616,13 +618,11 @@ ALIGN_PARTIAL, ALIGN_MOMENTS = 19, 20                           # SH_ALIGN_PARTI
 def _surface_partner(who, faces, face, uv, d2, B, M):
     """The scan -> model partner of a surface moments call, checked: the table `faces` (int32 HIP [nF, 3]) and what
     sh_nearest_surface recorded on it; returns the C arguments that take the place of (idx_sm, d2_sm)."""
-    if not (torch.is_tensor(faces) and faces.is_cuda and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3
-            and faces.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.%s needs a contiguous int32 HIP face table [nF, 3] (scan.FaceTable makes one)" % who)
+    nF = _face_table_arg(faces, who)
     for t, dtype, shape, what in ((face, torch.int32, (B, M), "face"), (d2, torch.float32, (B, M), "d2"), (uv, torch.float32, (B, M, 2), "uv")):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
             raise RuntimeError("semantichuman_amd.%s: %s must be a contiguous %s HIP tensor %s" % (who, what, dtype, list(shape)))
-    return ptr(faces), faces.shape[0], ptr(face), ptr(uv), ptr(d2)
+    return ptr(faces), nF, ptr(face), ptr(uv), ptr(d2)
 
 
 def _align_moments(entry, per_range, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out, normals=None, surface=None):

@@ -313,55 +313,13 @@ def face_normals(x, faces, n=None):
     return ops.face_normals(x, ft.faces, ft.n)
 
 
-def _check_gate_on(what, gate_on, normal_angle, faces, scans, trunc):
-    """The checks of `gate_on` that need no device: ValueError on an unknown value, and for "surface" on whatever it needs and
-    lacks (normal_angle, faces=, scan normals, trunc - each named)."""
-    if gate_on not in ("vertices", "surface"):
-        raise ValueError("%s: gate_on must be 'vertices' or 'surface', got %r" % (what, gate_on))
-    if gate_on != "surface":
-        return
-    if normal_angle is None:
-        raise ValueError("%s: gate_on='surface' needs normal_angle (degrees)" % what)
-    if not 0.0 < float(normal_angle) <= 180.0:
-        raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
-    if faces is None:
-        raise ValueError("%s: gate_on='surface' needs faces= (the model's triangles: the gate is on the face's normal)" % what)
-    if isinstance(scans, ScanBatch) and scans.normals is None:
-        raise ValueError("%s: gate_on='surface' needs scan normals (ScanBatch(..., normals=))" % what)
-    if trunc is None:
-        raise ValueError("%s: gate_on='surface' needs trunc (a point with no compatible face counts as truncated; without trunc "
-                         "the loss would be infinite)" % what)
-
-
-def _normal_gate(what, normal_angle, normal_faces, scans, n, trunc, faces, device, gate_on="vertices"):
-    """Validates the arguments of a normal gate -> None (no gate) or (cos_min, FaceTable the vertex normals come from).  With
-    gate_on="surface" the gate is the face-normal gate of the surface search and `faces` must already be a FaceTable."""
-    _check_gate_on(what, gate_on, normal_angle, faces, scans, trunc)
-    if gate_on == "surface":
-        a = float(normal_angle)
-        ft = faces if normal_faces is None else _face_table(normal_faces, n, device)
-        if ft.n != n or faces.n != n:
-            raise ValueError("%s: the face table was made for %d vertices, the model has %d" % (what, ft.n if ft.n != n else faces.n, n))
-        return (-math.inf if a == 180.0 else math.cos(math.radians(a))), ft
-    if normal_angle is None:
-        return None
+def _cos_min(what, normal_angle):
+    """A gate's angle in degrees, checked -> the bound the kernels hold the fp32 dot product of two normals against; 180 opens the
+    gate (-inf)."""
     a = float(normal_angle)
     if not 0.0 < a <= 180.0:
         raise ValueError("%s: normal_angle must lie in (0, 180] degrees, got %r" % (what, normal_angle))
-    if faces is not None:
-        raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built for the gate on vertex normals; "
-                         "gate_on='surface' gates the surface search by the face's normal" % what)
-    if scans.normals is None:
-        raise ValueError("%s: normal_angle needs scan normals (ScanBatch(..., normals=))" % what)
-    if normal_faces is None:
-        raise ValueError("%s: normal_angle needs the model's triangles (normal_faces=, a FaceTable or an integer array)" % what)
-    if trunc is None:
-        raise ValueError("%s: normal_angle needs trunc (a point with no compatible partner counts as truncated; without trunc "
-                         "the loss would be infinite)" % what)
-    ft = _face_table(normal_faces, n, device)
-    if ft.n != n:
-        raise ValueError("%s: normal_faces was made for %d vertices, the model has %d" % (what, ft.n, n))
-    return (-math.inf if a == 180.0 else math.cos(math.radians(a))), ft
+    return -math.inf if a == 180.0 else math.cos(math.radians(a))
 
 
 def _query_normals(tn, rows):
@@ -391,10 +349,7 @@ def nearest_surface(q, x, faces, q_count=None, vertex_mask=None, chunks=0, cull=
     if (q_normals is None) != (normal_angle is None):
         raise ValueError("nearest_surface: q_normals and normal_angle come together")
     if normal_angle is not None:
-        a = float(normal_angle)
-        if not 0.0 < a <= 180.0:
-            raise ValueError("nearest_surface: normal_angle must lie in (0, 180] degrees, got %r" % (normal_angle,))
-        cos_min = -math.inf if a == 180.0 else math.cos(math.radians(a))
+        cos_min = _cos_min("nearest_surface", normal_angle)
         fn = ops.face_normals(x, ft.faces, ft.n)
         return ops.nearest_surface(q, x, ft.faces, ft.n, q_count, vertex_mask, None, chunks=chunks, cull=cull, gate=(q_normals.detach(), fn, cos_min))
     bound = None
@@ -415,79 +370,171 @@ def closest_points(x, faces, face, uv):
     return torch.where((face >= 0)[:, :, None], p, torch.zeros_like(p))
 
 
-class _ChamferSurface(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, scans, faces, n, v_mask, mask_sb, tau2, w_ms, matches=None, gate=None, vertex_matches=True):
-        s, cnt = scans.points, scans.counts
-        rows = x.shape[1]
-        idx_ms = d2_ms = tn = None
-        if gate is None:
-            idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n)    # the vertex search: the bound, and `matches`
-            face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, d2_v)
-            if w_ms > 0.0:
-                idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt)
-        else:                                                                       # (cos_min, FaceTable): the face-normal gate
-            cos_min, ft = gate
-            xd = x.detach()
-            fn = ops.face_normals(xd, faces, n)                                     # once per forward pass
-            face, d2_sm, uv = ops.nearest_surface(s, x, faces, n, cnt, v_mask, None, gate=(scans.normals, fn, cos_min))
-            idx_sm = d2_v = None
-            record = matches is not None and vertex_matches
-            if w_ms > 0.0 or record:
-                tn = ops.vertex_normals(xd, ft.faces, ft.vf_ptr, ft.vf_idx, n)
-            if w_ms > 0.0:                                                          # vertex to scan point, gated by vertex normals
-                idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt, gate=(_query_normals(tn, rows), scans.normals, cos_min))
-            if record:                                                              # the gated VERTEX matches, for `pose_update`
-                idx_sm, d2_v = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, gate=(scans.normals, tn, cos_min))
-        loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
-        ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
-        ctx.save_for_backward(x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts)
-        if matches is not None:
-            matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_v, idx_ms=idx_ms,
-                           d2_ms=d2_ms, face=face, uv=uv, d2_surface=d2_sm, faces=faces, tn=tn)
-        return loss
+VERTEX, VERTEX_GATED, SURFACE, SURFACE_GATED = "vertex", "vertex, gated", "surface", "surface, gated"
+
+
+class _MatchPlan:
+    """What one call of `chamfer` or `align` matches, resolved once from its arguments - every check of them included, in the order
+    the docstrings promise - and the one routine, `search`, that runs the searches of a forward pass or an ICP iteration.
+
+    n, rows, v_mask, mask_sb, tau2, w: the arguments as the kernels take them; `scans` the ScanBatch.  cos_min: the gate's bound, or
+    None without a gate.  surface: the FaceTable of the surface distance, or None.  normals: the FaceTable the vertex normals come
+    from (a gate's, or with step="plane" the table the step's normals need), or None.  recorded: the table `matches` receives as
+    `normal_faces` - `normals`, else `surface`, else with record=True a given normal_faces - or None.  kind: the scan -> model
+    partner, one of VERTEX, VERTEX_GATED, SURFACE (bounded by the vertex search), SURFACE_GATED (the face-normal gate).  An
+    array becomes a FaceTable here, once; a FaceTable is used as it is.  pair: what `_check_pair` returned; `chamfer`
+    takes no pose step and leaves `step` alone."""
+
+    def __init__(self, what, x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step="point", record=False):
+        self.scans, B, self.rows, self.n = pair
+        self.w = float(w_model_to_scan)
+        if not self.w >= 0.0:
+            raise ValueError("%s: w_model_to_scan must be >= 0" % what)
+        if trunc is not None and not float(trunc) > 0.0:
+            raise ValueError("%s: trunc must be > 0" % what)
+        self.tau2 = math.inf if trunc is None else float(trunc) ** 2
+        self.v_mask, self.mask_sb = ops._mask_arg(vertex_mask, B, self.n, x.device)
+
+        def table(f):
+            return _face_table(f, self.n, x.device)
+
+        def same_n(ft, name="the face table"):
+            if ft.n != self.n:
+                raise ValueError("%s: %s was made for %d vertices, the model has %d" % (what, name, ft.n, self.n))
+
+        self.surface = table(faces) if gate_on == "surface" and faces is not None else None
+        self.cos_min = self.check_gate(what, gate_on, normal_angle, faces, self.scans, trunc)
+        self.normals = None
+        if self.cos_min is not None:                                                # the face-normal gate of the surface search
+            self.normals = self.surface if normal_faces is None else table(normal_faces)
+            same_n(self.normals)
+            same_n(self.surface)
+        elif normal_angle is not None:                                              # the gate on vertex normals
+            self.cos_min = _cos_min(what, normal_angle)
+            if faces is not None:
+                raise ValueError("%s: normal_angle together with faces= (the surface distance) is not built for the gate on vertex normals; "
+                                 "gate_on='surface' gates the surface search by the face's normal" % what)
+            if self.scans.normals is None:
+                raise ValueError("%s: normal_angle needs scan normals (ScanBatch(..., normals=))" % what)
+            if normal_faces is None:
+                raise ValueError("%s: normal_angle needs the model's triangles (normal_faces=, a FaceTable or an integer array)" % what)
+            if trunc is None:
+                raise ValueError("%s: normal_angle needs trunc (a point with no compatible partner counts as truncated; without trunc "
+                                 "the loss would be infinite)" % what)
+            self.normals = table(normal_faces)
+            same_n(self.normals, "normal_faces")
+        elif faces is not None:
+            self.surface = table(faces)
+        if step not in ("point", "plane"):
+            raise ValueError("%s: step must be 'point' or 'plane'" % what)
+        if step == "plane" and self.normals is None and (self.surface is None or self.w > 0.0):   # vertex normals are read, no gate brought a table
+            if self.surface is None and normal_faces is None:
+                raise ValueError("%s: step='plane' on vertex pairs needs the model's triangles (normal_faces=, a FaceTable or an integer array)" % what)
+            self.normals = self.surface if self.surface is not None else table(normal_faces)
+            same_n(self.normals)
+        self.recorded = self.normals if self.normals is not None else self.surface
+        if self.recorded is None and record and normal_faces is not None:
+            self.recorded = table(normal_faces)
+        self.kind = ((VERTEX, VERTEX_GATED), (SURFACE, SURFACE_GATED))[self.surface is not None][self.cos_min is not None]
 
     @staticmethod
-    def backward(ctx, gL):
-        x, faces, face, d2_sm, uv, idx_ms, d2_ms, counts = ctx.saved_tensors
-        g = ops.chamfer_surface_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, faces, face, d2_sm, uv, idx_ms, d2_ms, ctx.v_mask,
-                                    ctx.mask_sb, counts, ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None, None, None, None, None, None
+    def check_gate(what, gate_on, normal_angle, faces, scans, trunc):
+        """The checks of `gate_on` that need no device: ValueError on an unknown value, and for "surface" on whatever it needs and
+        lacks (normal_angle, faces=, scan normals, trunc - each named).  -> the face-normal gate's cos_min, None for "vertices"."""
+        if gate_on not in ("vertices", "surface"):
+            raise ValueError("%s: gate_on must be 'vertices' or 'surface', got %r" % (what, gate_on))
+        if gate_on != "surface":
+            return None
+        if normal_angle is None:
+            raise ValueError("%s: gate_on='surface' needs normal_angle (degrees)" % what)
+        cos_min = _cos_min(what, normal_angle)
+        if faces is None:
+            raise ValueError("%s: gate_on='surface' needs faces= (the model's triangles: the gate is on the face's normal)" % what)
+        if isinstance(scans, ScanBatch) and scans.normals is None:
+            raise ValueError("%s: gate_on='surface' needs scan normals (ScanBatch(..., normals=))" % what)
+        if trunc is None:
+            raise ValueError("%s: gate_on='surface' needs trunc (a point with no compatible face counts as truncated; without trunc "
+                             "the loss would be infinite)" % what)
+        return cos_min
+
+    def search(self, x, scans, normals=(None, None, None), out=(None, None, None), chunks=0, cull=True, vertex_matches=True):
+        """The searches of one forward pass or ICP iteration between the model points x and `scans` (the plan's, or those under a
+        pose) -> the `matches` dict.  By kind, in launch order:
+
+            VERTEX          nearest_points(s, x)                                                  |  w > 0: nearest_points(x, s)
+            VERTEX_GATED    vertex_normals, the same under the gate (scan normals, tn, cos_min)    |  under (tn padded to rows, scan normals, cos_min)
+            SURFACE         the vertex search, nearest_surface(bound = its d2; None with cull=False) |  ungated
+            SURFACE_GATED   face_normals, nearest_surface(gate=, bound=None), vertex_normals if     |  gated as above; then, with vertex_matches,
+                            w > 0 or vertex_matches                                                |  the gated vertex search, last
+
+        normals: (tn, qn, fn) - vertex normals, their padded form and face normals - where the caller has them already (x fixed);
+        what is None is computed here when it is read.  out: ((idx, d2) scan -> model, (face, d2, uv), (idx, d2) model -> scan)
+        buffers to fill; None allocates.  vertex_matches: whether a SURFACE_GATED pass records vertex matches at all."""
+        s, cnt, n, w, v_mask, cos_min, surf = scans.points, scans.counts, self.n, self.w, self.v_mask, self.cos_min, self.surface
+        tn, qn, fn = normals
+        sm, sf, ms = out
+        idx_sm = d2_sm = idx_ms = d2_ms = None
+
+        def model_normals():
+            nonlocal tn, qn
+            if tn is None:
+                tn = ops.vertex_normals(x.detach(), self.normals.faces, self.normals.vf_ptr, self.normals.vf_idx, n)
+            if qn is None and w > 0.0:
+                qn = _query_normals(tn, self.rows)
+
+        if self.kind == SURFACE_GATED:
+            if fn is None:
+                fn = ops.face_normals(x.detach(), surf.faces, n)
+            found = ops.nearest_surface(s, x, surf.faces, n, cnt, v_mask, None, chunks=chunks, cull=cull, out=sf, gate=(scans.normals, fn, cos_min))
+            if w > 0.0 or vertex_matches:
+                model_normals()
+        else:
+            if self.kind == VERTEX_GATED:
+                model_normals()
+            idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm,
+                                               gate=None if cos_min is None else (scans.normals, tn, cos_min))
+            if surf is not None:                                                    # the vertex distance bounds the surface search
+                found = ops.nearest_surface(s, x, surf.faces, n, cnt, v_mask, d2_sm if cull else None, chunks=chunks, cull=cull, out=sf)
+        if w > 0.0:                                                                 # all rows are queries: [B, rows] as the kernels index it
+            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt, chunks=chunks, out=ms, gate=None if cos_min is None else (qn, scans.normals, cos_min))
+        if self.kind == SURFACE_GATED and vertex_matches:                           # the gated VERTEX matches, for `pose_update`
+            idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=(scans.normals, tn, cos_min))
+        m = dict(x=x.detach(), n=n, v_mask=v_mask, mask_sb=self.mask_sb, tau2=self.tau2, w_ms=w, idx_sm=idx_sm, d2_sm=d2_sm, idx_ms=idx_ms,
+                 d2_ms=d2_ms, tn=tn, normal_faces=self.recorded)
+        if surf is not None:
+            m.update(face=found[0], d2_surface=found[1], uv=found[2], faces=surf.faces)
+        return m
+
+    def loss(self, m, scans, out=None):
+        """sh_chamfer_fwd on what `search` found -> (loss [B], counts)."""
+        return ops.chamfer_fwd(m["d2_sm"] if self.surface is None else m["d2_surface"], scans.counts, m["d2_ms"], self.rows, self.n, self.v_mask,
+                               self.mask_sb, self.tau2, self.w, out=out)
 
 
 class _Chamfer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, scans, n, v_mask, mask_sb, tau2, w_ms, matches=None, gate=None):
-        s, cnt = scans.points, scans.counts
-        rows = x.shape[1]
-        g_sm = g_ms = tn = None
-        if gate is not None:                                                        # (cos_min, FaceTable): both directions gated
-            cos_min, ft = gate
-            tn = ops.vertex_normals(x.detach(), ft.faces, ft.vf_ptr, ft.vf_idx, n)  # once per forward pass
-            g_sm = (scans.normals, tn, cos_min)
-            g_ms = (_query_normals(tn, rows), scans.normals, cos_min) if w_ms > 0.0 else None
-        idx_sm, d2_sm = ops.nearest_points(s, x, q_count=cnt, t_mask=v_mask, nt=n, gate=g_sm)
-        idx_ms = d2_ms = None
-        if w_ms > 0.0:
-            idx_ms, d2_ms = ops.nearest_points(x, s, t_count=cnt, gate=g_ms)        # all rows are queries: [B, rows] as the kernels index it
-        loss, counts = ops.chamfer_fwd(d2_sm, cnt, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms)
-        ctx.scans, ctx.n, ctx.v_mask, ctx.mask_sb, ctx.tau2, ctx.w_ms = scans, n, v_mask, mask_sb, tau2, w_ms
-        ctx.save_for_backward(x, idx_sm, d2_sm, idx_ms, d2_ms, counts)
+    def forward(ctx, x, plan, matches, vertex_matches):
+        m = plan.search(x, plan.scans, vertex_matches=vertex_matches and matches is not None)
+        loss, counts = plan.loss(m, plan.scans)
+        ctx.plan = plan
+        partner = (m["idx_sm"], m["d2_sm"]) if plan.surface is None else (m["faces"], m["face"], m["d2_surface"], m["uv"])
+        ctx.save_for_backward(x, counts, m["idx_ms"], m["d2_ms"], *partner)
         if matches is not None:
-            matches.update(x=x.detach(), n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w_ms, idx_sm=idx_sm, d2_sm=d2_sm, idx_ms=idx_ms,
-                           d2_ms=d2_ms, tn=tn)
+            matches.update(m)
         return loss
 
     @staticmethod
     def backward(ctx, gL):
-        x, idx_sm, d2_sm, idx_ms, d2_ms, counts = ctx.saved_tensors
-        g = ops.chamfer_bwd(x, ctx.n, ctx.scans.points, ctx.scans.counts, idx_sm, d2_sm, idx_ms, d2_ms, ctx.v_mask, ctx.mask_sb, counts,
-                            ctx.tau2, ctx.w_ms, gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None, None, None, None
+        x, counts, idx_ms, d2_ms, *partner = ctx.saved_tensors
+        p = ctx.plan
+        bwd = ops.chamfer_bwd if p.surface is None else ops.chamfer_surface_bwd
+        g = bwd(x, p.n, p.scans.points, p.scans.counts, *partner, idx_ms, d2_ms, p.v_mask, p.mask_sb, counts, p.tau2, p.w,
+                gL.to(torch.float32).contiguous())
+        return g, None, None, None
 
 
 def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None, normal_angle=None,
-            normal_faces=None, gate_on="vertices", _vertex_matches=True):
+            normal_faces=None, gate_on="vertices"):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -529,25 +576,15 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     `matches` keeps its keys: `face`, `uv`, `d2_surface` are the gated surface results, `idx_sm` / `d2_sm` the gated VERTEX
     matches (one more gated vertex search, run only when `matches` is given), `tn` the vertex normals when they were computed.
     180 degrees gives the ungated `faces=` loss and gradient, bit for bit."""
-    scans, B, rows, n = _check_pair(x_hat, scans, n, "chamfer")
-    w, tau2 = _check_weights(w_model_to_scan, trunc, "chamfer")
-    v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
-    on_surface = gate_on == "surface"
-    if on_surface and faces is not None:
-        faces = _face_table(faces, n, x_hat.device)
-    gate = _normal_gate("chamfer", normal_angle, normal_faces, scans, n, trunc, faces, x_hat.device, gate_on)
-    if on_surface:
-        ft = gate[1]
-        loss = _ChamferSurface.apply(x_hat, scans, faces.faces, n, v_mask, mask_sb, tau2, w, matches, gate, _vertex_matches)
-    elif faces is not None:
-        ft = _face_table(faces, n, x_hat.device)
-        loss = _ChamferSurface.apply(x_hat, scans, ft.faces, n, v_mask, mask_sb, tau2, w, matches)
-    else:
-        ft = gate[1] if gate is not None else (None if normal_faces is None or matches is None else _face_table(normal_faces, n, x_hat.device))
-        loss = _Chamfer.apply(x_hat, scans, n, v_mask, mask_sb, tau2, w, matches, gate)
-    if matches is not None:
-        matches.update(normal_faces=ft)
-    return loss
+    return _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on)
+
+
+def _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on, vertex_matches=True):
+    """`chamfer`, and what editing.register_scan may add: vertex_matches=False when the pose update will read the foot points, so
+    that a face-normal-gated pass skips the vertex search it would run for `matches` alone."""
+    plan = _MatchPlan("chamfer", x_hat, _check_pair(x_hat, scans, n, "chamfer"), vertex_mask, trunc, w_model_to_scan, faces, normal_angle,
+                      normal_faces, gate_on, record=matches is not None)
+    return _Chamfer.apply(x_hat, plan, matches, vertex_matches)
 
 
 # ------------------------------------------------------------------------------------------------ alignment
@@ -655,16 +692,6 @@ def _check_pair(x, scans, n, what):
     if not 0 < n <= rows:
         raise ValueError("%s: n = %d outside (0, %d]" % (what, n, rows))
     return scans, B, rows, n
-
-
-def _check_weights(w_model_to_scan, trunc, what):
-    """w_model_to_scan / trunc as `chamfer` and `align` take them -> (w, tau2)."""
-    w = float(w_model_to_scan)
-    if not w >= 0.0:
-        raise ValueError("%s: w_model_to_scan must be >= 0" % what)
-    if trunc is not None and not float(trunc) > 0.0:
-        raise ValueError("%s: trunc must be > 0" % what)
-    return w, (math.inf if trunc is None else float(trunc) ** 2)
 
 
 def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
@@ -797,77 +824,50 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     neither is given.  The step is Gauss-Newton, without damping or line search: the logged value is not guaranteed to fall.  The
     returned pose carries `solved`, int32 [iters, B]: 0 where a body's system was singular to working precision (no kept pair, too
     few, planar or parallel normals) - that iteration left that body's pose exactly as it was."""
-    scans, B, rows, n = _check_pair(x, scans, n, "align")
+    pair = _check_pair(x, scans, n, "align")
     if mode not in ops.ALIGN_MODES:
         raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
     iters = int(iters)
     if iters < 0:
         raise ValueError("align: iters must be >= 0")
-    w, tau2 = _check_weights(w_model_to_scan, trunc, "align")
-    v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x.device)
     x = x.detach()
-    if gate_on == "surface" and faces is not None:
-        faces = _face_table(faces, n, x.device)
-    gate = _normal_gate("align", normal_angle, normal_faces, scans, n, trunc, faces, x.device, gate_on)
-    surf_gate = gate is not None and gate_on == "surface"
-    ft = None if faces is None else _face_table(faces, n, x.device)                     # x is fixed: once
-    if step not in ("point", "plane"):
-        raise ValueError("align: step must be 'point' or 'plane'")
-    nt = gate[1] if gate is not None else None                                          # the table the vertex normals come from
-    if step == "plane" and nt is None and (ft is None or w > 0.0):
-        if ft is None and normal_faces is None:
-            raise ValueError("align: step='plane' on vertex pairs needs the model's triangles (normal_faces=, a FaceTable or an integer array)")
-        nt = ft if ft is not None else _face_table(normal_faces, n, x.device)
-        if nt.n != n:
-            raise ValueError("align: the face table was made for %d vertices, the model has %d" % (nt.n, n))
+    plan = _MatchPlan("align", x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step)
+    scans, B, rows, n = pair
+    w, dev = plan.w, x.device
     if isinstance(init, Pose):
         if len(init) != B:
             raise ValueError("align: %d bodies, start pose for %d" % (B, len(init)))
-        pose = Pose.from_packed(init.packed.to(x.device).contiguous().clone(), init.scale.to(x.device).contiguous().clone())
+        pose = Pose.from_packed(init.packed.to(dev).contiguous().clone(), init.scale.to(dev).contiguous().clone())
     elif init == "moments":
         pose = moment_pose(scans, x, n, vertex_mask, scale=(mode == "similarity"))
     elif init == "identity":
-        pose = Pose.identity(B, x.device)
+        pose = Pose.identity(B, dev)
     else:
         raise ValueError("align: init must be 'moments', 'identity' or a Pose")
     aligned = pose.apply(scans)
-    log = torch.empty((iters, B), dtype=torch.float32, device=x.device)
-    cnt = scans.counts
+    log = torch.empty((iters, B), dtype=torch.float32, device=dev)
     M = scans.points.shape[1]
-    sm = (None, None) if surf_gate else \
-        (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device))   # gated surface: no vertex search on the scan -> model side
-    ms = (torch.empty((B, rows), dtype=torch.int32, device=x.device), torch.empty((B, rows), dtype=torch.float32, device=x.device)) if w > 0.0 \
-        else (None, None)
-    counts = torch.empty((B, 2), dtype=torch.int32, device=x.device)
-    matches = dict(x=x, n=n, v_mask=v_mask, mask_sb=mask_sb, tau2=tau2, w_ms=w, idx_sm=sm[0], d2_sm=sm[1], idx_ms=ms[0], d2_ms=ms[1])
-    if ft is not None:
-        sf = (torch.empty((B, M), dtype=torch.int32, device=x.device), torch.empty((B, M), dtype=torch.float32, device=x.device),
-              torch.empty((B, M, 2), dtype=torch.float32, device=x.device))
-        matches.update(face=sf[0], d2_surface=sf[1], uv=sf[2], faces=ft.faces)
+
+    def pair_buffers(width):
+        return torch.empty((B, width), dtype=torch.int32, device=dev), torch.empty((B, width), dtype=torch.float32, device=dev)
+
+    sm = None if plan.kind == SURFACE_GATED else pair_buffers(M)                        # gated surface: no vertex search on the scan -> model side
+    ms = pair_buffers(rows) if w > 0.0 else None
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    sf = None if plan.surface is None else (*pair_buffers(M), torch.empty((B, M, 2), dtype=torch.float32, device=dev))
     part = None
-    tn = qn = fn = None
-    if nt is not None and iters > 0 and not (surf_gate and w == 0.0):
-        tn = ops.vertex_normals(x, nt.faces, nt.vf_ptr, nt.vf_idx, n)                   # x is fixed: once
-        qn = _query_normals(tn, rows) if gate is not None and w > 0.0 else None
-    if surf_gate and iters > 0:
-        fn = ops.face_normals(x, ft.faces, n)                                           # x is fixed: once
+    tn = qn = fn = None                                                                 # x is fixed: the model's normals once
+    if plan.normals is not None and iters > 0 and not (plan.kind == SURFACE_GATED and w == 0.0):
+        tn = ops.vertex_normals(x, plan.normals.faces, plan.normals.vf_ptr, plan.normals.vf_idx, n)
+        qn = _query_normals(tn, rows) if plan.cos_min is not None and w > 0.0 else None
+    if plan.kind == SURFACE_GATED and iters > 0:
+        fn = ops.face_normals(x, plan.surface.faces, n)
     solved = None
     if step == "plane":
-        matches.update(tn=tn)
-        solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=x.device)
+        solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=dev)
     for k in range(iters):
-        g_sm = None if gate is None or surf_gate else (aligned.normals, tn, gate[0])
-        g_ms = None if gate is None else (qn, aligned.normals, gate[0])
-        if surf_gate:
-            ops.nearest_surface(aligned.points, x, ft.faces, n, cnt, v_mask, None, chunks=chunks, cull=cull, out=sf,
-                                gate=(aligned.normals, fn, gate[0]))
-        else:
-            ops.nearest_points(aligned.points, x, q_count=cnt, t_mask=v_mask, nt=n, chunks=chunks, out=sm, gate=g_sm)
-        if ft is not None and not surf_gate:
-            ops.nearest_surface(aligned.points, x, ft.faces, n, cnt, v_mask, sm[1] if cull else None, chunks=chunks, cull=cull, out=sf)
-        if w > 0.0:
-            ops.nearest_points(x, aligned.points, t_count=cnt, chunks=chunks, out=ms, gate=g_ms)
-        ops.chamfer_fwd(sm[1] if ft is None else sf[1], cnt, ms[1], rows, n, v_mask, mask_sb, tau2, w, out=(log[k], counts))
-        part = pose_update(pose, scans, aligned, matches, mode, partials=part, surface=ft is not None, step=step,
+        m = plan.search(x, aligned, (tn, qn, fn), (sm, sf, ms), chunks, cull, vertex_matches=False)
+        plan.loss(m, scans, out=(log[k], counts))
+        part = pose_update(pose, scans, aligned, m, mode, partials=part, surface=plan.surface is not None, step=step,
                            solved=None if solved is None else solved[k])
     return pose, aligned, log

@@ -14,6 +14,7 @@ from semantichuman_amd import editing, ops, scan, synthetic
 from semantichuman_amd.hierarchy import load_hierarchy
 from tests import align_ref as A
 from tests import scan_ref as R
+from tests.launch_record import launch_counts as launches
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -432,14 +433,6 @@ def test_register_scan_step_runs_the_new_kernels_no_extra_search_and_leaves_fit_
     m, z0, z_kps, dummy, clouds, _, _ = semantic_setup()
     unmoved, moved = scan.ScanBatch(clouds, DEV), scan.ScanBatch(move_clouds(clouds), DEV)
     kw = dict(parts=PARTS, steps=5, lr=1e-2, w_model_to_scan=0.5, dummy=dummy)
-
-    def launches(fn):
-        _lib.profile_enable(True)
-        out = fn()
-        torch.cuda.synchronize()
-        rec = [k for k, _, _ in _lib.profile_records_by_kernel()]
-        _lib.profile_enable(False)
-        return out, {k: rec.count(k) for k in set(rec)}
 
     a, n_fit = launches(lambda: editing.fit_scan(m, z0, z_kps, unmoved, **kw))
     r, n_reg = launches(lambda: editing.register_scan(m, z0, z_kps, moved, align_iters=0, align_every=1, **kw))

@@ -13,6 +13,7 @@ from tests import align_ref as A
 from tests import align_surface_ref as AS
 from tests import scan_ref
 from tests import surface_ref as S
+from tests.launch_record import launch_counts as launches
 from tests.test_align import MODES, MOVES, PARTS, check_rotation, ragged_counts, semantic_setup
 
 pytestmark = pytest.mark.gpu
@@ -308,15 +309,6 @@ def register_setup():
         clouds.append(A.apply(*A.inverse(At, tt), pts).astype(np.float32))
         truth.append((pts, At))
     return m, z0, z_kps, dummy, clouds, truth, x_star, n, faces, scan.FaceTable(faces, n, DEV)
-
-
-def launches(fn):
-    _lib.profile_enable(True)
-    out = fn()
-    torch.cuda.synchronize()
-    rec = [k for k, _, _ in _lib.profile_records_by_kernel()]
-    _lib.profile_enable(False)
-    return out, {k: rec.count(k) for k in set(rec)}
 
 
 def test_register_scan_on_the_surface():

@@ -13,6 +13,7 @@ from semantichuman_amd import _lib, editing, ops, scan
 from semantichuman_amd.hierarchy import load_hierarchy
 from tests import normals_ref as N
 from tests import scan_ref
+from tests.launch_record import recorded
 from tests.test_scan import PARTS, semantic_setup
 
 pytestmark = pytest.mark.gpu
@@ -31,18 +32,6 @@ def same(a, b):
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def recorded(fn):
-    """fn() with the dispatch record on -> (its result, the set of kernel names it launched)."""
-    _lib.profile_enable(True)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-        names = {k for k, _, _ in _lib.profile_records_by_kernel()}
-    finally:
-        _lib.profile_enable(False)
-    return out, names
 
 
 # ------------------------------------------------------------------------------------------------ G1

@@ -13,6 +13,7 @@ from semantichuman_amd import _lib, editing, ops, scan
 from semantichuman_amd.hierarchy import load_hierarchy
 from tests import surface_gated_ref as G
 from tests import surface_ref as R
+from tests.launch_record import recorded
 from tests.normals_ref import angle, bodies
 from tests.test_scan import PARTS, semantic_setup
 
@@ -33,18 +34,6 @@ def same(a, b):
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def recorded(fn):
-    """fn() with the dispatch record on -> (its result, the set of kernel names it launched)."""
-    _lib.profile_enable(True)
-    try:
-        out = fn()
-        torch.cuda.synchronize()
-        names = {k for k, _, _ in _lib.profile_records_by_kernel()}
-    finally:
-        _lib.profile_enable(False)
-    return out, names
 
 
 def batch_of(case, order=None, scale=None, flip=True):

@@ -187,5 +187,5 @@ def test_gate_on_errors_that_need_no_device():
                        (dict(gate_on="surface", normal_angle=60, trunc=0.1), "faces="),
                        (dict(gate_on="surface", normal_angle=60, faces=faces), "trunc")):
         with pytest.raises(ValueError, match=match):
-            scan._check_gate_on("chamfer", bad.get("gate_on"), bad.get("normal_angle"), bad.get("faces"), with_n, bad.get("trunc"))
-    scan._check_gate_on("chamfer", "vertices", None, None, bare, None)     # the default asks for nothing
+            scan._MatchPlan.check_gate("chamfer", bad.get("gate_on"), bad.get("normal_angle"), bad.get("faces"), with_n, bad.get("trunc"))
+    scan._MatchPlan.check_gate("chamfer", "vertices", None, None, bare, None)     # the default asks for nothing
