@@ -128,8 +128,8 @@ __global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict
             if (!(d2_sm[(long)b * M + j] < tau2)) continue;
             if constexpr (SURFACE) {
                 if ((unsigned)i >= (unsigned)sf.nF) continue;
-                const int i0 = sf.faces[3L * i], i1 = sf.faces[3L * i + 1], i2 = sf.faces[3L * i + 2];
-                if ((unsigned)i0 >= (unsigned)n || (unsigned)i1 >= (unsigned)n || (unsigned)i2 >= (unsigned)n) continue;
+                int i0, i1, i2;
+                if (!face_corners(sf.faces, i, n, i0, i1, i2)) continue;
                 const float v = sf.uv[2 * ((long)b * M + j)], w = sf.uv[2 * ((long)b * M + j) + 1];
                 const float *ca = xb + 3L * i0, *cb = xb + 3L * i1, *cc = xb + 3L * i2;
                 double n0, n1, n2;                                       // the face's, only where Sums takes a normal

@@ -1,5 +1,5 @@
 // What the scan-fitting sources (scan.hip, align.hip, surface.hip) share: the live-row count of a body, the fp64 wave sum, the
-// squared distance and a face's cross product in their one fixed form and the split of a target range into chunks.
+// squared distance and a face's cross product in their one fixed form, the check of a face's corners and the split of a target range into chunks.
 #pragma once
 #include "sh_common.h"
 #include <math.h>
@@ -35,6 +35,13 @@ __device__ __forceinline__ void face_cross(const float* a, const float* b, const
     cx = __builtin_fmaf(aby, acz, -(abz * acy));
     cy = __builtin_fmaf(abz, acx, -(abx * acz));
     cz = __builtin_fmaf(abx, acy, -(aby * acx));
+}
+
+// The three corners of face f (f inside the table); true when each is a vertex, i.e. lies in [0, n).  Every kernel that turns a
+// face into rows of the model passes over a face that fails this.
+__device__ __forceinline__ bool face_corners(const int32_t* __restrict__ faces, int f, int n, int& i0, int& i1, int& i2) {
+    i0 = faces[3L * f]; i1 = faces[3L * f + 1]; i2 = faces[3L * f + 2];
+    return (unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n;
 }
 
 // One Jacobi rotation of the symmetric N x N matrix `a` in the plane (P, Q), accumulated into the eigenvector matrix `v`.

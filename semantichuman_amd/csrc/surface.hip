@@ -1,11 +1,12 @@
-// Point-to-surface distance for scan fitting: the exact closest point of a triangle mesh to every scan point, and the gradient
-// of the Chamfer term built on it (include/sh_kernels.h, "Nearest surface points").  The reference has no counterpart.  The
+// Point-to-surface distance for scan fitting: the exact closest point of a triangle mesh to every scan point
+// (include/sh_kernels.h, "Nearest surface points"; the gradient of the Chamfer term built on it is scan.hip's
+// surface_bwd_kernel, beside the vertex form it follows).  The reference has no counterpart.  The
 // sweep follows nearest_search_kernel of scan.hip: queries in registers, one record per triangle streamed through LDS, every
 // lane reading the same LDS address (broadcast).  What is streamed is the triangle's bounding sphere; the region test of the
 // header runs for a triangle only when the wave's ballot says that some lane cannot rule it out.  The cull only ever skips a
 // triangle whose fp32 distance is provably larger than the query's best so far, so the result equals the unculled sweep's bit
 // for bit; the unculled sweep is kept (cull = 0) as its yardstick.  No atomics of any kind in the kernels a fit runs (the
-// only atomics are two counters of the diagnostic instantiation the benchmark asks for with `stats`): (d2, face) is kept under the lexicographic minimum, the gradient sums run in a fixed order.
+// only atomics are two counters of the diagnostic instantiation the benchmark asks for with `stats`): (d2, face) is kept under the lexicographic minimum.
 #include "sh_nn.h"
 
 namespace {
@@ -26,7 +27,7 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
 struct Foot { float v, w, d2; };
 
 // The header's expression, in its one fixed form: no contraction beyond the fused multiply-adds written out, so that every
-// kernel that inlines it (sweep, finish, gradient) and the numpy transcription of tests/surface_ref.py round alike.
+// kernel that inlines it (sweep, finish) and the numpy transcription of tests/surface_ref.py round alike.
 __device__ __forceinline__ Foot surf_foot(const float* __restrict__ T, float sx, float sy, float sz) {
 #pragma clang fp contract(off)
     const float ax = T[0], ay = T[1], az = T[2], abx = T[3], aby = T[4], abz = T[5], acx = T[6], acy = T[7], acz = T[8];
@@ -297,98 +298,6 @@ __global__ __launch_bounds__(256) void surface_finish_kernel(const SurfParams p,
     face[t] = bi; d2[t] = best; uv[2 * t] = v; uv[2 * t + 1] = w;
 }
 
-// Gradient w.r.t. the model points, gather form, the discipline of chamfer_bwd_kernel.  grid (row tile of 256, body), thread =
-// one row i.  The recorded faces are swept in tiles of 256 scan points: thread t looks at entry j = base + t and keeps the
-// corners of its face that lie in this workgroup's row range; the kept (row, weight, q - s) entries are compacted into LDS in
-// ascending j and corner order 0, 1, 2 within a j (wave ballots, waves in order), and every thread then walks that short list
-// and adds the terms whose row is its own - the order the header states, whatever the scheduling.
-__global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restrict__ x, long x_sb, int rows, int n,
-                                                         const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
-                                                         const int32_t* __restrict__ faces, int nF, const int32_t* __restrict__ face,
-                                                         const float* __restrict__ d2, const float* __restrict__ uv,
-                                                         const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms,
-                                                         const unsigned char* __restrict__ v_mask, long mask_sb,
-                                                         const int32_t* __restrict__ counts, float tau2, float w_ms,
-                                                         const float* __restrict__ gL, float* __restrict__ g_x) {
-#pragma clang fp contract(off)
-    __shared__ int wave_n[4];
-    __shared__ int list_r[768];
-    __shared__ float list_l[768];
-    __shared__ float list_x[768];
-    __shared__ float list_y[768];
-    __shared__ float list_z[768];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int i_lo = blockIdx.x * 256, i = i_lo + tid;
-    const int m = min(clamp_count(s_count, b, M), counts[2 * b]);
-    const int n_act = counts[2 * b + 1];
-    const float* xb = x + (long)b * x_sb;
-    const float* sb = s + (long)b * s_sb;
-    const bool mine = i < n;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int base = 0; base < m; base += 256) {                         // m is uniform over the workgroup
-        const int j = base + tid;
-        int r[3] = {-1, -1, -1};
-        float l[3] = {0.f, 0.f, 0.f}, ex = 0.f, ey = 0.f, ez = 0.f;
-        if (j < m) {
-            const long o = (long)b * M + j;
-            const int f = face[o];
-            if (f >= 0 && f < nF && d2[o] < tau2) {
-                const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
-                const bool ok = (unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n;
-                const bool h0 = (unsigned)(i0 - i_lo) < 256u, h1 = (unsigned)(i1 - i_lo) < 256u, h2 = (unsigned)(i2 - i_lo) < 256u;
-                if (ok && (h0 || h1 || h2)) {
-                    const float v = uv[2 * o], w = uv[2 * o + 1];
-                    const float ax = xb[3L * i0], ay = xb[3L * i0 + 1], az = xb[3L * i0 + 2];
-                    const float abx = xb[3L * i1] - ax, aby = xb[3L * i1 + 1] - ay, abz = xb[3L * i1 + 2] - az;
-                    const float acx = xb[3L * i2] - ax, acy = xb[3L * i2 + 1] - ay, acz = xb[3L * i2 + 2] - az;
-                    const float apx = sb[3L * j] - ax, apy = sb[3L * j + 1] - ay, apz = sb[3L * j + 2] - az;
-                    ex = __builtin_fmaf(w, acx, v * abx) - apx;          // q - s, the exact negative of the forward pass's residual
-                    ey = __builtin_fmaf(w, acy, v * aby) - apy;
-                    ez = __builtin_fmaf(w, acz, v * abz) - apz;
-                    l[0] = (1.0f - v) - w; l[1] = v; l[2] = w;
-                    r[0] = h0 ? i0 - i_lo : -1; r[1] = h1 ? i1 - i_lo : -1; r[2] = h2 ? i2 - i_lo : -1;
-                }
-            }
-        }
-        const unsigned long long b0 = __ballot(r[0] >= 0), b1 = __ballot(r[1] >= 0), b2 = __ballot(r[2] >= 0);
-        if (lane == 0) wave_n[wv] = __popcll(b0) + __popcll(b1) + __popcll(b2);
-        __syncthreads();
-        int off = 0, total = 0;
-        for (int w_ = 0; w_ < 4; ++w_) { off += w_ < wv ? wave_n[w_] : 0; total += wave_n[w_]; }
-        int pos = off + __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            if (r[k] >= 0) { list_r[pos] = r[k]; list_l[pos] = l[k]; list_x[pos] = ex; list_y[pos] = ey; list_z[pos] = ez; ++pos; }
-        __syncthreads();
-        for (int k = 0; k < total; ++k)
-            if (list_r[k] == tid && mine) {
-                const float lk = list_l[k];
-                a0 = a0 + lk * list_x[k]; a1 = a1 + lk * list_y[k]; a2 = a2 + lk * list_z[k];
-            }
-        __syncthreads();                                                 // the lists are rewritten by the next tile
-    }
-    if (i >= rows) return;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-    const bool active = mine && !(v_mask && v_mask[(long)b * mask_sb + i] == 0);
-    if (active && m > 0) {
-        const float g = gL[b];
-        const float c1 = 2.f / (float)m;
-        g0 = c1 * a0; g1 = c1 * a1; g2 = c1 * a2;
-        if (idx_ms && w_ms > 0.f && n_act > 0) {
-            const int k = idx_ms[(long)b * rows + i];
-            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) {
-                const float c2 = w_ms * 2.f / (float)n_act;
-                const float xi0 = xb[3L * i], xi1 = xb[3L * i + 1], xi2 = xb[3L * i + 2];
-                g0 = g0 + c2 * (xi0 - sb[3L * k]); g1 = g1 + c2 * (xi1 - sb[3L * k + 1]); g2 = g2 + c2 * (xi2 - sb[3L * k + 2]);
-            }
-        }
-        g0 *= g; g1 *= g; g2 *= g;
-    }
-    float* o = g_x + ((long)b * rows + i) * 3;
-    o[0] = g0; o[1] = g1; o[2] = g2;
-}
-
 // One thread per (body, face): the unit normal of the header ("Face normals"), in its one fixed form - the cross product as
 // vertex_normals_kernel forms a face's contribution, no contraction beyond the fused multiply-adds written out, so the numpy
 // transcription of tests/surface_gated_ref.py rounds alike.  A face with a corner outside [0, n), no area or an overflow gets
@@ -399,9 +308,9 @@ __global__ __launch_bounds__(256) void face_normals_kernel(const float* __restri
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)B * nF) return;
     const int b = (int)(t / nF), f = (int)(t - (long)b * nF);
-    const int i0 = faces[3L * f], i1 = faces[3L * f + 1], i2 = faces[3L * f + 2];
+    int i0, i1, i2;
     float nx = 0.f, ny = 0.f, nz = 0.f;
-    if ((unsigned)i0 < (unsigned)n && (unsigned)i1 < (unsigned)n && (unsigned)i2 < (unsigned)n) {
+    if (face_corners(faces, f, n, i0, i1, i2)) {
         const float* xb = x + (long)b * x_sb;
         float cx, cy, cz;
         face_cross(xb + 3L * i0, xb + 3L * i1, xb + 3L * i2, cx, cy, cz);
@@ -562,28 +471,6 @@ int sh_face_normals(const float* x, int64_t x_sb, int n, const int32_t* faces, i
     ShProfScope ps(st, "face_normals_kernel|B=%d n=%d nF=%d", B, n, nF);
     SH_LAUNCH_PS(ps, face_normals_kernel, dim3((unsigned)(((long)B * nF + 255) / 256)), dim3(256), 0, st, x, (long)x_sb, n, faces, nF, B, normals);
     SH_CHECK_LAUNCH("face_normals");
-    return SH_OK;
-}
-
-int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
-                           const int32_t* faces, int nF, const int32_t* face, const float* d2, const float* uv, const int32_t* idx_ms,
-                           const float* d2_ms, const uint8_t* v_mask, int64_t mask_sb, const int32_t* counts, float tau2, float w_ms,
-                           const float* gL, int B, float* g_x, sh_stream_t stream) {
-    SH_REQUIRE(x && s && face && d2 && uv && counts && gL && g_x && (faces || nF == 0), SH_ERR_INVALID_ARG,
-               "sh_chamfer_surface_bwd: null pointer");
-    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows && nF >= 0, SH_ERR_INVALID_ARG,
-               "sh_chamfer_surface_bwd: bad size (B %d, M %d, rows %d, n %d, nF %d)", B, M, rows, n, nF);
-    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_chamfer_surface_bwd: w_ms and tau2 must be >= 0 (and not NaN)");
-    SH_REQUIRE((idx_ms != nullptr) == (d2_ms != nullptr), SH_ERR_INVALID_ARG, "sh_chamfer_surface_bwd: idx_ms and d2_ms come together");
-    if (B == 0 || rows == 0) return SH_OK;
-    SH_REQUIRE(x_sb >= 3L * rows && s_sb >= 3L * M && (!v_mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
-               "sh_chamfer_surface_bwd: batch stride shorter than a body (x_sb %ld, s_sb %ld, mask_sb %ld)", (long)x_sb, (long)s_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * rows < (1L << 30), SH_ERR_UNSUPPORTED, "sh_chamfer_surface_bwd: B or B*rows too large");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ShProfScope ps(st, "surface_bwd_kernel|B=%d M=%d rows=%d", B, M, rows);
-    SH_LAUNCH_PS(ps, surface_bwd_kernel, dim3((unsigned)sh_cdiv(rows, 256), (unsigned)B), dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M,
-                 s_count, faces, nF, face, d2, uv, w_ms > 0.f ? idx_ms : nullptr, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, gL, g_x);
-    SH_CHECK_LAUNCH("chamfer_surface_bwd");
     return SH_OK;
 }
 

@@ -533,14 +533,21 @@ def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out
     return loss, counts
 
 
+def _chamfer_bwd(entry, x, n, s, s_count, partner, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out):
+    """Both gradient wrappers: C entry point `entry` -> g_x contiguous [B, rows, 3] (every element written).  partner: the C
+    arguments of the scan -> model partner, (idx_sm, d2_sm) or (faces, nF, face, d2, uv)."""
+    who = entry[3:]
+    B, rows, x_sb = _points(x, who)
+    _, M, s_sb = _points(s, who)
+    g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(getattr(_lib.load(), entry)(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), *partner, ptr(idx_ms), ptr(d2_ms), ptr(v_mask), mask_sb,
+                                      ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g), stream_ptr()), entry)
+    return g
+
+
 def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
     """sh_chamfer_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
-    B, rows, x_sb = _points(x, "chamfer_bwd")
-    _, M, s_sb = _points(s, "chamfer_bwd")
-    g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
-    check(_lib.load().sh_chamfer_bwd(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), ptr(idx_sm), ptr(d2_sm), ptr(idx_ms), ptr(d2_ms),
-                                     ptr(v_mask), mask_sb, ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g), stream_ptr()), "sh_chamfer_bwd")
-    return g
+    return _chamfer_bwd("sh_chamfer_bwd", x, n, s, s_count, (ptr(idx_sm), ptr(d2_sm)), idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out)
 
 
 def face_normals(x, faces, n, out=None):
@@ -602,13 +609,8 @@ def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunk
 
 def chamfer_surface_bwd(x, n, s, s_count, faces, face, d2, uv, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
     """sh_chamfer_surface_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
-    B, rows, x_sb = _points(x, "chamfer_surface_bwd")
-    _, M, s_sb = _points(s, "chamfer_surface_bwd")
-    g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
-    check(_lib.load().sh_chamfer_surface_bwd(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), ptr(faces), faces.shape[0], ptr(face), ptr(d2),
-                                             ptr(uv), ptr(idx_ms), ptr(d2_ms), ptr(v_mask), mask_sb, ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g),
-                                             stream_ptr()), "sh_chamfer_surface_bwd")
-    return g
+    return _chamfer_bwd("sh_chamfer_surface_bwd", x, n, s, s_count, (ptr(faces), faces.shape[0], ptr(face), ptr(d2), ptr(uv)), idx_ms, d2_ms,
+                        v_mask, mask_sb, counts, tau2, w_ms, gL, out)
 
 
 ALIGN_MODES = {"translation": 0, "rigid": 1, "similarity": 2}   # enum sh_align_mode
