@@ -766,6 +766,54 @@ SH_API int sh_cloud_normals(const float* s, int64_t s_sb, int M, const int32_t* 
                             size_t workspace_bytes, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Vertex visibility: which model vertices a sensor at a known position sees - the vertex mask of a partial (one-view) scan (no
+ * reference counterpart).  fp32, deterministic (no atomics of any kind), plain stores of every output element; the bits depend
+ * on neither batch, launch shape nor split.
+ *
+ * sh_vertex_visibility.  x: [B] bodies of model points, batch stride x_sb floats, the first n rows are vertices; rows >= n (the
+ * decoder's dummy row) are never read.  faces int32 [nF][3], ONE table for the batch; a face with a corner outside [0, n) is
+ * passed over.  view: fp32 [B][3] contiguous, the sensor's position per body in the frame of x.  mask as t_mask of
+ * sh_nearest_points, over n rows.  vis: uint8 [B][n] contiguous, 1 = visible.
+ * Unknown viewpoint.  A vertex whose mask is 0 is not visible.  A body whose viewpoint row holds a NaN has no viewpoint: all its
+ * active vertices are visible, nothing else is looked at (one batch may mix partial and full scans).
+ * Occlusion.  For vertex i with o = x_i and d = v_b - o (component-wise, fp32) the vertex is occluded when the open segment
+ * o + t d, 0 < t < 1, meets a face that does not name vertex i.  EVERY face of the table occludes, whatever the mask says:
+ * masked geometry is still in the way.  Faces that name i are skipped BY INDEX, not by arithmetic (for the origin at corner c,
+ * t = e2 . (e2 x e1) is no exact zero in fp32).  The test is Moeller-Trumbore without a division; for the face's corners a, b,
+ * c in the face's own order, everything in fp32, every operation rounded on its own except the fused multiply-adds written out
+ * (no other contraction - the rule of nn_d2 and of the region test of "Nearest surface points"):
+ *     dot(u, v)   = fma(u.z, v.z, fma(u.y, v.y, u.x * v.x))
+ *     cross(u, v) = (fma(u.y, v.z, -(u.z * v.y)),  fma(u.z, v.x, -(u.x * v.z)),  fma(u.x, v.y, -(u.y * v.x)))
+ *     e1 = b - a;  e2 = c - a;  s = o - a                                  (component-wise)
+ *     p = cross(d, e2);  det = dot(e1, p);  u = dot(s, p);  q = cross(s, e1);  w = dot(d, q);  t = dot(e2, q)
+ *     sigma = -1 when det < 0, else +1;   |det| = fabs(det)
+ *     hit  iff  det != 0  and  sigma u >= 0  and  sigma w >= 0  and  fl(sigma u + sigma w) <= |det|  and  0 < sigma t < |det|
+ * (sigma applied by negation, which is exact; a NaN compares false: no hit).  Edges and corners of a face belong to it; the two
+ * ends of the segment do not.  Two distinct vertices at (nearly) the same place may hide each other's faces or not: ambiguous
+ * by nature, as is a ray along an edge.
+ * Facing (tn != NULL).  tn: contiguous [B][n][3] unit vertex normals (sh_vertex_normals of the same x).  The vertex must also
+ * face the sensor:   dot(tn_i, d) >= fl(cos_g * sqrtf(dot(d, d)))        (a NaN compares false: not visible)
+ * cos_g in [0, 1) is the cosine of the largest angle between normal and line of sight; a zero ("unknown") normal passes only
+ * for cos_g == 0, as with the gates.  tn == NULL: no normal is read, cos_g is ignored.
+ * visible = active and facing (if asked) and not occluded.
+ *
+ * How it is computed.  The form of the nearest search: 256 threads, one vertex per thread in registers; faces streamed through
+ * double-buffered LDS tiles of 256 - each thread gathers one face's corners from x and stores (a, e1, e2, i0, i1, i2), 48 bytes,
+ * and the inner loop reads a face as three 16-byte reads at an address common to all lanes.  Any-hit: a lane is done once it is
+ * hit, masked, beyond n or turned away; a wave stops testing when a ballot finds every lane done, and the tile loop ends
+ * for the workgroup when all four waves are (the fetch of the next tile, already in flight by then, is dropped).  The face range may be split into `chunks` ranges of whole tiles (0: chosen from B, n, nF to fill the
+ * chip, the rule of sh_nearest_points); each chunk then stores its flag into workspace [chunks][B][n] bytes and a second launch
+ * ORs them - no atomics, and an OR depends on no order, so every split returns the same bits.  A split into more than one chunk
+ * needs sh_vertex_visibility_workspace(B, n, nF, chunks) bytes.  Brute force: O(n nF) tests per body before the early exits.
+ * B == 0 or n == 0: SH_OK, nothing launched.  Null x / view / vis, negative sizes, a stride shorter than a body, cos_g outside
+ * [0, 1) with tn: SH_ERR_INVALID_ARG before the device is touched.
+ */
+SH_API size_t sh_vertex_visibility_workspace(int B, int n, int nF, int chunks);
+SH_API int sh_vertex_visibility(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view,
+                                float cos_g, const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace,
+                                size_t workspace_bytes, uint8_t* vis, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.

@@ -1,0 +1,180 @@
+// Which model vertices a sensor sees (include/sh_kernels.h, "Vertex visibility"): per vertex the segment to the body's viewpoint
+// against every triangle of the table.  The reference has no counterpart.  The sweep has the form of scan.hip's
+// nearest_search_kernel - one vertex per thread in registers, the faces streamed through double-buffered LDS tiles, every lane
+// reading the same LDS address (broadcast) - but it is an any-hit search: a lane that has been hit is done, and a wave whose
+// lanes are all done stops testing.  No atomics, no scratch: the face range may be split into chunks whose flags a second
+// launch ORs, and an OR does not depend on order.
+#include "sh_nn.h"
+
+namespace {
+
+constexpr int NT = 256;          // threads per workgroup = vertices per workgroup
+constexpr int TF = 256;          // faces per LDS tile: one face gathered per thread and tile
+
+// The header's products, each in its one fixed form.
+__device__ __forceinline__ float vis_dot(float ux, float uy, float uz, float vx, float vy, float vz) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(uz, vz, __builtin_fmaf(uy, vy, ux * vx));
+}
+__device__ __forceinline__ void vis_cross(float ux, float uy, float uz, float vx, float vy, float vz, float& cx, float& cy, float& cz) {
+#pragma clang fp contract(off)
+    cx = __builtin_fmaf(uy, vz, -(uz * vy));
+    cy = __builtin_fmaf(uz, vx, -(ux * vz));
+    cz = __builtin_fmaf(ux, vy, -(uy * vx));
+}
+
+// grid (vertex tile, face chunk, body).  final != 0: the one chunk's answer is the answer, flag = vis [B][n], 1 = visible;
+// otherwise flag = the workspace [chunks][B][n], 1 = NOT visible on this chunk's evidence, for visibility_fold_kernel.
+// A face enters LDS as three 16-byte records - (a, e1.x) (e1.y, e1.z, e2.x, e2.y) (e2.z, i0, i1, i2) - written by the thread that
+// gathered its corners; a face beyond the table, or with a corner outside [0, n), enters as NaN with indices -1: its det is NaN and
+// no compare of the hit test holds.  A lane is `done` when nothing a face could do would change its answer: beyond n, masked,
+// turned away from the sensor, or already hit.  The inner loop asks the wave every four faces whether any lane is still open;
+// the tile loop asks the workgroup once per tile, through two LDS words per wave written before the tile's one barrier.
+__global__ __launch_bounds__(NT) void vertex_visibility_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
+                                                              int nF, const float* __restrict__ tn, const float* __restrict__ view,
+                                                              float cos_g, const unsigned char* __restrict__ mask, long mask_sb, int B,
+                                                              int tiles_per_chunk, int final, unsigned char* __restrict__ flag) {
+#pragma clang fp contract(off)
+    __shared__ f32x4 sf[2][3 * TF];
+    __shared__ int sopen[2][NT / 64];
+    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
+    const int i = blockIdx.x * NT + tid;
+    const bool inside = i < n;
+    const float* xb = x + (long)b * x_sb;
+    const float vx = view[3L * b], vy = view[3L * b + 1], vz = view[3L * b + 2];
+    const bool known = vx == vx && vy == vy && vz == vz;                 // uniform: a NaN row = no viewpoint, nothing is hidden
+    const bool active = inside && (!mask || mask[(long)b * mask_sb + i] != 0);
+    const float ox = inside ? xb[3L * i] : 0.f, oy = inside ? xb[3L * i + 1] : 0.f, oz = inside ? xb[3L * i + 2] : 0.f;
+    const float dx = vx - ox, dy = vy - oy, dz = vz - oz;
+    bool hidden = !active;
+    if (known && active && tn) {                                         // the facing test; tn is uniform
+        const float* t = tn + ((long)b * n + i) * 3;
+        const float along = vis_dot(t[0], t[1], t[2], dx, dy, dz);
+        const float len = sqrtf(vis_dot(dx, dy, dz, dx, dy, dz));
+        hidden = !(along >= cos_g * len);                                // a NaN compares false: hidden
+    }
+    const int tiles = (nF + TF - 1) / TF;
+    const int tile_lo = c * tiles_per_chunk;
+    const int tile_hi = min(tile_lo + tiles_per_chunk, tiles);
+    if (known && tile_lo < tile_hi) {                                    // uniform
+        bool done = hidden;
+        const int wave = sh_wave_id();
+        f32x4 r0, r1, r2;
+        auto fetch = [&](int tile) {
+            const int f = tile * TF + tid;
+            int i0 = -1, i1 = -1, i2 = -1;
+            const bool ok = f < nF && face_corners(faces, f, n, i0, i1, i2);
+            float ax = NAN, ay = NAN, az = NAN, bx = NAN, by = NAN, bz = NAN, cx = NAN, cy = NAN, cz = NAN;
+            if (ok) {
+                ax = xb[3L * i0]; ay = xb[3L * i0 + 1]; az = xb[3L * i0 + 2];
+                bx = xb[3L * i1]; by = xb[3L * i1 + 1]; bz = xb[3L * i1 + 2];
+                cx = xb[3L * i2]; cy = xb[3L * i2 + 1]; cz = xb[3L * i2 + 2];
+            } else {
+                i0 = i1 = i2 = -1;
+            }
+            r0 = f32x4{ax, ay, az, bx - ax};
+            r1 = f32x4{by - ay, bz - az, cx - ax, cy - ay};
+            r2 = f32x4{cz - az, __int_as_float(i0), __int_as_float(i1), __int_as_float(i2)};
+        };
+        auto stage = [&](int buf) { sf[buf][3 * tid] = r0; sf[buf][3 * tid + 1] = r1; sf[buf][3 * tid + 2] = r2; };
+        fetch(tile_lo);
+        stage(0);
+        int open = __ballot(!done) != 0ull;                               // uniform over the wave
+        if ((tid & 63) == 0) sopen[0][wave] = open;
+        __syncthreads();
+        for (int tile = tile_lo; tile < tile_hi; ++tile) {
+            const int cur = (tile - tile_lo) & 1;
+            if ((sopen[cur][0] | sopen[cur][1] | sopen[cur][2] | sopen[cur][3]) == 0) break;   // uniform over the workgroup: every lane is done
+            const bool more = tile + 1 < tile_hi;
+            if (more) fetch(tile + 1);                                   // in flight under this tile's arithmetic
+            for (int u = 0; u < TF; u += 4) {
+                if (__ballot(!done) == 0ull) break;                      // uniform over the wave
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const f32x4 R0 = sf[cur][3 * (u + e)], R1 = sf[cur][3 * (u + e) + 1], R2 = sf[cur][3 * (u + e) + 2];
+                    const float ax = R0[0], ay = R0[1], az = R0[2], e1x = R0[3], e1y = R1[0], e1z = R1[1];
+                    const float e2x = R1[2], e2y = R1[3], e2z = R2[0];
+                    const bool names = __float_as_int(R2[1]) == i || __float_as_int(R2[2]) == i || __float_as_int(R2[3]) == i;
+                    float px, py, pz, qx, qy, qz;
+                    vis_cross(dx, dy, dz, e2x, e2y, e2z, px, py, pz);
+                    const float det = vis_dot(e1x, e1y, e1z, px, py, pz);
+                    const float sx = ox - ax, sy = oy - ay, sz = oz - az;
+                    const float uu = vis_dot(sx, sy, sz, px, py, pz);
+                    vis_cross(sx, sy, sz, e1x, e1y, e1z, qx, qy, qz);
+                    const float ww = vis_dot(dx, dy, dz, qx, qy, qz);
+                    const float tt = vis_dot(e2x, e2y, e2z, qx, qy, qz);
+                    const bool neg = det < 0.f;
+                    const float ad = fabsf(det), su = neg ? -uu : uu, sw = neg ? -ww : ww, st = neg ? -tt : tt;
+                    const bool hit = det != 0.f && su >= 0.f && sw >= 0.f && su + sw <= ad && st > 0.f && st < ad;   // a NaN compares false
+                    done = done || (hit && !names);
+                }
+            }
+            if (more) {
+                stage(cur ^ 1);
+                open = __ballot(!done) != 0ull;
+                if ((tid & 63) == 0) sopen[cur ^ 1][wave] = open;
+            }
+            __syncthreads();                                             // one barrier per tile, as in nearest_search_kernel
+        }
+        hidden = done;
+    }
+    if (!inside) return;
+    if (final) flag[(long)b * n + i] = hidden ? 0 : 1;
+    else flag[((long)c * B + b) * n + i] = hidden ? 1 : 0;
+}
+
+// vis[b][i] = 1 unless some chunk says "not visible".  One thread per (body, vertex).
+__global__ __launch_bounds__(256) void visibility_fold_kernel(const unsigned char* __restrict__ part, long per_chunk, int chunks,
+                                                             unsigned char* __restrict__ vis) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= per_chunk) return;
+    unsigned char any = 0;
+    for (int c = 0; c < chunks; ++c) any |= part[(long)c * per_chunk + t];
+    vis[t] = any ? 0 : 1;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sh_vertex_visibility_workspace(int B, int n, int nF, int chunks) {
+    if (B <= 0 || n <= 0 || nF < 0 || chunks < 0) return 0;
+    int tpc;
+    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
+    return c <= 1 ? 0 : (size_t)c * B * n;
+}
+
+int sh_vertex_visibility(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view, float cos_g,
+                         const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace, size_t workspace_bytes, uint8_t* vis,
+                         sh_stream_t stream) {
+    SH_REQUIRE(x && view && vis && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_vertex_visibility: null pointer");
+    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "sh_vertex_visibility: negative size (B %d, n %d, nF %d, chunks %d)",
+               B, n, nF, chunks);
+    SH_REQUIRE(!tn || (cos_g >= 0.f && cos_g < 1.f), SH_ERR_INVALID_ARG, "sh_vertex_visibility: cos_g must lie in [0, 1) (and not be NaN)");
+    if (B == 0 || n == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * n && (!mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_vertex_visibility: batch stride shorter than a body (x_sb %ld, mask_sb %ld)", (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "sh_vertex_visibility: B, B*n or nF too large");
+    int tpc;
+    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
+    SH_REQUIRE(c <= 65535, SH_ERR_UNSUPPORTED, "sh_vertex_visibility: %d face chunks", c);
+    const size_t need = c <= 1 ? 0 : (size_t)c * B * n;
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
+               "sh_vertex_visibility: workspace too small (%zu bytes needed for %d chunks)", need, c);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int final = c <= 1;
+    unsigned char* flag = final ? vis : static_cast<unsigned char*>(workspace);
+    {
+        ShProfScope ps(st, "vertex_visibility_kernel|B=%d n=%d nF=%d chunks=%d", B, n, nF, c);
+        SH_LAUNCH_PS(ps, vertex_visibility_kernel, dim3((unsigned)sh_cdiv(n, NT), (unsigned)c, (unsigned)B), dim3(NT), 0, st, x, (long)x_sb, n, faces,
+                     nF, tn, view, cos_g, mask, (long)mask_sb, B, tpc, final, flag);
+    }
+    if (!final) {
+        ShProfScope ps(st, "visibility_fold_kernel|B=%d n=%d chunks=%d", B, n, c);
+        SH_LAUNCH_PS(ps, visibility_fold_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, st, flag, (long)B * n, c, vis);
+    }
+    SH_CHECK_LAUNCH("vertex_visibility");
+    return SH_OK;
+}
+
+}  // extern "C"

@@ -219,8 +219,17 @@ def fit_part_girths(model, z, z_kps, rings, target, edit, hold=(), parts=None, b
     return z_new, g_final, losses
 
 
+def _visibility_cache(what, visibility, visibility_every):
+    """The state scan._chamfer keeps between the passes of a fit: the last visibility mask and the pass counter."""
+    every = int(visibility_every)
+    if every < 1:
+        raise ValueError("%s: visibility_every must be >= 1" % what)
+    return None if visibility is None else {"every": every, "t": 0, "mask": None}
+
+
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None,
-             faces=None, normal_angle=None, normal_faces=None, gate_on="vertices"):
+             faces=None, normal_angle=None, normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None,
+             grazing_angle=None, visibility_every=1):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
     The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
@@ -232,12 +241,19 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     gate of scan.chamfer (degrees; needs scans.normals, the model's triangles and trunc; None: none, the same bits as ever).
     gate_on: "vertices" (the default: that gate, on vertex normals, not built together with faces) or "surface" - the gate of the
     surface distance, on the face's normal (scan.chamfer; needs faces, normal_angle, scan normals and trunc).
+    visibility: None (the default: everything above, bit for bit) or "viewpoint" - one-view scans: only the model vertices seen
+    from scans.viewpoints take part (scan.chamfer(..., visibility=); visibility_faces / grazing_angle as there), which makes
+    w_model_to_scan > 0 usable on them.  The mask is recomputed from the decoded body every `visibility_every`-th step (1: every
+    step) and reused in between; the returned Chamfer value uses a fresh one.  A pass costs about half a vertex fit step at B = 64
+    (DESIGN 4q): 1 while pose or shape still move, 4 once the fit has settled.
     Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
         raise ValueError("fit_scan: %d bodies, %d scans" % (z.shape[0], len(scans)))
     scan._MatchPlan.check_gate("fit_scan", gate_on, normal_angle, faces, scans, trunc)
+    scan._MatchPlan.check_visibility("fit_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
+    vis_cache = _visibility_cache("fit_scan", visibility, visibility_every)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -246,17 +262,27 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     def objective(x_hat):
         if not tables:                                                     # validated and uploaded once, at the first decode: n is known here
             tables.update(faces=_face_table(faces, x_hat), normal_faces=_face_table(normal_faces, x_hat) if normal_angle is not None else None)
-        return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, normal_angle=normal_angle, gate_on=gate_on, **tables)
+            if visibility is not None:
+                vf = visibility_faces if visibility_faces is not None else (faces if faces is not None else normal_faces)
+                tables.update(visibility_faces=tables["faces"] if vf is faces else _face_table(vf, x_hat))
+        if visibility is None:
+            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, normal_angle=normal_angle, gate_on=gate_on, **tables)
+        return scan._chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, None, tables["faces"], normal_angle, tables["normal_faces"],
+                             gate_on, visibility=visibility, visibility_faces=tables["visibility_faces"], grazing_angle=grazing_angle,
+                             vis_cache=vis_cache)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():
+        if vis_cache is not None:
+            vis_cache["t"] = 0                                             # the result is measured under a fresh mask
         final = objective(_decode(model, z_new, z_kps, dummy))
     return z_new, final, losses
 
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
-                  normal_angle=None, normal_faces=None, align_on="vertices", align_step="point", gate_on="vertices"):
+                  normal_angle=None, normal_faces=None, align_on="vertices", align_step="point", gate_on="vertices", visibility=None,
+                  visibility_faces=None, grazing_angle=None, visibility_every=1):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -288,7 +314,11 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     default: the gate above, on vertex normals, not built together with faces) or "surface" - the fit's surface distance is gated
     by the face's normal (scan.chamfer(..., gate_on="surface"); needs faces, normal_angle, scan normals and trunc), with either
     align_on: "surface" gates both pose stages' foot points the same way, "vertices" runs them on vertex pairs gated by the
-    vertex normals (of normal_faces, or of faces when that is omitted).  No file reader."""
+    vertex normals (of normal_faces, or of faces when that is omitted).  visibility: None (the default: everything above, bit
+    for bit) or "viewpoint" - one-view scans: scans.viewpoints, in the SCAN's frame, follow the pose; stage 1 is
+    scan.align(..., visibility=) (a fresh mask every iteration), the fit uses scan.chamfer(..., visibility=) on the aligned
+    batch with the mask recomputed every `visibility_every`-th step, and every in-loop pose update moves the viewpoint with the
+    scan.  visibility_faces / grazing_angle as in scan.chamfer.  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -308,6 +338,8 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     if on_surface and faces is None:
         raise ValueError("register_scan: align_on='surface' needs faces (the model's triangles)")
     surface_gate = scan._MatchPlan.check_gate("register_scan", gate_on, normal_angle, faces, scans, trunc) is not None
+    scan._MatchPlan.check_visibility("register_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
+    vis_cache = _visibility_cache("register_scan", visibility, visibility_every)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -318,15 +350,22 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
         raise ValueError("register_scan: normal_angle together with faces= (the surface distance) is not built for the gate on vertex "
                          "normals; gate_on='surface' gates the surface search by the face's normal")
     normal_faces, faces = _face_table(normal_faces, x0), _face_table(faces, x0)
+    if visibility is not None:
+        vf = visibility_faces if visibility_faces is not None else (faces if faces is not None else normal_faces)
+        visibility_faces = faces if vf is faces else _face_table(vf, x0)
     if normal_faces is None:                                                            # the vertex normals' table falls back to the surface's
         normal_faces = faces
+    vis = {} if visibility is None else dict(visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
                                   vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
-                                  faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices")
+                                  faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices", **vis)
     matches = {} if align_every > 0 else None
     state = {"partials": None}
 
     def objective(x_hat):                                                               # foot-point pose updates read no vertex record
+        if visibility is not None:
+            return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
+                                 vertex_matches=not on_surface, vis_cache=vis_cache, **vis)
         return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
                              vertex_matches=not on_surface)
 
@@ -339,5 +378,5 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
                                 after_step=after_step if align_every > 0 else None)
     with torch.no_grad():
         final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan, faces=faces,
-                             normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on)
+                             normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on, **vis)
     return z_new, pose, final, losses

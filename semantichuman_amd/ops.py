@@ -523,6 +523,36 @@ def cloud_normals(s, count=None, k=16, view=None, out=None):
     return nrm, var, r2, cnt
 
 
+def vertex_visibility(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks=0, out=None):
+    """sh_vertex_visibility: x [B, *, 3] of which the first n rows are vertices, faces int32 HIP [nF, 3], view fp32 HIP [B, 3]
+    (a NaN row: no viewpoint, every active vertex visible) -> uint8 [B, n], 1 = the vertex is active, not occluded by any face
+    that does not name it and - with tn, contiguous fp32 [B, n, 3] vertex normals - faces the sensor to within cos_g.  v_mask
+    [n] or [B, n].  chunks: 0 = the library's split of the face range, k = that many ranges; every split gives the same bits."""
+    B, rows, x_sb = _points(x, "vertex_visibility")
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("vertex_visibility: n = %d exceeds the model's %d rows" % (n, rows))
+    nF = _face_table_arg(faces, "vertex_visibility")
+    if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous() and tuple(view.shape) == (B, 3)):
+        raise ValueError("vertex_visibility: view must be a contiguous fp32 HIP tensor [%d, 3], got %s" % (B, tuple(getattr(view, "shape", ()))))
+    if tn is not None and not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous()
+                               and tuple(tn.shape) == (B, n, 3)):
+        raise ValueError("vertex_visibility: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (B, n))
+    mask, mask_sb = _mask_arg(v_mask, B, n, x.device)
+    chunks = int(chunks)
+    if chunks < 0:
+        raise ValueError("vertex_visibility: chunks must be >= 0")
+    lib = _lib.load()
+    vis = out if out is not None else torch.empty((B, n), dtype=torch.uint8, device=x.device)
+    if not (torch.is_tensor(vis) and vis.device == x.device and vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (B, n)):
+        raise ValueError("vertex_visibility: out must be a contiguous uint8 tensor [%d, %d] on the device of x" % (B, n))
+    nbytes = lib.sh_vertex_visibility_workspace(B, n, nF, chunks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    check(lib.sh_vertex_visibility(ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view), float(cos_g), ptr(mask), mask_sb, B, chunks, ptr(ws),
+                                   nbytes, ptr(vis), stream_ptr()), "sh_vertex_visibility")
+    return vis
+
+
 def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None):
     """sh_chamfer_fwd -> (loss [B], counts int32 [B, 2])."""
     B, M = d2_sm.shape

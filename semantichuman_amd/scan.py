@@ -18,6 +18,9 @@
   * `estimate_normals(points, k)`, `ScanBatch(..., normals="estimate")`  normals of a bare cloud, from the cloud: per point the k
                                      nearest points of its own cloud and the direction of least spread among them
                                      (sh_cloud_normals) - unoriented unless `viewpoints` are given
+  * `visible_vertices(x, faces, viewpoints)`, `visibility="viewpoint"` on chamfer / align  partial scans: the model vertices the
+                                     sensor sees from `ScanBatch(..., viewpoints=)` - not occluded by any triangle, optionally
+                                     facing the sensor (sh_vertex_visibility) - are the vertex mask of every search and term
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -30,6 +33,7 @@ The search, the loss and the alignment have no CPU path: tensors must live on th
 from __future__ import annotations
 
 import math
+import sys
 
 import numpy as np
 import torch
@@ -158,8 +162,17 @@ class ScanBatch:
     frame - [3], [B, 3] or a list of [m_b, 3] arrays (one row per point, in the order of the clouds given; sorted with them) - and
     every normal then points into its viewpoint's half space.  Without viewpoints the normals are UNORIENTED: the sign is a
     convention (largest component positive), so about half of them point into the body, and a gate narrower than 90 degrees
-    rejects correct partners; a gate blind to orientation (on |cos|) is not part of the library.  normal_k and viewpoints are
-    read only with normals="estimate".  ValueError for a normal_k outside [3, 64] or viewpoints of another shape."""
+    rejects correct partners; a gate blind to orientation (on |cos|) is not part of the library.
+    normal_k is read only with normals="estimate".  ValueError for a normal_k outside [3, 64] or viewpoints of another shape.
+
+    `viewpoints`: fp32 [B, 3] on the device when a per-body viewpoint ([3] or [B, 3]) was given, with or without
+    normals="estimate" - what `visibility="viewpoint"` of chamfer / align reads; None otherwise (per-point viewpoints serve the
+    normals' orientation only).  A row set to NaN afterwards marks a body as a full scan: no viewpoint, every vertex visible.
+    Without normals="estimate" a viewpoint that cannot be packed (another shape, NaN or inf) raises nothing here, as ever; the
+    field is None and `visibility="viewpoint"` later names the reason."""
+
+    viewpoints = None                                                                   # for batches made without __init__ or _from_parts
+    viewpoints_error = None
 
     def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None):
         if order not in (None, "morton"):
@@ -170,7 +183,15 @@ class ScanBatch:
                 raise ValueError("ScanBatch: normals must be None, arrays or 'estimate', got %r" % (normals,))
             normal_k = _check_normal_k("ScanBatch: normal_k", normal_k)
         pts, counts = pack_clouds(clouds)
-        view = pack_viewpoints(viewpoints, counts, pts.shape[1]) if estimate and viewpoints is not None else None
+        view = None
+        if viewpoints is not None:
+            try:
+                view = pack_viewpoints(viewpoints, counts, pts.shape[1])
+            except ValueError:
+                if estimate:
+                    raise
+                view = None                                                    # without "estimate" a viewpoint that fits no shape is not read, as ever
+                self.viewpoints_error = str(sys.exc_info()[1])
         nrm = None if normals is None or estimate else pack_normals(normals, counts, pts.shape[1])
         self.perm = None
         if order == "morton":
@@ -187,23 +208,27 @@ class ScanBatch:
         self.points = torch.from_numpy(pts).to(dev)
         self.counts = torch.from_numpy(counts).to(dev)
         self.normals = None if nrm is None else torch.from_numpy(nrm).to(dev)
+        view = None if view is None else torch.from_numpy(view).to(dev)
+        self.viewpoints = view if view is not None and view.dim() == 2 else None
         if estimate:
-            self.normals = ops.cloud_normals(self.points, self.counts, normal_k, None if view is None else torch.from_numpy(view).to(dev))[0]
+            self.normals = ops.cloud_normals(self.points, self.counts, normal_k, view)[0]
 
     def __len__(self):
         return self.points.shape[0]
 
     @classmethod
-    def _from_parts(cls, points, counts, host_counts, perm, normals):
+    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None):
         """A ScanBatch around tensors that are already packed and resident: every field, nothing copied or checked."""
         out = cls.__new__(cls)
         out.points, out.counts, out.host_counts, out.perm, out.normals = points, counts, host_counts, perm, normals
+        out.viewpoints = viewpoints
         return out
 
     def select(self, sl):
         """The bodies `sl` (a slice) as a ScanBatch sharing this one's memory."""
         return ScanBatch._from_parts(self.points[sl], self.counts[sl].contiguous(), self.host_counts[sl],
-                                     None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl])
+                                     None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl],
+                                     viewpoints=None if self.viewpoints is None else self.viewpoints[sl].contiguous())
 
 
 def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
@@ -313,6 +338,57 @@ def face_normals(x, faces, n=None):
     return ops.face_normals(x, ft.faces, ft.n)
 
 
+def _cos_grazing(what, grazing_angle):
+    """A grazing angle in degrees, checked -> the bound sh_vertex_visibility holds the normal's component along the line of sight
+    against; 90 is an exact 0 (a zero normal passes there, and only there)."""
+    a = float(grazing_angle)
+    if not 0.0 < a <= 90.0:
+        raise ValueError("%s: grazing_angle must lie in (0, 90] degrees, got %r" % (what, grazing_angle))
+    return 0.0 if a == 90.0 else math.cos(math.radians(a))
+
+
+def _view_arg(what, viewpoints, B, device):
+    """Per-body viewpoints as the kernel takes them: host [3] / [B, 3] (a NaN row = no viewpoint) or an fp32 device tensor [B, 3]
+    -> contiguous fp32 [B, 3] on `device` (None: where it is).  ValueError on any other shape."""
+    v = viewpoints
+    if torch.is_tensor(v) and v.is_cuda:
+        if v.dtype != torch.float32 or tuple(v.shape) != (B, 3):
+            raise ValueError("%s: device viewpoints must be fp32 [%d, 3], got %s %s" % (what, B, v.dtype, tuple(v.shape)))
+        return v.detach().contiguous()
+    if torch.is_tensor(v):
+        v = v.detach().numpy()
+    try:
+        a = np.asarray(v, dtype=np.float32)
+    except (ValueError, TypeError):
+        a = None
+    if a is None or a.shape not in ((3,), (B, 3)):
+        raise ValueError("%s: viewpoints must be [3] or [%d, 3], got %s" % (what, B, "shape %s" % (a.shape,) if a is not None else type(v).__name__))
+    out = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (B, 3))))
+    return out if device is None else out.to(device)
+
+
+def visible_vertices(x, faces, viewpoints, n=None, vertex_mask=None, grazing_angle=None, chunks=0):
+    """The model vertices a sensor sees: bool [B, n] on the device (sh_vertex_visibility; include/sh_kernels.h, "Vertex
+    visibility").  Vertex i of body b is visible when it is active (vertex_mask [n] or [B, n], False = not visible), the open
+    segment from it to the body's viewpoint meets no triangle of `faces` other than those that name i - every triangle occludes,
+    masked or not - and, with grazing_angle (degrees in (0, 90]), its normal (`vertex_normals(x, faces)`) lies within that angle
+    of the line of sight; a zero normal passes only at 90.  Without grazing_angle no normals are computed.  x [B, rows, 3]; faces:
+    a FaceTable or an integer array [nF, 3]; n as in `chamfer` (None = rows - 1).  viewpoints: host [3] / [B, 3] or an fp32 device
+    tensor [B, 3], in the frame of x; a body whose row holds a NaN has no viewpoint and all its active vertices are visible.
+    chunks: the split of the face range (0 = chosen by the library; every split gives the same bits).  Brute force, O(n nF) per
+    body with early exits.  Deterministic, not differentiable.  ValueError for a wrong viewpoint shape or a grazing_angle outside
+    (0, 90]."""
+    cos_g = None if grazing_angle is None else _cos_grazing("visible_vertices", grazing_angle)
+    if torch.is_tensor(x) and x.dim() == 3:
+        viewpoints = _view_arg("visible_vertices", viewpoints, x.shape[0], None)    # the shape check needs no device
+        x = x.detach()
+    B, rows, _ = ops._points(x, "scan.visible_vertices")
+    view = viewpoints.to(x.device)
+    ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
+    tn = None if cos_g is None else ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
+    return ops.vertex_visibility(x, ft.faces, ft.n, view, vertex_mask, tn, 0.0 if cos_g is None else cos_g, chunks=chunks).bool()
+
+
 def _cos_min(what, normal_angle):
     """A gate's angle in degrees, checked -> the bound the kernels hold the fp32 dot product of two normals against; 180 opens the
     gate (-inf)."""
@@ -383,10 +459,16 @@ class _MatchPlan:
     `normal_faces` - `normals`, else `surface`, else with record=True a given normal_faces - or None.  kind: the scan -> model
     partner, one of VERTEX, VERTEX_GATED, SURFACE (bounded by the vertex search), SURFACE_GATED (the face-normal gate).  An
     array becomes a FaceTable here, once; a FaceTable is used as it is.  pair: what `_check_pair` returned; `chamfer`
-    takes no pose step and leaves `step` alone."""
+    takes no pose step and leaves `step` alone.
 
-    def __init__(self, what, x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step="point", record=False):
+    visibility: None, or "viewpoint" - then `see(x, view)` replaces v_mask by the given mask AND the vertices the sensor at `view`
+    sees (sh_vertex_visibility on `vis_table`: visibility_faces, else faces, else normal_faces), with mask_sb = n; searches, loss,
+    gradient, moments and `pose_update` read it as they read a given mask.  cos_g: the grazing bound, or None."""
+
+    def __init__(self, what, x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step="point", record=False,
+                 visibility=None, visibility_faces=None, grazing_angle=None):
         self.scans, B, self.rows, self.n = pair
+        self.check_visibility(what, visibility, visibility_faces, faces, normal_faces, grazing_angle, self.scans)
         self.w = float(w_model_to_scan)
         if not self.w >= 0.0:
             raise ValueError("%s: w_model_to_scan must be >= 0" % what)
@@ -436,6 +518,48 @@ class _MatchPlan:
         if self.recorded is None and record and normal_faces is not None:
             self.recorded = table(normal_faces)
         self.kind = ((VERTEX, VERTEX_GATED), (SURFACE, SURFACE_GATED))[self.surface is not None][self.cos_min is not None]
+        self.visibility, self.vis_table, self.cos_g, self.vis_tn = visibility, None, None, None
+        if visibility is not None:
+            self.given_mask = self.v_mask
+            self.cos_g = None if grazing_angle is None else _cos_grazing(what, grazing_angle)
+            vf = visibility_faces if visibility_faces is not None else (faces if faces is not None else normal_faces)
+            if vf is faces and self.surface is not None:                            # a table already made from the same argument serves
+                self.vis_table = self.surface
+            elif vf is normal_faces and self.normals is not None and self.normals is not self.surface:
+                self.vis_table = self.normals
+            else:
+                self.vis_table = table(vf)
+            same_n(self.vis_table, "visibility_faces")
+
+    @staticmethod
+    def check_visibility(what, visibility, visibility_faces, faces, normal_faces, grazing_angle, scans):
+        """The checks of `visibility` that need no device: ValueError on an unknown value, and for "viewpoint" on what it needs and
+        lacks (per-body viewpoints on the scans, a face table), or on a grazing_angle outside (0, 90]."""
+        if visibility not in (None, "viewpoint"):
+            raise ValueError("%s: visibility must be None or 'viewpoint', got %r" % (what, visibility))
+        if visibility is None:
+            return
+        if grazing_angle is not None:
+            _cos_grazing(what, grazing_angle)
+        if isinstance(scans, ScanBatch) and scans.viewpoints is None or not isinstance(scans, ScanBatch):
+            why = getattr(scans, "viewpoints_error", None)
+            raise ValueError("%s: visibility='viewpoint' needs the sensor's position per body (ScanBatch(..., viewpoints=[3] or [B, 3]))%s"
+                             % (what, "; the viewpoints given were not kept: %s" % why if why else ""))
+        if visibility_faces is None and faces is None and normal_faces is None:
+            raise ValueError("%s: visibility='viewpoint' needs the model's triangles (visibility_faces=, faces= or normal_faces=)" % what)
+
+    def see(self, x, view, out=None, static_x=False):
+        """Recompute the mask for the model points x seen from `view` fp32 [B, 3]: v_mask = given mask AND visible, uint8 [B, n].
+        static_x: x does not change between calls of this plan, so the facing test's normals are computed once."""
+        ft, tn = self.vis_table, None
+        if self.cos_g is not None:
+            tn = self.vis_tn
+            if tn is None:
+                tn = ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
+                self.vis_tn = tn if static_x else None
+        self.v_mask = ops.vertex_visibility(x, ft.faces, ft.n, view, self.given_mask, tn, 0.0 if self.cos_g is None else self.cos_g, out=out)
+        self.mask_sb = self.n
+        return self.v_mask
 
     @staticmethod
     def check_gate(what, gate_on, normal_angle, faces, scans, trunc):
@@ -513,7 +637,17 @@ class _MatchPlan:
 
 class _Chamfer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, plan, matches, vertex_matches):
+    def forward(ctx, x, plan, matches, vertex_matches, vis_cache=None):
+        if plan.visibility is not None:                                             # the mask of this pass: the plan carries it to the backward pass
+            c = vis_cache
+            if c is None or c["mask"] is None or c["t"] % c["every"] == 0:
+                plan.see(x.detach(), plan.scans.viewpoints)
+                if c is not None:
+                    c["mask"] = plan.v_mask
+            else:
+                plan.v_mask, plan.mask_sb = c["mask"], plan.n
+            if c is not None:
+                c["t"] += 1
         m = plan.search(x, plan.scans, vertex_matches=vertex_matches and matches is not None)
         loss, counts = plan.loss(m, plan.scans)
         ctx.plan = plan
@@ -530,11 +664,11 @@ class _Chamfer(torch.autograd.Function):
         bwd = ops.chamfer_bwd if p.surface is None else ops.chamfer_surface_bwd
         g = bwd(x, p.n, p.scans.points, p.scans.counts, *partner, idx_ms, d2_ms, p.v_mask, p.mask_sb, counts, p.tau2, p.w,
                 gL.to(torch.float32).contiguous())
-        return g, None, None, None
+        return g, None, None, None, None
 
 
 def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None, normal_angle=None,
-            normal_faces=None, gate_on="vertices"):
+            normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None, grazing_angle=None):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -575,16 +709,32 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     term stays vertex to scan point and is gated by the vertex normals as above.  The backward pass is that of `faces=`.
     `matches` keeps its keys: `face`, `uv`, `d2_surface` are the gated surface results, `idx_sm` / `d2_sm` the gated VERTEX
     matches (one more gated vertex search, run only when `matches` is given), `tn` the vertex normals when they were computed.
-    180 degrees gives the ungated `faces=` loss and gradient, bit for bit."""
-    return _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on)
+    180 degrees gives the ungated `faces=` loss and gradient, bit for bit.
+
+    visibility: None (the default: everything above, bit for bit, the same launches) or "viewpoint" - for a partial scan taken
+    from one sensor position, `scans.viewpoints` (ScanBatch(..., viewpoints=), in the model's frame like the scan).  Only the
+    model vertices that sensor sees take part: the mask of this pass is vertex_mask AND `visible_vertices(x_hat, visibility_faces,
+    scans.viewpoints, vertex_mask=, grazing_angle=)`, recomputed in every forward pass (sh_vertex_visibility) and read by the
+    searches, the loss and the gradient exactly as a given vertex_mask is - the unseen back of the model is no target and has
+    no term, so w_model_to_scan > 0 becomes usable on one-view scans.  visibility_faces: the occluding triangles (default:
+    faces, else normal_faces; one of the three is needed).  grazing_angle: None, or degrees in (0, 90] - a vertex must also face
+    the sensor to within that angle.  A body whose viewpoint row holds a NaN is a full scan: no vertex of it is hidden.  The
+    scan's own points are not tested for visibility."""
+    return _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
+                    visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
 
 
-def _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on, vertex_matches=True):
-    """`chamfer`, and what editing.register_scan may add: vertex_matches=False when the pose update will read the foot points, so
-    that a face-normal-gated pass skips the vertex search it would run for `matches` alone."""
+def _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on, vertex_matches=True,
+             visibility=None, visibility_faces=None, grazing_angle=None, vis_cache=None):
+    """`chamfer`, and what editing.fit_scan / register_scan may add: vertex_matches=False when the pose update will read the foot
+    points, so that a face-normal-gated pass skips the vertex search it would run for `matches` alone; vis_cache, a dict
+    (every=, t=0, mask=None), makes a pass reuse the last visibility mask unless t is a multiple of `every`."""
     plan = _MatchPlan("chamfer", x_hat, _check_pair(x_hat, scans, n, "chamfer"), vertex_mask, trunc, w_model_to_scan, faces, normal_angle,
-                      normal_faces, gate_on, record=matches is not None)
-    return _Chamfer.apply(x_hat, plan, matches, vertex_matches)
+                      normal_faces, gate_on, record=matches is not None, visibility=visibility, visibility_faces=visibility_faces,
+                      grazing_angle=grazing_angle)
+    if visibility is None:
+        return _Chamfer.apply(x_hat, plan, matches, vertex_matches)
+    return _Chamfer.apply(x_hat, plan, matches, vertex_matches, vis_cache)
 
 
 # ------------------------------------------------------------------------------------------------ alignment
@@ -596,6 +746,7 @@ class Pose:
     solved (0: singular, that step left the pose as it was)."""
 
     solved = None
+    visible = None                                                                      # bool [iters, B, n] on the pose `align(..., visibility=)` returns
 
     def __init__(self, A, t, scale=None):
         A = torch.as_tensor(A, dtype=torch.float32)
@@ -754,7 +905,11 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     (recorded by `chamfer` whenever it was given faces= or normal_faces=).  The step is Gauss-Newton: it minimises the linearised
     residual, so the Chamfer value is not guaranteed to fall.  solved: None, or an int32 HIP tensor [B] that receives 1 per body
     whose system was solved and 0 where it was singular to working precision (no pairs, too few, planar or parallel normals) -
-    that body's pose is left exactly as it was.  ValueError when the normals are needed and cannot be had."""
+    that body's pose is left exactly as it was.  ValueError when the normals are needed and cannot be had.
+
+    When `aligned` carries viewpoints (the batch `align(..., visibility="viewpoint")` returns does; `Pose.apply` gives none), they
+    are overwritten with the ORIGINAL `scans.viewpoints` under the new pose - the sensor moves with its scan (one more
+    sh_transform_points over [B, 1, 3])."""
     m = matches
     if step not in ("point", "plane"):
         raise ValueError("pose_update: step must be 'point' or 'plane'")
@@ -775,11 +930,14 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     ops.transform_points(scans.points, scans.counts, pose.packed, out=aligned.points)
     if scans.normals is not None and aligned.normals is not None:
         ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)
+    if scans.viewpoints is not None and aligned.viewpoints is not None:                 # only `align(..., visibility=)` gives `aligned` any
+        ops.transform_points(scans.viewpoints[:, None, :], None, pose.packed, out=aligned.viewpoints[:, None, :])
     return part
 
 
 def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
-          normal_angle=None, normal_faces=None, faces=None, cull=True, step="point", gate_on="vertices"):
+          normal_angle=None, normal_faces=None, faces=None, cull=True, step="point", gate_on="vertices", visibility=None,
+          visibility_faces=None, grazing_angle=None):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -823,7 +981,15 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     (shared with the gate's when normal_angle is given) from `faces`, or in vertex form from `normal_faces` - ValueError when
     neither is given.  The step is Gauss-Newton, without damping or line search: the logged value is not guaranteed to fall.  The
     returned pose carries `solved`, int32 [iters, B]: 0 where a body's system was singular to working precision (no kept pair, too
-    few, planar or parallel normals) - that iteration left that body's pose exactly as it was."""
+    few, planar or parallel normals) - that iteration left that body's pose exactly as it was.
+
+    visibility: None (the default: everything above, bit for bit, the same launches) or "viewpoint" - the partial-scan form of
+    `chamfer(..., visibility=)`, with visibility_faces / grazing_angle as there.  `scans.viewpoints` live in the SCAN's frame and
+    move with the pose: every iteration carries the original viewpoint through the pose so far (the sh_transform_points call
+    that moves the scan, on [B, 1, 3]) and recomputes the mask - x is fixed, the sensor moves - before the searches.  The returned
+    batch carries the viewpoints in the model's frame, and the returned pose carries `visible`, bool [iters, B, n]: row k is the
+    mask iteration k used.  With it w_model_to_scan = 1 works on one-view scans: the unseen side of the model pulls nothing.
+    The start pose `init="moments"` still takes the centroid and radius of the whole model."""
     pair = _check_pair(x, scans, n, "align")
     if mode not in ops.ALIGN_MODES:
         raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
@@ -831,7 +997,8 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     if iters < 0:
         raise ValueError("align: iters must be >= 0")
     x = x.detach()
-    plan = _MatchPlan("align", x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step)
+    plan = _MatchPlan("align", x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step,
+                      visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
     scans, B, rows, n = pair
     w, dev = plan.w, x.device
     if isinstance(init, Pose):
@@ -865,7 +1032,14 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     solved = None
     if step == "plane":
         solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=dev)
+    visible = None
+    if plan.visibility is not None:
+        aligned.viewpoints = ops.transform_points(scans.viewpoints[:, None, :], None, pose.packed)[:, 0]
+        visible = torch.empty((iters, B, n), dtype=torch.uint8, device=dev)
+        pose.visible = visible.view(torch.bool)
     for k in range(iters):
+        if visible is not None:
+            plan.see(x, aligned.viewpoints, out=visible[k], static_x=True)
         m = plan.search(x, aligned, (tn, qn, fn), (sm, sf, ms), chunks, cull, vertex_matches=False)
         plan.loss(m, scans, out=(log[k], counts))
         part = pose_update(pose, scans, aligned, m, mode, partials=part, surface=plan.surface is not None, step=step,
