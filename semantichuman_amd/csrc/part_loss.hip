@@ -247,6 +247,31 @@ int fill(PLParams& q, const float* x_rec, const float* x_gt, const float* bone, 
     return SH_OK;
 }
 
+// the part's two coordinate tables in LDS: 24 bytes a vertex, beside pairdist_fwd_kernel's 16 bytes of wave sums - a part of
+// 6826 vertices fills the 160 KiB of a compute unit exactly
+int part_lds(int max_part, size_t* smem) {
+    SH_REQUIRE(max_part > 0 && (size_t)max_part * 24 <= 160 * 1024, SH_ERR_UNSUPPORTED, "sh_part_pairdist_loss: part of %d vertices exceeds LDS", max_part);
+    *smem = (size_t)max_part * 24;
+    return SH_OK;
+}
+
+// dynamic LDS above 64 KiB needs the attribute raised once - to what the kernel's static LDS leaves of the 160 KiB: the
+// runtime refuses a limit that static and dynamic LDS together could not get
+int raise_lds(const void* kern, size_t smem, bool& attr_set, const char* what) {
+    if (smem > 65536 && !attr_set) {
+        hipFuncAttributes fa{};
+        if (hipFuncGetAttributes(&fa, kern) != hipSuccess ||
+            hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes) != hipSuccess) {
+            (void)hipGetLastError();
+            sh_set_error("%s: cannot raise the dynamic LDS limit to 160 KiB less %zu static bytes (this launch needs %zu)", what,
+                         fa.sharedSizeBytes, smem);
+            return SH_ERR_LAUNCH;
+        }
+        attr_set = true;
+    }
+    return SH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -271,12 +296,15 @@ int sh_part_pairdist_loss_fwd_grad(const float* x_rec, const float* x_gt, const 
     if (rc != SH_OK) return rc;
     SH_REQUIRE(loss && part_sum && part_cnt && workspace, SH_ERR_INVALID_ARG, "sh_part_pairdist_loss_fwd: null output");
     SH_REQUIRE(workspace_bytes >= (size_t)B * T * 2 * sizeof(float), SH_ERR_WORKSPACE, "sh_part_pairdist_loss_fwd: workspace too small");
-    SH_REQUIRE(max_part > 0 && (size_t)max_part * 24 <= 160 * 1024, SH_ERR_UNSUPPORTED, "sh_part_pairdist_loss: part of %d vertices exceeds LDS", max_part);
+    size_t smem = 0;
+    static bool attr_set = false;
+    if (const int rl = part_lds(max_part, &smem); rl != SH_OK) return rl;
+    if (const int rl = raise_lds(reinterpret_cast<const void*>(pairdist_fwd_kernel), smem, attr_set, "sh_part_pairdist_loss_fwd"); rl != SH_OK) return rl;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* partial = static_cast<float*>(workspace);
     {
         ShProfScope ps(st, "pairdist_fwd_kernel|B=%d T=%d grad=%d", B, T, grad_raw ? 1 : 0);
-        hipLaunchKernelGGL(pairdist_fwd_kernel, dim3((unsigned)(B * T)), dim3(PNT), (size_t)max_part * 24, st, q, partial, grad_raw);
+        hipLaunchKernelGGL(pairdist_fwd_kernel, dim3((unsigned)(B * T)), dim3(PNT), smem, st, q, partial, grad_raw);
     }
     hipLaunchKernelGGL(pairdist_final_kernel, dim3(1), dim3(256), 0, st, partial, tile_ptr, w_part, B, P, T, part_sum, part_cnt, loss);
     SH_CHECK_LAUNCH("part_pairdist_loss_fwd");
@@ -291,6 +319,10 @@ int sh_part_pairdist_loss_bwd(const float* x_rec, const float* x_gt, const float
     const int rc = fill(q, x_rec, x_gt, bone, scale, part_ptr, part_vert, tile_ptr, flags, w_part, B, N1, P, T, w_mode, w_threshold, relat);
     if (rc != SH_OK) return rc;
     SH_REQUIRE(part_cnt && gscale && grad, SH_ERR_INVALID_ARG, "sh_part_pairdist_loss_bwd: null pointer");
+    size_t smem = 0;
+    static bool attr_set = false;
+    if (const int rl = part_lds(max_part, &smem); rl != SH_OK) return rl;
+    if (const int rl = raise_lds(reinterpret_cast<const void*>(pairdist_bwd_kernel), smem, attr_set, "sh_part_pairdist_loss_bwd"); rl != SH_OK) return rl;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(grad, 0, (size_t)B * N1 * 3 * sizeof(float), st) != hipSuccess) {
         sh_set_error("sh_part_pairdist_loss_bwd: memset failed");
@@ -298,7 +330,7 @@ int sh_part_pairdist_loss_bwd(const float* x_rec, const float* x_gt, const float
     }
     {
         ShProfScope ps(st, "pairdist_bwd_kernel|B=%d T=%d", B, T);
-        hipLaunchKernelGGL(pairdist_bwd_kernel, dim3((unsigned)(B * T)), dim3(PNT), (size_t)max_part * 24, st, q, part_cnt, gscale, grad);
+        hipLaunchKernelGGL(pairdist_bwd_kernel, dim3((unsigned)(B * T)), dim3(PNT), smem, st, q, part_cnt, gscale, grad);
     }
     SH_CHECK_LAUNCH("part_pairdist_loss_bwd");
     return SH_OK;
