@@ -51,9 +51,58 @@ int check_steps(int n, const sh_stack_step* st, int c0, const char* what) {
     return SH_OK;
 }
 
-}  // namespace
+// What every sequencer checks first; `what` is the entry point's name, `pointers` whether its required pointers are all there.
+int check_call(int n, const sh_stack_step* st, int rows0, int c0, int B, bool pointers, const char* what) {
+    int rc = check_steps(n, st, c0, what);
+    if (rc != SH_OK) return rc;
+    if (B > 0 && (rc = check_tensor_sizes(n, st, rows0, c0, B, what)) != SH_OK) return rc;
+    SH_REQUIRE(pointers && B > 0, SH_ERR_INVALID_ARG, "%s: null pointer or empty batch", what);
+    SH_REQUIRE(n <= 64, SH_ERR_UNSUPPORTED, "%s: more than 64 steps", what);
+    return SH_OK;
+}
 
-namespace {
+// channels entering step i
+void fill_cin_of(int n, const sh_stack_step* st, int c0, int* cin_of) {
+    for (int i = 0, c = c0; i < n; ++i) { cin_of[i] = c; if (st[i].kind == 0) c = st[i].cout; }
+}
+
+// bf16 path: the fragment-ordered working copies of the conv weights (transpose: the backward-data operands; skip_first: not of step
+// 0, whose input gradient nobody wants) - every conv step has its buffer, and ONE launch fills them unless the caller did (ready)
+int prep_wfrags(int n_steps, const sh_stack_step* steps, const float* const* weights, void* const* frag, int transpose, bool skip_first,
+                bool ready, const char* what, sh_stream_t stream) {
+    const float* w[64]; void* wf[64]; int S[64], Ci[64], Co[64], tr[64];
+    int n = 0;
+    for (int i = skip_first ? 1 : 0; i < n_steps; ++i) {
+        if (steps[i].kind != 0) continue;
+        SH_REQUIRE(frag && frag[i], SH_ERR_INVALID_ARG, "%s: no weight-fragment buffer for step %d", what, i);
+        w[n] = weights[steps[i].param]; wf[n] = frag[i]; S[n] = steps[i].S; Ci[n] = steps[i].cin; Co[n] = steps[i].cout; tr[n] = transpose;
+        ++n;
+    }
+    return n && !ready ? sh_conv_wfrag_prep_multi(n, w, wf, S, Ci, Co, tr, stream) : SH_OK;
+}
+
+// The reductions of the weight-gradient slabs, deferred to the end of a backward pass: 16 layers per launch.
+struct ReduceJobs {
+    typedef int (*Reduce)(int, const void* const*, float* const*, float* const*, const int*, const int*, const int*, const int*, const int*,
+                          const int*, sh_stream_t);
+    const void* ws[64]; float* dW[64]; float* db[64]; int B[64], R[64], S[64], Ci[64], Co[64], kind[64];
+    int n = 0;
+    void add(const void* workspace, float* dw, float* dbias, int b, const sh_stack_step& s, int k) {
+        ws[n] = workspace; dW[n] = dw; db[n] = dbias; B[n] = b; R[n] = s.R; S[n] = s.S; Ci[n] = s.cin; Co[n] = s.cout; kind[n] = k;
+        ++n;
+    }
+    int flush(Reduce reduce, sh_stream_t stream) const {
+        for (int k = 0; k < n; k += 16) {
+            const int rc = reduce(n - k < 16 ? n - k : 16, ws + k, dW + k, db + k, B + k, R + k, S + k, Ci + k, Co + k, kind + k, stream);
+            if (rc != SH_OK) return rc;
+        }
+        return SH_OK;
+    }
+};
+int reduce_bf16(int n, const void* const* ws, float* const* dW, float* const* db, const int* B, const int* R, const int* S, const int* Ci,
+                const int* Co, const int*, sh_stream_t stream) {
+    return sh_spiral_conv_bwd_wgt_reduce_multi_bf16(n, ws, dW, db, B, R, S, Ci, Co, stream);
+}
 
 // ---- The kernel forms of an fp32 stack (sh_stack_plan_f32).  plan_f32 decides, for every step and both passes, which kernels run:
 // from the steps, the batch, the input layout, whether the three-plane form (SH_MMA_PLANES3) is on, keep_fp32 and the switches
@@ -186,11 +235,8 @@ int sh_stack_plan_f32(int n_steps, const sh_stack_step* steps, int c0, int B, in
 int sh_stack_forward(int n_steps, const sh_stack_step* steps, const float* x, int x_layout, int rows0, int c0, int B,
                      const float* const* weights, const float* const* biases, float* const* outs, int out_layout, int mma_mode,
                      void* const* planes, const void* const* wfrag3, int keep_fp32, sh_stream_t stream) {
-    int rc = check_steps(n_steps, steps, c0, "sh_stack_forward");
+    int rc = check_call(n_steps, steps, rows0, c0, B, x && weights && outs, "sh_stack_forward");
     if (rc != SH_OK) return rc;
-    if (B > 0 && (rc = check_tensor_sizes(n_steps, steps, rows0, c0, B, "sh_stack_forward")) != SH_OK) return rc;
-    SH_REQUIRE(x && weights && outs && B > 0, SH_ERR_INVALID_ARG, "sh_stack_forward: null pointer or empty batch");
-    SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_forward: more than 64 steps");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_stack_forward: unknown mma_mode %d", mma_mode);
     SH_REQUIRE(keep_fp32 >= 0 && keep_fp32 <= 2, SH_ERR_INVALID_ARG, "sh_stack_forward: keep_fp32 = %d (0, 1 or 2)", keep_fp32);
     Forms f[64];
@@ -244,11 +290,8 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                       const size_t* workspace_bytes, float* const* dW, float* const* dbias, int need_x_grad, int mma_mode,
                       void* const* gin_planes, void* dpre_last_planes, const void* const* wfrag3_t, const void* const* in_planes,
                       int acts_fp32, sh_stream_t stream) {
-    int rc = check_steps(n_steps, steps, c0, "sh_stack_backward");
+    int rc = check_call(n_steps, steps, rows0, c0, B, x && acts && g && weights && gin && dW, "sh_stack_backward");
     if (rc != SH_OK) return rc;
-    if (B > 0 && (rc = check_tensor_sizes(n_steps, steps, rows0, c0, B, "sh_stack_backward")) != SH_OK) return rc;
-    SH_REQUIRE(x && acts && g && weights && gin && dW && B > 0, SH_ERR_INVALID_ARG, "sh_stack_backward: null pointer or empty batch");
-    SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_backward: more than 64 steps");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_stack_backward: unknown mma_mode %d", mma_mode);
     const bool planes3 = mma_mode == SH_MMA_PLANES3 && gin_planes && wfrag3_t;
     SH_REQUIRE(acts_fp32 == 1 || (acts_fp32 == 2 && planes3 && in_planes), SH_ERR_INVALID_ARG,
@@ -265,11 +308,8 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                    "sh_stack_backward: step %d reads the image of its input: in_planes[%d] is NULL", i, i);
     }
     const Switches& sw = switches();
-    int cin_of[64];                                            // channels entering step i
-    {
-        int c = c0;
-        for (int i = 0; i < n_steps; ++i) { cin_of[i] = c; if (steps[i].kind == 0) c = steps[i].cout; }
-    }
+    int cin_of[64];
+    fill_cin_of(n_steps, steps, c0, cin_of);
     // all weight transposes of the stack (backward-data on planes reads fragments instead): workgroups of the launch that opens the
     // pass (the last step's activation backward), or a launch of their own when the pass opens with a re-sampling step
     const float* tr_w[32]; float* tr_wt[32]; int tr_S[32], tr_Ci[32], tr_Co[32];
@@ -307,8 +347,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
             cur = g; cl = lay(out_layout, s.m_rows, B, cin_of[last]);
         }
     }
-    const void* job_ws[64]; float* job_dW[64]; float* job_db[64]; int jB[64], jR[64], jS[64], jCi[64], jCo[64], jK[64];
-    int njobs = 0;
+    ReduceJobs jobs;
     for (int i = last; i >= 0; --i) {
         const sh_stack_step& s = steps[i];
         const Forms& q = f[i];
@@ -374,11 +413,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
                 }
                 if (rc != SH_OK) return rc;
             }
-            if (wgrad) {
-                job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
-                jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout; jK[njobs] = p3w ? 2 : 0;
-                ++njobs;
-            }
+            if (wgrad) jobs.add(workspace[i], dW[s.param], dbias ? dbias[s.param] : nullptr, B, s, p3w ? 2 : 0);
             if (want_in) {
                 SH_REQUIRE(s.table_t, SH_ERR_INVALID_ARG, "sh_stack_backward: step %d has no transposed table", i);
                 float* mut = const_cast<float*>(cur);          // the extra rows behind the R real ones of this step's own buffer
@@ -437,12 +472,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
         }
         if (want_in) { cur = gi; cl = gl; cur_img = gi_img; cur_img_done = gi_img_done; }
     }
-    for (int k = 0; k < njobs; k += 16) {
-        const int n = njobs - k < 16 ? njobs - k : 16;
-        rc = sh_spiral_conv_bwd_wgt_reduce_multi_kinds(n, job_ws + k, job_dW + k, job_db + k, jB + k, jR + k, jS + k, jCi + k, jCo + k, jK + k, stream);
-        if (rc != SH_OK) return rc;
-    }
-    return SH_OK;
+    return jobs.flush(sh_spiral_conv_bwd_wgt_reduce_multi_kinds, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -454,25 +484,10 @@ static inline long esz_of(int dtype) { return dtype == SH_DTYPE_BF16 ? 2 : 4; }
 int sh_stack_forward_bf16(int n_steps, const sh_stack_step* steps, const void* x, int x_dtype, int x_layout, int rows0, int c0, int B,
                           const float* const* weights, const float* const* biases, void* const* wfrag, int wfrag_ready,
                           void* const* outs, int out_dtype, int out_layout, sh_stream_t stream) {
-    int rc = check_steps(n_steps, steps, c0, "sh_stack_forward_bf16");
+    int rc = check_call(n_steps, steps, rows0, c0, B, x && weights && outs && wfrag, "sh_stack_forward_bf16");
     if (rc != SH_OK) return rc;
-    if (B > 0 && (rc = check_tensor_sizes(n_steps, steps, rows0, c0, B, "sh_stack_forward_bf16")) != SH_OK) return rc;
-    SH_REQUIRE(x && weights && outs && wfrag && B > 0, SH_ERR_INVALID_ARG, "sh_stack_forward_bf16: null pointer or empty batch");
-    SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_forward_bf16: more than 64 steps");
-    {
-        const float* w[64]; void* wf[64]; int S[64], Ci[64], Co[64], tr[64];
-        int n = 0;
-        for (int i = 0; i < n_steps; ++i) {
-            if (steps[i].kind != 0) continue;
-            SH_REQUIRE(wfrag[i], SH_ERR_INVALID_ARG, "sh_stack_forward_bf16: no weight-fragment buffer for step %d", i);
-            w[n] = weights[steps[i].param]; wf[n] = wfrag[i]; S[n] = steps[i].S; Ci[n] = steps[i].cin; Co[n] = steps[i].cout; tr[n] = 0;
-            ++n;
-        }
-        if (n && !wfrag_ready) {
-            rc = sh_conv_wfrag_prep_multi(n, w, wf, S, Ci, Co, tr, stream);
-            if (rc != SH_OK) return rc;
-        }
-    }
+    rc = prep_wfrags(n_steps, steps, weights, wfrag, 0, false, wfrag_ready != 0, "sh_stack_forward_bf16", stream);
+    if (rc != SH_OK) return rc;
     const void* cur = x;
     int cd = x_dtype;
     Lay cl = lay(x_layout, rows0, B, c0);
@@ -511,31 +526,14 @@ int sh_stack_backward_bf16(int n_steps, const sh_stack_step* steps, const void* 
                            void* const* gin, int gx_dtype, void* dpre_last, void* const* wfrag_t, int wfrag_ready,
                            void* const* workspace, const size_t* workspace_bytes, float* const* dW, float* const* dbias, int need_x_grad,
                            sh_stream_t stream) {
-    int rc = check_steps(n_steps, steps, c0, "sh_stack_backward_bf16");
+    int rc = check_call(n_steps, steps, rows0, c0, B, x && acts && g && weights && gin && dW, "sh_stack_backward_bf16");
     if (rc != SH_OK) return rc;
-    if (B > 0 && (rc = check_tensor_sizes(n_steps, steps, rows0, c0, B, "sh_stack_backward_bf16")) != SH_OK) return rc;
-    SH_REQUIRE(x && acts && g && weights && gin && dW && B > 0, SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: null pointer or empty batch");
-    SH_REQUIRE(n_steps <= 64, SH_ERR_UNSUPPORTED, "sh_stack_backward_bf16: more than 64 steps");
     const int last = n_steps - 1;
     int cin_of[64];
-    {
-        int c = c0;
-        for (int i = 0; i < n_steps; ++i) { cin_of[i] = c; if (steps[i].kind == 0) c = steps[i].cout; }
-    }
-    {   // backward-data operands of all conv steps: one conversion launch
-        const float* w[64]; void* wf[64]; int S[64], Ci[64], Co[64], tr[64];
-        int n = 0;
-        for (int i = 0; i < n_steps; ++i) {
-            if (steps[i].kind != 0 || !(i > 0 || need_x_grad)) continue;
-            SH_REQUIRE(wfrag_t && wfrag_t[i], SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: no weight-fragment buffer for step %d", i);
-            w[n] = weights[steps[i].param]; wf[n] = wfrag_t[i]; S[n] = steps[i].S; Ci[n] = steps[i].cin; Co[n] = steps[i].cout; tr[n] = 1;
-            ++n;
-        }
-        if (n && !wfrag_ready) {
-            rc = sh_conv_wfrag_prep_multi(n, w, wf, S, Ci, Co, tr, stream);
-            if (rc != SH_OK) return rc;
-        }
-    }
+    fill_cin_of(n_steps, steps, c0, cin_of);
+    // backward-data operands of all conv steps: one conversion launch
+    rc = prep_wfrags(n_steps, steps, weights, wfrag_t, 1, !need_x_grad, wfrag_ready != 0, "sh_stack_backward_bf16", stream);
+    if (rc != SH_OK) return rc;
     const void* cur; Lay cl; int cd;
     {
         const sh_stack_step& s = steps[last];
@@ -555,8 +553,7 @@ int sh_stack_backward_bf16(int n_steps, const sh_stack_step* steps, const void* 
             cur = g; cl = lay(out_layout, s.m_rows, B, cin_of[last]); cd = out_dtype;
         }
     }
-    const void* job_ws[64]; float* job_dW[64]; float* job_db[64]; int jB[64], jR[64], jS[64], jCi[64], jCo[64];
-    int njobs = 0;
+    ReduceJobs jobs;
     for (int i = last; i >= 0; --i) {
         const sh_stack_step& s = steps[i];
         const bool want_in = i > 0 || need_x_grad;
@@ -585,11 +582,7 @@ int sh_stack_backward_bf16(int n_steps, const sh_stack_step* steps, const void* 
                                                  s.R, s.S, s.cin, s.cout, stream);
                 if (rc != SH_OK) return rc;
             }
-            if (wgrad) {
-                job_ws[njobs] = workspace[i]; job_dW[njobs] = dW[s.param]; job_db[njobs] = dbias ? dbias[s.param] : nullptr;
-                jB[njobs] = B; jR[njobs] = s.R; jS[njobs] = s.S; jCi[njobs] = s.cin; jCo[njobs] = s.cout;
-                ++njobs;
-            }
+            if (wgrad) jobs.add(workspace[i], dW[s.param], dbias ? dbias[s.param] : nullptr, B, s, 0);
             if (want_in) {
                 SH_REQUIRE(s.table_t, SH_ERR_INVALID_ARG, "sh_stack_backward_bf16: step %d has no transposed table", i);
                 // backward-data over ragged source lists (round 6): every source a real row of dpre - neither the pre-sum launches nor
@@ -637,12 +630,7 @@ int sh_stack_backward_bf16(int n_steps, const sh_stack_step* steps, const void* 
         }
         if (want_in) { cur = gi; cl = gl; cd = gd; }
     }
-    for (int k = 0; k < njobs; k += 16) {
-        const int n = njobs - k < 16 ? njobs - k : 16;
-        rc = sh_spiral_conv_bwd_wgt_reduce_multi_bf16(n, job_ws + k, job_dW + k, job_db + k, jB + k, jR + k, jS + k, jCi + k, jCo + k, stream);
-        if (rc != SH_OK) return rc;
-    }
-    return SH_OK;
+    return jobs.flush(reduce_bf16, stream);
 }
 
 }  // extern "C"

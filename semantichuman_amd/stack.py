@@ -16,10 +16,15 @@ The reference runs encode/decode as a Python loop of small autograd ops
 
 Plan construction is pure numpy (testable without a GPU); `to(device)` uploads the tables.
 
-The launches of a stack are issued by ONE library call each way (`sh_stack_forward` / `sh_stack_backward`,
-csrc/stack_exec.hip) into buffers carved out of one arena per pass: issued call by call from Python
-(`run_forward` / `run_backward` below, kept for the side-stream experiments and as the cross-check of the native
-sequencing, SH_STACK_NATIVE=0) a launch costs ~25 us of host time, which made the host pace an eagerly
+The launches of a stack are issued by ONE library call each way (`sh_stack_forward` / `sh_stack_backward` and their
+`_bf16` twins, csrc/stack_exec.hip) into buffers carved out of one arena per pass.  Where each buffer lives is a `Plan`:
+one routine (`Stack._layout`) lays out what the fp32 and the bf16 path share - every offset in bytes, 256-byte aligned -
+from the element sizes and the per-path sizes of the weight operands and workspaces; the bf16 path adds its forward
+weight fragments to the forward arena, the fp32 path its three-plane arenas (`Stack._layout_p3`, driven by the library's
+plan of the kernel forms).  The helpers in front of `Stack` turn a plan into the pointer arrays of a call.
+
+Issued call by call from Python (`run_forward` / `run_backward` below, kept for the side-stream experiments and as the
+cross-check of the native sequencing, SH_STACK_NATIVE=0) a launch costs ~25 us of host time, which made the host pace an eagerly
 launched step (1.2 ms of host time per step against 1.85 ms of GPU time, and more than that with gradient
 collectives in the loop).
 """
@@ -45,11 +50,11 @@ _P3_RAGGED = os.environ.get("SH_P3_RAGGED", "1").strip() != "0"
 # rows of an earlier, identical step.
 DEBUG_POISON = os.environ.get("SH_DEBUG_POISON", "0").strip() == "1"
 _P3_GROUPED = os.environ.get("SH_P3_GROUPED", "1").strip() != "0"
-_ALIGN = 64                       # floats: every carved buffer starts 256-byte aligned (16-byte vector accesses)
+_ALIGN_BYTES = 256                # where every carved buffer starts, and the least that is allocated (16-byte vector accesses)
 
 
-def _round(n: int) -> int:
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+def _align(nbytes) -> int:
+    return -(-int(nbytes) // _ALIGN_BYTES) * _ALIGN_BYTES
 
 # Side-stream options, both OFF: measured on MI355X, concurrency between these kernels only re-orders MFMA/HBM-saturated
 # work and pays for the fork/join.
@@ -217,6 +222,72 @@ def mark_dead_dummy(steps, input_dummy_dead: bool = False):
     return steps
 
 
+class Plan:
+    """Where every buffer of a stack lives for one batch size.  `*_off` / `*_total`: bytes from the start of an arena, aligned
+    (`_align`); per step (dW / db: per parameter index) a uint64 array, with a mask that is 1 where the step has that buffer."""
+    __slots__ = (
+        "out_rows", "out_ch", "npar", "shapes",          # shapes: per parameter index (cout, S * cin), None for an unused index
+        "conv_mask",                                     # 1 for a conv step: it has wt, ws and (bf16) wf
+        "f_off", "f_total", "wf_off",                    # forward arena: step outputs | bf16 path: forward weight fragments
+        "dpre_last_off", "g_off", "g_mask", "wt_off", "ws_off", "ws_bytes", "b_total",      # backward arena
+        "dW_off", "db_off", "p_total",                   # the flat fp32 tensor of the parameter gradients
+        # fp32 path, three-plane form: images of the forward buffers (in_img: 1 where the backward pass reads the image of the step's
+        # input) | images of the gradients (dpl: the last step's) | weight fragments, wf3_jobs: (step, transpose, offset) of each
+        "pl_off", "pl_mask", "pl_total", "in_img", "gpl_off", "gpl_mask", "dpl_off", "dpl_mask", "gpl_total",
+        "wf3_off", "wf3_mask", "wf3t_off", "wf3t_mask", "wf3_jobs", "wf3_total")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        assert not fields, fields
+
+
+# ---- what the four native_* methods share in turning a plan into the pointer arrays of one call
+_DTYPE_NAME = {torch.float32: "fp32", torch.bfloat16: "bf16"}
+
+
+def _check_input(x, dtypes):
+    if not (x.is_contiguous() and x.dtype in dtypes):
+        raise ValueError("expected a contiguous %s 3-D tensor, got %s %s" % (" / ".join(_DTYPE_NAME[d] for d in dtypes), tuple(x.shape), x.dtype))
+    if x.numel() >= 2 ** 32:
+        raise RuntimeError("semantichuman_amd: gathered tensors are addressed with 32-bit element offsets; "
+                           "%d elements is too large - split the batch" % x.numel())
+
+
+def _bind(base: int, off, mask):
+    """Device pointers (uint64 array): base + off where the mask is 1, NULL elsewhere."""
+    return (off + np.uint64(base)) * mask
+
+
+def _step_outputs(plan: Plan, arena, out):
+    """Where every step's output lives: the inner steps' in the forward arena, the last one's in `out`."""
+    p = plan.f_off + np.uint64(arena.data_ptr())
+    p[-1] = out.data_ptr()
+    return p
+
+
+def _bind_param_grads(plan: Plan, flat, weights, need_bias, frozen):
+    """-> (frozen as a list, dW pointers, db pointers) per parameter index: NULL for a frozen layer's dW and an unwanted db."""
+    assert len(need_bias) == plan.npar == len(weights)
+    frozen = list(frozen) if frozen else [False] * plan.npar
+    assert not any(f and nb for f, nb in zip(frozen, need_bias))
+    return (frozen, _bind(flat.data_ptr(), plan.dW_off, np.array([0 if f else 1 for f in frozen], dtype=np.uint64)),
+            _bind(flat.data_ptr(), plan.db_off, np.array([1 if nb else 0 for nb in need_bias], dtype=np.uint64)))
+
+
+def _param_grad_views(plan: Plan, flat, frozen, need_bias):
+    """{parameter index: (dW, db or None)}: views of the flat fp32 gradient tensor."""
+    grads = {}
+    for j, shp in enumerate(plan.shapes):
+        if shp is None or frozen[j]:
+            continue
+        o = int(plan.dW_off[j]) // 4
+        dWj = flat[o:o + shp[0] * shp[1]].view(shp)
+        o = int(plan.db_off[j]) // 4
+        grads[j] = (dWj, flat[o:o + shp[0]] if need_bias[j] else None)
+    return grads
+
+
 class Stack:
     def __init__(self, steps, input_dummy_dead: bool = False):
         fold_identity_rows(steps)
@@ -292,121 +363,145 @@ class Stack:
                                                  keep_fp32, 1 if need_x_grad else 0, out.ctypes.data), "sh_stack_plan_f32")
         return out
 
-    def _plan(self, B: int, c0: int):
-        """Buffer sizes / arena offsets (in floats) for batch B; cached."""
-        key = (B, c0)
+    def _plan(self, B: int, c0: int, bf16: bool = False, out_is_f32: bool = True) -> Plan:
+        """The buffer plan for batch B, cached.  bf16: the bf16 compute path - tensors between the steps are bf16, the last step's
+        pre-activation gradient has the output's type (out_is_f32), and both arenas hold fragment-ordered bf16 working copies of
+        the conv weights.  The type of the stack's INPUT moves nothing (its gradient is a tensor of its own), so it is no key."""
+        key = (B, c0, bf16, out_is_f32)
         plans = self.__dict__.setdefault("_plans", {})
-        if key in plans:
-            return plans[key]
-        lib = _lib.load()
-        n = len(self.steps)
+        if key not in plans:
+            lib = _lib.load()
+            if bf16:
+                plans[key] = self._layout(
+                    B, c0, 2, 4 if out_is_f32 else 2, wt_bytes=lambda st: lib.sh_conv_wfrag_bytes(st.S, st.cout, st.cin),
+                    ws_bytes=lambda st: lib.sh_spiral_conv_bwd_wgt_workspace_bf16(B, st.R, st.S, st.cin, st.cout),
+                    wf_bytes=lambda st: lib.sh_conv_wfrag_bytes(st.S, st.cin, st.cout))
+            else:
+                # (room for either plan of the step's partial slabs: the fp32 kernels' or the three-plane weight gradient's)
+                plans[key] = self._layout_p3(self._layout(
+                    B, c0, 4, 4, wt_bytes=lambda st: st.cin * st.S * st.cout * 4,
+                    ws_bytes=lambda st: max(int(lib.sh_spiral_conv_bwd_wgt_workspace(B, st.R, st.S, st.cin, st.cout)),
+                                            int(lib.sh_spiral_conv_bwd_wgt_p3_workspace(B, st.R, st.S, st.cin, st.cout)))), B, c0)
+        return plans[key]
+
+    def _layout(self, B: int, c0: int, esz: int, esz_last: int, wt_bytes, ws_bytes, wf_bytes=None) -> Plan:
+        """What both paths share, laid out once.  esz: element size of the tensors between steps, esz_last: of the last step's
+        pre-activation gradient; per conv step, wt_bytes(step): the size of its backward-data operand, ws_bytes(step): of its
+        weight-gradient workspace, wf_bytes(step): of its forward operand where that lives in the forward arena (None: not there)."""
+        steps, n = self.steps, len(self.steps)
+        zeros = lambda k=n: np.zeros(k, dtype=np.uint64)              # noqa: E731
         cin_of, c = [], c0
-        for st in self.steps:
+        for st in steps:
             cin_of.append(c)
             c = st.cout if st.kind == "conv" else c
-        out_rows = [st.R if st.kind == "conv" else st.csr.rows for st in self.steps]
-        out_ch = [st.cout if st.kind == "conv" else cin_of[i] for i, st in enumerate(self.steps)]
+        out_rows = [st.R if st.kind == "conv" else st.csr.rows for st in steps]
+        out_ch = [st.cout if st.kind == "conv" else cin_of[i] for i, st in enumerate(steps)]
         # forward arena: outputs of all steps but the last
-        f_off, o = np.zeros(n, dtype=np.uint64), 0
+        f_off, o = zeros(), 0
         for i in range(n - 1):
             if self._extends(i):                       # appends its rows to the previous step's buffer
                 f_off[i] = f_off[i - 1]
                 continue
             f_off[i] = o
-            o += _round(self._buffer_rows(i) * B * out_ch[i])
+            o += _align(self._buffer_rows(i) * B * out_ch[i] * esz)
+        conv = [i for i, st in enumerate(steps) if st.kind == "conv"]
+        conv_mask = zeros()
+        conv_mask[conv] = 1
+        wf_off = None
+        if wf_bytes is not None:
+            wf_off = zeros()
+            for i in conv:
+                wf_off[i] = o
+                o += _align(wf_bytes(steps[i]))
         f_total = o
         # backward arena: dpre of the last step | two alternating regions for the input-gradient chain | weight_t | slabs
-        last = self.steps[-1]
-        o = 0
-        dpre_last_off = 0
+        last = steps[-1]
+        dpre_last_off, o = 0, 0
         if last.kind == "conv":
-            o += _round((last.R + last.n_extra) * B * last.cout)
+            o += _align((last.R + last.n_extra) * B * last.cout * esz_last)
         gin_size = [0] * n
         for i in range(1, n):
-            st, prev = self.steps[i], self.steps[i - 1]
+            st, prev = steps[i], steps[i - 1]
             rows_in = st.n_in if st.kind == "conv" else st.csr.cols
-            gin_size[i] = (rows_in + (prev.n_extra if prev.kind == "conv" else 0)) * B * cin_of[i]
-        region = [_round(max([gin_size[i] for i in range(1, n) if i % 2 == par] + [0])) for par in (0, 1)]
+            gin_size[i] = (rows_in + (prev.n_extra if prev.kind == "conv" else 0)) * B * cin_of[i] * esz
+        region = [_align(max([gin_size[i] for i in range(1, n) if i % 2 == par] + [0])) for par in (0, 1)]
         region_off = [o, o + region[0]]
         o += region[0] + region[1]
-        g_off = np.zeros(n, dtype=np.uint64)
-        g_mask = np.zeros(n, dtype=np.uint64)
+        g_off, g_mask = zeros(), zeros()
         for i in range(1, n):
             g_off[i], g_mask[i] = region_off[i % 2], 1
-        wt_off, wt_mask = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-        ws_off, ws_mask, ws_bytes = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-        for i, st in enumerate(self.steps):
-            if st.kind != "conv":
-                continue
-            wt_off[i], wt_mask[i] = o, 1
-            o += _round(st.cin * st.S * st.cout)
-            # (room for either plan of the step's partial slabs: the fp32 kernels' or the three-plane weight gradient's)
-            nb = max(int(lib.sh_spiral_conv_bwd_wgt_workspace(B, st.R, st.S, st.cin, st.cout)),
-                     int(lib.sh_spiral_conv_bwd_wgt_p3_workspace(B, st.R, st.S, st.cin, st.cout)))
-            ws_off[i], ws_mask[i], ws_bytes[i] = o, 1, nb
-            o += _round((nb + 3) // 4)
+        wt_off, ws_off, ws_nb = zeros(), zeros(), zeros()
+        for i in conv:
+            wt_off[i] = o
+            o += _align(wt_bytes(steps[i]))
+            ws_off[i], ws_nb[i] = o, int(ws_bytes(steps[i]))
+            o += _align(ws_nb[i])
         b_total = o
-        # gradients of the parameters: one flat tensor, dW then dbias per parameter index
-        npar = 1 + max([st.param for st in self.steps if st.kind == "conv"], default=-1)
-        dW_off, db_off, shapes, o = np.zeros(npar, dtype=np.uint64), np.zeros(npar, dtype=np.uint64), [None] * npar, 0
-        for st in self.steps:
-            if st.kind != "conv":
-                continue
+        # gradients of the parameters: one flat fp32 tensor, dW then dbias per parameter index
+        npar = 1 + max([steps[i].param for i in conv], default=-1)
+        dW_off, db_off, shapes, o = zeros(npar), zeros(npar), [None] * npar, 0
+        for st in (steps[i] for i in conv):
             dW_off[st.param] = o
-            o += _round(st.cout * st.S * st.cin)
+            o += _align(st.cout * st.S * st.cin * 4)
             db_off[st.param] = o
-            o += _round(st.cout)
+            o += _align(st.cout * 4)
             shapes[st.param] = (st.cout, st.S * st.cin)
-        # three-plane form (SH_MMA_PLANES3): byte offsets of the plane images of the forward buffers (one arena), of the gradient
-        # buffers (another; no aliasing - 288 GB) and of the weight fragments (forward and backward-data operand, one buffer
-        # filled by ONE conversion launch per forward pass) - where the library's plan of the stack's kernel forms has them
-        # (sh_stack_plan_f32; planned for a pass that wants the input gradient, which needs a superset of the buffers)
+        return Plan(out_rows=out_rows, out_ch=out_ch, npar=npar, shapes=shapes, conv_mask=conv_mask, f_off=f_off, f_total=f_total,
+                    wf_off=wf_off, dpre_last_off=dpre_last_off, g_off=g_off, g_mask=g_mask, wt_off=wt_off, ws_off=ws_off, ws_bytes=ws_nb,
+                    b_total=b_total, dW_off=dW_off, db_off=db_off, p_total=o)
+
+    def _layout_p3(self, plan: Plan, B: int, c0: int):
+        """fp32 path, three-plane form (SH_MMA_PLANES3): the plane images of the forward buffers (one arena), of the gradient
+        buffers (another; no aliasing - 288 GB) and the weight fragments (forward and backward-data operand, one buffer
+        filled by ONE conversion launch per forward pass) - where the library's plan of the stack's kernel forms has them
+        (sh_stack_plan_f32; planned for a pass that wants the input gradient, which needs a superset of the buffers)."""
+        lib = _lib.load()
+        n, last, out_ch = len(self.steps), self.steps[-1], plan.out_ch
+        zeros = lambda: np.zeros(n, dtype=np.uint64)                   # noqa: E731
         forms = self.forms(B, c0, "planes3")
         has = lambda i, name: bool(forms[i] & _lib.FORM[name])         # noqa: E731
-        al = lambda nbytes: (int(nbytes) + 255) // 256 * 256          # noqa: E731
-        pl_off, pl_mask, o3 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), 0
+        pl_off, pl_mask, o3 = zeros(), zeros(), 0
         for i in range(n - 1):
             if self._extends(i):
                 pl_off[i], pl_mask[i] = pl_off[i - 1], pl_mask[i - 1]
             elif has(i, "fwd_img"):
                 pl_off[i], pl_mask[i] = o3, 1
-                o3 += al(lib.sh_p3_bytes(self._buffer_rows(i), B, out_ch[i]))
-        pl_total = o3
+                o3 += _align(lib.sh_p3_bytes(self._buffer_rows(i), B, out_ch[i]))
+        plan.pl_off, plan.pl_mask, plan.pl_total = pl_off, pl_mask, o3
         # the images of step inputs the backward pass reads (in_planes)
-        in_img = np.array([1 if forms[i] & (_lib.FORM["bwd_p3w"] | _lib.FORM["bwd_yimg"]) else 0 for i in range(n)], dtype=np.uint64)
-        gpl_off, gpl_mask, o3 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), 0
+        plan.in_img = np.array([1 if forms[i] & (_lib.FORM["bwd_p3w"] | _lib.FORM["bwd_yimg"]) else 0 for i in range(n)], dtype=np.uint64)
+        gpl_off, gpl_mask, o3 = zeros(), zeros(), 0
         for i in range(1, n):
             prev = self.steps[i - 1]
             if has(i - 1, "bwd_gimg"):
                 gpl_off[i], gpl_mask[i] = o3, 1
-                o3 += al(lib.sh_p3_bytes(prev.R + prev.n_extra, B, prev.cout))
-        dpl_off, dpl_mask = 0, 0
+                o3 += _align(lib.sh_p3_bytes(prev.R + prev.n_extra, B, prev.cout))
+        plan.dpl_off, plan.dpl_mask = 0, 0
         if has(n - 1, "bwd_gimg"):
-            dpl_off, dpl_mask = o3, 1
-            o3 += al(lib.sh_p3_bytes(last.R + last.n_extra, B, last.cout))
-        gpl_total = o3
-        wf3_off, wf3_mask, wf3t_off, wf3t_mask = (np.zeros(n, dtype=np.uint64) for _ in range(4))
+            plan.dpl_off, plan.dpl_mask = o3, 1
+            o3 += _align(lib.sh_p3_bytes(last.R + last.n_extra, B, last.cout))
+        plan.gpl_off, plan.gpl_mask, plan.gpl_total = gpl_off, gpl_mask, o3
+        wf3_off, wf3_mask, wf3t_off, wf3t_mask = zeros(), zeros(), zeros(), zeros()
         o3 = 0
         wf3_jobs = []                                                  # (step index, transpose, byte offset)
         for i, st in enumerate(self.steps):
             if has(i, "fwd_p3"):
                 wf3_off[i], wf3_mask[i] = o3, 1
                 wf3_jobs.append((i, 0, o3))
-                o3 += al(lib.sh_conv_wfrag3_bytes(st.S, st.cin, st.cout))
+                o3 += _align(lib.sh_conv_wfrag3_bytes(st.S, st.cin, st.cout))
             if has(i, "bwd_gimg"):
                 wf3t_off[i], wf3t_mask[i] = o3, 1
                 wf3_jobs.append((i, 1, o3))
-                o3 += al(lib.sh_conv_wfrag3_bytes(st.S, st.cout, st.cin))
-        wf3_total = o3
-        plan = dict(pl_off=pl_off, pl_mask=pl_mask, pl_total=pl_total, in_img=in_img, gpl_off=gpl_off, gpl_mask=gpl_mask, dpl_off=dpl_off,
-                    dpl_mask=dpl_mask, gpl_total=gpl_total, wf3_off=wf3_off, wf3_mask=wf3_mask, wf3t_off=wf3t_off,
-                    wf3t_mask=wf3t_mask, wf3_jobs=wf3_jobs, wf3_total=wf3_total,
-                    f_off=f_off * 4, f_total=f_total, dpre_last_off=dpre_last_off, g_off=g_off * 4, g_mask=g_mask,
-                    wt_off=wt_off * 4, wt_mask=wt_mask, ws_off=ws_off * 4, ws_mask=ws_mask, ws_bytes=ws_bytes, b_total=b_total,
-                    dW_off=dW_off * 4, db_off=db_off * 4, dW_off_f=dW_off, db_off_f=db_off, shapes=shapes, p_total=o, npar=npar,
-                    out_rows=out_rows, out_ch=out_ch)
-        plans[key] = plan
+                o3 += _align(lib.sh_conv_wfrag3_bytes(st.S, st.cout, st.cin))
+        plan.wf3_off, plan.wf3_mask, plan.wf3t_off, plan.wf3t_mask = wf3_off, wf3_mask, wf3t_off, wf3t_mask
+        plan.wf3_jobs, plan.wf3_total = wf3_jobs, o3
         return plan
+
+    @staticmethod
+    def _io_dims(x, layout):
+        B = x.shape[0] if layout == "bm" else x.shape[1]
+        rows = x.shape[1] if layout == "bm" else x.shape[0]
+        return B, rows, x.shape[2]
 
     @staticmethod
     def _ptr_array(tensors):
@@ -415,33 +510,26 @@ class Stack:
     def _p3_prepare(self, plan, weights, with_backward: bool, device):
         """Three-plane form: the image arena of the forward buffers and the weight fragments - this stack's own conversion
         launch, unless `prepare_p3_frags` already converted them together with other stacks' (one launch per training step)."""
-        planes = torch.empty(max(256, plan["pl_total"]), dtype=torch.uint8, device=device)
+        planes = torch.empty(max(_ALIGN_BYTES, plan.pl_total), dtype=torch.uint8, device=device)
         pre = self.__dict__.pop("_p3_next", None)
         if pre is not None and pre[2] == id(plan) and (pre[3] or not with_backward):
             return planes, pre[0], pre[1]
-        wf3 = torch.empty(max(256, plan["wf3_total"]), dtype=torch.uint8, device=device)
+        wf3 = torch.empty(max(_ALIGN_BYTES, plan.wf3_total), dtype=torch.uint8, device=device)
         convert_p3_frags([(self, plan, weights, wf3, 0)], with_backward)
         return planes, wf3, 0
 
     def native_forward(self, x, in_layout, out_layout, weights, biases, mma: str = "exact", with_backward: bool = False, frozen=None):
         """-> (output, arena holding the outputs of the inner steps, three-plane state or None).
         frozen: per parameter index, True = the backward pass will not compute that layer's weight gradient (None: none)."""
-        B = x.shape[0] if in_layout == "bm" else x.shape[1]
-        rows0 = x.shape[1] if in_layout == "bm" else x.shape[0]
-        c0 = x.shape[2]
-        if not (x.is_contiguous() and x.dtype == torch.float32):
-            raise ValueError("expected a contiguous fp32 3-D tensor, got %s %s" % (tuple(x.shape), x.dtype))
-        if x.numel() >= 2 ** 32:
-            raise RuntimeError("semantichuman_amd: gathered tensors are addressed with 32-bit element offsets; "
-                               "%d elements is too large - split the batch" % x.numel())
+        B, rows0, c0 = self._io_dims(x, in_layout)
+        _check_input(x, (torch.float32,))
         plan = self._plan(B, c0)
         n = len(self.steps)
-        arena = torch.empty(max(1, plan["f_total"]), dtype=torch.float32, device=x.device)
+        arena = torch.empty(max(1, plan.f_total // 4), dtype=torch.float32, device=x.device)
         if DEBUG_POISON:
             arena.fill_(float("nan"))
-        out = ops.alloc(B, plan["out_rows"][-1], plan["out_ch"][-1], out_layout, x.device)
-        outs = plan["f_off"] + np.uint64(arena.data_ptr())
-        outs[n - 1] = out.data_ptr()
+        out = ops.alloc(B, plan.out_rows[-1], plan.out_ch[-1], out_layout, x.device)
+        outs = _step_outputs(plan, arena, out)
         p3 = None
         keep = 1 if with_backward else 0
         # a frozen layer's backward pass reads the fp32 rows of its input (no plane weight gradient): keep_fp32 == 1, and the image
@@ -449,18 +537,18 @@ class Stack:
         any_frozen = bool(frozen) and any(frozen)
         any_trained = not frozen or not all(frozen)
         planes_p = wf3_p = None
-        if mma == "planes3" and plan["wf3_total"]:
+        if mma == "planes3" and plan.wf3_total:
             planes, wf3, wbase = self._p3_prepare(plan, weights, with_backward, x.device)
             # what the backward pass needs of this: the weight fragments - and, since round 6, the image arena of the forward
             # activations (6 bytes per element) where the plan has the backward pass read a step's input through its image (the
             # three-plane weight gradient, csrc/wgrad_p3.hip; none with SH_P3_WGRAD=0)
-            p3 = (planes if (with_backward and any_trained and plan["in_img"].any()) else None, wf3, wbase)
+            p3 = (planes if (with_backward and any_trained and plan.in_img.any()) else None, wf3, wbase)
             # ... and with the images kept, the fp32 rows that neither pass reads are not written (sh_stack_forward keep_fp32 == 2;
             # SH_P3_DROP_FP32=0: every row, as before)
             if p3[0] is not None and not any_frozen:
                 keep = 2
-            pl = (plan["pl_off"] + np.uint64(planes.data_ptr())) * plan["pl_mask"]
-            wf = (plan["wf3_off"] + np.uint64(wf3.data_ptr() + wbase)) * plan["wf3_mask"]
+            pl = _bind(planes.data_ptr(), plan.pl_off, plan.pl_mask)
+            wf = _bind(wf3.data_ptr() + wbase, plan.wf3_off, plan.wf3_mask)
             planes_p, wf3_p = pl.ctypes.data, wf.ctypes.data
         _lib.check(_lib.load().sh_stack_forward(n, self._native_steps(), _lib.ptr(x), _LAYOUT_ID[in_layout], rows0, c0, B,
                                                 self._ptr_array(weights), self._ptr_array(biases), outs.ctypes.data,
@@ -471,155 +559,57 @@ class Stack:
     def native_backward(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, mma: str = "exact", p3=None,
                         frozen=None):
         """-> (grad_x or None, {param: (dW, db)}); frozen: as for native_forward (the same list), those parameters get (None, None)."""
-        B = x.shape[0] if in_layout == "bm" else x.shape[1]
-        rows0 = x.shape[1] if in_layout == "bm" else x.shape[0]
-        c0 = x.shape[2]
+        B, rows0, c0 = self._io_dims(x, in_layout)
         plan = self._plan(B, c0)
         n = len(self.steps)
         dev = x.device
-        work = torch.empty(max(1, plan["b_total"]), dtype=torch.float32, device=dev)
+        work = torch.empty(max(1, plan.b_total // 4), dtype=torch.float32, device=dev)
         if DEBUG_POISON:
             work.fill_(float("nan"))
-        flat = torch.empty(max(1, plan["p_total"]), dtype=torch.float32, device=dev)
+        flat = torch.empty(max(1, plan.p_total // 4), dtype=torch.float32, device=dev)
         gx = ops.alloc(B, rows0, c0, in_layout, dev) if need_x_grad else None
-        acts = plan["f_off"] + np.uint64(arena.data_ptr())
-        acts[n - 1] = out.data_ptr()
-        wbase, fbase = np.uint64(work.data_ptr()), np.uint64(flat.data_ptr())
-        gin = (plan["g_off"] + wbase) * plan["g_mask"]
+        acts = _step_outputs(plan, arena, out)
+        wbase = work.data_ptr()
+        gin = _bind(wbase, plan.g_off, plan.g_mask)
         gin[0] = gx.data_ptr() if need_x_grad else 0
-        wt = (plan["wt_off"] + wbase) * plan["wt_mask"]
-        ws = (plan["ws_off"] + wbase) * plan["ws_mask"]
-        assert len(need_bias) == plan["npar"] == len(weights)
-        frozen = list(frozen) if frozen else [False] * plan["npar"]
-        assert not any(f and nb for f, nb in zip(frozen, need_bias))
-        dW = (plan["dW_off"] + fbase) * np.array([0 if f else 1 for f in frozen], dtype=np.uint64)
-        db = (plan["db_off"] + fbase) * np.array([1 if nb else 0 for nb in need_bias], dtype=np.uint64)
+        wt = _bind(wbase, plan.wt_off, plan.conv_mask)
+        ws = _bind(wbase, plan.ws_off, plan.conv_mask)
+        frozen, dW, db = _bind_param_grads(plan, flat, weights, need_bias, frozen)
         gpl_p = wf3t_p = inpl_p = None
         dpl = ctypes.c_void_p(0)
         if mma == "planes3" and p3 is not None and p3[0] is not None:
             # image of the INPUT of step i = image of the buffer step i - 1 wrote
             inpl = np.zeros(n, dtype=np.uint64)
-            inpl[1:] = (plan["pl_off"][:n - 1] + np.uint64(p3[0].data_ptr())) * plan["in_img"][1:]
+            inpl[1:] = _bind(p3[0].data_ptr(), plan.pl_off[:n - 1], plan.in_img[1:])
             inpl_p = inpl.ctypes.data
         if mma == "planes3" and p3 is not None:
-            gimg = torch.empty(max(256, plan["gpl_total"]), dtype=torch.uint8, device=dev)
-            gpl = (plan["gpl_off"] + np.uint64(gimg.data_ptr())) * plan["gpl_mask"]
-            wf = (plan["wf3t_off"] + np.uint64(p3[1].data_ptr() + p3[2])) * plan["wf3t_mask"]
+            gimg = torch.empty(max(_ALIGN_BYTES, plan.gpl_total), dtype=torch.uint8, device=dev)
+            gpl = _bind(gimg.data_ptr(), plan.gpl_off, plan.gpl_mask)
+            wf = _bind(p3[1].data_ptr() + p3[2], plan.wf3t_off, plan.wf3t_mask)
             gpl_p, wf3t_p = gpl.ctypes.data, wf.ctypes.data
-            if plan["dpl_mask"]:
-                dpl = ctypes.c_void_p(gimg.data_ptr() + int(plan["dpl_off"]))
+            if plan.dpl_mask:
+                dpl = ctypes.c_void_p(gimg.data_ptr() + int(plan.dpl_off))
         _lib.check(_lib.load().sh_stack_backward(
             n, self._native_steps(), _lib.ptr(x), _LAYOUT_ID[in_layout], rows0, c0, B, acts.ctypes.data, _lib.ptr(g),
-            _LAYOUT_ID[out_layout], self._ptr_array(weights), gin.ctypes.data, ctypes.c_void_p(int(wbase) + 4 * plan["dpre_last_off"]),
-            wt.ctypes.data, ws.ctypes.data, plan["ws_bytes"].ctypes.data, dW.ctypes.data, db.ctypes.data, 1 if need_x_grad else 0,
+            _LAYOUT_ID[out_layout], self._ptr_array(weights), gin.ctypes.data, ctypes.c_void_p(wbase + plan.dpre_last_off),
+            wt.ctypes.data, ws.ctypes.data, plan.ws_bytes.ctypes.data, dW.ctypes.data, db.ctypes.data, 1 if need_x_grad else 0,
             _lib.mma_id(mma), gpl_p, dpl, wf3t_p, inpl_p, 2 if (inpl_p is not None and not any(frozen)) else 1, _lib.stream_ptr()),
             "sh_stack_backward")
-        grads = {}
-        for j, shp in enumerate(plan["shapes"]):
-            if shp is None or frozen[j]:
-                continue
-            o = int(plan["dW_off_f"][j])
-            dWj = flat[o:o + shp[0] * shp[1]].view(shp)
-            o = int(plan["db_off_f"][j])
-            grads[j] = (dWj, flat[o:o + shp[0]] if need_bias[j] else None)
-        return gx, grads
+        return gx, _param_grad_views(plan, flat, frozen, need_bias)
 
     # ------------------------------------------------------------------ bf16 compute path (BASELINE config 3)
-    def _plan_bf16(self, B: int, c0: int, x_is_f32: bool, out_is_f32: bool):
-        """Arena offsets in BYTES for the bf16 path: activations / gradients between steps are bf16, the fragment-ordered
-        working copies of the conv weights and the fp32 partial slabs of the weight gradients live in the same arenas."""
-        key = ("bf16", B, c0, x_is_f32, out_is_f32)
-        plans = self.__dict__.setdefault("_plans", {})
-        if key in plans:
-            return plans[key]
-        lib = _lib.load()
-        al = lambda nbytes: (int(nbytes) + 255) // 256 * 256          # noqa: E731
-        n = len(self.steps)
-        cin_of, c = [], c0
-        for st in self.steps:
-            cin_of.append(c)
-            c = st.cout if st.kind == "conv" else c
-        out_rows = [st.R if st.kind == "conv" else st.csr.rows for st in self.steps]
-        out_ch = [st.cout if st.kind == "conv" else cin_of[i] for i, st in enumerate(self.steps)]
-        f_off, wf_off, wf_mask, o = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), 0
-        for i in range(n - 1):
-            if self._extends(i):
-                f_off[i] = f_off[i - 1]
-                continue
-            f_off[i] = o
-            o += al(self._buffer_rows(i) * B * out_ch[i] * 2)
-        for i, st in enumerate(self.steps):
-            if st.kind == "conv":
-                wf_off[i], wf_mask[i] = o, 1
-                o += al(lib.sh_conv_wfrag_bytes(st.S, st.cin, st.cout))
-        f_total = o
-        last = self.steps[-1]
-        o = 0
-        if last.kind == "conv":
-            o += al((last.R + last.n_extra) * B * last.cout * (4 if out_is_f32 else 2))
-        gin_size = [0] * n
-        for i in range(1, n):
-            st, prev = self.steps[i], self.steps[i - 1]
-            rows_in = st.n_in if st.kind == "conv" else st.csr.cols
-            gin_size[i] = (rows_in + (prev.n_extra if prev.kind == "conv" else 0)) * B * cin_of[i] * 2
-        region = [al(max([gin_size[i] for i in range(1, n) if i % 2 == par] + [0])) for par in (0, 1)]
-        region_off = [o, o + region[0]]
-        o += region[0] + region[1]
-        g_off, g_mask = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-        for i in range(1, n):
-            g_off[i], g_mask[i] = region_off[i % 2], 1
-        wt_off, wt_mask = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-        ws_off, ws_mask, ws_bytes = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
-        for i, st in enumerate(self.steps):
-            if st.kind != "conv":
-                continue
-            wt_off[i], wt_mask[i] = o, 1
-            o += al(lib.sh_conv_wfrag_bytes(st.S, st.cout, st.cin))
-            nb = int(lib.sh_spiral_conv_bwd_wgt_workspace_bf16(B, st.R, st.S, st.cin, st.cout))
-            ws_off[i], ws_mask[i], ws_bytes[i] = o, 1, nb
-            o += al(nb)
-        b_total = o
-        npar = 1 + max([st.param for st in self.steps if st.kind == "conv"], default=-1)
-        dW_off, db_off, shapes, o = np.zeros(npar, dtype=np.uint64), np.zeros(npar, dtype=np.uint64), [None] * npar, 0
-        for st in self.steps:
-            if st.kind != "conv":
-                continue
-            dW_off[st.param] = o
-            o += _round(st.cout * st.S * st.cin)
-            db_off[st.param] = o
-            o += _round(st.cout)
-            shapes[st.param] = (st.cout, st.S * st.cin)
-        plan = dict(f_off=f_off, wf_off=wf_off, wf_mask=wf_mask, f_total=f_total, g_off=g_off, g_mask=g_mask, wt_off=wt_off,
-                    wt_mask=wt_mask, ws_off=ws_off, ws_mask=ws_mask, ws_bytes=ws_bytes, b_total=b_total, dW_off=dW_off * 4,
-                    db_off=db_off * 4, dW_off_f=dW_off, db_off_f=db_off, shapes=shapes, p_total=o, npar=npar, out_rows=out_rows,
-                    out_ch=out_ch)
-        plans[key] = plan
-        return plan
-
-    @staticmethod
-    def _io_dims(x, layout):
-        B = x.shape[0] if layout == "bm" else x.shape[1]
-        rows = x.shape[1] if layout == "bm" else x.shape[0]
-        return B, rows, x.shape[2]
-
     def native_forward_bf16(self, x, in_layout, out_layout, out_dtype, weights, biases, wf=None):
         """x: bf16, or fp32 with 3 channels.  -> (output of type out_dtype, byte arena holding the inner activations).
         wf: a WFrags holding this stack's converted weights (then no conversion launch), or None."""
         B, rows0, c0 = self._io_dims(x, in_layout)
-        if not (x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)):
-            raise ValueError("expected a contiguous fp32 / bf16 3-D tensor, got %s %s" % (tuple(x.shape), x.dtype))
-        if x.numel() >= 2 ** 32:
-            raise RuntimeError("semantichuman_amd: gathered tensors are addressed with 32-bit element offsets; "
-                               "%d elements is too large - split the batch" % x.numel())
-        plan = self._plan_bf16(B, c0, x.dtype == torch.float32, out_dtype == torch.float32)
+        _check_input(x, (torch.float32, torch.bfloat16))
+        plan = self._plan(B, c0, bf16=True, out_is_f32=out_dtype == torch.float32)
         n = len(self.steps)
-        arena = torch.empty(max(256, plan["f_total"]), dtype=torch.uint8, device=x.device)
-        rows_o, ch_o = plan["out_rows"][-1], plan["out_ch"][-1]
+        arena = torch.empty(max(_ALIGN_BYTES, plan.f_total), dtype=torch.uint8, device=x.device)
+        rows_o, ch_o = plan.out_rows[-1], plan.out_ch[-1]
         out = torch.empty((B, rows_o, ch_o) if out_layout == "bm" else (rows_o, B, ch_o), dtype=out_dtype, device=x.device)
-        base = np.uint64(arena.data_ptr())
-        outs = plan["f_off"] + base
-        outs[n - 1] = out.data_ptr()
-        wfp = wf.fwd[id(self)] if wf is not None else (plan["wf_off"] + base) * plan["wf_mask"]
+        outs = _step_outputs(plan, arena, out)
+        wfp = wf.fwd[id(self)] if wf is not None else _bind(arena.data_ptr(), plan.wf_off, plan.conv_mask)
         _lib.check(_lib.load().sh_stack_forward_bf16(
             n, self._native_steps(), _lib.ptr(x), ops.dtype_id(x), _LAYOUT_ID[in_layout], rows0, c0, B, self._ptr_array(weights),
             self._ptr_array(biases), wfp.ctypes.data, 1 if wf is not None else 0, outs.ctypes.data, ops.dtype_id(out),
@@ -628,39 +618,26 @@ class Stack:
 
     def native_backward_bf16(self, x, in_layout, out_layout, arena, out, g, weights, need_x_grad, need_bias, wf=None, frozen=None):
         B, rows0, c0 = self._io_dims(x, in_layout)
-        plan = self._plan_bf16(B, c0, x.dtype == torch.float32, out.dtype == torch.float32)
+        plan = self._plan(B, c0, bf16=True, out_is_f32=out.dtype == torch.float32)
         n = len(self.steps)
         dev = x.device
-        work = torch.empty(max(256, plan["b_total"]), dtype=torch.uint8, device=dev)
-        flat = torch.empty(max(1, plan["p_total"]), dtype=torch.float32, device=dev)
+        work = torch.empty(max(_ALIGN_BYTES, plan.b_total), dtype=torch.uint8, device=dev)
+        flat = torch.empty(max(1, plan.p_total // 4), dtype=torch.float32, device=dev)
         gx = torch.empty_like(x) if need_x_grad else None
-        abase, wbase, fbase = np.uint64(arena.data_ptr()), np.uint64(work.data_ptr()), np.uint64(flat.data_ptr())
-        acts = plan["f_off"] + abase
-        acts[n - 1] = out.data_ptr()
-        gin = (plan["g_off"] + wbase) * plan["g_mask"]
+        acts = _step_outputs(plan, arena, out)
+        wbase = work.data_ptr()
+        gin = _bind(wbase, plan.g_off, plan.g_mask)
         gin[0] = gx.data_ptr() if need_x_grad else 0
         ready = wf is not None and wf.bwd is not None
-        wt = wf.bwd[id(self)] if ready else (plan["wt_off"] + wbase) * plan["wt_mask"]
-        ws = (plan["ws_off"] + wbase) * plan["ws_mask"]
-        assert len(need_bias) == plan["npar"] == len(weights)
-        frozen = list(frozen) if frozen else [False] * plan["npar"]
-        assert not any(f and nb for f, nb in zip(frozen, need_bias))
-        dW = (plan["dW_off"] + fbase) * np.array([0 if f else 1 for f in frozen], dtype=np.uint64)
-        db = (plan["db_off"] + fbase) * np.array([1 if nb else 0 for nb in need_bias], dtype=np.uint64)
+        wt = wf.bwd[id(self)] if ready else _bind(wbase, plan.wt_off, plan.conv_mask)
+        ws = _bind(wbase, plan.ws_off, plan.conv_mask)
+        frozen, dW, db = _bind_param_grads(plan, flat, weights, need_bias, frozen)
         _lib.check(_lib.load().sh_stack_backward_bf16(
             n, self._native_steps(), _lib.ptr(x), ops.dtype_id(x), _LAYOUT_ID[in_layout], rows0, c0, B, acts.ctypes.data, _lib.ptr(g),
             ops.dtype_id(out), _LAYOUT_ID[out_layout], self._ptr_array(weights), gin.ctypes.data, ops.dtype_id(x),
-            ctypes.c_void_p(int(wbase)), wt.ctypes.data, 1 if ready else 0, ws.ctypes.data, plan["ws_bytes"].ctypes.data, dW.ctypes.data,
-            db.ctypes.data, 1 if need_x_grad else 0, _lib.stream_ptr()), "sh_stack_backward_bf16")
-        grads = {}
-        for j, shp in enumerate(plan["shapes"]):
-            if shp is None or frozen[j]:
-                continue
-            o = int(plan["dW_off_f"][j])
-            dWj = flat[o:o + shp[0] * shp[1]].view(shp)
-            o = int(plan["db_off_f"][j])
-            grads[j] = (dWj, flat[o:o + shp[0]] if need_bias[j] else None)
-        return gx, grads
+            ctypes.c_void_p(wbase + plan.dpre_last_off), wt.ctypes.data, 1 if ready else 0, ws.ctypes.data, plan.ws_bytes.ctypes.data,
+            dW.ctypes.data, db.ctypes.data, 1 if need_x_grad else 0, _lib.stream_ptr()), "sh_stack_backward_bf16")
+        return gx, _param_grad_views(plan, flat, frozen, need_bias)
 
     def _side_stream(self, dev):
         s = getattr(self, "_side", None)
@@ -822,7 +799,7 @@ def convert_p3_frags(items, with_backward: bool):
     lib = _lib.load()
     w_p, o_p, S, Ci, Co, tr = [], [], [], [], [], []
     for stack, plan, weights, buf, base in items:
-        for i, t, off in plan["wf3_jobs"]:
+        for i, t, off in plan.wf3_jobs:
             if t and not with_backward:
                 continue
             st = stack.steps[i]
@@ -849,10 +826,10 @@ def prepare_p3_frags(stacks_convs_c0, B: int, with_backward: bool):
     items, total = [], 0
     for stack, convs, c0 in stacks_convs_c0:
         plan = stack._plan(B, c0)
-        if not plan["wf3_total"]:
+        if not plan.wf3_total:
             continue
         items.append((stack, plan, [m.conv.weight for m in convs], None, total))
-        total += (int(plan["wf3_total"]) + 255) // 256 * 256
+        total += _align(plan.wf3_total)
     if not items:
         return
     buf = torch.empty(total, dtype=torch.uint8, device=items[0][2][0].device)
@@ -868,6 +845,14 @@ def _frozen_mask(needs_input_grad, first: int, n: int):
     if FULL_WGRAD:
         return [False] * n
     return [not (needs_input_grad[first + 2 * j] or needs_input_grad[first + 2 * j + 1]) for j in range(n)]
+
+
+def _backward_result(n_lead: int, gx, grads, n_params: int):
+    """What an autograd node of a stack returns: None for the n_lead inputs in front of x, the gradient of x, then (dW, db) per parameter."""
+    res = [None] * n_lead + [gx]
+    for j in range(n_params):
+        res += grads.get(j, (None, None))
+    return tuple(res)
 
 
 class StackFunction(torch.autograd.Function):
@@ -919,11 +904,7 @@ class StackFunction(torch.autograd.Function):
             finally:
                 _lib.set_f32_mma_mode(was)
             ctx.acts = None
-        res = [None, None, None, gx]
-        for j in range(len(weights)):
-            dW, db = grads.get(j, (None, None))
-            res += [dW, db]
-        return tuple(res)
+        return _backward_result(3, gx, grads, len(weights))
 
 
 class WFrags:
@@ -935,7 +916,6 @@ class WFrags:
     def __init__(self, stacks_and_weights, with_backward: bool):
         lib = _lib.load()
         jobs, total = [], 0                                              # (stack, step, weight, transpose, byte offset)
-        al = lambda n: (n + 255) // 256 * 256                            # noqa: E731
         for stack, weights in stacks_and_weights:
             for i, st in enumerate(stack.steps):
                 if st.kind != "conv":
@@ -943,9 +923,9 @@ class WFrags:
                 for tr in ((0, 1) if with_backward else (0,)):
                     nb = lib.sh_conv_wfrag_bytes(st.S, st.cout if tr else st.cin, st.cin if tr else st.cout)
                     jobs.append((stack, i, st, weights[st.param], tr, total))
-                    total += al(nb)
+                    total += _align(nb)
         dev = stacks_and_weights[0][1][0].device
-        self.buf = torch.empty(max(256, total), dtype=torch.uint8, device=dev)
+        self.buf = torch.empty(max(_ALIGN_BYTES, total), dtype=torch.uint8, device=dev)
         base = self.buf.data_ptr()
         self.fwd = {id(stack): np.zeros(len(stack.steps), dtype=np.uint64) for stack, _ in stacks_and_weights}
         self.bwd = {id(stack): np.zeros(len(stack.steps), dtype=np.uint64) for stack, _ in stacks_and_weights} if with_backward else None
@@ -994,25 +974,31 @@ class StackFunctionBF16(torch.autograd.Function):
         need_bias = [hb and ctx.needs_input_grad[7 + 2 * j] for j, hb in enumerate(ctx.has_bias)]
         gx, grads = ctx.stack.native_backward_bf16(x, in_layout, out_layout, arena, out, g, weights, ctx.needs_input_grad[5], need_bias,
                                                    ctx.wf, ctx.frozen)
-        res = [None, None, None, None, None, gx]
-        for j in range(len(weights)):
-            dW, db = grads.get(j, (None, None))
-            res += [dW, db]
-        return tuple(res)
+        return _backward_result(5, gx, grads, len(weights))
 
 
-def run_stack_bf16(stack: Stack, x, in_layout, out_layout, out_dtype, convs, wf=None):
-    """bf16 compute path of `run_stack`: x bf16 (or fp32 with 3 channels), output of type out_dtype.  wf: a WFrags made by
-    `prepare_wfrags` for (at least) this stack in this forward pass; None = the stack converts its own weights."""
+def _check_device(stack: Stack, x):
     if not x.is_cuda:
         raise RuntimeError("semantichuman_amd: input is on %s; the spiral-convolution kernels run on a HIP device "
                            "only (there is no CPU fallback)" % x.device)
     if stack.device is None or stack.device != x.device:
         raise RuntimeError("semantichuman_amd: model tables are on %s but the input is on %s - move the module with "
                            ".to(device)" % (stack.device, x.device))
+
+
+def _params_of(convs):
+    """(w_0, b_0, w_1, b_1, ...) of a ModuleList of SpiralConv: the parameter inputs of the autograd nodes."""
     params = []
     for m in convs:
         params += [m.conv.weight, m.conv.bias]
+    return params
+
+
+def run_stack_bf16(stack: Stack, x, in_layout, out_layout, out_dtype, convs, wf=None):
+    """bf16 compute path of `run_stack`: x bf16 (or fp32 with 3 channels), output of type out_dtype.  wf: a WFrags made by
+    `prepare_wfrags` for (at least) this stack in this forward pass; None = the stack converts its own weights."""
+    _check_device(stack, x)
+    params = _params_of(convs)
     if wf is None:
         wf = prepare_wfrags([(stack, convs)])
     if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
@@ -1022,15 +1008,8 @@ def run_stack_bf16(stack: Stack, x, in_layout, out_layout, out_dtype, convs, wf=
 
 def run_stack(stack: Stack, x, in_layout, out_layout, convs):
     """convs: the ModuleList of SpiralConv modules this stack's ConvSteps index into."""
-    if not x.is_cuda:
-        raise RuntimeError("semantichuman_amd: input is on %s; the spiral-convolution kernels run on a HIP device "
-                           "only (there is no CPU fallback)" % x.device)
-    if stack.device is None or stack.device != x.device:
-        raise RuntimeError("semantichuman_amd: model tables are on %s but the input is on %s - move the module with "
-                           ".to(device)" % (stack.device, x.device))
-    params = []
-    for m in convs:
-        params += [m.conv.weight, m.conv.bias]
+    _check_device(stack, x)
+    params = _params_of(convs)
     if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
         return StackFunction.apply(stack, in_layout, out_layout, x, *params)
     if NATIVE:
