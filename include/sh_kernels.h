@@ -940,6 +940,92 @@ SH_API int sh_align_plane_solve(const double* partials, int M, int n, const int3
                                 int32_t* solved, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Robust terms: a robust penalty in the data term of the Chamfer loss and the matching IRLS weight in the pose steps (no
+ * reference counterpart).  Two numbers select it: robust (enum sh_robust) and scale2 = sigma^2 > 0, sigma in the model's
+ * normalised units.  The `_robust` entry points below take the arguments of their namesakes followed by (robust, scale2);
+ * robust = SH_ROBUST_NONE is the namesake itself - the same kernels under the same names, the same bits, scale2 unread - and
+ * the namesakes are that call.  An unknown robust, or with robust != SH_ROBUST_NONE a scale2 that is not finite and > 0:
+ * SH_ERR_INVALID_ARG before anything else is looked at.
+ *
+ * The penalty applies to a pair's squared distance AFTER truncation: u = fminf(d2, tau2) for the value, and the kept rule
+ * d2 < tau2 of the gradient and the moments is unchanged (there u = d2), so tau2 keeps its meaning and a point without a partner
+ * (d2 = +inf under a gate) still counts as truncated.  Everything fp32, every operation rounded on its own (no contraction),
+ * division and square root correctly rounded:
+ *     SH_ROBUST_GEMAN_MCCLURE   t = scale2 / (scale2 + u);   rho = u * t;   w = t * t
+ *     SH_ROBUST_HUBER           u <= scale2:  rho = u,  w = 1
+ *       (on the distance)       otherwise:    rho = 2 * sqrtf(scale2 * u) - scale2,   w = sqrtf(scale2 / u)
+ *                               as selects: rho = u <= scale2 ? u : r, w = u <= scale2 ? 1 : sqrtf(scale2 / (u <= scale2 ? 1 : u)),
+ *                               so u = 0 never reaches the division
+ * w = d rho / d u.  Both reduce to rho = u, w = 1 for u << scale2 and are continuous, with a continuous weight, across
+ * u = scale2 (Huber: rho = scale2, w = 1 on both sides; Geman-McClure: rho = scale2 / 2, w = 1 / 4).  Geman-McClure is bounded
+ * by scale2 and its weight falls as 1 / u^2: far points stop pulling.  Huber grows like the distance and its pull is constant.
+ * u = +inf (no partner and no truncation) makes Geman-McClure's value NaN (inf * 0), where the plain value is +inf.
+ *
+ * sh_chamfer_fwd_robust.  L[b] of sh_chamfer_fwd with rho(min(d2, tau2)) in place of min(d2, tau2) in both sums: the same
+ * normalisation (1 / m_b, w_ms / n_act), the terms widened to fp64 and summed in the same order.  counts as ever.
+ *
+ * sh_chamfer_bwd_robust, sh_chamfer_surface_bwd_robust.  The gradient of that value, w taken from the recorded fp32 d2 of the
+ * pair: a kept pair contributes w * 2 (x - s) in place of 2 (x - s).
+ *     vertex partner:   acc = fma(w(d2_sm[j]), fl(x_i - s_j), acc) per coordinate, ascending j           (fp32)
+ *     surface partner:  e = fl(w(d2[j]) * e) per coordinate, once per pair, before the corners' l_k; the rest as ever
+ *     model -> scan:    the factor (w_ms 2/n_act) becomes fl((w_ms 2/n_act) * w(d2_ms[i])), both forms
+ * The kept rule, the order, the epilogue and the rows that receive zeros are those of the namesakes.
+ *
+ * sh_align_moments_robust, sh_align_moments_surface_robust, sh_align_plane_moments_robust,
+ * sh_align_plane_moments_surface_robust.  One IRLS step: a kept pair adds w times what it adds in the namesake, w = the fp32
+ * weight above of the pair's recorded d2 (d2_sm / the surface d2 / d2_ms), widened to fp64; the pair's terms are formed exactly
+ * as in the namesake and each multiplied by w once before it is added.  Slot [0] of a range, "pairs kept", is therefore the sum
+ * of the weights; the active-vertex slot stays a count.  Ranges, grid, order and the partials' layout do not change, and the
+ * two solve calls finish these partials unchanged.  What every divisor of the solve kernels means under weights:
+ *     1 / m_b and w_ms / n_act    the two directions' normalisation: counts of points and of active vertices, as in the value -
+ *                                 not pair counts, so they stay counts
+ *     1 / W (sh_align_solve)      W = sum of the joined weights (direction weight times w): p_bar, q_bar, H and var_p are the
+ *                                 weighted means and covariances, which is what weighted Procrustes asks for
+ *     W > 0 / sy[0] > 0           "something was kept" - a sum of positive weights is positive whenever a pair was kept (w > 0
+ *                                 for every finite u)
+ *     mom[18]                     the sum of the two directions' slots [0]: the unnormalised sum of weights; with
+ *                                 SH_ROBUST_NONE the pair count, as ever
+ *     sh_align_plane_solve        divides by nothing of the kind: H and g carry the same factor
+ * The weight is taken from the RECORDED d2 - the distance the search measured, which is also the distance the value's rho was
+ * evaluated at - not recomputed from the pair: for a foot point or a gated match that is the only distance there is, and value,
+ * gradient and pose step then weigh a pair alike.
+ *
+ * No atomics; the same bits for a body alone or in any padded batch.
+ */
+enum sh_robust { SH_ROBUST_NONE = 0, SH_ROBUST_GEMAN_MCCLURE = 1, SH_ROBUST_HUBER = 2 };
+SH_API int sh_chamfer_fwd_robust(const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n,
+                                 const uint8_t* v_mask, int64_t mask_sb, float tau2, float w_ms, int B, float* loss, int32_t* counts,
+                                 sh_stream_t stream, int robust, float scale2);
+SH_API int sh_chamfer_bwd_robust(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M,
+                                 const int32_t* s_count, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
+                                 const float* d2_ms, const uint8_t* v_mask, int64_t mask_sb, const int32_t* counts, float tau2,
+                                 float w_ms, const float* gL, int B, float* g_x, sh_stream_t stream, int robust, float scale2);
+SH_API int sh_chamfer_surface_bwd_robust(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M,
+                                         const int32_t* s_count, const int32_t* faces, int nF, const int32_t* face, const float* d2,
+                                         const float* uv, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
+                                         int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B,
+                                         float* g_x, sh_stream_t stream, int robust, float scale2);
+SH_API int sh_align_moments_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows,
+                                   int n, const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm,
+                                   const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials,
+                                   size_t partials_bytes, sh_stream_t stream, int robust, float scale2);
+SH_API int sh_align_moments_surface_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb,
+                                           int rows, int n, const uint8_t* v_mask, int64_t mask_sb, const int32_t* faces, int nF,
+                                           const int32_t* face, const float* uv, const float* d2, const int32_t* idx_ms,
+                                           const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                                           sh_stream_t stream, int robust, float scale2);
+SH_API int sh_align_plane_moments_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb,
+                                         int rows, int n, const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm,
+                                         const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
+                                         double* partials, size_t partials_bytes, sh_stream_t stream, int robust, float scale2);
+SH_API int sh_align_plane_moments_surface_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x,
+                                                 int64_t x_sb, int rows, int n, const uint8_t* v_mask, int64_t mask_sb, const float* tn,
+                                                 const int32_t* faces, int nF, const int32_t* face, const float* uv, const float* d2,
+                                                 const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
+                                                 double* partials, size_t partials_bytes, sh_stream_t stream, int robust,
+                                                 float scale2);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

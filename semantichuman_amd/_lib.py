@@ -100,6 +100,18 @@ SIGNATURES = {
     "sh_align_plane_moments_surface": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P,
                                                c_size_t, _P]),
     "sh_align_plane_solve": (c_int, [_P, _I, _I, _P, c_float, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    # robust terms: the namesake's arguments, then (robust, scale2)
+    "sh_chamfer_fwd_robust": (c_int, [_P, _I, _P, _P, _I, _I, _P, _L, c_float, c_float, _I, _P, _P, _P, _I, c_float]),
+    "sh_chamfer_bwd_robust": (c_int, [_P, _L, _I, _I, _P, _L, _I, _P, _P, _P, _P, _P, _P, _L, _P, c_float, c_float, _P, _I, _P, _P, _I, c_float]),
+    "sh_chamfer_surface_bwd_robust": (c_int, [_P, _L, _I, _I, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, c_float, c_float, _P, _I, _P, _P,
+                                              _I, c_float]),
+    "sh_align_moments_robust": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P, _I, c_float]),
+    "sh_align_moments_surface_robust": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P,
+                                                _I, c_float]),
+    "sh_align_plane_moments_robust": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P, _I,
+                                              c_float]),
+    "sh_align_plane_moments_surface_robust": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, c_float, c_float, _I, _P,
+                                                      c_size_t, _P, _I, c_float]),
     "sh_dataset_normalize": (c_int, [_P, _P, _I, _I, _I, ctypes.c_uint, _P, _P, _P, _P, _P, _P]),
     "sh_gather_meshes": (c_int, [_P, _L, _P, _I, _P, _P]),
     "sh_adam_step": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P] + [ctypes.c_double] * 4 + [_P]),

@@ -53,6 +53,8 @@ struct PointSums {
     static constexpr bool NORMALS = false;
     static constexpr const char* SCOPE = "align_moments_kernel|B=%d M=%d n=%d ranges=%d";
     static constexpr const char* SCOPE_SURFACE = "align_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d";
+    static constexpr const char* SCOPE_ROBUST = "align_moments_robust_kernel|B=%d M=%d n=%d ranges=%d robust=%d";
+    static constexpr const char* SCOPE_SURFACE_ROBUST = "align_moments_surface_robust_kernel|B=%d M=%d n=%d nF=%d ranges=%d robust=%d";
     double a[N];
     __device__ __forceinline__ void add(const float* p, double q0, double q1, double q2) {
         const double p0 = p[0], p1 = p[1], p2 = p[2];
@@ -74,6 +76,8 @@ struct PlaneSums {
     static constexpr bool NORMALS = true;
     static constexpr const char* SCOPE = "align_plane_moments_kernel|B=%d M=%d n=%d ranges=%d";
     static constexpr const char* SCOPE_SURFACE = "align_plane_moments_surface_kernel|B=%d M=%d n=%d nF=%d ranges=%d";
+    static constexpr const char* SCOPE_ROBUST = "align_plane_moments_robust_kernel|B=%d M=%d n=%d ranges=%d robust=%d";
+    static constexpr const char* SCOPE_SURFACE_ROBUST = "align_plane_moments_surface_robust_kernel|B=%d M=%d n=%d nF=%d ranges=%d robust=%d";
     double a[N];
     __device__ __forceinline__ void add(const float* p, double q0, double q1, double q2, double n0, double n1, double n2) {
 #pragma clang fp contract(off)
@@ -98,13 +102,16 @@ struct PlaneSums {
 // adds them.  SURFACE: idx_sm / d2_sm are the recorded face and the surface distance, and the partner of s_j is the foot point on
 // that face instead of a vertex - with the face's normal, formed from the three corners the foot point needs anyway, where Sums
 // takes one; nothing else differs.  A vertex partner's normal is its row of tn, which no other form reads.
-template <class Sums, bool SURFACE>
+// ROBUST (header, "Robust terms"): a kept pair adds w times what it adds otherwise, w = the fp32 weight of its recorded d2 widened
+// to fp64 - its terms are formed by the same Sums::add into a zeroed set and each multiplied by w once.  The active-vertex slot
+// stays a count.  SH_ROBUST_NONE adds straight into the range's sums, as ever.
+template <class Sums, bool SURFACE, int ROBUST>
 __global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
                                                          const float* __restrict__ x, long x_sb, int rows, int n,
                                                          const unsigned char* __restrict__ v_mask, long mask_sb, const float* __restrict__ tn,
                                                          const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
                                                          const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms, float tau2,
-                                                         int r_sm, AlignSurface sf, double* __restrict__ partials) {
+                                                         float scale2, int r_sm, AlignSurface sf, double* __restrict__ partials) {
     constexpr int N = Sums::N;
     __shared__ double red[N][4];
     const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -116,16 +123,31 @@ __global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict
     Sums acc;
 #pragma unroll
     for (int c = 0; c < N; ++c) acc.a[c] = 0.0;
-    auto add_vertex = [&](long ip, int i) {                              // the partner of scan point ip is vertex i
+    auto add_pair = [&](float d2, auto... pair) {                        // a kept pair with the recorded distance d2
+        if constexpr (ROBUST != 0) {
+            const double w = robust_weight<ROBUST>(d2, scale2);
+            Sums one;
+#pragma unroll
+            for (int c = 0; c < N; ++c) one.a[c] = 0.0;
+            one.add(pair...);
+#pragma unroll
+            for (int c = 0; c < N; ++c) acc.a[c] += w * one.a[c];
+        } else {
+            acc.add(pair...);
+        }
+    };
+    auto add_vertex = [&](float d2, long ip, int i) {                    // the partner of scan point ip is vertex i
         const float* q = xb + 3L * i;
-        if constexpr (Sums::NORMALS) acc.add(sb + 3 * ip, q[0], q[1], q[2], tb[3L * i], tb[3L * i + 1], tb[3L * i + 2]);
-        else acc.add(sb + 3 * ip, q[0], q[1], q[2]);
+        if constexpr (Sums::NORMALS) add_pair(d2, sb + 3 * ip, (double)q[0], (double)q[1], (double)q[2], (double)tb[3L * i], (double)tb[3L * i + 1],
+                                              (double)tb[3L * i + 2]);
+        else add_pair(d2, sb + 3 * ip, (double)q[0], (double)q[1], (double)q[2]);
     };
     if (r < r_sm) {                                                      // uniform over the workgroup
         const int lo = r * RANGE, hi = min(lo + RANGE, m);
         for (int j = lo + tid; j < hi; j += NT) {
             const int i = idx_sm[(long)b * M + j];
-            if (!(d2_sm[(long)b * M + j] < tau2)) continue;
+            const float d2 = d2_sm[(long)b * M + j];
+            if (!(d2 < tau2)) continue;
             if constexpr (SURFACE) {
                 if ((unsigned)i >= (unsigned)sf.nF) continue;
                 int i0, i1, i2;
@@ -136,10 +158,10 @@ __global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict
                 if constexpr (Sums::NORMALS) face_normal(ca, cb, cc, n0, n1, n2);
                 const double q0 = foot_coord(ca[0], cb[0], cc[0], v, w), q1 = foot_coord(ca[1], cb[1], cc[1], v, w),
                              q2 = foot_coord(ca[2], cb[2], cc[2], v, w);
-                if constexpr (Sums::NORMALS) acc.add(sb + 3L * j, q0, q1, q2, n0, n1, n2);
-                else acc.add(sb + 3L * j, q0, q1, q2);
+                if constexpr (Sums::NORMALS) add_pair(d2, sb + 3L * j, q0, q1, q2, n0, n1, n2);
+                else add_pair(d2, sb + 3L * j, q0, q1, q2);
             } else {
-                if (i >= 0 && i < n) add_vertex(j, i);
+                if (i >= 0 && i < n) add_vertex(d2, j, i);
             }
         }
     } else {
@@ -149,7 +171,9 @@ __global__ __launch_bounds__(NT) void align_pairs_kernel(const float* __restrict
             if (mb && mb[i] == 0) continue;
             acc.a[Sums::N_ACT] += 1.0;                                   // n_act
             const int k = idx_ms[(long)b * rows + i];
-            if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) add_vertex(k, i);
+            if (k < 0 || k >= m) continue;
+            const float d2 = d2_ms[(long)b * rows + i];
+            if (d2 < tau2) add_vertex(d2, k, i);
         }
     }
 #pragma unroll
@@ -442,13 +466,15 @@ int align_moments_check(const char* who, const float* s, int64_t s_sb, int M, co
 
 // The four moments entry points (sf == nullptr: the vertex forms; Sums: the closed form's or the point-to-plane step's sums): the
 // checks, the normals' for the plane step, then the launch.  idx_sm / d2_sm are the surface form's face / d2; tn is read by the
-// plane step only.
+// plane step only.  robust / scale2: the form of the header's "Robust terms" (the _robust twins; SH_ROBUST_NONE for the others, which
+// launch the plain kernels under their plain names).
 template <class Sums>
 int align_moments(const char* who, const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
                   const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm, const AlignSurface* sf,
-                  const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
-                  sh_stream_t stream) {
+                  const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int robust, float scale2, int B, double* partials,
+                  size_t partials_bytes, sh_stream_t stream) {
     int R = 0;
+    if (const int rb = robust_check(who, robust, scale2)) return rb;
     const int rc = align_moments_check(who, s, s_sb, M, x, x_sb, rows, n, v_mask, mask_sb, idx_sm, d2_sm, sf, idx_ms, d2_ms, tau2, w_ms, B, partials,
                                        partials_bytes, Sums::N, &R);
     if (rc != SH_OK) return rc;
@@ -460,15 +486,18 @@ int align_moments(const char* who, const float* s, int64_t s_sb, int M, const in
     const int r_sm = ranges_of(M);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)R, (unsigned)B);
-    if (sf) {
-        ShProfScope ps(st, Sums::SCOPE_SURFACE, B, M, n, sf->nF, R);
-        SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, true>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
-                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, *sf, partials);
-    } else {
-        ShProfScope ps(st, Sums::SCOPE, B, M, n, R);
-        SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, false>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
-                     (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, r_sm, AlignSurface{}, partials);
-    }
+    robust_dispatch(robust, [&](auto form) {
+        constexpr int RB = decltype(form)::value;
+        if (sf) {
+            ShProfScope ps(st, RB ? Sums::SCOPE_SURFACE_ROBUST : Sums::SCOPE_SURFACE, B, M, n, sf->nF, R, RB);
+            SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, true, RB>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                         (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, scale2, r_sm, *sf, partials);
+        } else {
+            ShProfScope ps(st, RB ? Sums::SCOPE_ROBUST : Sums::SCOPE, B, M, n, R, RB);
+            SH_LAUNCH_PS(ps, (align_pairs_kernel<Sums, false, RB>), grid, dim3(NT), 0, st, s, (long)s_sb, M, s_count, x, (long)x_sb, rows, n, v_mask,
+                         (long)mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, scale2, r_sm, AlignSurface{}, partials);
+        }
+    });
     SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
     return SH_OK;
 }
@@ -504,7 +533,14 @@ int sh_align_moments(const float* s, int64_t s_sb, int M, const int32_t* s_count
                      const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
                      const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes, sh_stream_t stream) {
     return align_moments<PointSums>("sh_align_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, idx_sm, d2_sm, nullptr,
-                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+                                    idx_ms, d2_ms, tau2, w_ms, SH_ROBUST_NONE, 0.f, B, partials, partials_bytes, stream);
+}
+
+int sh_align_moments_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                     const uint8_t* v_mask, int64_t mask_sb, const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms,
+                     const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes, sh_stream_t stream, int robust, float scale2) {
+    return align_moments<PointSums>("sh_align_moments_robust", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, idx_sm, d2_sm, nullptr,
+                                    idx_ms, d2_ms, tau2, w_ms, robust, scale2, B, partials, partials_bytes, stream);
 }
 
 int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
@@ -513,7 +549,16 @@ int sh_align_moments_surface(const float* s, int64_t s_sb, int M, const int32_t*
                              size_t partials_bytes, sh_stream_t stream) {
     const AlignSurface sf{faces, nF, uv};
     return align_moments<PointSums>("sh_align_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, face, d2, &sf,
-                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+                                    idx_ms, d2_ms, tau2, w_ms, SH_ROBUST_NONE, 0.f, B, partials, partials_bytes, stream);
+}
+
+int sh_align_moments_surface_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                             const uint8_t* v_mask, int64_t mask_sb, const int32_t* faces, int nF, const int32_t* face, const float* uv,
+                             const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials,
+                             size_t partials_bytes, sh_stream_t stream, int robust, float scale2) {
+    const AlignSurface sf{faces, nF, uv};
+    return align_moments<PointSums>("sh_align_moments_surface_robust", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, nullptr, face, d2, &sf,
+                                    idx_ms, d2_ms, tau2, w_ms, robust, scale2, B, partials, partials_bytes, stream);
 }
 
 size_t sh_align_plane_partials_bytes(int B, int M, int n, float w_ms) {
@@ -526,7 +571,15 @@ int sh_align_plane_moments(const float* s, int64_t s_sb, int M, const int32_t* s
                            const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
                            sh_stream_t stream) {
     return align_moments<PlaneSums>("sh_align_plane_moments", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, idx_sm, d2_sm, nullptr,
-                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+                                    idx_ms, d2_ms, tau2, w_ms, SH_ROBUST_NONE, 0.f, B, partials, partials_bytes, stream);
+}
+
+int sh_align_plane_moments_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                           const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* idx_sm, const float* d2_sm,
+                           const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B, double* partials, size_t partials_bytes,
+                           sh_stream_t stream, int robust, float scale2) {
+    return align_moments<PlaneSums>("sh_align_plane_moments_robust", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, idx_sm, d2_sm, nullptr,
+                                    idx_ms, d2_ms, tau2, w_ms, robust, scale2, B, partials, partials_bytes, stream);
 }
 
 int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
@@ -535,7 +588,16 @@ int sh_align_plane_moments_surface(const float* s, int64_t s_sb, int M, const in
                                    double* partials, size_t partials_bytes, sh_stream_t stream) {
     const AlignSurface sf{faces, nF, uv};
     return align_moments<PlaneSums>("sh_align_plane_moments_surface", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, face, d2, &sf,
-                                    idx_ms, d2_ms, tau2, w_ms, B, partials, partials_bytes, stream);
+                                    idx_ms, d2_ms, tau2, w_ms, SH_ROBUST_NONE, 0.f, B, partials, partials_bytes, stream);
+}
+
+int sh_align_plane_moments_surface_robust(const float* s, int64_t s_sb, int M, const int32_t* s_count, const float* x, int64_t x_sb, int rows, int n,
+                                   const uint8_t* v_mask, int64_t mask_sb, const float* tn, const int32_t* faces, int nF, const int32_t* face,
+                                   const float* uv, const float* d2, const int32_t* idx_ms, const float* d2_ms, float tau2, float w_ms, int B,
+                                   double* partials, size_t partials_bytes, sh_stream_t stream, int robust, float scale2) {
+    const AlignSurface sf{faces, nF, uv};
+    return align_moments<PlaneSums>("sh_align_plane_moments_surface_robust", s, s_sb, M, s_count, x, x_sb, rows, n, v_mask, mask_sb, tn, face, d2, &sf,
+                                    idx_ms, d2_ms, tau2, w_ms, robust, scale2, B, partials, partials_bytes, stream);
 }
 
 int sh_align_plane_solve(const double* partials, int M, int n, const int32_t* s_count, float w_ms, int mode, int B, const float* pose_in,

@@ -160,21 +160,23 @@ __global__ __launch_bounds__(256) void nearest_merge_kernel(const int32_t* __res
 }
 
 // One workgroup per body.  Stage 1: thread t sums the terms t, t + 256, ... in order (fp64); stage 2: the 256 sums through the
-// wave butterfly and the four wave sums in order.  counts[b] = (m_b, n_act).
+// wave butterfly and the four wave sums in order.  counts[b] = (m_b, n_act).  ROBUST: a term is rho(min(d2, tau2)) of the header's
+// "Robust terms"; SH_ROBUST_NONE is the plain sum, scale2 unread.
+template <int ROBUST>
 __global__ __launch_bounds__(256) void chamfer_fwd_kernel(const float* __restrict__ d2_sm, int M, const int32_t* __restrict__ s_count,
                                                          const float* __restrict__ d2_ms, int rows, int n,
                                                          const unsigned char* __restrict__ v_mask, long mask_sb, float tau2, float w_ms,
-                                                         float* __restrict__ loss, int32_t* __restrict__ counts) {
+                                                         float scale2, float* __restrict__ loss, int32_t* __restrict__ counts) {
     __shared__ double red[3][4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int m = clamp_count(s_count, b, M);
     const unsigned char* mb = v_mask ? v_mask + (long)b * mask_sb : nullptr;
     double s1 = 0.0, s2 = 0.0, na = 0.0;
-    for (int j = tid; j < m; j += 256) s1 += (double)fminf(d2_sm[(long)b * M + j], tau2);
+    for (int j = tid; j < m; j += 256) s1 += (double)robust_rho<ROBUST>(fminf(d2_sm[(long)b * M + j], tau2), scale2);
     for (int i = tid; i < n; i += 256) {
         if (mb && mb[i] == 0) continue;
         na += 1.0;
-        if (d2_ms) s2 += (double)fminf(d2_ms[(long)b * rows + i], tau2);
+        if (d2_ms) s2 += (double)robust_rho<ROBUST>(fminf(d2_ms[(long)b * rows + i], tau2), scale2);
     }
     s1 = wave_sum_d(s1); s2 = wave_sum_d(s2); na = wave_sum_d(na);
     if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; red[2][tid >> 6] = na; }
@@ -196,16 +198,30 @@ __global__ __launch_bounds__(256) void chamfer_fwd_kernel(const float* __restric
 // swept in tiles of 256: thread t looks at entry j = base + t and keeps it when its (untruncated) index lies in this workgroup's
 // row range; the kept entries are compacted into LDS in ascending j (wave ballot, waves in order), and every thread then walks
 // that short list and adds the terms whose row is its own - ascending j, the order the header states, whatever the scheduling.
+// ROBUST: a kept pair's term carries the weight w(d2) of the header's "Robust terms" - one more LDS list, one fused multiply-add
+// per term in place of the addition; SH_ROBUST_NONE has neither the list nor the weight.
+template <int ROBUST>
+__device__ __forceinline__ float* weight_list() {                       // the list exists in the robust instantiations only
+    if constexpr (ROBUST != 0) {
+        __shared__ float w[256];
+        return w;
+    } else {
+        return nullptr;
+    }
+}
+
+template <int ROBUST>
 __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restrict__ x, long x_sb, int rows, int n,
                                                          const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
                                                          const int32_t* __restrict__ idx_sm, const float* __restrict__ d2_sm,
                                                          const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms,
                                                          const unsigned char* __restrict__ v_mask, long mask_sb,
-                                                         const int32_t* __restrict__ counts, float tau2, float w_ms,
+                                                         const int32_t* __restrict__ counts, float tau2, float w_ms, float scale2,
                                                          const float* __restrict__ gL, float* __restrict__ g_x) {
     __shared__ int wave_n[4];
     __shared__ int list_j[256];
     __shared__ int list_r[256];
+    float* const list_w = weight_list<ROBUST>();
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int i_lo = blockIdx.x * 256, i = i_lo + tid;
     const int m = min(clamp_count(s_count, b, M), counts[2 * b]);
@@ -215,14 +231,18 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
     const bool mine = i < n;
     const float xi0 = mine ? xb[3L * i] : 0.f, xi1 = mine ? xb[3L * i + 1] : 0.f, xi2 = mine ? xb[3L * i + 2] : 0.f;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    auto fetch = [&](int base) {
+    float wt = 0.f, wt_next = 0.f;                                       // the weights of id / id_next, ROBUST only
+    auto fetch = [&](int base, float& w) {
         const int j = base + tid;
         if (j >= m) return -1;
-        return d2_sm[(long)b * M + j] < tau2 ? idx_sm[(long)b * M + j] : -1;
+        const float d = d2_sm[(long)b * M + j];
+        if (!(d < tau2)) return -1;
+        if constexpr (ROBUST != 0) w = robust_weight<ROBUST>(d, scale2);   // kept pairs only: a truncated one costs no division
+        return idx_sm[(long)b * M + j];
     };
-    int id = m > 0 ? fetch(0) : -1;
+    int id = m > 0 ? fetch(0, wt) : -1;
     for (int base = 0; base < m; base += 256) {                         // m is uniform over the workgroup
-        const int id_next = base + 256 < m ? fetch(base + 256) : -1;     // in flight under this tile's compaction
+        const int id_next = base + 256 < m ? fetch(base + 256, wt_next) : -1;   // in flight under this tile's compaction
         const bool hit = (unsigned)(id - i_lo) < 256u;
         const unsigned long long bal = __ballot(hit);
         if (lane == 0) wave_n[wv] = __popcll(bal);
@@ -232,15 +252,22 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
         if (hit) {
             const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
             list_j[pos] = base + tid; list_r[pos] = id - i_lo;
+            if constexpr (ROBUST != 0) list_w[pos] = wt;
         }
         __syncthreads();
         for (int k = 0; k < total; ++k)
             if (list_r[k] == tid && mine) {
                 const long j = list_j[k];
-                a0 += xi0 - sb[3 * j]; a1 += xi1 - sb[3 * j + 1]; a2 += xi2 - sb[3 * j + 2];
+                if constexpr (ROBUST != 0) {
+                    const float w = list_w[k];
+                    a0 = __builtin_fmaf(w, xi0 - sb[3 * j], a0); a1 = __builtin_fmaf(w, xi1 - sb[3 * j + 1], a1);
+                    a2 = __builtin_fmaf(w, xi2 - sb[3 * j + 2], a2);
+                } else {
+                    a0 += xi0 - sb[3 * j]; a1 += xi1 - sb[3 * j + 1]; a2 += xi2 - sb[3 * j + 2];
+                }
             }
         __syncthreads();                                                 // the lists are rewritten by the next tile
-        id = id_next;
+        id = id_next; wt = wt_next;
     }
     if (i >= rows) return;
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
@@ -252,7 +279,8 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
         if (idx_ms && w_ms > 0.f && n_act > 0) {
             const int k = idx_ms[(long)b * rows + i];
             if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) {
-                const float c2 = w_ms * 2.f / (float)n_act;
+                float c2 = w_ms * 2.f / (float)n_act;
+                if constexpr (ROBUST != 0) c2 *= robust_weight<ROBUST>(d2_ms[(long)b * rows + i], scale2);
                 g0 += c2 * (xi0 - sb[3L * k]); g1 += c2 * (xi1 - sb[3L * k + 1]); g2 += c2 * (xi2 - sb[3L * k + 2]);
             }
         }
@@ -268,14 +296,16 @@ __global__ __launch_bounds__(256) void chamfer_bwd_kernel(const float* __restric
 // 256, body), thread = one row i.  The recorded faces are swept in tiles of 256 scan points: thread t looks at entry j = base + t and keeps the
 // corners of its face that lie in this workgroup's row range; the kept (row, weight, q - s) entries are compacted into LDS in
 // ascending j and corner order 0, 1, 2 within a j (wave ballots, waves in order), and every thread then walks that short list
-// and adds the terms whose row is its own - the order the header states, whatever the scheduling.
+// and adds the terms whose row is its own - the order the header states, whatever the scheduling.  ROBUST: the pair's q - s is
+// multiplied by its weight w(d2) once, before the corners' barycentric weights; SH_ROBUST_NONE is the plain walk.
+template <int ROBUST>
 __global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restrict__ x, long x_sb, int rows, int n,
                                                          const float* __restrict__ s, long s_sb, int M, const int32_t* __restrict__ s_count,
                                                          const int32_t* __restrict__ faces, int nF, const int32_t* __restrict__ face,
                                                          const float* __restrict__ d2, const float* __restrict__ uv,
                                                          const int32_t* __restrict__ idx_ms, const float* __restrict__ d2_ms,
                                                          const unsigned char* __restrict__ v_mask, long mask_sb,
-                                                         const int32_t* __restrict__ counts, float tau2, float w_ms,
+                                                         const int32_t* __restrict__ counts, float tau2, float w_ms, float scale2,
                                                          const float* __restrict__ gL, float* __restrict__ g_x) {
 #pragma clang fp contract(off)
     __shared__ int wave_n[4];
@@ -313,6 +343,10 @@ __global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restric
                     ex = __builtin_fmaf(w, acx, v * abx) - apx;          // q - s, the exact negative of the forward pass's residual
                     ey = __builtin_fmaf(w, acy, v * aby) - apy;
                     ez = __builtin_fmaf(w, acz, v * abz) - apz;
+                    if constexpr (ROBUST != 0) {
+                        const float wr = robust_weight<ROBUST>(d2[o], scale2);
+                        ex = wr * ex; ey = wr * ey; ez = wr * ez;
+                    }
                     l[0] = (1.0f - v) - w; l[1] = v; l[2] = w;
                     r[0] = h0 ? i0 - i_lo : -1; r[1] = h1 ? i1 - i_lo : -1; r[2] = h2 ? i2 - i_lo : -1;
                 }
@@ -345,7 +379,8 @@ __global__ __launch_bounds__(256) void surface_bwd_kernel(const float* __restric
         if (idx_ms && w_ms > 0.f && n_act > 0) {
             const int k = idx_ms[(long)b * rows + i];
             if (k >= 0 && k < m && d2_ms[(long)b * rows + i] < tau2) {
-                const float c2 = w_ms * 2.f / (float)n_act;
+                float c2 = w_ms * 2.f / (float)n_act;
+                if constexpr (ROBUST != 0) c2 = c2 * robust_weight<ROBUST>(d2_ms[(long)b * rows + i], scale2);
                 const float xi0 = xb[3L * i], xi1 = xb[3L * i + 1], xi2 = xb[3L * i + 2];
                 g0 = g0 + c2 * (xi0 - sb[3L * k]); g1 = g1 + c2 * (xi1 - sb[3L * k + 1]); g2 = g2 + c2 * (xi2 - sb[3L * k + 2]);
             }
@@ -433,11 +468,14 @@ int nn_search(const char* who, NNParams p, const NNGate* g, int B, int chunks, i
 // face and the surface distance take the place of idx_sm and d2_sm).
 struct BwdSurface { const int32_t* faces; int nF; const float* uv; };
 
-// sh_chamfer_bwd (sf == nullptr) and sh_chamfer_surface_bwd: the checks both make, then the launch.  `who` is the entry point's
-// name in every error text.
+// sh_chamfer_bwd (sf == nullptr), sh_chamfer_surface_bwd and their _robust twins: the checks all make, then the launch of the
+// robust form's instantiation (SH_ROBUST_NONE: the plain kernels under their plain names).  `who` is the entry point's name in
+// every error text.
 int chamfer_bwd(const char* who, const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
                 const int32_t* idx_sm, const float* d2_sm, const BwdSurface* sf, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
-                int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x, sh_stream_t stream) {
+                int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, int robust, float scale2, const float* gL, int B, float* g_x,
+                sh_stream_t stream) {
+    if (const int rc = robust_check(who, robust, scale2)) return rc;
     SH_REQUIRE(x && s && idx_sm && d2_sm && counts && gL && g_x && (!sf || (sf->uv && (sf->faces || sf->nF == 0))), SH_ERR_INVALID_ARG,
                "%s: null pointer", who);
     SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows && (!sf || sf->nF >= 0), SH_ERR_INVALID_ARG,       // each its own text
@@ -451,14 +489,38 @@ int chamfer_bwd(const char* who, const float* x, int64_t x_sb, int rows, int n, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)sh_cdiv(rows, 256), (unsigned)B);
     if (w_ms <= 0.f) idx_ms = nullptr;                                   // the kernels read the model -> scan matches only through idx_ms
-    ShProfScope ps(st, "%s|B=%d M=%d rows=%d", sf ? "surface_bwd_kernel" : "chamfer_bwd_kernel", B, M, rows);
-    if (sf)
-        SH_LAUNCH_PS(ps, surface_bwd_kernel, grid, dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M, s_count, sf->faces, sf->nF, idx_sm,
-                     d2_sm, sf->uv, idx_ms, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, gL, g_x);
-    else
-        SH_LAUNCH_PS(ps, chamfer_bwd_kernel, grid, dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M, s_count, idx_sm, d2_sm, idx_ms,
-                     d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, gL, g_x);
+    const char* name = sf ? (robust ? "surface_bwd_robust_kernel" : "surface_bwd_kernel") : (robust ? "chamfer_bwd_robust_kernel" : "chamfer_bwd_kernel");
+    ShProfScope ps(st, robust ? "%s|B=%d M=%d rows=%d robust=%d" : "%s|B=%d M=%d rows=%d", name, B, M, rows, robust);
+    robust_dispatch(robust, [&](auto form) {
+        constexpr int R = decltype(form)::value;
+        if (sf)
+            SH_LAUNCH_PS(ps, surface_bwd_kernel<R>, grid, dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M, s_count, sf->faces, sf->nF,
+                         idx_sm, d2_sm, sf->uv, idx_ms, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, scale2, gL, g_x);
+        else
+            SH_LAUNCH_PS(ps, chamfer_bwd_kernel<R>, grid, dim3(256), 0, st, x, (long)x_sb, rows, n, s, (long)s_sb, M, s_count, idx_sm, d2_sm,
+                         idx_ms, d2_ms, v_mask, (long)mask_sb, counts, tau2, w_ms, scale2, gL, g_x);
+    });
     SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
+
+// sh_chamfer_fwd and its _robust twin: the checks both make, then the launch of the robust form's instantiation.
+int chamfer_fwd(const char* who, const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n, const uint8_t* v_mask,
+                int64_t mask_sb, float tau2, float w_ms, int robust, float scale2, int B, float* loss, int32_t* counts, sh_stream_t stream) {
+    if (const int rc = robust_check(who, robust, scale2)) return rc;
+    SH_REQUIRE(d2_sm && loss && counts, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "%s: bad size (B %d, M %d, rows %d, n %d)", who, B, M, rows,
+               n);
+    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "%s: w_ms and tau2 must be >= 0 (and not NaN)", who);
+    SH_REQUIRE(!v_mask || mask_sb == 0 || mask_sb >= n, SH_ERR_INVALID_ARG, "%s: mask stride %ld shorter than n", who, (long)mask_sb);
+    if (B == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ShProfScope ps(st, robust ? "chamfer_fwd_robust_kernel|B=%d M=%d n=%d robust=%d" : "chamfer_fwd_kernel|B=%d M=%d n=%d", B, M, n, robust);
+    robust_dispatch(robust, [&](auto form) {
+        SH_LAUNCH_PS(ps, chamfer_fwd_kernel<decltype(form)::value>, dim3((unsigned)B), dim3(256), 0, st, d2_sm, M, s_count,
+                     w_ms > 0.f ? d2_ms : nullptr, rows, n, v_mask, (long)mask_sb, tau2, w_ms, scale2, loss, counts);
+    });
+    SH_CHECK_LAUNCH("chamfer_fwd");
     return SH_OK;
 }
 
@@ -513,25 +575,29 @@ int sh_vertex_normals(const float* x, int64_t x_sb, int n, const int32_t* faces,
 
 int sh_chamfer_fwd(const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n, const uint8_t* v_mask,
                    int64_t mask_sb, float tau2, float w_ms, int B, float* loss, int32_t* counts, sh_stream_t stream) {
-    SH_REQUIRE(d2_sm && loss && counts, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: null pointer");
-    SH_REQUIRE(B >= 0 && M >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: bad size (B %d, M %d, rows %d, n %d)",
-               B, M, rows, n);
-    SH_REQUIRE(w_ms >= 0.f && tau2 >= 0.f, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: w_ms and tau2 must be >= 0 (and not NaN)");
-    SH_REQUIRE(!v_mask || mask_sb == 0 || mask_sb >= n, SH_ERR_INVALID_ARG, "sh_chamfer_fwd: mask stride %ld shorter than n", (long)mask_sb);
-    if (B == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    ShProfScope ps(st, "chamfer_fwd_kernel|B=%d M=%d n=%d", B, M, n);
-    SH_LAUNCH_PS(ps, chamfer_fwd_kernel, dim3((unsigned)B), dim3(256), 0, st, d2_sm, M, s_count, w_ms > 0.f ? d2_ms : nullptr, rows, n, v_mask,
-                 (long)mask_sb, tau2, w_ms, loss, counts);
-    SH_CHECK_LAUNCH("chamfer_fwd");
-    return SH_OK;
+    return chamfer_fwd("sh_chamfer_fwd", d2_sm, M, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, SH_ROBUST_NONE, 0.f, B, loss, counts, stream);
+}
+
+int sh_chamfer_fwd_robust(const float* d2_sm, int M, const int32_t* s_count, const float* d2_ms, int rows, int n, const uint8_t* v_mask,
+                          int64_t mask_sb, float tau2, float w_ms, int B, float* loss, int32_t* counts, sh_stream_t stream, int robust,
+                          float scale2) {
+    return chamfer_fwd("sh_chamfer_fwd_robust", d2_sm, M, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, robust, scale2, B, loss, counts,
+                       stream);
 }
 
 int sh_chamfer_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
                    const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
                    int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x, sh_stream_t stream) {
     return chamfer_bwd("sh_chamfer_bwd", x, x_sb, rows, n, s, s_sb, M, s_count, idx_sm, d2_sm, nullptr, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2,
-                       w_ms, gL, B, g_x, stream);
+                       w_ms, SH_ROBUST_NONE, 0.f, gL, B, g_x, stream);
+}
+
+int sh_chamfer_bwd_robust(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
+                          const int32_t* idx_sm, const float* d2_sm, const int32_t* idx_ms, const float* d2_ms, const uint8_t* v_mask,
+                          int64_t mask_sb, const int32_t* counts, float tau2, float w_ms, const float* gL, int B, float* g_x, sh_stream_t stream,
+                          int robust, float scale2) {
+    return chamfer_bwd("sh_chamfer_bwd_robust", x, x_sb, rows, n, s, s_sb, M, s_count, idx_sm, d2_sm, nullptr, idx_ms, d2_ms, v_mask, mask_sb, counts,
+                       tau2, w_ms, robust, scale2, gL, B, g_x, stream);
 }
 
 int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
@@ -540,7 +606,16 @@ int sh_chamfer_surface_bwd(const float* x, int64_t x_sb, int rows, int n, const 
                            const float* gL, int B, float* g_x, sh_stream_t stream) {
     const BwdSurface sf{faces, nF, uv};
     return chamfer_bwd("sh_chamfer_surface_bwd", x, x_sb, rows, n, s, s_sb, M, s_count, face, d2, &sf, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2,
-                       w_ms, gL, B, g_x, stream);
+                       w_ms, SH_ROBUST_NONE, 0.f, gL, B, g_x, stream);
+}
+
+int sh_chamfer_surface_bwd_robust(const float* x, int64_t x_sb, int rows, int n, const float* s, int64_t s_sb, int M, const int32_t* s_count,
+                                  const int32_t* faces, int nF, const int32_t* face, const float* d2, const float* uv, const int32_t* idx_ms,
+                                  const float* d2_ms, const uint8_t* v_mask, int64_t mask_sb, const int32_t* counts, float tau2, float w_ms,
+                                  const float* gL, int B, float* g_x, sh_stream_t stream, int robust, float scale2) {
+    const BwdSurface sf{faces, nF, uv};
+    return chamfer_bwd("sh_chamfer_surface_bwd_robust", x, x_sb, rows, n, s, s_sb, M, s_count, face, d2, &sf, idx_ms, d2_ms, v_mask, mask_sb, counts,
+                       tau2, w_ms, robust, scale2, gL, B, g_x, stream);
 }
 
 }  // extern "C"

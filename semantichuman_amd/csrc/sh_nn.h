@@ -3,6 +3,7 @@
 #pragma once
 #include "sh_common.h"
 #include <math.h>
+#include <type_traits>
 
 constexpr int NN_WG_SLOTS = 2048;   // workgroups the chip holds at once (256 CUs x 8): the automatic split aims at this many
 
@@ -22,6 +23,54 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 __device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
     const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
     return __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+}
+
+// The robust terms of the header ("Robust terms"), each in its one fixed fp32 form, every operation rounded on its own.  u: a
+// pair's squared distance after truncation; scale2 = sigma^2 > 0.  ROBUST == SH_ROBUST_NONE is the identity / the constant 1 and
+// costs nothing.  Huber is written as a select, so u == 0 never reaches the division.
+template <int ROBUST>
+__device__ __forceinline__ float robust_rho(float u, float scale2) {
+#pragma clang fp contract(off)
+    if constexpr (ROBUST == SH_ROBUST_GEMAN_MCCLURE) {
+        const float t = scale2 / (scale2 + u);
+        return u * t;
+    } else if constexpr (ROBUST == SH_ROBUST_HUBER) {
+        const float r = 2.0f * sqrtf(scale2 * u) - scale2;
+        return u <= scale2 ? u : r;
+    } else {
+        return u;
+    }
+}
+
+template <int ROBUST>
+__device__ __forceinline__ float robust_weight(float u, float scale2) {
+#pragma clang fp contract(off)
+    if constexpr (ROBUST == SH_ROBUST_GEMAN_MCCLURE) {
+        const float t = scale2 / (scale2 + u);
+        return t * t;
+    } else if constexpr (ROBUST == SH_ROBUST_HUBER) {
+        const bool inside = u <= scale2;
+        return inside ? 1.0f : sqrtf(scale2 / (inside ? 1.0f : u));
+    } else {
+        return 1.0f;
+    }
+}
+
+// The checks every `_robust` entry point makes of its two extra arguments.
+static inline int robust_check(const char* who, int robust, float scale2) {
+    SH_REQUIRE(robust == SH_ROBUST_NONE || robust == SH_ROBUST_GEMAN_MCCLURE || robust == SH_ROBUST_HUBER, SH_ERR_INVALID_ARG,
+               "%s: unknown robust form %d", who, robust);
+    SH_REQUIRE(robust == SH_ROBUST_NONE || (scale2 > 0.f && scale2 < INFINITY), SH_ERR_INVALID_ARG,
+               "%s: scale2 must be finite and > 0 with a robust form (got %g)", who, (double)scale2);
+    return SH_OK;
+}
+
+// f(std::integral_constant<int, robust>): how a launcher picks the instantiation of a checked robust form.
+template <class F>
+static inline void robust_dispatch(int robust, F&& f) {
+    if (robust == SH_ROBUST_GEMAN_MCCLURE) f(std::integral_constant<int, SH_ROBUST_GEMAN_MCCLURE>{});
+    else if (robust == SH_ROBUST_HUBER) f(std::integral_constant<int, SH_ROBUST_HUBER>{});
+    else f(std::integral_constant<int, SH_ROBUST_NONE>{});
 }
 
 // The cross product (b - a) x (c - a) of a face's corners, the header's expression ("Vertex normals") in its one fixed form: fp32

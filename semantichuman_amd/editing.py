@@ -229,7 +229,7 @@ def _visibility_cache(what, visibility, visibility_every):
 
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None,
              faces=None, normal_angle=None, normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None,
-             grazing_angle=None, visibility_every=1):
+             grazing_angle=None, visibility_every=1, robust=None, robust_scale=None):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
     The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
@@ -246,6 +246,9 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     w_model_to_scan > 0 usable on them.  The mask is recomputed from the decoded body every `visibility_every`-th step (1: every
     step) and reused in between; the returned Chamfer value uses a fresh one.  A pass costs about half a vertex fit step at B = 64
     (DESIGN 4q): 1 while pose or shape still move, 4 once the fit has settled.
+    robust / robust_scale: None (the default - off: everything above, bit for bit) or the robust data term of scan.chamfer
+    ("geman-mcclure" / "huber" with sigma in the model's normalised units): scan points far from the body - clothing, hair, a
+    floor patch - fade out of value and gradient instead of dominating them.
     Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
@@ -254,6 +257,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     scan._MatchPlan.check_gate("fit_scan", gate_on, normal_angle, faces, scans, trunc)
     scan._MatchPlan.check_visibility("fit_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
     vis_cache = _visibility_cache("fit_scan", visibility, visibility_every)
+    rb = {} if scan._robust_arg("fit_scan", robust, robust_scale) is None else dict(robust=robust, robust_scale=robust_scale)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -266,10 +270,10 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
                 vf = visibility_faces if visibility_faces is not None else (faces if faces is not None else normal_faces)
                 tables.update(visibility_faces=tables["faces"] if vf is faces else _face_table(vf, x_hat))
         if visibility is None:
-            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, normal_angle=normal_angle, gate_on=gate_on, **tables)
+            return scan.chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, normal_angle=normal_angle, gate_on=gate_on, **tables, **rb)
         return scan._chamfer(x_hat, scans, None, vertex_mask, trunc, w_model_to_scan, None, tables["faces"], normal_angle, tables["normal_faces"],
                              gate_on, visibility=visibility, visibility_faces=tables["visibility_faces"], grazing_angle=grazing_angle,
-                             vis_cache=vis_cache)
+                             vis_cache=vis_cache, **rb)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():
@@ -282,7 +286,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
                   normal_angle=None, normal_faces=None, align_on="vertices", align_step="point", gate_on="vertices", visibility=None,
-                  visibility_faces=None, grazing_angle=None, visibility_every=1):
+                  visibility_faces=None, grazing_angle=None, visibility_every=1, robust=None, robust_scale=None):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -318,7 +322,9 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     for bit) or "viewpoint" - one-view scans: scans.viewpoints, in the SCAN's frame, follow the pose; stage 1 is
     scan.align(..., visibility=) (a fresh mask every iteration), the fit uses scan.chamfer(..., visibility=) on the aligned
     batch with the mask recomputed every `visibility_every`-th step, and every in-loop pose update moves the viewpoint with the
-    scan.  visibility_faces / grazing_angle as in scan.chamfer.  No file reader."""
+    scan.  visibility_faces / grazing_angle as in scan.chamfer.  robust / robust_scale: None (the default - off: everything
+    above, bit for bit) or the robust term of scan.chamfer, in all three places: stage 1 is scan.align(..., robust=) (IRLS), the
+    fit's objective is the robust Chamfer value, and every in-loop pose update weighs its pairs the same way.  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -340,6 +346,7 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     surface_gate = scan._MatchPlan.check_gate("register_scan", gate_on, normal_angle, faces, scans, trunc) is not None
     scan._MatchPlan.check_visibility("register_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
     vis_cache = _visibility_cache("register_scan", visibility, visibility_every)
+    rb = {} if scan._robust_arg("register_scan", robust, robust_scale) is None else dict(robust=robust, robust_scale=robust_scale)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -358,25 +365,25 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     vis = {} if visibility is None else dict(visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
     pose, aligned, _ = scan.align(x0, scans, mode=mode, iters=align_iters, init=init, trunc=trunc, w_model_to_scan=w_align,
                                   vertex_mask=vertex_mask, normal_angle=normal_angle, normal_faces=normal_faces,
-                                  faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices", **vis)
+                                  faces=faces if on_surface else None, step=align_step, gate_on=gate_on if on_surface else "vertices", **vis, **rb)
     matches = {} if align_every > 0 else None
     state = {"partials": None}
 
     def objective(x_hat):                                                               # foot-point pose updates read no vertex record
         if visibility is not None:
             return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
-                                 vertex_matches=not on_surface, vis_cache=vis_cache, **vis)
+                                 vertex_matches=not on_surface, vis_cache=vis_cache, **vis, **rb)
         return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
-                             vertex_matches=not on_surface)
+                             vertex_matches=not on_surface, **rb)
 
     def after_step(t):
         if (t + 1) % align_every == 0:
             state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"], surface=on_surface,
-                                                 step=align_step)
+                                                 step=align_step, **rb)
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
                                 after_step=after_step if align_every > 0 else None)
     with torch.no_grad():
         final = scan.chamfer(_decode(model, z_new, z_kps, dummy), aligned, None, vertex_mask, trunc, w_model_to_scan, faces=faces,
-                             normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on, **vis)
+                             normal_angle=normal_angle, normal_faces=normal_faces, gate_on=gate_on, **vis, **rb)
     return z_new, pose, final, losses

@@ -553,31 +553,44 @@ def vertex_visibility(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks
     return vis
 
 
-def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None):
-    """sh_chamfer_fwd -> (loss [B], counts int32 [B, 2])."""
+ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                 # enum sh_robust (0: none)
+
+
+def _robust_entry(entry, robust):
+    """How every wrapper with a `robust` argument picks its C entry point: None -> (entry, no extra arguments), the plain call,
+    exactly as ever; (form id, scale2) -> (entry + "_robust", those two)."""
+    return (entry, ()) if robust is None else (entry + "_robust", (int(robust[0]), float(robust[1])))
+
+
+def chamfer_fwd(d2_sm, s_count, d2_ms, rows, n, v_mask, mask_sb, tau2, w_ms, out=None, robust=None):
+    """sh_chamfer_fwd -> (loss [B], counts int32 [B, 2]).  robust: None, or (form id of ROBUST_FORMS, scale2) - then
+    sh_chamfer_fwd_robust; so in every wrapper below that takes it."""
     B, M = d2_sm.shape
     loss, counts = out if out is not None else (torch.empty(B, dtype=torch.float32, device=d2_sm.device),
                                                 torch.empty((B, 2), dtype=torch.int32, device=d2_sm.device))
-    check(_lib.load().sh_chamfer_fwd(ptr(d2_sm), M, ptr(s_count), ptr(d2_ms), rows, n, ptr(v_mask), mask_sb, tau2, w_ms, B, ptr(loss),
-                                     ptr(counts), stream_ptr()), "sh_chamfer_fwd")
+    entry, extra = _robust_entry("sh_chamfer_fwd", robust)
+    check(getattr(_lib.load(), entry)(ptr(d2_sm), M, ptr(s_count), ptr(d2_ms), rows, n, ptr(v_mask), mask_sb, tau2, w_ms, B, ptr(loss),
+                                      ptr(counts), stream_ptr(), *extra), entry)
     return loss, counts
 
 
-def _chamfer_bwd(entry, x, n, s, s_count, partner, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out):
+def _chamfer_bwd(entry, x, n, s, s_count, partner, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out, robust=None):
     """Both gradient wrappers: C entry point `entry` -> g_x contiguous [B, rows, 3] (every element written).  partner: the C
     arguments of the scan -> model partner, (idx_sm, d2_sm) or (faces, nF, face, d2, uv)."""
+    entry, extra = _robust_entry(entry, robust)
     who = entry[3:]
     B, rows, x_sb = _points(x, who)
     _, M, s_sb = _points(s, who)
     g = out if out is not None else torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
     check(getattr(_lib.load(), entry)(ptr(x), x_sb, rows, n, ptr(s), s_sb, M, ptr(s_count), *partner, ptr(idx_ms), ptr(d2_ms), ptr(v_mask), mask_sb,
-                                      ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g), stream_ptr()), entry)
+                                      ptr(counts), tau2, w_ms, ptr(gL), B, ptr(g), stream_ptr(), *extra), entry)
     return g
 
 
-def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
+def chamfer_bwd(x, n, s, s_count, idx_sm, d2_sm, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None, robust=None):
     """sh_chamfer_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
-    return _chamfer_bwd("sh_chamfer_bwd", x, n, s, s_count, (ptr(idx_sm), ptr(d2_sm)), idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out)
+    return _chamfer_bwd("sh_chamfer_bwd", x, n, s, s_count, (ptr(idx_sm), ptr(d2_sm)), idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out,
+                        robust)
 
 
 def face_normals(x, faces, n, out=None):
@@ -637,10 +650,10 @@ def nearest_surface(q, x, faces, n, q_count=None, v_mask=None, bound=None, chunk
     return face, d2, uv
 
 
-def chamfer_surface_bwd(x, n, s, s_count, faces, face, d2, uv, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None):
+def chamfer_surface_bwd(x, n, s, s_count, faces, face, d2, uv, idx_ms, d2_ms, v_mask, mask_sb, counts, tau2, w_ms, gL, out=None, robust=None):
     """sh_chamfer_surface_bwd -> g_x contiguous [B, rows, 3] (every element written)."""
     return _chamfer_bwd("sh_chamfer_surface_bwd", x, n, s, s_count, (ptr(faces), faces.shape[0], ptr(face), ptr(d2), ptr(uv)), idx_ms, d2_ms,
-                        v_mask, mask_sb, counts, tau2, w_ms, gL, out)
+                        v_mask, mask_sb, counts, tau2, w_ms, gL, out, robust)
 
 
 ALIGN_MODES = {"translation": 0, "rigid": 1, "similarity": 2}   # enum sh_align_mode
@@ -657,9 +670,11 @@ def _surface_partner(who, faces, face, uv, d2, B, M):
     return ptr(faces), nF, ptr(face), ptr(uv), ptr(d2)
 
 
-def _align_moments(entry, per_range, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out, normals=None, surface=None):
+def _align_moments(entry, per_range, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out, normals=None, surface=None,
+                   robust=None):
     """The four moments wrappers: C entry point `entry` -> the ranges' partial sums, fp64 [B, ranges, per_range].  normals: None, or
     (tn, needed) of a point-to-plane call; surface: None, or (faces, face, uv, d2), the partner instead of (idx_sm, d2_sm)."""
+    entry, extra = _robust_entry(entry, robust)
     who = entry[3:]
     B, M, s_sb = _points(s, who)
     _, rows, x_sb = _points(x, who)
@@ -668,21 +683,22 @@ def _align_moments(entry, per_range, s, s_count, x, n, v_mask, mask_sb, idx_sm, 
     lib = _lib.load()
     part = out if out is not None else torch.empty((B, lib.sh_align_ranges(M, n, w_ms), per_range), dtype=torch.float64, device=s.device)
     check(getattr(lib, entry)(ptr(s), s_sb, M, ptr(s_count), ptr(x), x_sb, rows, n, ptr(v_mask), mask_sb, *tn, *partner, ptr(idx_ms), ptr(d2_ms),
-                              tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr()), entry)
+                              tau2, w_ms, B, ptr(part), part.numel() * 8, stream_ptr(), *extra), entry)
     return part
 
 
-def align_moments(s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
+def align_moments(s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None, robust=None):
     """sh_align_moments -> the ranges' partial sums, fp64 [B, ranges, 19] (stage 1; sh_align_solve finishes them)."""
-    return _align_moments("sh_align_moments", ALIGN_PARTIAL, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out)
+    return _align_moments("sh_align_moments", ALIGN_PARTIAL, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out,
+                          robust=robust)
 
 
-def align_moments_surface(s, s_count, x, n, v_mask, mask_sb, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
+def align_moments_surface(s, s_count, x, n, v_mask, mask_sb, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None, robust=None):
     """sh_align_moments_surface -> the ranges' partial sums, fp64 [B, ranges, 19]: sh_align_moments with the scan -> model partner
     the foot point (face, uv) that sh_nearest_surface recorded on the table `faces` (int32 HIP [nF, 3]); d2 is the surface
     distance."""
     return _align_moments("sh_align_moments_surface", ALIGN_PARTIAL, s, s_count, x, n, v_mask, mask_sb, None, None, idx_ms, d2_ms, tau2, w_ms, out,
-                          surface=(faces, face, uv, d2))
+                          surface=(faces, face, uv, d2), robust=robust)
 
 
 def align_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, inc=None, mom=None):
@@ -707,19 +723,19 @@ def _plane_normals(tn, B, n, what, needed):
     return tn
 
 
-def align_plane_moments(s, s_count, x, n, v_mask, mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None):
+def align_plane_moments(s, s_count, x, n, v_mask, mask_sb, tn, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms, out=None, robust=None):
     """sh_align_plane_moments -> the ranges' partial sums of the point-to-plane step, fp64 [B, ranges, 38] (stage 1;
     sh_align_plane_solve finishes them).  tn: the vertex normals, contiguous fp32 [B, n, 3]."""
     return _align_moments("sh_align_plane_moments", ALIGN_PLANE_PARTIAL, s, s_count, x, n, v_mask, mask_sb, idx_sm, d2_sm, idx_ms, d2_ms, tau2, w_ms,
-                          out, normals=(tn, True))
+                          out, normals=(tn, True), robust=robust)
 
 
-def align_plane_moments_surface(s, s_count, x, n, v_mask, mask_sb, tn, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None):
+def align_plane_moments_surface(s, s_count, x, n, v_mask, mask_sb, tn, faces, face, uv, d2, idx_ms, d2_ms, tau2, w_ms, out=None, robust=None):
     """sh_align_plane_moments_surface -> fp64 [B, ranges, 38]: sh_align_plane_moments with the scan -> model partner the foot point
     (face, uv) that sh_nearest_surface recorded on the table `faces` and the normal that face's; tn (the model -> scan pairs'
     normals) may be None when w_ms == 0."""
     return _align_moments("sh_align_plane_moments_surface", ALIGN_PLANE_PARTIAL, s, s_count, x, n, v_mask, mask_sb, None, None, idx_ms, d2_ms, tau2,
-                          w_ms, out, normals=(tn, w_ms > 0), surface=(faces, face, uv, d2))
+                          w_ms, out, normals=(tn, w_ms > 0), surface=(faces, face, uv, d2), robust=robust)
 
 
 def align_plane_solve(part, M, n, s_count, w_ms, mode, pose=None, scale=None, pose_out=None, scale_out=None, sys=None, solved=None):

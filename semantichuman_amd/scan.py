@@ -449,6 +449,52 @@ def closest_points(x, faces, face, uv):
 VERTEX, VERTEX_GATED, SURFACE, SURFACE_GATED = "vertex", "vertex, gated", "surface", "surface, gated"
 
 
+def _robust_arg(what, robust, robust_scale):
+    """`robust` / `robust_scale` checked -> None (no robust term: the plain kernels) or (form id, scale2 = sigma^2) as the `_robust`
+    entry points take them.  ValueError on an unknown name, a scale without a name, a name without a scale, or a scale that is
+    not a positive finite number."""
+    if robust is None:
+        if robust_scale is not None:
+            raise ValueError("%s: robust_scale given without robust (one of %s)" % (what, sorted(ops.ROBUST_FORMS)))
+        return None
+    if not isinstance(robust, str) or robust not in ops.ROBUST_FORMS:
+        raise ValueError("%s: robust must be None or one of %s, got %r" % (what, sorted(ops.ROBUST_FORMS), robust))
+    if robust_scale is None:
+        raise ValueError("%s: robust=%r needs robust_scale (sigma, in the model's normalised units)" % (what, robust))
+    try:
+        sigma = float(robust_scale)
+    except (TypeError, ValueError):
+        sigma = math.nan
+    scale2 = sigma * sigma
+    if not (sigma > 0.0 and math.isfinite(scale2) and float(np.float32(scale2)) > 0.0 and math.isfinite(float(np.float32(scale2)))):
+        raise ValueError("%s: robust_scale must be a positive finite number, got %r" % (what, robust_scale))
+    return ops.ROBUST_FORMS[robust], scale2
+
+
+def robust_weights(d2, robust, robust_scale, trunc=None):
+    """The per-pair weights of recorded squared distances d2 under a robust term, for inspection: w = d rho / d u at u = d2 in the
+    fp32 expressions of include/sh_kernels.h ("Robust terms") for the kept pairs (d2 < trunc^2, all finite ones without trunc),
+    0 for the truncated ones.  Plain torch in fp32 on whatever device d2 lives on; the kernels compute the same expressions
+    themselves and never call this.  robust=None gives 1 for every kept pair.  Errors as in `chamfer`."""
+    rb = _robust_arg("robust_weights", robust, robust_scale)
+    if trunc is not None and not float(trunc) > 0.0:
+        raise ValueError("robust_weights: trunc must be > 0")
+    u = torch.as_tensor(d2, dtype=torch.float32)
+    tau2 = torch.tensor(math.inf if trunc is None else float(trunc) ** 2, dtype=torch.float32, device=u.device)
+    one = torch.ones_like(u)
+    if rb is None:
+        w = one
+    else:
+        s2 = torch.tensor(rb[1], dtype=torch.float32, device=u.device)
+        if rb[0] == ops.ROBUST_FORMS["geman-mcclure"]:
+            t = s2 / (s2 + u)
+            w = t * t
+        else:
+            inside = u <= s2
+            w = torch.where(inside, one, torch.sqrt(s2 / torch.where(inside, one, u)))
+    return torch.where(u < tau2, w, torch.zeros_like(u))
+
+
 class _MatchPlan:
     """What one call of `chamfer` or `align` matches, resolved once from its arguments - every check of them included, in the order
     the docstrings promise - and the one routine, `search`, that runs the searches of a forward pass or an ICP iteration.
@@ -463,10 +509,13 @@ class _MatchPlan:
 
     visibility: None, or "viewpoint" - then `see(x, view)` replaces v_mask by the given mask AND the vertices the sensor at `view`
     sees (sh_vertex_visibility on `vis_table`: visibility_faces, else faces, else normal_faces), with mask_sb = n; searches, loss,
-    gradient, moments and `pose_update` read it as they read a given mask.  cos_g: the grazing bound, or None."""
+    gradient, moments and `pose_update` read it as they read a given mask.  cos_g: the grazing bound, or None.
+
+    robust: None, or (form id, scale2) of the robust term (`_robust_arg`) - what `loss`, the backward pass and `align`'s pose steps
+    hand to the wrappers of ops; None takes the plain entry points."""
 
     def __init__(self, what, x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step="point", record=False,
-                 visibility=None, visibility_faces=None, grazing_angle=None):
+                 visibility=None, visibility_faces=None, grazing_angle=None, robust=None, robust_scale=None):
         self.scans, B, self.rows, self.n = pair
         self.check_visibility(what, visibility, visibility_faces, faces, normal_faces, grazing_angle, self.scans)
         self.w = float(w_model_to_scan)
@@ -475,6 +524,7 @@ class _MatchPlan:
         if trunc is not None and not float(trunc) > 0.0:
             raise ValueError("%s: trunc must be > 0" % what)
         self.tau2 = math.inf if trunc is None else float(trunc) ** 2
+        self.robust = _robust_arg(what, robust, robust_scale)
         self.v_mask, self.mask_sb = ops._mask_arg(vertex_mask, B, self.n, x.device)
 
         def table(f):
@@ -632,7 +682,7 @@ class _MatchPlan:
     def loss(self, m, scans, out=None):
         """sh_chamfer_fwd on what `search` found -> (loss [B], counts)."""
         return ops.chamfer_fwd(m["d2_sm"] if self.surface is None else m["d2_surface"], scans.counts, m["d2_ms"], self.rows, self.n, self.v_mask,
-                               self.mask_sb, self.tau2, self.w, out=out)
+                               self.mask_sb, self.tau2, self.w, out=out, **({} if self.robust is None else dict(robust=self.robust)))
 
 
 class _Chamfer(torch.autograd.Function):
@@ -663,12 +713,12 @@ class _Chamfer(torch.autograd.Function):
         p = ctx.plan
         bwd = ops.chamfer_bwd if p.surface is None else ops.chamfer_surface_bwd
         g = bwd(x, p.n, p.scans.points, p.scans.counts, *partner, idx_ms, d2_ms, p.v_mask, p.mask_sb, counts, p.tau2, p.w,
-                gL.to(torch.float32).contiguous())
+                gL.to(torch.float32).contiguous(), **({} if p.robust is None else dict(robust=p.robust)))
         return g, None, None, None, None
 
 
 def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=0.0, matches=None, faces=None, normal_angle=None,
-            normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None, grazing_angle=None):
+            normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None, grazing_angle=None, robust=None, robust_scale=None):
     """Chamfer distance between decoded bodies and their scans, one value per body [B], differentiable w.r.t. x_hat:
 
         L[b] = mean_j min(|s_j - nn_x(s_j)|^2, trunc^2)  +  w_model_to_scan * mean_{i active} min(|x_i - nn_s(x_i)|^2, trunc^2)
@@ -719,19 +769,29 @@ def chamfer(x_hat, scans, n=None, vertex_mask=None, trunc=None, w_model_to_scan=
     no term, so w_model_to_scan > 0 becomes usable on one-view scans.  visibility_faces: the occluding triangles (default:
     faces, else normal_faces; one of the three is needed).  grazing_angle: None, or degrees in (0, 90] - a vertex must also face
     the sensor to within that angle.  A body whose viewpoint row holds a NaN is a full scan: no vertex of it is hidden.  The
-    scan's own points are not tested for visibility."""
+    scan's own points are not tested for visibility.
+
+    robust: None (the default - off: everything above, bit for bit, the same launches) or "geman-mcclure" / "huber", with
+    robust_scale = sigma > 0 in the model's normalised units (both or neither).  Every term of both directions is then
+    rho(min(d2, trunc^2)) instead of min(d2, trunc^2) - Geman-McClure rho = u sigma^2 / (sigma^2 + u), bounded by sigma^2, or
+    Huber on the distance, rho = u up to sigma^2 and 2 sigma sqrt(u) - sigma^2 beyond (include/sh_kernels.h, "Robust terms") - and
+    a kept pair pulls with w = d rho / d u times its plain gradient (`robust_weights`), the corners of a foot point included.
+    Far points - hair, clothing, a floor patch, flying pixels - fade out smoothly instead of dominating or being cut at trunc;
+    trunc keeps its meaning (and a gate still needs it).  Works with every other argument.  ValueError for an unknown name, a
+    scale without a name, a name without a scale, or a scale that is not a positive finite number."""
     return _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
-                    visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
+                    visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle, robust=robust,
+                    robust_scale=robust_scale)
 
 
 def _chamfer(x_hat, scans, n, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on, vertex_matches=True,
-             visibility=None, visibility_faces=None, grazing_angle=None, vis_cache=None):
+             visibility=None, visibility_faces=None, grazing_angle=None, vis_cache=None, robust=None, robust_scale=None):
     """`chamfer`, and what editing.fit_scan / register_scan may add: vertex_matches=False when the pose update will read the foot
     points, so that a face-normal-gated pass skips the vertex search it would run for `matches` alone; vis_cache, a dict
     (every=, t=0, mask=None), makes a pass reuse the last visibility mask unless t is a multiple of `every`."""
     plan = _MatchPlan("chamfer", x_hat, _check_pair(x_hat, scans, n, "chamfer"), vertex_mask, trunc, w_model_to_scan, faces, normal_angle,
                       normal_faces, gate_on, record=matches is not None, visibility=visibility, visibility_faces=visibility_faces,
-                      grazing_angle=grazing_angle)
+                      grazing_angle=grazing_angle, robust=robust, robust_scale=robust_scale)
     if visibility is None:
         return _Chamfer.apply(x_hat, plan, matches, vertex_matches)
     return _Chamfer.apply(x_hat, plan, matches, vertex_matches, vis_cache)
@@ -887,7 +947,8 @@ def _plane_normals(what, m, surface):
     return tn
 
 
-def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None, surface=False, step="point", solved=None):
+def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None, surface=False, step="point", solved=None, robust=None,
+                robust_scale=None):
     """One closed-form pose step from recorded matches, no search: moments of the matched pairs (`matches`, as `chamfer(...,
     matches=)` or `align` fill it, found on `aligned`), the pose increment that minimises the same weighted squared distances,
     composed into `pose` in place, and `aligned.points` overwritten with the ORIGINAL `scans` under the new pose.  Three
@@ -909,8 +970,15 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
 
     When `aligned` carries viewpoints (the batch `align(..., visibility="viewpoint")` returns does; `Pose.apply` gives none), they
     are overwritten with the ORIGINAL `scans.viewpoints` under the new pose - the sensor moves with its scan (one more
-    sh_transform_points over [B, 1, 3])."""
+    sh_transform_points over [B, 1, 3]).
+
+    robust / robust_scale: None (the default: everything above, bit for bit, the same launches) or the robust term of `chamfer` -
+    one IRLS step: every kept pair enters the moments (or the normal equations of step="plane") with the weight
+    `robust_weights` gives the distance recorded for it, so the increment minimises the weighted squared distances; the solve is
+    unchanged (sh_align_moments_robust and its three twins).  Pass what the matches were recorded with.  ValueError as in
+    `chamfer`."""
     m = matches
+    rb = _robust_arg("pose_update", robust, robust_scale)
     if step not in ("point", "plane"):
         raise ValueError("pose_update: step must be 'point' or 'plane'")
     if surface and any(m.get(k) is None for k in ("face", "uv", "d2_surface", "faces")):
@@ -921,7 +989,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     partner = (m["faces"], m["face"], m["uv"], m["d2_surface"]) if surface else (m["idx_sm"], m["d2_sm"])
     moments = ((ops.align_moments, ops.align_moments_surface), (ops.align_plane_moments, ops.align_plane_moments_surface))[plane][bool(surface)]
     part = moments(aligned.points, scans.counts, m["x"], m["n"], m["v_mask"], m["mask_sb"], *normals, *partner, m["idx_ms"], m["d2_ms"], m["tau2"],
-                   m["w_ms"], out=partials)
+                   m["w_ms"], out=partials, **({} if rb is None else dict(robust=rb)))
     solve = (aligned.points.shape[1], m["n"], scans.counts, m["w_ms"], mode, pose.packed, pose.scale, pose.packed, pose.scale)
     if plane:
         ops.align_plane_solve(part, *solve, solved=solved)
@@ -937,7 +1005,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
 
 def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_model_to_scan=1.0, n=None, vertex_mask=None, chunks=0,
           normal_angle=None, normal_faces=None, faces=None, cull=True, step="point", gate_on="vertices", visibility=None,
-          visibility_faces=None, grazing_angle=None):
+          visibility_faces=None, grazing_angle=None, robust=None, robust_scale=None):
     """Batched ICP: the pose (scan frame -> model frame) that brings each scan onto its body x[b], by alternating the
     nearest-point search with the closed-form pose of the matched pairs.  Pairs and weights are those of `chamfer` with the same
     trunc / w_model_to_scan / n / vertex_mask, so every iteration lowers that Chamfer value (up to fp32 rounding).
@@ -989,7 +1057,15 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
     that moves the scan, on [B, 1, 3]) and recomputes the mask - x is fixed, the sensor moves - before the searches.  The returned
     batch carries the viewpoints in the model's frame, and the returned pose carries `visible`, bool [iters, B, n]: row k is the
     mask iteration k used.  With it w_model_to_scan = 1 works on one-view scans: the unseen side of the model pulls nothing.
-    The start pose `init="moments"` still takes the centroid and radius of the whole model."""
+    The start pose `init="moments"` still takes the centroid and radius of the whole model.
+
+    robust / robust_scale: None (the default - off: everything above, bit for bit, the same launches) or the robust term of
+    `chamfer` ("geman-mcclure" / "huber" with sigma): ICP becomes iteratively re-weighted least squares.  The logged value is the
+    robust Chamfer value, and every pose step weighs a kept pair by `robust_weights` of the distance this iteration's search
+    recorded for it (`pose_update(..., robust=)`), with step="point" and step="plane", vertex and surface partners alike.  Scan
+    points with no counterpart on the model - a floor patch, a hand-held object - then stop biasing the pose without a trunc
+    tight enough to cut them.  sigma is fixed for the run (no annealing: run twice for a coarse and a fine pass); the start pose
+    `init="moments"` is not robust - it still takes the centroid and radius of the whole scan."""
     pair = _check_pair(x, scans, n, "align")
     if mode not in ops.ALIGN_MODES:
         raise ValueError("align: mode must be one of %s" % sorted(ops.ALIGN_MODES))
@@ -998,7 +1074,8 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         raise ValueError("align: iters must be >= 0")
     x = x.detach()
     plan = _MatchPlan("align", x, pair, vertex_mask, trunc, w_model_to_scan, faces, normal_angle, normal_faces, gate_on, step,
-                      visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle)
+                      visibility=visibility, visibility_faces=visibility_faces, grazing_angle=grazing_angle, robust=robust, robust_scale=robust_scale)
+    rb = {} if plan.robust is None else dict(robust=robust, robust_scale=robust_scale)
     scans, B, rows, n = pair
     w, dev = plan.w, x.device
     if isinstance(init, Pose):
@@ -1043,5 +1120,5 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         m = plan.search(x, aligned, (tn, qn, fn), (sm, sf, ms), chunks, cull, vertex_matches=False)
         plan.loss(m, scans, out=(log[k], counts))
         part = pose_update(pose, scans, aligned, m, mode, partials=part, surface=plan.surface is not None, step=step,
-                           solved=None if solved is None else solved[k])
+                           solved=None if solved is None else solved[k], **rb)
     return pose, aligned, log
