@@ -1026,6 +1026,64 @@ SH_API int sh_align_plane_moments_surface_robust(const float* s, int64_t s_sb, i
                                                  float scale2);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth images: a depth map as a scan - the camera-frame point of every usable pixel, its normal from the pixel grid, and the
+ * rows packed per body in a fixed order (no reference counterpart).  Deterministic: no atomics of any kind, every output element
+ * written by one plain store; the bits depend on neither batch, padding nor launch shape.
+ *
+ * Inputs.  depth: contiguous [B][H][W], fp32 (dtype SH_DEPTH_F32) or 16-bit unsigned words (SH_DEPTH_U16, raw sensor units; a
+ * buffer of int16 is read as unsigned).  intr: fp32 [B][4] = (fx, fy, cx, cy) per body, pinhole, no distortion.  mask: uint8
+ * [B][H][W] or NULL, 0 = "not the subject".  z_near, z_far: the accepted range (-inf / +inf: none).  max_step: the largest depth
+ * difference between grid neighbours of one surface (+inf: none).  stride >= 1.  Pixel (u, v): column u, row v.
+ * Everything below is fp32 with every operation rounded on its own (no contraction) and a correctly rounded division, except
+ * the normal, which is fp64 as marked.
+ *     z      = fl((float)raw * depth_scale)                                         (both input types)
+ *     valid  iff z is finite and z > 0, z_near <= z <= z_far, raw != 0 for 16-bit input, and mask != 0 where a mask is given
+ *     X = fl(fl(fl((float)u - cx) * z) / fx);   Y = fl(fl(fl((float)v - cy) * z) / fy);   Z = z;      P = (X, Y, Z)
+ * The frame is the camera's; the viewpoint is the origin.
+ * Usable neighbour of pixel c: inside the image, valid, and fabsf(z_nb - z_c) <= max_step.  A depth step between neighbours is
+ * what a silhouette (and a flying pixel on it) looks like: no tangent crosses one.
+ * Tangents, differences component-wise in fp32.  Horizontal, over L = (u - 1, v) and R = (u + 1, v):
+ *     dx = P_R - P_L  when both are usable;  else P_R - P_c;  else P_c - P_L;  else none
+ * vertical dy by the same rule over (u, v - 1) and (u, v + 1).  Tangents always read the full-resolution neighbours, whatever the
+ * stride.
+ * Normal, fp64: the components of dx, dy and P_c widened, products of two such values exact.
+ *     c    = dx x dy       each component one rounded subtraction of two exact products
+ *     len2 = (c_x c_x + c_y c_y) + c_z c_z
+ *     unknown - a row of exact zeros, as everywhere in this library - when a tangent is missing or !(len2 > 0)
+ *     n    = c / sqrt(len2), negated when (c_x X + c_y Y) + c_z Z > 0 (it then points away from the camera), each component
+ *            rounded to fp32 once
+ * Kept: valid, u % stride == 0 and v % stride == 0, and - when drop_isolated != 0 - the normal is known.
+ * Order of the kept rows, part of the contract: SH_DEPTH_TILE x SH_DEPTH_TILE pixel tiles in row-major tile order; inside a
+ * tile the Z-order of (u & 15, v & 15): bit k of u is bit 2k of the rank, bit k of v bit 2k + 1.  Tile order on the image is a
+ * space-filling order on the surface - what the surface search's cull lives on.
+ *
+ * sh_depth_count -> counts int32 [B], the kept pixels per body, and in `workspace` (sh_depth_workspace(B, H, W) bytes, int32
+ * [B][tiles]) the first row of every tile.  sh_depth_points, given the same inputs, that workspace, the counts and a width
+ * M >= max_count (the largest count, as the caller read it), -> points fp32 [B][M][3], normals fp32 [B][M][3], pixel int32 [B][M]
+ * = v * W + u; rows at or beyond a body's count hold zeros in points and normals and -1 in pixel.  No row >= M is ever written.
+ *
+ * How it is computed.  One workgroup of 256 threads per tile, thread = Z-rank: the 18 x 18 tile with its halo goes into LDS in
+ * coalesced rows as z (NaN where not valid, so that one compare decides "usable"), and the five points are formed from LDS.
+ * (1) The count pass: a wave ballot of "kept", popcount, the four wave totals combined through LDS -> the tile's count.  (2) A
+ * per-body exclusive scan of the tile counts, one workgroup per body looping over the tiles, in place; it also writes counts.
+ * (3) The emit pass recomputes the pixel; its row is the tile's first row plus its rank among the tile's kept pixels from the
+ * ballot prefix; the workgroups of a body also share out the padding rows.  Memory-bound: the depth (and mask) is read twice,
+ * every output written once.
+ * B == 0 or H * W == 0: SH_OK, nothing launched.  Null pointers (mask excepted), negative sizes, stride < 1, M < max_count or an
+ * unknown dtype: SH_ERR_INVALID_ARG before the device is touched; a workspace that is too small: SH_ERR_WORKSPACE.
+ */
+enum sh_depth_dtype { SH_DEPTH_F32 = 0, SH_DEPTH_U16 = 1 };
+#define SH_DEPTH_TILE 16
+SH_API size_t sh_depth_workspace(int B, int H, int W);
+SH_API int sh_depth_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W,
+                          float z_near, float z_far, float max_step, int drop_isolated, int stride, int32_t* counts, void* workspace,
+                          size_t workspace_bytes, sh_stream_t stream);
+SH_API int sh_depth_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W,
+                           float z_near, float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts,
+                           int max_count, int M, const void* workspace, size_t workspace_bytes, float* points, float* normals,
+                           int32_t* pixel, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

@@ -1,0 +1,251 @@
+// Depth images as scans (include/sh_kernels.h, "Depth images"): per pixel the camera-frame point, the normal from the grid
+// neighbours, and the kept pixels packed per body in tile / Z-order.  The reference has no counterpart.  One workgroup per
+// 16 x 16 tile, thread = Z-rank inside the tile, so the ballot prefix of "kept" IS the rank among the tile's rows: a count pass,
+// a per-body scan of the tile counts and an emit pass that recomputes the pixel - no atomics, every output element one plain
+// store, nothing that depends on the batch, the padding or the launch shape.
+#include <limits.h>
+#include "sh_common.h"
+
+#pragma clang fp contract(off)          // the header's expressions: every operation rounded on its own, in the whole file
+
+namespace {
+
+constexpr int TILE = SH_DEPTH_TILE;
+constexpr int NT = TILE * TILE;         // threads per workgroup: one per pixel of the tile
+constexpr int HALO = TILE + 2;          // the tile with one pixel around it
+// LDS row stride in floats.  The 32 lanes of one ds_read_b32 group are ranks 32 g .. 32 g + 31 = 8 columns x 4 rows of the tile:
+// with 24 the four rows start at banks 0, 24, 16, 8 - no two lanes on one bank, for the centre and for every neighbour (a
+// uniform shift).  With 18 rows 0 / 2 and 1 / 3 would share four banks each.
+constexpr int LROW = 24;
+static_assert(TILE == 16, "the Z-rank below is 4 + 4 bits");
+
+struct DepthArgs {
+    const void* depth; const float* intr; const uint8_t* mask;
+    int H, W, tiles_x, tiles;
+    float depth_scale, z_near, z_far, max_step;
+    int drop_isolated, stride;
+};
+struct P3 { float x, y, z; };
+
+// bits 0, 2, 4, 6 of r -> a 4-bit number: the u of a Z-rank (its v: the same of r >> 1)
+__device__ __forceinline__ int even_bits(int r) {
+    r &= 0x55;
+    r = (r | (r >> 1)) & 0x33;
+    return (r | (r >> 2)) & 0x0f;
+}
+
+__device__ __forceinline__ bool raw_ok(float) { return true; }
+__device__ __forceinline__ bool raw_ok(uint16_t raw) { return raw != 0; }
+
+// The tile at (u0, v0) with its halo -> zt[HALO][LROW]: z where the pixel is valid, NaN where it is not or lies outside the
+// image.  Consecutive threads read consecutive pixels of a row.
+template <typename T>
+__device__ __forceinline__ void load_tile(const DepthArgs& a, int b, int u0, int v0, float* zt) {
+    const long body = (long)b * a.H * a.W;
+    const T* d = static_cast<const T*>(a.depth) + body;
+    const uint8_t* m = a.mask ? a.mask + body : nullptr;
+    for (int i = threadIdx.x; i < HALO * HALO; i += NT) {
+        const int r = i / HALO, c = i - r * HALO;
+        const int u = u0 - 1 + c, v = v0 - 1 + r;
+        float z = NAN;
+        if (u >= 0 && u < a.W && v >= 0 && v < a.H) {
+            const long p = (long)v * a.W + u;
+            const T raw = d[p];
+            const float zz = (float)raw * a.depth_scale;
+            const bool ok = zz > 0.f && zz < INFINITY && a.z_near <= zz && zz <= a.z_far && raw_ok(raw) && (!m || m[p] != 0);   // a NaN compares false
+            z = ok ? zz : NAN;
+        }
+        zt[r * LROW + c] = z;
+    }
+}
+
+__device__ __forceinline__ P3 unproject(int u, int v, float z, float fx, float fy, float cx, float cy) {
+    return {(((float)u - cx) * z) / fx, (((float)v - cy) * z) / fy, z};
+}
+
+// The header's tangent rule over the lower and upper neighbour of c: hi - lo, else hi - c, else c - lo; false: none.
+__device__ __forceinline__ bool tangent(const P3& lo, bool has_lo, const P3& c, const P3& hi, bool has_hi, P3& t) {
+    const P3 a = has_hi ? hi : c, b = has_lo ? lo : c;
+    t = {a.x - b.x, a.y - b.y, a.z - b.z};
+    return has_lo || has_hi;
+}
+
+// grid (tile, body).  EMIT = false, the count pass: tile_row[b][tile] = the tile's kept pixels.  EMIT = true: tile_row holds the
+// tile's first row (depth_scan_kernel), and the kept pixels and the body's padding are written.
+template <typename T, bool EMIT>
+__global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restrict__ tile_row, const int32_t* __restrict__ counts, int M,
+                                                  float* __restrict__ points, float* __restrict__ normals, int32_t* __restrict__ pixel) {
+    __shared__ float zt[HALO * LROW];
+    __shared__ int wsum[NT / 64];
+    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    load_tile<T>(a, b, tx * TILE, ty * TILE, zt);
+    __syncthreads();
+    const int lu = even_bits(tid), lv = even_bits(tid >> 1);
+    const int u = tx * TILE + lu, v = ty * TILE + lv;
+    const float* zc = zt + (lv + 1) * LROW + (lu + 1);
+    const float z = zc[0];
+    const bool valid = z == z;                                           // NaN: not valid, or outside the image
+    bool kept = valid && u % a.stride == 0 && v % a.stride == 0;
+    P3 p = {0.f, 0.f, 0.f};
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if (EMIT || a.drop_isolated) {                                       // uniform
+        const float* k = a.intr + 4L * b;
+        const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+        const float zl = zc[-1], zr = zc[1], zu = zc[-LROW], zd = zc[LROW];
+        p = unproject(u, v, z, fx, fy, cx, cy);
+        P3 dx, dy;                                                       // usable: the compare is false for a NaN on either side
+        const bool has_dx = tangent(unproject(u - 1, v, zl, fx, fy, cx, cy), fabsf(zl - z) <= a.max_step, p,
+                                    unproject(u + 1, v, zr, fx, fy, cx, cy), fabsf(zr - z) <= a.max_step, dx);
+        const bool has_dy = tangent(unproject(u, v - 1, zu, fx, fy, cx, cy), fabsf(zu - z) <= a.max_step, p,
+                                    unproject(u, v + 1, zd, fx, fy, cx, cy), fabsf(zd - z) <= a.max_step, dy);
+        const double ax = dx.x, ay = dx.y, az = dx.z, bx = dy.x, by = dy.y, bz = dy.z;
+        const double c0 = ay * bz - az * by, c1 = az * bx - ax * bz, c2 = ax * by - ay * bx;
+        const double len2 = (c0 * c0 + c1 * c1) + c2 * c2;
+        const bool known = valid && has_dx && has_dy && len2 > 0.0;      // a NaN compares false
+        const double len = sqrt(len2);
+        const bool away = (c0 * (double)p.x + c1 * (double)p.y) + c2 * (double)p.z > 0.0;
+        const double n0 = c0 / len, n1 = c1 / len, n2 = c2 / len;
+        nx = known ? (float)(away ? -n0 : n0) : 0.f;
+        ny = known ? (float)(away ? -n1 : n1) : 0.f;
+        nz = known ? (float)(away ? -n2 : n2) : 0.f;
+        if (a.drop_isolated) kept = kept && known;
+    }
+    // rank among the tile's kept pixels: lanes below in the wave (ballot), waves below in the workgroup (LDS)
+    const int lane = tid & 63, w = sh_wave_id();
+    const unsigned long long bal = __ballot(kept);
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) {
+        const int s = wsum[i];
+        before += i < w ? s : 0;
+        total += s;
+    }
+    const long slot = (long)b * a.tiles + tile;
+    if (!EMIT) {
+        if (tid == 0) tile_row[slot] = total;
+        return;
+    }
+    const long body = (long)b * M;
+    if (kept) {
+        const int row = tile_row[slot] + before + __popcll(bal & ((1ull << lane) - 1ull));
+        if (row < M) {                                                   // holds whenever M >= the count; never a store beyond the body
+            const long o = body + row;
+            points[3 * o] = p.x; points[3 * o + 1] = p.y; points[3 * o + 2] = p.z;
+            normals[3 * o] = nx; normals[3 * o + 1] = ny; normals[3 * o + 2] = nz;
+            pixel[o] = v * a.W + u;
+        }
+    }
+    // the padding rows of the body, shared out over its workgroups
+    for (long j = (long)max(counts[b], 0) + (long)tile * NT + tid; j < M; j += (long)a.tiles * NT) {
+        const long o = body + j;
+        points[3 * o] = 0.f; points[3 * o + 1] = 0.f; points[3 * o + 2] = 0.f;
+        normals[3 * o] = 0.f; normals[3 * o + 1] = 0.f; normals[3 * o + 2] = 0.f;
+        pixel[o] = -1;
+    }
+}
+
+// grid (body).  tile_row[b][0 .. tiles): counts -> their exclusive prefix sums, in place; counts[b] = the total.  256 tiles per
+// round: an inclusive wave scan by shuffles, the wave totals through LDS, the carry in a register.  Integer sums: no order.
+__global__ __launch_bounds__(NT) void depth_scan_kernel(int32_t* __restrict__ tile_row, int tiles, int32_t* __restrict__ counts) {
+    __shared__ int wsum[NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = sh_wave_id();
+    int32_t* t = tile_row + (long)b * tiles;
+    int carry = 0;
+    for (int base = 0; base < tiles; base += NT) {                       // uniform
+        const int i = base + tid;
+        const int own = i < tiles ? t[i] : 0;
+        int s = own;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int below = __shfl_up(s, o, 64);
+            s += lane >= o ? below : 0;
+        }
+        if (lane == 63) wsum[w] = s;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; ++k) {
+            const int ws = wsum[k];
+            before += k < w ? ws : 0;
+            total += ws;
+        }
+        if (i < tiles) t[i] = carry + before + s - own;
+        carry += total;
+        __syncthreads();                                                 // wsum is rewritten in the next round
+    }
+    if (tid == 0) counts[b] = carry;
+}
+
+int tiles_of(int H, int W) { return sh_cdiv(H, TILE) * sh_cdiv(W, TILE); }
+
+// What both entry points ask of the inputs they share; `who` names the caller in the message.
+int check_inputs(const char* who, const void* depth, int dtype, const float* intr, int B, int H, int W, int stride) {
+    SH_REQUIRE(dtype == SH_DEPTH_F32 || dtype == SH_DEPTH_U16, SH_ERR_INVALID_ARG, "%s: unknown depth dtype %d", who, dtype);
+    SH_REQUIRE(depth && intr, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(B >= 0 && H >= 0 && W >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, H %d, W %d)", who, B, H, W);
+    SH_REQUIRE(stride >= 1, SH_ERR_INVALID_ARG, "%s: stride = %d, must be at least 1", who, stride);
+    SH_REQUIRE(B <= 65535 && (long)H * W <= INT_MAX, SH_ERR_UNSUPPORTED, "%s: B or H * W too large", who);
+    return SH_OK;
+}
+
+template <bool EMIT>
+void launch_tiles(hipStream_t st, int dtype, const DepthArgs& a, int B, int32_t* tile_row, const int32_t* counts, int M, float* points,
+                  float* normals, int32_t* pixel) {
+    ShProfScope ps(st, "%s|B=%d H=%d W=%d u16=%d", EMIT ? "depth_emit_kernel" : "depth_count_kernel", B, a.H, a.W, dtype == SH_DEPTH_U16);
+    const dim3 grid((unsigned)a.tiles, (unsigned)B);
+    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_kernel<uint16_t, EMIT>), grid, dim3(NT), 0, st, a, tile_row, counts, M, points, normals, pixel);
+    else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT>), grid, dim3(NT), 0, st, a, tile_row, counts, M, points, normals, pixel);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sh_depth_workspace(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)B * tiles_of(H, W) * sizeof(int32_t);
+}
+
+int sh_depth_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
+                   float z_far, float max_step, int drop_isolated, int stride, int32_t* counts, void* workspace, size_t workspace_bytes,
+                   sh_stream_t stream) {
+    const int rc = check_inputs("sh_depth_count", depth, dtype, intr, B, H, W, stride);
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(counts, SH_ERR_INVALID_ARG, "sh_depth_count: null pointer");
+    if (B == 0 || H == 0 || W == 0) return SH_OK;
+    const size_t need = sh_depth_workspace(B, H, W);
+    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_count: the workspace holds the tile rows (%zu bytes needed)", need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
+    int32_t* tile_row = static_cast<int32_t*>(workspace);
+    launch_tiles<false>(st, dtype, a, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
+    {
+        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, a.tiles);
+        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, a.tiles, counts);
+    }
+    SH_CHECK_LAUNCH("depth_count");
+    return SH_OK;
+}
+
+int sh_depth_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
+                    float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts, int max_count, int M,
+                    const void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel, sh_stream_t stream) {
+    const int rc = check_inputs("sh_depth_points", depth, dtype, intr, B, H, W, stride);
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(counts && points && normals && pixel, SH_ERR_INVALID_ARG, "sh_depth_points: null pointer");
+    SH_REQUIRE(M >= 0 && max_count >= 0, SH_ERR_INVALID_ARG, "sh_depth_points: negative size (M %d, max_count %d)", M, max_count);
+    SH_REQUIRE(M >= max_count, SH_ERR_INVALID_ARG, "sh_depth_points: M = %d rows cannot hold the largest body's %d", M, max_count);
+    if (B == 0 || H == 0 || W == 0) return SH_OK;
+    const size_t need = sh_depth_workspace(B, H, W);
+    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_points: the workspace of sh_depth_count is needed (%zu bytes)", need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
+    launch_tiles<true>(st, dtype, a, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts, M, points, normals, pixel);
+    SH_CHECK_LAUNCH("depth_points");
+    return SH_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,8 @@ The kernels take explicit strides, so both layouts go through the same code.
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import _lib
@@ -551,6 +553,63 @@ def vertex_visibility(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks
     check(lib.sh_vertex_visibility(ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view), float(cos_g), ptr(mask), mask_sb, B, chunks, ptr(ws),
                                    nbytes, ptr(vis), stream_ptr()), "sh_vertex_visibility")
     return vis
+
+
+DEPTH_DTYPES = {torch.float32: 0, torch.int16: 1}               # enum sh_depth_dtype: 16-bit words travel as int16 and are read unsigned
+
+
+def _depth_args(who, depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
+    """The inputs sh_depth_count and sh_depth_points share, checked -> (B, H, W, their C arguments up to `stride`)."""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in DEPTH_DTYPES and depth.dim() == 3 and depth.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.%s needs a contiguous fp32 or 16-bit HIP depth image [B, H, W] (got %s %s %s); there is no "
+                           "CPU path" % (who, getattr(depth, "device", None), getattr(depth, "dtype", type(depth)), tuple(getattr(depth, "shape", ()))))
+    B, H, W = depth.shape
+    if not (torch.is_tensor(intr) and intr.device == depth.device and intr.dtype == torch.float32 and intr.is_contiguous() and tuple(intr.shape) == (B, 4)):
+        raise ValueError("%s: intr must be a contiguous fp32 tensor [%d, 4] = (fx, fy, cx, cy) on the depth's device" % (who, B))
+    if mask is not None and not (torch.is_tensor(mask) and mask.device == depth.device and mask.dtype == torch.uint8 and mask.is_contiguous()
+                                 and mask.shape == depth.shape):
+        raise ValueError("%s: mask must be a contiguous uint8 tensor %s on the depth's device" % (who, tuple(depth.shape)))
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("%s: stride = %d, must be at least 1" % (who, stride))
+    return B, H, W, (ptr(depth), DEPTH_DTYPES[depth.dtype], float(depth_scale), ptr(intr), ptr(mask), B, H, W, float(z_near), float(z_far),
+                     float(max_step), int(bool(drop_isolated)), stride)
+
+
+def depth_count(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False, stride=1):
+    """sh_depth_count: depth [B, H, W] fp32 or 16-bit words on the device, intr fp32 [B, 4] = (fx, fy, cx, cy), mask uint8
+    [B, H, W] or None -> (counts int32 [B], the kept pixels per body; the workspace sh_depth_points reads, the first row of every
+    16 x 16 tile).  Nothing is synchronised."""
+    B, H, W, args = _depth_args("depth_count", depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    lib = _lib.load()
+    counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
+    nbytes = lib.sh_depth_workspace(B, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
+    check(lib.sh_depth_count(*args, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_depth_count")
+    return counts, ws
+
+
+def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf,
+                 drop_isolated=False, stride=1):
+    """sh_depth_points: the inputs and options of the `depth_count` call that made (counts, workspace), a width M and the largest
+    count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the camera's frame, normals fp32 [B, M, 3] - a
+    zero row: unknown -, pixel int32 [B, M] = v * W + u), rows in tile / Z-order; beyond a body's count zeros, zeros and -1."""
+    B, H, W, args = _depth_args("depth_points", depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    M, max_count = int(M), int(max_count)
+    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise ValueError("depth_points: counts must be the int32 tensor [%d] of depth_count" % B)
+    lib = _lib.load()
+    nbytes = lib.sh_depth_workspace(B, H, W)
+    if not (torch.is_tensor(workspace) and workspace.device == depth.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+            and workspace.numel() >= nbytes):
+        raise ValueError("depth_points: workspace must be the one depth_count returned for this image (%d bytes)" % nbytes)
+    points = torch.empty((B, max(M, 0), 3), dtype=torch.float32, device=depth.device)
+    normals = torch.empty_like(points)
+    pixel = torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device)
+    check(lib.sh_depth_points(*args, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), ptr(points), ptr(normals), ptr(pixel),
+                              stream_ptr()), "sh_depth_points")
+    return points, normals, pixel
 
 
 ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                 # enum sh_robust (0: none)

@@ -21,13 +21,17 @@
   * `visible_vertices(x, faces, viewpoints)`, `visibility="viewpoint"` on chamfer / align  partial scans: the model vertices the
                                      sensor sees from `ScanBatch(..., viewpoints=)` - not occluded by any triangle, optionally
                                      facing the sensor (sh_vertex_visibility) - are the vertex mask of every search and term
+  * `unproject_depth(depth, intrinsics, ...)`, `ScanBatch.from_depth(depth, intrinsics, device, ...)`  depth images as scans: the
+                                     camera-frame point of every usable pixel, its normal from the pixel grid, oriented to the
+                                     camera, and the rows packed in tile order (sh_depth_count, sh_depth_points)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
 model's normalised frame; `align` (and editing.register_scan, which alternates it with the fit) brings a scan there by a
 translation, a rigid motion or a similarity.  The alignment works on vertex pairs, or with `faces=` on (scan point, foot point on
-the surface) pairs - point-to-surface ICP in the same closed form (sh_align_moments_surface); there is no file reader.  With `normal_angle` a pair is a match only when its two normals agree to within that angle (a point with no compatible
-partner counts as truncated, so a gate needs `trunc`); the gate applies to vertex pairs, not to the surface distance of `faces=`.
+the surface) pairs - point-to-surface ICP in the same closed form (sh_align_moments_surface).  Depth images enter through
+`ScanBatch.from_depth`, as arrays: there is still no file reader.  With `normal_angle` a pair is a match only when its two
+normals agree to within that angle (a point with no compatible partner counts as truncated, so a gate needs `trunc`); the gate applies to vertex pairs, not to the surface distance of `faces=`.
 The search, the loss and the alignment have no CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
@@ -114,7 +118,7 @@ def pack_viewpoints(viewpoints, counts, width):
         except (ValueError, TypeError):
             a = None
         if a is not None and a.shape == (3,):
-            out = np.array(np.broadcast_to(a, (B, 3)))                                # a copy: writable
+            out = np.broadcast_to(a, (B, 3)).copy()                                   # a copy: writable, and row-major for every B
         elif a is not None and a.shape == (B, 3):
             out = np.ascontiguousarray(a)
         else:
@@ -169,10 +173,14 @@ class ScanBatch:
     normals="estimate" - what `visibility="viewpoint"` of chamfer / align reads; None otherwise (per-point viewpoints serve the
     normals' orientation only).  A row set to NaN afterwards marks a body as a full scan: no viewpoint, every vertex visible.
     Without normals="estimate" a viewpoint that cannot be packed (another shape, NaN or inf) raises nothing here, as ever; the
-    field is None and `visibility="viewpoint"` later names the reason."""
+    field is None and `visibility="viewpoint"` later names the reason.
+
+    `pixels`: int32 [B, Mmax] on a batch made by `from_depth` - the pixel v * W + u each row came from, -1 in the padding; None on
+    batches made any other way."""
 
     viewpoints = None                                                                   # for batches made without __init__ or _from_parts
     viewpoints_error = None
+    pixels = None
 
     def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None):
         if order not in (None, "morton"):
@@ -217,18 +225,29 @@ class ScanBatch:
         return self.points.shape[0]
 
     @classmethod
-    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None):
+    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None, pixels=None):
         """A ScanBatch around tensors that are already packed and resident: every field, nothing copied or checked."""
         out = cls.__new__(cls)
         out.points, out.counts, out.host_counts, out.perm, out.normals = points, counts, host_counts, perm, normals
-        out.viewpoints = viewpoints
+        out.viewpoints, out.pixels = viewpoints, pixels
         return out
+
+    @classmethod
+    def from_depth(cls, depth, intrinsics, device, **options):
+        """Depth images as a batch of scans: `unproject_depth(depth, intrinsics, device=device, **options)` kept whole - points in
+        the camera's frame in tile order (perm None), counts, the grid normals (oriented to the camera; a zero row: unknown),
+        `viewpoints` = zeros [B, 3] (the camera centre) and `pixels`.  Ready for normal_angle=, gate_on=, visibility="viewpoint"
+        and robust= without further arguments.  One host synchronisation, to read the counts."""
+        points, normals, pixel, counts, host_counts = _unproject_depth(depth, intrinsics, device=device, **options)
+        return cls._from_parts(points, counts, host_counts, None, normals,
+                               viewpoints=torch.zeros((points.shape[0], 3), dtype=torch.float32, device=points.device), pixels=pixel)
 
     def select(self, sl):
         """The bodies `sl` (a slice) as a ScanBatch sharing this one's memory."""
         return ScanBatch._from_parts(self.points[sl], self.counts[sl].contiguous(), self.host_counts[sl],
                                      None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl],
-                                     viewpoints=None if self.viewpoints is None else self.viewpoints[sl].contiguous())
+                                     viewpoints=None if self.viewpoints is None else self.viewpoints[sl].contiguous(),
+                                     pixels=None if self.pixels is None else self.pixels[sl])
 
 
 def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
@@ -264,6 +283,89 @@ def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
     elif view is not None:
         view = view.detach().to(torch.float32).contiguous()
     return ops.cloud_normals(pts, cnt, k, view)
+
+
+def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
+    """`unproject_depth`, with the counts as the host read them as a fifth result.  Every ValueError is raised before the device is
+    used."""
+    what = "unproject_depth"
+    if torch.is_tensor(depth):
+        d = depth.detach()
+        if hasattr(torch, "uint16") and d.dtype == torch.uint16:
+            d = d.view(torch.int16)                                                     # the words as they are: the kernel reads them unsigned
+        known = d.dtype in (torch.float32, torch.int16)
+    else:
+        d = np.asarray(depth)
+        known = d.dtype in (np.float32, np.uint16)
+        if known:
+            d = np.ascontiguousarray(d)
+            d = torch.from_numpy(d.view(np.int16) if d.dtype == np.uint16 else d)
+    if not known or d.dim() not in (2, 3) or min(d.shape) < 1:
+        raise ValueError("%s: depth must be fp32 or 16-bit unsigned, [H, W] or [B, H, W] and not empty, got %s %s"
+                         % (what, getattr(depth, "dtype", type(depth).__name__), tuple(getattr(depth, "shape", ()))))
+    lead = () if d.dim() == 2 else (d.shape[0],)
+    d = d.reshape((-1,) + tuple(d.shape[-2:]))
+    B = d.shape[0]
+    try:
+        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
+    except (ValueError, TypeError):
+        k = None
+    if k is None or k.shape not in ((4,), (B, 4)):
+        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as [4] or [%d, 4], got %s"
+                         % (what, B, "shape %s" % (k.shape,) if k is not None else type(intrinsics).__name__))
+    k = np.broadcast_to(k.astype(np.float32), (B, 4)).copy()
+    if not np.isfinite(k).all() or not (k[:, :2] > 0).all():
+        raise ValueError("%s: fx and fy must be finite and positive, cx and cy finite" % what)
+    m = mask
+    if m is not None:
+        m = m.detach() if torch.is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m))
+        if tuple(m.shape) != lead + tuple(d.shape[-2:]) or m.is_floating_point() or m.is_complex():
+            raise ValueError("%s: mask must be a bool or integer array of the depth's shape %s, got %s %s"
+                             % (what, lead + tuple(d.shape[-2:]), m.dtype, tuple(m.shape)))
+        m = m.reshape(d.shape)
+    near, far = -math.inf, math.inf
+    if z_range is not None:
+        try:
+            near, far = (float(v) for v in z_range)
+        except (ValueError, TypeError):
+            near = math.nan
+        if not near <= far:
+            raise ValueError("%s: z_range must be a pair (near, far) with near <= far, got %r" % (what, z_range))
+    step = math.inf if max_step is None else float(max_step)
+    if not step >= 0:
+        raise ValueError("%s: max_step must be None or >= 0, got %r" % (what, max_step))
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
+    dev = torch.device(device if device is not None else d.device if d.is_cuda else "cuda")
+    d = d.to(dev).contiguous()
+    k = torch.from_numpy(k).to(dev)
+    if m is not None:
+        m = (m.to(dev) != 0).to(torch.uint8).contiguous()
+    opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
+    counts, ws = ops.depth_count(d, k, **opts)
+    host_counts = counts.cpu().numpy()                                                  # the one synchronisation
+    most = int(host_counts.max())
+    return ops.depth_points(d, k, counts, ws, max(most, 1), most, **opts) + (counts, host_counts)
+
+
+def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
+    """Depth images -> scans (sh_depth_count, sh_depth_points; include/sh_kernels.h, "Depth images").  depth: a host array or a
+    tensor [B, H, W] or [H, W], fp32 or 16-bit unsigned words (a tensor of int16 is read as such words); z = raw * depth_scale.
+    intrinsics: (fx, fy, cx, cy) as [4] or [B, 4], pinhole, no distortion.  A pixel is valid when z is finite and positive, lies
+    in z_range = (near, far) if given, is not the word 0, and mask (bool or integer, the depth's shape) is non-zero there.  Its
+    point is ((u - cx) z / fx, (v - cy) z / fy, z) in the camera's frame.  Its normal comes from its grid neighbours - central
+    differences where both are usable, one-sided where one is; a neighbour is usable when valid and within max_step in depth
+    (None: any step), so no tangent crosses a silhouette - as the unit cross product in fp64, turned towards the camera; a zero
+    row where a tangent is missing: "unknown", as everywhere.  Kept: valid pixels on the grid of every stride-th column and row
+    (normals still read the full-resolution neighbours) and, with drop_isolated, of known normal - which drops flying pixels
+    that max_step has cut off on all sides.
+    -> (points fp32 [B, M, 3], normals fp32 [B, M, 3], pixel int32 [B, M] = v * W + u, counts int32 [B]) on `device` (None: the
+    depth's, or the default HIP device for a host array), M the largest count (at least 1); rows beyond a count are zeros, zeros
+    and -1.  Rows are in 16 x 16 tile order, Z-order inside a tile: neighbours in memory are neighbours on the surface.  One host
+    synchronisation, to read the counts: a packing-time operation.  Deterministic - the same bits for an image alone and inside
+    any batch.  Not differentiable.  ValueError for wrong shapes or dtypes, fx / fy not finite and positive, stride < 1 or a
+    negative max_step."""
+    return _unproject_depth(depth, intrinsics, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
