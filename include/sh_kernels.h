@@ -1084,6 +1084,81 @@ SH_API int sh_depth_points(const void* depth, int dtype, float depth_scale, cons
                            int32_t* pixel, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth field: what a depth image says about where the body is NOT - the way back from the model to the image (no reference
+ * counterpart).  A packing-time field per image (sh_depth_field) and a per-step vertex term with its gradient
+ * (sh_free_space_fwd / _bwd).  Deterministic: no atomics of any kind, every output element written by one plain store; the bits
+ * depend on neither batch nor launch shape.
+ *
+ * sh_depth_field.  Inputs: those of sh_depth_count - depth, dtype, depth_scale, intr, mask, z_near, z_far, with the same
+ * z = fl((float)raw * depth_scale) and the same "valid" (one set of device helpers serves both).  intr is not read: the field is
+ * a function of the image alone; it is taken so that the two calls have one argument list.  Per pixel three planes:
+ *     cls uint8 [B][H][W]     SH_FIELD_SURFACE (2): valid in the sense of "Depth images".
+ *                             SH_FIELD_EMPTY (0): there is a reading (z finite and positive, the word not 0), the pixel is not
+ *                             SURFACE, and z >= z_near - the sensor saw past the working volume, or the mask says "not the
+ *                             subject" at a depth that cannot occlude it.
+ *                             SH_FIELD_UNKNOWN (1): everything else - no reading, or something nearer than z_near, behind which
+ *                             the body may be.
+ *     z fp32 [B][H][W]        the depth of a SURFACE pixel, 0 elsewhere
+ *     nearest int32 [B][H][W] the exact feature transform of the ALLOWED set, allowed = cls != 0: the index v' * W + u' of the
+ *                             allowed pixel that minimises the integer (u - u')^2 + (v - v')^2; ties go to the smallest index;
+ *                             an allowed pixel is its own nearest; -1 when the image has no allowed pixel.
+ * nearest is a pure function of cls: the same bits for an image alone and in any batch.
+ * How it is computed.  (1) The column pass, one thread per column (coalesced across u): down the column it classifies and
+ * records the row of the nearest allowed pixel at or above, up again the nearest at or below, and keeps the closer of the two, a
+ * tie going to the upper (the smaller index) - one candidate row per (pixel, column), int16 in `workspace`
+ * (sh_depth_field_workspace(B, H, W) bytes), -1 for a column with no allowed pixel.  One candidate is enough: within a column d2
+ * and the index grow together.  (2) The row pass, one workgroup per image row with the row's W candidates in LDS (2 W bytes, at
+ * most 32 KiB: never chunked): a pixel walks outward from its own column, k = 0, 1, ..., takes the minimum of the key
+ * (d2, v' * W + u') over columns u - k and u + k, and leaves once k * k > its best d2 (at k * k == best a tie of smaller index is
+ * still possible).  The walk is as long as the distance to the nearest allowed pixel; an image without one walks every row whole.
+ * H or W above SH_FIELD_MAX_SIDE (d2 must fit in 31 bits, a row in int16) or B > 65535: SH_ERR_UNSUPPORTED.  Null pointers (mask
+ * excepted), negative sizes, an unknown dtype and a workspace that is too small: SH_ERR_INVALID_ARG.  All of that before the
+ * device is touched.  B == 0 or H * W == 0: SH_OK, nothing launched.
+ *
+ * sh_free_space_fwd / sh_free_space_bwd.  x: fp32 [B] bodies of CAMERA-frame points, batch stride x_sb; the first n of `rows`
+ * rows are vertices, rows >= n are never read and get zero gradient.  v_mask [n] (mask_sb = 0) or [B][n] (mask_sb = n), NULL: all
+ * active.  margin fp32 >= 0.  cls, z, nearest: a field of the same B, H, W; intr [B][4] = (fx, fy, cx, cy).  Everything is fp32
+ * with every operation rounded on its own (no contraction) and a correctly rounded division.  For an active vertex (X, Y, Z):
+ *     kind SH_FS_OUTSIDE (4), no term:   !(Z > 0) (a NaN included), or (uf, vf) below not inside
+ *     uf = fl(fl(fl(X * fx) / Z) + cx);  vf = fl(fl(fl(Y * fy) / Z) + cy)
+ *     inside: uf >= -0.5f, uf < W - 0.5f, vf >= -0.5f, vf < H - 0.5f                                    (a NaN is outside)
+ *     u = (int)floorf(fl(uf + 0.5f));  v = (int)floorf(fl(vf + 0.5f));  c = cls[b][v][u]              (nearest-pixel sampling)
+ *     c == 1:  kind SH_FS_UNKNOWN (3), no term
+ *     c == 2:  e = fl(fl(z[b][v][u] - margin) - Z);  e > 0: kind SH_FS_FREE (1), term = fl(e * e), g = (0, 0, fl(-2 * e));
+ *              else kind SH_FS_NONE (0), no term
+ *     c == 0:  q = nearest[b][v][u];  q < 0: kind 0, no term.  Else (uq, vq) = (q % W, q / W),
+ *              a = fl(fl((float)uq - cx) / fx),  b = fl(fl((float)vq - cy) / fy),
+ *              rx = fl(X - fl(a * Z)),  ry = fl(Y - fl(b * Z))     (the vertex's offset from the ray through that pixel, at its
+ *              own depth);  kind SH_FS_SILHOUETTE (2), term = fl(fl(rx * rx) + fl(ry * ry)),
+ *              g = (fl(2 * rx), fl(2 * ry), fl(-2 * fl(fl(a * rx) + fl(b * ry))))
+ * nearest is taken as a constant, as the Chamfer gradient takes its indices; so is the image: there is no image gradient.  A
+ * masked vertex has kind 0, no term and no gradient.
+ * sh_free_space_fwd -> term fp32 [B][n] (0 where there is none), kind uint8 [B][n], loss fp32 [B][2] = (1 / n_act) * the sum of
+ * the terms of kind 1 and of kind 2 (n_act = the active vertices; sums in fp64 in the order of sh_chamfer_fwd: thread t of 256
+ * takes vertices t, t + 256, ..., then the wave butterfly and the four wave sums in order; one rounding to fp32; n_act == 0:
+ * zeros), counts int32 [B][4] = (n_act, #kind 1, #kind 2, #kind 4).  One launch, one workgroup per body.
+ * sh_free_space_bwd, given the forward call's arguments, its counts and gL fp32 [B][2] -> g_x fp32 [B][rows][3], contiguous:
+ *     g_x[b][i] = fl(fl(gL[b][k] * fl(1 / (float)n_act)) * g)  per component, k = 0 for kind 1 and 1 for kind 2
+ * and zeros in every other row below `rows`.  One launch, one thread per row; the vertex's case list is evaluated again.
+ * Null pointers (v_mask excepted), negative sizes, n > rows, a batch or mask stride shorter than n, a negative or NaN margin,
+ * H * W == 0 with n > 0: SH_ERR_INVALID_ARG; H or W above SH_FIELD_MAX_SIDE: SH_ERR_UNSUPPORTED; before the device is touched.
+ * B == 0: SH_OK, nothing launched.
+ */
+enum sh_field_class { SH_FIELD_EMPTY = 0, SH_FIELD_UNKNOWN = 1, SH_FIELD_SURFACE = 2 };
+enum sh_free_space_kind { SH_FS_NONE = 0, SH_FS_FREE = 1, SH_FS_SILHOUETTE = 2, SH_FS_UNKNOWN = 3, SH_FS_OUTSIDE = 4 };
+#define SH_FIELD_MAX_SIDE 16384
+SH_API size_t sh_depth_field_workspace(int B, int H, int W);
+SH_API int sh_depth_field(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W,
+                          float z_near, float z_far, uint8_t* cls, float* z, int32_t* nearest, void* workspace, size_t workspace_bytes,
+                          sh_stream_t stream);
+SH_API int sh_free_space_fwd(const float* x, int64_t x_sb, int rows, int n, const uint8_t* cls, const float* z, const int32_t* nearest,
+                             const float* intr, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B, float* term,
+                             uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream);
+SH_API int sh_free_space_bwd(const float* x, int64_t x_sb, int rows, int n, const uint8_t* cls, const float* z, const int32_t* nearest,
+                             const float* intr, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, const int32_t* counts,
+                             const float* gL, int B, float* g_x, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

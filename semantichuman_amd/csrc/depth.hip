@@ -3,8 +3,7 @@
 // 16 x 16 tile, thread = Z-rank inside the tile, so the ballot prefix of "kept" IS the rank among the tile's rows: a count pass,
 // a per-body scan of the tile counts and an emit pass that recomputes the pixel - no atomics, every output element one plain
 // store, nothing that depends on the batch, the padding or the launch shape.
-#include <limits.h>
-#include "sh_common.h"
+#include "sh_depth.h"
 
 #pragma clang fp contract(off)          // the header's expressions: every operation rounded on its own, in the whole file
 
@@ -34,9 +33,6 @@ __device__ __forceinline__ int even_bits(int r) {
     return (r | (r >> 2)) & 0x0f;
 }
 
-__device__ __forceinline__ bool raw_ok(float) { return true; }
-__device__ __forceinline__ bool raw_ok(uint16_t raw) { return raw != 0; }
-
 // The tile at (u0, v0) with its halo -> zt[HALO][LROW]: z where the pixel is valid, NaN where it is not or lies outside the
 // image.  Consecutive threads read consecutive pixels of a row.
 template <typename T>
@@ -51,9 +47,8 @@ __device__ __forceinline__ void load_tile(const DepthArgs& a, int b, int u0, int
         if (u >= 0 && u < a.W && v >= 0 && v < a.H) {
             const long p = (long)v * a.W + u;
             const T raw = d[p];
-            const float zz = (float)raw * a.depth_scale;
-            const bool ok = zz > 0.f && zz < INFINITY && a.z_near <= zz && zz <= a.z_far && raw_ok(raw) && (!m || m[p] != 0);   // a NaN compares false
-            z = ok ? zz : NAN;
+            const float zz = depth_z(raw, a.depth_scale);
+            z = depth_valid(raw, zz, a.z_near, a.z_far, m, p) ? zz : NAN;
         }
         zt[r * LROW + c] = z;
     }
@@ -183,9 +178,7 @@ int tiles_of(int H, int W) { return sh_cdiv(H, TILE) * sh_cdiv(W, TILE); }
 
 // What both entry points ask of the inputs they share; `who` names the caller in the message.
 int check_inputs(const char* who, const void* depth, int dtype, const float* intr, int B, int H, int W, int stride) {
-    SH_REQUIRE(dtype == SH_DEPTH_F32 || dtype == SH_DEPTH_U16, SH_ERR_INVALID_ARG, "%s: unknown depth dtype %d", who, dtype);
-    SH_REQUIRE(depth && intr, SH_ERR_INVALID_ARG, "%s: null pointer", who);
-    SH_REQUIRE(B >= 0 && H >= 0 && W >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, H %d, W %d)", who, B, H, W);
+    if (const int rc = depth_check_inputs(who, depth, dtype, intr, B, H, W)) return rc;
     SH_REQUIRE(stride >= 1, SH_ERR_INVALID_ARG, "%s: stride = %d, must be at least 1", who, stride);
     SH_REQUIRE(B <= 65535 && (long)H * W <= INT_MAX, SH_ERR_UNSUPPORTED, "%s: B or H * W too large", who);
     return SH_OK;

@@ -8,7 +8,8 @@ Measurement-targeted editing: `fit_latents` optimises part latents through the f
 (the decoder's backward pass then computes no weight gradient); `fit_part_girths` asks for girths ("chest +4 %, waist unchanged")
 through the differentiable measurements of measure.py; `fit_scan` fits the latents to unregistered point clouds (scans, depth
 clouds, meshes of another topology) with the Chamfer objective of scan.py; `register_scan` does the same for scans that arrive
-in their own frame and units, solving for the pose (scan.align) before and during the fit.
+in their own frame and units, solving for the pose (scan.align) before and during the fit.  Both take the free-space and
+silhouette terms of a depth image (`free_space=`, a scan.DepthField) on top of the Chamfer objective.
 """
 from __future__ import annotations
 
@@ -227,9 +228,27 @@ def _visibility_cache(what, visibility, visibility_every):
     return None if visibility is None else {"every": every, "t": 0, "mask": None}
 
 
+def _free_space_term(what, field, B, free_space_weight, silhouette_weight, margin, pose, vertex_mask=None):
+    """The free-space arguments of a fit, checked -> None without a field, else x_hat -> free_space_weight * free +
+    silhouette_weight * silhouette [B] (scan.free_space under `pose`, read afresh in every call, and the given vertex_mask)."""
+    if field is None:
+        return None
+    scan._check_free_space_weights(what, field, B, margin, (("free_space_weight", free_space_weight), ("silhouette_weight", silhouette_weight)))
+    if pose is not None and (not isinstance(pose, scan.Pose) or len(pose) != B):
+        raise ValueError("%s: free_space_pose must be a scan.Pose of %d bodies" % (what, B))
+    fw, sw, margin = float(free_space_weight), float(silhouette_weight), float(margin)
+
+    def term(x_hat):
+        free, silhouette = scan.free_space(x_hat, field, pose=pose, vertex_mask=vertex_mask, margin=margin)
+        return fw * free + sw * silhouette
+
+    return term
+
+
 def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=None, w_model_to_scan=0.0, vertex_mask=None, dummy=None,
              faces=None, normal_angle=None, normal_faces=None, gate_on="vertices", visibility=None, visibility_faces=None,
-             grazing_angle=None, visibility_every=1, robust=None, robust_scale=None):
+             grazing_angle=None, visibility_every=1, robust=None, robust_scale=None, free_space=None, free_space_weight=1.0,
+             silhouette_weight=1.0, free_space_margin=0.0, free_space_pose=None):
     """Fit bodies to unregistered point clouds: `fit_latents` with the objective scan.chamfer(decode(z), scans).  Each body has its
     own scan (a scan.ScanBatch, or a list of [m_b, 3] arrays / one [B, M, 3] array packed here once); no correspondence is needed.
     The scans must be in the model's normalised frame - nothing here aligns them; `register_scan` (or scan.align beforehand)
@@ -249,6 +268,15 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     robust / robust_scale: None (the default - off: everything above, bit for bit) or the robust data term of scan.chamfer
     ("geman-mcclure" / "huber" with sigma in the model's normalised units): scan points far from the body - clothing, hair, a
     floor patch - fade out of value and gradient instead of dominating them.
+    free_space: None (the default - off: everything above, bit for bit, the same launches) or a scan.DepthField of the depth
+    images the scans came from.  The objective gains free_space_weight * free + silhouette_weight * silhouette of
+    scan.free_space(decode(z), free_space, pose=free_space_pose, margin=free_space_margin): model vertices in space the sensor
+    saw through, or projecting outside the body's silhouette, are pushed back - the data term a one-view fit lacks for the half
+    of the body that visibility= only removes (two launches per step).  free_space_pose: the scan.Pose (camera frame
+    -> model frame) that brought the scans into the model's frame, None when the model's frame is the camera's.  A given
+    vertex_mask holds for the term too; the mask of visibility= does not - the unseen vertices are the ones it is for.  Nearest-pixel sampling, no image gradient, no robust form, pinhole only.  The loss per step
+    includes the term; the returned Chamfer value does not.  ValueError for a field of another batch size, a negative weight or
+    margin.
     Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
@@ -258,12 +286,13 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     scan._MatchPlan.check_visibility("fit_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
     vis_cache = _visibility_cache("fit_scan", visibility, visibility_every)
     rb = {} if scan._robust_arg("fit_scan", robust, robust_scale) is None else dict(robust=robust, robust_scale=robust_scale)
+    extra = _free_space_term("fit_scan", free_space, z.shape[0], free_space_weight, silhouette_weight, free_space_margin, free_space_pose, vertex_mask)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
     tables = {}
 
-    def objective(x_hat):
+    def data(x_hat):
         if not tables:                                                     # validated and uploaded once, at the first decode: n is known here
             tables.update(faces=_face_table(faces, x_hat), normal_faces=_face_table(normal_faces, x_hat) if normal_angle is not None else None)
             if visibility is not None:
@@ -275,18 +304,20 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
                              gate_on, visibility=visibility, visibility_faces=tables["visibility_faces"], grazing_angle=grazing_angle,
                              vis_cache=vis_cache, **rb)
 
+    objective = data if extra is None else (lambda x_hat: data(x_hat) + extra(x_hat))
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():
         if vis_cache is not None:
             vis_cache["t"] = 0                                             # the result is measured under a fresh mask
-        final = objective(_decode(model, z_new, z_kps, dummy))
+        final = data(_decode(model, z_new, z_kps, dummy))                  # the Chamfer value alone
     return z_new, final, losses
 
 
 def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init="moments", align_iters=30, align_every=1, steps=200,
                   lr=1e-2, trunc=None, w_model_to_scan=0.0, align_w_model_to_scan=None, vertex_mask=None, dummy=None, faces=None,
                   normal_angle=None, normal_faces=None, align_on="vertices", align_step="point", gate_on="vertices", visibility=None,
-                  visibility_faces=None, grazing_angle=None, visibility_every=1, robust=None, robust_scale=None):
+                  visibility_faces=None, grazing_angle=None, visibility_every=1, robust=None, robust_scale=None, free_space=None,
+                  free_space_weight=1.0, silhouette_weight=1.0, free_space_margin=0.0):
     """`fit_scan` for scans in their own frame and units: solves for the pose (scan frame -> model frame, a scan.Pose) together
     with the latents.
 
@@ -324,7 +355,13 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     batch with the mask recomputed every `visibility_every`-th step, and every in-loop pose update moves the viewpoint with the
     scan.  visibility_faces / grazing_angle as in scan.chamfer.  robust / robust_scale: None (the default - off: everything
     above, bit for bit) or the robust term of scan.chamfer, in all three places: stage 1 is scan.align(..., robust=) (IRLS), the
-    fit's objective is the robust Chamfer value, and every in-loop pose update weighs its pairs the same way.  No file reader."""
+    fit's objective is the robust Chamfer value, and every in-loop pose update weighs its pairs the same way.  free_space /
+    free_space_weight / silhouette_weight / free_space_margin: None (the default - off: everything above, bit for bit, the same
+    launches) or the free-space and silhouette terms of fit_scan, for scans that are depth images in the camera's frame (the
+    scan's frame): the term of every step is scan.free_space(decode(z), free_space, pose=the pose as it stands), so it follows
+    every in-loop pose update.  The term moves the latents only - it does NOT move the pose: stage 1 (scan.align) and the in-loop
+    pose updates are what they are without it.  The loss per step includes the term; the returned Chamfer value does not.
+    ValueError for a field of another batch size, a negative weight or margin.  No file reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -347,6 +384,8 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     scan._MatchPlan.check_visibility("register_scan", visibility, visibility_faces, faces, normal_faces, grazing_angle, scans)
     vis_cache = _visibility_cache("register_scan", visibility, visibility_every)
     rb = {} if scan._robust_arg("register_scan", robust, robust_scale) is None else dict(robust=robust, robust_scale=robust_scale)
+    if free_space is not None:                                                          # checked before the device is used; the pose comes below
+        _free_space_term("register_scan", free_space, z.shape[0], free_space_weight, silhouette_weight, free_space_margin, None)
     semantic = hasattr(model, "kps_encode")
     if semantic and dummy is None:
         dummy = _default_dummy(model, z)
@@ -369,12 +408,16 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     matches = {} if align_every > 0 else None
     state = {"partials": None}
 
-    def objective(x_hat):                                                               # foot-point pose updates read no vertex record
+    extra = _free_space_term("register_scan", free_space, z.shape[0], free_space_weight, silhouette_weight, free_space_margin, pose, vertex_mask)
+
+    def data(x_hat):                                                                    # foot-point pose updates read no vertex record
         if visibility is not None:
             return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
                                  vertex_matches=not on_surface, vis_cache=vis_cache, **vis, **rb)
         return scan._chamfer(x_hat, aligned, None, vertex_mask, trunc, w_model_to_scan, matches, faces, normal_angle, normal_faces, gate_on,
                              vertex_matches=not on_surface, **rb)
+
+    objective = data if extra is None else (lambda x_hat: data(x_hat) + extra(x_hat))  # `pose` is updated in place: the term reads it afresh
 
     def after_step(t):
         if (t + 1) % align_every == 0:

@@ -612,6 +612,63 @@ def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_
     return points, normals, pixel
 
 
+def depth_field(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):
+    """sh_depth_field: the image inputs of `depth_count` -> (cls uint8 [B, H, W]: 0 empty, 1 unknown, 2 surface; z fp32 [B, H, W],
+    the surface depth; nearest int32 [B, H, W], the nearest pixel that is not empty as v * W + u, -1: the image has none).
+    Nothing is synchronised."""
+    B, H, W, args = _depth_args("depth_field", depth, intr, mask, depth_scale, z_near, z_far, math.inf, False, 1)
+    lib = _lib.load()
+    cls = torch.empty((B, H, W), dtype=torch.uint8, device=depth.device)
+    z = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)
+    nearest = torch.empty((B, H, W), dtype=torch.int32, device=depth.device)
+    nbytes = lib.sh_depth_field_workspace(B, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
+    check(lib.sh_depth_field(*args[:10], ptr(cls), ptr(z), ptr(nearest), ptr(ws), nbytes, stream_ptr()), "sh_depth_field")
+    return cls, z, nearest
+
+
+def _free_space_args(who, x, n, cls, z, nearest, intr, v_mask, mask_sb, margin):
+    """The arguments sh_free_space_fwd and sh_free_space_bwd share, checked -> (B, rows, their C arguments up to `margin`)."""
+    B, rows, x_sb = _points(x, who)
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("%s: n = %d exceeds the model's %d rows" % (who, n, rows))
+    if not (torch.is_tensor(cls) and cls.device == x.device and cls.dtype == torch.uint8 and cls.dim() == 3 and cls.shape[0] == B
+            and cls.is_contiguous()):
+        raise ValueError("%s: cls must be a contiguous uint8 tensor [%d, H, W] on the device of x" % (who, B))
+    H, W = cls.shape[1:]
+    for t, dtype, shape, what in ((z, torch.float32, (B, H, W), "z fp32"), (nearest, torch.int32, (B, H, W), "nearest int32"),
+                                  (intr, torch.float32, (B, 4), "intr fp32")):
+        if not (torch.is_tensor(t) and t.device == x.device and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous tensor %s on the device of x" % (who, what, list(shape)))
+    return B, rows, (ptr(x), x_sb, rows, n, ptr(cls), ptr(z), ptr(nearest), ptr(intr), H, W, ptr(v_mask), mask_sb, float(margin))
+
+
+def free_space_fwd(x, n, cls, z, nearest, intr, v_mask=None, mask_sb=0, margin=0.0):
+    """sh_free_space_fwd: x [B, *, 3] camera-frame points of which the first n rows are vertices, a depth field (cls, z, nearest)
+    and intr [B, 4] of the same B; v_mask uint8 [n] (mask_sb 0) or [B, n] (mask_sb n), as `_mask_arg` makes it -> (term fp32
+    [B, n], kind uint8 [B, n], loss fp32 [B, 2] = (free space, silhouette), counts int32 [B, 4] = (active, kind 1, 2, 4))."""
+    B, rows, args = _free_space_args("free_space_fwd", x, n, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    n = int(n)
+    term = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    kind = torch.empty((B, n), dtype=torch.uint8, device=x.device)
+    loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=x.device)
+    check(_lib.load().sh_free_space_fwd(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_free_space_fwd")
+    return term, kind, loss, counts
+
+
+def free_space_bwd(x, n, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
+    """sh_free_space_bwd: the forward call's arguments, its counts and gL fp32 [B, 2] -> g_x contiguous [B, rows, 3] (every element
+    written)."""
+    B, rows, args = _free_space_args("free_space_bwd", x, n, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    if not (torch.is_tensor(gL) and gL.device == x.device and gL.dtype == torch.float32 and gL.is_contiguous() and tuple(gL.shape) == (B, 2)):
+        raise ValueError("free_space_bwd: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % B)
+    g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_free_space_bwd(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_free_space_bwd")
+    return g
+
+
 ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                 # enum sh_robust (0: none)
 
 

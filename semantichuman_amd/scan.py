@@ -24,6 +24,10 @@
   * `unproject_depth(depth, intrinsics, ...)`, `ScanBatch.from_depth(depth, intrinsics, device, ...)`  depth images as scans: the
                                      camera-frame point of every usable pixel, its normal from the pixel grid, oriented to the
                                      camera, and the rows packed in tile order (sh_depth_count, sh_depth_points)
+  * `DepthField.from_depth(depth, intrinsics, ...)`, `free_space(x_hat, field, ...)`  what a depth image says about where the
+                                     body is not: per pixel surface / empty / unknown and the nearest pixel that is not empty
+                                     (sh_depth_field); per vertex a free-space and a silhouette term, differentiable
+                                     (sh_free_space_fwd / _bwd) - off unless asked for
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -285,10 +289,9 @@ def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
     return ops.cloud_normals(pts, cnt, k, view)
 
 
-def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
-    """`unproject_depth`, with the counts as the host read them as a fifth result.  Every ValueError is raised before the device is
-    used."""
-    what = "unproject_depth"
+def _depth_inputs(what, depth, intrinsics, mask, z_range):
+    """The checks `unproject_depth` and `DepthField.from_depth` share, nothing moved to the device yet -> (depth [B, H, W] fp32 or
+    int16 words, intrinsics float32 numpy [B, 4], mask [B, H, W] or None, near, far)."""
     if torch.is_tensor(depth):
         d = depth.detach()
         if hasattr(torch, "uint16") and d.dtype == torch.uint16:
@@ -331,16 +334,27 @@ def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None
             near = math.nan
         if not near <= far:
             raise ValueError("%s: z_range must be a pair (near, far) with near <= far, got %r" % (what, z_range))
+    return d, k, m, near, far
+
+
+def _depth_upload(d, k, m, device):
+    """What `_depth_inputs` returned, resident: (depth, intrinsics fp32 [B, 4], mask uint8 or None) on `device` (None: the
+    depth's, or the default HIP device for a host array)."""
+    dev = torch.device(device if device is not None else d.device if d.is_cuda else "cuda")
+    return d.to(dev).contiguous(), torch.from_numpy(k).to(dev), None if m is None else (m.to(dev) != 0).to(torch.uint8).contiguous()
+
+
+def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
+    """`unproject_depth`, with the counts as the host read them as a fifth result.  Every ValueError is raised before the device is
+    used."""
+    what = "unproject_depth"
+    d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
     step = math.inf if max_step is None else float(max_step)
     if not step >= 0:
         raise ValueError("%s: max_step must be None or >= 0, got %r" % (what, max_step))
     if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
         raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
-    dev = torch.device(device if device is not None else d.device if d.is_cuda else "cuda")
-    d = d.to(dev).contiguous()
-    k = torch.from_numpy(k).to(dev)
-    if m is not None:
-        m = (m.to(dev) != 0).to(torch.uint8).contiguous()
+    d, k, m = _depth_upload(d, k, m, device)
     opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
     counts, ws = ops.depth_count(d, k, **opts)
     host_counts = counts.cpu().numpy()                                                  # the one synchronisation
@@ -366,6 +380,35 @@ def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=No
     any batch.  Not differentiable.  ValueError for wrong shapes or dtypes, fx / fy not finite and positive, stride < 1 or a
     negative max_step."""
     return _unproject_depth(depth, intrinsics, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
+
+
+class DepthField:
+    """What B depth images say about where the body is NOT, resident on the device (sh_depth_field; include/sh_kernels.h, "Depth
+    field"): `cls` uint8 [B, H, W] - 2 SURFACE (a valid pixel in the sense of `unproject_depth`), 0 EMPTY (a reading that is not
+    the surface, at or beyond the near end of z_range: the sensor saw through here), 1 UNKNOWN (no reading, or something nearer
+    than z_range) -, `z` fp32 [B, H, W] the surface depth (0 elsewhere), `nearest` int32 [B, H, W] the nearest pixel that is not
+    EMPTY as v * W + u (exact, ties to the smallest index, -1 when the image has none), `intrinsics` fp32 [B, 4] and `shape` =
+    (H, W).  `free_space` reads it; made once per image batch by `from_depth`."""
+
+    def __init__(self, cls, z, nearest, intrinsics):
+        self.cls, self.z, self.nearest, self.intrinsics = cls, z, nearest, intrinsics
+        self.shape = tuple(cls.shape[1:])
+
+    @classmethod
+    def from_depth(cls, depth, intrinsics, device=None, *, depth_scale=1.0, mask=None, z_range=None):
+        """depth, intrinsics, depth_scale, mask, z_range and device as in `unproject_depth`, with its checks and ValueErrors (raised
+        before the device is used).  Two launches, no host synchronisation.  Deterministic - the same bits for an image alone and
+        inside any batch.  RuntimeError for an image side above 16384."""
+        d, k, m, near, far = _depth_inputs("DepthField.from_depth", depth, intrinsics, mask, z_range)
+        d, k, m = _depth_upload(d, k, m, device)
+        return cls(*ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far), k)
+
+    def __len__(self):
+        return self.cls.shape[0]
+
+    def select(self, sl):
+        """The images `sl` (a slice) as a DepthField sharing this one's memory."""
+        return DepthField(self.cls[sl], self.z[sl], self.nearest[sl], self.intrinsics[sl])
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
@@ -1005,6 +1048,87 @@ def _check_pair(x, scans, n, what):
     if not 0 < n <= rows:
         raise ValueError("%s: n = %d outside (0, %d]" % (what, n, rows))
     return scans, B, rows, n
+
+
+# ------------------------------------------------------------------------------------------------ free space and silhouette
+class _FreeSpace(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, field, n, v_mask, mask_sb, margin):
+        _, _, loss, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
+        ctx.args = (field, n, v_mask, mask_sb, margin)
+        ctx.save_for_backward(x, counts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gL):
+        x, counts = ctx.saved_tensors
+        field, n, v_mask, mask_sb, margin = ctx.args
+        g = ops.free_space_bwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
+                               gL.to(torch.float32).contiguous())
+        return g, None, None, None, None, None
+
+
+def _check_free_space_weights(what, field, B, margin, weights=()):
+    """The ValueErrors of the free-space arguments: a DepthField of B images, a margin and weights that are >= 0 (and not NaN)."""
+    if not isinstance(field, DepthField):
+        raise ValueError("%s: the field must be a scan.DepthField, got %s" % (what, type(field).__name__))
+    if len(field) != B:
+        raise ValueError("%s: %d bodies, a field of %d images" % (what, B, len(field)))
+    if not float(margin) >= 0:
+        raise ValueError("%s: the margin must be >= 0, got %r" % (what, margin))
+    for name, w in weights:
+        if not float(w) >= 0:
+            raise ValueError("%s: %s must be >= 0, got %r" % (what, name, w))
+
+
+def _free_space_args(what, x_hat, field, pose, n, vertex_mask, margin):
+    if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
+        raise RuntimeError("semantichuman_amd.scan.%s needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
+                           % (what, getattr(x_hat, "device", type(x_hat))))
+    B, rows, _ = ops._points(x_hat, "scan." + what)
+    _check_free_space_weights(what, field, B, margin)
+    if pose is not None and len(pose) != B:
+        raise ValueError("%s: %d bodies, %d poses" % (what, B, len(pose)))
+    n = rows - 1 if n is None else int(n)
+    if not 0 < n <= rows:
+        raise ValueError("%s: n = %d outside (0, %d]" % (what, n, rows))
+    v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
+    x = x_hat if pose is None else pose.to_scan_frame(x_hat)
+    return x, n, v_mask, mask_sb
+
+
+def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0):
+    """What a one-view depth image adds to a fit beyond its points: -> (free [B], silhouette [B]), differentiable w.r.t. x_hat
+    (sh_free_space_fwd / _bwd; include/sh_kernels.h, "Depth field").  x_hat [B, rows, 3] fp32 on the GPU, field: a `DepthField` of
+    the same B.  Every active vertex is projected into its image (pinhole, the field's intrinsics) and reads the ONE pixel it
+    falls into:
+      * a SURFACE pixel whose depth, less `margin`, lies behind the vertex: the vertex stands in space the sensor saw through -
+        it adds (z - margin - Z)^2 to `free`;
+      * an EMPTY pixel: the body does not project here - it adds to `silhouette` the squared offset of the vertex from the ray
+        through the nearest pixel that is not EMPTY, at the vertex's own depth (the same units as `free`);
+      * an UNKNOWN pixel, a pixel outside the image, a vertex behind the camera: nothing.
+    Both are means over the active vertices.  n and vertex_mask as in `chamfer` (n=None: rows - 1).  pose: None - x_hat is in the
+    camera's frame - or a `Pose` (scan frame -> model frame): the vertices are carried into the camera's frame by
+    `pose.to_scan_frame` (plain torch, differentiable) and both values multiplied by pose.scale^2, which puts them in the units
+    of x_hat, where they add to a Chamfer value.  The pose takes no gradient.
+    Limits: nearest-pixel sampling - the image is read as a constant, the nearest pixel too, so there is no image gradient and
+    the value steps as a vertex crosses a pixel boundary; no robust or truncated form; pinhole without distortion; one view.
+    ValueError for a field of another batch size or a negative margin."""
+    x, n, v_mask, mask_sb = _free_space_args("free_space", x_hat, field, pose, n, vertex_mask, margin)
+    loss = _FreeSpace.apply(x, field, n, v_mask, mask_sb, float(margin))
+    if pose is not None:
+        loss = loss * (pose.scale * pose.scale)[:, None]
+    return loss[:, 0], loss[:, 1]
+
+
+def free_space_kinds(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0):
+    """What `free_space` did with every vertex -> (kind uint8 [B, n]: 0 no term, 1 free space, 2 silhouette, 3 an UNKNOWN pixel,
+    4 outside the image or behind the camera; counts int32 [B, 4] = active vertices and how many of kind 1, 2 and 4).  Not
+    differentiable."""
+    x, n, v_mask, mask_sb = _free_space_args("free_space_kinds", x_hat.detach() if torch.is_tensor(x_hat) else x_hat, field, pose, n,
+                                             vertex_mask, margin)
+    _, kind, _, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, float(margin))
+    return kind, counts
 
 
 def moment_pose(scans, x, n=None, vertex_mask=None, scale=True):
