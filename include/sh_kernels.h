@@ -255,7 +255,7 @@ typedef struct sh_stack_step {
 
 /* The kernel forms of an fp32 stack (sh_stack_forward / sh_stack_backward), decided in one place for both passes: from the steps, c0,
  * B, x_layout, mma_mode, keep_fp32 (the forward pass's; the backward pass's acts_fp32), need_x_grad and the switches SH_P3_N16_MAXB,
- * SH_P3_BWD, SH_P3_WGRAD, SH_P3_YPREV_IMG, SH_P3_DROP_FP32, SH_P3_RAGGED, SH_P3_GROUPED, SH_P3_PRESUM_IMG, SH_TR_RIDE.
+ * SH_P3_WGRAD, SH_P3_DROP_FP32, SH_P3_RAGGED, SH_P3_GROUPED.
  * sh_stack_plan_f32 writes per step an OR of SH_FORM_* flags (backward flags as a layer with a weight gradient runs them).  Both
  * sequencers compute this plan and require the per-step buffers it names (SH_ERR_INVALID_ARG when one is NULL); a caller sizes its
  * buffers from it. */
@@ -351,7 +351,7 @@ SH_API int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* 
  * update function), without writing and re-reading the gradient: 24 instead of 32 bytes of HBM traffic per weight.  `step` is
  * NOT advanced here (every workgroup reads it): the caller advances it once the launch is queued (sh_adam_bump, or a numel == 0 entry of sh_adam_step).  dbias as in
  * sh_linear_bwd_wgt (the bias keeps its ordinary gradient).  Served shapes: sh_linear_bwd_wgt_adam_ok (M <= 64, N and K
- * multiples of 64; SH_LIN_WGT_ADAM=0 makes it answer 0); others return SH_ERR_UNSUPPORTED and nothing is launched.
+ * multiples of 64); others return SH_ERR_UNSUPPORTED and nothing is launched.
  * Replaces, for one parameter, the pair reference `loss.backward()` (models.py:130 / :144 autograd of nn.Linear) +
  * `optimizer.step()` (train_funcs.py:391-392, 509-510).  Only valid when nothing else consumes that gradient between backward
  * and step (no all-reduce, clipping or accumulation over several backward passes).
@@ -1438,7 +1438,7 @@ SH_API int sh_spiral_conv_bwd_data_p3_rag(const void* dprep, const int32_t* rag_
 SH_API int sh_spiral_conv_p3_grp_ok(int B, int S, int Cg, int Nout, int g_L);
 SH_API int sh_spiral_conv_p3_grp_members(int B, int S, int Cg, int Nout);
 /* 1 when the launch has enough groups x batch groups to fill the chip with its coarser work items (the sequencers' rule for taking
- * the grouped form; SH_P3_GRP_MIN_ITEMS_PER_CU, default 12). */
+ * the grouped form: 12 work items per CU). */
 SH_API int sh_spiral_conv_p3_grp_pays(int B, int n_groups);
 SH_API int sh_spiral_conv_p3_grp(const void* xp, const int32_t* g_rows, const uint32_t* g_pos, const int32_t* g_out, int n_groups, int g_L,
                                  const void* wfrag3, const float* bias, float* y, int64_t y_sv, int64_t y_sb, void* yp, const float* yprev,

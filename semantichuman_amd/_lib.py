@@ -271,7 +271,8 @@ def build_id() -> str:
 
 
 def env_overrides() -> dict:
-    """The SH_* tuning / ablation switches set in this process's environment (they select kernels, never results)."""
+    """The SH_* switches set in this process's environment (they select kernels, never results).  The ones the library
+    still reads are listed, with who sets each, in DESIGN.md's "Switches" table."""
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("SH_") and not k.startswith(("SH_BENCH_", "SH_KERNEL_LIB"))}
 
 

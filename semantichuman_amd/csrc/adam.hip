@@ -122,7 +122,6 @@ static int adam_impl(int n_tensors, float* const* params, const float* const* gr
     SH_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0, SH_ERR_INVALID_ARG,
                "sh_adam_step: hyper-parameter out of range");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static const int nontemporal = sh_env_int("SH_ADAM_NT", 1, 0, 1);
     for (int t0 = 0; t0 < n_tensors; t0 += AT) {
         AdamArgs a{};
         a.nt = n_tensors - t0 < AT ? n_tensors - t0 : AT;
@@ -141,7 +140,7 @@ static int adam_impl(int n_tensors, float* const* params, const float* const* gr
             SH_REQUIRE(blocks < (1L << 31), SH_ERR_UNSUPPORTED, "sh_adam_step: too many elements in one launch");
         }
         a.blk_start[a.nt] = (int)blocks;
-        a.nontemporal = nontemporal;
+        a.nontemporal = 1;          // the full chunks stream past the caches (see the kernel)
         a.lr = lr; a.beta1 = beta1; a.beta2 = beta2;
         a.w1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.w2 = (float)(1.0 - beta2); a.eps = (float)eps; a.wd = (float)weight_decay;
         if (blocks > 0) {

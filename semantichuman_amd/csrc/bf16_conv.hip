@@ -477,7 +477,7 @@ int launch_bc(BCParams& p, hipStream_t st) {
         attr_set = 160 * 1024;
     }
     p.n_vg = sh_cdiv(p.R, RT);
-    const long tiles = (long)p.n_vg * sh_cdiv(p.B, MODE == BC_C64 ? 8 : 16);
+    const long tiles = (long)p.n_vg * sh_cdiv(p.B, 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_bf16: %ld work items", tiles);
     p.n_tiles = (int)tiles;
     // waves per workgroup and workgroups per CU from the LDS footprint of the resident weight (<= 16 waves per CU: the
@@ -547,20 +547,17 @@ int dispatch_bc_nt(BCParams& p, hipStream_t st) {
     p.nsplit = p.nt_tot / nt;
     while (nt > 1 && (long)p.nks * nt > 128) { nt >>= 1; p.nsplit <<= 1; }
     SH_REQUIRE((long)p.nks * nt <= 150, SH_ERR_UNSUPPORTED, "conv_bf16: K = %d too long for an LDS-resident weight slice", p.nks * 32);
-    const long tiles16 = (long)p.R * sh_cdiv(p.B, MODE == BC_C64 ? 8 : 16);      // work items if every wave took ONE vertex
+    const long tiles16 = (long)p.R * sh_cdiv(p.B, 16);      // work items if every wave took ONE vertex
     const long fill = 2L * num_cus() * 16;                       // aim for >= 2 items per resident wave
     if constexpr (OUTF32 || MODE == BC_C3F) {
         SH_REQUIRE(nt == 1 && p.nsplit == 1, SH_ERR_UNSUPPORTED, "conv_bf16: a 3-channel fp32 side needs <= 16 channels on the other (%d)",
                    p.Nout);
         return launch_bc<1, (MODE == BC_C3F ? 2 : 4), MODE, BWD, OUTF32>(p, st);
     } else {
-        constexpr int R4 = MODE == BC_C64 ? 2 : 4;              // the full-line form keeps two accumulator sets: 4 vertices per wave would not fit 128 VGPRs
-        if (nt == 1) return launch_bc<1, R4, MODE, BWD, false>(p, st);
-        if (nt == 2) return tiles16 / 4 >= fill ? launch_bc<2, R4, MODE, BWD, false>(p, st) : launch_bc<2, 2, MODE, BWD, false>(p, st);
+        if (nt == 1) return launch_bc<1, 4, MODE, BWD, false>(p, st);
+        if (nt == 2) return tiles16 / 4 >= fill ? launch_bc<2, 4, MODE, BWD, false>(p, st) : launch_bc<2, 2, MODE, BWD, false>(p, st);
         if (nt == 4) return tiles16 / 2 >= fill ? launch_bc<4, 2, MODE, BWD, false>(p, st) : launch_bc<4, 1, MODE, BWD, false>(p, st);
-        if constexpr (MODE != BC_C64) {                        // (two accumulator sets of 8 x 2 tiles would not fit the register budget)
-            if (tiles16 / 2 >= fill) return launch_bc<8, 2, MODE, BWD, false>(p, st);
-        }
+        if (tiles16 / 2 >= fill) return launch_bc<8, 2, MODE, BWD, false>(p, st);
         return launch_bc<8, 1, MODE, BWD, false>(p, st);
     }
 }
@@ -583,19 +580,13 @@ int dispatch_bc(BCParams& p, int in_f32, int out_f32, hipStream_t st) {
         SH_REQUIRE(p.Nout <= 16, SH_ERR_UNSUPPORTED, "conv_bf16: an fp32 output has <= 16 channels (got %d)", p.Nout);
         return p.Cg == 16 ? dispatch_bc_nt<BC_C16, BWD, true>(p, st) : dispatch_bc_nt<BC_C32, BWD, true>(p, st);
     }
-    static const int c64_on = sh_env_int("SH_BC_C64", 1, 0, 1);      // full-line form for 64 / 128 gathered channels
     SH_REQUIRE(p.Nout % 4 == 0 && ((reinterpret_cast<uintptr_t>(p.y) | (uintptr_t)p.y_rb | (uintptr_t)p.y_bb) & 7) == 0 &&
                (!p.yprev || ((reinterpret_cast<uintptr_t>(p.yprev) | (uintptr_t)p.yp_rb | (uintptr_t)p.yp_bb) & 7) == 0) &&
                (!p.bias || (reinterpret_cast<uintptr_t>(p.bias) & 15) == 0),
                SH_ERR_UNSUPPORTED, "conv_bf16: bf16 output needs channels %% 4 == 0 and 8-byte aligned rows");
-    // ... where the layer has <= 2 channel tiles per workgroup: with 4 or 8 the doubled weight-fragment reads from LDS cost more
-    // than the better loads bring (measured: 128 -> 64 and 64 -> 128 channel layers 19-26 us -> 22-27 us; 64 -> 32: 28 -> 21 us)
-    int nt_wg = p.nt_tot > 8 ? 8 : p.nt_tot;
-    while (nt_wg > 1 && (long)p.nks * nt_wg > 128) nt_wg >>= 1;
-    static const int co_on = sh_env_int("SH_BC_CO", 2, 0, 2);          // line-wise loads (BC_C32C); 2 (default): also instead of the full-line form (21.4 -> 17.0, 20.4 -> 14.8 us)
-    if (p.Cg % 64 == 0 && c64_on && nt_wg <= 2 && co_on < 2) return dispatch_bc_nt<BC_C64, BWD, false>(p, st);
-    if (p.Cg % 32 == 0 && co_on) return dispatch_bc_nt<BC_C32C, BWD, false>(p, st);
-    return p.Cg == 16 ? dispatch_bc_nt<BC_C16, BWD, false>(p, st) : dispatch_bc_nt<BC_C32, BWD, false>(p, st);
+    // line-wise loads (BC_C32C) for every multiple of 32 gathered channels: measured against the full-line form (BC_C64) on the
+    // 64- and 128-channel layers, 21.4 -> 17.0 and 20.4 -> 14.8 us
+    return p.Cg == 16 ? dispatch_bc_nt<BC_C16, BWD, false>(p, st) : dispatch_bc_nt<BC_C32C, BWD, false>(p, st);
 }
 
 inline bool dtype_ok(int d) { return d == SH_DTYPE_F32 || d == SH_DTYPE_BF16; }

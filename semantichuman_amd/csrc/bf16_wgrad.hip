@@ -327,13 +327,13 @@ __global__ __launch_bounds__(256) void wgrad_bf16_dma_kernel(const BDParams p) {
     }
 }
 
+constexpr int BW_SLAB_MB = 32;          // MiB of partial weight-gradient slabs one launch may write (both forms)
 struct BWPlan { int dma, qt, pt, n_qg, n_pt, nsplit, nslab, sps; long n_stages; };   // nsplit row chunks (one per wave), nslab = ceil(nsplit / 4) slabs
 BWPlan plan_bw(int B, int R, int S, int Cin, int Cout) {
     BWPlan w{};
-    static const int dma_on = sh_env_int("SH_BW_DMA", 1, 0, 1);
     const int K = S * Cin;
     const long rows = (long)R * B;
-    w.dma = dma_on && Cin % 16 == 0 && Cout % 16 == 0 && rows % 32 == 0;
+    w.dma = Cin % 16 == 0 && Cout % 16 == 0 && rows % 32 == 0;
     if (!w.dma) return w;
     const int pb = sh_cdiv(Cout, 16);
     w.pt = pb >= 4 ? 4 : pb >= 2 ? 2 : 1;
@@ -345,11 +345,10 @@ BWPlan plan_bw(int B, int R, int S, int Cin, int Cout) {
     // 1024 waves = 256 workgroups = ONE round of the chip (a workgroup's 160 KiB of LDS fills a CU): 2048 left a second round
     // of 240 workgroups behind the first 256 (6890 vertices, batch 64: the five launches 37.5 / 26.0 / 21.2 / 26.1 / 19.6 ->
     // 33.1 / 21.5 / 17.0 / 22.0 / 15.4 us, step 0.965 -> 0.945 ms; 768 and 1280 are both slower)
-    static const int wave_target = sh_env_int("SH_BW_WAVES", 1024, 64, 1 << 16);
-    static const int slab_mb = sh_env_int("SH_BW_SLAB_MB", 32, 1, 4096);
+    constexpr int BW_WAVES = 1024;
     const long tiles = (long)w.n_qg * w.n_pt;
-    long ns = wave_target / tiles;
-    const long cap = 4 * (((long)slab_mb << 20) / ((long)Cout * K * 4));  // four row chunks share a slab
+    long ns = BW_WAVES / tiles;
+    const long cap = 4 * (((long)BW_SLAB_MB << 20) / ((long)Cout * K * 4));  // four row chunks share a slab
     if (ns > cap) ns = cap;
     if (ns > w.n_stages / 6) ns = w.n_stages / 6;                        // >= 6 stages per wave (the ring holds 3-4)
     if (ns < 1) ns = 1;
@@ -398,10 +397,9 @@ int sh_wgrad_bf16_nsplit(int B, int R, int S, int Cin, int Cout) {
     const int Kq = Cin == 3 ? 4 * S : S * Cin, K = S * Cin;
     const long tiles = (long)sh_cdiv(Kq, 64) * sh_cdiv(Cout, 64);
     const long nst = ((long)R * B + 63) >> 6;
-    static const int wg_target = sh_env_int("SH_BW_BLOCKS", 2048, 64, 1 << 16);
-    static const int slab_mb = sh_env_int("SH_BW_SLAB_MB", 32, 1, 4096);
-    long ns = wg_target / tiles;
-    const long cap = ((long)slab_mb << 20) / ((long)Cout * K * 4);       // partial slabs are written and re-read once
+    constexpr int BW_BLOCKS = 2048;                                      // workgroups the staged form aims for
+    long ns = BW_BLOCKS / tiles;
+    const long cap = ((long)BW_SLAB_MB << 20) / ((long)Cout * K * 4);    // partial slabs are written and re-read once
     if (ns > cap) ns = cap;
     if (ns > nst / 4) ns = nst / 4;                                      // >= 4 stages per split
     if (ns < 1) ns = 1;

@@ -233,10 +233,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
 // wgrad_stream_kernel (spiral_conv.hip).  Every wave owns an output tile and feeds the matrix pipe
 // straight from 16-byte global loads; a few steps of loads are in flight while one multiplies.
 // MFMA t of a step takes element t of each loaded quad, so one 16-byte load feeds four MFMAs.
-#ifndef SH_LS_DEPTH
-#define SH_LS_DEPTH 2      // steps of loads in flight besides the one multiplying; measured 2 <= 3 < 5 (register pressure)
-#endif
-constexpr int LS_DEPTH = SH_LS_DEPTH;
+constexpr int LS_DEPTH = 2;      // steps of loads in flight besides the one multiplying; measured 2 <= 3 < 5 (register pressure)
 
 // runs f(s + J, J) for J = 0 .. D-1, stopping after the last valid step; the early exits are explicit branches so the
 // compiler sees that a skipped step ends the loop (independent `if`s make it drain all loads where the paths merge)
@@ -663,81 +660,15 @@ __global__ __launch_bounds__(LTHREADS) void linear_bwd_data_x3_kernel(const LSPa
     }
 }
 
-// weight gradient: dW[n][k] = sum_m dy[m][n] x[m][k].  Item = 64 x 64 output tile; the reduction index m (<= 64) is the
-// MFMA K dimension, both operands are loaded as quads along their OUTPUT index: lane (a, rr) holds dy[m0+rr][n0+4a..] and
-// x[m0+rr][k0+4a..]; MFMA (t', t) produces dW[n0 + 4 i + t'][k0 + 4 j + t] - one pair of loads feeds 16 MFMAs.
-// (A 16 x 256 tile with 1 KiB-contiguous writes was measured slower: 39 / 48 us against 38 / 40 us.)
-__global__ __launch_bounds__(LTHREADS) void linear_bwd_wgt_stream_kernel(const LSParams p) {
-    const int lane = threadIdx.x & 63, wave = sh_wave_id();
-    const int item = sh_xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
-    const int ktiles = p.K >> 6;
-    if (item >= (p.N >> 6) * ktiles) return;
-    const int kt = item % ktiles, ntile = item / ktiles;
-    const int n0 = ntile * 64, k0 = kt * 64;
-    const int la = lane & 15, rr = lane >> 4;
-    const int nsteps = (p.M + 3) >> 2;
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 dq[4], xq[4];
-    auto load = [&](int s, f32x4& d4, f32x4& x4) {
-        s = s < nsteps ? s : nsteps - 1;
-        const int m = 4 * s + rr;
-        const int mc = m < p.M ? m : p.M - 1;
-        d4 = *reinterpret_cast<const f32x4*>(p.a + (long)mc * p.N + n0 + 4 * la);
-        x4 = *reinterpret_cast<const f32x4*>(p.w + (long)mc * p.K + k0 + 4 * la);
-        if (m >= p.M) d4 = (f32x4){0.f, 0.f, 0.f, 0.f};            // rows are the reduction index
-    };
-    // the tiles of the first column block also own the bias gradient of their 64 rows: db[n] = sum_m dy[m][n]
-    const bool own_bias = kt == 0 && p.dbias != nullptr;
-    f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
-    auto mma = [&](const f32x4& d4, const f32x4& x4) {
-#pragma unroll
-        for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk) acc[tn][tk] = __builtin_amdgcn_mfma_f32_16x16x4f32(d4[tn], x4[tk], acc[tn][tk], 0, 0, 0);
-        if (own_bias) bsum += d4;
-    };
-    // M <= 64 -> at most 16 steps: four register sets rotate
-    load(0, dq[0], xq[0]); load(1, dq[1], xq[1]); load(2, dq[2], xq[2]);
-    for (int s = 0; s < nsteps; s += 4) {
-        load(s + 3, dq[3], xq[3]); __builtin_amdgcn_sched_barrier(0); mma(dq[0], xq[0]);
-        if (s + 1 >= nsteps) break;
-        load(s + 4, dq[0], xq[0]); __builtin_amdgcn_sched_barrier(0); mma(dq[1], xq[1]);
-        if (s + 2 >= nsteps) break;
-        load(s + 5, dq[1], xq[1]); __builtin_amdgcn_sched_barrier(0); mma(dq[2], xq[2]);
-        if (s + 3 >= nsteps) break;
-        load(s + 6, dq[2], xq[2]); __builtin_amdgcn_sched_barrier(0); mma(dq[3], xq[3]);
-    }
-    if (own_bias) {                                                   // fixed order: steps in sequence, then the four row groups
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v = bsum[j];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            bsum[j] = v;
-        }
-        if (rr == 0) *reinterpret_cast<f32x4*>(p.dbias + n0 + 4 * la) = bsum;
-    }
-    // acc[tn][tk][jj] = dW[n0 + 16 rr + 4 jj + tn][k0 + 4 la + tk]
-#pragma unroll
-    for (int tn = 0; tn < 4; ++tn)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            float* dst = p.out + (long)(n0 + 16 * rr + 4 * jj + tn) * p.K + k0 + 4 * la;
-            __builtin_nontemporal_store((f32x4){acc[tn][0][jj], acc[tn][1][jj], acc[tn][2][jj], acc[tn][3][jj]}, reinterpret_cast<f32x4*>(dst));
-        }
-}
-
-// LDS-DMA form of the weight gradient (round 2).  The streaming kernel above keeps three 2-KiB steps of loads in flight per
-// wave against 16 MFMAs (0.2 us) per step: a tile is a chain of ~5 round trips.  Here a workgroup takes one 64-row block of
-// dy and FOUR 64-column blocks of x: the whole dy tile [M <= 64][64] (shared) and each wave's x tile [M][64] go memory -> LDS
-// in one volley of global_load_lds_dwordx4 (256-byte rows, four per instruction, their 16-byte pieces XOR-swizzled by the row
-// so that the four row groups of a fragment read hit different banks), one wait, one barrier, then the same 16 x 16 MFMAs
-// per 4 reduction rows as above with both quads read from LDS.  80 KiB per workgroup: two per CU, one loading while the
-// other multiplies.  Same products in the same order as the streaming kernel: bit-identical results.
+// Weight gradient: dW[n][k] = sum_m dy[m][n] x[m][k], LDS-DMA form (round 2).  A wave owns a 64 x 64 output tile; the reduction
+// index m (<= 64) is the MFMA K dimension and both operands are read as quads along their OUTPUT index, so MFMA (t', t) of a step
+// produces dW[n0 + 4 i + t'][k0 + 4 j + t] - one pair of quads feeds 16 MFMAs.  (The wave-autonomous form it replaced kept three
+// 2-KiB steps of loads in flight per wave against 16 MFMAs (0.2 us) per step: a tile was a chain of ~5 round trips.)  A workgroup
+// takes one 64-row block of dy and FOUR 64-column blocks of x: the whole dy tile [M <= 64][64] (shared) and each wave's x tile
+// [M][64] go memory -> LDS in one volley of global_load_lds_dwordx4 (256-byte rows, four per instruction, their 16-byte pieces
+// XOR-swizzled by the row so that the four row groups of a fragment read hit different banks), one wait, one barrier, then
+// 16 x 16 MFMAs per 4 reduction rows with both quads read from LDS.  80 KiB per workgroup: two per CU, one loading while the
+// other multiplies.
 // X3 (round 5): steps of 32 reduction rows on v_mfma_f32_16x16x32_bf16; a lane's eight rows are m = 32 s + 4 j + rr (j = 0..7; rows
 // 4 apart, so that the four row groups of a read keep their different swizzles: no bank conflicts), element tn / tk of its eight
 // dy / x quads split exactly into three bf16 terms: 16 x 6 MFMAs of 16 cycles per 32 rows against 8 x 16 of 32.
@@ -911,14 +842,11 @@ void linear_bwd_wgt_dma_kernel(const LSParams p) {
 struct LSPlan { bool ok; int range, nsplit, groups; };
 LSPlan plan_stream(int M, int out_cols, int red_len, int gran = 16, bool chunked = false) {   // gran: reduction steps of the kernel (bf16x3 forms: 32)
     LSPlan pl{false, red_len, 1, out_cols / 64};
-    static const int on = sh_env_int("SH_LIN_STREAM", 1, 0, 1);
     // chunked: the forward LDS-DMA kernel takes any batch as 64-row chunks (gridDim.y) when the reduction is not split
-    // (only with the LDS-DMA forward kernel enabled - under SH_LIN_DMA=0 a batch above 64 rows keeps the skinny GEMM: ADVICE r5)
-    static const int dma_on = sh_env_int("SH_LIN_DMA", 1, 0, 1);
-    const bool big_ok = chunked && dma_on && red_len < 1024 && red_len % 32 == 0 && (out_cols / 64) % 4 == 0;
-    if (!on || (M > 64 && !big_ok) || out_cols % 64 != 0 || red_len % gran != 0) return pl;
+    const bool big_ok = chunked && red_len < 1024 && red_len % 32 == 0 && (out_cols / 64) % 4 == 0;
+    if ((M > 64 && !big_ok) || out_cols % 64 != 0 || red_len % gran != 0) return pl;
     pl.ok = true;
-    static const int items = sh_env_int("SH_LIN_ITEMS", 1024, 64, 1 << 20);
+    constexpr int items = 1024;          // one wave per SIMD
     if (pl.groups < items / 2 && red_len >= 1024) {
         int ns = items / pl.groups;
         int rg = sh_cdiv(sh_cdiv(red_len, ns), gran) * gran;
@@ -982,11 +910,8 @@ int run_gemm(SGParams& p, void* ws, size_t ws_bytes, hipStream_t st, const char*
 }
 
 // launches the forward / backward-data streaming kernel (+ the split reduction); `cols` = output columns
-// does this call run the bf16x3 kernels?  (mma_mode SH_MMA_SPLIT3 / SH_MMA_PLANES3; SH_LIN_X3=0 keeps the fp32 MFMA kernels)
-inline bool lin_x3(int mma_mode) {
-    static const int on = sh_env_int("SH_LIN_X3", 1, 0, 1);
-    return on && (mma_mode == SH_MMA_SPLIT3 || mma_mode == SH_MMA_PLANES3);
-}
+// does this call run the bf16x3 kernels?  (mma_mode SH_MMA_SPLIT3 / SH_MMA_PLANES3)
+inline bool lin_x3(int mma_mode) { return mma_mode == SH_MMA_SPLIT3 || mma_mode == SH_MMA_PLANES3; }
 
 template <bool FWD>
 int run_stream(LSParams& p, const LSPlan& pl, int cols, void* ws, size_t ws_bytes, hipStream_t st, const char* what, bool x3 = false) {
@@ -1004,9 +929,8 @@ int run_stream(LSParams& p, const LSPlan& pl, int cols, void* ws, size_t ws_byte
 #define SH_LS_CASE(MTV)                                                                                                   \
     if (FWD) SH_LAUNCH_PS(ps, linear_fwd_stream_kernel<MTV>, dim3(grid), dim3(LTHREADS), 0, st, p);                     \
     else SH_LAUNCH_PS(ps, linear_bwd_data_stream_kernel<MTV>, dim3(grid), dim3(LTHREADS), 0, st, p)
-        static const int dma_on = sh_env_int("SH_LIN_DMA", 1, 0, 1);
-        const bool dma = FWD && dma_on && p.K % 32 == 0 && p.range % 32 == 0 && p.groups % 4 == 0;
-        SH_REQUIRE(mchunks == 1 || dma, SH_ERR_UNSUPPORTED, "%s: more than 64 rows need the LDS-DMA forward form (SH_LIN_DMA=1)", what);
+        const bool dma = FWD && p.K % 32 == 0 && p.range % 32 == 0 && p.groups % 4 == 0;
+        SH_REQUIRE(mchunks == 1 || dma, SH_ERR_UNSUPPORTED, "%s: more than 64 rows need the LDS-DMA forward form", what);
         if (x3 && !FWD) {
             snprintf(ps.name, sizeof ps.name, "linear_bwd_data_x3_kernel<%d>|M=%d N=%d K=%d split=%d", mt, p.M, p.N, p.K, p.nsplit);
             if (mt == 1) SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<1>, dim3(grid), dim3(LTHREADS), 0, st, p);
@@ -1098,33 +1022,29 @@ int sh_linear_fwd(const float* x, const float* weight, const float* bias, float*
     if (lin_x3(mma_mode) && M > 64 && K % 32 == 0 && K <= 384 && N % 64 == 0 && aligned16(x, weight, y) &&
         (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0)) {
         // large batch, short reduction: the weight tile split once per workgroup (linear_fwd_wide_x3_kernel)
-        static const int wide_on = sh_env_int("SH_LIN_WIDE", 1, 0, 1);
-        if (wide_on) {
-            hipStream_t st = static_cast<hipStream_t>(stream);
-            const size_t smem = (size_t)(K / 32) * 4 * 3072;
-            static bool attr_set = false;
-            if (!attr_set) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_wide_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        160 * 1024) != hipSuccess) {
-                    (void)hipGetLastError();
-                    sh_set_error("linear_fwd: cannot raise the dynamic LDS limit to %zu bytes", smem);
-                    return SH_ERR_LAUNCH;
-                }
-                attr_set = true;
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        const size_t smem = (size_t)(K / 32) * 4 * 3072;
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_wide_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    160 * 1024) != hipSuccess) {
+                (void)hipGetLastError();
+                sh_set_error("linear_fwd: cannot raise the dynamic LDS limit to %zu bytes", smem);
+                return SH_ERR_LAUNCH;
             }
-            LSParams s{};
-            s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
-            ShProfScope ps(st, "linear_fwd_wide_x3_kernel|M=%d N=%d K=%d", M, N, K);
-            SH_LAUNCH_PS(ps, linear_fwd_wide_x3_kernel, dim3(N / 64), dim3(LFW_WAVES * 64), smem, st, s);
-            SH_CHECK_LAUNCH("linear_fwd_wide");
-            return SH_OK;
+            attr_set = true;
         }
+        LSParams s{};
+        s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
+        ShProfScope ps(st, "linear_fwd_wide_x3_kernel|M=%d N=%d K=%d", M, N, K);
+        SH_LAUNCH_PS(ps, linear_fwd_wide_x3_kernel, dim3(N / 64), dim3(LFW_WAVES * 64), smem, st, s);
+        SH_CHECK_LAUNCH("linear_fwd_wide");
+        return SH_OK;
     }
     {
         // bf16x3 form: the LDS-DMA kernel's shapes (32-wide stages, four column groups per workgroup); anything else keeps fp32 MFMA
         const bool x3 = lin_x3(mma_mode) && K % 32 == 0 && (N / 64) % 4 == 0;
-        static const int chunk_on = sh_env_int("SH_LIN_CHUNKED", 1, 0, 1);
-        const LSPlan pl = plan_stream(M, N, K, x3 ? 32 : 16, chunk_on && M > 64);
+        const LSPlan pl = plan_stream(M, N, K, x3 ? 32 : 16, M > 64);
         if (pl.ok && aligned16(x, weight, y) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0)) {
             LSParams s{};
             s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
@@ -1184,26 +1104,18 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
     SH_REQUIRE(dy && x && dW && M > 0 && N > 0 && K > 0, SH_ERR_INVALID_ARG, "sh_linear_bwd_wgt: bad argument");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_linear_bwd_wgt: unknown mma_mode %d", mma_mode);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static const int stream_on = sh_env_int("SH_LIN_STREAM", 1, 0, 1);
-    if (stream_on && M <= 64 && N % 64 == 0 && K % 64 == 0 && aligned16(dy, x, dW)) {
+    if (M <= 64 && N % 64 == 0 && K % 64 == 0 && aligned16(dy, x, dW)) {
         LSParams s{};
         s.a = dy; s.w = x; s.out = dW; s.M = M; s.N = N; s.K = K;
         s.dbias = (dbias && (reinterpret_cast<uintptr_t>(dbias) & 15) == 0) ? dbias : nullptr;      // fused into the tile kernel
-        const int items = (N / 64) * (K / 64);
-        static const int dma_on = sh_env_int("SH_LIN_WGT_DMA", 1, 0, 1);
-        if (dma_on) {
-            if (!wgt_dma_attr()) return SH_ERR_LAUNCH;
-            const int wgs = (N / 64) * sh_cdiv(K / 64, 4);
-            if (lin_x3(mma_mode)) {
-                ShProfScope ps(st, "linear_bwd_wgt_x3_kernel|M=%d N=%d K=%d", M, N, K);
-                SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<true>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-            } else {
-                ShProfScope ps(st, "linear_bwd_wgt_dma_kernel|M=%d N=%d K=%d", M, N, K);
-                SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<false>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-            }
+        if (!wgt_dma_attr()) return SH_ERR_LAUNCH;
+        const int wgs = (N / 64) * sh_cdiv(K / 64, 4);
+        if (lin_x3(mma_mode)) {
+            ShProfScope ps(st, "linear_bwd_wgt_x3_kernel|M=%d N=%d K=%d", M, N, K);
+            SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<true>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
         } else {
-            ShProfScope ps(st, "linear_bwd_wgt_stream_kernel|M=%d N=%d K=%d", M, N, K);
-            SH_LAUNCH_PS(ps, linear_bwd_wgt_stream_kernel, dim3(sh_cdiv(items, 4)), dim3(LTHREADS), 0, st, s);
+            ShProfScope ps(st, "linear_bwd_wgt_dma_kernel|M=%d N=%d K=%d", M, N, K);
+            SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<false>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
         }
         if (dbias && !s.dbias) hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, dy, M, N, dbias);
         SH_CHECK_LAUNCH("linear_bwd_wgt");
@@ -1224,8 +1136,7 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
 }
 
 int sh_linear_bwd_wgt_adam_ok(int M, int N, int K) {
-    static const int on = sh_env_int("SH_LIN_WGT_ADAM", 1, 0, 1);
-    return on && M > 0 && M <= 64 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0;
+    return M > 0 && M <= 64 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0;
 }
 
 int sh_linear_bwd_wgt_adam(const void* dy, int dy_dtype, const void* x, int x_dtype, float* weight, void* weight_bf16, float* exp_avg,

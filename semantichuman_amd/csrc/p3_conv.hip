@@ -108,6 +108,8 @@ __device__ __forceinline__ bool p3_ring_steps(int ks, int nks, F&& f) {
 #ifndef P3_WAVES_PER_EU
 #define P3_WAVES_PER_EU 4
 #endif
+constexpr int P3_WAVES_CU = 4 * P3_WAVES_PER_EU;      // resident waves per CU the registers allow (the launchers' 16 / 8 / 4 waves per workgroup)
+static_assert(P3_WAVES_CU == 16, "the launchers size workgroups for 16 resident waves per CU");
 // Diagnostic builds only (tools/exp/r06_p3_ablate.sh; never the shipped library): what of a k-step is left in conv_p3_kernel -
 // 1: no gathered loads (operands from registers), 2: the loads alone (no weight reads, no MFMAs), 3: loads + weight-fragment reads from
 // LDS, no MFMAs, 4: loads + MFMAs with weight fragments from registers (no LDS reads).  Results are garbage; times tell what bounds it.
@@ -965,19 +967,15 @@ inline P3Geom p3_geom(int S, int Cg, int Nout) {
 }
 // the streaming form: gathered channels in 32s; whole slices of 64 output channels, or 32 output channels (two tiles)
 inline bool p3s_shape_ok(int S, int Cg, int Nout) {
-    static const int on = sh_env_int("SH_P3_STREAM", 1, 0, 1);
-    static const int pad_on = sh_env_int("SH_P3S_PAD", 1, 0, 1), nt2_on = sh_env_int("SH_P3S_NT2", 1, 0, 1);
-    if (!on || Cg % 32 || !(Nout % 64 == 0 || (nt2_on && Nout == 32))) return false;
-    const ShFragGeom g = sh_frag_geom(S, Cg, Nout);
-    return (pad_on || g.nks % P3S_KC == 0) && (Nout == 32 || g.nt_tot % P3S_NT == 0);
+    if (Cg % 32 || !(Nout % 64 == 0 || Nout == 32)) return false;
+    return Nout == 32 || sh_frag_geom(S, Cg, Nout).nt_tot % P3S_NT == 0;      // (k-steps are padded to whole chunks: p3_nks)
 }
 // (dispatch_p3_nt builds 1, 2, 4 and 8 channel tiles per workgroup, and only 1 and 2 for 16 gathered channels; the list kernels
 // check their own, fewer, tile counts)
 inline bool p3_resident_ok(int S, int Cg, int Nout) {
     const P3Geom g = p3_geom(S, Cg, Nout);
-    static const int max_split = sh_env_int("SH_P3_MAX_SPLIT", 1, 1, 8);      // output-channel slices re-gather the input
     const bool built = Cg == 16 ? g.nt <= 2 : (g.nt == 1 || g.nt == 2 || g.nt == 4 || g.nt == 8);
-    return (long)g.nks * g.nt * 3 <= 150 && g.nsplit <= max_split && built;
+    return (long)g.nks * g.nt * 3 <= 150 && g.nsplit == 1 && built;      // one slice: output-channel slices re-gather the input
 }
 // k-steps of a layer's three-plane fragment buffer: sh_frag_geom's, rounded up to whole chunks where the weight is streamed
 inline int p3_nks(int S, int Cg, int Nout) {
@@ -1025,9 +1023,8 @@ int launch_p3s(P3Params& p, hipStream_t st) {
 }
 template <bool BWD, int NP>
 int dispatch_p3s(P3Params& p, hipStream_t st) {
-    static const int rt = sh_env_int("SH_P3S_RT", 2, 1, 2);
     if (p.nt_tot == 2) return launch_p3s<2, BWD, NP, 2>(p, st);          // 32 output channels: two tiles, two vertices per wave
-    return rt == 2 ? launch_p3s<2, BWD, NP>(p, st) : launch_p3s<1, BWD, NP>(p, st);
+    return launch_p3s<2, BWD, NP>(p, st);
 }
 
 template <int NT, int RT, bool C16, bool BWD, int NP, bool F32R = false>
@@ -1048,10 +1045,8 @@ int launch_p3(P3Params& p, hipStream_t st) {
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3: %ld work items", tiles);
     p.n_tiles = (int)tiles;
     const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    static const int waves_cu = sh_env_int("SH_P3_WAVES_CU", 4 * P3_WAVES_PER_EU, 16, 32);      // resident waves per CU the registers allow
-    int nw = waves_cu / per_cu;
-    if (nw > 16) nw = 16;
-    while (nw > 4 && (nw & 1) == 0 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
+    int nw = P3_WAVES_CU / per_cu;
+    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
     long groups = (tiles + nw - 1) / nw;
     const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
     if (groups > cap) groups = cap;
@@ -1084,10 +1079,8 @@ int launch_p3r(P3Params& p, hipStream_t st) {
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3r: %ld work items", tiles);
     p.n_tiles = (int)tiles;
     const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    static const int waves_cu = sh_env_int("SH_P3_WAVES_CU", 4 * P3_WAVES_PER_EU, 16, 32);
-    int nw = waves_cu / per_cu;
-    if (nw > 16) nw = 16;
-    while (nw > 4 && (nw & 1) == 0 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
+    int nw = P3_WAVES_CU / per_cu;
+    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
     long groups = (tiles + nw - 1) / nw;
     const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
     if (groups > cap) groups = cap;
@@ -1119,10 +1112,8 @@ int launch_p3g(P3Params& p, hipStream_t st) {
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3g: %ld work items", tiles);
     p.n_tiles = (int)tiles;
     const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    static const int waves_cu = sh_env_int("SH_P3_WAVES_CU", 4 * P3_WAVES_PER_EU, 16, 32);
-    int nw = waves_cu / per_cu;
-    if (nw > 16) nw = 16;
-    while (nw > 4 && (nw & 1) == 0 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
+    int nw = P3_WAVES_CU / per_cu;
+    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
     long groups = (tiles + nw - 1) / nw;
     const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
     if (groups > cap) groups = cap;
@@ -1141,8 +1132,7 @@ template <bool C16, bool BWD, int NP, bool F32R = false>
 int dispatch_p3_nt(P3Params& p, int nt, hipStream_t st) {
     const long tiles16 = (long)p.R * (p.B / 16);
     const long fill = 2L * p3_num_cus() * 16;
-    static const int rt_force = sh_env_int("SH_P3_RT", 0, 0, 2);
-    const bool two = rt_force ? rt_force == 2 : tiles16 / 2 >= fill;
+    const bool two = tiles16 / 2 >= fill;
     if (nt == 1) return two ? launch_p3<1, 2, C16, BWD, NP, F32R>(p, st) : launch_p3<1, 1, C16, BWD, NP, F32R>(p, st);
     if (nt == 2) return two ? launch_p3<2, 2, C16, BWD, NP, F32R>(p, st) : launch_p3<2, 1, C16, BWD, NP, F32R>(p, st);
     if constexpr (!C16) {
@@ -1286,8 +1276,7 @@ int sh_spiral_conv_bwd_data_p3(const void* dprep, int dpre_zero_row, const float
         p.yvi_bgb = Cin == 16 ? 1536 : (long)(Cin / 32) * 3072; p.yvi_vb = p.yvi_bgb * (B / 16);
     }
     p.B = B; p.R = n_in; p.S = S; p.Cg = Cout; p.Nout = Cin; p.act = act_prev; p.zero_row = zero_row;
-    static const int skip_on = sh_env_int("SH_P3_SKIP", 1, 0, 1);
-    p.skip_row = skip_on ? dpre_zero_row : -1;
+    p.skip_row = dpre_zero_row;
     p.n_img = 0x7fffffff;
     if (dpre_f32) {
         SH_REQUIRE(n_image_rows >= 0 && (reinterpret_cast<uintptr_t>(dpre_f32) & 15) == 0 && ((dp_sv | dp_sb) & 3) == 0, SH_ERR_INVALID_ARG,
@@ -1347,8 +1336,7 @@ int sh_spiral_conv_bwd_data_p3_rag(const void* dprep, const int32_t* rag_rows, c
 }
 
 int sh_spiral_conv_p3_grp_ok(int B, int S, int Cg, int Nout, int g_L) {
-    static const int c16_on = sh_env_int("SH_P3_GRP_C16", 1, 0, 1);
-    if (!(Cg % 32 == 0 || (Cg == 16 && c16_on && p3_geom(S, Cg, Nout).nt <= 2))) return 0;
+    if (!(Cg % 32 == 0 || (Cg == 16 && p3_geom(S, Cg, Nout).nt <= 2))) return 0;
     return p3_shape_ok(B, S, Cg, Nout) && p3_resident_ok(S, Cg, Nout) && p3_geom(S, Cg, Nout).nt <= 4 && S < 255 && g_L > 0 && g_L <= 64;
 }
 
@@ -1363,8 +1351,8 @@ int sh_spiral_conv_p3_grp_members(int B, int S, int Cg, int Nout) {
 // item of up to four rows - with fewer than ~one item per resident wave the launch loses more to its coarser, uneven items than the
 // halved gather brings (449-493 groups x 4 batch groups: +2.3 ... +4.0 us; 886-1760 x 4: -0.8 ... -8.2 us).
 int sh_spiral_conv_p3_grp_pays(int B, int n_groups) {
-    static const int min_per_cu = sh_env_int("SH_P3_GRP_MIN_ITEMS_PER_CU", 12, 0, 1 << 20);
-    return B >= 16 && (long)n_groups * (B / 16) >= (long)min_per_cu * p3_num_cus();
+    constexpr int P3_GRP_MIN_ITEMS_PER_CU = 12;
+    return B >= 16 && (long)n_groups * (B / 16) >= (long)P3_GRP_MIN_ITEMS_PER_CU * p3_num_cus();
 }
 
 int sh_spiral_conv_p3_grp(const void* xp, const int32_t* g_rows, const uint32_t* g_pos, const int32_t* g_out, int n_groups, int g_L,

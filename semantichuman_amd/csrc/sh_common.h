@@ -101,17 +101,8 @@ __device__ __forceinline__ int sh_xcd_remap(int bid, int nwg) {
 // The index of a wave in its workgroup as a SCALAR (readfirstlane of threadIdx.x >> 6, which is uniform over a wave by
 // construction - hipcc does not know).  Work-item decoding, loop bounds and branches derived from it are then uniform values:
 // real branches and SALU arithmetic instead of predicated VALU code.  Round 5, measured kernel by kernel (profiles/
-// r05_kernel_experiments.txt); -DSH_SCALAR_WAVE=0 builds the old form.
-#ifndef SH_SCALAR_WAVE
-#define SH_SCALAR_WAVE 1
-#endif
-__device__ __forceinline__ int sh_wave_id() {
-#if SH_SCALAR_WAVE
-    return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
-    return (int)(threadIdx.x >> 6);
-#endif
-}
+// r05_kernel_experiments.txt).
+__device__ __forceinline__ int sh_wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 __device__ __forceinline__ float sh_wave_sum(float v) {
 #pragma unroll
@@ -136,5 +127,7 @@ struct ShMmaScope {
     explicit ShMmaScope(int mode);
     ~ShMmaScope();
 };
-// tuning knob from the environment (read once by the caller through a function-local static)
+// a switch from the environment (read once by the caller through a function-local static).  Every name read here has a row in
+// DESIGN.md's "Switches" table saying who outside the library sets it (tests/test_host_logic.py compares the two sets): a new
+// A/B experiment belongs in a scratch build, not in a new read.
 int sh_env_int(const char* name, int dflt, int lo, int hi);

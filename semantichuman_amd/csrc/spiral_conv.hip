@@ -769,19 +769,13 @@ __global__ __launch_bounds__(NTHREADS) void gather_gemm_split3_kernel(const GGPa
 template <int NT, bool BWD_EPI>
 int launch_s3(const GGParams& p_in, int rt, hipStream_t st) {
     GGParams p = p_in;
-    const int tb = 1 << p.log2TB;
-    if (tb > 64 * rt) rt = 2;
     const int TV = (64 * rt) >> p.log2TB;
     p.n_vtiles = sh_cdiv(p.R, TV);
     const int nblocks = p.n_vtiles * p.n_btiles * p.nsplit;
     const size_t smem = (size_t)(3 * 3 * NT * 64) * 16 + (size_t)(TV * p.S) * sizeof(int);
-    static const int all9 = sh_env_int("SH_S3_ALL9", 0, 0, 1);
-    ShProfScope ps(st, "gather_gemm_split3_kernel<%d, %s, %d, %s>|R=%d B=%d K=%d N=%d grid=%d", NT, BWD_EPI ? "true" : "false", rt,
-                   all9 ? "true" : "false", p.R, p.B, p.K, p.Nout, nblocks);
-    if (all9) {
-        if (rt == 1) SH_LAUNCH_PS(ps, (gather_gemm_split3_kernel<NT, BWD_EPI, 1, true>), dim3(nblocks), dim3(NTHREADS), smem, st, p);
-        else SH_LAUNCH_PS(ps, (gather_gemm_split3_kernel<NT, BWD_EPI, 2, true>), dim3(nblocks), dim3(NTHREADS), smem, st, p);
-    } else if (rt == 1) SH_LAUNCH_PS(ps, (gather_gemm_split3_kernel<NT, BWD_EPI, 1>), dim3(nblocks), dim3(NTHREADS), smem, st, p);
+    ShProfScope ps(st, "gather_gemm_split3_kernel<%d, %s, %d, false>|R=%d B=%d K=%d N=%d grid=%d", NT, BWD_EPI ? "true" : "false", rt,
+                   p.R, p.B, p.K, p.Nout, nblocks);
+    if (rt == 1) SH_LAUNCH_PS(ps, (gather_gemm_split3_kernel<NT, BWD_EPI, 1>), dim3(nblocks), dim3(NTHREADS), smem, st, p);
     else SH_LAUNCH_PS(ps, (gather_gemm_split3_kernel<NT, BWD_EPI, 2>), dim3(nblocks), dim3(NTHREADS), smem, st, p);
     SH_CHECK_LAUNCH("gather_gemm_split3");
     return SH_OK;
@@ -792,11 +786,8 @@ int launch_ggd(const GGParams& p_in, int nblocks128 /* workgroups if the tiles h
     // 16-row tiles per wave.  Measured on MI355X (B = 64): one tile per wave (64-row workgroups, twice as many of them)
     // is 3-8 % faster while the launch has <= 1024 workgroups of 128 rows, two tiles are level above that, four are
     // 10-30 % slower (registers: fewer waves per SIMD to hide the LDS and global latencies).
-    static const int rt_pref = sh_env_int("SH_GG_RT", 0, 0, 2);
     GGParams p = p_in;
-    const int tb = 1 << p.log2TB;
-    int rt = rt_pref == 0 ? (nblocks128 <= 1024 ? 1 : 2) : rt_pref;
-    if (tb > 64 * rt) rt = 2;
+    const int rt = nblocks128 <= 1024 ? 1 : 2;
     const int TV = (64 * rt) >> p.log2TB;
     p.n_vtiles = sh_cdiv(p.R, TV);
     const int nblocks = p.n_vtiles * p.n_btiles * p.nsplit;
@@ -906,7 +897,7 @@ __global__ __launch_bounds__(256) void conv_out3_linewise_kernel(const GGParams 
 
 template <int S>
 int launch_out3(const GGParams& p, hipStream_t st) {
-    static const int grid = 8 * sh_env_int("SH_OUT3_WG_PER_XCD", 64, 1, 1024);       // 2 workgroups per CU
+    constexpr int grid = 8 * 64;       // 64 workgroups per XCD: 2 per CU
     ShProfScope ps(st, "conv_out3_linewise_kernel<%d>|R=%d B=%d K=%d N=%d grid=%d pass=%d", S, p.R, p.B, p.pass == 1 ? S * 16 : p.K, p.Nout, grid, p.pass);
     SH_LAUNCH_PS(ps, conv_out3_linewise_kernel<S>, dim3(grid), dim3(256), 0, st, p);
     SH_CHECK_LAUNCH("conv_out3_linewise");
@@ -934,14 +925,13 @@ int launch_gg(const GGParams& p, int nblocks, hipStream_t st) {
 
 template <bool BWD_EPI>
 int dispatch_gg(GGParams& p, hipStream_t st) {
-    // batch slice per tile: a power of two <= SH_GG_TB (default 16).  Narrow slices keep the
+    // batch slice per tile: a power of two <= GG_TB.  Narrow slices keep the
     // working set of an XCD's sweep (neighbour rows x slice width) inside its 4 MiB L2.
-    static const int tb_pref = sh_env_int("SH_GG_TB", 16, 1, TM);
+    constexpr int GG_TB = 16;
     int tb = 1;
-    while (tb < p.B && tb < tb_pref) tb <<= 1;
+    while (tb < p.B && tb < GG_TB) tb <<= 1;
     p.log2TB = sh_ilog2_floor(tb);
-    static const int skip_env = sh_env_int("SH_GG_SKIP", 1, 0, 1);
-    p.skip_on = (BWD_EPI && skip_env && p.skip_on && tb == 16 && p.Cg % 16 == 0) ? 1 : 0;
+    p.skip_on = (BWD_EPI && p.skip_on && tb == 16 && p.Cg % 16 == 0) ? 1 : 0;
     const int TV = TM >> p.log2TB;
     p.n_btiles = sh_cdiv(p.B, tb);
     p.n_vtiles = sh_cdiv(p.R, TV);
@@ -952,8 +942,7 @@ int dispatch_gg(GGParams& p, hipStream_t st) {
     int nt = nt_all <= 1 ? 1 : nt_all <= 2 ? 2 : nt_all <= 4 ? 4 : 8;
     const int nsplit0 = sh_cdiv(nt_all, nt);
     // 3-channel gathered rows (built for one channel tile): dwordx3 loads, K counted in zero-padded quads
-    static const int c3_on = sh_env_int("SH_GG_C3", 1, 0, 1);
-    const bool c3 = c3_on && p.Cg == 3 && nt == 1 && reinterpret_cast<uintptr_t>(p.w) % 4 == 0;
+    const bool c3 = p.Cg == 3 && nt == 1 && reinterpret_cast<uintptr_t>(p.w) % 4 == 0;
     if (c3) { p.Cg = 4; p.K = 4 * p.S; }
     p.nchunks = sh_cdiv(p.K, KC);
     const long nblocks = (long)p.n_vtiles * p.n_btiles;
@@ -966,8 +955,7 @@ int dispatch_gg(GGParams& p, hipStream_t st) {
                 (!p.bias || reinterpret_cast<uintptr_t>(p.bias) % 16 == 0) &&
                 (!p.yprev || ((p.yp_sv % 4 == 0) && (p.yp_sb % 4 == 0) && reinterpret_cast<uintptr_t>(p.yprev) % 16 == 0));
     // <= 3 output channels over 16-channel rows: the line-wise VALU kernel (both arithmetic forms: nothing for a split to win)
-    static const int out3_on = sh_env_int("SH_GG_OUT3", 1, 0, 1);
-    if (!BWD_EPI && out3_on && p.Nout <= 3 && p.Cg == 16 && vec4 && p.S >= 6 && p.S <= 24) {
+    if (!BWD_EPI && p.Nout <= 3 && p.Cg == 16 && vec4 && p.S >= 6 && p.S <= 24) {
         p.Kw = p.K;
         auto run = [&](int n) -> int {
             switch (n) {
@@ -990,50 +978,40 @@ int dispatch_gg(GGParams& p, hipStream_t st) {
         p.s0 = s1; p.pass = 2;
         return run(p.S - s1);
     }
-    // bf16x3 form (mma_mode SH_MMA_SPLIT3): up to four channel tiles per workgroup, the rest split over workgroups
-    static const int s3_min_nt = sh_env_int("SH_S3_MIN_NT", 4, 1, 8);      // layers with fewer channel tiles keep the exact form (no gain there)
-    if (sh_f32_mma_mode() != SH_MMA_EXACT && vec4 && p.vec_out && !c3 && p.Cg % 8 == 0 && nt >= s3_min_nt) {
-        static const int s3_nt = sh_env_int("SH_S3_NT", 4, 1, 8), s3_rt = sh_env_int("SH_S3_RT", 0, 0, 2);
-        static const int s3_rt2_at = sh_env_int("SH_S3_RT2_AT", 2048, 1, 1 << 30);
-        int ntw = nt;
-        p.nsplit = nsplit0;
-        while (ntw > s3_nt) { ntw >>= 1; p.nsplit <<= 1; }
-        const long wg64 = (long)sh_cdiv(p.R, 64 >> (p.log2TB < 6 ? p.log2TB : 6)) * p.n_btiles * p.nsplit;      // workgroups of 64 rows
+    // bf16x3 form (mma_mode SH_MMA_SPLIT3): four channel tiles per workgroup, the rest split over workgroups; layers with fewer
+    // than four channel tiles keep the exact form (no gain there)
+    if (sh_f32_mma_mode() != SH_MMA_EXACT && vec4 && p.vec_out && !c3 && p.Cg % 8 == 0 && nt >= 4) {
+        p.nsplit = nt == 8 ? 2 * nsplit0 : nsplit0;
+        const long wg64 = (long)sh_cdiv(p.R, 64 >> p.log2TB) * p.n_btiles * p.nsplit;      // workgroups of 64 rows
         // two row tiles per wave halve the weight-split work per MFMA: pays from ~1000 reduction columns on (67.7 -> 64.7, 64.2 -> 60.5 us)
-        const int rt = s3_rt ? s3_rt : ((wg64 >= s3_rt2_at || (p.K >= 1024 && wg64 >= 512)) ? 2 : 1);
-        switch (ntw) {
-            case 1: return launch_s3<1, BWD_EPI>(p, rt, st);
-            case 2: return launch_s3<2, BWD_EPI>(p, rt, st);
-            case 4: return launch_s3<4, BWD_EPI>(p, rt, st);
-            default: return launch_s3<8, BWD_EPI>(p, rt, st);
-        }
+        const int rt = (wg64 >= 2048 || (p.K >= 1024 && wg64 >= 512)) ? 2 : 1;
+        return launch_s3<4, BWD_EPI>(p, rt, st);
     }
     // too few row tiles to fill 256 CUs x ~3 workgroups: split the output channels over workgroups
-    static const int fill_target = sh_env_int("SH_GG_FILL", 768, 1, 1 << 20);
-    static const int direct_on = sh_env_int("SH_GG_DIRECT", 1, 0, 1);
+    constexpr int GG_FILL = 768;
     p.nsplit = nsplit0;
-    while (nt > 2 && nblocks * p.nsplit < fill_target) { nt >>= 1; p.nsplit <<= 1; }
+    while (nt > 2 && nblocks * p.nsplit < GG_FILL) { nt >>= 1; p.nsplit <<= 1; }
     // two channel tiles run in the direct form with 64-row workgroups (twice the count): only split them further if even
     // that does not fill the chip - one tile per workgroup is the slower staged form
-    if (nt == 2 && nblocks * p.nsplit * ((vec4 && direct_on) ? 2 : 1) < fill_target) { nt = 1; p.nsplit <<= 1; }
+    if (nt == 2 && nblocks * p.nsplit * (vec4 ? 2 : 1) < GG_FILL) { nt = 1; p.nsplit <<= 1; }
     // eight channel tiles only exist staged; two workgroups of four tiles in the direct form are faster although each
     // gathers the rows again (27 554-vertex template, 128 channels: 88 -> ~105 TFLOP/s)
-    if (nt == 8 && vec4 && direct_on) { nt = 4; p.nsplit <<= 1; }
+    if (nt == 8 && vec4) { nt = 4; p.nsplit <<= 1; }
     const long nitems = nblocks * p.nsplit;
-#define SH_GG_CASE(NTV)                                                                  \
-    return vec4 ? launch_gg<NTV, true, BWD_EPI>(p, (int)nitems, st)              \
-                : launch_gg<NTV, false, BWD_EPI>(p, (int)nitems, st)
     if (c3) return launch_gg<1, true, BWD_EPI, true>(p, (int)nitems, st);
-    // the direct form serves 2 and 4 channel tiles; one tile (16 channels) measured 25-30 % slower in it than staged
-    if (nt == 4 && vec4 && direct_on) return launch_ggd<4, BWD_EPI>(p, (int)nitems, st);
-    if (nt <= 1) { SH_GG_CASE(1); }
-    // the direct form wins for two channel tiles (2-8 us per launch on MI355X) and loses for 1 and 4: a chunk of a
-    // one-tile layer has too few MFMAs between the weight-chunk barriers, four tiles are bound elsewhere
-    if (nt <= 2 && vec4 && direct_on) return launch_ggd<2, BWD_EPI>(p, (int)nitems, st);
-    if (nt <= 2) { SH_GG_CASE(2); }
-    if (nt <= 4) { SH_GG_CASE(4); }
-    SH_GG_CASE(8);
-#undef SH_GG_CASE
+    // 16-byte aligned quads: the direct form serves 2 and 4 channel tiles (two tiles: 2-8 us per launch faster on MI355X); one
+    // tile (16 channels) measured 25-30 % slower in it than staged - a chunk of a one-tile layer has too few MFMAs between the
+    // weight-chunk barriers
+    if (vec4) {
+        if (nt == 4) return launch_ggd<4, BWD_EPI>(p, (int)nitems, st);
+        if (nt == 2) return launch_ggd<2, BWD_EPI>(p, (int)nitems, st);
+        return launch_gg<1, true, BWD_EPI>(p, (int)nitems, st);
+    }
+    // anything else: the staged form with scalar loads
+    if (nt <= 1) return launch_gg<1, false, BWD_EPI>(p, (int)nitems, st);
+    if (nt <= 2) return launch_gg<2, false, BWD_EPI>(p, (int)nitems, st);
+    if (nt <= 4) return launch_gg<4, false, BWD_EPI>(p, (int)nitems, st);
+    return launch_gg<8, false, BWD_EPI>(p, (int)nitems, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1688,10 +1666,11 @@ WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
     WGPlan w;
     w.xg_G = w.xg_cpg = w.xg_Vg = 0;
     const int K = S * Cin;
-    static const int tb_pref = sh_env_int("SH_WG_TB", 8, 1, TMW);
-    static const int blocks_target = sh_env_int("SH_WG_BLOCKS", 1024, 64, 65536);
+    constexpr int WG_TB = 8;              // batch slice of the staged form
+    constexpr int WG_BLOCKS = 1024;       // workgroups it aims for
+    constexpr int WS_SLAB_MB = 32;        // MiB of partial slabs the streaming form may write
     int tb = 1;
-    while (tb < B && tb < tb_pref) tb <<= 1;
+    while (tb < B && tb < WG_TB) tb <<= 1;
     w.log2TB = sh_ilog2_floor(tb);
     const int tv = TMW >> w.log2TB;
     w.n_btiles = sh_cdiv(B, tb);
@@ -1704,13 +1683,12 @@ WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
     {
         const int cp = w.cot * 16;
         const long cost1 = (long)sh_cdiv(K, 64) * (64 + cp), cost2 = (long)sh_cdiv(K, 128) * (128 + cp);
-        static const int force = sh_env_int("SH_WG_CTW", 0, 0, 2);
-        w.ctw = force ? force : ((w.cot == 8 || cost1 <= cost2) ? 1 : 2);
+        w.ctw = (w.cot == 8 || cost1 <= cost2) ? 1 : 2;
     }
     w.ncg = sh_cdiv(K, 64 * w.ctw);
     // vertex chunks per batch slice: enough blocks to fill the chip, few enough that the partial
     // slabs stay small, and a table slice that fits its LDS area
-    int nvc = blocks_target / (w.ncg * w.n_btiles);
+    int nvc = WG_BLOCKS / (w.ncg * w.n_btiles);
     if (nvc < 1) nvc = 1;
     if (nvc > w.n_vtiles) nvc = w.n_vtiles;
     const int max_steps = WG_TABLE_CAP / (tv * S) > 0 ? WG_TABLE_CAP / (tv * S) : 1;
@@ -1719,26 +1697,22 @@ WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
     w.nvc = sh_cdiv(w.n_vtiles, w.steps_per_block);
     w.nrc = w.nvc * w.n_btiles;
     // streaming form (wgrad_stream_kernel): work item = (64-column group, batch slice, vertex chunk), one per wave
-    static const int stream_on = sh_env_int("SH_WG_STREAM", 1, 0, 1);
-    w.stream = (stream_on && (Cin % 4 == 0 || Cin == 3)) ? 1 : 0;
+    w.stream = (Cin % 4 == 0 || Cin == 3) ? 1 : 0;
     w.vpc = 0;
     if (w.stream) {
-        static const int items_env = sh_env_int("SH_WS_ITEMS", 1024, 64, 1 << 20);
-        // the 16 -> 3 layer's slabs are written by the role-swapped kernel (wgrad_thin.hip: one workgroup of four waves per slab, each
+        // items: one wave per SIMD.  The 16 -> 3 layer's slabs are written by the role-swapped kernel (wgrad_thin.hip: one workgroup of four waves per slab, each
         // wave paced by the latency of its own load ring): 512 slabs = two waves per SIMD instead of 340 = 1.33 (45 -> 36 us at 6890
         // vertices, batch 64; the slabs are 1.9 KB each)
-        const int items_target = (Cin == 16 && Cout <= 3 && items_env < 1536) ? 1536 : items_env;
-        static const int slab_mb = sh_env_int("SH_WS_SLAB_MB", 32, 1, 4096);
+        const int items_target = (Cin == 16 && Cout <= 3) ? 1536 : 1024;
         // batch slice: 1 or 4 groups of 4 rows; 8 groups for ONE channel tile (a vertex is then 32 MFMAs instead of 16 behind the
         // same table read and address arithmetic: 69.5 -> 62 us on the level-0 32 -> 16 layer; with two tiles the registers of the
-        // deeper prefetch cost more than that: 72 -> 78 us.  SH_WS_TBS=16 keeps the narrow slice everywhere)
-        static const int tbs_env = sh_env_int("SH_WS_TBS", 32, 16, 32);
-        const int tbs = B <= 4 ? 4 : (tbs_env == 32 && B % 32 == 0 && Cout <= 16 && Cin != 3) ? 32 : 16;
+        // deeper prefetch cost more than that: 72 -> 78 us)
+        const int tbs = B <= 4 ? 4 : (B % 32 == 0 && Cout <= 16 && Cin != 3) ? 32 : 16;
         w.log2TB = sh_ilog2_floor(tbs);
         w.n_btiles = sh_cdiv(B, tbs);
         w.ncg = sh_cdiv(Cin == 3 ? 4 * S : K, 64);            // 3-channel inputs: columns counted in padded quads
         long nrc_t = items_target / w.ncg;
-        const long cap = ((long)slab_mb << 20) / ((long)Cout * K * 4);     // partial slabs are written and re-read once
+        const long cap = ((long)WS_SLAB_MB << 20) / ((long)Cout * K * 4);     // partial slabs are written and re-read once
         if (nrc_t > cap) nrc_t = cap;
         if (nrc_t < 1) nrc_t = 1;
         long nvc_t = nrc_t / w.n_btiles;
@@ -1756,7 +1730,7 @@ WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
             if (items > items_target) {
                 const long rounds = (items + items_target - 1) / items_target;
                 long nvc_goal = rounds * items_target / per_chunk;
-                const long cap2 = 2 * (((long)slab_mb << 20) / ((long)Cout * K * 4)) / w.n_btiles;
+                const long cap2 = 2 * cap / w.n_btiles;
                 if (nvc_goal > cap2) nvc_goal = cap2;
                 if (nvc_goal > sh_cdiv(R, vpc)) vpc = sh_cdiv(R, (int)nvc_goal);
             }
@@ -1765,9 +1739,7 @@ WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
         w.nvc = sh_cdiv(R, vpc);
         w.nrc = w.nvc * w.n_btiles;
         // one vertex range per XCD (WSParams::xg_*): 1 / 2 / 4 / 8 batch slices, not the layer the role-swapped kernel serves
-        static const int xg_on = sh_env_int("SH_WS_XCD_RANGES", 1, 0, 1);
-        w.xg_G = w.xg_cpg = w.xg_Vg = 0;
-        if (xg_on && (w.n_btiles == 1 || w.n_btiles == 2 || w.n_btiles == 4 || w.n_btiles == 8) && Cout > 3) {
+        if ((w.n_btiles == 1 || w.n_btiles == 2 || w.n_btiles == 4 || w.n_btiles == 8) && Cout > 3) {
             const int G = 8 / w.n_btiles;
             const int Vg = sh_cdiv(R, G);
             // chunks per XCD: whole "rounds" of the item target (one wave per SIMD = items_target / 8 items per XCD), as many rounds
@@ -1802,8 +1774,7 @@ int launch_ws(const WSParams& p, hipStream_t st) {
                    c3 ? "true" : "false", p.R, p.B, p.K, p.Cout, p.grid_main, p.tail_blocks ? p.tail_rows : 0);
     // interleaved channel tiles (one gradient load per batch group instead of COT): all 16 COT channels of the launch exist and
     // a lane's COT values are COT-float aligned
-    static const int ilv_on = sh_env_int("SH_WS_ILV", 1, 0, 1);
-    const bool ilv = ilv_on && COT >= 2 && !c3 && p.Cout - p.co0 >= 16 * COT && p.dp_sb % COT == 0 && p.dp_sv % COT == 0 &&
+    const bool ilv = COT >= 2 && !c3 && p.Cout - p.co0 >= 16 * COT && p.dp_sb % COT == 0 && p.dp_sv % COT == 0 &&
                      (reinterpret_cast<uintptr_t>(p.dpre) & 15) == 0;
     if constexpr (COT >= 2) {
         if (ilv) {
@@ -1968,14 +1939,10 @@ int launch_ws3(const WSParams& p, hipStream_t st) {
 // 2 and 4 channel tiles (8 would need more than the 512 registers of a one-wave-per-SIMD kernel; one tile: the splits outweigh
 // the matrix time saved)
 bool ws_uses_split3(int cot, const WSParams& p) {
-    static const int s3_min_cot = sh_env_int("SH_S3_WG_MIN_COT", 2, 1, 16);
     const bool full = (p.B & ((1 << p.log2TB) - 1)) == 0;
     // (the three-plane form keeps the exact weight-gradient kernels: they host the pre-sum riders up to four channel tiles, the
     // split ones only with two - measured 30 us per step in their favour once the riders also write plane images)
-    static const int p3_wg_split = sh_env_int("SH_P3_WG_SPLIT3", 0, 0, 1);
-    const int mode = sh_f32_mma_mode();
-    const bool split = mode == SH_MMA_SPLIT3 || (mode == SH_MMA_PLANES3 && p3_wg_split);
-    return (cot == 2 || cot == 4) && split && cot >= s3_min_cot && full && p.log2TB == 4 && p.Cin % 4 == 0;
+    return (cot == 2 || cot == 4) && sh_f32_mma_mode() == SH_MMA_SPLIT3 && full && p.log2TB == 4 && p.Cin % 4 == 0;
 }
 
 template <int COT>
@@ -2226,8 +2193,7 @@ int sh_spiral_conv_bwd_wgt_presum(const float* dpre, int64_t dp_sv, int64_t dp_s
         s.log2TB = w.log2TB; s.n_btiles = w.n_btiles; s.nvc = w.nvc; s.vpc = w.vpc; s.ncg = w.ncg;
         s.n_items = w.nrc * w.ncg;
         s.grid_main = sh_cdiv(s.n_items, 4);
-        static const int vstride = sh_env_int("SH_WS_VSTRIDE", 1, 0, 1);
-        s.vstride = vstride;
+        s.vstride = 1;
         if (w.xg_G > 0) {
             s.vstride = 2; s.xg_G = w.xg_G; s.xg_cpg = w.xg_cpg; s.xg_Vg = w.xg_Vg;
             s.grid_main = 8 * sh_cdiv(w.xg_cpg * w.ncg, 4);
@@ -2235,10 +2201,10 @@ int sh_spiral_conv_bwd_wgt_presum(const float* dpre, int64_t dp_sv, int64_t dp_s
         // The pre-sum job rides as tail workgroups of this launch when a second wave of the kernel fits beside the first on
         // a SIMD (exact form: up to four channel tiles; bf16x3 form: two) and the rows take 16-byte accesses; otherwise it is
         // the launch of its own it used to be.  Measured: the seven foldable launches of a step were 58 us + their gaps.
-        static const int tail_on = sh_env_int("SH_WS_TAIL", 1, 0, 1), tail_cap = sh_env_int("SH_WS_TAIL_BLOCKS", 768, 1, 1 << 16);
+        constexpr int WS_TAIL_BLOCKS = 768;      // at most this many tail workgroups
         const bool sum_vec = (Cout % 4 == 0) && (dp_sv % 4 == 0) && (dp_sb % 4 == 0) &&
                              ((reinterpret_cast<uintptr_t>(dpre) | reinterpret_cast<uintptr_t>(sum_out)) % 16 == 0);
-        bool fold = tail_on && sum_rows > 0 && sum_vec && Cout <= 128 && !(Cin == 3) &&
+        const bool fold = sum_rows > 0 && sum_vec && Cout <= 128 && !(Cin == 3) &&
                     (ws_uses_split3(w.cot, s) ? w.cot == 2 : w.cot <= 4);
         if (sum_rows > 0 && !fold) {
             rc = sh_spmm_p3(sum_rowptr, sum_col, sum_val, dpre, dp_sv, dp_sb, sum_out, dp_sv, dp_sb, sum_out_planes, nullptr, 0, 0, 0, -1, B,
@@ -2247,7 +2213,7 @@ int sh_spiral_conv_bwd_wgt_presum(const float* dpre, int64_t dp_sv, int64_t dp_s
         }
         if (fold) {
             const long items = (long)sum_rows * (((long)B * (Cout / 4) + 255) / 256);
-            s.tail_blocks = (int)(items < tail_cap ? items : tail_cap);
+            s.tail_blocks = (int)(items < WS_TAIL_BLOCKS ? items : WS_TAIL_BLOCKS);
             s.tail_rows = sum_rows; s.tail_rowptr = sum_rowptr; s.tail_col = sum_col; s.tail_val = sum_val; s.tail_y = sum_out;
             if (sum_out_planes) {
                 SH_REQUIRE(dp_sb == Cout && dp_sv == (int64_t)B * Cout && sh_p3_bytes(1, B, Cout) && (reinterpret_cast<uintptr_t>(sum_out_planes) & 15) == 0,
@@ -2312,9 +2278,8 @@ static int reduce_multi_impl(int n_layers, const void* const* workspaces, float*
         m.slab[nd] = slab; m.stride[nd] = stride; m.nslab[nd] = nrc; m.n[nd] = stride; m.out[nd] = dW[i]; m.block0[nd] = blocks;
         // measured (tools/exp/r05_quick.sh): four outputs per thread win where a workgroup has many slabs to walk (27 554 vertices, 720-760
         // slabs: 33.0 / 22.2 -> 24.5 / 16.5 us) and in the bf16 plan (10.1 / 10.3 -> 9.2 / 9.8), and lose on the headline's 256 slabs (13.4 /
-        // 16.8 -> 14.6 / 18.6: a quarter of the workgroups, each as long): 1 = that rule, 0 = never, 2 = always
-        static const int vec_on = sh_env_int("SH_SLAB_REDUCE_VEC", 1, 0, 2);
-        if ((vec_on == 2 || (vec_on == 1 && (nrc >= 512 || bf16_plan))) && stride % 4 == 0 && ((reinterpret_cast<uintptr_t>(slab) | reinterpret_cast<uintptr_t>(dW[i])) & 15) == 0) {
+        // 16.8 -> 14.6 / 18.6: a quarter of the workgroups, each as long)
+        if ((nrc >= 512 || bf16_plan) && stride % 4 == 0 && ((reinterpret_cast<uintptr_t>(slab) | reinterpret_cast<uintptr_t>(dW[i])) & 15) == 0) {
             m.vec_mask |= 1u << nd;
             blocks += (int)((stride / 4 + 63) / 64);
         } else

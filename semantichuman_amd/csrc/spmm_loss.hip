@@ -394,7 +394,7 @@ int sh_spmm_p3(const int32_t* rowptr, const int32_t* col, const float* val, cons
     const bool vec = (C % 4 == 0) && (x_sv % 4 == 0) && (x_sb % 4 == 0) && (y_sv % 4 == 0) && (y_sb % 4 == 0) &&
                      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16 == 0) &&
                      (!yprev || (yp_sv % 4 == 0 && yp_sb % 4 == 0 && reinterpret_cast<uintptr_t>(yprev) % 16 == 0));
-    static const int grid_cap = sh_env_int("SH_SPMM_GRID", 4096, 64, 1 << 20);
+    constexpr int grid_cap = 4096;          // grid-stride launch: at most this many workgroups
     const long items = (long)rows * (((long)B * (vec ? C / 4 : C) + 255) / 256);
     const int grid = (int)(items < grid_cap ? items : grid_cap);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -404,9 +404,8 @@ int sh_spmm_p3(const int32_t* rowptr, const int32_t* col, const float* val, cons
         const long bgb = C == 16 ? 1536 : (long)(C / 32) * 3072;
         ShProfScope ps(st, "spmm_kernel<true, p3>|rows=%d B=%d C=%d f32=%d", rows, B, C, y ? 1 : 0);
         // measured (profiles/r05_spmm_x8.txt): the eight-channel form wins on wide rows (C = 128: 396 -> 286 us at batch 1024, 19.1 -> 18.1
-        // at 64; C = 64 at batch 1024: 156 -> 138) and loses 1-7 % on the 32-channel levels: 0 = never, 1 = that rule, 2 = always
-        static const int x8_mode = sh_env_int("SH_SPMM_P3X8", 1, 0, 2);
-        const bool x8 = x8_mode == 2 || (x8_mode == 1 && (C >= 128 || (C == 64 && B >= 256)));
+        // at 64; C = 64 at batch 1024: 156 -> 138) and loses 1-7 % on the 32-channel levels
+        const bool x8 = C >= 128 || (C == 64 && B >= 256);
         if (x8) {
             const long items8 = (long)rows * (((long)B * (C / 8) + 255) / 256);
             const int grid8 = (int)(items8 < grid_cap ? items8 : grid_cap);

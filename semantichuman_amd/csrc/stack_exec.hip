@@ -110,15 +110,13 @@ int reduce_bf16(int n, const void* const* ws, float* const* dW, float* const* db
 // image exactly where the forward pass wrote one and leaves unread exactly the fp32 rows the forward pass left unwritten.  Buffers
 // follow the plan (a per-step pointer the plan needs and the caller left NULL is an error); two things stay outside it: a frozen
 // layer (dW[p] == NULL drops what lives in the weight-gradient launch) and the size of the caller's workspace.
-// the switches, read once: SH_P3_N16_MAXB (the rule in plan_f32); SH_P3_BWD, SH_P3_WGRAD, SH_P3_YPREV_IMG, SH_P3_DROP_FP32, SH_P3_RAGGED,
-// SH_P3_GROUPED = 0: that plane form off (with SH_P3_WGRAD=0 the backward pass reads no forward image); SH_P3_PRESUM_IMG: 0 / 1 force,
-// 2 = the rule in plan_f32; SH_TR_RIDE=0: the weight transposes get a launch of their own
-struct Switches { int n16_maxb, bwd, wgrad, yprev_img, drop_fp32, ragged, grouped, presum_img, tr_ride; };
+// the switches, read once ("Switches": each has a reader outside the library): SH_P3_N16_MAXB (the rule in plan_f32);
+// SH_P3_WGRAD, SH_P3_DROP_FP32, SH_P3_RAGGED, SH_P3_GROUPED = 0: that plane form off (with SH_P3_WGRAD=0 the backward pass reads no
+// forward image)
+struct Switches { int n16_maxb, wgrad, drop_fp32, ragged, grouped; };
 const Switches& switches() {
-    static const Switches s{sh_env_int("SH_P3_N16_MAXB", 256, 0, 1 << 30), sh_env_int("SH_P3_BWD", 1, 0, 1), sh_env_int("SH_P3_WGRAD", 1, 0, 1),
-                            sh_env_int("SH_P3_YPREV_IMG", 1, 0, 1),        sh_env_int("SH_P3_DROP_FP32", 1, 0, 1),
-                            sh_env_int("SH_P3_RAGGED", 1, 0, 1),           sh_env_int("SH_P3_GROUPED", 1, 0, 1),
-                            sh_env_int("SH_P3_PRESUM_IMG", 2, 0, 2),       sh_env_int("SH_TR_RIDE", 1, 0, 1)};
+    static const Switches s{sh_env_int("SH_P3_N16_MAXB", 256, 0, 1 << 30), sh_env_int("SH_P3_WGRAD", 1, 0, 1), sh_env_int("SH_P3_DROP_FP32", 1, 0, 1),
+                            sh_env_int("SH_P3_RAGGED", 1, 0, 1), sh_env_int("SH_P3_GROUPED", 1, 0, 1)};
     return s;
 }
 
@@ -172,7 +170,7 @@ void plan_f32(int n, const sh_stack_step* st, int B, int x_layout, bool planes3,
         Forms& q = f[i];
         if (s.kind != 0 || !(i > 0 || need_x_grad) || !s.table_t) continue;
         // backward-data on the image of the pre-activation gradient where the kernels take the transposed shape
-        q.b_gimg = planes3 && sw.bwd && sh_spiral_conv_p3_ok(B, s.S, s.cout, s.cin);
+        q.b_gimg = planes3 && sh_spiral_conv_p3_ok(B, s.S, s.cout, s.cin);
         // a 16 -> 3 channel layer takes its weight gradient in role-swapped form (wgrad_thin.hip), on a plain vertex-major input
         q.b_thin = s.R == s.n_in && (i > 0 || x_layout == 0) && sh_spiral_conv_bwd_wgt_thin_ok(B, s.n_in, s.S, s.cin, s.cout, SH_DTYPE_F32);
         if (q.b_gimg) {
@@ -186,8 +184,7 @@ void plan_f32(int n, const sh_stack_step* st, int B, int x_layout, bool planes3,
             // pre-summed rows: imaged by their producers (the riders / pre-sum launches), or - LDS-resident plane kernel and at least
             // half as many of them as real rows - left fp32 and split by the backward-data kernel itself (they are ~6 % of what it
             // gathers; the riders' image stores cost their hosts more)
-            q.b_presum_img = sw.presum_img == 1 ||
-                             !(sh_spiral_conv_p3_kind(B, s.S, s.cout, s.cin) == 1 && (sw.presum_img == 0 || 2 * (s.n1 + s.n2) >= s.R));
+            q.b_presum_img = !(sh_spiral_conv_p3_kind(B, s.S, s.cout, s.cin) == 1 && 2 * (s.n1 + s.n2) >= s.R);
         }
         const bool p3 = q.b_data != BD_F32 && !q.b_thin;
         q.b_ride = !q.b_thin && q.b_data < BD_RAG && (s.n1 || s.n2);
@@ -195,8 +192,8 @@ void plan_f32(int n, const sh_stack_step* st, int B, int x_layout, bool planes3,
         // takes the shape
         q.b_p3w = p3 && sw.wgrad && i > 0 && f[i - 1].f_img && sh_spiral_conv_bwd_wgt_p3_ok(B, s.R, s.S, s.cin, s.cout) &&
                   (((long)s.R * (B / 16)) % 2 == 0 || s.zero_row >= 0);
-        q.b_yimg = q.b_data != BD_F32 && sw.wgrad && sw.yprev_img && i > 0 && st[i - 1].kind == 0 && f[i - 1].f_img;
-        q.b_in_img_only = keep_fp32 == 2 && sw.drop_fp32 && sw.yprev_img && q.b_p3w;
+        q.b_yimg = q.b_data != BD_F32 && sw.wgrad && i > 0 && st[i - 1].kind == 0 && f[i - 1].f_img;
+        q.b_in_img_only = keep_fp32 == 2 && sw.drop_fp32 && q.b_p3w;
         // ... and its gradient rows, when besides no pre-sum launch or rider reads them: list forms, or a table without multiplicities
         q.b_grad_img_only = q.b_in_img_only && (q.b_data >= BD_RAG || (s.n1 == 0 && s.n2 == 0));
     }
@@ -307,7 +304,6 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
         SH_REQUIRE(!in_planes || !(f[i].b_p3w || f[i].b_yimg) || in_planes[i], SH_ERR_INVALID_ARG,
                    "sh_stack_backward: step %d reads the image of its input: in_planes[%d] is NULL", i, i);
     }
-    const Switches& sw = switches();
     int cin_of[64];
     fill_cin_of(n_steps, steps, c0, cin_of);
     // all weight transposes of the stack (backward-data on planes reads fragments instead): workgroups of the launch that opens the
@@ -321,7 +317,7 @@ int sh_stack_backward(int n_steps, const sh_stack_step* steps, const float* x, i
         tr_w[n_tr] = weights[steps[i].param]; tr_wt[n_tr] = weight_t[i]; tr_S[n_tr] = steps[i].S; tr_Ci[n_tr] = steps[i].cin; tr_Co[n_tr] = steps[i].cout;
         ++n_tr;
     }
-    if (n_tr && !(sw.tr_ride && steps[last].kind == 0)) {
+    if (n_tr && steps[last].kind != 0) {
         rc = sh_weight_transpose_multi(n_tr, tr_w, tr_wt, tr_S, tr_Ci, tr_Co, stream);
         if (rc != SH_OK) return rc;
         n_tr = 0;

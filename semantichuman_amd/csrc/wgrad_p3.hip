@@ -457,15 +457,13 @@ WP3Plan plan_wp3(int B, int R, int S, int Cin, int Cout) {
     // and with only a handful of stages per wave the rounding of that count decides (1724 rows x 16 groups: 3.4 stages of 17
     // groups per wave = 4 x 17, or split in two column groups 6.7 stages of 9 = 7 x 9).  Minimise it; ties: the wider group
     // (dpre is re-read once per column group).
-    static const int wg_target = sh_env_int("SH_WP3_BLOCKS", 256, 8, 1 << 16);
-    static const int slab_mb = sh_env_int("SH_WP3_SLAB_MB", 32, 1, 4096);
-    static const int q_force = sh_env_int("SH_WP3_QF", 0, 0, 16);
+    constexpr int wg_target = 256;          // one workgroup per CU
+    constexpr int slab_mb = 32;             // MiB of partial slabs a launch may write
     const long cap = (((long)slab_mb << 20) / ((long)Cout * S * Cin * 4)) / 8;
     const long per_xcd = (w.n_stages + 7) / 8;
     const int ngd = w.pt / 2;
     long best = -1, sgx = 1;
     auto consider = [&](int q) {
-        if (q_force && q != q_force) return;
         const int n_qg = sh_cdiv(w.nxg, q);
         if (q > w.nxg && q != (w.pt == 2 ? WP_QF2[0] : WP_QF4[0])) return;       // wider than the layer: only the narrowest form
         const long tiles = (long)n_qg * w.n_pt;

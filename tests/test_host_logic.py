@@ -465,3 +465,22 @@ def test_grouped_lists_cover_every_source_exactly_once():
     t = mesh_ops.spirals_to_table(h.spirals[2])
     rag = mesh_ops.transpose_table_ragged(t, t.shape[0], none_row=t.shape[0] - 1, skip_row=t.shape[0] - 1)
     check(rag[0], rag[1], 2)
+
+
+def test_library_switches_match_the_design_table():
+    """Every SH_* name the kernel library reads through sh_env_int has a row in DESIGN.md's "Switches" table (name, default, who
+    reads it), and the table names nothing the library no longer reads."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    read = set()
+    csrc = os.path.join(root, "semantichuman_amd", "csrc")
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        with open(path) as f:
+            read |= set(re.findall(r'sh_env_int\(\s*"(SH_[A-Z0-9_]+)"', f.read()))
+    with open(os.path.join(root, "DESIGN.md")) as f:
+        design = f.read()
+    section = re.search(r"^## \d+\. Switches\n(.*?)(?=^## |\Z)", design, re.M | re.S)
+    assert section, "DESIGN.md has no 'Switches' section"
+    table = set(re.findall(r"^\| `(SH_[A-Z0-9_]+)` \|", section.group(1), re.M))
+    assert read and read == table, (sorted(read - table), sorted(table - read))

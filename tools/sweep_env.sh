@@ -1,7 +1,7 @@
 #!/bin/bash
-# A/B tuning knobs of libsh_kernels.so on the GPU box: runs bench.py once per setting and prints
-# one compact line each (ms/step + the per-kernel milliseconds measured by the library's HIP events).
-# usage: tools/sweep_env.sh "SH_GG_TB=64 SH_WG_TB=32" "SH_GG_TB=16 SH_WG_TB=8" ...
+# A/B the switches libsh_kernels.so still reads ("Switches") on the GPU box: runs bench.py once per setting and
+# prints one compact line each (ms/step + the per-kernel milliseconds measured by the library's HIP events).
+# usage: tools/sweep_env.sh "SH_P3_NP=6" "SH_P3_NP=9" "SH_P3_RAGGED=0 SH_P3_GROUPED=0" ...
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for setting in "$@"; do
