@@ -814,6 +814,38 @@ SH_API int sh_vertex_visibility(const float* x, int64_t x_sb, int n, const int32
                                 size_t workspace_bytes, uint8_t* vis, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Vertex visibility from a rig: which model vertices AT LEAST ONE of V sensors sees - the vertex mask of a scan fused from a rig
+ * of depth cameras.  Everything of "Vertex visibility" holds: fp32, no atomics, plain stores, bits independent of batch, launch
+ * shape and split.
+ *
+ * sh_vertex_visibility_views.  The arguments of sh_vertex_visibility, with view: fp32 [B][V][3] contiguous, 1 <= V <=
+ * SH_VISIBILITY_MAX_VIEWS, and a second output seen: uint32 [B][n] contiguous, or NULL.
+ * Bit v of seen[b][i] is set iff vertex i is active and, for view v ALONE, faces the sensor (if tn is given) and is not occluded:
+ * the predicate of "Vertex visibility" with d = view[b][v] - o, the same dot / cross forms, the same Moeller-Trumbore
+ * expression, incident faces skipped by index - so bit v equals, bit for bit, what sh_vertex_visibility returns when given view v
+ * alone.  A view row that holds a NaN is an absent camera: its bit is never set.  vis[b][i] = (seen[b][i] != 0), except for a
+ * body ALL of whose view rows hold a NaN: it is a full scan, seen is 0 and every active vertex is visible (the single-view rule;
+ * V == 1 reproduces sh_vertex_visibility).
+ *
+ * How it is computed.  ONE sweep over the faces in the form of the single-view kernel (256 threads, one vertex per thread, the
+ * same double-buffered 256-face LDS tiles of 48 bytes).  Per face and vertex s = o - a, q = cross(s, e1) and t = dot(e2, q) do
+ * not depend on the view and are formed once; p, det, u and w are formed per view.  A lane carries the 32-bit mask of the views
+ * it is still unoccluded from - live and facing, minus hits - and walks its set bits only; the viewpoints sit in LDS (16 bytes
+ * per view) and d is formed again from them.  The wave's ballot ("any view open") every four faces and the workgroup's exit per
+ * tile work as in the single-view kernel.  `chunks` splits the face range as there; each chunk then stores the views its faces
+ * hide into workspace uint32 [chunks][B][n] and a second launch ORs them and takes them off "live and facing", formed again -
+ * every split gives the same bits.  sh_vertex_visibility_views_workspace(B, n, nF, V, chunks) bytes are needed for a split into
+ * more than one chunk.
+ * B == 0 or n == 0: SH_OK, nothing launched.  What sh_vertex_visibility refuses, and V outside [1, SH_VISIBILITY_MAX_VIEWS]:
+ * SH_ERR_INVALID_ARG before the device is touched.
+ */
+#define SH_VISIBILITY_MAX_VIEWS 32
+SH_API size_t sh_vertex_visibility_views_workspace(int B, int n, int nF, int V, int chunks);
+SH_API int sh_vertex_visibility_views(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view,
+                                      int V, float cos_g, const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace,
+                                      size_t workspace_bytes, uint8_t* vis, uint32_t* seen, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Scan alignment: the similarity that carries a scan into the model's frame, from the matches the search above has recorded
  * (no reference counterpart).  A pose maps scan frame -> model frame, s' = A s + t with A = c R, R a proper rotation, c > 0.
  * Stored fp32: pose contiguous [B][12] (A row-major, then t) and scale [B] (= c).  No atomics; every sum in a fixed order.
@@ -1082,6 +1114,48 @@ SH_API int sh_depth_points(const void* depth, int dtype, float depth_scale, cons
                            float z_near, float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts,
                            int max_count, int M, const void* workspace, size_t workspace_bytes, float* points, float* normals,
                            int32_t* pixel, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Depth views: the V calibrated depth cameras of a rig as ONE scan per body, in the rig's frame (no reference counterpart).
+ * Deterministic as "Depth images": no atomics, every output element one plain store, bits independent of B, of the padding and
+ * of the other bodies.
+ *
+ * Inputs.  depth [B][V][H][W], intr fp32 [B][V][4], mask uint8 [B][V][H][W] or NULL: per image as in "Depth images", with its
+ * dtype / depth_scale / z_near / z_far / max_step / drop_isolated / stride.  ext: fp32 [B][V][12], camera frame -> rig frame in
+ * the layout of sh_transform_points - R row-major (r_00 .. r_22), then t - and rigid (R a proper rotation, no scale; the caller's
+ * duty).  1 <= V <= SH_DEPTH_MAX_VIEWS.  A view whose ext row holds a NaN is ABSENT: it emits no row, its counts are 0, and
+ * nothing else of it - depth, mask, intrinsics - is read.
+ * Per pixel, everything up to the camera-frame point P = (X, Y, Z) and the fp64 unit normal n (after its flip towards the
+ * camera, BEFORE its rounding) is "Depth images", unchanged.  Then, with no contraction:
+ *     P'_i = fl(fl(fl(fl(r_i0 * X) + fl(r_i1 * Y)) + fl(r_i2 * Z)) + t_i)        fp32, i = 0..2
+ *     n'_i = (r_i0 * n_x + r_i1 * n_y) + r_i2 * n_z                              fp64: R widened; each component rounded to fp32
+ *                                                                                once (this replaces the rounding of n)
+ *     an unknown normal (a zero row) stays a zero row
+ * Order.  Within a body view-major; inside a view the tile / Z-order of "Depth images".
+ *
+ * sh_depth_views_count -> counts int32 [B], the kept pixels of a body over all its views, and in `workspace`
+ * (sh_depth_views_workspace(B, V, H, W) bytes, int32 [B][V][tiles]) the first row of every tile.  sh_depth_views_points, given
+ * the same inputs, that workspace, the counts and a width M >= max_count, -> points fp32 [B][M][3] = P', normals fp32 [B][M][3] =
+ * n', pixel int32 [B][M] = v * W + u within the row's own view, view uint8 [B][M], and view_first int32 [B][V + 1]: the first
+ * row of each view, the last entry the count (an empty or absent view repeats its successor's).  Rows at or beyond a body's
+ * count hold zeros, zeros, -1 and 255.  No row >= M is ever written.
+ *
+ * How it is computed.  The three passes of "Depth images" with image = body * V + view: the count pass over B V images, ONE
+ * exclusive scan per body over its V * tiles tile counts, and the emit pass, which applies the transform and shares the body's
+ * padding out over the workgroups of all its views.
+ * B == 0 or H * W == 0: SH_OK, nothing launched (view_first is not written).  Null pointers (mask excepted), V outside
+ * [1, SH_DEPTH_MAX_VIEWS], negative sizes, stride < 1, M < max_count or an unknown dtype: SH_ERR_INVALID_ARG before the device is
+ * touched; a workspace that is too small: SH_ERR_WORKSPACE; B * V > 65535 or V * H * W > INT_MAX: SH_ERR_UNSUPPORTED.
+ */
+#define SH_DEPTH_MAX_VIEWS 32
+SH_API size_t sh_depth_views_workspace(int B, int V, int H, int W);
+SH_API int sh_depth_views_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext,
+                                int B, int V, int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride,
+                                int32_t* counts, void* workspace, size_t workspace_bytes, sh_stream_t stream);
+SH_API int sh_depth_views_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext,
+                                 int B, int V, int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride,
+                                 const int32_t* counts, int max_count, int M, const void* workspace, size_t workspace_bytes, float* points,
+                                 float* normals, int32_t* pixel, uint8_t* view, int32_t* view_first, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Depth field: what a depth image says about where the body is NOT - the way back from the model to the image (no reference

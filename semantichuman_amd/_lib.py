@@ -89,9 +89,15 @@ SIGNATURES = {
     "sh_cloud_normals": (c_int, [_P, _L, _I, _P, _I, _I, _P, _L, _L, _P, _P, _P, _P, _P, c_size_t, _P]),
     "sh_vertex_visibility_workspace": (c_size_t, [_I, _I, _I, _I]),
     "sh_vertex_visibility": (c_int, [_P, _L, _I, _P, _I, _P, _P, c_float, _P, _L, _I, _I, _P, c_size_t, _P, _P]),
+    "sh_vertex_visibility_views_workspace": (c_size_t, [_I, _I, _I, _I, _I]),
+    "sh_vertex_visibility_views": (c_int, [_P, _L, _I, _P, _I, _P, _P, _I, c_float, _P, _L, _I, _I, _P, c_size_t, _P, _P, _P]),
     "sh_depth_workspace": (c_size_t, [_I, _I, _I]),
     "sh_depth_count": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _P, c_size_t, _P]),
     "sh_depth_points": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _I, _P, c_size_t, _P, _P, _P, _P]),
+    "sh_depth_views_workspace": (c_size_t, [_I, _I, _I, _I]),
+    "sh_depth_views_count": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _P, c_size_t, _P]),
+    "sh_depth_views_points": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _I, _P, c_size_t, _P, _P,
+                                      _P, _P, _P, _P]),
     "sh_depth_field_workspace": (c_size_t, [_I, _I, _I]),
     "sh_depth_field": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "sh_free_space_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),

@@ -24,6 +24,13 @@ struct DepthArgs {
     float depth_scale, z_near, z_far, max_step;
     int drop_isolated, stride;
 };
+// The rig form ("Depth views"): V images per body, each with its camera -> rig transform; ext == nullptr: one camera, its own frame.
+struct ViewArgs {
+    const float* ext;                   // [B][V][12], R row-major then t; a NaN anywhere in a row: the view is absent
+    int V;
+    uint8_t* view;                      // [B][M], the view a row came from, 255 in the padding
+    int32_t* view_first;                // [B][V + 1]
+};
 struct P3 { float x, y, z; };
 
 // bits 0, 2, 4, 6 of r -> a 4-bit number: the u of a Z-rank (its v: the same of r >> 1)
@@ -65,16 +72,30 @@ __device__ __forceinline__ bool tangent(const P3& lo, bool has_lo, const P3& c, 
     return has_lo || has_hi;
 }
 
-// grid (tile, body).  EMIT = false, the count pass: tile_row[b][tile] = the tile's kept pixels.  EMIT = true: tile_row holds the
-// tile's first row (depth_scan_kernel), and the kept pixels and the body's padding are written.
-template <typename T, bool EMIT>
-__global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restrict__ tile_row, const int32_t* __restrict__ counts, int M,
-                                                  float* __restrict__ points, float* __restrict__ normals, int32_t* __restrict__ pixel) {
+// grid (tile, image).  EMIT = false, the count pass: tile_row[image][tile] = the tile's kept pixels.  EMIT = true: tile_row holds the
+// tile's first row (depth_scan_kernel), and the kept pixels and the body's padding are written.  VIEWS = false: an image is a
+// body.  VIEWS = true: image = body * V + view, a body's rows are its views' in turn - tile_row [B][V][tiles] is scanned per body -
+// and the emit pass moves point and normal into the rig's frame; an absent view enters as a tile of NaN: nothing kept, nothing
+// of it read.
+template <typename T, bool EMIT, bool VIEWS>
+__global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, ViewArgs va, int32_t* __restrict__ tile_row, const int32_t* __restrict__ counts,
+                                                  int M, float* __restrict__ points, float* __restrict__ normals, int32_t* __restrict__ pixel) {
     __shared__ float zt[HALO * LROW];
     __shared__ int wsum[NT / 64];
-    const int tile = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int tile = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    const int b = VIEWS ? img / va.V : img, view = VIEWS ? img - b * va.V : 0;
     const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
-    load_tile<T>(a, b, tx * TILE, ty * TILE, zt);
+    float e[12] = {};
+    bool present = true;                                                 // uniform
+    if (VIEWS) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            e[k] = va.ext[12L * img + k];
+            present = present && e[k] == e[k];
+        }
+    }
+    if (present) load_tile<T>(a, img, tx * TILE, ty * TILE, zt);
+    else for (int i = tid; i < HALO * LROW; i += NT) zt[i] = NAN;
     __syncthreads();
     const int lu = even_bits(tid), lv = even_bits(tid >> 1);
     const int u = tx * TILE + lu, v = ty * TILE + lv;
@@ -84,8 +105,8 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restr
     bool kept = valid && u % a.stride == 0 && v % a.stride == 0;
     P3 p = {0.f, 0.f, 0.f};
     float nx = 0.f, ny = 0.f, nz = 0.f;
-    if (EMIT || a.drop_isolated) {                                       // uniform
-        const float* k = a.intr + 4L * b;
+    if ((EMIT || a.drop_isolated) && present) {                          // uniform
+        const float* k = a.intr + 4L * img;
         const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
         const float zl = zc[-1], zr = zc[1], zu = zc[-LROW], zd = zc[LROW];
         p = unproject(u, v, z, fx, fy, cx, cy);
@@ -101,9 +122,20 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restr
         const double len = sqrt(len2);
         const bool away = (c0 * (double)p.x + c1 * (double)p.y) + c2 * (double)p.z > 0.0;
         const double n0 = c0 / len, n1 = c1 / len, n2 = c2 / len;
-        nx = known ? (float)(away ? -n0 : n0) : 0.f;
-        ny = known ? (float)(away ? -n1 : n1) : 0.f;
-        nz = known ? (float)(away ? -n2 : n2) : 0.f;
+        const double m0 = away ? -n0 : n0, m1 = away ? -n1 : n1, m2 = away ? -n2 : n2;
+        if (VIEWS && EMIT) {                                             // "Depth views": the point in fp32, the normal in fp64 from the unrounded n
+            nx = known ? (float)(((double)e[0] * m0 + (double)e[1] * m1) + (double)e[2] * m2) : 0.f;
+            ny = known ? (float)(((double)e[3] * m0 + (double)e[4] * m1) + (double)e[5] * m2) : 0.f;
+            nz = known ? (float)(((double)e[6] * m0 + (double)e[7] * m1) + (double)e[8] * m2) : 0.f;
+            const P3 c = p;
+            p.x = ((e[0] * c.x + e[1] * c.y) + e[2] * c.z) + e[9];
+            p.y = ((e[3] * c.x + e[4] * c.y) + e[5] * c.z) + e[10];
+            p.z = ((e[6] * c.x + e[7] * c.y) + e[8] * c.z) + e[11];
+        } else {
+            nx = known ? (float)m0 : 0.f;
+            ny = known ? (float)m1 : 0.f;
+            nz = known ? (float)m2 : 0.f;
+        }
         if (a.drop_isolated) kept = kept && known;
     }
     // rank among the tile's kept pixels: lanes below in the wave (ballot), waves below in the workgroup (LDS)
@@ -118,12 +150,16 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restr
         before += i < w ? s : 0;
         total += s;
     }
-    const long slot = (long)b * a.tiles + tile;
+    const long slot = (long)img * a.tiles + tile;
     if (!EMIT) {
         if (tid == 0) tile_row[slot] = total;
         return;
     }
     const long body = (long)b * M;
+    if (VIEWS && tile == 0 && tid == 0) {                                // the view's first row; the last view also closes the list
+        va.view_first[(long)b * (va.V + 1) + view] = tile_row[slot];
+        if (view == va.V - 1) va.view_first[(long)b * (va.V + 1) + va.V] = counts[b];
+    }
     if (kept) {
         const int row = tile_row[slot] + before + __popcll(bal & ((1ull << lane) - 1ull));
         if (row < M) {                                                   // holds whenever M >= the count; never a store beyond the body
@@ -131,14 +167,17 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, int32_t* __restr
             points[3 * o] = p.x; points[3 * o + 1] = p.y; points[3 * o + 2] = p.z;
             normals[3 * o] = nx; normals[3 * o + 1] = ny; normals[3 * o + 2] = nz;
             pixel[o] = v * a.W + u;
+            if (VIEWS) va.view[o] = (uint8_t)view;
         }
     }
     // the padding rows of the body, shared out over its workgroups
-    for (long j = (long)max(counts[b], 0) + (long)tile * NT + tid; j < M; j += (long)a.tiles * NT) {
+    const long wg = VIEWS ? (long)view * a.tiles + tile : tile, wgs = VIEWS ? (long)va.V * a.tiles : a.tiles;
+    for (long j = (long)max(counts[b], 0) + wg * NT + tid; j < M; j += wgs * NT) {
         const long o = body + j;
         points[3 * o] = 0.f; points[3 * o + 1] = 0.f; points[3 * o + 2] = 0.f;
         normals[3 * o] = 0.f; normals[3 * o + 1] = 0.f; normals[3 * o + 2] = 0.f;
         pixel[o] = -1;
+        if (VIEWS) va.view[o] = 255;
     }
 }
 
@@ -184,13 +223,26 @@ int check_inputs(const char* who, const void* depth, int dtype, const float* int
     return SH_OK;
 }
 
-template <bool EMIT>
-void launch_tiles(hipStream_t st, int dtype, const DepthArgs& a, int B, int32_t* tile_row, const int32_t* counts, int M, float* points,
-                  float* normals, int32_t* pixel) {
-    ShProfScope ps(st, "%s|B=%d H=%d W=%d u16=%d", EMIT ? "depth_emit_kernel" : "depth_count_kernel", B, a.H, a.W, dtype == SH_DEPTH_U16);
-    const dim3 grid((unsigned)a.tiles, (unsigned)B);
-    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_kernel<uint16_t, EMIT>), grid, dim3(NT), 0, st, a, tile_row, counts, M, points, normals, pixel);
-    else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT>), grid, dim3(NT), 0, st, a, tile_row, counts, M, points, normals, pixel);
+// The same for the rig form: V images per body with their extrinsics.  int32 rows per body: V * H * W must fit.
+int check_views(const char* who, const void* depth, int dtype, const float* intr, const float* ext, int B, int V, int H, int W, int stride) {
+    SH_REQUIRE(ext, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(V >= 1 && V <= SH_DEPTH_MAX_VIEWS, SH_ERR_INVALID_ARG, "%s: V = %d views, must lie in [1, %d]", who, V, SH_DEPTH_MAX_VIEWS);
+    if (const int rc = check_inputs(who, depth, dtype, intr, B, H, W, stride)) return rc;
+    SH_REQUIRE((long)B * V <= 65535 && (long)V * H * W <= INT_MAX, SH_ERR_UNSUPPORTED, "%s: B * V or V * H * W too large", who);
+    return SH_OK;
+}
+
+// One pass over the tiles of B bodies: of one image each (va.ext == nullptr, the record reads as before), or of va.V views each.
+template <bool EMIT, bool VIEWS>
+void launch_tiles(hipStream_t st, int dtype, const DepthArgs& a, const ViewArgs& va, int B, int32_t* tile_row, const int32_t* counts, int M,
+                  float* points, float* normals, int32_t* pixel) {
+    char name[96];
+    if (VIEWS) snprintf(name, sizeof name, "%s|B=%d V=%d H=%d W=%d u16=%d", EMIT ? "depth_views_emit_kernel" : "depth_views_count_kernel", B, va.V, a.H, a.W, dtype == SH_DEPTH_U16);
+    else snprintf(name, sizeof name, "%s|B=%d H=%d W=%d u16=%d", EMIT ? "depth_emit_kernel" : "depth_count_kernel", B, a.H, a.W, dtype == SH_DEPTH_U16);
+    ShProfScope ps(st, "%s", name);
+    const dim3 grid((unsigned)a.tiles, (unsigned)(VIEWS ? B * va.V : B));
+    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_kernel<uint16_t, EMIT, VIEWS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel);
+    else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT, VIEWS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel);
 }
 
 }  // namespace
@@ -214,7 +266,7 @@ int sh_depth_count(const void* depth, int dtype, float depth_scale, const float*
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
     int32_t* tile_row = static_cast<int32_t*>(workspace);
-    launch_tiles<false>(st, dtype, a, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
+    launch_tiles<false, false>(st, dtype, a, ViewArgs{}, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
     {
         ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, a.tiles);
         SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, a.tiles, counts);
@@ -236,8 +288,55 @@ int sh_depth_points(const void* depth, int dtype, float depth_scale, const float
     SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_points: the workspace of sh_depth_count is needed (%zu bytes)", need);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
-    launch_tiles<true>(st, dtype, a, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts, M, points, normals, pixel);
+    launch_tiles<true, false>(st, dtype, a, ViewArgs{}, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts, M, points, normals, pixel);
     SH_CHECK_LAUNCH("depth_points");
+    return SH_OK;
+}
+
+size_t sh_depth_views_workspace(int B, int V, int H, int W) {
+    if (B <= 0 || V < 1 || V > SH_DEPTH_MAX_VIEWS || H <= 0 || W <= 0) return 0;
+    return (size_t)B * V * tiles_of(H, W) * sizeof(int32_t);
+}
+
+int sh_depth_views_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                         int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, int32_t* counts,
+                         void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    const int rc = check_views("sh_depth_views_count", depth, dtype, intr, ext, B, V, H, W, stride);
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(counts, SH_ERR_INVALID_ARG, "sh_depth_views_count: null pointer");
+    if (B == 0 || H == 0 || W == 0) return SH_OK;
+    const size_t need = sh_depth_views_workspace(B, V, H, W);
+    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_views_count: the workspace holds the tile rows (%zu bytes needed)", need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
+    int32_t* tile_row = static_cast<int32_t*>(workspace);
+    launch_tiles<false, true>(st, dtype, a, ViewArgs{ext, V, nullptr, nullptr}, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
+    {
+        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, V * a.tiles);
+        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, V * a.tiles, counts);
+    }
+    SH_CHECK_LAUNCH("depth_views_count");
+    return SH_OK;
+}
+
+int sh_depth_views_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                          int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts,
+                          int max_count, int M, const void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel,
+                          uint8_t* view, int32_t* view_first, sh_stream_t stream) {
+    const int rc = check_views("sh_depth_views_points", depth, dtype, intr, ext, B, V, H, W, stride);
+    if (rc != SH_OK) return rc;
+    SH_REQUIRE(counts && points && normals && pixel && view && view_first, SH_ERR_INVALID_ARG, "sh_depth_views_points: null pointer");
+    SH_REQUIRE(M >= 0 && max_count >= 0, SH_ERR_INVALID_ARG, "sh_depth_views_points: negative size (M %d, max_count %d)", M, max_count);
+    SH_REQUIRE(M >= max_count, SH_ERR_INVALID_ARG, "sh_depth_views_points: M = %d rows cannot hold the largest body's %d", M, max_count);
+    if (B == 0 || H == 0 || W == 0) return SH_OK;
+    const size_t need = sh_depth_views_workspace(B, V, H, W);
+    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE,
+               "sh_depth_views_points: the workspace of sh_depth_views_count is needed (%zu bytes)", need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
+    launch_tiles<true, true>(st, dtype, a, ViewArgs{ext, V, view, view_first}, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts,
+                             M, points, normals, pixel);
+    SH_CHECK_LAUNCH("depth_views_points");
     return SH_OK;
 }
 

@@ -23,11 +23,29 @@ __device__ __forceinline__ void vis_cross(float ux, float uy, float uz, float vx
     cz = __builtin_fmaf(ux, vy, -(uy * vx));
 }
 
+// Face f as its three 16-byte LDS records - (a, e1.x) (e1.y, e1.z, e2.x, e2.y) (e2.z, i0, i1, i2); a face beyond the table, or with a
+// corner outside [0, n), as NaN with indices -1: its det is NaN and no compare of the hit test holds.
+__device__ __forceinline__ void gather_face(const float* __restrict__ xb, const int32_t* __restrict__ faces, int f, int nF, int n, f32x4& r0,
+                                            f32x4& r1, f32x4& r2) {
+#pragma clang fp contract(off)
+    int i0 = -1, i1 = -1, i2 = -1;
+    const bool ok = f < nF && face_corners(faces, f, n, i0, i1, i2);
+    float ax = NAN, ay = NAN, az = NAN, bx = NAN, by = NAN, bz = NAN, cx = NAN, cy = NAN, cz = NAN;
+    if (ok) {
+        ax = xb[3L * i0]; ay = xb[3L * i0 + 1]; az = xb[3L * i0 + 2];
+        bx = xb[3L * i1]; by = xb[3L * i1 + 1]; bz = xb[3L * i1 + 2];
+        cx = xb[3L * i2]; cy = xb[3L * i2 + 1]; cz = xb[3L * i2 + 2];
+    } else {
+        i0 = i1 = i2 = -1;
+    }
+    r0 = f32x4{ax, ay, az, bx - ax};
+    r1 = f32x4{by - ay, bz - az, cx - ax, cy - ay};
+    r2 = f32x4{cz - az, __int_as_float(i0), __int_as_float(i1), __int_as_float(i2)};
+}
+
 // grid (vertex tile, face chunk, body).  final != 0: the one chunk's answer is the answer, flag = vis [B][n], 1 = visible;
 // otherwise flag = the workspace [chunks][B][n], 1 = NOT visible on this chunk's evidence, for visibility_fold_kernel.
-// A face enters LDS as three 16-byte records - (a, e1.x) (e1.y, e1.z, e2.x, e2.y) (e2.z, i0, i1, i2) - written by the thread that
-// gathered its corners; a face beyond the table, or with a corner outside [0, n), enters as NaN with indices -1: its det is NaN and
-// no compare of the hit test holds.  A lane is `done` when nothing a face could do would change its answer: beyond n, masked,
+// A face enters LDS as the three records of gather_face, written by the thread that gathered its corners.  A lane is `done` when nothing a face could do would change its answer: beyond n, masked,
 // turned away from the sensor, or already hit.  The inner loop asks the wave every four faces whether any lane is still open;
 // the tile loop asks the workgroup once per tile, through two LDS words per wave written before the tile's one barrier.
 __global__ __launch_bounds__(NT) void vertex_visibility_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
@@ -60,22 +78,7 @@ __global__ __launch_bounds__(NT) void vertex_visibility_kernel(const float* __re
         bool done = hidden;
         const int wave = sh_wave_id();
         f32x4 r0, r1, r2;
-        auto fetch = [&](int tile) {
-            const int f = tile * TF + tid;
-            int i0 = -1, i1 = -1, i2 = -1;
-            const bool ok = f < nF && face_corners(faces, f, n, i0, i1, i2);
-            float ax = NAN, ay = NAN, az = NAN, bx = NAN, by = NAN, bz = NAN, cx = NAN, cy = NAN, cz = NAN;
-            if (ok) {
-                ax = xb[3L * i0]; ay = xb[3L * i0 + 1]; az = xb[3L * i0 + 2];
-                bx = xb[3L * i1]; by = xb[3L * i1 + 1]; bz = xb[3L * i1 + 2];
-                cx = xb[3L * i2]; cy = xb[3L * i2 + 1]; cz = xb[3L * i2 + 2];
-            } else {
-                i0 = i1 = i2 = -1;
-            }
-            r0 = f32x4{ax, ay, az, bx - ax};
-            r1 = f32x4{by - ay, bz - az, cx - ax, cy - ay};
-            r2 = f32x4{cz - az, __int_as_float(i0), __int_as_float(i1), __int_as_float(i2)};
-        };
+        auto fetch = [&](int tile) { gather_face(xb, faces, tile * TF + tid, nF, n, r0, r1, r2); };
         auto stage = [&](int buf) { sf[buf][3 * tid] = r0; sf[buf][3 * tid + 1] = r1; sf[buf][3 * tid + 2] = r2; };
         fetch(tile_lo);
         stage(0);
@@ -133,6 +136,145 @@ __global__ __launch_bounds__(256) void visibility_fold_kernel(const unsigned cha
     vis[t] = any ? 0 : 1;
 }
 
+// ------------------------------------------------------------------------------------------------ any-view form
+constexpr int VMAX = SH_VISIBILITY_MAX_VIEWS;
+static_assert(VMAX == 32, "one bit of a 32-bit word per view");
+
+// The views a vertex at o can be seen from before any face is looked at: bit v = the view's row holds no NaN (-> `live`, uniform)
+// and the vertex is active and - with a normal row t - faces it, by the single-view kernel's own expressions.  view: the body's
+// [V][3]; its addresses are uniform, so the rows arrive by scalar loads.
+__device__ __forceinline__ uint32_t view_candidates(const float* __restrict__ view, int V, bool active, float ox, float oy, float oz,
+                                                    const float* __restrict__ t, float cos_g, uint32_t& live) {
+#pragma clang fp contract(off)
+    uint32_t cand = 0;
+    live = 0;
+    for (int v = 0; v < V; ++v) {
+        const float vx = view[3 * v], vy = view[3 * v + 1], vz = view[3 * v + 2];
+        if (!(vx == vx && vy == vy && vz == vz)) continue;               // uniform: an absent camera
+        live |= 1u << v;
+        bool ok = active;
+        if (ok && t) {
+            const float dx = vx - ox, dy = vy - oy, dz = vz - oz;
+            const float along = vis_dot(t[0], t[1], t[2], dx, dy, dz);
+            const float len = sqrtf(vis_dot(dx, dy, dz, dx, dy, dz));
+            ok = along >= cos_g * len;                                   // a NaN compares false: not facing
+        }
+        cand |= ok ? 1u << v : 0u;
+    }
+    return cand;
+}
+
+// grid (vertex tile, face chunk, body): vertex_visibility_kernel with `open`, the views from which the vertex is still unoccluded,
+// in place of `done`.  A face's s = o - a, q = s x e1 and t = e2 . q do not depend on the view and are formed once; a lane then walks
+// the set bits of `open` (none for a face that names it), reads that view's position from LDS - one 16-byte read, a broadcast
+// where the lanes agree - and forms d, p, det, u, w.  The early exits are the single-view kernel's: a ballot of "any view open"
+// every four faces, the workgroup's through two LDS words per wave.  final != 0: out = seen [B][n] (may be null) and vis is
+// written; otherwise out = the workspace [chunks][B][n], the views this chunk's faces hide, for visibility_views_fold_kernel.
+__global__ __launch_bounds__(NT) void vertex_visibility_views_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
+                                                                    int nF, const float* __restrict__ tn, const float* __restrict__ view, int V,
+                                                                    float cos_g, const unsigned char* __restrict__ mask, long mask_sb, int B,
+                                                                    int tiles_per_chunk, int final, uint32_t* __restrict__ out,
+                                                                    unsigned char* __restrict__ vis) {
+#pragma clang fp contract(off)
+    __shared__ f32x4 sf[2][3 * TF];
+    __shared__ f32x4 sview[VMAX];
+    __shared__ int sopen[2][NT / 64];
+    const int b = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
+    const int i = blockIdx.x * NT + tid;
+    const bool inside = i < n;
+    const float* xb = x + (long)b * x_sb;
+    const float* vb = view + 3L * b * V;
+    if (tid < V) sview[tid] = f32x4{vb[3 * tid], vb[3 * tid + 1], vb[3 * tid + 2], 0.f};
+    const bool active = inside && (!mask || mask[(long)b * mask_sb + i] != 0);
+    const float ox = inside ? xb[3L * i] : 0.f, oy = inside ? xb[3L * i + 1] : 0.f, oz = inside ? xb[3L * i + 2] : 0.f;
+    uint32_t live;
+    const uint32_t cand = view_candidates(vb, V, active, ox, oy, oz, tn ? tn + ((long)b * n + i) * 3 : nullptr, cos_g, live);   // tn is read where active
+    uint32_t open = cand;
+    const int tiles = (nF + TF - 1) / TF;
+    const int tile_lo = c * tiles_per_chunk;
+    const int tile_hi = min(tile_lo + tiles_per_chunk, tiles);
+    if (live != 0u && tile_lo < tile_hi) {                               // uniform
+        const int wave = sh_wave_id();
+        f32x4 r0, r1, r2;
+        auto fetch = [&](int tile) { gather_face(xb, faces, tile * TF + tid, nF, n, r0, r1, r2); };
+        auto stage = [&](int buf) { sf[buf][3 * tid] = r0; sf[buf][3 * tid + 1] = r1; sf[buf][3 * tid + 2] = r2; };
+        fetch(tile_lo);
+        stage(0);
+        int any = __ballot(open != 0u) != 0ull;                          // uniform over the wave
+        if ((tid & 63) == 0) sopen[0][wave] = any;
+        __syncthreads();                                                 // sview as well
+        for (int tile = tile_lo; tile < tile_hi; ++tile) {
+            const int cur = (tile - tile_lo) & 1;
+            if ((sopen[cur][0] | sopen[cur][1] | sopen[cur][2] | sopen[cur][3]) == 0) break;   // uniform over the workgroup
+            const bool more = tile + 1 < tile_hi;
+            if (more) fetch(tile + 1);
+            for (int u = 0; u < TF; u += 4) {
+                if (__ballot(open != 0u) == 0ull) break;                 // uniform over the wave
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const f32x4 R0 = sf[cur][3 * (u + e)], R1 = sf[cur][3 * (u + e) + 1], R2 = sf[cur][3 * (u + e) + 2];
+                    const float ax = R0[0], ay = R0[1], az = R0[2], e1x = R0[3], e1y = R1[0], e1z = R1[1];
+                    const float e2x = R1[2], e2y = R1[3], e2z = R2[0];
+                    const bool names = __float_as_int(R2[1]) == i || __float_as_int(R2[2]) == i || __float_as_int(R2[3]) == i;
+                    float qx, qy, qz;
+                    const float sx = ox - ax, sy = oy - ay, sz = oz - az;
+                    vis_cross(sx, sy, sz, e1x, e1y, e1z, qx, qy, qz);
+                    const float tt = vis_dot(e2x, e2y, e2z, qx, qy, qz);
+                    for (uint32_t m = names ? 0u : open; m != 0u; m &= m - 1u) {
+                        const int v = __builtin_ctz(m);
+                        const f32x4 vw = sview[v];
+                        const float dx = vw[0] - ox, dy = vw[1] - oy, dz = vw[2] - oz;
+                        float px, py, pz;
+                        vis_cross(dx, dy, dz, e2x, e2y, e2z, px, py, pz);
+                        const float det = vis_dot(e1x, e1y, e1z, px, py, pz);
+                        const float uu = vis_dot(sx, sy, sz, px, py, pz);
+                        const float ww = vis_dot(dx, dy, dz, qx, qy, qz);
+                        const bool neg = det < 0.f;
+                        const float ad = fabsf(det), su = neg ? -uu : uu, sw = neg ? -ww : ww, st = neg ? -tt : tt;
+                        const bool hit = det != 0.f && su >= 0.f && sw >= 0.f && su + sw <= ad && st > 0.f && st < ad;   // a NaN compares false
+                        open &= hit ? ~(1u << v) : ~0u;
+                    }
+                }
+            }
+            if (more) {
+                stage(cur ^ 1);
+                any = __ballot(open != 0u) != 0ull;
+                if ((tid & 63) == 0) sopen[cur ^ 1][wave] = any;
+            }
+            __syncthreads();
+        }
+    }
+    if (!inside) return;
+    const long o = (long)b * n + i;
+    if (final) {
+        if (out) out[o] = open;
+        vis[o] = (live == 0u ? active : open != 0u) ? 1 : 0;             // no camera at all: a full scan
+    } else {
+        out[((long)c * B + b) * n + i] = cand & ~open;
+    }
+}
+
+// grid (vertex tile, body).  seen = the candidate views of the vertex (formed again: V dot products) minus what any chunk hides.
+__global__ __launch_bounds__(256) void visibility_views_fold_kernel(const float* __restrict__ x, long x_sb, int n, const float* __restrict__ tn,
+                                                                   const float* __restrict__ view, int V, float cos_g,
+                                                                   const unsigned char* __restrict__ mask, long mask_sb, int B,
+                                                                   const uint32_t* __restrict__ part, int chunks, uint32_t* __restrict__ seen,
+                                                                   unsigned char* __restrict__ vis) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* xb = x + (long)b * x_sb;
+    const bool active = !mask || mask[(long)b * mask_sb + i] != 0;
+    uint32_t live;
+    const uint32_t cand = view_candidates(view + 3L * b * V, V, active, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2],
+                                          tn ? tn + ((long)b * n + i) * 3 : nullptr, cos_g, live);
+    const long o = (long)b * n + i;
+    uint32_t hits = 0;
+    for (int c = 0; c < chunks; ++c) hits |= part[(long)c * B * n + o];
+    const uint32_t s = cand & ~hits;
+    if (seen) seen[o] = s;
+    vis[o] = (live == 0u ? active : s != 0u) ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,6 +316,48 @@ int sh_vertex_visibility(const float* x, int64_t x_sb, int n, const int32_t* fac
         SH_LAUNCH_PS(ps, visibility_fold_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, st, flag, (long)B * n, c, vis);
     }
     SH_CHECK_LAUNCH("vertex_visibility");
+    return SH_OK;
+}
+
+size_t sh_vertex_visibility_views_workspace(int B, int n, int nF, int V, int chunks) {
+    if (B <= 0 || n <= 0 || nF < 0 || V < 1 || V > VMAX || chunks < 0) return 0;
+    int tpc;
+    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
+    return c <= 1 ? 0 : (size_t)c * B * n * sizeof(uint32_t);
+}
+
+int sh_vertex_visibility_views(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view, int V,
+                               float cos_g, const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace, size_t workspace_bytes,
+                               uint8_t* vis, uint32_t* seen, sh_stream_t stream) {
+    SH_REQUIRE(x && view && vis && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: null pointer");
+    SH_REQUIRE(V >= 1 && V <= VMAX, SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: V = %d views, must lie in [1, %d]", V, VMAX);
+    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
+               "sh_vertex_visibility_views: negative size (B %d, n %d, nF %d, chunks %d)", B, n, nF, chunks);
+    SH_REQUIRE(!tn || (cos_g >= 0.f && cos_g < 1.f), SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: cos_g must lie in [0, 1) (and not be NaN)");
+    if (B == 0 || n == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * n && (!mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "sh_vertex_visibility_views: batch stride shorter than a body (x_sb %ld, mask_sb %ld)", (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "sh_vertex_visibility_views: B, B*n or nF too large");
+    int tpc;
+    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
+    SH_REQUIRE(c <= 65535, SH_ERR_UNSUPPORTED, "sh_vertex_visibility_views: %d face chunks", c);
+    const size_t need = c <= 1 ? 0 : (size_t)c * B * n * sizeof(uint32_t);
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
+               "sh_vertex_visibility_views: workspace too small (%zu bytes needed for %d chunks)", need, c);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int final = c <= 1;
+    uint32_t* part = static_cast<uint32_t*>(workspace);
+    {
+        ShProfScope ps(st, "vertex_visibility_views_kernel|B=%d n=%d nF=%d V=%d chunks=%d", B, n, nF, V, c);
+        SH_LAUNCH_PS(ps, vertex_visibility_views_kernel, dim3((unsigned)sh_cdiv(n, NT), (unsigned)c, (unsigned)B), dim3(NT), 0, st, x, (long)x_sb, n,
+                     faces, nF, tn, view, V, cos_g, mask, (long)mask_sb, B, tpc, final, final ? seen : part, vis);
+    }
+    if (!final) {
+        ShProfScope ps(st, "visibility_views_fold_kernel|B=%d n=%d V=%d chunks=%d", B, n, V, c);
+        SH_LAUNCH_PS(ps, visibility_views_fold_kernel, dim3((unsigned)sh_cdiv(n, 256), (unsigned)B), dim3(256), 0, st, x, (long)x_sb, n, tn, view, V,
+                     cos_g, mask, (long)mask_sb, B, part, c, seen, vis);
+    }
+    SH_CHECK_LAUNCH("vertex_visibility_views");
     return SH_OK;
 }
 

@@ -555,7 +555,44 @@ def vertex_visibility(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks
     return vis
 
 
-DEPTH_DTYPES = {torch.float32: 0, torch.int16: 1}               # enum sh_depth_dtype: 16-bit words travel as int16 and are read unsigned
+MAX_VIEWS = 32                                                  # SH_VISIBILITY_MAX_VIEWS, SH_DEPTH_MAX_VIEWS
+
+
+def vertex_visibility_views(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks=0, out=None, seen=False):
+    """sh_vertex_visibility_views: `vertex_visibility` for a rig, view fp32 HIP [B, V, 3] with 1 <= V <= 32 (a NaN row: an absent
+    camera; all rows NaN: a full scan) -> uint8 [B, n], 1 = some view sees the vertex; with seen=True -> (that, uint32 [B, n]
+    carried as int32: bit v = view v alone sees it).  Every other argument as there."""
+    B, rows, x_sb = _points(x, "vertex_visibility_views")
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("vertex_visibility_views: n = %d exceeds the model's %d rows" % (n, rows))
+    nF = _face_table_arg(faces, "vertex_visibility_views")
+    if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous() and view.dim() == 3
+            and view.shape[0] == B and view.shape[2] == 3):
+        raise ValueError("vertex_visibility_views: view must be a contiguous fp32 HIP tensor [%d, V, 3], got %s" % (B, tuple(getattr(view, "shape", ()))))
+    V = view.shape[1]
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("vertex_visibility_views: V = %d views, must lie in [1, %d]" % (V, MAX_VIEWS))
+    if tn is not None and not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous()
+                               and tuple(tn.shape) == (B, n, 3)):
+        raise ValueError("vertex_visibility_views: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (B, n))
+    mask, mask_sb = _mask_arg(v_mask, B, n, x.device)
+    chunks = int(chunks)
+    if chunks < 0:
+        raise ValueError("vertex_visibility_views: chunks must be >= 0")
+    lib = _lib.load()
+    vis = out if out is not None else torch.empty((B, n), dtype=torch.uint8, device=x.device)
+    if not (torch.is_tensor(vis) and vis.device == x.device and vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (B, n)):
+        raise ValueError("vertex_visibility_views: out must be a contiguous uint8 tensor [%d, %d] on the device of x" % (B, n))
+    bits = torch.empty((B, n), dtype=torch.int32, device=x.device) if seen else None
+    nbytes = lib.sh_vertex_visibility_views_workspace(B, n, nF, V, chunks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    check(lib.sh_vertex_visibility_views(ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view), V, float(cos_g), ptr(mask), mask_sb, B, chunks,
+                                         ptr(ws), nbytes, ptr(vis), ptr(bits), stream_ptr()), "sh_vertex_visibility_views")
+    return (vis, bits) if seen else vis
+
+
+DEPTH_DTYPES ={torch.float32: 0, torch.int16: 1}               # enum sh_depth_dtype: 16-bit words travel as int16 and are read unsigned
 
 
 def _depth_args(who, depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
@@ -610,6 +647,67 @@ def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_
     check(lib.sh_depth_points(*args, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), ptr(points), ptr(normals), ptr(pixel),
                               stream_ptr()), "sh_depth_points")
     return points, normals, pixel
+
+
+def _depth_views_args(who, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
+    """The inputs sh_depth_views_count and sh_depth_views_points share, checked -> (B, V, H, W, their C arguments up to `stride`)."""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in DEPTH_DTYPES and depth.dim() == 4 and depth.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.%s needs a contiguous fp32 or 16-bit HIP depth image [B, V, H, W] (got %s %s %s); there is no "
+                           "CPU path" % (who, getattr(depth, "device", None), getattr(depth, "dtype", type(depth)), tuple(getattr(depth, "shape", ()))))
+    B, V, H, W = depth.shape
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    for t, shape, what in ((intr, (B, V, 4), "intr [%d, %d, 4] = (fx, fy, cx, cy)" % (B, V)), (ext, (B, V, 12), "ext [%d, %d, 12] = (R row-major, t)" % (B, V))):
+        if not (torch.is_tensor(t) and t.device == depth.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("%s: %s must be a contiguous fp32 tensor on the depth's device" % (who, what))
+    if mask is not None and not (torch.is_tensor(mask) and mask.device == depth.device and mask.dtype == torch.uint8 and mask.is_contiguous()
+                                 and mask.shape == depth.shape):
+        raise ValueError("%s: mask must be a contiguous uint8 tensor %s on the depth's device" % (who, tuple(depth.shape)))
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("%s: stride = %d, must be at least 1" % (who, stride))
+    return B, V, H, W, (ptr(depth), DEPTH_DTYPES[depth.dtype], float(depth_scale), ptr(intr), ptr(mask), ptr(ext), B, V, H, W, float(z_near),
+                        float(z_far), float(max_step), int(bool(drop_isolated)), stride)
+
+
+def depth_views_count(depth, intr, ext, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False,
+                      stride=1):
+    """sh_depth_views_count: depth [B, V, H, W] fp32 or 16-bit words on the device, intr fp32 [B, V, 4], ext fp32 [B, V, 12] (camera ->
+    rig, R row-major then t; a NaN row: the view is absent), mask uint8 [B, V, H, W] or None -> (counts int32 [B], the kept pixels
+    per body over its views; the workspace sh_depth_views_points reads).  Nothing is synchronised."""
+    B, V, H, W, args = _depth_views_args("depth_views_count", depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    lib = _lib.load()
+    counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
+    nbytes = lib.sh_depth_views_workspace(B, V, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
+    check(lib.sh_depth_views_count(*args, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_depth_views_count")
+    return counts, ws
+
+
+def depth_views_points(depth, intr, ext, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf,
+                       max_step=math.inf, drop_isolated=False, stride=1):
+    """sh_depth_views_points: the inputs and options of the `depth_views_count` call that made (counts, workspace), a width M and the
+    largest count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the rig's frame, normals fp32 [B, M, 3],
+    pixel int32 [B, M] = v * W + u in the row's view, view uint8 [B, M], view_first int32 [B, V + 1]); rows view-major, tile /
+    Z-order inside a view; beyond a body's count zeros, zeros, -1 and 255."""
+    B, V, H, W, args = _depth_views_args("depth_views_points", depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    M, max_count = int(M), int(max_count)
+    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise ValueError("depth_views_points: counts must be the int32 tensor [%d] of depth_views_count" % B)
+    lib = _lib.load()
+    nbytes = lib.sh_depth_views_workspace(B, V, H, W)
+    if not (torch.is_tensor(workspace) and workspace.device == depth.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+            and workspace.numel() >= nbytes):
+        raise ValueError("depth_views_points: workspace must be the one depth_views_count returned for these images (%d bytes)" % nbytes)
+    points = torch.empty((B, max(M, 0), 3), dtype=torch.float32, device=depth.device)
+    normals = torch.empty_like(points)
+    pixel = torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device)
+    view = torch.empty((B, max(M, 0)), dtype=torch.uint8, device=depth.device)
+    view_first = torch.empty((B, V + 1), dtype=torch.int32, device=depth.device)
+    check(lib.sh_depth_views_points(*args, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), ptr(points), ptr(normals), ptr(pixel),
+                                    ptr(view), ptr(view_first), stream_ptr()), "sh_depth_views_points")
+    return points, normals, pixel, view, view_first
 
 
 def depth_field(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):

@@ -28,6 +28,10 @@
                                      body is not: per pixel surface / empty / unknown and the nearest pixel that is not empty
                                      (sh_depth_field); per vertex a free-space and a silhouette term, differentiable
                                      (sh_free_space_fwd / _bwd) - off unless asked for
+  * `unproject_depth_views(depth, intrinsics, extrinsics, ...)`, `ScanBatch.from_depth(..., extrinsics=)`  a rig of calibrated
+                                     depth cameras as ONE scan per body in the rig's frame (sh_depth_views_count / _points);
+                                     its `viewpoints` are [B, V, 3], and `visible_vertices` / `visibility="viewpoint"` then
+                                     mean "seen by at least one camera" (sh_vertex_visibility_views, one sweep over the faces)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -180,13 +184,22 @@ class ScanBatch:
     field is None and `visibility="viewpoint"` later names the reason.
 
     `pixels`: int32 [B, Mmax] on a batch made by `from_depth` - the pixel v * W + u each row came from, -1 in the padding; None on
-    batches made any other way."""
+    batches made any other way.
+
+    A RIG batch - a scan fused from V sensors - carries `viewpoints` fp32 [B, V, 3] instead: the camera centres, a NaN row for an
+    absent camera; `visibility="viewpoint"` then means "seen by at least one of them" (sh_vertex_visibility_views).
+    `from_depth(..., extrinsics=)` makes one, with `view` uint8 [B, Mmax] (the camera each row came from, 255 in the padding) and
+    `view_first` int32 [B, V + 1]; rig_viewpoints=[V, 3] or [B, V, 3] (at most 32 views, NaN rows allowed, no inf) sets the
+    field for a cloud fused elsewhere and takes the place of a per-body `viewpoints` there (per-point viewpoints still orient
+    estimated normals)."""
 
     viewpoints = None                                                                   # for batches made without __init__ or _from_parts
     viewpoints_error = None
     pixels = None
+    view = None
+    view_first = None
 
-    def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None):
+    def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None, rig_viewpoints=None):
         if order not in (None, "morton"):
             raise ValueError("ScanBatch: order must be None or 'morton'")
         estimate = isinstance(normals, str)
@@ -195,6 +208,9 @@ class ScanBatch:
                 raise ValueError("ScanBatch: normals must be None, arrays or 'estimate', got %r" % (normals,))
             normal_k = _check_normal_k("ScanBatch: normal_k", normal_k)
         pts, counts = pack_clouds(clouds)
+        if torch.is_tensor(rig_viewpoints):
+            rig_viewpoints = rig_viewpoints.detach().cpu()
+        rig = None if rig_viewpoints is None else _view_arg("ScanBatch: rig_viewpoints", rig_viewpoints, len(counts), None, rig=True)
         view = None
         if viewpoints is not None:
             try:
@@ -221,7 +237,7 @@ class ScanBatch:
         self.counts = torch.from_numpy(counts).to(dev)
         self.normals = None if nrm is None else torch.from_numpy(nrm).to(dev)
         view = None if view is None else torch.from_numpy(view).to(dev)
-        self.viewpoints = view if view is not None and view.dim() == 2 else None
+        self.viewpoints = rig.to(dev) if rig is not None else view if view is not None and view.dim() == 2 else None
         if estimate:
             self.normals = ops.cloud_normals(self.points, self.counts, normal_k, view)[0]
 
@@ -229,19 +245,28 @@ class ScanBatch:
         return self.points.shape[0]
 
     @classmethod
-    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None, pixels=None):
+    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None, pixels=None, view=None, view_first=None):
         """A ScanBatch around tensors that are already packed and resident: every field, nothing copied or checked."""
         out = cls.__new__(cls)
         out.points, out.counts, out.host_counts, out.perm, out.normals = points, counts, host_counts, perm, normals
-        out.viewpoints, out.pixels = viewpoints, pixels
+        out.viewpoints, out.pixels, out.view, out.view_first = viewpoints, pixels, view, view_first
         return out
 
     @classmethod
-    def from_depth(cls, depth, intrinsics, device, **options):
+    def from_depth(cls, depth, intrinsics, device, extrinsics=None, **options):
         """Depth images as a batch of scans: `unproject_depth(depth, intrinsics, device=device, **options)` kept whole - points in
         the camera's frame in tile order (perm None), counts, the grid normals (oriented to the camera; a zero row: unknown),
         `viewpoints` = zeros [B, 3] (the camera centre) and `pixels`.  Ready for normal_angle=, gate_on=, visibility="viewpoint"
-        and robust= without further arguments.  One host synchronisation, to read the counts."""
+        and robust= without further arguments.  One host synchronisation, to read the counts.
+        extrinsics: None, or the camera -> rig transforms of a rig of V depth cameras - then `unproject_depth_views(depth,
+        intrinsics, extrinsics, device=device, **options)` kept whole as a rig batch: one fused scan per body in the rig's frame,
+        view-major, with `pixels`, `view`, `view_first` and `viewpoints` fp32 [B, V, 3] = the camera centres t (NaN for an absent
+        camera).  Still one host synchronisation."""
+        if extrinsics is not None:
+            points, normals, pixel, view, view_first, counts, host_counts, ext = _unproject_depth_views(depth, intrinsics, extrinsics,
+                                                                                                       device=device, **options)
+            return cls._from_parts(points, counts, host_counts, None, normals, viewpoints=torch.from_numpy(ext[:, :, 9:].copy()).to(points.device),
+                                   pixels=pixel, view=view, view_first=view_first)
         points, normals, pixel, counts, host_counts = _unproject_depth(depth, intrinsics, device=device, **options)
         return cls._from_parts(points, counts, host_counts, None, normals,
                                viewpoints=torch.zeros((points.shape[0], 3), dtype=torch.float32, device=points.device), pixels=pixel)
@@ -251,7 +276,8 @@ class ScanBatch:
         return ScanBatch._from_parts(self.points[sl], self.counts[sl].contiguous(), self.host_counts[sl],
                                      None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl],
                                      viewpoints=None if self.viewpoints is None else self.viewpoints[sl].contiguous(),
-                                     pixels=None if self.pixels is None else self.pixels[sl])
+                                     pixels=None if self.pixels is None else self.pixels[sl], view=None if self.view is None else self.view[sl],
+                                     view_first=None if self.view_first is None else self.view_first[sl])
 
 
 def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
@@ -382,6 +408,98 @@ def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=No
     return _unproject_depth(depth, intrinsics, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
 
 
+def pack_extrinsics(extrinsics, what="extrinsics"):
+    """Camera -> rig transforms, host side: [V, 3, 4] or [B, V, 3, 4] = (R | t), or 4 x 4 matrices whose last row is 0 0 0 1 ->
+    (float32 [B, V, 12] in the layout of sh_transform_points - R row-major, then t -, batched: whether a batch axis was given).
+    An all-NaN matrix is an absent camera and is kept as NaN.  ValueError on any other shape, a matrix that mixes NaN with
+    numbers or holds inf, a last row that is not 0 0 0 1, or a rotation block with max |R^T R - I| > 1e-4 or det <= 0."""
+    e = extrinsics.detach().cpu().numpy() if torch.is_tensor(extrinsics) else extrinsics
+    try:
+        e = np.asarray(e, dtype=np.float64)
+    except (ValueError, TypeError):
+        e = None
+    if e is None or e.ndim not in (3, 4) or e.shape[-2:] not in ((3, 4), (4, 4)) or min(e.shape) < 1:
+        raise ValueError("%s: must be [V, 3, 4] or [B, V, 3, 4] (or 4 x 4 matrices), got %s"
+                         % (what, "shape %s" % (e.shape,) if e is not None else type(extrinsics).__name__))
+    batched = e.ndim == 4
+    e = e.reshape((-1,) + e.shape[-3:]) if batched else e[None]
+    absent = np.isnan(e).all((-2, -1))
+    if not np.isfinite(e[~absent]).all():
+        raise ValueError("%s: a matrix holds NaN or inf (an absent camera is a matrix of NaN only)" % what)
+    if e.shape[-2] == 4:
+        if not (e[~absent][:, 3] == np.array([0.0, 0.0, 0.0, 1.0])).all():
+            raise ValueError("%s: the last row of a 4 x 4 matrix must be 0 0 0 1" % what)
+        e = e[..., :3, :]
+    R = e[~absent][:, :, :3]
+    if R.size and (np.abs(np.swapaxes(R, 1, 2) @ R - np.eye(3)).max() > 1e-4 or (np.linalg.det(R) <= 0).any()):
+        raise ValueError("%s: every rotation block must be a proper rotation (max |R^T R - I| <= 1e-4, det > 0; no scale, no mirror)" % what)
+    out = np.concatenate([e[..., :3].reshape(e.shape[:2] + (9,)), e[..., 3]], -1).astype(np.float32)
+    return np.ascontiguousarray(out), batched
+
+
+def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
+                           device=None):
+    """`unproject_depth_views`, with the counts as the host read them and the extrinsics float32 [B, V, 12] as two more results.
+    Every ValueError is raised before the device is used."""
+    what = "unproject_depth_views"
+    ext, batched = pack_extrinsics(extrinsics, what + ": extrinsics")
+    B, V = ext.shape[:2]
+    if V > ops.MAX_VIEWS:
+        raise ValueError("%s: %d views, at most %d" % (what, V, ops.MAX_VIEWS))
+    shape = tuple(getattr(depth, "shape", np.shape(depth)))
+    if len(shape) != (4 if batched else 3) or shape[:-2] != ((B, V) if batched else (V,)):
+        raise ValueError("%s: depth must be %s for extrinsics of %d bodies x %d views, got %s"
+                         % (what, "[%d, %d, H, W]" % (B, V) if batched else "[%d, H, W]" % V, B, V, shape))
+    try:
+        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
+    except (ValueError, TypeError):
+        k = None
+    if k is None or k.shape not in ((4,), (V, 4), (B, V, 4)):
+        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as [4], [%d, 4] or [%d, %d, 4], got %s"
+                         % (what, V, B, V, "shape %s" % (k.shape,) if k is not None else type(intrinsics).__name__))
+    flat = lambda a: None if a is None else a.reshape((B * V,) + tuple(a.shape[-2:]))      # noqa: E731 - [B * V, H, W]: an image per row
+    if mask is not None and tuple(getattr(mask, "shape", np.shape(mask))) != shape:
+        raise ValueError("%s: mask must have the depth's shape %s" % (what, shape))
+    d, k, m, near, far = _depth_inputs(what, flat(depth if torch.is_tensor(depth) else np.asarray(depth)),
+                                       np.broadcast_to(k, (B, V, 4)).reshape(B * V, 4),
+                                       flat(mask if mask is None or torch.is_tensor(mask) else np.asarray(mask)), z_range)
+    step = math.inf if max_step is None else float(max_step)
+    if not step >= 0:
+        raise ValueError("%s: max_step must be None or >= 0, got %r" % (what, max_step))
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
+    d, k, m = _depth_upload(d, k, m, device)
+    H, W = d.shape[-2:]
+    d, k, m = d.view(B, V, H, W), k.view(B, V, 4), None if m is None else m.view(B, V, H, W)
+    e = torch.from_numpy(ext).to(d.device)
+    opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
+    counts, ws = ops.depth_views_count(d, k, e, **opts)
+    host_counts = counts.cpu().numpy()                                                  # the one synchronisation
+    most = int(host_counts.max())
+    return ops.depth_views_points(d, k, e, counts, ws, max(most, 1), most, **opts) + (counts, host_counts, ext)
+
+
+def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
+                          device=None):
+    """The depth cameras of a rig -> ONE scan per body in the rig's frame (sh_depth_views_count, sh_depth_views_points;
+    include/sh_kernels.h, "Depth views").  depth: [B, V, H, W], or [V, H, W] with extrinsics that have no batch axis (B = 1); fp32 or
+    16-bit words as in `unproject_depth`, and depth_scale, mask (the depth's shape), z_range, max_step, drop_isolated and stride
+    mean per image what they mean there.  intrinsics: (fx, fy, cx, cy) as [4], [V, 4] or [B, V, 4].  extrinsics: camera -> rig as
+    [V, 3, 4] or [B, V, 3, 4] = (R | t), or 4 x 4 with the last row 0 0 0 1 (`pack_extrinsics`); rigid; an all-NaN matrix is an
+    absent camera, which contributes nothing.  Every pixel's camera-frame point P and fp64 normal n are those of `unproject_depth`;
+    the rows hold P' = R P + t (fp32, the header's order of operations) and n' = R n (fp64, rounded once), so a normal still faces
+    its own camera.
+    -> (points fp32 [B, M, 3], normals fp32 [B, M, 3], pixel int32 [B, M] = v * W + u within the row's view, view uint8 [B, M],
+    counts int32 [B], view_first int32 [B, V + 1]: view v's rows are view_first[b, v]:view_first[b, v + 1]); M the largest count
+    (at least 1); rows beyond a count are zeros, zeros, -1 and 255.  Rows are view-major, inside a view in tile / Z-order.  One
+    host synchronisation.  Deterministic - the same bits for a body alone and inside any batch.  Not differentiable.  ValueError
+    (before the device is used) for wrong shapes or dtypes, more than 32 views, fx / fy not finite and positive, stride < 1, a
+    negative max_step, or extrinsics that are no rigid transforms."""
+    points, normals, pixel, view, view_first, counts = _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale, mask, z_range, max_step,
+                                                                              drop_isolated, stride, device)[:6]
+    return points, normals, pixel, view, counts, view_first
+
+
 class DepthField:
     """What B depth images say about where the body is NOT, resident on the device (sh_depth_field; include/sh_kernels.h, "Depth
     field"): `cls` uint8 [B, H, W] - 2 SURFACE (a valid pixel in the sense of `unproject_depth`), 0 EMPTY (a reading that is not
@@ -492,13 +610,18 @@ def _cos_grazing(what, grazing_angle):
     return 0.0 if a == 90.0 else math.cos(math.radians(a))
 
 
-def _view_arg(what, viewpoints, B, device):
-    """Per-body viewpoints as the kernel takes them: host [3] / [B, 3] (a NaN row = no viewpoint) or an fp32 device tensor [B, 3]
-    -> contiguous fp32 [B, 3] on `device` (None: where it is).  ValueError on any other shape."""
+def _view_arg(what, viewpoints, B, device, rig=False):
+    """Per-body viewpoints as the kernels take them: host [3] / [B, 3] (a NaN row = no viewpoint) or an fp32 device tensor [B, 3]
+    or [B, V, 3] (a rig of 1 <= V <= 32 sensors; a NaN row = an absent one) -> contiguous fp32 [B, 3] or [B, V, 3] on `device`
+    (None: where it is).  A HOST array of rank 3 is refused here, as it always was: a rig's viewpoints reach the kernels as a
+    device tensor - what a rig batch carries.  rig=True (ScanBatch's rig_viewpoints=): a rig is meant, host [V, 3] (one rig for
+    every body) or [B, V, 3] is taken, inf is refused.  ValueError on any other shape."""
     v = viewpoints
+    rig_ok = lambda shape: len(shape) == 3 and shape[0] == B and 1 <= shape[1] <= ops.MAX_VIEWS and shape[2] == 3      # noqa: E731
     if torch.is_tensor(v) and v.is_cuda:
-        if v.dtype != torch.float32 or tuple(v.shape) != (B, 3):
-            raise ValueError("%s: device viewpoints must be fp32 [%d, 3], got %s %s" % (what, B, v.dtype, tuple(v.shape)))
+        if v.dtype != torch.float32 or not (tuple(v.shape) == (B, 3) and not rig or rig_ok(tuple(v.shape))):
+            raise ValueError("%s: device viewpoints must be fp32 [%d, 3] or [%d, V <= %d, 3], got %s %s"
+                             % (what, B, B, ops.MAX_VIEWS, v.dtype, tuple(v.shape)))
         return v.detach().contiguous()
     if torch.is_tensor(v):
         v = v.detach().numpy()
@@ -506,13 +629,36 @@ def _view_arg(what, viewpoints, B, device):
         a = np.asarray(v, dtype=np.float32)
     except (ValueError, TypeError):
         a = None
-    if a is None or a.shape not in ((3,), (B, 3)):
-        raise ValueError("%s: viewpoints must be [3] or [%d, 3], got %s" % (what, B, "shape %s" % (a.shape,) if a is not None else type(v).__name__))
-    out = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (B, 3))))
+    if rig and a is not None and a.ndim == 2:
+        a = np.broadcast_to(a, (B,) + a.shape)
+    if a is None or not (rig_ok(a.shape) and not np.isinf(a).any() if rig else a.shape in ((3,), (B, 3))):
+        raise ValueError("%s: viewpoints must be %s, got %s"
+                         % (what, "[V, 3] or [%d, V <= %d, 3] without inf" % (B, ops.MAX_VIEWS) if rig else
+                            "[3] or [%d, 3] (a rig's [%d, V <= %d, 3]: an fp32 device tensor)" % (B, B, ops.MAX_VIEWS),
+                            "shape %s" % (a.shape,) if a is not None else type(v).__name__))
+    out = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (B, 3)) if a.ndim < 3 else a))
     return out if device is None else out.to(device)
 
 
-def visible_vertices(x, faces, viewpoints, n=None, vertex_mask=None, grazing_angle=None, chunks=0):
+def _visibility(x, ft, view, v_mask, tn, cos_g, chunks=0, out=None, seen=False):
+    """The one place that picks the visibility kernel by the viewpoints' rank: [B, 3] -> sh_vertex_visibility (launches and bits as
+    ever), [B, V, 3] -> sh_vertex_visibility_views.  seen=True (a rig only): (vis, the per-view bits)."""
+    if view.dim() == 3:
+        return ops.vertex_visibility_views(x, ft.faces, ft.n, view, v_mask, tn, cos_g, chunks=chunks, out=out, seen=seen)
+    if seen:
+        raise ValueError("visible_vertices: return_seen needs rig viewpoints [B, V, 3], got [B, 3]")
+    return ops.vertex_visibility(x, ft.faces, ft.n, view, v_mask, tn, cos_g, chunks=chunks, out=out)
+
+
+def _move_viewpoints(view, packed, out=None):
+    """Viewpoints [B, 3] or [B, V, 3] under the poses `packed` [B, 12] (sh_transform_points, one row per sensor; a NaN row stays
+    NaN) -> the same shape; out: a tensor of that shape to write into."""
+    rows = view[:, None, :] if view.dim() == 2 else view
+    moved = ops.transform_points(rows, None, packed, out=None if out is None else (out[:, None, :] if out.dim() == 2 else out))
+    return moved[:, 0] if view.dim() == 2 else moved
+
+
+def visible_vertices(x, faces, viewpoints, n=None, vertex_mask=None, grazing_angle=None, chunks=0, return_seen=False):
     """The model vertices a sensor sees: bool [B, n] on the device (sh_vertex_visibility; include/sh_kernels.h, "Vertex
     visibility").  Vertex i of body b is visible when it is active (vertex_mask [n] or [B, n], False = not visible), the open
     segment from it to the body's viewpoint meets no triangle of `faces` other than those that name i - every triangle occludes,
@@ -522,7 +668,13 @@ def visible_vertices(x, faces, viewpoints, n=None, vertex_mask=None, grazing_ang
     tensor [B, 3], in the frame of x; a body whose row holds a NaN has no viewpoint and all its active vertices are visible.
     chunks: the split of the face range (0 = chosen by the library; every split gives the same bits).  Brute force, O(n nF) per
     body with early exits.  Deterministic, not differentiable.  ValueError for a wrong viewpoint shape or a grazing_angle outside
-    (0, 90]."""
+    (0, 90].
+    A rig: viewpoints an fp32 device tensor [B, V, 3], 1 <= V <= 32 - a rig batch's `viewpoints`; a host array of rank 3 stays
+    refused, as before rigs existed - -> visible from AT LEAST ONE of the V sensors
+    (sh_vertex_visibility_views: one sweep over the faces, not V).  A NaN row is an absent sensor; a body whose rows are all NaN
+    has no viewpoint.  return_seen=True (a rig only) -> (visible, seen): seen [B, n] holds the 32-bit word whose bit v says that
+    sensor v alone sees the vertex - exactly what the call with viewpoints[:, v] returns - as torch.uint32 where torch has it,
+    else the same bits as int32."""
     cos_g = None if grazing_angle is None else _cos_grazing("visible_vertices", grazing_angle)
     if torch.is_tensor(x) and x.dim() == 3:
         viewpoints = _view_arg("visible_vertices", viewpoints, x.shape[0], None)    # the shape check needs no device
@@ -531,7 +683,10 @@ def visible_vertices(x, faces, viewpoints, n=None, vertex_mask=None, grazing_ang
     view = viewpoints.to(x.device)
     ft = _face_table(faces, rows if isinstance(faces, FaceTable) else (rows - 1 if n is None else int(n)), x.device)
     tn = None if cos_g is None else ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
-    return ops.vertex_visibility(x, ft.faces, ft.n, view, vertex_mask, tn, 0.0 if cos_g is None else cos_g, chunks=chunks).bool()
+    got = _visibility(x, ft, view, vertex_mask, tn, 0.0 if cos_g is None else cos_g, chunks=chunks, seen=return_seen)
+    if not return_seen:
+        return got.bool()
+    return got[0].bool(), got[1].view(torch.uint32) if hasattr(torch, "uint32") else got[1]
 
 
 def _cos_min(what, normal_angle):
@@ -738,13 +893,13 @@ class _MatchPlan:
             _cos_grazing(what, grazing_angle)
         if isinstance(scans, ScanBatch) and scans.viewpoints is None or not isinstance(scans, ScanBatch):
             why = getattr(scans, "viewpoints_error", None)
-            raise ValueError("%s: visibility='viewpoint' needs the sensor's position per body (ScanBatch(..., viewpoints=[3] or [B, 3]))%s"
+            raise ValueError("%s: visibility='viewpoint' needs the sensor's position per body (ScanBatch(..., viewpoints=[3] or [B, 3]), or a rig's: rig_viewpoints= / from_depth(extrinsics=))%s"
                              % (what, "; the viewpoints given were not kept: %s" % why if why else ""))
         if visibility_faces is None and faces is None and normal_faces is None:
             raise ValueError("%s: visibility='viewpoint' needs the model's triangles (visibility_faces=, faces= or normal_faces=)" % what)
 
     def see(self, x, view, out=None, static_x=False):
-        """Recompute the mask for the model points x seen from `view` fp32 [B, 3]: v_mask = given mask AND visible, uint8 [B, n].
+        """Recompute the mask for the model points x seen from `view` fp32 [B, 3] (or a rig's [B, V, 3]): v_mask = given mask AND visible, uint8 [B, n].
         static_x: x does not change between calls of this plan, so the facing test's normals are computed once."""
         ft, tn = self.vis_table, None
         if self.cos_g is not None:
@@ -752,7 +907,7 @@ class _MatchPlan:
             if tn is None:
                 tn = ops.vertex_normals(x, ft.faces, ft.vf_ptr, ft.vf_idx, ft.n)
                 self.vis_tn = tn if static_x else None
-        self.v_mask = ops.vertex_visibility(x, ft.faces, ft.n, view, self.given_mask, tn, 0.0 if self.cos_g is None else self.cos_g, out=out)
+        self.v_mask = _visibility(x, ft, view, self.given_mask, tn, 0.0 if self.cos_g is None else self.cos_g, out=out)
         self.mask_sb = self.n
         return self.v_mask
 
@@ -1225,7 +1380,7 @@ def pose_update(pose, scans, aligned, matches, mode="similarity", partials=None,
     if scans.normals is not None and aligned.normals is not None:
         ops.transform_points(scans.normals, scans.counts, pose.rotation_packed(), out=aligned.normals)
     if scans.viewpoints is not None and aligned.viewpoints is not None:                 # only `align(..., visibility=)` gives `aligned` any
-        ops.transform_points(scans.viewpoints[:, None, :], None, pose.packed, out=aligned.viewpoints[:, None, :])
+        _move_viewpoints(scans.viewpoints, pose.packed, out=aligned.viewpoints)
     return part
 
 
@@ -1337,7 +1492,7 @@ def align(x, scans, mode="similarity", iters=30, init="moments", trunc=None, w_m
         solved = pose.solved = torch.empty((iters, B), dtype=torch.int32, device=dev)
     visible = None
     if plan.visibility is not None:
-        aligned.viewpoints = ops.transform_points(scans.viewpoints[:, None, :], None, pose.packed)[:, 0]
+        aligned.viewpoints = _move_viewpoints(scans.viewpoints, pose.packed)
         visible = torch.empty((iters, B, n), dtype=torch.uint8, device=dev)
         pose.visible = visible.view(torch.bool)
     for k in range(iters):
