@@ -986,6 +986,12 @@ int run_stream(LSParams& p, const LSPlan& pl, int cols, void* ws, size_t ws_byte
     return SH_OK;
 }
 
+// the stand-alone bias gradient (a dbias the tile kernel cannot store 16 bytes at a time, or the generic kernel's shapes)
+void run_colsum(const float* dy, int M, int N, float* dbias, hipStream_t st) {
+    ShProfScope ps(st, "colsum_kernel|M=%d N=%d", M, N);
+    SH_LAUNCH_PS(ps, colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, dy, M, N, dbias);
+}
+
 }  // namespace
 
 // Measured and not kept (round 3, MI355X, batch 64, 256 x 55 296): the six latent GEMMs in the bf16x3 form of the conv kernels
@@ -1117,7 +1123,7 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
             ShProfScope ps(st, "linear_bwd_wgt_dma_kernel|M=%d N=%d K=%d", M, N, K);
             SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<false>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
         }
-        if (dbias && !s.dbias) hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, dy, M, N, dbias);
+        if (dbias && !s.dbias) run_colsum(dy, M, N, dbias, st);
         SH_CHECK_LAUNCH("linear_bwd_wgt");
         return SH_OK;
     }
@@ -1129,7 +1135,7 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
     const int rc = run_gemm(p, workspace, workspace_bytes, st, "linear_bwd_wgt");
     if (rc != SH_OK) return rc;
     if (dbias) {
-        hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, dy, M, N, dbias);
+        run_colsum(dy, M, N, dbias, st);
         SH_CHECK_LAUNCH("colsum");
     }
     return SH_OK;
@@ -1177,7 +1183,7 @@ int sh_linear_bwd_wgt_adam(const void* dy, int dy_dtype, const void* x, int x_dt
         ShProfScope ps(st, "linear_bwd_wgt_adam_kernel|M=%d N=%d K=%d", M, N, K);
         SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<false, true>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
     }
-    if (dbias && !s.dbias) hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, static_cast<const float*>(dy), M, N, dbias);
+    if (dbias && !s.dbias) run_colsum(static_cast<const float*>(dy), M, N, dbias, st);
     SH_CHECK_LAUNCH("linear_bwd_wgt_adam");
     return SH_OK;
 }
