@@ -245,99 +245,84 @@ void launch_tiles(hipStream_t st, int dtype, const DepthArgs& a, const ViewArgs&
     else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT, VIEWS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel);
 }
 
+// The tile rows of B bodies of `images` images each, in bytes: the workspace of both passes.
+size_t tile_rows_bytes(int B, int images, int H, int W) { return (size_t)B * images * tiles_of(H, W) * sizeof(int32_t); }
+
+// Everything behind the four entry points: the checks, the workspace need, the tiles and - for the count pass - the per-body scan.
+// EMIT: the points pass, which reads counts and the workspace the count pass wrote.  VIEWS: a rig of V images per body with the
+// extrinsics ext and the outputs view and view_first; else one camera: ext, view and view_first are null and V counts as 1.
+template <bool EMIT, bool VIEWS>
+int depth_pass(const char* who, const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+               int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, int32_t* counts, int max_count, int M,
+               void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel, uint8_t* view, int32_t* view_first,
+               sh_stream_t stream) {
+    if (const int rc = VIEWS ? check_views(who, depth, dtype, intr, ext, B, V, H, W, stride) : check_inputs(who, depth, dtype, intr, B, H, W, stride))
+        return rc;
+    SH_REQUIRE(counts && (!EMIT || (points && normals && pixel && (!VIEWS || (view && view_first)))), SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (EMIT) {
+        SH_REQUIRE(M >= 0 && max_count >= 0, SH_ERR_INVALID_ARG, "%s: negative size (M %d, max_count %d)", who, M, max_count);
+        SH_REQUIRE(M >= max_count, SH_ERR_INVALID_ARG, "%s: M = %d rows cannot hold the largest body's %d", who, M, max_count);
+    }
+    if (B == 0 || H == 0 || W == 0) return SH_OK;
+    const int images = VIEWS ? V : 1;
+    const size_t need = tile_rows_bytes(B, images, H, W);
+    if (EMIT) {
+        SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "%s: the workspace of %s is needed (%zu bytes)", who,
+                   VIEWS ? "sh_depth_views_count" : "sh_depth_count", need);
+    } else {
+        SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "%s: the workspace holds the tile rows (%zu bytes needed)", who, need);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
+    int32_t* tile_row = static_cast<int32_t*>(workspace);
+    launch_tiles<EMIT, VIEWS>(st, dtype, a, ViewArgs{ext, V, view, view_first}, B, tile_row, EMIT ? counts : nullptr, M, points, normals, pixel);
+    if (!EMIT) {
+        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, images * a.tiles);
+        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, images * a.tiles, counts);
+    }
+    SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-size_t sh_depth_workspace(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)B * tiles_of(H, W) * sizeof(int32_t);
-}
+size_t sh_depth_workspace(int B, int H, int W) { return B <= 0 || H <= 0 || W <= 0 ? 0 : tile_rows_bytes(B, 1, H, W); }
 
 int sh_depth_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
                    float z_far, float max_step, int drop_isolated, int stride, int32_t* counts, void* workspace, size_t workspace_bytes,
                    sh_stream_t stream) {
-    const int rc = check_inputs("sh_depth_count", depth, dtype, intr, B, H, W, stride);
-    if (rc != SH_OK) return rc;
-    SH_REQUIRE(counts, SH_ERR_INVALID_ARG, "sh_depth_count: null pointer");
-    if (B == 0 || H == 0 || W == 0) return SH_OK;
-    const size_t need = sh_depth_workspace(B, H, W);
-    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_count: the workspace holds the tile rows (%zu bytes needed)", need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
-    int32_t* tile_row = static_cast<int32_t*>(workspace);
-    launch_tiles<false, false>(st, dtype, a, ViewArgs{}, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
-    {
-        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, a.tiles);
-        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, a.tiles, counts);
-    }
-    SH_CHECK_LAUNCH("depth_count");
-    return SH_OK;
+    return depth_pass<false, false>("sh_depth_count", depth, dtype, depth_scale, intr, mask, nullptr, B, 0, H, W, z_near, z_far, max_step, drop_isolated,
+                                    stride, counts, 0, 0, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int sh_depth_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
                     float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts, int max_count, int M,
                     const void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel, sh_stream_t stream) {
-    const int rc = check_inputs("sh_depth_points", depth, dtype, intr, B, H, W, stride);
-    if (rc != SH_OK) return rc;
-    SH_REQUIRE(counts && points && normals && pixel, SH_ERR_INVALID_ARG, "sh_depth_points: null pointer");
-    SH_REQUIRE(M >= 0 && max_count >= 0, SH_ERR_INVALID_ARG, "sh_depth_points: negative size (M %d, max_count %d)", M, max_count);
-    SH_REQUIRE(M >= max_count, SH_ERR_INVALID_ARG, "sh_depth_points: M = %d rows cannot hold the largest body's %d", M, max_count);
-    if (B == 0 || H == 0 || W == 0) return SH_OK;
-    const size_t need = sh_depth_workspace(B, H, W);
-    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_points: the workspace of sh_depth_count is needed (%zu bytes)", need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
-    launch_tiles<true, false>(st, dtype, a, ViewArgs{}, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts, M, points, normals, pixel);
-    SH_CHECK_LAUNCH("depth_points");
-    return SH_OK;
+    return depth_pass<true, false>("sh_depth_points", depth, dtype, depth_scale, intr, mask, nullptr, B, 0, H, W, z_near, z_far, max_step, drop_isolated,
+                                   stride, const_cast<int32_t*>(counts), max_count, M, const_cast<void*>(workspace), workspace_bytes, points, normals,
+                                   pixel, nullptr, nullptr, stream);
 }
 
 size_t sh_depth_views_workspace(int B, int V, int H, int W) {
-    if (B <= 0 || V < 1 || V > SH_DEPTH_MAX_VIEWS || H <= 0 || W <= 0) return 0;
-    return (size_t)B * V * tiles_of(H, W) * sizeof(int32_t);
+    return B <= 0 || V < 1 || V > SH_DEPTH_MAX_VIEWS || H <= 0 || W <= 0 ? 0 : tile_rows_bytes(B, V, H, W);
 }
 
 int sh_depth_views_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
                          int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, int32_t* counts,
                          void* workspace, size_t workspace_bytes, sh_stream_t stream) {
-    const int rc = check_views("sh_depth_views_count", depth, dtype, intr, ext, B, V, H, W, stride);
-    if (rc != SH_OK) return rc;
-    SH_REQUIRE(counts, SH_ERR_INVALID_ARG, "sh_depth_views_count: null pointer");
-    if (B == 0 || H == 0 || W == 0) return SH_OK;
-    const size_t need = sh_depth_views_workspace(B, V, H, W);
-    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "sh_depth_views_count: the workspace holds the tile rows (%zu bytes needed)", need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
-    int32_t* tile_row = static_cast<int32_t*>(workspace);
-    launch_tiles<false, true>(st, dtype, a, ViewArgs{ext, V, nullptr, nullptr}, B, tile_row, nullptr, 0, nullptr, nullptr, nullptr);
-    {
-        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, V * a.tiles);
-        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, V * a.tiles, counts);
-    }
-    SH_CHECK_LAUNCH("depth_views_count");
-    return SH_OK;
+    return depth_pass<false, true>("sh_depth_views_count", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, max_step, drop_isolated,
+                                   stride, counts, 0, 0, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int sh_depth_views_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
                           int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, const int32_t* counts,
                           int max_count, int M, const void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel,
                           uint8_t* view, int32_t* view_first, sh_stream_t stream) {
-    const int rc = check_views("sh_depth_views_points", depth, dtype, intr, ext, B, V, H, W, stride);
-    if (rc != SH_OK) return rc;
-    SH_REQUIRE(counts && points && normals && pixel && view && view_first, SH_ERR_INVALID_ARG, "sh_depth_views_points: null pointer");
-    SH_REQUIRE(M >= 0 && max_count >= 0, SH_ERR_INVALID_ARG, "sh_depth_views_points: negative size (M %d, max_count %d)", M, max_count);
-    SH_REQUIRE(M >= max_count, SH_ERR_INVALID_ARG, "sh_depth_views_points: M = %d rows cannot hold the largest body's %d", M, max_count);
-    if (B == 0 || H == 0 || W == 0) return SH_OK;
-    const size_t need = sh_depth_views_workspace(B, V, H, W);
-    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE,
-               "sh_depth_views_points: the workspace of sh_depth_views_count is needed (%zu bytes)", need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
-    launch_tiles<true, true>(st, dtype, a, ViewArgs{ext, V, view, view_first}, B, const_cast<int32_t*>(static_cast<const int32_t*>(workspace)), counts,
-                             M, points, normals, pixel);
-    SH_CHECK_LAUNCH("depth_views_points");
-    return SH_OK;
+    return depth_pass<true, true>("sh_depth_views_points", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, max_step, drop_isolated,
+                                  stride, const_cast<int32_t*>(counts), max_count, M, const_cast<void*>(workspace), workspace_bytes, points, normals,
+                                  pixel, view, view_first, stream);
 }
 
 }  // extern "C"

@@ -3,7 +3,9 @@
 // nearest_search_kernel - one vertex per thread in registers, the faces streamed through double-buffered LDS tiles, every lane
 // reading the same LDS address (broadcast) - but it is an any-hit search: a lane that has been hit is done, and a wave whose
 // lanes are all done stops testing.  No atomics, no scratch: the face range may be split into chunks whose flags a second
-// launch ORs, and an OR does not depend on order.
+// launch ORs, and an OR does not depend on order.  One camera and a rig share the face gathering, the fold kernel and the host
+// routine; the two sweeps stay apart: every shared form tried cost one camera 7 - 10 % (DESIGN 4v,
+// profiles/rig_of_one_shared_sweep.json).
 #include "sh_nn.h"
 
 namespace {
@@ -44,7 +46,7 @@ __device__ __forceinline__ void gather_face(const float* __restrict__ xb, const 
 }
 
 // grid (vertex tile, face chunk, body).  final != 0: the one chunk's answer is the answer, flag = vis [B][n], 1 = visible;
-// otherwise flag = the workspace [chunks][B][n], 1 = NOT visible on this chunk's evidence, for visibility_fold_kernel.
+// otherwise flag = the workspace [chunks][B][n], 1 = NOT visible on this chunk's evidence, for visibility_fold_kernel<false>.
 // A face enters LDS as the three records of gather_face, written by the thread that gathered its corners.  A lane is `done` when nothing a face could do would change its answer: beyond n, masked,
 // turned away from the sensor, or already hit.  The inner loop asks the wave every four faces whether any lane is still open;
 // the tile loop asks the workgroup once per tile, through two LDS words per wave written before the tile's one barrier.
@@ -126,16 +128,6 @@ __global__ __launch_bounds__(NT) void vertex_visibility_kernel(const float* __re
     else flag[((long)c * B + b) * n + i] = hidden ? 1 : 0;
 }
 
-// vis[b][i] = 1 unless some chunk says "not visible".  One thread per (body, vertex).
-__global__ __launch_bounds__(256) void visibility_fold_kernel(const unsigned char* __restrict__ part, long per_chunk, int chunks,
-                                                             unsigned char* __restrict__ vis) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= per_chunk) return;
-    unsigned char any = 0;
-    for (int c = 0; c < chunks; ++c) any |= part[(long)c * per_chunk + t];
-    vis[t] = any ? 0 : 1;
-}
-
 // ------------------------------------------------------------------------------------------------ any-view form
 constexpr int VMAX = SH_VISIBILITY_MAX_VIEWS;
 static_assert(VMAX == 32, "one bit of a 32-bit word per view");
@@ -169,7 +161,7 @@ __device__ __forceinline__ uint32_t view_candidates(const float* __restrict__ vi
 // the set bits of `open` (none for a face that names it), reads that view's position from LDS - one 16-byte read, a broadcast
 // where the lanes agree - and forms d, p, det, u, w.  The early exits are the single-view kernel's: a ballot of "any view open"
 // every four faces, the workgroup's through two LDS words per wave.  final != 0: out = seen [B][n] (may be null) and vis is
-// written; otherwise out = the workspace [chunks][B][n], the views this chunk's faces hide, for visibility_views_fold_kernel.
+// written; otherwise out = the workspace [chunks][B][n], the views this chunk's faces hide, for visibility_fold_kernel<true>.
 __global__ __launch_bounds__(NT) void vertex_visibility_views_kernel(const float* __restrict__ x, long x_sb, int n, const int32_t* __restrict__ faces,
                                                                     int nF, const float* __restrict__ tn, const float* __restrict__ view, int V,
                                                                     float cos_g, const unsigned char* __restrict__ mask, long mask_sb, int B,
@@ -254,25 +246,89 @@ __global__ __launch_bounds__(NT) void vertex_visibility_views_kernel(const float
     }
 }
 
-// grid (vertex tile, body).  seen = the candidate views of the vertex (formed again: V dot products) minus what any chunk hides.
-__global__ __launch_bounds__(256) void visibility_views_fold_kernel(const float* __restrict__ x, long x_sb, int n, const float* __restrict__ tn,
-                                                                   const float* __restrict__ view, int V, float cos_g,
-                                                                   const unsigned char* __restrict__ mask, long mask_sb, int B,
-                                                                   const uint32_t* __restrict__ part, int chunks, uint32_t* __restrict__ seen,
-                                                                   unsigned char* __restrict__ vis) {
+// The workspace element of a chunk: one camera - 1 = NOT visible on this chunk's evidence; a rig - the views this chunk's faces hide.
+template <bool RIG> using Part = std::conditional_t<RIG, uint32_t, unsigned char>;
+
+// grid (vertex tile, body).  The OR of the chunks' elements -> vis; for a rig seen (may be null) = the candidate views of the vertex
+// (formed again: V dot products) minus what any chunk hides, and the arguments before `B` are read.
+template <bool RIG>
+__global__ __launch_bounds__(256) void visibility_fold_kernel(const float* __restrict__ x, long x_sb, int n, const float* __restrict__ tn,
+                                                             const float* __restrict__ view, int V, float cos_g,
+                                                             const unsigned char* __restrict__ mask, long mask_sb, int B,
+                                                             const Part<RIG>* __restrict__ part, int chunks, uint32_t* __restrict__ seen,
+                                                             unsigned char* __restrict__ vis) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float* xb = x + (long)b * x_sb;
-    const bool active = !mask || mask[(long)b * mask_sb + i] != 0;
-    uint32_t live;
-    const uint32_t cand = view_candidates(view + 3L * b * V, V, active, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2],
-                                          tn ? tn + ((long)b * n + i) * 3 : nullptr, cos_g, live);
     const long o = (long)b * n + i;
-    uint32_t hits = 0;
+    Part<RIG> hits = 0;
     for (int c = 0; c < chunks; ++c) hits |= part[(long)c * B * n + o];
-    const uint32_t s = cand & ~hits;
-    if (seen) seen[o] = s;
-    vis[o] = (live == 0u ? active : s != 0u) ? 1 : 0;
+    if constexpr (RIG) {
+        const float* xb = x + (long)b * x_sb;
+        const bool active = !mask || mask[(long)b * mask_sb + i] != 0;
+        uint32_t live;
+        const uint32_t cand = view_candidates(view + 3L * b * V, V, active, xb[3L * i], xb[3L * i + 1], xb[3L * i + 2],
+                                              tn ? tn + ((long)b * n + i) * 3 : nullptr, cos_g, live);
+        const uint32_t s = cand & ~hits;
+        if (seen) seen[o] = s;
+        vis[o] = (live == 0u ? active : s != 0u) ? 1 : 0;
+    } else {
+        vis[o] = hits ? 0 : 1;
+    }
+}
+
+// The face split taken for `chunks` (0 = the library's) -> the workspace it needs in bytes, 0 for one chunk: no fold.
+size_t workspace_need(int B, int n, int nF, int chunks, size_t part_bytes, int* c, int* tpc) {
+    *c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, tpc);
+    return *c <= 1 ? 0 : (size_t)*c * B * n * part_bytes;
+}
+
+// Every check and both launches of the two entry points; `who` names the one that was called in every error text.  One camera:
+// RIG = false, V = 0 and seen = nullptr.
+template <bool RIG>
+int vertex_visibility(const char* who, const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view, int V,
+                      float cos_g, const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace, size_t workspace_bytes, uint8_t* vis,
+                      uint32_t* seen, sh_stream_t stream) {
+    SH_REQUIRE(x && view && vis && (faces || nF == 0), SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(!RIG || (V >= 1 && V <= VMAX), SH_ERR_INVALID_ARG, "%s: V = %d views, must lie in [1, %d]", who, V, VMAX);
+    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, n %d, nF %d, chunks %d)", who, B, n, nF,
+               chunks);
+    SH_REQUIRE(!tn || (cos_g >= 0.f && cos_g < 1.f), SH_ERR_INVALID_ARG, "%s: cos_g must lie in [0, 1) (and not be NaN)", who);
+    if (B == 0 || n == 0) return SH_OK;
+    SH_REQUIRE(x_sb >= 3L * n && (!mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
+               "%s: batch stride shorter than a body (x_sb %ld, mask_sb %ld)", who, (long)x_sb, (long)mask_sb);
+    SH_REQUIRE(B <= 65535 && (long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "%s: B, B*n or nF too large", who);
+    int c, tpc;
+    const size_t need = workspace_need(B, n, nF, chunks, sizeof(Part<RIG>), &c, &tpc);
+    SH_REQUIRE(c <= 65535, SH_ERR_UNSUPPORTED, "%s: %d face chunks", who, c);
+    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE, "%s: workspace too small (%zu bytes needed for %d chunks)", who,
+               need, c);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int final = c <= 1;
+    Part<RIG>* part = static_cast<Part<RIG>*>(workspace);
+    const dim3 grid((unsigned)sh_cdiv(n, NT), (unsigned)c, (unsigned)B);
+    if constexpr (RIG) {
+        ShProfScope ps(st, "vertex_visibility_views_kernel|B=%d n=%d nF=%d V=%d chunks=%d", B, n, nF, V, c);
+        SH_LAUNCH_PS(ps, vertex_visibility_views_kernel, grid, dim3(NT), 0, st, x, (long)x_sb, n, faces, nF, tn, view, V, cos_g, mask, (long)mask_sb, B,
+                     tpc, final, final ? seen : part, vis);
+    } else {
+        ShProfScope ps(st, "vertex_visibility_kernel|B=%d n=%d nF=%d chunks=%d", B, n, nF, c);
+        SH_LAUNCH_PS(ps, vertex_visibility_kernel, grid, dim3(NT), 0, st, x, (long)x_sb, n, faces, nF, tn, view, cos_g, mask, (long)mask_sb, B, tpc,
+                     final, final ? vis : part);
+    }
+    if (!final) {
+        const dim3 fold_grid((unsigned)sh_cdiv(n, 256), (unsigned)B);
+        if constexpr (RIG) {
+            ShProfScope ps(st, "visibility_views_fold_kernel|B=%d n=%d V=%d chunks=%d", B, n, V, c);
+            SH_LAUNCH_PS(ps, visibility_fold_kernel<true>, fold_grid, dim3(256), 0, st, x, (long)x_sb, n, tn, view, V, cos_g, mask, (long)mask_sb, B, part,
+                         c, seen, vis);
+        } else {
+            ShProfScope ps(st, "visibility_fold_kernel|B=%d n=%d chunks=%d", B, n, c);
+            SH_LAUNCH_PS(ps, visibility_fold_kernel<false>, fold_grid, dim3(256), 0, st, x, (long)x_sb, n, tn, view, V, cos_g, mask, (long)mask_sb, B, part,
+                         c, seen, vis);
+        }
+    }
+    SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
 }
 
 }  // namespace
@@ -280,85 +336,27 @@ __global__ __launch_bounds__(256) void visibility_views_fold_kernel(const float*
 extern "C" {
 
 size_t sh_vertex_visibility_workspace(int B, int n, int nF, int chunks) {
-    if (B <= 0 || n <= 0 || nF < 0 || chunks < 0) return 0;
-    int tpc;
-    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
-    return c <= 1 ? 0 : (size_t)c * B * n;
+    int c, tpc;
+    return B <= 0 || n <= 0 || nF < 0 || chunks < 0 ? 0 : workspace_need(B, n, nF, chunks, sizeof(Part<false>), &c, &tpc);
 }
 
 int sh_vertex_visibility(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view, float cos_g,
                          const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace, size_t workspace_bytes, uint8_t* vis,
                          sh_stream_t stream) {
-    SH_REQUIRE(x && view && vis && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_vertex_visibility: null pointer");
-    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG, "sh_vertex_visibility: negative size (B %d, n %d, nF %d, chunks %d)",
-               B, n, nF, chunks);
-    SH_REQUIRE(!tn || (cos_g >= 0.f && cos_g < 1.f), SH_ERR_INVALID_ARG, "sh_vertex_visibility: cos_g must lie in [0, 1) (and not be NaN)");
-    if (B == 0 || n == 0) return SH_OK;
-    SH_REQUIRE(x_sb >= 3L * n && (!mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
-               "sh_vertex_visibility: batch stride shorter than a body (x_sb %ld, mask_sb %ld)", (long)x_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "sh_vertex_visibility: B, B*n or nF too large");
-    int tpc;
-    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
-    SH_REQUIRE(c <= 65535, SH_ERR_UNSUPPORTED, "sh_vertex_visibility: %d face chunks", c);
-    const size_t need = c <= 1 ? 0 : (size_t)c * B * n;
-    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
-               "sh_vertex_visibility: workspace too small (%zu bytes needed for %d chunks)", need, c);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int final = c <= 1;
-    unsigned char* flag = final ? vis : static_cast<unsigned char*>(workspace);
-    {
-        ShProfScope ps(st, "vertex_visibility_kernel|B=%d n=%d nF=%d chunks=%d", B, n, nF, c);
-        SH_LAUNCH_PS(ps, vertex_visibility_kernel, dim3((unsigned)sh_cdiv(n, NT), (unsigned)c, (unsigned)B), dim3(NT), 0, st, x, (long)x_sb, n, faces,
-                     nF, tn, view, cos_g, mask, (long)mask_sb, B, tpc, final, flag);
-    }
-    if (!final) {
-        ShProfScope ps(st, "visibility_fold_kernel|B=%d n=%d chunks=%d", B, n, c);
-        SH_LAUNCH_PS(ps, visibility_fold_kernel, dim3((unsigned)(((long)B * n + 255) / 256)), dim3(256), 0, st, flag, (long)B * n, c, vis);
-    }
-    SH_CHECK_LAUNCH("vertex_visibility");
-    return SH_OK;
+    return vertex_visibility<false>("sh_vertex_visibility", x, x_sb, n, faces, nF, tn, view, 0, cos_g, mask, mask_sb, B, chunks, workspace,
+                                    workspace_bytes, vis, nullptr, stream);
 }
 
 size_t sh_vertex_visibility_views_workspace(int B, int n, int nF, int V, int chunks) {
-    if (B <= 0 || n <= 0 || nF < 0 || V < 1 || V > VMAX || chunks < 0) return 0;
-    int tpc;
-    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
-    return c <= 1 ? 0 : (size_t)c * B * n * sizeof(uint32_t);
+    int c, tpc;
+    return B <= 0 || n <= 0 || nF < 0 || V < 1 || V > VMAX || chunks < 0 ? 0 : workspace_need(B, n, nF, chunks, sizeof(Part<true>), &c, &tpc);
 }
 
 int sh_vertex_visibility_views(const float* x, int64_t x_sb, int n, const int32_t* faces, int nF, const float* tn, const float* view, int V,
                                float cos_g, const uint8_t* mask, int64_t mask_sb, int B, int chunks, void* workspace, size_t workspace_bytes,
                                uint8_t* vis, uint32_t* seen, sh_stream_t stream) {
-    SH_REQUIRE(x && view && vis && (faces || nF == 0), SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: null pointer");
-    SH_REQUIRE(V >= 1 && V <= VMAX, SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: V = %d views, must lie in [1, %d]", V, VMAX);
-    SH_REQUIRE(B >= 0 && n >= 0 && nF >= 0 && chunks >= 0, SH_ERR_INVALID_ARG,
-               "sh_vertex_visibility_views: negative size (B %d, n %d, nF %d, chunks %d)", B, n, nF, chunks);
-    SH_REQUIRE(!tn || (cos_g >= 0.f && cos_g < 1.f), SH_ERR_INVALID_ARG, "sh_vertex_visibility_views: cos_g must lie in [0, 1) (and not be NaN)");
-    if (B == 0 || n == 0) return SH_OK;
-    SH_REQUIRE(x_sb >= 3L * n && (!mask || mask_sb == 0 || mask_sb >= n), SH_ERR_INVALID_ARG,
-               "sh_vertex_visibility_views: batch stride shorter than a body (x_sb %ld, mask_sb %ld)", (long)x_sb, (long)mask_sb);
-    SH_REQUIRE(B <= 65535 && (long)B * n < (1L << 30) && nF < (1 << 29), SH_ERR_UNSUPPORTED, "sh_vertex_visibility_views: B, B*n or nF too large");
-    int tpc;
-    const int c = nn_resolve_chunks(B, n, nF, TF, NT, chunks, &tpc);
-    SH_REQUIRE(c <= 65535, SH_ERR_UNSUPPORTED, "sh_vertex_visibility_views: %d face chunks", c);
-    const size_t need = c <= 1 ? 0 : (size_t)c * B * n * sizeof(uint32_t);
-    SH_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), SH_ERR_WORKSPACE,
-               "sh_vertex_visibility_views: workspace too small (%zu bytes needed for %d chunks)", need, c);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int final = c <= 1;
-    uint32_t* part = static_cast<uint32_t*>(workspace);
-    {
-        ShProfScope ps(st, "vertex_visibility_views_kernel|B=%d n=%d nF=%d V=%d chunks=%d", B, n, nF, V, c);
-        SH_LAUNCH_PS(ps, vertex_visibility_views_kernel, dim3((unsigned)sh_cdiv(n, NT), (unsigned)c, (unsigned)B), dim3(NT), 0, st, x, (long)x_sb, n,
-                     faces, nF, tn, view, V, cos_g, mask, (long)mask_sb, B, tpc, final, final ? seen : part, vis);
-    }
-    if (!final) {
-        ShProfScope ps(st, "visibility_views_fold_kernel|B=%d n=%d V=%d chunks=%d", B, n, V, c);
-        SH_LAUNCH_PS(ps, visibility_views_fold_kernel, dim3((unsigned)sh_cdiv(n, 256), (unsigned)B), dim3(256), 0, st, x, (long)x_sb, n, tn, view, V,
-                     cos_g, mask, (long)mask_sb, B, part, c, seen, vis);
-    }
-    SH_CHECK_LAUNCH("vertex_visibility_views");
-    return SH_OK;
+    return vertex_visibility<true>("sh_vertex_visibility_views", x, x_sb, n, faces, nF, tn, view, V, cos_g, mask, mask_sb, B, chunks, workspace,
+                                   workspace_bytes, vis, seen, stream);
 }
 
 }  // extern "C"

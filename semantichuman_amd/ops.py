@@ -525,105 +525,138 @@ def cloud_normals(s, count=None, k=16, view=None, out=None):
     return nrm, var, r2, cnt
 
 
+MAX_VIEWS = 32                                                  # SH_VISIBILITY_MAX_VIEWS, SH_DEPTH_MAX_VIEWS
+
+
+def _visibility(who, rig, x, faces, n, view, v_mask, tn, cos_g, chunks, out, seen=False):
+    """`vertex_visibility` and `vertex_visibility_views` behind one set of checks.  rig False: view must be [B, 3], sh_vertex_visibility
+    is called; rig True: view must be [B, V, 3], sh_vertex_visibility_views is called and can return the per-view bits.  who: the
+    public name, for the messages only."""
+    B, rows, x_sb = _points(x, who)
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("%s: n = %d exceeds the model's %d rows" % (who, n, rows))
+    nF = _face_table_arg(faces, who)
+    if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous() and view.dim() == (3 if rig else 2)
+            and view.shape[0] == B and view.shape[-1] == 3):
+        raise ValueError("%s: view must be a contiguous fp32 HIP tensor [%d, %s3], got %s" % (who, B, "V, " if rig else "", tuple(getattr(view, "shape", ()))))
+    V = view.shape[1] if rig else 0
+    if rig and not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    if tn is not None and not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous()
+                               and tuple(tn.shape) == (B, n, 3)):
+        raise ValueError("%s: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (who, B, n))
+    mask, mask_sb = _mask_arg(v_mask, B, n, x.device)
+    chunks = int(chunks)
+    if chunks < 0:
+        raise ValueError("%s: chunks must be >= 0" % who)
+    lib = _lib.load()
+    vis = out if out is not None else torch.empty((B, n), dtype=torch.uint8, device=x.device)
+    if not (torch.is_tensor(vis) and vis.device == x.device and vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (B, n)):
+        raise ValueError("%s: out must be a contiguous uint8 tensor [%d, %d] on the device of x" % (who, B, n))
+    nbytes = lib.sh_vertex_visibility_views_workspace(B, n, nF, V, chunks) if rig else lib.sh_vertex_visibility_workspace(B, n, nF, chunks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    head, tail = (ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view)), (float(cos_g), ptr(mask), mask_sb, B, chunks, ptr(ws), nbytes, ptr(vis))
+    if not rig:
+        check(lib.sh_vertex_visibility(*head, *tail, stream_ptr()), "sh_vertex_visibility")
+        return vis
+    bits = torch.empty((B, n), dtype=torch.int32, device=x.device) if seen else None
+    check(lib.sh_vertex_visibility_views(*head, V, *tail, ptr(bits), stream_ptr()), "sh_vertex_visibility_views")
+    return (vis, bits) if seen else vis
+
+
 def vertex_visibility(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks=0, out=None):
     """sh_vertex_visibility: x [B, *, 3] of which the first n rows are vertices, faces int32 HIP [nF, 3], view fp32 HIP [B, 3]
     (a NaN row: no viewpoint, every active vertex visible) -> uint8 [B, n], 1 = the vertex is active, not occluded by any face
     that does not name it and - with tn, contiguous fp32 [B, n, 3] vertex normals - faces the sensor to within cos_g.  v_mask
     [n] or [B, n].  chunks: 0 = the library's split of the face range, k = that many ranges; every split gives the same bits."""
-    B, rows, x_sb = _points(x, "vertex_visibility")
-    n = int(n)
-    if not 0 <= n <= rows:
-        raise ValueError("vertex_visibility: n = %d exceeds the model's %d rows" % (n, rows))
-    nF = _face_table_arg(faces, "vertex_visibility")
-    if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous() and tuple(view.shape) == (B, 3)):
-        raise ValueError("vertex_visibility: view must be a contiguous fp32 HIP tensor [%d, 3], got %s" % (B, tuple(getattr(view, "shape", ()))))
-    if tn is not None and not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous()
-                               and tuple(tn.shape) == (B, n, 3)):
-        raise ValueError("vertex_visibility: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (B, n))
-    mask, mask_sb = _mask_arg(v_mask, B, n, x.device)
-    chunks = int(chunks)
-    if chunks < 0:
-        raise ValueError("vertex_visibility: chunks must be >= 0")
-    lib = _lib.load()
-    vis = out if out is not None else torch.empty((B, n), dtype=torch.uint8, device=x.device)
-    if not (torch.is_tensor(vis) and vis.device == x.device and vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (B, n)):
-        raise ValueError("vertex_visibility: out must be a contiguous uint8 tensor [%d, %d] on the device of x" % (B, n))
-    nbytes = lib.sh_vertex_visibility_workspace(B, n, nF, chunks)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    check(lib.sh_vertex_visibility(ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view), float(cos_g), ptr(mask), mask_sb, B, chunks, ptr(ws),
-                                   nbytes, ptr(vis), stream_ptr()), "sh_vertex_visibility")
-    return vis
-
-
-MAX_VIEWS = 32                                                  # SH_VISIBILITY_MAX_VIEWS, SH_DEPTH_MAX_VIEWS
+    return _visibility("vertex_visibility", False, x, faces, n, view, v_mask, tn, cos_g, chunks, out)
 
 
 def vertex_visibility_views(x, faces, n, view, v_mask=None, tn=None, cos_g=0.0, chunks=0, out=None, seen=False):
     """sh_vertex_visibility_views: `vertex_visibility` for a rig, view fp32 HIP [B, V, 3] with 1 <= V <= 32 (a NaN row: an absent
     camera; all rows NaN: a full scan) -> uint8 [B, n], 1 = some view sees the vertex; with seen=True -> (that, uint32 [B, n]
     carried as int32: bit v = view v alone sees it).  Every other argument as there."""
-    B, rows, x_sb = _points(x, "vertex_visibility_views")
-    n = int(n)
-    if not 0 <= n <= rows:
-        raise ValueError("vertex_visibility_views: n = %d exceeds the model's %d rows" % (n, rows))
-    nF = _face_table_arg(faces, "vertex_visibility_views")
-    if not (torch.is_tensor(view) and view.is_cuda and view.dtype == torch.float32 and view.is_contiguous() and view.dim() == 3
-            and view.shape[0] == B and view.shape[2] == 3):
-        raise ValueError("vertex_visibility_views: view must be a contiguous fp32 HIP tensor [%d, V, 3], got %s" % (B, tuple(getattr(view, "shape", ()))))
-    V = view.shape[1]
-    if not 1 <= V <= MAX_VIEWS:
-        raise ValueError("vertex_visibility_views: V = %d views, must lie in [1, %d]" % (V, MAX_VIEWS))
-    if tn is not None and not (torch.is_tensor(tn) and tn.is_cuda and tn.dtype == torch.float32 and tn.is_contiguous()
-                               and tuple(tn.shape) == (B, n, 3)):
-        raise ValueError("vertex_visibility_views: tn must be a contiguous fp32 HIP tensor [%d, %d, 3]" % (B, n))
-    mask, mask_sb = _mask_arg(v_mask, B, n, x.device)
-    chunks = int(chunks)
-    if chunks < 0:
-        raise ValueError("vertex_visibility_views: chunks must be >= 0")
-    lib = _lib.load()
-    vis = out if out is not None else torch.empty((B, n), dtype=torch.uint8, device=x.device)
-    if not (torch.is_tensor(vis) and vis.device == x.device and vis.dtype == torch.uint8 and vis.is_contiguous() and tuple(vis.shape) == (B, n)):
-        raise ValueError("vertex_visibility_views: out must be a contiguous uint8 tensor [%d, %d] on the device of x" % (B, n))
-    bits = torch.empty((B, n), dtype=torch.int32, device=x.device) if seen else None
-    nbytes = lib.sh_vertex_visibility_views_workspace(B, n, nF, V, chunks)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    check(lib.sh_vertex_visibility_views(ptr(x), x_sb, n, ptr(faces), nF, ptr(tn), ptr(view), V, float(cos_g), ptr(mask), mask_sb, B, chunks,
-                                         ptr(ws), nbytes, ptr(vis), ptr(bits), stream_ptr()), "sh_vertex_visibility_views")
-    return (vis, bits) if seen else vis
+    return _visibility("vertex_visibility_views", True, x, faces, n, view, v_mask, tn, cos_g, chunks, out, seen)
 
 
 DEPTH_DTYPES ={torch.float32: 0, torch.int16: 1}               # enum sh_depth_dtype: 16-bit words travel as int16 and are read unsigned
 
 
-def _depth_args(who, depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
-    """The inputs sh_depth_count and sh_depth_points share, checked -> (B, H, W, their C arguments up to `stride`)."""
-    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in DEPTH_DTYPES and depth.dim() == 3 and depth.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.%s needs a contiguous fp32 or 16-bit HIP depth image [B, H, W] (got %s %s %s); there is no "
-                           "CPU path" % (who, getattr(depth, "device", None), getattr(depth, "dtype", type(depth)), tuple(getattr(depth, "shape", ()))))
-    B, H, W = depth.shape
-    if not (torch.is_tensor(intr) and intr.device == depth.device and intr.dtype == torch.float32 and intr.is_contiguous() and tuple(intr.shape) == (B, 4)):
-        raise ValueError("%s: intr must be a contiguous fp32 tensor [%d, 4] = (fx, fy, cx, cy) on the depth's device" % (who, B))
+def _depth_args(who, rig, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
+    """The inputs the depth entry points share, checked -> (B, V, H, W, their C arguments up to `stride`).  rig True: a rig's depth
+    [B, V, H, W] with ext [B, V, 12]; rig False: one camera's [B, H, W] - then V = 0 and ext is neither read nor among the arguments.
+    who: the public name, for the messages only."""
+    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in DEPTH_DTYPES and depth.dim() == (4 if rig else 3) and depth.is_contiguous()):
+        raise RuntimeError("semantichuman_amd.%s needs a contiguous fp32 or 16-bit HIP depth image [B, %sH, W] (got %s %s %s); there is no CPU path"
+                           % (who, "V, " if rig else "", getattr(depth, "device", None), getattr(depth, "dtype", type(depth)),
+                              tuple(getattr(depth, "shape", ()))))
+    lead, (H, W) = tuple(depth.shape[:-2]), depth.shape[-2:]
+    B, V = lead[0], lead[1] if rig else 0
+    if rig and not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    for t, shape, what in ((intr, lead + (4,), "intr"), (ext, lead + (12,), "ext"))[:1 + rig]:
+        if not (torch.is_tensor(t) and t.device == depth.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+            if not rig:
+                raise ValueError("%s: intr must be a contiguous fp32 tensor [%d, 4] = (fx, fy, cx, cy) on the depth's device" % (who, B))
+            raise ValueError("%s: %s %s = %s must be a contiguous fp32 tensor on the depth's device"
+                             % (who, what, list(shape), "(fx, fy, cx, cy)" if t is intr else "(R row-major, t)"))
     if mask is not None and not (torch.is_tensor(mask) and mask.device == depth.device and mask.dtype == torch.uint8 and mask.is_contiguous()
                                  and mask.shape == depth.shape):
         raise ValueError("%s: mask must be a contiguous uint8 tensor %s on the depth's device" % (who, tuple(depth.shape)))
     stride = int(stride)
     if stride < 1:
         raise ValueError("%s: stride = %d, must be at least 1" % (who, stride))
-    return B, H, W, (ptr(depth), DEPTH_DTYPES[depth.dtype], float(depth_scale), ptr(intr), ptr(mask), B, H, W, float(z_near), float(z_far),
-                     float(max_step), int(bool(drop_isolated)), stride)
+    return B, V, H, W, ((ptr(depth), DEPTH_DTYPES[depth.dtype], float(depth_scale), ptr(intr), ptr(mask)) + ((ptr(ext), B, V) if rig else (B,))
+                        + (H, W, float(z_near), float(z_far), float(max_step), int(bool(drop_isolated)), stride))
+
+
+def _depth_workspace(lib, B, V, H, W):
+    """Bytes of the tile rows the count pass leaves for the points pass; V = 0: one camera."""
+    return lib.sh_depth_views_workspace(B, V, H, W) if V else lib.sh_depth_workspace(B, H, W)
+
+
+def _depth_count(who, rig, depth, *args):
+    """`depth_count` and `depth_views_count` (rig): args as `_depth_args` takes them after depth."""
+    B, V, H, W, cargs = _depth_args(who, rig, depth, *args)
+    lib = _lib.load()
+    counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
+    nbytes = _depth_workspace(lib, B, V, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
+    entry = lib.sh_depth_views_count if rig else lib.sh_depth_count
+    check(entry(*cargs, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_" + who)
+    return counts, ws
+
+
+def _depth_points(who, rig, counts, workspace, M, max_count, depth, *args):
+    """`depth_points` and `depth_views_points` (rig): args as `_depth_args` takes them after depth; a rig's view and view_first are
+    appended to the outputs."""
+    B, V, H, W, cargs = _depth_args(who, rig, depth, *args)
+    M, max_count = int(M), int(max_count)
+    counted = "depth_views_count" if rig else "depth_count"
+    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise ValueError("%s: counts must be the int32 tensor [%d] of %s" % (who, B, counted))
+    lib = _lib.load()
+    nbytes = _depth_workspace(lib, B, V, H, W)
+    if not (torch.is_tensor(workspace) and workspace.device == depth.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+            and workspace.numel() >= nbytes):
+        raise ValueError("%s: workspace must be the one %s returned for %s (%d bytes)"
+                         % (who, counted, "these images" if rig else "this image", nbytes))
+    points = torch.empty((B, max(M, 0), 3), dtype=torch.float32, device=depth.device)
+    outs = (points, torch.empty_like(points), torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device))
+    if rig:
+        outs += (torch.empty((B, max(M, 0)), dtype=torch.uint8, device=depth.device), torch.empty((B, V + 1), dtype=torch.int32, device=depth.device))
+    entry = lib.sh_depth_views_points if rig else lib.sh_depth_points
+    check(entry(*cargs, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), *[ptr(t) for t in outs], stream_ptr()), "sh_" + who)
+    return outs
 
 
 def depth_count(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False, stride=1):
     """sh_depth_count: depth [B, H, W] fp32 or 16-bit words on the device, intr fp32 [B, 4] = (fx, fy, cx, cy), mask uint8
     [B, H, W] or None -> (counts int32 [B], the kept pixels per body; the workspace sh_depth_points reads, the first row of every
     16 x 16 tile).  Nothing is synchronised."""
-    B, H, W, args = _depth_args("depth_count", depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
-    lib = _lib.load()
-    counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
-    nbytes = lib.sh_depth_workspace(B, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
-    check(lib.sh_depth_count(*args, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_depth_count")
-    return counts, ws
+    return _depth_count("depth_count", False, depth, intr, None, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
 
 
 def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf,
@@ -631,43 +664,8 @@ def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_
     """sh_depth_points: the inputs and options of the `depth_count` call that made (counts, workspace), a width M and the largest
     count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the camera's frame, normals fp32 [B, M, 3] - a
     zero row: unknown -, pixel int32 [B, M] = v * W + u), rows in tile / Z-order; beyond a body's count zeros, zeros and -1."""
-    B, H, W, args = _depth_args("depth_points", depth, intr, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
-    M, max_count = int(M), int(max_count)
-    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
-            and tuple(counts.shape) == (B,)):
-        raise ValueError("depth_points: counts must be the int32 tensor [%d] of depth_count" % B)
-    lib = _lib.load()
-    nbytes = lib.sh_depth_workspace(B, H, W)
-    if not (torch.is_tensor(workspace) and workspace.device == depth.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-            and workspace.numel() >= nbytes):
-        raise ValueError("depth_points: workspace must be the one depth_count returned for this image (%d bytes)" % nbytes)
-    points = torch.empty((B, max(M, 0), 3), dtype=torch.float32, device=depth.device)
-    normals = torch.empty_like(points)
-    pixel = torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device)
-    check(lib.sh_depth_points(*args, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), ptr(points), ptr(normals), ptr(pixel),
-                              stream_ptr()), "sh_depth_points")
-    return points, normals, pixel
-
-
-def _depth_views_args(who, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride):
-    """The inputs sh_depth_views_count and sh_depth_views_points share, checked -> (B, V, H, W, their C arguments up to `stride`)."""
-    if not (torch.is_tensor(depth) and depth.is_cuda and depth.dtype in DEPTH_DTYPES and depth.dim() == 4 and depth.is_contiguous()):
-        raise RuntimeError("semantichuman_amd.%s needs a contiguous fp32 or 16-bit HIP depth image [B, V, H, W] (got %s %s %s); there is no "
-                           "CPU path" % (who, getattr(depth, "device", None), getattr(depth, "dtype", type(depth)), tuple(getattr(depth, "shape", ()))))
-    B, V, H, W = depth.shape
-    if not 1 <= V <= MAX_VIEWS:
-        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
-    for t, shape, what in ((intr, (B, V, 4), "intr [%d, %d, 4] = (fx, fy, cx, cy)" % (B, V)), (ext, (B, V, 12), "ext [%d, %d, 12] = (R row-major, t)" % (B, V))):
-        if not (torch.is_tensor(t) and t.device == depth.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
-            raise ValueError("%s: %s must be a contiguous fp32 tensor on the depth's device" % (who, what))
-    if mask is not None and not (torch.is_tensor(mask) and mask.device == depth.device and mask.dtype == torch.uint8 and mask.is_contiguous()
-                                 and mask.shape == depth.shape):
-        raise ValueError("%s: mask must be a contiguous uint8 tensor %s on the depth's device" % (who, tuple(depth.shape)))
-    stride = int(stride)
-    if stride < 1:
-        raise ValueError("%s: stride = %d, must be at least 1" % (who, stride))
-    return B, V, H, W, (ptr(depth), DEPTH_DTYPES[depth.dtype], float(depth_scale), ptr(intr), ptr(mask), ptr(ext), B, V, H, W, float(z_near),
-                        float(z_far), float(max_step), int(bool(drop_isolated)), stride)
+    return _depth_points("depth_points", False, counts, workspace, M, max_count, depth, intr, None, mask, depth_scale, z_near, z_far, max_step,
+                         drop_isolated, stride)
 
 
 def depth_views_count(depth, intr, ext, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False,
@@ -675,13 +673,7 @@ def depth_views_count(depth, intr, ext, mask=None, depth_scale=1.0, z_near=-math
     """sh_depth_views_count: depth [B, V, H, W] fp32 or 16-bit words on the device, intr fp32 [B, V, 4], ext fp32 [B, V, 12] (camera ->
     rig, R row-major then t; a NaN row: the view is absent), mask uint8 [B, V, H, W] or None -> (counts int32 [B], the kept pixels
     per body over its views; the workspace sh_depth_views_points reads).  Nothing is synchronised."""
-    B, V, H, W, args = _depth_views_args("depth_views_count", depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
-    lib = _lib.load()
-    counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
-    nbytes = lib.sh_depth_views_workspace(B, V, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
-    check(lib.sh_depth_views_count(*args, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_depth_views_count")
-    return counts, ws
+    return _depth_count("depth_views_count", True, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
 
 
 def depth_views_points(depth, intr, ext, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf,
@@ -690,31 +682,15 @@ def depth_views_points(depth, intr, ext, counts, workspace, M, max_count, mask=N
     largest count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the rig's frame, normals fp32 [B, M, 3],
     pixel int32 [B, M] = v * W + u in the row's view, view uint8 [B, M], view_first int32 [B, V + 1]); rows view-major, tile /
     Z-order inside a view; beyond a body's count zeros, zeros, -1 and 255."""
-    B, V, H, W, args = _depth_views_args("depth_views_points", depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
-    M, max_count = int(M), int(max_count)
-    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
-            and tuple(counts.shape) == (B,)):
-        raise ValueError("depth_views_points: counts must be the int32 tensor [%d] of depth_views_count" % B)
-    lib = _lib.load()
-    nbytes = lib.sh_depth_views_workspace(B, V, H, W)
-    if not (torch.is_tensor(workspace) and workspace.device == depth.device and workspace.dtype == torch.uint8 and workspace.is_contiguous()
-            and workspace.numel() >= nbytes):
-        raise ValueError("depth_views_points: workspace must be the one depth_views_count returned for these images (%d bytes)" % nbytes)
-    points = torch.empty((B, max(M, 0), 3), dtype=torch.float32, device=depth.device)
-    normals = torch.empty_like(points)
-    pixel = torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device)
-    view = torch.empty((B, max(M, 0)), dtype=torch.uint8, device=depth.device)
-    view_first = torch.empty((B, V + 1), dtype=torch.int32, device=depth.device)
-    check(lib.sh_depth_views_points(*args, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), ptr(points), ptr(normals), ptr(pixel),
-                                    ptr(view), ptr(view_first), stream_ptr()), "sh_depth_views_points")
-    return points, normals, pixel, view, view_first
+    return _depth_points("depth_views_points", True, counts, workspace, M, max_count, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step,
+                         drop_isolated, stride)
 
 
 def depth_field(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):
     """sh_depth_field: the image inputs of `depth_count` -> (cls uint8 [B, H, W]: 0 empty, 1 unknown, 2 surface; z fp32 [B, H, W],
     the surface depth; nearest int32 [B, H, W], the nearest pixel that is not empty as v * W + u, -1: the image has none).
     Nothing is synchronised."""
-    B, H, W, args = _depth_args("depth_field", depth, intr, mask, depth_scale, z_near, z_far, math.inf, False, 1)
+    B, _, H, W, args = _depth_args("depth_field", False, depth, intr, None, mask, depth_scale, z_near, z_far, math.inf, False, 1)
     lib = _lib.load()
     cls = torch.empty((B, H, W), dtype=torch.uint8, device=depth.device)
     z = torch.empty((B, H, W), dtype=torch.float32, device=depth.device)

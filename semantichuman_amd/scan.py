@@ -267,7 +267,7 @@ class ScanBatch:
                                                                                                        device=device, **options)
             return cls._from_parts(points, counts, host_counts, None, normals, viewpoints=torch.from_numpy(ext[:, :, 9:].copy()).to(points.device),
                                    pixels=pixel, view=view, view_first=view_first)
-        points, normals, pixel, counts, host_counts = _unproject_depth(depth, intrinsics, device=device, **options)
+        points, normals, pixel, counts, host_counts = _depth_rows("unproject_depth", depth, intrinsics, device=device, **options)
         return cls._from_parts(points, counts, host_counts, None, normals,
                                viewpoints=torch.zeros((points.shape[0], 3), dtype=torch.float32, device=points.device), pixels=pixel)
 
@@ -315,6 +315,19 @@ def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
     return ops.cloud_normals(pts, cnt, k, view)
 
 
+def _intrinsics_arg(what, intrinsics, shapes):
+    """(fx, fy, cx, cy) rows as a float64 array whose shape is one of `shapes`, else ValueError."""
+    try:
+        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
+    except (ValueError, TypeError):
+        k = None
+    if k is None or k.shape not in shapes:
+        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as %s or %s, got %s"
+                         % (what, ", ".join(str(list(s)) for s in shapes[:-1]), list(shapes[-1]),
+                            "shape %s" % (k.shape,) if k is not None else type(intrinsics).__name__))
+    return k
+
+
 def _depth_inputs(what, depth, intrinsics, mask, z_range):
     """The checks `unproject_depth` and `DepthField.from_depth` share, nothing moved to the device yet -> (depth [B, H, W] fp32 or
     int16 words, intrinsics float32 numpy [B, 4], mask [B, H, W] or None, near, far)."""
@@ -335,14 +348,7 @@ def _depth_inputs(what, depth, intrinsics, mask, z_range):
     lead = () if d.dim() == 2 else (d.shape[0],)
     d = d.reshape((-1,) + tuple(d.shape[-2:]))
     B = d.shape[0]
-    try:
-        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
-    except (ValueError, TypeError):
-        k = None
-    if k is None or k.shape not in ((4,), (B, 4)):
-        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as [4] or [%d, 4], got %s"
-                         % (what, B, "shape %s" % (k.shape,) if k is not None else type(intrinsics).__name__))
-    k = np.broadcast_to(k.astype(np.float32), (B, 4)).copy()
+    k = np.broadcast_to(_intrinsics_arg(what, intrinsics, ((4,), (B, 4))).astype(np.float32), (B, 4)).copy()
     if not np.isfinite(k).all() or not (k[:, :2] > 0).all():
         raise ValueError("%s: fx and fy must be finite and positive, cx and cy finite" % what)
     m = mask
@@ -370,10 +376,12 @@ def _depth_upload(d, k, m, device):
     return d.to(dev).contiguous(), torch.from_numpy(k).to(dev), None if m is None else (m.to(dev) != 0).to(torch.uint8).contiguous()
 
 
-def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
-    """`unproject_depth`, with the counts as the host read them as a fifth result.  Every ValueError is raised before the device is
-    used."""
-    what = "unproject_depth"
+def _depth_rows(what, depth, intrinsics, ext=None, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
+                device=None):
+    """`unproject_depth` (ext None), with the counts as the host read them as a fifth result - and what `unproject_depth_views`
+    shares with it: `_depth_inputs` and the checks of max_step and stride - every ValueError before the device is used -, then
+    upload, count, read the counts once, points.  ext: a rig's float32 [B, V, 12] - depth, intrinsics and mask then hold an image
+    per row, body-major, and ops.depth_views_points' results come first."""
     d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
     step = math.inf if max_step is None else float(max_step)
     if not step >= 0:
@@ -381,11 +389,17 @@ def _unproject_depth(depth, intrinsics, depth_scale=1.0, mask=None, z_range=None
     if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
         raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
     d, k, m = _depth_upload(d, k, m, device)
+    lead, count, points = (d, k), ops.depth_count, ops.depth_points
+    if ext is not None:
+        rig = tuple(ext.shape[:2])
+        lead = (d.view(rig + tuple(d.shape[-2:])), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device))
+        m = None if m is None else m.view(lead[0].shape)
+        count, points = ops.depth_views_count, ops.depth_views_points
     opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
-    counts, ws = ops.depth_count(d, k, **opts)
+    counts, ws = count(*lead, **opts)
     host_counts = counts.cpu().numpy()                                                  # the one synchronisation
     most = int(host_counts.max())
-    return ops.depth_points(d, k, counts, ws, max(most, 1), most, **opts) + (counts, host_counts)
+    return points(*lead, counts, ws, max(most, 1), most, **opts) + (counts, host_counts)
 
 
 def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
@@ -405,7 +419,7 @@ def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=No
     synchronisation, to read the counts: a packing-time operation.  Deterministic - the same bits for an image alone and inside
     any batch.  Not differentiable.  ValueError for wrong shapes or dtypes, fx / fy not finite and positive, stride < 1 or a
     negative max_step."""
-    return _unproject_depth(depth, intrinsics, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
+    return _depth_rows("unproject_depth", depth, intrinsics, None, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
 
 
 def pack_extrinsics(extrinsics, what="extrinsics"):
@@ -450,33 +464,13 @@ def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=
     if len(shape) != (4 if batched else 3) or shape[:-2] != ((B, V) if batched else (V,)):
         raise ValueError("%s: depth must be %s for extrinsics of %d bodies x %d views, got %s"
                          % (what, "[%d, %d, H, W]" % (B, V) if batched else "[%d, H, W]" % V, B, V, shape))
-    try:
-        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
-    except (ValueError, TypeError):
-        k = None
-    if k is None or k.shape not in ((4,), (V, 4), (B, V, 4)):
-        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as [4], [%d, 4] or [%d, %d, 4], got %s"
-                         % (what, V, B, V, "shape %s" % (k.shape,) if k is not None else type(intrinsics).__name__))
+    k = _intrinsics_arg(what, intrinsics, ((4,), (V, 4), (B, V, 4)))
     flat = lambda a: None if a is None else a.reshape((B * V,) + tuple(a.shape[-2:]))      # noqa: E731 - [B * V, H, W]: an image per row
     if mask is not None and tuple(getattr(mask, "shape", np.shape(mask))) != shape:
         raise ValueError("%s: mask must have the depth's shape %s" % (what, shape))
-    d, k, m, near, far = _depth_inputs(what, flat(depth if torch.is_tensor(depth) else np.asarray(depth)),
-                                       np.broadcast_to(k, (B, V, 4)).reshape(B * V, 4),
-                                       flat(mask if mask is None or torch.is_tensor(mask) else np.asarray(mask)), z_range)
-    step = math.inf if max_step is None else float(max_step)
-    if not step >= 0:
-        raise ValueError("%s: max_step must be None or >= 0, got %r" % (what, max_step))
-    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-        raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
-    d, k, m = _depth_upload(d, k, m, device)
-    H, W = d.shape[-2:]
-    d, k, m = d.view(B, V, H, W), k.view(B, V, 4), None if m is None else m.view(B, V, H, W)
-    e = torch.from_numpy(ext).to(d.device)
-    opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
-    counts, ws = ops.depth_views_count(d, k, e, **opts)
-    host_counts = counts.cpu().numpy()                                                  # the one synchronisation
-    most = int(host_counts.max())
-    return ops.depth_views_points(d, k, e, counts, ws, max(most, 1), most, **opts) + (counts, host_counts, ext)
+    return _depth_rows(what, flat(depth if torch.is_tensor(depth) else np.asarray(depth)), np.broadcast_to(k, (B, V, 4)).reshape(B * V, 4), ext,
+                       depth_scale, flat(mask if mask is None or torch.is_tensor(mask) else np.asarray(mask)), z_range, max_step, drop_isolated,
+                       stride, device) + (ext,)
 
 
 def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
@@ -643,11 +637,11 @@ def _view_arg(what, viewpoints, B, device, rig=False):
 def _visibility(x, ft, view, v_mask, tn, cos_g, chunks=0, out=None, seen=False):
     """The one place that picks the visibility kernel by the viewpoints' rank: [B, 3] -> sh_vertex_visibility (launches and bits as
     ever), [B, V, 3] -> sh_vertex_visibility_views.  seen=True (a rig only): (vis, the per-view bits)."""
-    if view.dim() == 3:
-        return ops.vertex_visibility_views(x, ft.faces, ft.n, view, v_mask, tn, cos_g, chunks=chunks, out=out, seen=seen)
-    if seen:
+    if seen and view.dim() != 3:
         raise ValueError("visible_vertices: return_seen needs rig viewpoints [B, V, 3], got [B, 3]")
-    return ops.vertex_visibility(x, ft.faces, ft.n, view, v_mask, tn, cos_g, chunks=chunks, out=out)
+    rig = view.dim() == 3
+    return ops._visibility("vertex_visibility_views" if rig else "vertex_visibility", rig, x, ft.faces, ft.n, view, v_mask, tn, cos_g, chunks,
+                           out, seen)
 
 
 def _move_viewpoints(view, packed, out=None):

@@ -167,6 +167,75 @@ def test_absent_cameras():
         assert np.array_equal(seen[2], full[1][2] & np.uint32(1)) and np.array_equal(vis[2], seen[2] != 0) and not vis[2][mask[2]].all()
 
 
+@functools.lru_cache(maxsize=None)
+def barrel():
+    """Two bodies of 300 vertices - two vertex tiles of 256, the second partial - under 600 faces - three LDS tiles of 256, the last
+    partial: 15 rings of 20 on a barrel, its two caps as fans, four wall faces once more with the other winding.  With three
+    viewpoints per body and a vertex mask."""
+    rings, seg = 15, 20
+    t, a = np.linspace(-1.0, 1.0, rings), 2 * np.pi * np.arange(seg) / seg
+    r = 1.0 - 0.35 * t ** 2
+    v = np.stack([np.outer(r, np.cos(a)), np.outer(r, np.sin(a)), np.repeat(t[:, None], seg, 1)], -1).reshape(-1, 3)
+    i = (np.arange(rings - 1)[:, None] * seg + np.arange(seg)[None]).ravel()
+    j = (np.arange(rings - 1)[:, None] * seg + (np.arange(seg)[None] + 1) % seg).ravel()
+    wall = np.concatenate([np.stack([i, j, j + seg], -1), np.stack([i, j + seg, i + seg], -1)])
+    k = np.arange(1, seg - 1)
+    caps = np.concatenate([np.stack([0 * k, k + 1, k], -1), (rings - 1) * seg + np.stack([0 * k, k, k + 1], -1)])
+    f = np.concatenate([wall, caps, wall[:4, ::-1]]).astype(np.int64)
+    assert v.shape == (300, 3) and f.shape == (600, 3)
+    x = np.stack([v, v * np.array([1.2, 0.8, 1.1])]).astype(np.float32)
+    views = np.stack([viewpoints(x[b], 3 + b)[b:b + 3] for b in range(2)])
+    mask = np.random.default_rng(5).random((2, 300)) > 0.2
+    return x, f, views, mask
+
+
+def sentinel_run(x, ft, view, mask, tn, cos_g, chunks):
+    """The C entry point of the view's rank - [B, 3] or [B, V, 3] - on outputs and a workspace filled with a sentinel beforehand, so
+    that an element left unwritten shows -> (vis uint8 [B, n], seen uint32 [B, n] - None for [B, 3]) on the host."""
+    lib = _lib.load()
+    B, n, nF = x.shape[0], ft.n, len(ft)
+    vis = torch.full((B, n), 0xAA, dtype=torch.uint8, device=DEV)
+    seen = torch.full((B, n), 0x5A5A5A5A, dtype=torch.int32, device=DEV) if view.dim() == 3 else None
+    head = (ops.ptr(x), x.stride(0), n, ops.ptr(ft.faces), nF, ops.ptr(tn), ops.ptr(view))
+    if seen is None:
+        nbytes = lib.sh_vertex_visibility_workspace(B, n, nF, chunks)
+    else:
+        nbytes = lib.sh_vertex_visibility_views_workspace(B, n, nF, view.shape[1], chunks)
+    ws = torch.full((max(nbytes, 1),), 0xAA, dtype=torch.uint8, device=DEV)
+    tail = (cos_g, ops.ptr(mask), n, B, chunks, ops.ptr(ws), nbytes, ops.ptr(vis))
+    if seen is None:
+        ops.check(lib.sh_vertex_visibility(*head, *tail, ops.stream_ptr()), "sh_vertex_visibility")
+        return vis.cpu().numpy(), None
+    ops.check(lib.sh_vertex_visibility_views(*head, view.shape[1], *tail, ops.ptr(seen), ops.stream_ptr()), "sh_vertex_visibility_views")
+    return vis.cpu().numpy(), seen.cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("chunks", [1, 3])
+def test_partial_tiles_mask_grazing_and_splits_together(chunks):
+    """Two vertex tiles and three face tiles, the last of each partial, two bodies, a vertex mask and a grazing angle, one chunk
+    and three: a rig of one is the single-view kernel bit for bit, an absent view's bit is 0 everywhere, a body without any view
+    is fully visible where active, and every output element is written."""
+    xh, f, views, maskh = barrel()
+    x, ft = dev(xh), scan.FaceTable(f, xh.shape[1], DEV)
+    mask = dev(maskh).to(torch.uint8)
+    tn, cos_g = normals_for(x, ft, 75.0)
+    alone = [sentinel_run(x, ft, dev(views[:, v]), mask, tn, cos_g, chunks)[0] for v in range(3)]
+    for a in alone:
+        assert np.isin(a, (0, 1)).all() and not a[~maskh].any() and 0 < a.sum() < maskh.sum()
+    plain = ops.vertex_visibility(x, ft.faces, ft.n, dev(views[:, 0]), mask).cpu().numpy()
+    assert (plain != alone[0]).any()                                       # the grazing angle matters
+    vis, seen = sentinel_run(x, ft, dev(views[:, :1]), mask, tn, cos_g, chunks)       # a rig of one
+    assert np.array_equal(vis, alone[0]) and np.array_equal(seen, alone[0].astype(np.uint32))
+    holed = views.copy()
+    holed[:, 1] = np.nan                                                   # an absent camera between two live ones
+    holed[1] = np.nan                                                      # and a body with no camera at all
+    vis, seen = sentinel_run(x, ft, dev(holed), mask, tn, cos_g, chunks)
+    assert not bit(seen, 1).any() and (seen >> np.uint32(3) == 0).all() and np.isin(vis, (0, 1)).all()
+    assert np.array_equal(bit(seen[0], 0), alone[0][0] != 0) and np.array_equal(bit(seen[0], 2), alone[2][0] != 0)
+    assert np.array_equal(vis[0] != 0, seen[0] != 0)
+    assert (seen[1] == 0).all() and np.array_equal(vis[1] != 0, maskh[1])
+
+
 def test_view_counts_outside_1_to_32_are_refused():
     x, f, views, _ = batch()
     ft = scan.FaceTable(f, x.shape[1], DEV)
