@@ -468,14 +468,7 @@ int launch_bc(BCParams& p, hipStream_t st) {
     auto kern = conv_bf16_kernel<NT, RT, MODE, BWD, OUTF32>;
     const size_t smem = (size_t)p.nks * NT * 1024;
     static size_t attr_set = 0;                            // dynamic LDS above 64 KiB needs the attribute raised once
-    if (smem > 65536 && smem > attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_bf16: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = 160 * 1024;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_bf16", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.n_vg = sh_cdiv(p.R, RT);
     const long tiles = (long)p.n_vg * sh_cdiv(p.B, 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_bf16: %ld work items", tiles);
@@ -505,14 +498,7 @@ int launch_bcr(BCParams& p, hipStream_t st) {
     auto kern = conv_bf16r_kernel<NT>;
     const size_t smem = (size_t)p.nks * NT * 1024;
     static size_t attr_set = 0;
-    if (smem > 65536 && smem > attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_bf16r: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = 160 * 1024;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_bf16r", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.n_vg = p.R;
     const long tiles = (long)p.R * sh_cdiv(p.B, 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_bf16r: %ld work items", tiles);

@@ -370,14 +370,7 @@ int launch_bd(BDParams& p, hipStream_t st) {
     auto kern = wgrad_bf16_dma_kernel<QT, PT>;
     const size_t smem = (size_t)4 * bd_wave_lds<QT, PT>();
     static bool attr_set = false;
-    if (smem > 65536 && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("wgrad_bf16_dma: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (smem > 65536 && sh_lds_limit(attr_set, smem, "wgrad_bf16_dma", kern) != SH_OK) return SH_ERR_LAUNCH;
     const int grid = p.n_items;
     ShProfScope ps(st, "wgrad_bf16_dma_kernel<%d, %d>|R=%d B=%d S=%d Cin=%d N=%d grid=%d split=%d", QT, PT, p.R, p.B, p.S, p.Cin, p.Cout, grid,
                    p.nsplit);

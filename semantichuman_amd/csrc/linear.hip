@@ -16,6 +16,8 @@
 #include "sh_bf16.h"
 #include "sh_adam.h"
 
+#include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 
 namespace {
@@ -838,14 +840,12 @@ void linear_bwd_wgt_dma_kernel(const LSParams p) {
     }
 }
 
-// plan of the streaming forms: enough items for one wave per SIMD (1024), reduction ranges multiples of 16
-struct LSPlan { bool ok; int range, nsplit, groups; };
-LSPlan plan_stream(int M, int out_cols, int red_len, int gran = 16, bool chunked = false) {   // gran: reduction steps of the kernel (bf16x3 forms: 32)
-    LSPlan pl{false, red_len, 1, out_cols / 64};
-    // chunked: the forward LDS-DMA kernel takes any batch as 64-row chunks (gridDim.y) when the reduction is not split
-    const bool big_ok = chunked && red_len < 1024 && red_len % 32 == 0 && (out_cols / 64) % 4 == 0;
-    if ((M > 64 && !big_ok) || out_cols % 64 != 0 || red_len % gran != 0) return pl;
-    pl.ok = true;
+// ------------------------------------------------------------------------------------------------- host: choose once, then launch
+// reduction ranges of the streaming forms: enough items for one wave per SIMD (1024), ranges multiples of `gran` (the reduction
+// steps of the kernel: 16, bf16x3 forms 32).  The caller has checked out_cols % 64 == 0 and red_len % gran == 0.
+struct LSPlan { int range, nsplit, groups; };
+LSPlan plan_stream(int out_cols, int red_len, int gran) {
+    LSPlan pl{red_len, 1, out_cols / 64};
     constexpr int items = 1024;          // one wave per SIMD
     if (pl.groups < items / 2 && red_len >= 1024) {
         int ns = items / pl.groups;
@@ -856,8 +856,11 @@ LSPlan plan_stream(int M, int out_cols, int red_len, int gran = 16, bool chunked
     }
     return pl;
 }
-bool aligned16(const void* a, const void* b, const void* c) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+// every tensor of a call starts on a 16-byte boundary (an absent one, null, counts as aligned)
+bool aligned16(std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+    return (bits & 15) == 0;
 }
 
 int mode_of(const float* base, long s_row, long s_r, int rows, int R) {
@@ -881,107 +884,169 @@ SGPlan plan_split(int M, int N, int R) {
     return pl;
 }
 
-int run_gemm(SGParams& p, void* ws, size_t ws_bytes, hipStream_t st, const char* what) {
-    const SGPlan pl = plan_split(p.M, p.N, p.R);
-    p.nsplit = pl.nsplit; p.rchunk = pl.rchunk;
+// What one pass runs: decided once per call by choose_fwd / choose_bwd_data / choose_bwd_wgt - plain arithmetic on the shape, the
+// mma_mode and the operands' alignment, no HIP call - and read by the launch code below and by sh_linear_workspace.  Nothing else
+// in this file tests a shape.
+//
+// Measured and not kept (round 3, MI355X, batch 64, 256 x 55 296): the six latent GEMMs in the bf16x3 form of the conv kernels
+// (both fp32 operands split while staged, six bf16 MFMAs per product) took 22.8-32.7 us each against 25.5-33.5 us here - these
+// passes are not bound by the matrix pipe but by how many bytes of the 56.6 MB weight stream a CU keeps in flight.
+enum LinForm { LF_GEMM, LF_FWD_STREAM, LF_FWD_DMA, LF_FWD_X3, LF_FWD_WIDE_X3, LF_BWD_STREAM, LF_BWD_X3, LF_WGT_TILE };
+struct LinChoice {
+    LinForm form;
+    int mt;              // streaming forms: 16-row tiles of the batch a workgroup holds (the kernels' MT)
+    LSPlan ls;           // streaming forms
+    SGPlan sg;           // LF_GEMM
+    int variant;         // LF_WGT_TILE: which instantiation of the tile kernel (run_wgt_tile's table)
+    unsigned gx, gy;     // grid
+    size_t lds;          // dynamic LDS bytes
+    size_t ws_bytes;     // slab of a split reduction (0: none)
+};
+
+// does this call run the bf16x3 kernels?  (mma_mode SH_MMA_SPLIT3 / SH_MMA_PLANES3)
+inline bool lin_x3(int mma_mode) { return mma_mode == SH_MMA_SPLIT3 || mma_mode == SH_MMA_PLANES3; }
+
+// the generic kernel: any shape, any alignment (out = [rows][cols])
+LinChoice choose_gemm(int rows, int cols, int red) {
+    LinChoice c{};
+    c.form = LF_GEMM;
+    c.sg = plan_split(rows, cols, red);
+    c.gx = (unsigned)((long)sh_cdiv(rows, LT) * sh_cdiv(cols, LT) * c.sg.nsplit);
+    c.gy = 1;
+    if (c.sg.nsplit > 1) c.ws_bytes = (size_t)c.sg.nsplit * rows * cols * sizeof(float);
+    return c;
+}
+// a streaming form: four items (64 output columns x one reduction range) per workgroup
+LinChoice choose_stream(LinForm form, int M, int cols, int red, int gran) {
+    LinChoice c{};
+    c.form = form;
+    c.mt = M > 64 ? 4 : sh_cdiv(M, 16);
+    c.ls = plan_stream(cols, red, gran);
+    c.gx = sh_cdiv(c.ls.groups * c.ls.nsplit, 4);
+    c.gy = 1;
+    if (c.ls.nsplit > 1) c.ws_bytes = (size_t)c.ls.nsplit * M * cols * sizeof(float);
+    return c;
+}
+
+// y[M][N]: reduction K.  aligned: x, weight, y and bias
+LinChoice choose_fwd(int M, int N, int K, int mma_mode, bool aligned) {
+    if (!aligned || N % 64 != 0) return choose_gemm(M, N, K);
+    const bool x3 = lin_x3(mma_mode);
+    if (x3 && M > 64 && K % 32 == 0 && K <= 384) {   // large batch, short reduction: the weight tile split once per workgroup
+        LinChoice c{};
+        c.form = LF_FWD_WIDE_X3;
+        c.gx = N / 64; c.gy = 1;
+        c.lds = (size_t)(K / 32) * 4 * 3072;
+        return c;
+    }
+    // the LDS-DMA kernel's shapes: 32-wide stages, four column groups per workgroup.  It also takes any batch as 64-row chunks
+    // (gridDim.y) when the reduction is not split; no other streaming form takes more than 64 rows.
+    const bool dma_shape = K % 32 == 0 && (N / 64) % 4 == 0;
+    if (M > 64 && !(dma_shape && K < 1024)) return choose_gemm(M, N, K);
+    const int gran = x3 && dma_shape ? 32 : 16;      // bf16x3 form: the LDS-DMA kernel's shapes only; anything else keeps fp32 MFMA
+    if (K % gran != 0) return choose_gemm(M, N, K);
+    LinChoice c = choose_stream(LF_FWD_STREAM, M, N, K, gran);
+    // ranges of 16-granular plans may be odd multiples of 16; 32-granular ranges and an unsplit K % 32 == 0 always pass, so a
+    // bf16x3 plan and a plan with M > 64 (K < 1024 is never split) are LDS-DMA plans
+    if (dma_shape && c.ls.range % 32 == 0) {
+        c.form = gran == 32 ? LF_FWD_X3 : LF_FWD_DMA;
+        c.gy = sh_cdiv(M, 64);
+        c.lds = LFD_LDS;
+    }
+    return c;
+}
+
+// dx[M][K]: reduction N.  aligned: dy, weight and dx
+LinChoice choose_bwd_data(int M, int N, int K, int mma_mode, bool aligned) {
+    const bool x3 = lin_x3(mma_mode) && N % 32 == 0;               // a reduction the 32-row steps cannot take keeps fp32 MFMA
+    if (!aligned || M > 64 || K % 64 != 0 || (!x3 && N % 16 != 0)) return choose_gemm(M, K, N);
+    return choose_stream(x3 ? LF_BWD_X3 : LF_BWD_STREAM, M, K, N, x3 ? 32 : 16);
+}
+
+// dW[N][K]: reduction M.  aligned: dy, x and dW (the fused Adam form: its moments and shadow too).  adam / dy16 / x16: the tile
+// kernel applies the update, reads bf16 operands (their products are exact on the fp32 MFMA: no bf16x3 variant)
+LinChoice choose_bwd_wgt(int M, int N, int K, int mma_mode, bool aligned, bool adam = false, bool dy16 = false, bool x16 = false) {
+    if (!aligned || M > 64 || N % 64 != 0 || K % 64 != 0) return choose_gemm(N, K, M);
+    LinChoice c{};
+    c.form = LF_WGT_TILE;
+    c.variant = !adam ? lin_x3(mma_mode) : (dy16 || x16) ? 3 + dy16 + 2 * x16 : 2 + lin_x3(mma_mode);
+    c.gx = (N / 64) * sh_cdiv(K / 64, 4); c.gy = 1;
+    c.lds = LWD_LDS;
+    return c;
+}
+
+void run_split_reduce(const float* slab, int nsplit, int M, int cols, const float* bias, float* out, hipStream_t st) {
+    const long mn = (long)M * cols;
+    ShProfScope ps(st, "split_reduce_kernel");
+    SH_LAUNCH_PS(ps, split_reduce_kernel, dim3((unsigned)((mn + 63) / 64)), dim3(1024), 0, st, slab, nsplit, mn, cols, bias, out);
+}
+
+int run_gemm(const LinChoice& c, SGParams& p, void* ws, size_t ws_bytes, hipStream_t st, const char* what) {
+    p.nsplit = c.sg.nsplit; p.rchunk = c.sg.rchunk;
     p.n_mtiles = sh_cdiv(p.M, LT); p.n_ntiles = sh_cdiv(p.N, LT);
     p.a_mode = mode_of(p.a, p.a_sm, p.a_sr, p.M, p.R);
     p.b_mode = mode_of(p.b, p.b_sn, p.b_sr, p.N, p.R);
     const float* bias = p.bias;
     if (p.nsplit > 1) {
         SH_REQUIRE(p.c_sn == 1 && p.c_sm == p.N, SH_ERR_UNSUPPORTED, "%s: split reduction needs a contiguous output", what);
-        SH_REQUIRE(ws && ws_bytes >= (size_t)p.nsplit * p.M * p.N * sizeof(float), SH_ERR_WORKSPACE, "%s: workspace too small", what);
+        SH_REQUIRE(ws && ws_bytes >= c.ws_bytes, SH_ERR_WORKSPACE, "%s: workspace too small", what);
         p.slab = static_cast<float*>(ws);
         p.bias = nullptr;
     }
-    const long grid = (long)p.n_mtiles * p.n_ntiles * p.nsplit;
     {
         ShProfScope ps(st, "skinny_gemm_kernel|%s M=%d N=%d R=%d split=%d modes=%d%d", what, p.M, p.N, p.R, p.nsplit, p.a_mode, p.b_mode);
-        SH_LAUNCH_PS(ps, skinny_gemm_kernel, dim3((unsigned)grid), dim3(LTHREADS), 0, st, p);
+        SH_LAUNCH_PS(ps, skinny_gemm_kernel, dim3(c.gx), dim3(LTHREADS), 0, st, p);
     }
-    if (p.nsplit > 1) {
-        const long mn = (long)p.M * p.N;
-        ShProfScope ps(st, "split_reduce_kernel");
-        SH_LAUNCH_PS(ps, split_reduce_kernel, dim3((unsigned)((mn + 63) / 64)), dim3(1024), 0, st, p.slab, p.nsplit, mn, p.N,
-                           bias, p.c);
-    }
+    if (p.nsplit > 1) run_split_reduce(p.slab, p.nsplit, p.M, p.N, bias, p.c, st);
     SH_CHECK_LAUNCH(what);
     return SH_OK;
 }
 
-// launches the forward / backward-data streaming kernel (+ the split reduction); `cols` = output columns
-// does this call run the bf16x3 kernels?  (mma_mode SH_MMA_SPLIT3 / SH_MMA_PLANES3)
-inline bool lin_x3(int mma_mode) { return mma_mode == SH_MMA_SPLIT3 || mma_mode == SH_MMA_PLANES3; }
+// a runtime tile count (1 .. 4) as the compile-time constant the streaming kernels are instantiated for
+template <class F>
+void with_mt(int mt, F&& f) {
+    switch (mt) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
 
-template <bool FWD>
-int run_stream(LSParams& p, const LSPlan& pl, int cols, void* ws, size_t ws_bytes, hipStream_t st, const char* what, bool x3 = false) {
-    p.range = pl.range; p.nsplit = pl.nsplit; p.groups = pl.groups;
-    const float* bias = p.bias;
+// the LDS-DMA forward kernels need 120 KiB of dynamic LDS: raise the limit once, for the four tile counts of a form
+template <bool X3>
+int raise_fwd_dma(size_t bytes, const char* what) {
+    static bool raised = false;
+    return sh_lds_limit(raised, bytes, what, linear_fwd_dma_kernel<1, X3>, linear_fwd_dma_kernel<2, X3>, linear_fwd_dma_kernel<3, X3>,
+                        linear_fwd_dma_kernel<4, X3>);
+}
+
+// launches the forward / backward-data streaming kernel of the choice (+ the split reduction); `cols` = output columns
+int run_stream(const LinChoice& c, LSParams& p, int cols, void* ws, size_t ws_bytes, hipStream_t st, const char* what) {
+    static const char* const names[] = {nullptr, "linear_fwd_stream_kernel", "linear_fwd_dma_kernel", "linear_fwd_x3_kernel", nullptr,
+                                        "linear_bwd_data_stream_kernel", "linear_bwd_data_x3_kernel"};       // by LinForm
+    p.range = c.ls.range; p.nsplit = c.ls.nsplit; p.groups = c.ls.groups;
     if (p.nsplit > 1) {
-        SH_REQUIRE(ws && ws_bytes >= (size_t)p.nsplit * p.M * cols * sizeof(float), SH_ERR_WORKSPACE, "%s: workspace too small", what);
+        SH_REQUIRE(ws && ws_bytes >= c.ws_bytes, SH_ERR_WORKSPACE, "%s: workspace too small", what);
         p.slab = static_cast<float*>(ws);
     }
-    const int items = p.groups * p.nsplit, grid = sh_cdiv(items, 4), mchunks = sh_cdiv(p.M, 64), mt = p.M > 64 ? 4 : sh_cdiv(p.M, 16);
-    SH_REQUIRE(mchunks == 1 || (FWD && p.nsplit == 1), SH_ERR_UNSUPPORTED, "%s: more than 64 rows need the unsplit forward form", what);
+    if (c.form == LF_FWD_DMA && raise_fwd_dma<false>(c.lds, what) != SH_OK) return SH_ERR_LAUNCH;
+    if (c.form == LF_FWD_X3 && raise_fwd_dma<true>(c.lds, what) != SH_OK) return SH_ERR_LAUNCH;
     {
-        ShProfScope ps(st, "%s<%d>|M=%d N=%d K=%d split=%d", FWD ? "linear_fwd_stream_kernel" : "linear_bwd_data_stream_kernel", mt, p.M,
-                       p.N, p.K, p.nsplit);
-#define SH_LS_CASE(MTV)                                                                                                   \
-    if (FWD) SH_LAUNCH_PS(ps, linear_fwd_stream_kernel<MTV>, dim3(grid), dim3(LTHREADS), 0, st, p);                     \
-    else SH_LAUNCH_PS(ps, linear_bwd_data_stream_kernel<MTV>, dim3(grid), dim3(LTHREADS), 0, st, p)
-        const bool dma = FWD && p.K % 32 == 0 && p.range % 32 == 0 && p.groups % 4 == 0;
-        SH_REQUIRE(mchunks == 1 || dma, SH_ERR_UNSUPPORTED, "%s: more than 64 rows need the LDS-DMA forward form", what);
-        if (x3 && !FWD) {
-            snprintf(ps.name, sizeof ps.name, "linear_bwd_data_x3_kernel<%d>|M=%d N=%d K=%d split=%d", mt, p.M, p.N, p.K, p.nsplit);
-            if (mt == 1) SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<1>, dim3(grid), dim3(LTHREADS), 0, st, p);
-            else if (mt == 2) SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<2>, dim3(grid), dim3(LTHREADS), 0, st, p);
-            else if (mt == 3) SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<3>, dim3(grid), dim3(LTHREADS), 0, st, p);
-            else SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<4>, dim3(grid), dim3(LTHREADS), 0, st, p);
-        } else if (x3 && dma) {
-            static bool attr3_set = false;
-            if (!attr3_set) {
-                const void* ks[4] = {reinterpret_cast<const void*>(linear_fwd_dma_kernel<1, true>), reinterpret_cast<const void*>(linear_fwd_dma_kernel<2, true>),
-                                     reinterpret_cast<const void*>(linear_fwd_dma_kernel<3, true>), reinterpret_cast<const void*>(linear_fwd_dma_kernel<4, true>)};
-                for (const void* k : ks)
-                    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                        (void)hipGetLastError();
-                        sh_set_error("%s: cannot raise the dynamic LDS limit to %d bytes", what, LFD_LDS);
-                        return SH_ERR_LAUNCH;
-                    }
-                attr3_set = true;
+        ShProfScope ps(st, "%s<%d>|M=%d N=%d K=%d split=%d", names[c.form], c.mt, p.M, p.N, p.K, p.nsplit);
+        const dim3 grid(c.gx, c.gy), block(LTHREADS);
+        with_mt(c.mt, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            switch (c.form) {
+                case LF_FWD_STREAM: SH_LAUNCH_PS(ps, linear_fwd_stream_kernel<MT>, grid, block, c.lds, st, p); break;
+                case LF_FWD_DMA: SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<MT, false>), grid, block, c.lds, st, p); break;
+                case LF_FWD_X3: SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<MT, true>), grid, block, c.lds, st, p); break;
+                case LF_BWD_STREAM: SH_LAUNCH_PS(ps, linear_bwd_data_stream_kernel<MT>, grid, block, c.lds, st, p); break;
+                default: SH_LAUNCH_PS(ps, linear_bwd_data_x3_kernel<MT>, grid, block, c.lds, st, p); break;
             }
-            snprintf(ps.name, sizeof ps.name, "linear_fwd_x3_kernel<%d>|M=%d N=%d K=%d split=%d", mt, p.M, p.N, p.K, p.nsplit);
-            if (mt == 1) SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<1, true>), dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else if (mt == 2) SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<2, true>), dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else if (mt == 3) SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<3, true>), dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else SH_LAUNCH_PS(ps, (linear_fwd_dma_kernel<4, true>), dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-        } else if (dma) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                const void* ks[4] = {reinterpret_cast<const void*>(linear_fwd_dma_kernel<1>), reinterpret_cast<const void*>(linear_fwd_dma_kernel<2>),
-                                     reinterpret_cast<const void*>(linear_fwd_dma_kernel<3>), reinterpret_cast<const void*>(linear_fwd_dma_kernel<4>)};
-                for (const void* k : ks)
-                    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                        (void)hipGetLastError();
-                        sh_set_error("%s: cannot raise the dynamic LDS limit to %d bytes", what, LFD_LDS);
-                        return SH_ERR_LAUNCH;
-                    }
-                attr_set = true;
-            }
-            snprintf(ps.name, sizeof ps.name, "linear_fwd_dma_kernel<%d>|M=%d N=%d K=%d split=%d", mt, p.M, p.N, p.K, p.nsplit);
-            if (mt == 1) SH_LAUNCH_PS(ps, linear_fwd_dma_kernel<1>, dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else if (mt == 2) SH_LAUNCH_PS(ps, linear_fwd_dma_kernel<2>, dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else if (mt == 3) SH_LAUNCH_PS(ps, linear_fwd_dma_kernel<3>, dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-            else SH_LAUNCH_PS(ps, linear_fwd_dma_kernel<4>, dim3(grid, mchunks), dim3(LTHREADS), LFD_LDS, st, p);
-        } else if (mt == 1) { SH_LS_CASE(1); } else if (mt == 2) { SH_LS_CASE(2); } else if (mt == 3) { SH_LS_CASE(3); } else { SH_LS_CASE(4); }
-#undef SH_LS_CASE
+        });
     }
-    if (p.nsplit > 1) {
-        const long mn = (long)p.M * cols;
-        ShProfScope ps(st, "split_reduce_kernel");
-        SH_LAUNCH_PS(ps, split_reduce_kernel, dim3((unsigned)((mn + 63) / 64)), dim3(1024), 0, st, p.slab, p.nsplit, mn, cols, bias,
-                           p.out);
-    }
+    if (p.nsplit > 1) run_split_reduce(p.slab, p.nsplit, p.M, cols, p.bias, p.out, st);
     SH_CHECK_LAUNCH(what);
     return SH_OK;
 }
@@ -992,32 +1057,41 @@ void run_colsum(const float* dy, int M, int N, float* dbias, hipStream_t st) {
     SH_LAUNCH_PS(ps, colsum_kernel, dim3((unsigned)sh_cdiv(N, 256)), dim3(256), 0, st, dy, M, N, dbias);
 }
 
-}  // namespace
+// launches the weight-gradient tile kernel in the variant the choice names: plain, bf16x3, with the Adam update, that in bf16x3,
+// and with the Adam update reading a bf16 dy, a bf16 x, both.  s.dbias is the bias gradient the kernel fuses (16-byte aligned),
+// `dbias` the one asked for: the stand-alone column sum serves the difference.  `operands`: the record's suffix for bf16 operands
+int run_wgt_tile(const LinChoice& c, const LSParams& s, float* dbias, const char* operands, hipStream_t st, const char* what) {
+    using Kernel = void (*)(const LSParams);
+    static const Kernel k[7] = {linear_bwd_wgt_dma_kernel<false>, linear_bwd_wgt_dma_kernel<true>,
+                                linear_bwd_wgt_dma_kernel<false, true>, linear_bwd_wgt_dma_kernel<true, true>,
+                                linear_bwd_wgt_dma_kernel<false, true, true, false>, linear_bwd_wgt_dma_kernel<false, true, false, true>,
+                                linear_bwd_wgt_dma_kernel<false, true, true, true>};
+    static const char* const names[7] = {"linear_bwd_wgt_dma_kernel", "linear_bwd_wgt_x3_kernel", "linear_bwd_wgt_adam_kernel",
+                                         "linear_bwd_wgt_adam_x3_kernel", "linear_bwd_wgt_adam_kernel", "linear_bwd_wgt_adam_kernel",
+                                         "linear_bwd_wgt_adam_kernel"};
+    static bool raised = false;                     // 80 KiB of dynamic LDS: raise the limit once, for every variant
+    if (sh_lds_limit(raised, c.lds, "linear_bwd_wgt", k[0], k[1], k[2], k[3], k[4], k[5], k[6]) != SH_OK) return SH_ERR_LAUNCH;
+    {
+        const Kernel kern = k[c.variant];
+        ShProfScope ps(st, "%s|M=%d N=%d K=%d%s", names[c.variant], s.M, s.N, s.K, operands);
+        SH_LAUNCH_PS(ps, kern, dim3(c.gx), dim3(LTHREADS), c.lds, st, s);
+    }
+    if (dbias && !s.dbias) run_colsum(s.a, s.M, s.N, dbias, st);
+    SH_CHECK_LAUNCH(what);
+    return SH_OK;
+}
 
-// Measured and not kept (round 3, MI355X, batch 64, 256 x 55 296): the six latent GEMMs in the bf16x3 form of the conv kernels
-// (both fp32 operands split while staged, six bf16 MFMAs per product) took 22.8-32.7 us each against 25.5-33.5 us here - these
-// passes are not bound by the matrix pipe but by how many bytes of the 56.6 MB weight stream a CU keeps in flight.
+}  // namespace
 
 extern "C" {
 
 size_t sh_linear_workspace(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     size_t need = 0;
-    {   // streaming forms: forward splits K (output [M][N]), backward-data splits N (output [M][K])
-        for (int gran : {16, 32}) {                                  // fp32 MFMA forms / bf16x3 forms
-            const LSPlan f = plan_stream(M, N, K, gran), d = plan_stream(M, K, N, gran);
-            if (f.ok && f.nsplit > 1 && (size_t)f.nsplit * M * N * sizeof(float) > need) need = (size_t)f.nsplit * M * N * sizeof(float);
-            if (d.ok && d.nsplit > 1 && (size_t)d.nsplit * M * K * sizeof(float) > need) need = (size_t)d.nsplit * M * K * sizeof(float);
-        }
-    }
-    const int dims[3][3] = {{M, N, K}, {M, K, N}, {N, K, M}};      // fwd, bwd_data, bwd_wgt as (rows, cols, reduction)
-    for (auto& d : dims) {
-        const SGPlan pl = plan_split(d[0], d[1], d[2]);
-        if (pl.nsplit > 1) {
-            const size_t b = (size_t)pl.nsplit * d[0] * d[1] * sizeof(float);
-            if (b > need) need = b;
-        }
-    }
+    for (int mode : {SH_MMA_EXACT, SH_MMA_SPLIT3})                   // the two families of lin_x3
+        for (bool aligned : {true, false})
+            need = std::max({need, choose_fwd(M, N, K, mode, aligned).ws_bytes, choose_bwd_data(M, N, K, mode, aligned).ws_bytes,
+                             choose_bwd_wgt(M, N, K, mode, aligned).ws_bytes});
     return need;
 }
 
@@ -1025,84 +1099,44 @@ int sh_linear_fwd(const float* x, const float* weight, const float* bias, float*
                   size_t workspace_bytes, int mma_mode, sh_stream_t stream) {
     SH_REQUIRE(x && weight && y && M > 0 && N > 0 && K > 0, SH_ERR_INVALID_ARG, "sh_linear_fwd: bad argument");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_linear_fwd: unknown mma_mode %d", mma_mode);
-    if (lin_x3(mma_mode) && M > 64 && K % 32 == 0 && K <= 384 && N % 64 == 0 && aligned16(x, weight, y) &&
-        (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0)) {
-        // large batch, short reduction: the weight tile split once per workgroup (linear_fwd_wide_x3_kernel)
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        const size_t smem = (size_t)(K / 32) * 4 * 3072;
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(linear_fwd_wide_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess) {
-                (void)hipGetLastError();
-                sh_set_error("linear_fwd: cannot raise the dynamic LDS limit to %zu bytes", smem);
-                return SH_ERR_LAUNCH;
-            }
-            attr_set = true;
-        }
-        LSParams s{};
-        s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
-        ShProfScope ps(st, "linear_fwd_wide_x3_kernel|M=%d N=%d K=%d", M, N, K);
-        SH_LAUNCH_PS(ps, linear_fwd_wide_x3_kernel, dim3(N / 64), dim3(LFW_WAVES * 64), smem, st, s);
-        SH_CHECK_LAUNCH("linear_fwd_wide");
-        return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LinChoice c = choose_fwd(M, N, K, mma_mode, aligned16({x, weight, y, bias}));
+    if (c.form == LF_GEMM) {
+        SGParams p{};
+        p.a = x; p.a_sm = K; p.a_sr = 1;
+        p.b = weight; p.b_sn = K; p.b_sr = 1;
+        p.c = y; p.c_sm = N; p.c_sn = 1; p.bias = bias;
+        p.M = M; p.N = N; p.R = K;
+        return run_gemm(c, p, workspace, workspace_bytes, st, "linear_fwd");
     }
-    {
-        // bf16x3 form: the LDS-DMA kernel's shapes (32-wide stages, four column groups per workgroup); anything else keeps fp32 MFMA
-        const bool x3 = lin_x3(mma_mode) && K % 32 == 0 && (N / 64) % 4 == 0;
-        const LSPlan pl = plan_stream(M, N, K, x3 ? 32 : 16, M > 64);
-        if (pl.ok && aligned16(x, weight, y) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0)) {
-            LSParams s{};
-            s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
-            return run_stream<true>(s, pl, N, workspace, workspace_bytes, static_cast<hipStream_t>(stream), "linear_fwd", x3);
-        }
-    }
-    SGParams p{};
-    p.a = x; p.a_sm = K; p.a_sr = 1;
-    p.b = weight; p.b_sn = K; p.b_sr = 1;
-    p.c = y; p.c_sm = N; p.c_sn = 1; p.bias = bias;
-    p.M = M; p.N = N; p.R = K;
-    return run_gemm(p, workspace, workspace_bytes, static_cast<hipStream_t>(stream), "linear_fwd");
+    LSParams s{};
+    s.a = x; s.w = weight; s.bias = bias; s.out = y; s.M = M; s.N = N; s.K = K;
+    if (c.form != LF_FWD_WIDE_X3) return run_stream(c, s, N, workspace, workspace_bytes, st, "linear_fwd");
+    static bool raised = false;
+    if (sh_lds_limit(raised, c.lds, "linear_fwd", linear_fwd_wide_x3_kernel) != SH_OK) return SH_ERR_LAUNCH;
+    ShProfScope ps(st, "linear_fwd_wide_x3_kernel|M=%d N=%d K=%d", M, N, K);
+    SH_LAUNCH_PS(ps, linear_fwd_wide_x3_kernel, dim3(c.gx), dim3(LFW_WAVES * 64), c.lds, st, s);
+    SH_CHECK_LAUNCH("linear_fwd_wide");
+    return SH_OK;
 }
 
 int sh_linear_bwd_data(const float* dy, const float* weight, float* dx, int M, int N, int K, void* workspace,
                        size_t workspace_bytes, int mma_mode, sh_stream_t stream) {
     SH_REQUIRE(dy && weight && dx && M > 0 && N > 0 && K > 0, SH_ERR_INVALID_ARG, "sh_linear_bwd_data: bad argument");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_linear_bwd_data: unknown mma_mode %d", mma_mode);
-    {
-        const bool x3 = lin_x3(mma_mode) && N % 32 == 0;
-        const LSPlan pl = plan_stream(M, K, N, x3 ? 32 : 16);
-        if (pl.ok && aligned16(dy, weight, dx)) {
-            LSParams s{};
-            s.a = dy; s.w = weight; s.bias = nullptr; s.out = dx; s.M = M; s.N = N; s.K = K;
-            return run_stream<false>(s, pl, K, workspace, workspace_bytes, static_cast<hipStream_t>(stream), "linear_bwd_data", x3);
-        }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LinChoice c = choose_bwd_data(M, N, K, mma_mode, aligned16({dy, weight, dx}));
+    if (c.form != LF_GEMM) {
+        LSParams s{};
+        s.a = dy; s.w = weight; s.bias = nullptr; s.out = dx; s.M = M; s.N = N; s.K = K;
+        return run_stream(c, s, K, workspace, workspace_bytes, st, "linear_bwd_data");
     }
     SGParams p{};                                   // dx(m,k) = sum_n dy(m,n) W(n,k)
     p.a = dy; p.a_sm = N; p.a_sr = 1;
     p.b = weight; p.b_sn = 1; p.b_sr = K;           // B(k, n) = W[n*K + k]
     p.c = dx; p.c_sm = K; p.c_sn = 1; p.bias = nullptr;
     p.M = M; p.N = K; p.R = N;
-    return run_gemm(p, workspace, workspace_bytes, static_cast<hipStream_t>(stream), "linear_bwd_data");
-}
-
-// the LDS-DMA weight-gradient kernels need 80 KiB of dynamic LDS: raise the limit once
-static bool wgt_dma_attr() {
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (const void* k : {reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<false>), reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<true>),
-                              reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<false, true>), reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<true, true>),
-                              reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<false, true, true, false>),
-                              reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<false, true, false, true>),
-                              reinterpret_cast<const void*>(linear_bwd_wgt_dma_kernel<false, true, true, true>)})
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                (void)hipGetLastError();
-                sh_set_error("linear_bwd_wgt: cannot raise the dynamic LDS limit to %d bytes", LWD_LDS);
-                return false;
-            }
-        attr_set = true;
-    }
-    return true;
+    return run_gemm(c, p, workspace, workspace_bytes, st, "linear_bwd_data");
 }
 
 int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, int M, int N, int K, void* workspace,
@@ -1110,29 +1144,19 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
     SH_REQUIRE(dy && x && dW && M > 0 && N > 0 && K > 0, SH_ERR_INVALID_ARG, "sh_linear_bwd_wgt: bad argument");
     SH_REQUIRE(sh_mma_mode_valid(mma_mode), SH_ERR_INVALID_ARG, "sh_linear_bwd_wgt: unknown mma_mode %d", mma_mode);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (M <= 64 && N % 64 == 0 && K % 64 == 0 && aligned16(dy, x, dW)) {
+    const LinChoice c = choose_bwd_wgt(M, N, K, mma_mode, aligned16({dy, x, dW}));
+    if (c.form == LF_WGT_TILE) {
         LSParams s{};
         s.a = dy; s.w = x; s.out = dW; s.M = M; s.N = N; s.K = K;
-        s.dbias = (dbias && (reinterpret_cast<uintptr_t>(dbias) & 15) == 0) ? dbias : nullptr;      // fused into the tile kernel
-        if (!wgt_dma_attr()) return SH_ERR_LAUNCH;
-        const int wgs = (N / 64) * sh_cdiv(K / 64, 4);
-        if (lin_x3(mma_mode)) {
-            ShProfScope ps(st, "linear_bwd_wgt_x3_kernel|M=%d N=%d K=%d", M, N, K);
-            SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<true>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-        } else {
-            ShProfScope ps(st, "linear_bwd_wgt_dma_kernel|M=%d N=%d K=%d", M, N, K);
-            SH_LAUNCH_PS(ps, linear_bwd_wgt_dma_kernel<false>, dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-        }
-        if (dbias && !s.dbias) run_colsum(dy, M, N, dbias, st);
-        SH_CHECK_LAUNCH("linear_bwd_wgt");
-        return SH_OK;
+        s.dbias = aligned16({dbias}) ? dbias : nullptr;             // fused into the tile kernel
+        return run_wgt_tile(c, s, dbias, "", st, "linear_bwd_wgt");
     }
     SGParams p{};                                   // dW(n,k) = sum_m dy(m,n) x(m,k)
     p.a = dy; p.a_sm = 1; p.a_sr = N;               // A(n, m) = dy[m*N + n]
     p.b = x; p.b_sn = 1; p.b_sr = K;                // B(k, m) = x[m*K + k]
     p.c = dW; p.c_sm = K; p.c_sn = 1; p.bias = nullptr;
     p.M = N; p.N = K; p.R = M;
-    const int rc = run_gemm(p, workspace, workspace_bytes, st, "linear_bwd_wgt");
+    const int rc = run_gemm(c, p, workspace, workspace_bytes, st, "linear_bwd_wgt");
     if (rc != SH_OK) return rc;
     if (dbias) {
         run_colsum(dy, M, N, dbias, st);
@@ -1142,7 +1166,7 @@ int sh_linear_bwd_wgt(const float* dy, const float* x, float* dW, float* dbias, 
 }
 
 int sh_linear_bwd_wgt_adam_ok(int M, int N, int K) {
-    return M > 0 && M <= 64 && N > 0 && K > 0 && N % 64 == 0 && K % 64 == 0;
+    return M > 0 && N > 0 && K > 0 && choose_bwd_wgt(M, N, K, SH_MMA_EXACT, true, true).form == LF_WGT_TILE;
 }
 
 int sh_linear_bwd_wgt_adam(const void* dy, int dy_dtype, const void* x, int x_dtype, float* weight, void* weight_bf16, float* exp_avg,
@@ -1155,37 +1179,23 @@ int sh_linear_bwd_wgt_adam(const void* dy, int dy_dtype, const void* x, int x_dt
                "sh_linear_bwd_wgt_adam: unknown element type");
     SH_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0 && weight_decay >= 0, SH_ERR_INVALID_ARG,
                "sh_linear_bwd_wgt_adam: hyper-parameter out of range");
-    SH_REQUIRE(sh_linear_bwd_wgt_adam_ok(M, N, K) && aligned16(dy, x, weight) && aligned16(exp_avg, exp_avg_sq, weight) &&
-               (reinterpret_cast<uintptr_t>(weight_bf16) & 7) == 0, SH_ERR_UNSUPPORTED,
+    const bool a16 = dy_dtype == SH_DTYPE_BF16, w16 = x_dtype == SH_DTYPE_BF16;
+    const LinChoice c = choose_bwd_wgt(M, N, K, mma_mode, aligned16({dy, x, weight, exp_avg, exp_avg_sq}) &&
+                                       (reinterpret_cast<uintptr_t>(weight_bf16) & 7) == 0, true, a16, w16);
+    SH_REQUIRE(c.form == LF_WGT_TILE, SH_ERR_UNSUPPORTED,
                "sh_linear_bwd_wgt_adam: M=%d N=%d K=%d is not served by the tile kernel (M <= 64, N and K multiples of 64, 16-byte aligned "
                "tensors): use sh_linear_bwd_wgt + sh_adam_step", M, N, K);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!wgt_dma_attr()) return SH_ERR_LAUNCH;
     LSParams s{};
     s.a = static_cast<const float*>(dy); s.w = static_cast<const float*>(x); s.out = weight; s.M = M; s.N = N; s.K = K;
     s.am = exp_avg; s.av = exp_avg_sq; s.shadow = static_cast<__bf16*>(weight_bf16);
     s.ad.lr = lr; s.ad.step = step; s.ad.beta1 = beta1; s.ad.beta2 = beta2;
     s.ad.w1 = (float)(1.0 - beta1); s.ad.b2 = (float)beta2; s.ad.w2 = (float)(1.0 - beta2); s.ad.eps = (float)eps; s.ad.wd = (float)weight_decay;
-    const bool a16 = dy_dtype == SH_DTYPE_BF16, w16 = x_dtype == SH_DTYPE_BF16;
     // the bias gradient is summed from the dy tile in LDS, whatever it was loaded from
-    s.dbias = (dbias && (reinterpret_cast<uintptr_t>(dbias) & 15) == 0) ? dbias : nullptr;
+    s.dbias = aligned16({dbias}) ? dbias : nullptr;
     SH_REQUIRE(!dbias || s.dbias || !a16, SH_ERR_UNSUPPORTED, "sh_linear_bwd_wgt_adam: a bf16 dy needs a 16-byte aligned dbias");
-    const int wgs = (N / 64) * sh_cdiv(K / 64, 4);
-    if (a16 || w16) {                                  // bf16 operands: their products are exact on the fp32 MFMA
-        ShProfScope ps(st, "linear_bwd_wgt_adam_kernel|M=%d N=%d K=%d dy=%s x=%s", M, N, K, a16 ? "bf16" : "f32", w16 ? "bf16" : "f32");
-        if (a16 && w16) SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<false, true, true, true>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-        else if (a16)   SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<false, true, true, false>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-        else            SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<false, true, false, true>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-    } else if (lin_x3(mma_mode)) {
-        ShProfScope ps(st, "linear_bwd_wgt_adam_x3_kernel|M=%d N=%d K=%d", M, N, K);
-        SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<true, true>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-    } else {
-        ShProfScope ps(st, "linear_bwd_wgt_adam_kernel|M=%d N=%d K=%d", M, N, K);
-        SH_LAUNCH_PS(ps, (linear_bwd_wgt_dma_kernel<false, true>), dim3(wgs), dim3(LTHREADS), LWD_LDS, st, s);
-    }
-    if (dbias && !s.dbias) run_colsum(static_cast<const float*>(dy), M, N, dbias, st);
-    SH_CHECK_LAUNCH("linear_bwd_wgt_adam");
-    return SH_OK;
+    char operands[24] = "";
+    if (a16 || w16) snprintf(operands, sizeof operands, " dy=%s x=%s", a16 ? "bf16" : "f32", w16 ? "bf16" : "f32");
+    return run_wgt_tile(c, s, dbias, operands, static_cast<hipStream_t>(stream), "linear_bwd_wgt_adam");
 }
 
 }  // extern "C"

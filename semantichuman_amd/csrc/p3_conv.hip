@@ -995,14 +995,7 @@ int launch_p3s(P3Params& p, hipStream_t st) {
     constexpr int WAVES = 16 / RT;
     const size_t smem = (size_t)2 * P3S_KC * NT * 3072;
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_p3s: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_p3s", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.nsplit = p.nt_tot / NT;
     p.n_vg = sh_cdiv(p.R, RT);
     const long tiles = (long)p.n_vg * (p.B / 16);
@@ -1032,14 +1025,7 @@ int launch_p3(P3Params& p, hipStream_t st) {
     auto kern = conv_p3_kernel<NT, RT, C16, BWD, NP, F32R>;
     const size_t smem = (size_t)p.nks * NT * 3072;
     static size_t attr_set = 0;
-    if (smem > 65536 && smem > attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_p3: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = 160 * 1024;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_p3", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.n_vg = sh_cdiv(p.R, RT);
     const long tiles = (long)p.n_vg * (p.B / 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3: %ld work items", tiles);
@@ -1066,14 +1052,7 @@ int launch_p3r(P3Params& p, hipStream_t st) {
     auto kern = conv_p3r_kernel<NT, NP>;
     const size_t smem = (size_t)p.nks * NT * 3072;
     static size_t attr_set = 0;
-    if (smem > 65536 && smem > attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_p3r: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = 160 * 1024;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_p3r", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.n_vg = p.R;
     const long tiles = (long)p.n_vg * (p.B / 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3r: %ld work items", tiles);
@@ -1099,14 +1078,7 @@ int launch_p3g(P3Params& p, hipStream_t st) {
     auto kern = conv_p3g_kernel<NT, G, BWD, NP, C16>;
     const size_t smem = (size_t)p.nks * NT * 3072;
     static size_t attr_set = 0;
-    if (smem > 65536 && smem > attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("conv_p3g: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = 160 * 1024;
-    }
+    if (sh_lds_limit(attr_set, smem, "conv_p3g", kern) != SH_OK) return SH_ERR_LAUNCH;
     p.n_vg = p.n_grp;
     const long tiles = (long)p.n_grp * (p.B / 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3g: %ld work items", tiles);

@@ -28,6 +28,30 @@ void sh_set_error(const char* fmt, ...);
         }                                                                           \
     } while (0)
 
+// ---------------------------------------------------------------------------- dynamic LDS above 64 KiB
+// A kernel launched with more than 64 KiB of dynamic LDS needs its limit raised first (to the CU's 160 KiB), once per process.
+// sh_lds_limit does that for the kernels named, under the caller's latch: a bool ("raised": nothing to do), or a size_t (the
+// limit raised so far: nothing to do for a launch of at most 64 KiB or of no more than that).  `bytes` is what this launch
+// needs, `what` the caller's name; on failure the message is "<what>: cannot raise the dynamic LDS limit to <bytes> bytes" and
+// the return value SH_ERR_LAUNCH.  The latch belongs to the caller, so a launcher template keeps one per instantiation.
+int sh_raise_lds_limit(const void* const* kernels, int n, size_t bytes, const char* what);
+template <class... K>
+int sh_lds_limit(bool& raised, size_t bytes, const char* what, K... kernels) {
+    if (raised) return SH_OK;
+    const void* ks[] = {reinterpret_cast<const void*>(kernels)...};
+    const int rc = sh_raise_lds_limit(ks, (int)sizeof...(K), bytes, what);
+    raised = rc == SH_OK;
+    return rc;
+}
+template <class... K>
+int sh_lds_limit(size_t& raised, size_t bytes, const char* what, K... kernels) {
+    if (bytes <= 65536 || bytes <= raised) return SH_OK;
+    const void* ks[] = {reinterpret_cast<const void*>(kernels)...};
+    const int rc = sh_raise_lds_limit(ks, (int)sizeof...(K), bytes, what);
+    if (rc == SH_OK) raised = 160 * 1024;
+    return rc;
+}
+
 // ---------------------------------------------------------------------------- kernel timing
 // RAII: records a hipEvent pair on `st` around the launches made inside its scope (only when
 // profiling was enabled through sh_profile_enable).

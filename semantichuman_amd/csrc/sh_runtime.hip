@@ -21,6 +21,16 @@ int sh_env_int(const char* name, int dflt, int lo, int hi) {
     return x < lo ? lo : (x > hi ? hi : x);
 }
 
+int sh_raise_lds_limit(const void* const* kernels, int n, size_t bytes, const char* what) {
+    for (int i = 0; i < n; ++i)
+        if (hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+            (void)hipGetLastError();                          // the error is sticky: clear it, the caller reports ours
+            sh_set_error("%s: cannot raise the dynamic LDS limit to %zu bytes", what, bytes);
+            return SH_ERR_LAUNCH;
+        }
+    return SH_OK;
+}
+
 // ---- kernel timing -----------------------------------------------------------------------
 #include <mutex>
 #include <string>

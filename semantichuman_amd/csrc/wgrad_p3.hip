@@ -496,14 +496,7 @@ int launch_wp3(const WP3Params& p, hipStream_t st) {
     auto kern = wgrad_p3_kernel<QF, PT, XC16>;
     const size_t smem = (size_t)4 * WP_WAVE_LDS;
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("wgrad_p3: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set = true;
-    }
+    if (sh_lds_limit(attr_set, smem, "wgrad_p3", kern) != SH_OK) return SH_ERR_LAUNCH;
     ShProfScope ps(st, "wgrad_p3_kernel<%d, %d, %s>|R=%d B=%d K=%d N=%d grid=%d presum=%d", QF, PT, XC16 ? "true" : "false", p.R, p.B, p.K, p.Cout,
                    p.n_items, p.tail_blocks ? p.tail_rows : 0);
     SH_LAUNCH_PS(ps, kern, dim3(p.n_items + p.tail_blocks), dim3(256), smem, st, p);

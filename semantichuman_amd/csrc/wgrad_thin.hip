@@ -322,15 +322,8 @@ int sh_spiral_conv_bwd_wgt_thin(const float* dpre_ext, int64_t dp_sv, int64_t dp
     const bool b16 = path_dtype == SH_DTYPE_BF16;
     const size_t smem = (size_t)nw * (b16 ? wt_wave_lds<true>() : wt_wave_lds<false>());
     static bool attr_set[2] = {false, false};
-    if (smem > 65536 && !attr_set[b16]) {
-        const void* k = b16 ? reinterpret_cast<const void*>(wgrad_thin_kernel<true>) : reinterpret_cast<const void*>(wgrad_thin_kernel<false>);
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            sh_set_error("wgrad_thin: cannot raise the dynamic LDS limit to %zu bytes", smem);
-            return SH_ERR_LAUNCH;
-        }
-        attr_set[b16] = true;
-    }
+    if (smem > 65536 && sh_lds_limit(attr_set[b16], smem, "wgrad_thin", b16 ? wgrad_thin_kernel<true> : wgrad_thin_kernel<false>) != SH_OK)
+        return SH_ERR_LAUNCH;
     // positions in launches of at most 10 (the kernel's two 16-column output tiles hold 3 x 10 columns)
     const int npass = (S + 9) / 10, s_per = (S + npass - 1) / npass;
     p.S_tot = S;

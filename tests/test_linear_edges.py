@@ -190,6 +190,9 @@ FWD[(3, 5, 2050)] = (GEMM, GEMM, 9, "22")                  # a last chunk of 2
 FWD[(65, 64, 1024)] = (GEMM, GEMM, 1, "00")
 FWD[(70, 130, 96)] = (GEMM, GEMM, 1, "00")
 FWD[(17, 64, 64)] = (S(2), S(2), 1, None)                  # the aligned partner of the misaligned cases below
+FWD[(17, 128, 64)] = (S(2), S(2), 1, None)                 # K % 32 == 0, but two column groups: not the LDS-DMA kernel's shape
+FWD[(17, 256, 48)] = (S(2), S(2), 1, None)                 # four column groups, but K % 32 != 0
+FWD[(65, 256, 1024)] = (GEMM, GEMM, 1, "00")               # M > 64 with a reduction that would be split (K > 384: no resident form)
 FWD_NOBIAS = [(17, 64, 48), (17, 256, 64), (5, 64, 1040), (5, 256, 1056), (65, 64, 32), (5, 7, 13), (4, 8, 2048)]
 FWD_PLANES3 = [(17, 64, 48), (33, 256, 64), (5, 256, 1056), (130, 128, 384), (3, 5, 2050)]     # one case per kernel
 
