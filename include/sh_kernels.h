@@ -1158,6 +1158,63 @@ SH_API int sh_depth_views_points(const void* depth, int dtype, float depth_scale
                                  float* normals, int32_t* pixel, uint8_t* view, int32_t* view_first, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth views: overlap - which rows of a rig's fused scan another, better-placed camera also measures (no reference counterpart).
+ * Projective data association: no search, O(M V) work, one scattered read of the depth images.  Deterministic: no atomics, every
+ * output element one plain store, bits independent of B, of the padding and of the launch shape.
+ *
+ * Inputs.  depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far: exactly those of sh_depth_views_points, and the
+ * packed rows that call produced: points fp32 [B][M][3], normals fp32 [B][M][3], view uint8 [B][M], counts int32 [B].  tol fp32
+ * >= 0 (+inf: any depth agrees).  max_step, drop_isolated and stride are not consulted.
+ * Everything is fp32, every operation rounded on its own (no contraction), the division correctly rounded; no square root.
+ * For a live row (row < counts[b]) with point P, normal n and own view a, every view c that is not absent (a NaN in its ext row):
+ *     e    = t_c - P                                                    component-wise
+ *     len2 = fl(fl(fl(e_x e_x) + fl(e_y e_y)) + fl(e_z e_z))
+ *     dot  = fl(fl(fl(n_x e_x) + fl(n_y e_y)) + fl(n_z e_z))
+ *     q_c  = fl(fl(dot * fabsf(dot)) / fl(fl(len2 * len2) * len2)),  0 when len2 == 0
+ * - cos^2(theta) / d^4 with the sign of the cosine, monotone in cos(theta) / d^2, what depth noise shrinks with - evaluated with the
+ * row's OWN normal (the same surface point has the same normal whoever looks at it), for c == a by the same expression; an
+ * unknown normal (a zero row) gives q = 0 for every view.  For c != a, with d = P - t_c:
+ *     Q_j  = fl(fl(fl(r_0j d_0) + fl(r_1j d_1)) + fl(r_2j d_2))         Q = R_c^T d, the point in c's camera frame
+ *     !(Q_z > 0) (a NaN included): c does not observe the row.  Else (uf, vf), "inside" and the nearest pixel (u, v) from
+ *     (Q_x, Q_y, Q_z) and view c's intrinsics exactly as sh_free_space_fwd forms them from (X, Y, Z); not inside: not observed
+ *     z_c  = fl((float)raw * depth_scale) at pixel (u, v) of image (b, c)
+ *     c OBSERVES the row iff that pixel is valid in the sense of "Depth images" (one set of device helpers serves all) and
+ *     fabsf(fl(z_c - Q_z)) <= tol
+ * Outputs.  seen uint32 [B][M]: bit c set iff c observes the row; bit a is always set for a live row.  keep uint8 [B][M]: 0 iff
+ * some observing c != a has q_c > q_a, or q_c == q_a and c < a (of two identical cameras the first survives); else 1.  Padding
+ * rows (row >= counts[b]) get 0 in both.
+ * How it is computed.  One launch, grid (256-row chunk, body), one thread per row; the body's V extrinsics and intrinsics are
+ * staged in LDS once per workgroup, the loop over the views is uniform.
+ * Null pointers (mask excepted), V outside [1, SH_DEPTH_MAX_VIEWS], negative sizes, an unknown dtype, tol negative or NaN:
+ * SH_ERR_INVALID_ARG; B > 65535, B * V > 65535 or V * H * W > INT_MAX: SH_ERR_UNSUPPORTED; all before the device is touched.
+ * B == 0 or M == 0: SH_OK, nothing launched.
+ *
+ * Scan compaction: sh_scan_compact, a stable per-body compaction of a rig's rows under a keep plane, out of place.  Inputs: points,
+ * normals fp32 [B][M][3], pixel int32 [B][M], view uint8 [B][M] (ascending within a body: view-major rows), seen uint32 [B][M] or
+ * NULL (then seen_out is NULL too), keep uint8 [B][M], counts int32 [B], V, and a width M_out >= max_kept, the largest kept
+ * count as the caller read it.  A row is kept iff row < counts[b] and keep != 0.
+ * Outputs: the same arrays at width M_out with the kept rows in their old order, the padding zeros, zeros, -1, 255 and 0;
+ * counts_out int32 [B]; view_first_out int32 [B][V + 1] with the meaning of "Depth views".  No row >= M_out is ever written.  No
+ * atomics; the same bits for a body alone and in any batch.
+ * How it is computed.  The three passes of "Depth images" over 256-row chunks: a count pass (ballot, popcount, four wave totals),
+ * the same per-body exclusive scan kernel (it writes counts_out), and an emit pass - output row = the chunk's first row + the
+ * ballot rank; view_first_out is written by the rows at which `view` steps and by the last live row.  `workspace`
+ * (sh_scan_compact_workspace(B, M) bytes, int32 [B][chunks]) holds the chunk rows.
+ * Null pointers (seen excepted), V outside [1, SH_DEPTH_MAX_VIEWS], negative sizes, M_out < max_kept, an output that is its
+ * input: SH_ERR_INVALID_ARG; B > 65535: SH_ERR_UNSUPPORTED; a workspace that is too small: SH_ERR_WORKSPACE; before the device
+ * is touched.  B == 0: SH_OK, nothing launched; M == 0 still writes the padding, counts_out and view_first_out (zeros).
+ */
+SH_API int sh_depth_views_overlap(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext,
+                                  int B, int V, int H, int W, float z_near, float z_far, const float* points, const float* normals,
+                                  const uint8_t* view, const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep,
+                                  sh_stream_t stream);
+SH_API size_t sh_scan_compact_workspace(int B, int M);
+SH_API int sh_scan_compact(const float* points, const float* normals, const int32_t* pixel, const uint8_t* view, const uint32_t* seen,
+                           const uint8_t* keep, const int32_t* counts, int B, int V, int M, int max_kept, int M_out, void* workspace,
+                           size_t workspace_bytes, float* points_out, float* normals_out, int32_t* pixel_out, uint8_t* view_out,
+                           uint32_t* seen_out, int32_t* counts_out, int32_t* view_first_out, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Depth field: what a depth image says about where the body is NOT - the way back from the model to the image (no reference
  * counterpart).  A packing-time field per image (sh_depth_field) and a per-step vertex term with its gradient
  * (sh_free_space_fwd / _bwd).  Deterministic: no atomics of any kind, every output element written by one plain store; the bits

@@ -98,6 +98,9 @@ SIGNATURES = {
     "sh_depth_views_count": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _P, c_size_t, _P]),
     "sh_depth_views_points": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _I, _P, c_size_t, _P, _P,
                                       _P, _P, _P, _P]),
+    "sh_depth_views_overlap": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, _P, _P, _P, _P, _I, c_float, _P, _P, _P]),
+    "sh_scan_compact_workspace": (c_size_t, [_I, _I]),
+    "sh_scan_compact": (c_int, [_P] * 7 + [_I] * 5 + [_P, c_size_t] + [_P] * 8),
     "sh_depth_field_workspace": (c_size_t, [_I, _I, _I]),
     "sh_depth_field": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "sh_free_space_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),

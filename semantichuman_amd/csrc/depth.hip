@@ -3,6 +3,8 @@
 // 16 x 16 tile, thread = Z-rank inside the tile, so the ballot prefix of "kept" IS the rank among the tile's rows: a count pass,
 // a per-body scan of the tile counts and an emit pass that recomputes the pixel - no atomics, every output element one plain
 // store, nothing that depends on the batch, the padding or the launch shape.
+// Also what follows the rig form of it: "Depth views: overlap" - per packed row, which other cameras measure the same surface point
+// and whether one of them is better placed - and "Scan compaction", the same three passes over 256-row chunks under a keep plane.
 #include "sh_depth.h"
 
 #pragma clang fp contract(off)          // the header's expressions: every operation rounded on its own, in the whole file
@@ -213,6 +215,152 @@ __global__ __launch_bounds__(NT) void depth_scan_kernel(int32_t* __restrict__ ti
     if (tid == 0) counts[b] = carry;
 }
 
+// ---------------------------------------------------------------------------------------------- "Depth views: overlap"
+struct OverlapArgs {
+    const void* depth; const float* intr; const uint8_t* mask; const float* ext;
+    int V, H, W;
+    float depth_scale, z_near, z_far, tol;
+    const float* points; const float* normals; const uint8_t* view; const int32_t* counts;
+    int M;
+};
+
+// The header's q of a row (point P, normal n) under the camera centre t: cos^2 / d^4 with the sign of the cosine.
+__device__ __forceinline__ float view_quality(const P3& P, const P3& n, const float* t) {
+    const float ex = t[0] - P.x, ey = t[1] - P.y, ez = t[2] - P.z;
+    const float len2 = (ex * ex + ey * ey) + ez * ez;
+    const float dot = (n.x * ex + n.y * ey) + n.z * ez;
+    return len2 == 0.f ? 0.f : (dot * fabsf(dot)) / ((len2 * len2) * len2);
+}
+
+// grid (256-row chunk, body), thread = one row.  The body's V extrinsics and intrinsics are staged in LDS once per workgroup
+// (an absent view: its intrinsics are not read); every view is then a uniform loop step whose LDS reads are broadcasts.  One
+// scattered depth (and mask) read per row and other view that has the point in front of it and inside its image.
+template <typename T>
+__global__ __launch_bounds__(NT) void depth_views_overlap_kernel(OverlapArgs a, uint32_t* __restrict__ seen, uint8_t* __restrict__ keep) {
+    __shared__ float se[SH_DEPTH_MAX_VIEWS * 12];
+    __shared__ float sk[SH_DEPTH_MAX_VIEWS * 4];
+    __shared__ int present[SH_DEPTH_MAX_VIEWS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    for (int i = tid; i < a.V * 12; i += NT) se[i] = a.ext[12L * b * a.V + i];
+    __syncthreads();
+    if (tid < a.V) {
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) ok = ok && se[12 * tid + k] == se[12 * tid + k];
+        present[tid] = ok;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sk[4 * tid + k] = ok ? a.intr[4L * ((long)b * a.V + tid) + k] : 0.f;
+    }
+    __syncthreads();
+    const long j = (long)blockIdx.x * NT + tid;
+    if (j >= a.M) return;
+    const long o = (long)b * a.M + j;
+    uint32_t bits = 0;
+    bool kp = false;
+    if (j < a.counts[b]) {
+        const P3 P = {a.points[3 * o], a.points[3 * o + 1], a.points[3 * o + 2]};
+        const P3 n = {a.normals[3 * o], a.normals[3 * o + 1], a.normals[3 * o + 2]};
+        const int own = a.view[o];
+        const float q_own = own < a.V ? view_quality(P, n, se + 12 * own + 9) : 0.f;   // an absent own view (no live row has one): NaN, every compare false
+        bits = own < 32 ? 1u << own : 0u;
+        kp = true;
+        const long image = (long)a.H * a.W;
+        for (int c = 0; c < a.V; ++c) {                                  // uniform
+            if (!present[c] || c == own) continue;
+            const float* e = se + 12 * c;
+            const float d0 = P.x - e[9], d1 = P.y - e[10], d2 = P.z - e[11];
+            const float X = (e[0] * d0 + e[3] * d1) + e[6] * d2;
+            const float Y = (e[1] * d0 + e[4] * d1) + e[7] * d2;
+            const float Z = (e[2] * d0 + e[5] * d1) + e[8] * d2;
+            if (!(Z > 0.f)) continue;                                    // a NaN included
+            const float fx = sk[4 * c], fy = sk[4 * c + 1], cx = sk[4 * c + 2], cy = sk[4 * c + 3];
+            const float uf = (X * fx) / Z + cx, vf = (Y * fy) / Z + cy;  // sh_free_space_fwd's projection, inside test and rounding
+            const bool inside = uf >= -0.5f && uf < (float)a.W - 0.5f && vf >= -0.5f && vf < (float)a.H - 0.5f;   // a NaN is outside
+            if (!inside) continue;
+            const int u = min((int)floorf(uf + 0.5f), a.W - 1), v = min((int)floorf(vf + 0.5f), a.H - 1);        // no read beyond the image whatever the rounding
+            const long p = ((long)b * a.V + c) * image + (long)v * a.W + u;
+            const T raw = static_cast<const T*>(a.depth)[p];
+            const float zc = depth_z(raw, a.depth_scale);
+            if (!(depth_valid(raw, zc, a.z_near, a.z_far, a.mask, p) && fabsf(zc - Z) <= a.tol)) continue;
+            bits |= 1u << c;
+            const float q = view_quality(P, n, e + 9);
+            if (q > q_own || (q == q_own && c < own)) kp = false;
+        }
+    }
+    seen[o] = bits;
+    keep[o] = kp ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------- "Scan compaction"
+struct CompactArgs {
+    const float* points; const float* normals; const int32_t* pixel; const uint8_t* view; const uint32_t* seen; const uint8_t* keep;
+    const int32_t* counts;
+    int V, M, chunks, M_out;
+};
+struct CompactOut { float* points; float* normals; int32_t* pixel; uint8_t* view; uint32_t* seen; int32_t* view_first; };
+
+// grid (256-row chunk, body), thread = one row: the three passes of depth_kernel with a chunk of rows for a tile.  EMIT = false:
+// chunk_row[body][chunk] = the chunk's kept rows.  EMIT = true: chunk_row holds the chunk's first output row and counts_out the
+// body's total (depth_scan_kernel); a kept row moves to that plus its ballot rank - the old order -, the body's workgroups
+// share out its padding, and view_first_out comes from the rows where `view` steps (the input is view-major): the kept rows
+// before that row are the first row of every view in the step, and the last live row closes the list.
+template <bool EMIT>
+__global__ __launch_bounds__(NT) void scan_compact_kernel(CompactArgs a, CompactOut out, int32_t* __restrict__ chunk_row,
+                                                         const int32_t* __restrict__ counts_out) {
+    __shared__ int wsum[NT / 64];
+    const int chunk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const long j = (long)chunk * NT + tid;
+    const int live_n = min(max(a.counts[b], 0), a.M);
+    const bool live = j < live_n;
+    const long in = (long)b * a.M + j;
+    const bool kept = live && a.keep[in] != 0;
+    const int lane = tid & 63, w = sh_wave_id();
+    const unsigned long long bal = __ballot(kept);
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) {
+        const int s = wsum[i];
+        before += i < w ? s : 0;
+        total += s;
+    }
+    const long slot = (long)b * a.chunks + chunk;
+    if (!EMIT) {
+        if (tid == 0) chunk_row[slot] = total;
+        return;
+    }
+    const int row = chunk_row[slot] + before + __popcll(bal & ((1ull << lane) - 1ull));   // the kept rows before this one
+    const int kept_n = counts_out[b];
+    int32_t* first = out.view_first + (long)b * (a.V + 1);
+    if (live) {
+        const int own = a.view[in], prev = j == 0 ? -1 : (int)a.view[in - 1];
+        for (int v = prev + 1; v <= own && v < a.V; ++v) first[v] = row;
+        if (j == live_n - 1)
+            for (int v = min(own + 1, a.V); v <= a.V; ++v) first[v] = kept_n;
+    }
+    if (live_n == 0 && chunk == 0 && tid <= a.V) first[tid] = 0;         // V + 1 <= 33 threads
+    const long body = (long)b * a.M_out;
+    if (kept && row < a.M_out) {                                         // holds whenever M_out >= the kept count; never a store beyond the body
+        const long o = body + row;
+        out.points[3 * o] = a.points[3 * in]; out.points[3 * o + 1] = a.points[3 * in + 1]; out.points[3 * o + 2] = a.points[3 * in + 2];
+        out.normals[3 * o] = a.normals[3 * in]; out.normals[3 * o + 1] = a.normals[3 * in + 1]; out.normals[3 * o + 2] = a.normals[3 * in + 2];
+        out.pixel[o] = a.pixel[in];
+        out.view[o] = a.view[in];
+        if (out.seen) out.seen[o] = a.seen[in];
+    }
+    for (long r = (long)max(kept_n, 0) + (long)chunk * NT + tid; r < a.M_out; r += (long)a.chunks * NT) {
+        const long o = body + r;
+        out.points[3 * o] = 0.f; out.points[3 * o + 1] = 0.f; out.points[3 * o + 2] = 0.f;
+        out.normals[3 * o] = 0.f; out.normals[3 * o + 1] = 0.f; out.normals[3 * o + 2] = 0.f;
+        out.pixel[o] = -1;
+        out.view[o] = 255;
+        if (out.seen) out.seen[o] = 0u;
+    }
+}
+
+int compact_chunks(int M) { return M <= 0 ? 1 : (int)(((long)M + NT - 1) / NT); }   // at least one workgroup per body: it writes the padding
+
 int tiles_of(int H, int W) { return sh_cdiv(H, TILE) * sh_cdiv(W, TILE); }
 
 // What both entry points ask of the inputs they share; `who` names the caller in the message.
@@ -323,6 +471,66 @@ int sh_depth_views_points(const void* depth, int dtype, float depth_scale, const
     return depth_pass<true, true>("sh_depth_views_points", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, max_step, drop_isolated,
                                   stride, const_cast<int32_t*>(counts), max_count, M, const_cast<void*>(workspace), workspace_bytes, points, normals,
                                   pixel, view, view_first, stream);
+}
+
+int sh_depth_views_overlap(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                           int H, int W, float z_near, float z_far, const float* points, const float* normals, const uint8_t* view,
+                           const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep, sh_stream_t stream) {
+    const char* who = "sh_depth_views_overlap";
+    if (const int rc = check_views(who, depth, dtype, intr, ext, B, V, H, W, 1)) return rc;
+    SH_REQUIRE(points && normals && view && counts && seen && keep, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(M >= 0, SH_ERR_INVALID_ARG, "%s: negative size (M %d)", who, M);
+    SH_REQUIRE(tol >= 0.f, SH_ERR_INVALID_ARG, "%s: tol must be >= 0 (and not NaN)", who);
+    if (B == 0 || M == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const OverlapArgs a = {depth, intr, mask, ext, V, H, W, depth_scale, z_near, z_far, tol, points, normals, view, counts, M};
+    ShProfScope ps(st, "depth_views_overlap_kernel|B=%d V=%d H=%d W=%d M=%d u16=%d", B, V, H, W, M, dtype == SH_DEPTH_U16);
+    const dim3 grid((unsigned)compact_chunks(M), (unsigned)B);
+    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, depth_views_overlap_kernel<uint16_t>, grid, dim3(NT), 0, st, a, seen, keep);
+    else SH_LAUNCH_PS(ps, depth_views_overlap_kernel<float>, grid, dim3(NT), 0, st, a, seen, keep);
+    SH_CHECK_LAUNCH("depth_views_overlap");
+    return SH_OK;
+}
+
+size_t sh_scan_compact_workspace(int B, int M) { return B <= 0 || M < 0 ? 0 : (size_t)B * compact_chunks(M) * sizeof(int32_t); }
+
+int sh_scan_compact(const float* points, const float* normals, const int32_t* pixel, const uint8_t* view, const uint32_t* seen, const uint8_t* keep,
+                    const int32_t* counts, int B, int V, int M, int max_kept, int M_out, void* workspace, size_t workspace_bytes,
+                    float* points_out, float* normals_out, int32_t* pixel_out, uint8_t* view_out, uint32_t* seen_out, int32_t* counts_out,
+                    int32_t* view_first_out, sh_stream_t stream) {
+    const char* who = "sh_scan_compact";
+    SH_REQUIRE(points && normals && pixel && view && keep && counts && points_out && normals_out && pixel_out && view_out && counts_out && view_first_out
+               && !seen == !seen_out, SH_ERR_INVALID_ARG, "%s: null pointer (seen and seen_out: both or neither)", who);
+    SH_REQUIRE(V >= 1 && V <= SH_DEPTH_MAX_VIEWS, SH_ERR_INVALID_ARG, "%s: V = %d views, must lie in [1, %d]", who, V, SH_DEPTH_MAX_VIEWS);
+    SH_REQUIRE(B >= 0 && M >= 0 && M_out >= 0 && max_kept >= 0, SH_ERR_INVALID_ARG, "%s: negative size (B %d, M %d, M_out %d, max_kept %d)", who, B, M,
+               M_out, max_kept);
+    SH_REQUIRE(M_out >= max_kept, SH_ERR_INVALID_ARG, "%s: M_out = %d rows cannot hold the largest body's %d", who, M_out, max_kept);
+    SH_REQUIRE(points_out != points && normals_out != normals && pixel_out != pixel && view_out != view && (!seen || seen_out != seen),
+               SH_ERR_INVALID_ARG, "%s: out of place only - an output is its input", who);
+    SH_REQUIRE(B <= 65535, SH_ERR_UNSUPPORTED, "%s: B too large", who);
+    if (B == 0) return SH_OK;
+    const int chunks = compact_chunks(M);
+    const size_t need = sh_scan_compact_workspace(B, M);
+    SH_REQUIRE(workspace && workspace_bytes >= need, SH_ERR_WORKSPACE, "%s: the workspace holds the chunk rows (%zu bytes needed)", who, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const CompactArgs a = {points, normals, pixel, view, seen, keep, counts, V, M, chunks, M_out};
+    const CompactOut out = {points_out, normals_out, pixel_out, view_out, seen_out, view_first_out};
+    int32_t* chunk_row = static_cast<int32_t*>(workspace);
+    const dim3 grid((unsigned)chunks, (unsigned)B);
+    {
+        ShProfScope ps(st, "scan_compact_count_kernel|B=%d M=%d", B, M);
+        SH_LAUNCH_PS(ps, scan_compact_kernel<false>, grid, dim3(NT), 0, st, a, out, chunk_row, static_cast<const int32_t*>(nullptr));
+    }
+    {
+        ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, chunks);
+        SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, chunk_row, chunks, counts_out);
+    }
+    {
+        ShProfScope ps(st, "scan_compact_emit_kernel|B=%d M=%d M_out=%d", B, M, M_out);
+        SH_LAUNCH_PS(ps, scan_compact_kernel<true>, grid, dim3(NT), 0, st, a, out, chunk_row, counts_out);
+    }
+    SH_CHECK_LAUNCH("scan_compact");
+    return SH_OK;
 }
 
 }  // extern "C"

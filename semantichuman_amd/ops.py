@@ -686,6 +686,76 @@ def depth_views_points(depth, intr, ext, counts, workspace, M, max_count, mask=N
                          drop_isolated, stride)
 
 
+def _rig_rows(who, B, M, device, **planes):
+    """The packed planes of a rig batch, checked: name=(tensor, dtype, trailing shape) -> nothing; ValueError for any that is not a
+    contiguous tensor [B, M, ...] of that dtype on `device`."""
+    for name, (t, dtype, tail) in planes.items():
+        if not (torch.is_tensor(t) and t.device == device and t.dtype in (dtype if isinstance(dtype, tuple) else (dtype,)) and t.is_contiguous()
+                and tuple(t.shape) == (B, M) + tail):
+            raise ValueError("%s: %s must be a contiguous %s tensor %s on the device of the rest, got %s %s"
+                             % (who, name, dtype, [B, M] + list(tail), getattr(t, "dtype", type(t).__name__), tuple(getattr(t, "shape", ()))))
+
+
+_SEEN = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+
+
+def depth_views_overlap(depth, intr, ext, points, normals, view, counts, tol, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):
+    """sh_depth_views_overlap: the images, calibration and range of the `depth_views_count` / `depth_views_points` calls that made the
+    packed rows (points, normals fp32 [B, M, 3], view uint8 [B, M], counts int32 [B]) and a depth tolerance tol >= 0 -> (seen int32
+    [B, M] read as unsigned: bit c set where camera c measures the row's surface point within tol, the row's own bit always; keep
+    uint8 [B, M]: 0 where an observing camera is better placed - larger cos / d^2 under the row's normal, the lower index on a
+    tie); zeros in the padding.  One launch, nothing synchronised."""
+    who = "depth_views_overlap"
+    B, V, H, W, cargs = _depth_args(who, True, depth, intr, ext, mask, depth_scale, z_near, z_far, math.inf, False, 1)
+    tol = float(tol)
+    if not tol >= 0:
+        raise ValueError("%s: tol must be >= 0, got %r" % (who, tol))
+    M = points.shape[1] if torch.is_tensor(points) and points.dim() == 3 else -1
+    _rig_rows(who, B, M, depth.device, points=(points, torch.float32, (3,)), normals=(normals, torch.float32, (3,)), view=(view, torch.uint8, ()))
+    if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise ValueError("%s: counts must be the int32 tensor [%d] of the packed rows" % (who, B))
+    seen = torch.empty((B, M), dtype=torch.int32, device=depth.device)
+    keep = torch.empty((B, M), dtype=torch.uint8, device=depth.device)
+    check(_lib.load().sh_depth_views_overlap(*cargs[:12], ptr(points), ptr(normals), ptr(view), ptr(counts), M, tol, ptr(seen), ptr(keep),
+                                             stream_ptr()), "sh_" + who)
+    return seen, keep
+
+
+def scan_compact(points, normals, pixel, view, keep, counts, V, M_out, max_kept, seen=None):
+    """sh_scan_compact: a rig batch's planes (points, normals fp32 [B, M, 3], pixel int32, view uint8, seen int32 or None, all
+    [B, M]; counts int32 [B]), a keep plane uint8 [B, M], a width M_out and the largest kept count as the caller read it
+    (M_out >= max_kept) -> (points, normals, pixel, view, seen or None, counts int32 [B], view_first int32 [B, V + 1]) at width
+    M_out: the kept live rows in their old order, then zeros, zeros, -1, 255 and 0.  Three launches, nothing synchronised."""
+    who = "scan_compact"
+    if not (torch.is_tensor(points) and points.is_cuda and points.dim() == 3):
+        raise RuntimeError("semantichuman_amd.%s needs fp32 HIP points [B, M, 3] (got %s %s); there is no CPU path"
+                           % (who, getattr(points, "device", None), tuple(getattr(points, "shape", ()))))
+    B, M, _ = points.shape
+    V, M_out, max_kept = int(V), int(M_out), int(max_kept)
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    planes = dict(points=(points, torch.float32, (3,)), normals=(normals, torch.float32, (3,)), pixel=(pixel, torch.int32, ()),
+                  view=(view, torch.uint8, ()), keep=(keep, torch.uint8, ()))
+    if seen is not None:
+        planes["seen"] = (seen, _SEEN, ())
+    _rig_rows(who, B, M, points.device, **planes)
+    if not (torch.is_tensor(counts) and counts.device == points.device and counts.dtype == torch.int32 and counts.is_contiguous()
+            and tuple(counts.shape) == (B,)):
+        raise ValueError("%s: counts must be an int32 tensor [%d] on the points' device" % (who, B))
+    lib = _lib.load()
+    dev, width = points.device, max(M_out, 0)
+    outs = [torch.empty((B, width, 3), dtype=torch.float32, device=dev), torch.empty((B, width, 3), dtype=torch.float32, device=dev),
+            torch.empty((B, width), dtype=torch.int32, device=dev), torch.empty((B, width), dtype=torch.uint8, device=dev),
+            None if seen is None else torch.empty((B, width), dtype=seen.dtype, device=dev),
+            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, V + 1), dtype=torch.int32, device=dev)]
+    nbytes = lib.sh_scan_compact_workspace(B, M)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib.sh_scan_compact(ptr(points), ptr(normals), ptr(pixel), ptr(view), ptr(seen), ptr(keep), ptr(counts), B, V, M, max_kept, M_out,
+                              ptr(ws), nbytes, *[ptr(t) for t in outs], stream_ptr()), "sh_" + who)
+    return tuple(outs)
+
+
 def depth_field(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):
     """sh_depth_field: the image inputs of `depth_count` -> (cls uint8 [B, H, W]: 0 empty, 1 unknown, 2 surface; z fp32 [B, H, W],
     the surface depth; nearest int32 [B, H, W], the nearest pixel that is not empty as v * W + u, -1: the image has none).

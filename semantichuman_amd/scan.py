@@ -32,6 +32,9 @@
                                      depth cameras as ONE scan per body in the rig's frame (sh_depth_views_count / _points);
                                      its `viewpoints` are [B, V, 3], and `visible_vertices` / `visibility="viewpoint"` then
                                      mean "seen by at least one camera" (sh_vertex_visibility_views, one sweep over the faces)
+  * `views_overlap(scans, depth, intrinsics, extrinsics, tol=)`, `merge_views(scans, keep, seen)`, `merge_tol=` on the two
+                                     above  the rows of a rig scan that a better-placed camera also measures, found by
+                                     projection (sh_depth_views_overlap), and the batch without them (sh_scan_compact)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -191,13 +194,15 @@ class ScanBatch:
     `from_depth(..., extrinsics=)` makes one, with `view` uint8 [B, Mmax] (the camera each row came from, 255 in the padding) and
     `view_first` int32 [B, V + 1]; rig_viewpoints=[V, 3] or [B, V, 3] (at most 32 views, NaN rows allowed, no inf) sets the
     field for a cloud fused elsewhere and takes the place of a per-body `viewpoints` there (per-point viewpoints still orient
-    estimated normals)."""
+    estimated normals).  `seen`: None, or on a batch made by `merge_views` / `from_depth(..., merge_tol=)` int32 [B, Mmax] read as
+    unsigned - bit c set where camera c also measured the row's surface point (`views_overlap`), 0 in the padding."""
 
     viewpoints = None                                                                   # for batches made without __init__ or _from_parts
     viewpoints_error = None
     pixels = None
     view = None
     view_first = None
+    seen = None
 
     def __init__(self, clouds, device, order=None, normals=None, normal_k=16, viewpoints=None, rig_viewpoints=None):
         if order not in (None, "morton"):
@@ -245,15 +250,15 @@ class ScanBatch:
         return self.points.shape[0]
 
     @classmethod
-    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None, pixels=None, view=None, view_first=None):
+    def _from_parts(cls, points, counts, host_counts, perm, normals, viewpoints=None, pixels=None, view=None, view_first=None, seen=None):
         """A ScanBatch around tensors that are already packed and resident: every field, nothing copied or checked."""
         out = cls.__new__(cls)
         out.points, out.counts, out.host_counts, out.perm, out.normals = points, counts, host_counts, perm, normals
-        out.viewpoints, out.pixels, out.view, out.view_first = viewpoints, pixels, view, view_first
+        out.viewpoints, out.pixels, out.view, out.view_first, out.seen = viewpoints, pixels, view, view_first, seen
         return out
 
     @classmethod
-    def from_depth(cls, depth, intrinsics, device, extrinsics=None, **options):
+    def from_depth(cls, depth, intrinsics, device, extrinsics=None, merge_tol=None, **options):
         """Depth images as a batch of scans: `unproject_depth(depth, intrinsics, device=device, **options)` kept whole - points in
         the camera's frame in tile order (perm None), counts, the grid normals (oriented to the camera; a zero row: unknown),
         `viewpoints` = zeros [B, 3] (the camera centre) and `pixels`.  Ready for normal_angle=, gate_on=, visibility="viewpoint"
@@ -261,12 +266,18 @@ class ScanBatch:
         extrinsics: None, or the camera -> rig transforms of a rig of V depth cameras - then `unproject_depth_views(depth,
         intrinsics, extrinsics, device=device, **options)` kept whole as a rig batch: one fused scan per body in the rig's frame,
         view-major, with `pixels`, `view`, `view_first` and `viewpoints` fp32 [B, V, 3] = the camera centres t (NaN for an absent
-        camera).  Still one host synchronisation."""
+        camera).  Still one host synchronisation.
+        merge_tol: None, or - a rig only - a depth tolerance >= 0: the rows that a better-placed camera also measures within it are
+        dropped before the batch is made, `merge_views(scans, *views_overlap(scans, ..., tol=merge_tol))` on the batch described
+        above with the images still resident, and `seen` is kept.  That costs TWO host synchronisations instead of one: the kept
+        counts are read as well.  ValueError for a merge_tol without extrinsics, negative or NaN."""
         if extrinsics is not None:
-            points, normals, pixel, view, view_first, counts, host_counts, ext = _unproject_depth_views(depth, intrinsics, extrinsics,
-                                                                                                       device=device, **options)
+            rows = _unproject_depth_views(depth, intrinsics, extrinsics, device=device, merge_tol=merge_tol, **options)
+            points, normals, pixel, view, view_first, counts, host_counts, ext = rows[:8]
             return cls._from_parts(points, counts, host_counts, None, normals, viewpoints=torch.from_numpy(ext[:, :, 9:].copy()).to(points.device),
-                                   pixels=pixel, view=view, view_first=view_first)
+                                   pixels=pixel, view=view, view_first=view_first, seen=rows[8] if len(rows) > 8 else None)
+        if merge_tol is not None:
+            raise ValueError("ScanBatch.from_depth: merge_tol needs a rig (extrinsics=); one camera has no overlap")
         points, normals, pixel, counts, host_counts = _depth_rows("unproject_depth", depth, intrinsics, device=device, **options)
         return cls._from_parts(points, counts, host_counts, None, normals,
                                viewpoints=torch.zeros((points.shape[0], 3), dtype=torch.float32, device=points.device), pixels=pixel)
@@ -277,7 +288,8 @@ class ScanBatch:
                                      None if self.perm is None else self.perm[sl], None if self.normals is None else self.normals[sl],
                                      viewpoints=None if self.viewpoints is None else self.viewpoints[sl].contiguous(),
                                      pixels=None if self.pixels is None else self.pixels[sl], view=None if self.view is None else self.view[sl],
-                                     view_first=None if self.view_first is None else self.view_first[sl])
+                                     view_first=None if self.view_first is None else self.view_first[sl],
+                                     seen=None if self.seen is None else self.seen[sl])
 
 
 def estimate_normals(points_or_scans, k=16, viewpoints=None, counts=None):
@@ -377,11 +389,12 @@ def _depth_upload(d, k, m, device):
 
 
 def _depth_rows(what, depth, intrinsics, ext=None, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                device=None):
+                device=None, merge_tol=None):
     """`unproject_depth` (ext None), with the counts as the host read them as a fifth result - and what `unproject_depth_views`
     shares with it: `_depth_inputs` and the checks of max_step and stride - every ValueError before the device is used -, then
     upload, count, read the counts once, points.  ext: a rig's float32 [B, V, 12] - depth, intrinsics and mask then hold an image
-    per row, body-major, and ops.depth_views_points' results come first."""
+    per row, body-major, and ops.depth_views_points' results come first.  merge_tol (a rig only, checked by the caller): the rows
+    are merged with the resident images (`_merge_rows`: a second synchronisation) and `seen` is an eighth result."""
     d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
     step = math.inf if max_step is None else float(max_step)
     if not step >= 0:
@@ -399,7 +412,11 @@ def _depth_rows(what, depth, intrinsics, ext=None, depth_scale=1.0, mask=None, z
     counts, ws = count(*lead, **opts)
     host_counts = counts.cpu().numpy()                                                  # the one synchronisation
     most = int(host_counts.max())
-    return points(*lead, counts, ws, max(most, 1), most, **opts) + (counts, host_counts)
+    rows = points(*lead, counts, ws, max(most, 1), most, **opts)
+    if merge_tol is None:
+        return rows + (counts, host_counts)
+    seen, keep = ops.depth_views_overlap(*lead, rows[0], rows[1], rows[3], counts, merge_tol, mask=m, depth_scale=depth_scale, z_near=near, z_far=far)
+    return _merge_rows(rows[0], rows[1], rows[2], rows[3], counts, rig[1], keep, seen)
 
 
 def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
@@ -451,11 +468,20 @@ def pack_extrinsics(extrinsics, what="extrinsics"):
     return np.ascontiguousarray(out), batched
 
 
-def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                           device=None):
-    """`unproject_depth_views`, with the counts as the host read them and the extrinsics float32 [B, V, 12] as two more results.
-    Every ValueError is raised before the device is used."""
-    what = "unproject_depth_views"
+def _check_merge_tol(what, tol, name="merge_tol"):
+    """A depth tolerance as a float; ValueError unless it is a number >= 0 (+inf allowed)."""
+    try:
+        t = float(tol)
+    except (ValueError, TypeError):
+        t = math.nan
+    if not t >= 0:
+        raise ValueError("%s: %s must be a number >= 0, got %r" % (what, name, tol))
+    return t
+
+
+def _rig_inputs(what, depth, intrinsics, extrinsics, mask):
+    """What every call that takes a rig's images checks first, nothing moved to the device -> (depth [B * V, H, W]: an image per
+    row, body-major; intrinsics float64 [B * V, 4]; ext float32 [B, V, 12]; mask [B * V, H, W] or None)."""
     ext, batched = pack_extrinsics(extrinsics, what + ": extrinsics")
     B, V = ext.shape[:2]
     if V > ops.MAX_VIEWS:
@@ -468,13 +494,24 @@ def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=
     flat = lambda a: None if a is None else a.reshape((B * V,) + tuple(a.shape[-2:]))      # noqa: E731 - [B * V, H, W]: an image per row
     if mask is not None and tuple(getattr(mask, "shape", np.shape(mask))) != shape:
         raise ValueError("%s: mask must have the depth's shape %s" % (what, shape))
-    return _depth_rows(what, flat(depth if torch.is_tensor(depth) else np.asarray(depth)), np.broadcast_to(k, (B, V, 4)).reshape(B * V, 4), ext,
-                       depth_scale, flat(mask if mask is None or torch.is_tensor(mask) else np.asarray(mask)), z_range, max_step, drop_isolated,
-                       stride, device) + (ext,)
+    return (flat(depth if torch.is_tensor(depth) else np.asarray(depth)), np.broadcast_to(k, (B, V, 4)).reshape(B * V, 4), ext,
+            flat(mask if mask is None or torch.is_tensor(mask) else np.asarray(mask)))
+
+
+def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
+                           device=None, merge_tol=None):
+    """`unproject_depth_views`, with the counts as the host read them and the extrinsics float32 [B, V, 12] as two more results -
+    and, with a merge_tol, `seen` as a ninth.  Every ValueError is raised before the device is used."""
+    what = "unproject_depth_views"
+    if merge_tol is not None:
+        merge_tol = _check_merge_tol(what, merge_tol)
+    d, k, ext, m = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
+    rows = _depth_rows(what, d, k, ext, depth_scale, m, z_range, max_step, drop_isolated, stride, device, merge_tol)
+    return rows[:7] + (ext,) + rows[7:]
 
 
 def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                          device=None):
+                          device=None, merge_tol=None):
     """The depth cameras of a rig -> ONE scan per body in the rig's frame (sh_depth_views_count, sh_depth_views_points;
     include/sh_kernels.h, "Depth views").  depth: [B, V, H, W], or [V, H, W] with extrinsics that have no batch axis (B = 1); fp32 or
     16-bit words as in `unproject_depth`, and depth_scale, mask (the depth's shape), z_range, max_step, drop_isolated and stride
@@ -488,10 +525,92 @@ def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mas
     (at least 1); rows beyond a count are zeros, zeros, -1 and 255.  Rows are view-major, inside a view in tile / Z-order.  One
     host synchronisation.  Deterministic - the same bits for a body alone and inside any batch.  Not differentiable.  ValueError
     (before the device is used) for wrong shapes or dtypes, more than 32 views, fx / fy not finite and positive, stride < 1, a
-    negative max_step, or extrinsics that are no rigid transforms."""
+    negative max_step, or extrinsics that are no rigid transforms.
+    merge_tol: None - nothing more is launched -, or a depth tolerance >= 0 (ValueError when negative or NaN): the rows that a
+    better-placed camera also measures within it are dropped (`views_overlap`, `merge_views`) and the six results are the merged
+    ones.  That costs TWO host synchronisations instead of one: the kept counts are read as well."""
     points, normals, pixel, view, view_first, counts = _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale, mask, z_range, max_step,
-                                                                              drop_isolated, stride, device)[:6]
+                                                                              drop_isolated, stride, device, merge_tol)[:6]
     return points, normals, pixel, view, counts, view_first
+
+
+def _merge_rows(points, normals, pixel, view, counts, V, keep, seen):
+    """A rig batch's planes under a keep plane (uint8 or bool [B, M]; the padding counts as dropped whatever it holds) -> (points,
+    normals, pixel, view, view_first, counts, host_counts, seen or None), compacted (ops.scan_compact).  The kept counts are an
+    integer sum in torch - exact - and reading them is the one synchronisation."""
+    M = points.shape[1]
+    live = torch.arange(M, device=points.device)[None, :] < counts[:, None]
+    keep = ((keep != 0) & live).to(torch.uint8).contiguous()
+    kept = keep.sum(1, dtype=torch.int32)
+    host_counts = kept.cpu().numpy()                                                    # the one synchronisation
+    most = int(host_counts.max()) if host_counts.size else 0
+    p, n, pix, vw, sn, cnt, first = ops.scan_compact(points, normals, pixel, view, keep, counts, V, max(most, 1), most, seen)
+    return p, n, pix, vw, first, cnt, host_counts, sn
+
+
+def _rig_batch(what, scans):
+    """ValueError unless `scans` is a rig batch made from depth images: `view`, `view_first`, `pixels`, normals and rig viewpoints."""
+    if not (isinstance(scans, ScanBatch) and scans.view is not None and scans.view_first is not None and scans.pixels is not None
+            and scans.normals is not None and scans.viewpoints is not None and scans.viewpoints.dim() == 3):
+        raise ValueError("%s: scans must be a rig batch made from depth images (ScanBatch.from_depth(..., extrinsics=)); a cloud fused "
+                         "elsewhere carries no images to compare" % what)
+    return scans.view_first.shape[1] - 1
+
+
+def views_overlap(scans, depth, intrinsics, extrinsics, *, tol, depth_scale=1.0, mask=None, z_range=None):
+    """Which rows of a rig batch a better-placed camera also measures (sh_depth_views_overlap; include/sh_kernels.h, "Depth views:
+    overlap").  scans: the rig batch `ScanBatch.from_depth(depth, intrinsics, device, extrinsics=extrinsics, ...)` made from THESE
+    images - depth, intrinsics, extrinsics, depth_scale, mask and z_range as given there (max_step, drop_isolated and stride are
+    not consulted).  Each row's point is projected into every other camera; that camera observes it when the nearest pixel is
+    valid and its depth agrees with the point's within tol (projective association: no search).  Of the cameras that observe a
+    row the one with the largest cos(theta) / d^2 under the row's own normal keeps it - depth noise grows with d^2 / cos(theta) -
+    and on a tie the lower index.
+    -> (keep bool [B, M]: False where another camera keeps the row, and in the padding; seen int32 [B, M] read as unsigned: bit c
+    set where camera c observes the row, its own bit always).  One launch, nothing synchronised; fp32 throughout, deterministic.
+    ValueError (before the device is used) for scans that are no rig batch or of another B or V, a tol that is negative or NaN,
+    and what `unproject_depth_views` refuses in the images."""
+    what = "views_overlap"
+    V = _rig_batch(what, scans)
+    tol = _check_merge_tol(what, tol, "tol")
+    d, k, ext, m = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
+    if ext.shape[:2] != (len(scans), V):
+        raise ValueError("%s: the scans hold %d bodies x %d views, the extrinsics %d x %d" % ((what, len(scans), V) + ext.shape[:2]))
+    d, k, m, near, far = _depth_inputs(what, d, k, m, z_range)
+    d, k, m = _depth_upload(d, k, m, scans.points.device)
+    rig = tuple(ext.shape[:2])
+    d = d.view(rig + tuple(d.shape[-2:]))
+    seen, keep = ops.depth_views_overlap(d, k.view(rig + (4,)), torch.from_numpy(ext).to(d.device), scans.points, scans.normals, scans.view,
+                                         scans.counts, tol, mask=None if m is None else m.view(d.shape), depth_scale=depth_scale, z_near=near,
+                                         z_far=far)
+    return keep.bool(), seen
+
+
+def merge_views(scans, keep, seen=None):
+    """A rig batch without the rows `keep` marks False (sh_scan_compact): a new rig ScanBatch with fresh points / normals / pixels /
+    view / view_first / counts / host_counts - the kept rows in their old order, so still view-major and in tile order inside a
+    view -, `viewpoints` carried over, perm None, and `seen` (int32 [B, M], `views_overlap`'s) compacted with them as
+    `ScanBatch.seen` when given.  keep: bool or integer [B, M], a tensor or a host array; what it holds in the padding is not
+    read.  One host synchronisation, to read the kept counts (`keep.sum(1)`, exact).  chamfer, align, fit_scan and register_scan
+    read the result like any rig batch.  ValueError for scans that are no rig batch made from depth images, or a keep / seen of
+    another shape."""
+    what = "merge_views"
+    V = _rig_batch(what, scans)
+    shape = tuple(scans.points.shape[:2])
+    planes = []
+    for name, t in (("keep", keep), ("seen", seen)):
+        if t is not None:
+            t = t.detach() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t))
+            if tuple(t.shape) != shape or t.is_floating_point() or t.is_complex():
+                raise ValueError("%s: %s must be a bool or integer array of the scans' shape %s, got %s %s" % (what, name, shape, t.dtype, tuple(t.shape)))
+        planes.append(t)
+    keep, seen = planes
+    dev = scans.points.device
+    if seen is not None:
+        seen = seen.to(dev)
+        seen = (seen if seen.dtype in ops._SEEN else seen.to(torch.int32)).contiguous()
+    p, n, pix, vw, first, cnt, host_counts, sn = _merge_rows(scans.points.contiguous(), scans.normals.contiguous(), scans.pixels.contiguous(),
+                                                            scans.view.contiguous(), scans.counts, V, keep.to(dev), seen)
+    return ScanBatch._from_parts(p, cnt, host_counts, None, n, viewpoints=scans.viewpoints, pixels=pix, view=vw, view_first=first, seen=sn)
 
 
 class DepthField:
