@@ -1022,12 +1022,10 @@ int dispatch_gg(GGParams& p, hipStream_t st) {
 // dimension is the ROW index.  Each block ends by writing its partial to a slab; a second kernel
 // sums the slabs in a fixed order (no atomics -> bitwise reproducible).
 constexpr int TMW = 32;
-#ifndef SH_WG_ABLATE
-#define SH_WG_ABLATE 0      // diagnostic builds only (tools/ablate_wgrad.sh): 1 no global loads, 2 no MFMA, 4 no LDS stores, 8 no LDS reads
-#endif
 constexpr int WG_TABLE_CAP = 8192;      // ints of gather table a workgroup keeps in LDS (32 KiB)
 
-struct WGParams {
+// what every weight-gradient kernel of this file reads of a call: the head of WGParams and of WSParams (wg_tensors fills it)
+struct WGTensors {
     const float* dpre; long dp_sv, dp_sb;
     const float* x; long x_sv, x_sb;
     const int* table;
@@ -1035,10 +1033,13 @@ struct WGParams {
     long slab_stride;   // Cout*K
     long bias_off;      // nrc*Cout*K
     int B, R, S, Cin, Cout, K;
+};
+
+struct WGParams : WGTensors {
     int log2TB, n_btiles, n_vtiles, nvc, steps_per_block, ncg;
 };
 
-template <int COT, int CTW, bool VEC4>
+template <int COT, int CTW>
 __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
     constexpr int KCW = 64 * CTW;
     constexpr int LDG = KCW + 16;                       // == 16 (mod 32): conflict-free ds_read_b32
@@ -1081,7 +1082,6 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
     // K read (s=0, c=0): they only feed weight columns that are never stored.
     const int gq = tid % GQ, grow0 = tid / GQ;
     const int k = cg * KCW + 4 * gq;
-    const bool k_in = k < p.K;
     int s4[4], c4[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1121,12 +1121,6 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
     // when the tile is written to LDS two steps later.  Invalid rows MUST be zeroed here because
     // rows are the reduction dimension.
     auto load_step = [&](int st, f32x4 (&rg)[GP], f32x4 (&rp)[PP], unsigned& mg, unsigned& mp) {
-        if (SH_WG_ABLATE & 1) {
-            mg = mp = ~0u;
-            for (int i = 0; i < GP; ++i) rg[i] = (f32x4){1.f, 2.f, 3.f, (float)st};
-            for (int i = 0; i < PP; ++i) rp[i] = (f32x4){1.f, 2.f, 3.f, (float)st};
-            return;
-        }
         st = st < nsteps ? st : nsteps - 1;
         const int vloc = st * TV;                       // local vertex index of the step's first vertex
         mg = 0; mp = 0;
@@ -1135,16 +1129,10 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
             const int vl = vloc + g_vl[i];
             const bool ok = vbase + vl < p.R && ((g_bok >> i) & 1u);
             mg |= (ok ? 1u : 0u) << i;
-            if (VEC4) {
-                // columns past K (padding of the last column group) all read ONE shared line
-                const long off = k_in ? (long)Tl[vl * S + s4[0]] * p.x_sv + g_boff[i] + c4[0] : 0;
-                rg[i] = *reinterpret_cast<const f32x4*>(p.x + off);
-            } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int u = Tl[vl * S + s4[j]];
-                    rg[i][j] = p.x[(long)u * p.x_sv + g_boff[i] + c4[j]];
-                }
+            for (int j = 0; j < 4; ++j) {
+                const int u = Tl[vl * S + s4[j]];
+                rg[i][j] = p.x[(long)u * p.x_sv + g_boff[i] + c4[j]];
             }
         }
 #pragma unroll
@@ -1165,7 +1153,6 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
         }
     };
     auto store_step = [&](int buf, const f32x4 (&rg)[GP], const f32x4 (&rp)[PP], unsigned mg, unsigned mp) {
-        if ((SH_WG_ABLATE & 4) && rg[0][0] != 12345.f) return;
         float* Gb = Gs + buf * TMW * LDG;
         float* Pb = Ps + buf * TMW * LDP;
 #pragma unroll
@@ -1197,9 +1184,9 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
             for (int kk = 0; kk < 4; ++kk) {
                 const int row = 16 * half + 4 * kk + lk;
 #pragma unroll
-                for (int a = 0; a < CTW; ++a) gf[kk][a] = (SH_WG_ABLATE & 8) ? (float)(row + a) : Gb[row * LDG + a * 16];
+                for (int a = 0; a < CTW; ++a) gf[kk][a] = Gb[row * LDG + a * 16];
 #pragma unroll
-                for (int b = 0; b < COT; ++b) pf[kk][b] = (SH_WG_ABLATE & 8) ? (float)(row - b) : Pb[row * LDP + b * 16];
+                for (int b = 0; b < COT; ++b) pf[kk][b] = Pb[row * LDP + b * 16];
             }
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
@@ -1207,8 +1194,7 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_kernel(const WGParams p) {
                 for (int a = 0; a < CTW; ++a)
 #pragma unroll
                     for (int b = 0; b < COT; ++b)
-                        if (SH_WG_ABLATE & 2) acc[a][b][0] += gf[kk][a] * pf[kk][b];
-                        else acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gf[kk][a], pf[kk][b], acc[a][b], 0, 0, 0);
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(gf[kk][a], pf[kk][b], acc[a][b], 0, 0, 0);
         }
         if (cg == 0 && tid < COT * 16) {
             const float* Pc = Ps + buf * TMW * LDP + tid;
@@ -1381,17 +1367,13 @@ __global__ __launch_bounds__(256) void weight_transpose_multi_kernel(const Multi
 //   outputs are the column sets {4i + t}.  The B operand is dpre[row kq][cout = a + 16 b], one
 //   4-byte load per output-channel tile.  acc[t][b][j] = dW[cout 16b + a][col 64cg + 16kq + 4j + t].
 // The loads of the next DEPTH-1 vertices are in flight while a vertex's MFMAs issue.
-struct WSParams {
-    const float* dpre; long dp_sv, dp_sb;
-    const float* x; long x_sv, x_sb;
-    const int* table;
-    float* slab; long slab_stride, bias_off;
-    int B, R, S, Cin, Cout, K;
+struct WSParams : WGTensors {
     int log2TB, n_btiles, nvc, vpc, ncg, n_items;     // vpc = vertices per chunk
     int co0;                                          // first output channel of this launch (groups of <= 128 channels)
     // vertex assignment of a row chunk: 0 = vc * vpc .. + vpc - 1 (a contiguous block per wave), 1 = vc, vc + nvc, vc + 2 nvc, ...
     // (the waves of an XCD walk the mesh TOGETHER: at any time they gather from ~nvc neighbouring vertices, which stay in the
-    // XCD's L2, instead of from one block of vpc vertices each - measured: the level-0 launch fetched 270 MB for 85 MB of input)
+    // XCD's L2, instead of from one block of vpc vertices each - measured: the level-0 launch fetched 270 MB for 85 MB of input).
+    // The host (choose_wgrad) produces 1 or 2 only; 0 is no longer produced and its arms of ws_item are dead.
     int vstride;
     // vstride == 2 (round 5): the strided walk INSIDE one vertex range per XCD.  With 1 / 2 / 4 / 8 batch slices, G = 8 / slices
     // XCDs share a slice; the plain strided walk had each of them stream EVERY vertex of the slice through its own L2 (PMC: the
@@ -1656,140 +1638,196 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_stream_kernel(const WSParams p
     }
 }
 
-struct WGPlan {
-    int log2TB, n_btiles, n_vtiles, nvc, steps_per_block, nrc, ncg, ctw, cot;
-    int stream, vpc;    // streaming form: batch slice 1 << log2TB, nvc chunks of vpc vertices, ncg = ceil(K / 64)
-    int xg_G, xg_cpg, xg_Vg;      // > 0: one vertex range per XCD (WSParams::vstride == 2)
+// ------------------------------------------------------------------------------------------
+// The weight gradient's host half.  choose_wgrad decides once per call which kernel runs with which plan - plain arithmetic on
+// the shape and a summary of the call's alignment, no HIP call.  The entry point, the workspace query, sh_wgrad_f32_nsplit and
+// the deferred reduction all ask it; nothing else in the file tests a weight-gradient shape.  (DESIGN 4x has the table.)
+enum WGForm { WG_STAGED, WG_STREAM, WG_SPLIT3 };
+enum WGRefusal { WG_SERVED, WG_X_UNALIGNED, WG_X_OFFSETS, WG_STAGED_COUT };     // why a call cannot be served
+
+// what the decisions need to know of a call's tensors.  The defaults (the workspace queries): everything aligned, no pre-sum job
+struct WGCall {
+    bool x_ok = true;      // x serves the streaming forms: 16-byte aligned with strides of whole quads; 3 channels: 32-bit row offsets
+    int dp_quantum = 8;    // dpre is 16-byte aligned and both its strides are multiples of this many floats (8, 4, 2, 1); 0: not aligned
+    bool rider = false;    // a pre-sum job rides along and its rows take 16-byte accesses (but for Cout % 4, which the chooser tests)
 };
 
-WGPlan plan_wgrad(int B, int R, int S, int Cin, int Cout) {
-    WGPlan w;
-    w.xg_G = w.xg_cpg = w.xg_Vg = 0;
-    const int K = S * Cin;
+// staged form (wgrad_kernel): work item = (column group of 64 ctw columns, batch slice, vertex chunk), one per workgroup
+struct WGStaged {
+    int cot, ctw;          // template constants: output-channel tiles of 16 (1, 2, 4, 8), column-group width in 64s
+    int log2TB, n_btiles, n_vtiles, nvc, steps_per_block, ncg;      // as WGParams
+    size_t lds;
+};
+
+// streaming forms (wgrad_stream_kernel, wgrad_split3_kernel): work item = (64-column group, batch slice, vertex chunk), one per wave
+struct WGStream {
+    int ng;                // template constants: batch slice in groups of 4 rows (1, 4, 8),
+    bool full, c3;         //   the batch is whole slices, 3-channel input
+    bool x3;               // launches of 2 or 4 channel tiles run in the bf16x3 form (wgrad_group)
+    int log2TB, n_btiles, ncg, vpc, nvc, n_items, grid_main;        // as WSParams
+    int walk, xg_G, xg_cpg, xg_Vg;      // vertex walk (WSParams::vstride): 1 strided over the mesh, 2 strided inside one range per XCD
+    size_t lds;
+    bool fold;             // the pre-sum job rides as tail workgroups of the launch (false: it is a launch of its own)
+};
+
+struct WGChoice {
+    WGForm form;           // of the first (for <= 128 output channels: the only) launch
+    int nrc;               // partial slabs: all the workspace query and the reductions need
+    WGRefusal refused;
+    WGStaged g;            // form == WG_STAGED
+    WGStream s;            // otherwise
+};
+
+// One launch serves a group of <= 128 output channels starting at co0.  Its channel tiles, whether it runs in the bf16x3 form
+// and whether its tiles interleave depend on the group: a layer of more than 128 channels ends in a short one.
+//   bf16x3: 2 and 4 channel tiles (8 would need more than the 512 registers of a one-wave-per-SIMD kernel; one tile: the splits
+//   outweigh the matrix time saved)
+//   interleaved channel tiles (one gradient load per batch group instead of cot): all 16 cot channels of the launch exist and a
+//   lane's cot values are cot-float aligned
+struct WGGroup { int cot; bool split3, ilv; };
+WGGroup wgrad_group(int Cout, int co0, bool x3, bool c3, int dp_quantum) {
+    const int tiles = sh_cdiv(Cout - co0 < 128 ? Cout - co0 : 128, 16);
+    WGGroup g;
+    g.cot = tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 4 ? 4 : 8;
+    g.split3 = x3 && (g.cot == 2 || g.cot == 4);
+    g.ilv = !g.split3 && g.cot >= 2 && !c3 && Cout - co0 >= 16 * g.cot && dp_quantum >= g.cot;
+    return g;
+}
+
+WGChoice choose_wgrad(int B, int R, int S, int Cin, int Cout, int mma_mode, const WGCall& call = WGCall()) {
     constexpr int WG_TB = 8;              // batch slice of the staged form
     constexpr int WG_BLOCKS = 1024;       // workgroups it aims for
     constexpr int WS_SLAB_MB = 32;        // MiB of partial slabs the streaming form may write
-    int tb = 1;
-    while (tb < B && tb < WG_TB) tb <<= 1;
-    w.log2TB = sh_ilog2_floor(tb);
-    const int tv = TMW >> w.log2TB;
-    w.n_btiles = sh_cdiv(B, tb);
-    w.n_vtiles = sh_cdiv(R, tv);
-    const int cot = sh_cdiv(Cout < 128 ? Cout : 128, 16);      // more than 128 output channels: launches of <= 128 (streaming form)
-    w.cot = cot <= 1 ? 1 : cot <= 2 ? 2 : cot <= 4 ? 4 : 8;
-    // column-group width (64 or 128 weight columns): minimise the staged work per row, i.e. column
-    // groups x (gathered columns incl. the padding of the last group + the dpre channels re-read by
-    // every group); 128 channels x 128 columns would need 360 registers (1 wave/SIMD) -> 64 there.
-    {
-        const int cp = w.cot * 16;
+    WGChoice c{};
+    const int K = S * Cin;
+    // streaming form: Cin % 4 == 0 (16-byte gathers) or Cin == 3 (columns counted in padded quads); everything else is staged
+    if (!(Cin % 4 == 0 || Cin == 3)) {
+        c.form = WG_STAGED;
+        WGStaged& g = c.g;
+        int tb = 1;
+        while (tb < B && tb < WG_TB) tb <<= 1;
+        g.log2TB = sh_ilog2_floor(tb);
+        const int tv = TMW >> g.log2TB;
+        g.n_btiles = sh_cdiv(B, tb);
+        g.n_vtiles = sh_cdiv(R, tv);
+        g.cot = wgrad_group(Cout, 0, false, false, 0).cot;
+        // column-group width (64 or 128 weight columns): minimise the staged work per row, i.e. column
+        // groups x (gathered columns incl. the padding of the last group + the dpre channels re-read by
+        // every group); 128 channels x 128 columns would need 360 registers (1 wave/SIMD) -> 64 there.
+        const int cp = g.cot * 16;
         const long cost1 = (long)sh_cdiv(K, 64) * (64 + cp), cost2 = (long)sh_cdiv(K, 128) * (128 + cp);
-        w.ctw = (w.cot == 8 || cost1 <= cost2) ? 1 : 2;
+        g.ctw = (g.cot == 8 || cost1 <= cost2) ? 1 : 2;
+        g.ncg = sh_cdiv(K, 64 * g.ctw);
+        // vertex chunks per batch slice: enough blocks to fill the chip, few enough that the partial
+        // slabs stay small, and a table slice that fits its LDS area
+        int nvc = WG_BLOCKS / (g.ncg * g.n_btiles);
+        if (nvc < 1) nvc = 1;
+        if (nvc > g.n_vtiles) nvc = g.n_vtiles;
+        const int max_steps = WG_TABLE_CAP / (tv * S) > 0 ? WG_TABLE_CAP / (tv * S) : 1;
+        g.steps_per_block = sh_cdiv(g.n_vtiles, nvc);
+        if (g.steps_per_block > max_steps) g.steps_per_block = max_steps;
+        g.nvc = sh_cdiv(g.n_vtiles, g.steps_per_block);
+        c.nrc = g.nvc * g.n_btiles;
+        const int ldg = 64 * g.ctw + 16, ldp = g.cot == 1 ? 16 : g.cot * 16 + 16;       // the kernel's LDG, LDP
+        g.lds = (size_t)2 * TMW * (ldg + ldp) * sizeof(float) + (size_t)g.steps_per_block * tv * S * sizeof(int);
+        if (Cout > 128) c.refused = WG_STAGED_COUT;      // more than 128 output channels need the streaming form
+        return c;
     }
-    w.ncg = sh_cdiv(K, 64 * w.ctw);
-    // vertex chunks per batch slice: enough blocks to fill the chip, few enough that the partial
-    // slabs stay small, and a table slice that fits its LDS area
-    int nvc = WG_BLOCKS / (w.ncg * w.n_btiles);
-    if (nvc < 1) nvc = 1;
-    if (nvc > w.n_vtiles) nvc = w.n_vtiles;
-    const int max_steps = WG_TABLE_CAP / (tv * S) > 0 ? WG_TABLE_CAP / (tv * S) : 1;
-    w.steps_per_block = sh_cdiv(w.n_vtiles, nvc);
-    if (w.steps_per_block > max_steps) w.steps_per_block = max_steps;
-    w.nvc = sh_cdiv(w.n_vtiles, w.steps_per_block);
-    w.nrc = w.nvc * w.n_btiles;
-    // streaming form (wgrad_stream_kernel): work item = (64-column group, batch slice, vertex chunk), one per wave
-    w.stream = (Cin % 4 == 0 || Cin == 3) ? 1 : 0;
-    w.vpc = 0;
-    if (w.stream) {
-        // items: one wave per SIMD.  The 16 -> 3 layer's slabs are written by the role-swapped kernel (wgrad_thin.hip: one workgroup of four waves per slab, each
-        // wave paced by the latency of its own load ring): 512 slabs = two waves per SIMD instead of 340 = 1.33 (45 -> 36 us at 6890
-        // vertices, batch 64; the slabs are 1.9 KB each)
-        const int items_target = (Cin == 16 && Cout <= 3) ? 1536 : 1024;
-        // batch slice: 1 or 4 groups of 4 rows; 8 groups for ONE channel tile (a vertex is then 32 MFMAs instead of 16 behind the
-        // same table read and address arithmetic: 69.5 -> 62 us on the level-0 32 -> 16 layer; with two tiles the registers of the
-        // deeper prefetch cost more than that: 72 -> 78 us)
-        const int tbs = B <= 4 ? 4 : (B % 32 == 0 && Cout <= 16 && Cin != 3) ? 32 : 16;
-        w.log2TB = sh_ilog2_floor(tbs);
-        w.n_btiles = sh_cdiv(B, tbs);
-        w.ncg = sh_cdiv(Cin == 3 ? 4 * S : K, 64);            // 3-channel inputs: columns counted in padded quads
-        long nrc_t = items_target / w.ncg;
-        const long cap = ((long)WS_SLAB_MB << 20) / ((long)Cout * K * 4);     // partial slabs are written and re-read once
-        if (nrc_t > cap) nrc_t = cap;
-        if (nrc_t < 1) nrc_t = 1;
-        long nvc_t = nrc_t / w.n_btiles;
-        if (nvc_t < 1) nvc_t = 1;
-        if (nvc_t > R) nvc_t = R;
-        int vpc = sh_cdiv(R, (int)nvc_t);
-        const int vcap = 2048 / S > 0 ? 2048 / S : 1;          // table lines of a wave: <= 8 KiB of LDS
-        if (vpc > vcap) vpc = vcap;
-        // The table cap can force more items than the target (long spirals on fine levels).  All of them are resident at
-        // once, so what matters is that every CU gets the same number: round the item count up to a whole multiple of
-        // the target (measured at 27 554 vertices, spiral 18: 2.1 "rounds" ran at 67 TFLOP/s, 3.0 at ~95).
-        {
-            const long per_chunk = (long)w.ncg * w.n_btiles;
-            const long items = per_chunk * sh_cdiv(R, vpc);
-            if (items > items_target) {
-                const long rounds = (items + items_target - 1) / items_target;
-                long nvc_goal = rounds * items_target / per_chunk;
-                const long cap2 = 2 * cap / w.n_btiles;
-                if (nvc_goal > cap2) nvc_goal = cap2;
-                if (nvc_goal > sh_cdiv(R, vpc)) vpc = sh_cdiv(R, (int)nvc_goal);
-            }
-        }
-        w.vpc = vpc;
-        w.nvc = sh_cdiv(R, vpc);
-        w.nrc = w.nvc * w.n_btiles;
-        // one vertex range per XCD (WSParams::xg_*): 1 / 2 / 4 / 8 batch slices, not the layer the role-swapped kernel serves
-        if ((w.n_btiles == 1 || w.n_btiles == 2 || w.n_btiles == 4 || w.n_btiles == 8) && Cout > 3) {
-            const int G = 8 / w.n_btiles;
-            const int Vg = sh_cdiv(R, G);
-            // chunks per XCD: whole "rounds" of the item target (one wave per SIMD = items_target / 8 items per XCD), as many rounds
-            // as the general plan above settled on (table cap, slab budget), more if a chunk's table lines would not fit
-            const long per_xcd = items_target / 8 > 0 ? items_target / 8 : 1;
-            long rounds = ((long)w.ncg * w.n_btiles * w.nvc + items_target / 2) / items_target;
-            if (rounds < 1) rounds = 1;
-            const int vcap2 = 2048 / S > 0 ? 2048 / S : 1;          // table lines of a wave: <= 8 KiB of LDS
-            int cpg = 1;
-            for (;; ++rounds) {
-                cpg = (int)(rounds * per_xcd / w.ncg);
-                if (cpg < 1) cpg = 1;
-                if (cpg >= Vg) { cpg = Vg; break; }
-                if (sh_cdiv(Vg, cpg) <= vcap2) break;
-            }
-            w.xg_G = G; w.xg_cpg = cpg; w.xg_Vg = Vg;
-            w.vpc = sh_cdiv(Vg, cpg);
-            w.nvc = cpg * G;
-            w.nrc = 8 * cpg;
+    WGStream& s = c.s;
+    s.c3 = Cin == 3;
+    // items: one wave per SIMD.  The 16 -> 3 layer's slabs are written by the role-swapped kernel (wgrad_thin.hip: one workgroup of four waves per slab, each
+    // wave paced by the latency of its own load ring): 512 slabs = two waves per SIMD instead of 340 = 1.33 (45 -> 36 us at 6890
+    // vertices, batch 64; the slabs are 1.9 KB each)
+    const int items_target = (Cin == 16 && Cout <= 3) ? 1536 : 1024;
+    // batch slice: 1 or 4 groups of 4 rows; 8 groups for ONE channel tile (a vertex is then 32 MFMAs instead of 16 behind the
+    // same table read and address arithmetic: 69.5 -> 62 us on the level-0 32 -> 16 layer; with two tiles the registers of the
+    // deeper prefetch cost more than that: 72 -> 78 us).  So ng == 8 comes with cot == 1 (Cout <= 16) and a whole batch only.
+    const int tbs = B <= 4 ? 4 : (B % 32 == 0 && Cout <= 16 && !s.c3) ? 32 : 16;
+    s.log2TB = sh_ilog2_floor(tbs);
+    s.ng = tbs / 4;
+    s.full = (B & ((1 << s.log2TB) - 1)) == 0;
+    s.n_btiles = sh_cdiv(B, tbs);
+    s.ncg = sh_cdiv(s.c3 ? 4 * S : K, 64);            // 3-channel inputs: columns counted in padded quads
+    long nrc_t = items_target / s.ncg;
+    const long cap = ((long)WS_SLAB_MB << 20) / ((long)Cout * K * 4);     // partial slabs are written and re-read once
+    if (nrc_t > cap) nrc_t = cap;
+    if (nrc_t < 1) nrc_t = 1;
+    long nvc_t = nrc_t / s.n_btiles;
+    if (nvc_t < 1) nvc_t = 1;
+    if (nvc_t > R) nvc_t = R;
+    const int vcap = 2048 / S > 0 ? 2048 / S : 1;          // table lines of a wave: <= 8 KiB of LDS
+    s.vpc = sh_cdiv(R, (int)nvc_t);
+    if (s.vpc > vcap) s.vpc = vcap;
+    // The table cap can force more items than the target (long spirals on fine levels).  All of them are resident at
+    // once, so what matters is that every CU gets the same number: round the item count up to a whole multiple of
+    // the target (measured at 27 554 vertices, spiral 18: 2.1 "rounds" ran at 67 TFLOP/s, 3.0 at ~95).
+    {
+        const long per_chunk = (long)s.ncg * s.n_btiles;
+        const long items = per_chunk * sh_cdiv(R, s.vpc);
+        if (items > items_target) {
+            const long rounds = (items + items_target - 1) / items_target;
+            long nvc_goal = rounds * items_target / per_chunk;
+            const long cap2 = 2 * cap / s.n_btiles;
+            if (nvc_goal > cap2) nvc_goal = cap2;
+            if (nvc_goal > sh_cdiv(R, s.vpc)) s.vpc = sh_cdiv(R, (int)nvc_goal);
         }
     }
-    return w;
+    s.nvc = sh_cdiv(R, s.vpc);
+    c.nrc = s.nvc * s.n_btiles;
+    s.walk = 1;
+    s.grid_main = sh_cdiv(c.nrc * s.ncg, 4);
+    // one vertex range per XCD (WSParams::xg_*): 1 / 2 / 4 / 8 batch slices, not the layer the role-swapped kernel serves
+    if ((s.n_btiles == 1 || s.n_btiles == 2 || s.n_btiles == 4 || s.n_btiles == 8) && Cout > 3) {
+        s.walk = 2;
+        s.xg_G = 8 / s.n_btiles;
+        s.xg_Vg = sh_cdiv(R, s.xg_G);
+        // chunks per XCD: whole "rounds" of the item target (one wave per SIMD = items_target / 8 items per XCD), as many rounds
+        // as the general plan above settled on (table cap, slab budget), more if a chunk's table lines would not fit
+        const long per_xcd = items_target / 8 > 0 ? items_target / 8 : 1;
+        long rounds = ((long)s.ncg * c.nrc + items_target / 2) / items_target;
+        if (rounds < 1) rounds = 1;
+        int cpg = 1;
+        for (;; ++rounds) {
+            cpg = (int)(rounds * per_xcd / s.ncg);
+            if (cpg < 1) cpg = 1;
+            if (cpg >= s.xg_Vg) { cpg = s.xg_Vg; break; }
+            if (sh_cdiv(s.xg_Vg, cpg) <= vcap) break;
+        }
+        s.xg_cpg = cpg;
+        s.vpc = sh_cdiv(s.xg_Vg, cpg);
+        s.nvc = cpg * s.xg_G;
+        c.nrc = 8 * cpg;
+        s.grid_main = 8 * sh_cdiv(cpg * s.ncg, 4);
+    }
+    s.n_items = c.nrc * s.ncg;
+    s.lds = (size_t)4 * s.vpc * S * sizeof(int);
+    // bf16x3 form: asked for, whole slices of 16 batch entries, 16-byte gathers.  (The three-plane mode keeps the exact kernels:
+    // they host the pre-sum riders up to four channel tiles, the split ones only with two - measured 30 us per step in their
+    // favour once the riders also write plane images.)
+    s.x3 = mma_mode == SH_MMA_SPLIT3 && s.full && s.log2TB == 4 && Cin % 4 == 0;
+    const WGGroup g0 = wgrad_group(Cout, 0, s.x3, s.c3, call.dp_quantum);
+    c.form = g0.split3 ? WG_SPLIT3 : WG_STREAM;
+    // The pre-sum job rides as tail workgroups of the launch when a second wave of the kernel fits beside the first on a SIMD
+    // (exact form: up to four channel tiles; bf16x3 form: two) and the rows take 16-byte accesses; otherwise it is the launch of
+    // its own it used to be.  Measured: the seven foldable launches of a step were 58 us + their gaps.
+    s.fold = call.rider && Cout % 4 == 0 && Cout <= 128 && !s.c3 && (g0.split3 ? g0.cot == 2 : g0.cot <= 4);
+    if (!call.x_ok) c.refused = s.c3 ? WG_X_OFFSETS : WG_X_UNALIGNED;
+    return c;
 }
 
-template <int COT, int NG, bool FULL>
-int launch_ws(const WSParams& p, hipStream_t st) {
-    constexpr int DEPTH = COT <= 2 ? 3 : 2;       // vertices of loads in flight (deeper measured no faster)
-    const size_t smem = (size_t)4 * p.vpc * p.S * sizeof(int);
-    const int grid = p.grid_main + p.tail_blocks;
-    const bool c3 = p.Cin == 3;
-    ShProfScope ps(st, "wgrad_stream_kernel<%d, %d, %d, %s, %s>|R=%d B=%d K=%d N=%d grid=%d presum=%d", COT, NG, DEPTH, FULL ? "true" : "false",
-                   c3 ? "true" : "false", p.R, p.B, p.K, p.Cout, p.grid_main, p.tail_blocks ? p.tail_rows : 0);
-    // interleaved channel tiles (one gradient load per batch group instead of COT): all 16 COT channels of the launch exist and
-    // a lane's COT values are COT-float aligned
-    const bool ilv = COT >= 2 && !c3 && p.Cout - p.co0 >= 16 * COT && p.dp_sb % COT == 0 && p.dp_sv % COT == 0 &&
-                     (reinterpret_cast<uintptr_t>(p.dpre) & 15) == 0;
-    if constexpr (COT >= 2) {
-        if (ilv) {
-            snprintf(ps.name, sizeof ps.name, "wgrad_stream_kernel<%d, %d, %d, %s, ilv>|R=%d B=%d K=%d N=%d grid=%d presum=%d", COT, NG, DEPTH,
-                     FULL ? "true" : "false", p.R, p.B, p.K, p.Cout, p.grid_main, p.tail_blocks ? p.tail_rows : 0);
-            SH_LAUNCH_PS(ps, (wgrad_stream_kernel<COT, NG, DEPTH, FULL, false, true>), dim3(grid), dim3(NTHREADS), smem, st, p);
-            SH_CHECK_LAUNCH("wgrad_stream");
-            return SH_OK;
-        }
-    }
-    if (c3) SH_LAUNCH_PS(ps, (wgrad_stream_kernel<COT, NG, DEPTH, FULL, true>), dim3(grid), dim3(NTHREADS), smem, st, p);
-    else SH_LAUNCH_PS(ps, (wgrad_stream_kernel<COT, NG, DEPTH, FULL, false>), dim3(grid), dim3(NTHREADS), smem, st, p);
-    SH_CHECK_LAUNCH("wgrad_stream");
-    return SH_OK;
+// the tensors of a call with nrc partial slabs in `workspace`
+WGTensors wg_tensors(const float* dpre, int64_t dp_sv, int64_t dp_sb, const float* x, int64_t x_sv, int64_t x_sb, const int32_t* table,
+                     void* workspace, int nrc, int B, int R, int S, int Cin, int Cout) {
+    WGTensors t{};
+    t.dpre = dpre; t.dp_sv = dp_sv; t.dp_sb = dp_sb;
+    t.x = x; t.x_sv = x_sv; t.x_sb = x_sb; t.table = table;
+    t.slab = static_cast<float*>(workspace);
+    t.B = B; t.R = R; t.S = S; t.Cin = Cin; t.Cout = Cout; t.K = S * Cin;
+    t.slab_stride = (long)Cout * t.K;
+    t.bias_off = (long)nrc * t.slab_stride;
+    return t;
 }
+
 
 // ------------------------------------------------------------------------------------------
 // Weight gradient in the bf16x3 form (mma_mode SH_MMA_SPLIT3; Cin % 4 == 0, batch % 16 == 0, >= 2 output-channel
@@ -1924,53 +1962,6 @@ __global__ __launch_bounds__(NTHREADS) void wgrad_split3_kernel(const WSParams p
     }
 }
 
-template <int COT>
-int launch_ws3(const WSParams& p, hipStream_t st) {
-    const size_t smem = (size_t)4 * p.vpc * p.S * sizeof(int);
-    const int grid = p.grid_main + p.tail_blocks;
-    ShProfScope ps(st, "wgrad_split3_kernel<%d>|R=%d B=%d K=%d N=%d grid=%d presum=%d", COT, p.R, p.B, p.K, p.Cout, p.grid_main,
-                   p.tail_blocks ? p.tail_rows : 0);
-    SH_LAUNCH_PS(ps, (wgrad_split3_kernel<COT>), dim3(grid), dim3(NTHREADS), smem, st, p);
-    SH_CHECK_LAUNCH("wgrad_split3");
-    return SH_OK;
-}
-
-// does a streaming weight-gradient launch with `cot` channel tiles run in the bf16x3 form?
-// 2 and 4 channel tiles (8 would need more than the 512 registers of a one-wave-per-SIMD kernel; one tile: the splits outweigh
-// the matrix time saved)
-bool ws_uses_split3(int cot, const WSParams& p) {
-    const bool full = (p.B & ((1 << p.log2TB) - 1)) == 0;
-    // (the three-plane form keeps the exact weight-gradient kernels: they host the pre-sum riders up to four channel tiles, the
-    // split ones only with two - measured 30 us per step in their favour once the riders also write plane images)
-    return (cot == 2 || cot == 4) && sh_f32_mma_mode() == SH_MMA_SPLIT3 && full && p.log2TB == 4 && p.Cin % 4 == 0;
-}
-
-template <int COT>
-int dispatch_ws(const WSParams& p, hipStream_t st) {
-    const bool full = (p.B & ((1 << p.log2TB) - 1)) == 0;
-    if ((COT == 2 || COT == 4) && ws_uses_split3(COT, p)) return launch_ws3<(COT == 4 ? 4 : 2)>(p, st);
-    if (p.log2TB == 2) return full ? launch_ws<COT, 1, true>(p, st) : launch_ws<COT, 1, false>(p, st);
-    if constexpr (COT == 1) {
-        if (p.log2TB == 5) return launch_ws<COT, 8, true>(p, st);
-    }
-    return full ? launch_ws<COT, 4, true>(p, st) : launch_ws<COT, 4, false>(p, st);
-}
-
-template <int COT, int CTW>
-int launch_wg(const WGParams& p, const WGPlan& w, bool vec4, hipStream_t st) {
-    constexpr int KCW = 64 * CTW;
-    constexpr int LDG = KCW + 16;
-    constexpr int LDP = COT == 1 ? 16 : COT * 16 + 16;
-    const int tv = TMW >> w.log2TB;
-    const size_t smem = (size_t)2 * TMW * (LDG + LDP) * sizeof(float) + (size_t)w.steps_per_block * tv * p.S * sizeof(int);
-    dim3 grid(w.ncg * w.nrc);
-    ShProfScope ps(st, "wgrad_kernel<%d, %d, %s>|R=%d B=%d K=%d N=%d grid=%d", COT, CTW, vec4 ? "true" : "false", p.R, p.B, p.K,
-                   p.Cout, w.ncg * w.nrc);
-    if (vec4) SH_LAUNCH_PS(ps, (wgrad_kernel<COT, CTW, true>), grid, dim3(NTHREADS), smem, st, p);
-    else SH_LAUNCH_PS(ps, (wgrad_kernel<COT, CTW, false>), grid, dim3(NTHREADS), smem, st, p);
-    SH_CHECK_LAUNCH("wgrad");
-    return SH_OK;
-}
 
 __global__ void weight_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt, int S, int Cin, int Cout) {
     // wt[ci][s*Cout + co] = w[co][s*Cin + ci]
@@ -2138,14 +2129,119 @@ int sh_weight_transpose(const float* weight, float* weight_t, int S, int Cin, in
 }
 
 }  // extern "C"
+// The weight gradient's launchers sit here, behind the forward and backward-data entry points, so that their kernels are
+// instantiated - and laid out in the code object - after those passes' kernels, as they always were.
+namespace {
+
+// a runtime count of channel tiles (1, 2, 4, 8) as the compile-time constant the weight-gradient kernels are instantiated for
+template <class F>
+void with_cot(int cot, F&& f) {
+    switch (cot) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+constexpr int ws_depth(int cot) { return cot <= 2 ? 3 : 2; }      // vertices of loads in flight (deeper measured no faster)
+
+using WSKernel = void (*)(const WSParams);
+template <int COT, int NG, bool FULL>
+WSKernel ws_stream_kernel(bool c3, bool ilv) {
+    constexpr int DEPTH = ws_depth(COT);
+    if constexpr (COT >= 2) {
+        if (ilv) return wgrad_stream_kernel<COT, NG, DEPTH, FULL, false, true>;
+    }
+    return c3 ? wgrad_stream_kernel<COT, NG, DEPTH, FULL, true> : wgrad_stream_kernel<COT, NG, DEPTH, FULL, false>;
+}
+
+// the kernel of a streaming launch: the one place where the choice becomes template constants
+template <int COT>
+WSKernel ws_kernel(const WGStream& s, const WGGroup& g) {
+    if constexpr (COT == 2 || COT == 4) {
+        if (g.split3) return wgrad_split3_kernel<COT>;
+    }
+    if (s.ng == 1) return s.full ? ws_stream_kernel<COT, 1, true>(s.c3, g.ilv) : ws_stream_kernel<COT, 1, false>(s.c3, g.ilv);
+    if (s.ng == 8) {              // choose_wgrad: one channel tile, whole batch - no other instance exists
+        if constexpr (COT == 1) return ws_stream_kernel<1, 8, true>(s.c3, g.ilv);
+        else return nullptr;
+    }
+    return s.full ? ws_stream_kernel<COT, 4, true>(s.c3, g.ilv) : ws_stream_kernel<COT, 4, false>(s.c3, g.ilv);
+}
+
+// launches the streaming kernel of the choice for the channel group g, which starts at p.co0
+int launch_ws(const WGStream& s, const WGGroup& g, const WSParams& p, hipStream_t st) {
+    WSKernel kernel = nullptr;
+    with_cot(g.cot, [&](auto cot) { kernel = ws_kernel<decltype(cot)::value>(s, g); });
+    SH_REQUIRE(kernel, SH_ERR_LAUNCH, "sh_spiral_conv_bwd_wgt: no kernel with %d channel tiles and %d batch groups", g.cot, s.ng);
+    char inst[64];
+    if (g.split3) snprintf(inst, sizeof inst, "wgrad_split3_kernel<%d>", g.cot);
+    else snprintf(inst, sizeof inst, "wgrad_stream_kernel<%d, %d, %d, %s, %s>", g.cot, s.ng, ws_depth(g.cot), s.full ? "true" : "false",
+                  g.ilv ? "ilv" : s.c3 ? "true" : "false");
+    ShProfScope ps(st, "%s|R=%d B=%d K=%d N=%d grid=%d presum=%d", inst, p.R, p.B, p.K, p.Cout, p.grid_main, p.tail_blocks ? p.tail_rows : 0);
+    SH_LAUNCH_PS(ps, kernel, dim3(p.grid_main + p.tail_blocks), dim3(NTHREADS), s.lds, st, p);
+    SH_CHECK_LAUNCH(g.split3 ? "wgrad_split3" : "wgrad_stream");
+    return SH_OK;
+}
+
+// launches the staged kernel of the choice
+int launch_wg(const WGStaged& g, int nrc, const WGParams& p, hipStream_t st) {
+    using WGKernel = void (*)(const WGParams);
+    WGKernel kernel = nullptr;
+    with_cot(g.cot, [&](auto cot) {
+        constexpr int COT = decltype(cot)::value;
+        kernel = g.ctw == 1 ? wgrad_kernel<COT, 1> : wgrad_kernel<COT, 2>;
+    });
+    // (the name keeps the third template argument the kernel had: the benchmark's tables and the committed profiles read it)
+    ShProfScope ps(st, "wgrad_kernel<%d, %d, false>|R=%d B=%d K=%d N=%d grid=%d", g.cot, g.ctw, p.R, p.B, p.K, p.Cout, g.ncg * nrc);
+    SH_LAUNCH_PS(ps, kernel, dim3(g.ncg * nrc), dim3(NTHREADS), g.lds, st, p);
+    SH_CHECK_LAUNCH("wgrad");
+    return SH_OK;
+}
+
+// the kernels' parameters, from the choice
+WGParams wg_params(const WGTensors& t, const WGStaged& g) {
+    WGParams p{};
+    static_cast<WGTensors&>(p) = t;
+    p.log2TB = g.log2TB; p.n_btiles = g.n_btiles; p.n_vtiles = g.n_vtiles; p.nvc = g.nvc; p.steps_per_block = g.steps_per_block; p.ncg = g.ncg;
+    return p;
+}
+
+// a pre-sum job: sum_out[r] = sum_e val[e] dpre[col[e]] for `rows` rows (+ the rows' plane image)
+struct WGRider { const int32_t* rowptr; const int32_t* col; const float* val; float* out; void* out_planes; int rows; };
+
+int ws_params(WSParams& p, const WGTensors& t, const WGStream& s, const WGRider& r) {
+    constexpr int WS_TAIL_BLOCKS = 768;      // at most this many tail workgroups
+    p = WSParams{};
+    static_cast<WGTensors&>(p) = t;
+    p.log2TB = s.log2TB; p.n_btiles = s.n_btiles; p.nvc = s.nvc; p.vpc = s.vpc; p.ncg = s.ncg;
+    p.n_items = s.n_items; p.grid_main = s.grid_main;
+    p.vstride = s.walk; p.xg_G = s.xg_G; p.xg_cpg = s.xg_cpg; p.xg_Vg = s.xg_Vg;
+    if (!s.fold) return SH_OK;
+    const long items = (long)r.rows * (((long)t.B * (t.Cout / 4) + 255) / 256);
+    p.tail_blocks = (int)(items < WS_TAIL_BLOCKS ? items : WS_TAIL_BLOCKS);
+    p.tail_rows = r.rows; p.tail_rowptr = r.rowptr; p.tail_col = r.col; p.tail_val = r.val; p.tail_y = r.out;
+    if (r.out_planes) {
+        SH_REQUIRE(t.dp_sb == t.Cout && t.dp_sv == (long)t.B * t.Cout && sh_p3_bytes(1, t.B, t.Cout) &&
+                       (reinterpret_cast<uintptr_t>(r.out_planes) & 15) == 0,
+                   SH_ERR_UNSUPPORTED, "sh_spiral_conv_bwd_wgt_presum: B=%d Cout=%d has no plane image", t.B, t.Cout);
+        p.tail_img = static_cast<char*>(r.out_planes);
+        p.tail_img_bgb = t.Cout == 16 ? 1536 : (long)(t.Cout / 32) * 3072;
+        p.tail_img_vb = p.tail_img_bgb * (t.B / 16);
+    }
+    return SH_OK;
+}
+
+}  // namespace
+
 // slab count of the fp32 weight-gradient plan; shared with the thin-layer kernel in wgrad_thin.hip
-int sh_wgrad_f32_nsplit(int B, int R, int S, int Cin, int Cout) { return plan_wgrad(B, R, S, Cin, Cout).nrc; }
+int sh_wgrad_f32_nsplit(int B, int R, int S, int Cin, int Cout) { return choose_wgrad(B, R, S, Cin, Cout, SH_MMA_EXACT).nrc; }
 extern "C" {
 
 size_t sh_spiral_conv_bwd_wgt_workspace(int B, int R, int S, int Cin, int Cout) {
     if (B <= 0 || R <= 0 || S <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    const WGPlan w = plan_wgrad(B, R, S, Cin, Cout);
-    return (size_t)w.nrc * ((size_t)Cout * S * Cin + Cout) * sizeof(float);
+    return (size_t)sh_wgrad_f32_nsplit(B, R, S, Cin, Cout) * ((size_t)Cout * S * Cin + Cout) * sizeof(float);
 }
 
 int sh_spiral_conv_bwd_wgt(const float* dpre, int64_t dp_sv, int64_t dp_sb, const float* x, int64_t x_sv, int64_t x_sb,
@@ -2169,109 +2265,63 @@ int sh_spiral_conv_bwd_wgt_presum(const float* dpre, int64_t dp_sv, int64_t dp_s
     SH_REQUIRE(workspace_bytes >= sh_spiral_conv_bwd_wgt_workspace(B, R, S, Cin, Cout), SH_ERR_WORKSPACE,
                "sh_spiral_conv_bwd_wgt: workspace too small");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const WGPlan w = plan_wgrad(B, R, S, Cin, Cout);
-    WGParams p{};
-    p.dpre = dpre; p.dp_sv = dp_sv; p.dp_sb = dp_sb;
-    p.x = x; p.x_sv = x_sv; p.x_sb = x_sb; p.table = table;
-    p.slab = static_cast<float*>(workspace);
-    p.B = B; p.R = R; p.S = S; p.Cin = Cin; p.Cout = Cout; p.K = S * Cin;
-    p.slab_stride = (long)Cout * p.K;
-    p.bias_off = (long)w.nrc * p.slab_stride;
-    p.log2TB = w.log2TB; p.n_btiles = w.n_btiles; p.n_vtiles = w.n_vtiles; p.nvc = w.nvc; p.steps_per_block = w.steps_per_block; p.ncg = w.ncg;
-    const bool vec4 = (Cin % 4 == 0) && (x_sv % 4 == 0) && (x_sb % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
-                      (reinterpret_cast<uintptr_t>(dpre) % 16 == 0);
+    const uintptr_t dp_addr = reinterpret_cast<uintptr_t>(dpre);
+    WGCall call;
+    call.x_ok = Cin == 3 ? (long)2 * (R + 1) * x_sv < 0x7fffffffL
+                         : (x_sv % 4 == 0) && (x_sb % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0);
+    call.dp_quantum = dp_addr % 16 != 0 ? 0 : (dp_sv | dp_sb) % 8 == 0 ? 8 : (dp_sv | dp_sb) % 4 == 0 ? 4 : (dp_sv | dp_sb) % 2 == 0 ? 2 : 1;
+    call.rider = sum_rows > 0 && (dp_sv % 4 == 0) && (dp_sb % 4 == 0) && ((dp_addr | reinterpret_cast<uintptr_t>(sum_out)) % 16 == 0);
+    const WGChoice c = choose_wgrad(B, R, S, Cin, Cout, mma_mode, call);
+    SH_REQUIRE(c.refused != WG_X_UNALIGNED, SH_ERR_UNSUPPORTED,
+               "sh_spiral_conv_bwd_wgt: x must be 16-byte aligned with strides that are multiples of 4 floats");
+    SH_REQUIRE(c.refused != WG_X_OFFSETS, SH_ERR_UNSUPPORTED,
+               "sh_spiral_conv_bwd_wgt: 3-channel input too large for 32-bit row offsets (R %d, row stride %ld)", R, (long)x_sv);
+    const WGTensors t = wg_tensors(dpre, dp_sv, dp_sb, x, x_sv, x_sb, table, workspace, c.nrc, B, R, S, Cin, Cout);
     int rc;
-    if (w.stream) {
-        SH_REQUIRE(Cin == 3 || ((x_sv % 4 == 0) && (x_sb % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0)), SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_bwd_wgt: x must be 16-byte aligned with strides that are multiples of 4 floats");
-        SH_REQUIRE(Cin != 3 || (long)2 * (R + 1) * x_sv < 0x7fffffffL, SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_bwd_wgt: 3-channel input too large for 32-bit row offsets (R %d, row stride %ld)", R, (long)x_sv);
-        WSParams s{};
-        s.dpre = dpre; s.dp_sv = dp_sv; s.dp_sb = dp_sb; s.x = x; s.x_sv = x_sv; s.x_sb = x_sb; s.table = table;
-        s.slab = p.slab; s.slab_stride = p.slab_stride; s.bias_off = p.bias_off;
-        s.B = B; s.R = R; s.S = S; s.Cin = Cin; s.Cout = Cout; s.K = p.K;
-        s.log2TB = w.log2TB; s.n_btiles = w.n_btiles; s.nvc = w.nvc; s.vpc = w.vpc; s.ncg = w.ncg;
-        s.n_items = w.nrc * w.ncg;
-        s.grid_main = sh_cdiv(s.n_items, 4);
-        s.vstride = 1;
-        if (w.xg_G > 0) {
-            s.vstride = 2; s.xg_G = w.xg_G; s.xg_cpg = w.xg_cpg; s.xg_Vg = w.xg_Vg;
-            s.grid_main = 8 * sh_cdiv(w.xg_cpg * w.ncg, 4);
-        }
-        // The pre-sum job rides as tail workgroups of this launch when a second wave of the kernel fits beside the first on
-        // a SIMD (exact form: up to four channel tiles; bf16x3 form: two) and the rows take 16-byte accesses; otherwise it is
-        // the launch of its own it used to be.  Measured: the seven foldable launches of a step were 58 us + their gaps.
-        constexpr int WS_TAIL_BLOCKS = 768;      // at most this many tail workgroups
-        const bool sum_vec = (Cout % 4 == 0) && (dp_sv % 4 == 0) && (dp_sb % 4 == 0) &&
-                             ((reinterpret_cast<uintptr_t>(dpre) | reinterpret_cast<uintptr_t>(sum_out)) % 16 == 0);
-        const bool fold = sum_rows > 0 && sum_vec && Cout <= 128 && !(Cin == 3) &&
-                    (ws_uses_split3(w.cot, s) ? w.cot == 2 : w.cot <= 4);
-        if (sum_rows > 0 && !fold) {
-            rc = sh_spmm_p3(sum_rowptr, sum_col, sum_val, dpre, dp_sv, dp_sb, sum_out, dp_sv, dp_sb, sum_out_planes, nullptr, 0, 0, 0, -1, B,
-                            sum_rows, Cout, stream);
-            if (rc != SH_OK) return rc;
-        }
-        if (fold) {
-            const long items = (long)sum_rows * (((long)B * (Cout / 4) + 255) / 256);
-            s.tail_blocks = (int)(items < WS_TAIL_BLOCKS ? items : WS_TAIL_BLOCKS);
-            s.tail_rows = sum_rows; s.tail_rowptr = sum_rowptr; s.tail_col = sum_col; s.tail_val = sum_val; s.tail_y = sum_out;
-            if (sum_out_planes) {
-                SH_REQUIRE(dp_sb == Cout && dp_sv == (int64_t)B * Cout && sh_p3_bytes(1, B, Cout) && (reinterpret_cast<uintptr_t>(sum_out_planes) & 15) == 0,
-                           SH_ERR_UNSUPPORTED, "sh_spiral_conv_bwd_wgt_presum: B=%d Cout=%d has no plane image", B, Cout);
-                s.tail_img = static_cast<char*>(sum_out_planes);
-                s.tail_img_bgb = Cout == 16 ? 1536 : (long)(Cout / 32) * 3072;
-                s.tail_img_vb = s.tail_img_bgb * (B / 16);
-            }
-        }
-        rc = SH_OK;
+    if (sum_rows > 0 && !c.s.fold) {          // the pre-sum job as a launch of its own
+        rc = sh_spmm_p3(sum_rowptr, sum_col, sum_val, dpre, dp_sv, dp_sb, sum_out, dp_sv, dp_sb, sum_out_planes, nullptr, 0, 0, 0, -1, B,
+                        sum_rows, Cout, stream);
+        if (rc != SH_OK) return rc;
+    }
+    SH_REQUIRE(c.refused != WG_STAGED_COUT, SH_ERR_UNSUPPORTED,      // (behind the pre-sum launch, where it has always been)
+               "sh_spiral_conv_bwd_wgt: more than 128 output channels (%d) need input channels that are a multiple of 4 (or 3)", Cout);
+    if (c.form == WG_STAGED) {
+        rc = launch_wg(c.g, c.nrc, wg_params(t, c.g), st);
+    } else {
+        WSParams s;
+        rc = ws_params(s, t, c.s, WGRider{sum_rowptr, sum_col, sum_val, sum_out, sum_out_planes, sum_rows});
         for (int co0 = 0; co0 < Cout && rc == SH_OK; co0 += 128) {          // one launch per group of <= 128 output channels
             s.co0 = co0;
-            const int tiles = sh_cdiv((Cout - co0 < 128 ? Cout - co0 : 128), 16);
-            const int cg_t = tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 4 ? 4 : 8;
-            rc = cg_t == 1 ? dispatch_ws<1>(s, st) : cg_t == 2 ? dispatch_ws<2>(s, st) : cg_t == 4 ? dispatch_ws<4>(s, st) : dispatch_ws<8>(s, st);
+            rc = launch_ws(c.s, wgrad_group(Cout, co0, c.s.x3, c.s.c3, call.dp_quantum), s, st);
         }
-    } else {
-        if (sum_rows > 0) {
-            rc = sh_spmm_p3(sum_rowptr, sum_col, sum_val, dpre, dp_sv, dp_sb, sum_out, dp_sv, dp_sb, sum_out_planes, nullptr, 0, 0, 0, -1, B,
-                            sum_rows, Cout, stream);
-            if (rc != SH_OK) return rc;
-        }
-        SH_REQUIRE(Cout <= 128, SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_bwd_wgt: more than 128 output channels (%d) need input channels that are a multiple of 4 (or 3)", Cout);
-#define SH_WG_CASE(C, T) rc = launch_wg<C, T>(p, w, vec4, st)
-    if (w.ctw == 1) {
-        if (w.cot == 1) SH_WG_CASE(1, 1); else if (w.cot == 2) SH_WG_CASE(2, 1); else if (w.cot == 4) SH_WG_CASE(4, 1); else SH_WG_CASE(8, 1);
-    } else {
-        if (w.cot == 1) SH_WG_CASE(1, 2); else if (w.cot == 2) SH_WG_CASE(2, 2); else if (w.cot == 4) SH_WG_CASE(4, 2); else SH_WG_CASE(8, 2);
     }
-    }
-#undef SH_WG_CASE
     if (rc != SH_OK) return rc;
     if (!dW) return SH_OK;            // deferred: the caller reduces several layers at once (.._reduce_multi)
-    const long n = p.slab_stride;
+    const long n = t.slab_stride;
     ShProfScope ps(st, "slab_reduce_kernel");
-    SH_LAUNCH_PS(ps, slab_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, st, p.slab, p.slab_stride, w.nrc, n, dW);
+    SH_LAUNCH_PS(ps, slab_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(1024), 0, st, t.slab, t.slab_stride, c.nrc, n, dW);
     if (dbias)
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(1024), 0, st, p.slab + p.bias_off,
-                           (long)Cout, w.nrc, (long)Cout, dbias);
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((Cout + 63) / 64)), dim3(1024), 0, st, t.slab + t.bias_off,
+                           (long)Cout, c.nrc, (long)Cout, dbias);
     SH_CHECK_LAUNCH("slab_reduce");
     return SH_OK;
 }
 
+
 static int reduce_multi_impl(int n_layers, const void* const* workspaces, float* const* dW, float* const* dbias, const int* B,
-                             const int* R, const int* S, const int* Cin, const int* Cout, bool bf16_plan_all, sh_stream_t stream,
-                             const int* kinds = nullptr) {
+                             const int* R, const int* S, const int* Cin, const int* Cout, const int* kinds, int default_kind,
+                             sh_stream_t stream) {       // plan kind of layer i: kinds[i], or default_kind without a list
     SH_REQUIRE(n_layers > 0 && 2 * n_layers <= MR_MAX && workspaces && dW && dbias && B && R && S && Cin && Cout,
                SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_wgt_reduce_multi: bad argument (at most %d layers)", MR_MAX / 2);
     MultiReduce m{};
     int nd = 0, blocks = 0;
     for (int i = 0; i < n_layers; ++i) {
         SH_REQUIRE(workspaces[i] && dW[i], SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_wgt_reduce_multi: null pointer in layer %d", i);
-        const int kind = kinds ? kinds[i] : (bf16_plan_all ? 1 : 0);
+        const int kind = kinds ? kinds[i] : default_kind;
         SH_REQUIRE(kind >= 0 && kind <= 2, SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_wgt_reduce_multi: unknown plan kind %d of layer %d", kind, i);
         const bool bf16_plan = kind == 1;                      // (slab-walk form below; the three-plane plan has the fp32 plan's slab counts)
         const int nrc = kind == 1 ? sh_wgrad_bf16_nsplit(B[i], R[i], S[i], Cin[i], Cout[i])
-                        : kind == 2 ? sh_wgrad_p3_nslab(B[i], R[i], S[i], Cin[i], Cout[i]) : plan_wgrad(B[i], R[i], S[i], Cin[i], Cout[i]).nrc;
+                        : kind == 2 ? sh_wgrad_p3_nslab(B[i], R[i], S[i], Cin[i], Cout[i]) : sh_wgrad_f32_nsplit(B[i], R[i], S[i], Cin[i], Cout[i]);
         SH_REQUIRE(nrc > 0, SH_ERR_UNSUPPORTED, "sh_spiral_conv_bwd_wgt_reduce_multi: layer %d has no plan of kind %d", i, kind);
         const long stride = (long)Cout[i] * S[i] * Cin[i];
         const float* slab = static_cast<const float*>(workspaces[i]);
@@ -2302,20 +2352,20 @@ static int reduce_multi_impl(int n_layers, const void* const* workspaces, float*
 int sh_spiral_conv_bwd_wgt_reduce_multi(int n_layers, const void* const* workspaces, float* const* dW, float* const* dbias,
                                         const int* B, const int* R, const int* S, const int* Cin, const int* Cout,
                                         sh_stream_t stream) {
-    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, false, stream);
+    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, nullptr, 0, stream);
 }
 
 int sh_spiral_conv_bwd_wgt_reduce_multi_kinds(int n_layers, const void* const* workspaces, float* const* dW, float* const* dbias,
                                               const int* B, const int* R, const int* S, const int* Cin, const int* Cout,
                                               const int* kinds, sh_stream_t stream) {
     SH_REQUIRE(kinds, SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_wgt_reduce_multi_kinds: no kinds");
-    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, false, stream, kinds);
+    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, kinds, 0, stream);
 }
 
 int sh_spiral_conv_bwd_wgt_reduce_multi_bf16(int n_layers, const void* const* workspaces, float* const* dW, float* const* dbias,
                                              const int* B, const int* R, const int* S, const int* Cin, const int* Cout,
                                              sh_stream_t stream) {
-    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, true, stream);
+    return reduce_multi_impl(n_layers, workspaces, dW, dbias, B, R, S, Cin, Cout, nullptr, 1, stream);
 }
 
 int sh_weight_transpose_multi(int n_layers, const float* const* weight, float* const* weight_t, const int* S, const int* Cin,
