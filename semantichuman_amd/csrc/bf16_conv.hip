@@ -452,17 +452,6 @@ __global__ __launch_bounds__(256) void wfrag_prep_kernel(const WFragArgs a) {
     a.out[d][i] = *reinterpret_cast<const u32x4*>(&o);
 }
 
-int g_num_cus = 0;
-int num_cus() {
-    if (!g_num_cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) g_num_cus = prop.multiProcessorCount;
-        if (g_num_cus <= 0) g_num_cus = 256;
-    }
-    return g_num_cus;
-}
-
 template <int NT, int RT, int MODE, bool BWD, bool OUTF32>
 int launch_bc(BCParams& p, hipStream_t st) {
     auto kern = conv_bf16_kernel<NT, RT, MODE, BWD, OUTF32>;
@@ -473,22 +462,10 @@ int launch_bc(BCParams& p, hipStream_t st) {
     const long tiles = (long)p.n_vg * sh_cdiv(p.B, 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_bf16: %ld work items", tiles);
     p.n_tiles = (int)tiles;
-    // waves per workgroup and workgroups per CU from the LDS footprint of the resident weight (<= 16 waves per CU: the
-    // kernel is built for <= 128 VGPRs)
-    const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    int nw = 16 / per_cu;
-    // few work items (coarse levels): as many resident waves as there are items (loads in flight per CU are what these
-    // launches live on), fewer waves per workgroup only when even one item per wave leaves waves idle
-    while (nw > 4 && (long)num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
-    long groups = (tiles + nw - 1) / nw;                         // workgroups (per channel slice) that still get an item
-    const long cap = (long)num_cus() * per_cu / p.nsplit;
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;                               // a multiple of 8 per slice -> every XCD label has all slices
-    const int grid = (int)groups * p.nsplit;
+    const ShGrid g = sh_resident_grid(smem, tiles, p.nsplit, sh_num_cus());
     ShProfScope ps(st, "conv_bf16_kernel<%d, %d, %d, %s, %s>|R=%d B=%d S=%d Cg=%d N=%d grid=%dx%d", NT, RT, MODE, BWD ? "true" : "false",
-                   OUTF32 ? "true" : "false", p.R, p.B, p.S, p.Cg, p.Nout, grid, nw * 64);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(nw * 64), smem, st, p);
+                   OUTF32 ? "true" : "false", p.R, p.B, p.S, p.Cg, p.Nout, g.grid, g.waves * 64);
+    SH_LAUNCH_PS(ps, kern, dim3(g.grid), dim3(g.waves * 64), smem, st, p);
     SH_CHECK_LAUNCH("conv_bf16");
     return SH_OK;
 }
@@ -503,17 +480,9 @@ int launch_bcr(BCParams& p, hipStream_t st) {
     const long tiles = (long)p.R * sh_cdiv(p.B, 16);
     SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_bf16r: %ld work items", tiles);
     p.n_tiles = (int)tiles;
-    const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    int nw = 16 / per_cu;
-    while (nw > 4 && (long)num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
-    long groups = (tiles + nw - 1) / nw;
-    const long cap = (long)num_cus() * per_cu / p.nsplit;
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;
-    const int grid = (int)groups * p.nsplit;
-    ShProfScope ps(st, "conv_bf16r_kernel<%d>|R=%d B=%d S=%d Cg=%d N=%d grid=%dx%d L=%d", NT, p.R, p.B, p.S, p.Cg, p.Nout, grid, nw * 64, p.rag_L);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(nw * 64), smem, st, p);
+    const ShGrid g = sh_resident_grid(smem, tiles, p.nsplit, sh_num_cus());
+    ShProfScope ps(st, "conv_bf16r_kernel<%d>|R=%d B=%d S=%d Cg=%d N=%d grid=%dx%d L=%d", NT, p.R, p.B, p.S, p.Cg, p.Nout, g.grid, g.waves * 64, p.rag_L);
+    SH_LAUNCH_PS(ps, kern, dim3(g.grid), dim3(g.waves * 64), smem, st, p);
     SH_CHECK_LAUNCH("conv_bf16r");
     return SH_OK;
 }
@@ -534,7 +503,7 @@ int dispatch_bc_nt(BCParams& p, hipStream_t st) {
     while (nt > 1 && (long)p.nks * nt > 128) { nt >>= 1; p.nsplit <<= 1; }
     SH_REQUIRE((long)p.nks * nt <= 150, SH_ERR_UNSUPPORTED, "conv_bf16: K = %d too long for an LDS-resident weight slice", p.nks * 32);
     const long tiles16 = (long)p.R * sh_cdiv(p.B, 16);      // work items if every wave took ONE vertex
-    const long fill = 2L * num_cus() * 16;                       // aim for >= 2 items per resident wave
+    const long fill = 2L * sh_num_cus() * 16;                      // aim for >= 2 items per resident wave
     if constexpr (OUTF32 || MODE == BC_C3F) {
         SH_REQUIRE(nt == 1 && p.nsplit == 1, SH_ERR_UNSUPPORTED, "conv_bf16: a 3-channel fp32 side needs <= 16 channels on the other (%d)",
                    p.Nout);

@@ -108,14 +108,8 @@ __device__ __forceinline__ bool p3_ring_steps(int ks, int nks, F&& f) {
 #ifndef P3_WAVES_PER_EU
 #define P3_WAVES_PER_EU 4
 #endif
-constexpr int P3_WAVES_CU = 4 * P3_WAVES_PER_EU;      // resident waves per CU the registers allow (the launchers' 16 / 8 / 4 waves per workgroup)
-static_assert(P3_WAVES_CU == 16, "the launchers size workgroups for 16 resident waves per CU");
-// Diagnostic builds only (tools/exp/r06_p3_ablate.sh; never the shipped library): what of a k-step is left in conv_p3_kernel -
-// 1: no gathered loads (operands from registers), 2: the loads alone (no weight reads, no MFMAs), 3: loads + weight-fragment reads from
-// LDS, no MFMAs, 4: loads + MFMAs with weight fragments from registers (no LDS reads).  Results are garbage; times tell what bounds it.
-#ifndef P3_ABLATE
-#define P3_ABLATE 0
-#endif
+// resident waves per CU the registers allow: what sh_resident_grid sizes the launchers' 16 / 8 / 4 waves per workgroup for
+static_assert(4 * P3_WAVES_PER_EU == SH_RESIDENT_WAVES_CU, "the launchers size workgroups for 16 resident waves per CU");
 template <int NT, int RT, bool C16, bool BWD, int NP, bool F32R = false>      // F32R: rows >= n_img are read as fp32 and split here
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(P3_WAVES_PER_EU, 8))) void conv_p3_kernel(const P3Params p) {
     constexpr int D = p3_depth(NT, RT);
@@ -186,13 +180,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(P3_WAVES_P
                     const char* src = f32row ? reinterpret_cast<const char*>(p.xf + (long)row * p.xf_sv + (long)(bs * 16 + r16) * p.xf_sb + lc * 32 + kq * 8)
                                              : xl + (F32R ? (long)row * p.x_vb : (long)((unsigned long)(unsigned)row << 4)) + (long)lc * 3072;
                     const int o1 = f32row ? 16 : PB, o2 = f32row ? 0 : 2 * PB;
-                    if constexpr (P3_ABLATE == 1) {
-                        a[m][0] = a[m][1] = a[m][2] = (u32x4){(unsigned)row, (unsigned)lane, (unsigned)lc, 0x3f803f80u};
-                    } else {
                     a[m][0] = *reinterpret_cast<const u32x4*>(src);
                     a[m][1] = *reinterpret_cast<const u32x4*>(src + o1);
                     a[m][2] = *reinterpret_cast<const u32x4*>(src + o2);
-                    }
                 }
                 if (++lc >= p.ncg) { lc = 0; ++ls; }
             } else {
@@ -265,25 +255,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(P3_WAVES_P
                     }
                 }
             }
-            if constexpr (P3_ABLATE == 2) {
-#pragma unroll
-                for (int m = 0; m < RT; ++m) acc[m][0][0] += __builtin_bit_cast(float, a[m][0][0] ^ a[m][1][1] ^ a[m][2][2]);
-                return;
-            }
             const u32x4* wk = Wl + ((long)ks * NT) * 192 + lane;
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
-                u32x4 r0, r1, r2;
-                if constexpr (P3_ABLATE == 4) {
-                    r0 = (u32x4){(unsigned)lane, 0x3f803f80u, (unsigned)n, 1u}; r1 = r0; r2 = r0;
-                } else {
-                    r0 = wk[n * 192]; r1 = wk[n * 192 + 64]; r2 = wk[n * 192 + 128];
-                }
-                if constexpr (P3_ABLATE == 3) {
-#pragma unroll
-                    for (int m = 0; m < RT; ++m) acc[m][n][0] += __builtin_bit_cast(float, r0[0] ^ r1[1] ^ r2[2] ^ a[m][0][0] ^ a[m][1][1] ^ a[m][2][2]);
-                    continue;
-                }
+                const u32x4 r0 = wk[n * 192], r1 = wk[n * 192 + 64], r2 = wk[n * 192 + 128];
                 const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&r0), wm = *reinterpret_cast<const bf16x8*>(&r1),
                              wl = *reinterpret_cast<const bf16x8*>(&r2);
 #pragma unroll
@@ -945,209 +920,229 @@ __global__ __launch_bounds__(256) void wfrag3_prep_kernel(const WFrag3Args a) {
     o[0] = h; o[64] = m; o[128] = l;
 }
 
-int p3_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
+// ------------------------------------------------------------------------------------------
+// The choice: which kernel a call of this family launches, with which tile counts, decided in ONE place from the
+// shape alone.  The entry points launch what it says, the predicates (sh_spiral_conv_p3_ok, _kind, _rag_ok, _grp_ok, _grp_members)
+// and the fragment-buffer sizes (sh_conv_wfrag3_bytes, sh_conv_wfrag3_prep_multi) read it, so none of them can disagree.
+enum P3Form { P3_REFUSED, P3_RESIDENT, P3_STREAMED, P3_RAGGED, P3_GROUPED };
+enum P3List { P3_NO_LIST, P3_RAG_LIST, P3_GRP_LIST };
+enum P3Why { P3_TAKEN, P3_WHY_SHAPE, P3_WHY_LIST, P3_WHY_F32_STREAMED, P3_WHY_F32_NP };
+struct P3Choice {
+    int form, why;                   // P3Form; P3Why, the refusal code of P3_REFUSED
+    // the fragment buffer's geometry, filled whatever the form (a refused layer still has a buffer size): k-steps (whole chunks where
+    // the weight is streamed), channel tiles in all, per workgroup, and output-channel slices
+    int nks, nt_tot, nt, nsplit;
+    int rt, members, np;             // row tiles per wave; members per group (grouped form); products per k-step (6 or 9)
+    bool bwd, c16, f32r;             // backward-data; 16 gathered channels; rows without an image are read as fp32
+    size_t lds;                      // dynamic LDS of the launch
+};
+// the instantiations that exist, as the rules choose_p3 decides by and p3_launch_choice instantiates from
+constexpr bool p3_nt_built(int nt, bool c16) { return c16 ? nt == 1 || nt == 2 : nt == 1 || nt == 2 || nt == 4 || nt == 8; }
+constexpr int p3_max_rt(int nt) { return nt == 8 ? 1 : 2; }
+// members per group: four while their accumulators leave room for the load ring (<= 2 channel tiles per workgroup), two with four
+constexpr int p3_grp_members(int nt) { return nt <= 2 ? 4 : 2; }
+constexpr int P3_MAX_LIST_NT = 4, P3_MAX_LIST = 64;      // the list kernels: channel tiles per workgroup, list entries
 
-// channel tiles per workgroup and output-channel slices for an LDS-resident three-plane weight (<= 150 KiB)
-struct P3Geom { int nks, nt_tot, nt, nsplit; };
-inline P3Geom p3_geom(int S, int Cg, int Nout) {
+// Plain arithmetic: no pointers, no HIP calls.  rows: output rows of a dense call (they decide the row tiles per wave only).
+inline P3Choice choose_p3(int B, long rows, int S, int Cg, int Nout, bool backward, bool f32_rows, int list, int list_len, int np,
+                          int num_cus) {
     const ShFragGeom g = sh_frag_geom(S, Cg, Nout);
-    P3Geom r{g.nks, g.nt_tot, g.nt_tot > 8 ? 8 : g.nt_tot, 1};
-    r.nsplit = g.nt_tot / r.nt;
-    while (r.nt > 1 && (long)g.nks * r.nt * 3 > 150) { r.nt >>= 1; r.nsplit <<= 1; }
-    return r;
-}
-// the streaming form: gathered channels in 32s; whole slices of 64 output channels, or 32 output channels (two tiles)
-inline bool p3s_shape_ok(int S, int Cg, int Nout) {
-    if (Cg % 32 || !(Nout % 64 == 0 || Nout == 32)) return false;
-    return Nout == 32 || sh_frag_geom(S, Cg, Nout).nt_tot % P3S_NT == 0;      // (k-steps are padded to whole chunks: p3_nks)
-}
-// (dispatch_p3_nt builds 1, 2, 4 and 8 channel tiles per workgroup, and only 1 and 2 for 16 gathered channels; the list kernels
-// check their own, fewer, tile counts)
-inline bool p3_resident_ok(int S, int Cg, int Nout) {
-    const P3Geom g = p3_geom(S, Cg, Nout);
-    const bool built = Cg == 16 ? g.nt <= 2 : (g.nt == 1 || g.nt == 2 || g.nt == 4 || g.nt == 8);
-    return (long)g.nks * g.nt * 3 <= 150 && g.nsplit == 1 && built;      // one slice: output-channel slices re-gather the input
-}
-// k-steps of a layer's three-plane fragment buffer: sh_frag_geom's, rounded up to whole chunks where the weight is streamed
-inline int p3_nks(int S, int Cg, int Nout) {
-    const ShFragGeom g = sh_frag_geom(S, Cg, Nout);
-    if (p3_resident_ok(S, Cg, Nout) || !p3s_shape_ok(S, Cg, Nout)) return g.nks;
-    return (g.nks + P3S_KC - 1) / P3S_KC * P3S_KC;
-}
-inline bool p3_shape_ok(int B, int S, int Cg, int Nout) {
-    if (B <= 0 || B % 16 || S <= 0 || S > 64 || Nout % 4) return false;
-    if (!(Cg == 16 || (Cg > 0 && Cg % 32 == 0))) return false;
-    return p3_resident_ok(S, Cg, Nout) || p3s_shape_ok(S, Cg, Nout);
-}
-
-template <int RT, bool BWD, int NP, int NT = P3S_NT>
-int launch_p3s(P3Params& p, hipStream_t st) {
-    auto kern = conv_p3s_kernel<RT, BWD, NP, NT>;
-    constexpr int WAVES = 16 / RT;
-    const size_t smem = (size_t)2 * P3S_KC * NT * 3072;
-    static bool attr_set = false;
-    if (sh_lds_limit(attr_set, smem, "conv_p3s", kern) != SH_OK) return SH_ERR_LAUNCH;
-    p.nsplit = p.nt_tot / NT;
-    p.n_vg = sh_cdiv(p.R, RT);
-    const long tiles = (long)p.n_vg * (p.B / 16);
-    SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3s: %ld work items", tiles);
-    p.n_tiles = (int)tiles;
-    long groups = (tiles + WAVES - 1) / WAVES;                         // workgroups per channel slice that still get an item
-    const long cap = (long)p3_num_cus() / p.nsplit;                    // one workgroup per CU (96 KiB of LDS)
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;
-    const int grid = (int)groups * p.nsplit;
-    ShProfScope ps(st, "conv_p3s_kernel<%d, %s, %d, %d>|R=%d B=%d K=%d N=%d grid=%dx%d f32=%d", RT, BWD ? "true" : "false", NP, NT, p.R, p.B,
-                   p.S * p.Cg, p.Nout, grid, WAVES * 64, p.y ? 1 : 0);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(WAVES * 64), smem, st, p);
-    SH_CHECK_LAUNCH("conv_p3s");
-    g_p3_launches.fetch_add(1, std::memory_order_relaxed);
-    return SH_OK;
-}
-template <bool BWD, int NP>
-int dispatch_p3s(P3Params& p, hipStream_t st) {
-    if (p.nt_tot == 2) return launch_p3s<2, BWD, NP, 2>(p, st);          // 32 output channels: two tiles, two vertices per wave
-    return launch_p3s<2, BWD, NP>(p, st);
-}
-
-template <int NT, int RT, bool C16, bool BWD, int NP, bool F32R = false>
-int launch_p3(P3Params& p, hipStream_t st) {
-    auto kern = conv_p3_kernel<NT, RT, C16, BWD, NP, F32R>;
-    const size_t smem = (size_t)p.nks * NT * 3072;
-    static size_t attr_set = 0;
-    if (sh_lds_limit(attr_set, smem, "conv_p3", kern) != SH_OK) return SH_ERR_LAUNCH;
-    p.n_vg = sh_cdiv(p.R, RT);
-    const long tiles = (long)p.n_vg * (p.B / 16);
-    SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3: %ld work items", tiles);
-    p.n_tiles = (int)tiles;
-    const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    int nw = P3_WAVES_CU / per_cu;
-    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
-    long groups = (tiles + nw - 1) / nw;
-    const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;
-    const int grid = (int)groups * p.nsplit;
-    ShProfScope ps(st, "conv_p3_kernel<%d, %d, %s, %s, %d, %s>|R=%d B=%d K=%d N=%d grid=%dx%d f32=%d", NT, RT, C16 ? "true" : "false",
-                   BWD ? "true" : "false", NP, F32R ? "true" : "false", p.R, p.B, p.S * p.Cg, p.Nout, grid, nw * 64, p.y ? 1 : 0);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(nw * 64), smem, st, p);
-    SH_CHECK_LAUNCH("conv_p3");
-    g_p3_launches.fetch_add(1, std::memory_order_relaxed);
-    return SH_OK;
-}
-
-template <int NT, int NP>
-int launch_p3r(P3Params& p, hipStream_t st) {
-    auto kern = conv_p3r_kernel<NT, NP>;
-    const size_t smem = (size_t)p.nks * NT * 3072;
-    static size_t attr_set = 0;
-    if (sh_lds_limit(attr_set, smem, "conv_p3r", kern) != SH_OK) return SH_ERR_LAUNCH;
-    p.n_vg = p.R;
-    const long tiles = (long)p.n_vg * (p.B / 16);
-    SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3r: %ld work items", tiles);
-    p.n_tiles = (int)tiles;
-    const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    int nw = P3_WAVES_CU / per_cu;
-    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
-    long groups = (tiles + nw - 1) / nw;
-    const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;
-    const int grid = (int)groups * p.nsplit;
-    ShProfScope ps(st, "conv_p3r_kernel<%d, %d>|R=%d B=%d K=%d N=%d grid=%dx%d L=%d f32=%d", NT, NP, p.R, p.B, p.S * p.Cg, p.Nout, grid, nw * 64, p.rag_L, p.y ? 1 : 0);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(nw * 64), smem, st, p);
-    SH_CHECK_LAUNCH("conv_p3r");
-    g_p3_launches.fetch_add(1, std::memory_order_relaxed);
-    return SH_OK;
-}
-
-template <int NT, int G, bool BWD, int NP, bool C16 = false>
-int launch_p3g(P3Params& p, hipStream_t st) {
-    auto kern = conv_p3g_kernel<NT, G, BWD, NP, C16>;
-    const size_t smem = (size_t)p.nks * NT * 3072;
-    static size_t attr_set = 0;
-    if (sh_lds_limit(attr_set, smem, "conv_p3g", kern) != SH_OK) return SH_ERR_LAUNCH;
-    p.n_vg = p.n_grp;
-    const long tiles = (long)p.n_grp * (p.B / 16);
-    SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "conv_p3g: %ld work items", tiles);
-    p.n_tiles = (int)tiles;
-    const int per_cu = smem <= 36 * 1024 ? 4 : smem <= 76 * 1024 ? 2 : 1;
-    int nw = P3_WAVES_CU / per_cu;
-    while (nw > 4 && (long)p3_num_cus() * per_cu * (nw >> 1) >= tiles * p.nsplit) nw >>= 1;
-    long groups = (tiles + nw - 1) / nw;
-    const long cap = (long)p3_num_cus() * per_cu / p.nsplit;
-    if (groups > cap) groups = cap;
-    if (groups < 8) groups = 8;
-    groups = (groups + 7) / 8 * 8;
-    const int grid = (int)groups * p.nsplit;
-    ShProfScope ps(st, "conv_p3g_kernel<%d, %d, %s, %d, %s>|R=%d B=%d K=%d N=%d grid=%dx%d groups=%d L=%d f32=%d", NT, G, BWD ? "true" : "false", NP,
-                   C16 ? "true" : "false", p.R, p.B, p.S * p.Cg, p.Nout, grid, nw * 64, p.n_grp, p.g_L, p.y ? 1 : 0);
-    SH_LAUNCH_PS(ps, kern, dim3(grid), dim3(nw * 64), smem, st, p);
-    SH_CHECK_LAUNCH("conv_p3g");
-    g_p3_launches.fetch_add(1, std::memory_order_relaxed);
-    return SH_OK;
-}
-
-template <bool C16, bool BWD, int NP, bool F32R = false>
-int dispatch_p3_nt(P3Params& p, int nt, hipStream_t st) {
-    const long tiles16 = (long)p.R * (p.B / 16);
-    const long fill = 2L * p3_num_cus() * 16;
-    const bool two = tiles16 / 2 >= fill;
-    if (nt == 1) return two ? launch_p3<1, 2, C16, BWD, NP, F32R>(p, st) : launch_p3<1, 1, C16, BWD, NP, F32R>(p, st);
-    if (nt == 2) return two ? launch_p3<2, 2, C16, BWD, NP, F32R>(p, st) : launch_p3<2, 1, C16, BWD, NP, F32R>(p, st);
-    if constexpr (!C16) {
-        if (nt == 4) return two ? launch_p3<4, 2, C16, BWD, NP, F32R>(p, st) : launch_p3<4, 1, C16, BWD, NP, F32R>(p, st);
-        if (nt == 8) return launch_p3<8, 1, C16, BWD, NP, F32R>(p, st);
+    P3Choice c{};
+    c.np = np == 9 ? 9 : 6; c.bwd = backward; c.c16 = Cg == 16; c.rt = 1;
+    // an LDS-resident three-plane weight (<= 150 KiB): channel tiles per workgroup halve, output-channel slices double, until it fits
+    c.nks = g.nks; c.nt_tot = g.nt_tot; c.nt = g.nt_tot > 8 ? 8 : g.nt_tot; c.nsplit = g.nt_tot / c.nt;
+    while (c.nt > 1 && (long)c.nks * c.nt * 3 > 150) { c.nt >>= 1; c.nsplit <<= 1; }
+    // ... in one slice only (output-channel slices re-gather the input), at a tile count that is built
+    const bool resident = (long)c.nks * c.nt * 3 <= 150 && c.nsplit == 1 && p3_nt_built(c.nt, c.c16);
+    // the streaming form: gathered channels in 32s; whole slices of 64 output channels, or 32 output channels (two tiles); k-steps
+    // padded to whole chunks (the fragments past K are zeros)
+    const bool streamed = !resident && Cg % 32 == 0 && (Nout == 32 || (Nout % 64 == 0 && g.nt_tot % P3S_NT == 0));
+    if (streamed) {
+        c.nks = (g.nks + P3S_KC - 1) / P3S_KC * P3S_KC;
+        c.nt = g.nt_tot == 2 ? 2 : P3S_NT;
+        c.nsplit = g.nt_tot / c.nt;
     }
-    sh_set_error("conv_p3: %d channel tiles per workgroup with %d gathered channels is not built", nt, p.Cg);
-    return SH_ERR_UNSUPPORTED;
+    c.lds = streamed ? (size_t)2 * P3S_KC * c.nt * 3072 : (size_t)c.nks * c.nt * 3072;
+    c.why = P3_WHY_SHAPE;
+    if (B <= 0 || B % 16 || S <= 0 || S > 64 || Nout % 4 || !(Cg == 16 || (Cg > 0 && Cg % 32 == 0)) || !(resident || streamed)) return c;
+    if (list != P3_NO_LIST) {
+        c.why = P3_WHY_LIST;
+        if (!resident || c.nt > P3_MAX_LIST_NT || (list == P3_RAG_LIST && Cg % 32) || list_len <= 0 || list_len > P3_MAX_LIST) return c;
+        c.form = list == P3_RAG_LIST ? P3_RAGGED : P3_GROUPED;
+        c.members = list == P3_GRP_LIST ? p3_grp_members(c.nt) : 0;
+    } else if (streamed) {
+        c.why = P3_WHY_F32_STREAMED;
+        if (f32_rows) return c;
+        c.form = P3_STREAMED; c.rt = 2;                           // two vertices per wave
+    } else {
+        c.why = P3_WHY_F32_NP;
+        if (f32_rows && np != 6) return c;
+        c.form = P3_RESIDENT; c.f32r = f32_rows;
+        // two-row tiles once every resident wave still gets >= 2 items of them
+        if (p3_max_rt(c.nt) == 2 && rows * (B / 16) / 2 >= 2L * num_cus * 16) c.rt = 2;
+    }
+    c.why = P3_TAKEN;
+    return c;
 }
 
-template <bool BWD>
-int dispatch_p3(P3Params& p, hipStream_t st) {
-    SH_REQUIRE(p3_shape_ok(p.B, p.S, p.Cg, p.Nout), SH_ERR_UNSUPPORTED,
-               "conv_p3: B=%d S=%d gathered channels=%d output channels=%d is outside the three-plane kernels (sh_spiral_conv_p3_ok)",
-               p.B, p.S, p.Cg, p.Nout);
-    const P3Geom g = p3_geom(p.S, p.Cg, p.Nout);
-    p.nks = g.nks; p.nt_tot = g.nt_tot; p.nsplit = g.nsplit; p.ncg = p.Cg / 32;
+int p3_np() {
+    static const int np = sh_env_int("SH_P3_NP", 6, 6, 9);
+    return np;
+}
+// the choice of a shape for the predicates and buffer sizes: no rows, no fp32 rows
+inline P3Choice p3_choice_of(int B, int S, int Cg, int Nout, int list = P3_NO_LIST, int list_len = 0) {
+    return choose_p3(B, 0, S, Cg, Nout, false, false, list, list_len, p3_np(), sh_num_cus());
+}
+
+// bytes of a C-channel plane image per row and 16-batch group (C == 16 or C % 32 == 0)
+inline size_t p3_image_bgb(int C) { return C == 16 ? 1536 : (size_t)(C / 32) * 3072; }
+
+// the image of yprev (same geometry as the image of the launch's output); `who` is the entry point, `chan` its name for the channels
+int p3_yprev_image(P3Params& p, const void* planes, const char* who, const char* chan) {
+    if (!planes) return SH_OK;
+    SH_REQUIRE(sh_p3_bytes(1, p.B, p.Nout) && (reinterpret_cast<uintptr_t>(planes) & 15) == 0, SH_ERR_UNSUPPORTED,
+               "%s: B=%d %s=%d has no plane image (yprev_planes)", who, p.B, chan, p.Nout);
+    p.yprev_img = static_cast<const char*>(planes);
+    p.yvi_bgb = (long)p3_image_bgb(p.Nout); p.yvi_vb = p.yvi_bgb * (p.B / 16);
+    return SH_OK;
+}
+
+// the derived fields of P3Params from the choice, and the checks every entry point makes on its tensors (`who` prefixes the texts)
+int p3_prepare(P3Params& p, const P3Choice& c, const char* who) {
+    p.nks = c.nks; p.nt_tot = c.nt_tot; p.nsplit = c.nsplit; p.ncg = p.Cg / 32;
     const int nbg = p.B / 16;
-    p.x_bgb = p.Cg == 16 ? 1536 : (long)p.ncg * 3072;
-    p.x_vb = p.x_bgb * nbg;
+    p.x_bgb = (long)p3_image_bgb(p.Cg); p.x_vb = p.x_bgb * nbg;
     if (p.yp) {
-        SH_REQUIRE(p.Nout == 16 || p.Nout % 32 == 0, SH_ERR_UNSUPPORTED, "conv_p3: a plane image has 16 or a multiple of 32 channels (%d)", p.Nout);
-        p.yp_bgb = p.Nout == 16 ? 1536 : (long)(p.Nout / 32) * 3072;
-        p.yp_vb = p.yp_bgb * nbg;
+        SH_REQUIRE(p.Nout == 16 || p.Nout % 32 == 0, SH_ERR_UNSUPPORTED, "%s: a plane image has 16 or a multiple of 32 channels (%d)", who, p.Nout);
+        p.yp_bgb = (long)p3_image_bgb(p.Nout); p.yp_vb = p.yp_bgb * nbg;
     }
-    SH_REQUIRE(p.y || p.yp, SH_ERR_INVALID_ARG, "conv_p3: no output");
+    SH_REQUIRE(p.y || p.yp, SH_ERR_INVALID_ARG, "%s: no output", who);
     SH_REQUIRE(((reinterpret_cast<uintptr_t>(p.xp) | reinterpret_cast<uintptr_t>(p.yp) | reinterpret_cast<uintptr_t>(p.y) |
                  reinterpret_cast<uintptr_t>(p.yprev) | reinterpret_cast<uintptr_t>(p.bias)) & 15) == 0 &&
-               ((p.y_sv | p.y_sb | p.yv_sv | p.yv_sb) & 3) == 0, SH_ERR_INVALID_ARG, "conv_p3: tensors must be 16-byte aligned with strides %% 4 == 0");
-    static const int np = sh_env_int("SH_P3_NP", 6, 6, 9);
-    if (!p3_resident_ok(p.S, p.Cg, p.Nout)) {
-        p.nks = p3_nks(p.S, p.Cg, p.Nout);                     // whole chunks (the fragments past K are zeros)
-        SH_REQUIRE(!p.xf, SH_ERR_UNSUPPORTED, "conv_p3: the weight-streaming form takes imaged rows only (sh_spiral_conv_p3_kind() == 2)");
-        return np == 9 ? dispatch_p3s<BWD, 9>(p, st) : dispatch_p3s<BWD, 6>(p, st);
+               ((p.y_sv | p.y_sb | p.yv_sv | p.yv_sb) & 3) == 0, SH_ERR_INVALID_ARG, "%s: tensors must be 16-byte aligned with strides %% 4 == 0", who);
+    return SH_OK;
+}
+
+// the streamed form's own grid: 16 / RT waves, one workgroup per CU (96 KiB of LDS)
+inline ShGrid p3s_grid(long tiles, const P3Choice& c, int num_cus) {
+    const int waves = 16 / c.rt;
+    long groups = (tiles + waves - 1) / waves;                         // workgroups per channel slice that still get an item
+    const long cap = (long)num_cus / c.nsplit;
+    if (groups > cap) groups = cap;
+    if (groups < 8) groups = 8;
+    groups = (groups + 7) / 8 * 8;
+    return {waves, (int)groups * c.nsplit};
+}
+
+// The launchers' shared tail.  `raised` is the caller's LDS-limit latch (one per instantiation), `what` its name in messages,
+// inst_fmt / a... the instantiation as the launch record spells it (formatted only while the record is on).
+template <class Latch, class... A>
+int p3_launch(void (*kern)(const P3Params), Latch& raised, const char* what, const P3Choice& c, P3Params& p, hipStream_t st,
+              const char* inst_fmt, A... a) {
+    if (sh_lds_limit(raised, c.lds, what, kern) != SH_OK) return SH_ERR_LAUNCH;
+    p.n_vg = c.form == P3_GROUPED ? p.n_grp : sh_cdiv(p.R, c.rt);
+    const long tiles = (long)p.n_vg * (p.B / 16);
+    SH_REQUIRE(tiles < (1L << 30), SH_ERR_UNSUPPORTED, "%s: %ld work items", what, tiles);
+    p.n_tiles = (int)tiles;
+    const ShGrid g = c.form == P3_STREAMED ? p3s_grid(tiles, c, sh_num_cus()) : sh_resident_grid(c.lds, tiles, c.nsplit, sh_num_cus());
+    char inst[64] = "", lists[40] = "";
+    if (sh_profile_on()) {
+        snprintf(inst, sizeof inst, inst_fmt, a...);
+        if (c.form == P3_RAGGED) snprintf(lists, sizeof lists, " L=%d", p.rag_L);
+        if (c.form == P3_GROUPED) snprintf(lists, sizeof lists, " groups=%d L=%d", p.n_grp, p.g_L);
     }
-    if constexpr (BWD) {
-        if (p.xf) {                                            // rows without an image: the six-product kernels that split them
-            SH_REQUIRE(np == 6, SH_ERR_UNSUPPORTED, "conv_p3: fp32 rows are built for the six-product form (SH_P3_NP=6)");
-            return p.Cg == 16 ? dispatch_p3_nt<true, true, 6, true>(p, g.nt, st) : dispatch_p3_nt<false, true, 6, true>(p, g.nt, st);
+    ShProfScope ps(st, "%s|R=%d B=%d K=%d N=%d grid=%dx%d%s f32=%d", inst, p.R, p.B, p.S * p.Cg, p.Nout, g.grid, g.waves * 64, lists, p.y ? 1 : 0);
+    SH_LAUNCH_PS(ps, kern, dim3(g.grid), dim3(g.waves * 64), c.lds, st, p);
+    SH_CHECK_LAUNCH(what);
+    g_p3_launches.fetch_add(1, std::memory_order_relaxed);
+    return SH_OK;
+}
+
+constexpr const char* tf(bool b) { return b ? "true" : "false"; }
+
+template <int NT, int RT, bool C16, bool BWD, int NP, bool F32R>
+int launch_p3(const P3Choice& c, P3Params& p, hipStream_t st) {
+    static size_t raised = 0;
+    return p3_launch(conv_p3_kernel<NT, RT, C16, BWD, NP, F32R>, raised, "conv_p3", c, p, st, "conv_p3_kernel<%d, %d, %s, %s, %d, %s>", NT, RT,
+                     tf(C16), tf(BWD), NP, tf(F32R));
+}
+template <int RT, bool BWD, int NP, int NT>
+int launch_p3s(const P3Choice& c, P3Params& p, hipStream_t st) {
+    static bool raised = false;
+    return p3_launch(conv_p3s_kernel<RT, BWD, NP, NT>, raised, "conv_p3s", c, p, st, "conv_p3s_kernel<%d, %s, %d, %d>", RT, tf(BWD), NP, NT);
+}
+template <int NT, int NP>
+int launch_p3r(const P3Choice& c, P3Params& p, hipStream_t st) {
+    static size_t raised = 0;
+    return p3_launch(conv_p3r_kernel<NT, NP>, raised, "conv_p3r", c, p, st, "conv_p3r_kernel<%d, %d>", NT, NP);
+}
+template <int NT, int G, bool BWD, int NP, bool C16>
+int launch_p3g(const P3Choice& c, P3Params& p, hipStream_t st) {
+    static size_t raised = 0;
+    return p3_launch(conv_p3g_kernel<NT, G, BWD, NP, C16>, raised, "conv_p3g", c, p, st, "conv_p3g_kernel<%d, %d, %s, %d, %s>", NT, G, tf(BWD), NP,
+                     tf(C16));
+}
+
+// The choice becomes template constants here and nowhere else.  Every branch is guarded by the rule choose_p3 decided by, so the
+// kernels instantiated are exactly those a choice can name; a choice without a kernel would be a bug in choose_p3.
+template <int NT, bool C16, bool BWD, int NP, bool F32R>
+int launch_resident(const P3Choice& c, P3Params& p, hipStream_t st) {
+    if constexpr (p3_max_rt(NT) == 2) {
+        if (c.rt == 2) return launch_p3<NT, 2, C16, BWD, NP, F32R>(c, p, st);
+    }
+    return launch_p3<NT, 1, C16, BWD, NP, F32R>(c, p, st);
+}
+template <int NT, bool C16, bool BWD, int NP>
+int launch_form(const P3Choice& c, P3Params& p, hipStream_t st) {
+    if constexpr (p3_nt_built(NT, C16)) {
+        if (c.form == P3_RESIDENT) {
+            if constexpr (BWD && NP == 6) {                        // rows without an image: the six-product kernels that split them
+                if (c.f32r) return launch_resident<NT, C16, true, 6, true>(c, p, st);
+            }
+            return launch_resident<NT, C16, BWD, NP, false>(c, p, st);
+        }
+        if constexpr (NT <= P3_MAX_LIST_NT) {
+            if (c.form == P3_GROUPED) return launch_p3g<NT, p3_grp_members(NT), BWD, NP, C16>(c, p, st);
+            if constexpr (BWD && !C16) {
+                if (c.form == P3_RAGGED) return launch_p3r<NT, NP>(c, p, st);
+            }
         }
     }
-    if (p.Cg == 16) return np == 9 ? dispatch_p3_nt<true, BWD, 9>(p, g.nt, st) : dispatch_p3_nt<true, BWD, 6>(p, g.nt, st);
-    return np == 9 ? dispatch_p3_nt<false, BWD, 9>(p, g.nt, st) : dispatch_p3_nt<false, BWD, 6>(p, g.nt, st);
+    if constexpr (!C16 && (NT == 2 || NT == P3S_NT)) {
+        if (c.form == P3_STREAMED) return launch_p3s<2, BWD, NP, NT>(c, p, st);
+    }
+    sh_set_error("conv_p3: no kernel for form %d with %d channel tiles per workgroup", c.form, NT);
+    return SH_ERR_LAUNCH;
+}
+template <int NT>
+int launch_nt(const P3Choice& c, P3Params& p, hipStream_t st) {
+    if (c.c16) {
+        if (c.np == 9) return c.bwd ? launch_form<NT, true, true, 9>(c, p, st) : launch_form<NT, true, false, 9>(c, p, st);
+        return c.bwd ? launch_form<NT, true, true, 6>(c, p, st) : launch_form<NT, true, false, 6>(c, p, st);
+    }
+    if (c.np == 9) return c.bwd ? launch_form<NT, false, true, 9>(c, p, st) : launch_form<NT, false, false, 9>(c, p, st);
+    return c.bwd ? launch_form<NT, false, true, 6>(c, p, st) : launch_form<NT, false, false, 6>(c, p, st);
+}
+int p3_launch_choice(const P3Choice& c, P3Params& p, hipStream_t st) {
+    switch (c.nt) {
+        case 1: return launch_nt<1>(c, p, st);
+        case 2: return launch_nt<2>(c, p, st);
+        case 4: return launch_nt<4>(c, p, st);
+        default: return launch_nt<8>(c, p, st);
+    }
+}
+
+// a dense call (forward or backward-data over a gather table): resident or streamed weight
+int p3_dense(P3Params& p, bool backward, hipStream_t st) {
+    const P3Choice c = choose_p3(p.B, p.R, p.S, p.Cg, p.Nout, backward, p.xf != nullptr, P3_NO_LIST, 0, p3_np(), sh_num_cus());
+    SH_REQUIRE(c.why != P3_WHY_SHAPE, SH_ERR_UNSUPPORTED,
+               "conv_p3: B=%d S=%d gathered channels=%d output channels=%d is outside the three-plane kernels (sh_spiral_conv_p3_ok)",
+               p.B, p.S, p.Cg, p.Nout);
+    if (const int rc = p3_prepare(p, c, "conv_p3")) return rc;
+    SH_REQUIRE(c.why != P3_WHY_F32_STREAMED, SH_ERR_UNSUPPORTED,
+               "conv_p3: the weight-streaming form takes imaged rows only (sh_spiral_conv_p3_kind() == 2)");
+    SH_REQUIRE(c.why != P3_WHY_F32_NP, SH_ERR_UNSUPPORTED, "conv_p3: fp32 rows are built for the six-product form (SH_P3_NP=6)");
+    return p3_launch_choice(c, p, st);
 }
 
 }  // namespace
@@ -1156,7 +1151,7 @@ extern "C" {
 
 size_t sh_p3_bytes(int rows, int B, int C) {
     if (rows <= 0 || B <= 0 || B % 16 || !(C == 16 || (C > 0 && C % 32 == 0))) return 0;
-    return (size_t)rows * (B / 16) * (C == 16 ? 1536 : (size_t)(C / 32) * 3072);
+    return (size_t)rows * (B / 16) * p3_image_bgb(C);
 }
 
 int sh_to_p3(const float* x, int64_t x_sv, int64_t x_sb, void* planes, int B, int rows, int C, sh_stream_t stream) {
@@ -1164,7 +1159,8 @@ int sh_to_p3(const float* x, int64_t x_sv, int64_t x_sb, void* planes, int B, in
     SH_REQUIRE(sh_p3_bytes(rows, B, C) > 0, SH_ERR_UNSUPPORTED, "sh_to_p3: B=%d C=%d has no plane image (B %% 16 == 0; C == 16 or C %% 32 == 0)", B, C);
     SH_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(planes)) & 15) == 0 && ((x_sv | x_sb) & 3) == 0,
                SH_ERR_INVALID_ARG, "sh_to_p3: tensors must be 16-byte aligned with strides %% 4 == 0");
-    ToP3Args a{x, (long)x_sv, (long)x_sb, static_cast<char*>(planes), B / 16, C, (long)rows * (B / 16) * (C == 16 ? 32 : (C / 32) * 64)};
+    // one thread per 16-byte piece of each of the three planes
+    ToP3Args a{x, (long)x_sv, (long)x_sb, static_cast<char*>(planes), B / 16, C, (long)rows * (B / 16) * (long)(p3_image_bgb(C) / 48)};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long blocks = (a.total + 255) / 256;
     SH_REQUIRE(blocks < (1L << 31), SH_ERR_UNSUPPORTED, "sh_to_p3: tensor too large");
@@ -1176,8 +1172,8 @@ int sh_to_p3(const float* x, int64_t x_sv, int64_t x_sb, void* planes, int B, in
 
 size_t sh_conv_wfrag3_bytes(int S, int Cg, int Nout) {
     if (S <= 0 || Cg <= 0 || Nout <= 0) return 0;
-    const ShFragGeom g = sh_frag_geom(S, Cg, Nout);
-    return (size_t)p3_nks(S, Cg, Nout) * g.nt_tot * 3072;
+    const P3Choice c = p3_choice_of(16, S, Cg, Nout);
+    return (size_t)c.nks * c.nt_tot * 3072;
 }
 
 int sh_conv_wfrag3_prep_multi(int n_layers, const float* const* weight, void* const* wfrag3, const int* S, const int* Cin,
@@ -1193,14 +1189,13 @@ int sh_conv_wfrag3_prep_multi(int n_layers, const float* const* weight, void* co
             SH_REQUIRE(weight[k] && wfrag3[k] && S[k] > 0 && Cin[k] > 0 && Cout[k] > 0, SH_ERR_INVALID_ARG,
                        "sh_conv_wfrag3_prep_multi: bad layer %d", k);
             SH_REQUIRE((reinterpret_cast<uintptr_t>(wfrag3[k]) & 15) == 0, SH_ERR_INVALID_ARG, "sh_conv_wfrag3_prep_multi: wfrag3 %d misaligned", k);
-            const int Cg = transpose[k] ? Cout[k] : Cin[k];
+            const int Cg = transpose[k] ? Cout[k] : Cin[k], Nout = transpose[k] ? Cin[k] : Cout[k];
             SH_REQUIRE(Cg % 8 == 0, SH_ERR_UNSUPPORTED, "sh_conv_wfrag3_prep_multi: %d gathered channels", Cg);
-            const ShFragGeom g = transpose[k] ? sh_frag_geom(S[k], Cout[k], Cin[k]) : sh_frag_geom(S[k], Cin[k], Cout[k]);
+            const P3Choice c = p3_choice_of(16, S[k], Cg, Nout);
             a.w[i] = weight[k]; a.out[i] = static_cast<u32x4*>(wfrag3[k]);
-            const int nks = transpose[k] ? p3_nks(S[k], Cout[k], Cin[k]) : p3_nks(S[k], Cin[k], Cout[k]);
-            a.S[i] = S[k]; a.Cin[i] = Cin[k]; a.Cout[i] = Cout[k]; a.tr[i] = transpose[k] ? 1 : 0; a.nks[i] = nks; a.nt_tot[i] = g.nt_tot;
+            a.S[i] = S[k]; a.Cin[i] = Cin[k]; a.Cout[i] = Cout[k]; a.tr[i] = transpose[k] ? 1 : 0; a.nks[i] = c.nks; a.nt_tot[i] = c.nt_tot;
             a.block0[i] = blocks;
-            blocks += (nks * g.nt_tot * 64 + 255) / 256;
+            blocks += (c.nks * c.nt_tot * 64 + 255) / 256;
         }
         a.block0[a.nd] = blocks;
         ShProfScope ps(st, "wfrag3_prep_kernel|layers=%d", a.nd);
@@ -1212,10 +1207,10 @@ int sh_conv_wfrag3_prep_multi(int n_layers, const float* const* weight, void* co
 
 int64_t sh_p3_launch_count(void) { return (int64_t)g_p3_launches.load(std::memory_order_relaxed); }
 
-int sh_spiral_conv_p3_ok(int B, int S, int Cg, int Nout) { return p3_shape_ok(B, S, Cg, Nout) ? 1 : 0; }
+int sh_spiral_conv_p3_ok(int B, int S, int Cg, int Nout) { return p3_choice_of(B, S, Cg, Nout).form != P3_REFUSED; }
 int sh_spiral_conv_p3_kind(int B, int S, int Cg, int Nout) {
-    if (!p3_shape_ok(B, S, Cg, Nout)) return 0;
-    return p3_resident_ok(S, Cg, Nout) ? 1 : 2;
+    const int form = p3_choice_of(B, S, Cg, Nout).form;
+    return form == P3_RESIDENT ? 1 : form == P3_STREAMED ? 2 : 0;
 }
 
 int sh_spiral_conv_fwd_p3(const void* xp, const int32_t* table, const void* wfrag3, const float* bias, float* y, int64_t y_sv,
@@ -1227,7 +1222,7 @@ int sh_spiral_conv_fwd_p3(const void* xp, const int32_t* table, const void* wfra
     p.xp = static_cast<const char*>(xp); p.table = table; p.wfrag = static_cast<const u32x4*>(wfrag3); p.bias = bias;
     p.y = y; p.y_sv = y_sv; p.y_sb = y_sb; p.yp = static_cast<char*>(yp);
     p.B = B; p.R = R; p.S = S; p.Cg = Cin; p.Nout = Cout; p.act = act; p.zero_row = zero_row; p.skip_row = -1; p.n_img = 0x7fffffff;
-    return dispatch_p3<false>(p, static_cast<hipStream_t>(stream));
+    return p3_dense(p, false, static_cast<hipStream_t>(stream));
 }
 
 int sh_spiral_conv_bwd_data_p3(const void* dprep, int dpre_zero_row, const float* dpre_f32, int64_t dp_sv, int64_t dp_sb, int n_image_rows,
@@ -1241,26 +1236,19 @@ int sh_spiral_conv_bwd_data_p3(const void* dprep, int dpre_zero_row, const float
     p.xp = static_cast<const char*>(dprep); p.table = table_t; p.wfrag = static_cast<const u32x4*>(wfrag3_t); p.bias = nullptr;
     p.y = dx; p.y_sv = dx_sv; p.y_sb = dx_sb; p.yp = static_cast<char*>(dxp);
     p.yprev = yprev; p.yv_sv = yp_sv; p.yv_sb = yp_sb;
-    if (yprev_planes) {
-        SH_REQUIRE(sh_p3_bytes(1, B, Cin) && (reinterpret_cast<uintptr_t>(yprev_planes) & 15) == 0, SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_bwd_data_p3: B=%d Cin=%d has no plane image (yprev_planes)", B, Cin);
-        p.yprev_img = static_cast<const char*>(yprev_planes);
-        p.yvi_bgb = Cin == 16 ? 1536 : (long)(Cin / 32) * 3072; p.yvi_vb = p.yvi_bgb * (B / 16);
-    }
     p.B = B; p.R = n_in; p.S = S; p.Cg = Cout; p.Nout = Cin; p.act = act_prev; p.zero_row = zero_row;
     p.skip_row = dpre_zero_row;
     p.n_img = 0x7fffffff;
+    if (const int rc = p3_yprev_image(p, yprev_planes, "sh_spiral_conv_bwd_data_p3", "Cin")) return rc;
     if (dpre_f32) {
         SH_REQUIRE(n_image_rows >= 0 && (reinterpret_cast<uintptr_t>(dpre_f32) & 15) == 0 && ((dp_sv | dp_sb) & 3) == 0, SH_ERR_INVALID_ARG,
                    "sh_spiral_conv_bwd_data_p3: the fp32 gradient must be 16-byte aligned with strides %% 4 == 0");
         p.xf = dpre_f32; p.xf_sv = dp_sv; p.xf_sb = dp_sb; p.n_img = n_image_rows;
     }
-    return dispatch_p3<true>(p, static_cast<hipStream_t>(stream));
+    return p3_dense(p, true, static_cast<hipStream_t>(stream));
 }
 
-int sh_spiral_conv_p3_rag_ok(int B, int S, int Cg, int Nout, int rag_L) {
-    return p3_shape_ok(B, S, Cg, Nout) && p3_resident_ok(S, Cg, Nout) && p3_geom(S, Cg, Nout).nt <= 4 && Cg % 32 == 0 && rag_L > 0 && rag_L <= 64;
-}
+int sh_spiral_conv_p3_rag_ok(int B, int S, int Cg, int Nout, int rag_L) { return p3_choice_of(B, S, Cg, Nout, P3_RAG_LIST, rag_L).form == P3_RAGGED; }
 
 int sh_spiral_conv_bwd_data_p3_rag(const void* dprep, const int32_t* rag_rows, const int32_t* rag_pos, int rag_L, const void* wfrag3_t, float* dx,
                                    int64_t dx_sv, int64_t dx_sb, void* dxp, const float* yprev, int64_t yp_sv, int64_t yp_sb,
@@ -1269,7 +1257,8 @@ int sh_spiral_conv_bwd_data_p3_rag(const void* dprep, const int32_t* rag_rows, c
     SH_REQUIRE(dprep && rag_rows && rag_pos && wfrag3_t, SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_data_p3_rag: null pointer");
     SH_REQUIRE(B > 0 && n_in > 0 && S > 0 && Cin > 0 && Cout > 0, SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_data_p3_rag: non-positive size");
     SH_REQUIRE(act_prev >= SH_ACT_IDENTITY && act_prev <= SH_ACT_TANH, SH_ERR_INVALID_ARG, "sh_spiral_conv_bwd_data_p3_rag: unknown activation");
-    SH_REQUIRE(sh_spiral_conv_p3_rag_ok(B, S, Cout, Cin, rag_L), SH_ERR_UNSUPPORTED,
+    const P3Choice c = choose_p3(B, n_in, S, Cout, Cin, true, false, P3_RAG_LIST, rag_L, p3_np(), sh_num_cus());
+    SH_REQUIRE(c.form == P3_RAGGED, SH_ERR_UNSUPPORTED,
                "sh_spiral_conv_bwd_data_p3_rag: B=%d S=%d gathered channels=%d output channels=%d lists of %d is not taken (resident three-plane "
                "weight, gathered channels %% 32 == 0, lists of at most 64 sources)", B, S, Cout, Cin, rag_L);
     P3Params p{};
@@ -1278,53 +1267,22 @@ int sh_spiral_conv_bwd_data_p3_rag(const void* dprep, const int32_t* rag_rows, c
     p.yprev = yprev; p.yv_sv = yp_sv; p.yv_sb = yp_sb;
     p.B = B; p.R = n_in; p.S = S; p.Cg = Cout; p.Nout = Cin; p.act = act_prev; p.zero_row = zero_row;
     p.rag_rows = rag_rows; p.rag_pos = rag_pos; p.rag_L = rag_L;
-    if (yprev_planes) {
-        SH_REQUIRE(sh_p3_bytes(1, B, Cin) && (reinterpret_cast<uintptr_t>(yprev_planes) & 15) == 0, SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_bwd_data_p3_rag: B=%d Cin=%d has no plane image (yprev_planes)", B, Cin);
-        p.yprev_img = static_cast<const char*>(yprev_planes);
-        p.yvi_bgb = Cin == 16 ? 1536 : (long)(Cin / 32) * 3072; p.yvi_vb = p.yvi_bgb * (B / 16);
-    }
-    const P3Geom g = p3_geom(p.S, p.Cg, p.Nout);
-    p.nks = g.nks; p.nt_tot = g.nt_tot; p.nsplit = g.nsplit; p.ncg = p.Cg / 32;
-    const int nbg = B / 16;
-    p.x_bgb = (long)p.ncg * 3072; p.x_vb = p.x_bgb * nbg;
-    if (p.yp) {
-        SH_REQUIRE(p.Nout == 16 || p.Nout % 32 == 0, SH_ERR_UNSUPPORTED, "conv_p3r: a plane image has 16 or a multiple of 32 channels (%d)", p.Nout);
-        p.yp_bgb = p.Nout == 16 ? 1536 : (long)(p.Nout / 32) * 3072; p.yp_vb = p.yp_bgb * nbg;
-    }
-    SH_REQUIRE(p.y || p.yp, SH_ERR_INVALID_ARG, "conv_p3r: no output");
-    SH_REQUIRE(((reinterpret_cast<uintptr_t>(p.xp) | reinterpret_cast<uintptr_t>(p.yp) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.yprev)) & 15) == 0 &&
-               ((p.y_sv | p.y_sb | p.yv_sv | p.yv_sb) & 3) == 0, SH_ERR_INVALID_ARG, "conv_p3r: tensors must be 16-byte aligned with strides %% 4 == 0");
-    static const int np = sh_env_int("SH_P3_NP", 6, 6, 9);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nt = g.nt;
-#define SH_P3R_CASE(N) (np == 9 ? launch_p3r<N, 9>(p, st) : launch_p3r<N, 6>(p, st))
-    if (nt == 1) return SH_P3R_CASE(1);
-    if (nt == 2) return SH_P3R_CASE(2);
-    if (nt == 4) return SH_P3R_CASE(4);
-#undef SH_P3R_CASE
-    sh_set_error("conv_p3r: %d channel tiles per workgroup is not built", nt);
-    return SH_ERR_UNSUPPORTED;
+    if (const int rc = p3_yprev_image(p, yprev_planes, "sh_spiral_conv_bwd_data_p3_rag", "Cin")) return rc;
+    if (const int rc = p3_prepare(p, c, "conv_p3r")) return rc;
+    return p3_launch_choice(c, p, static_cast<hipStream_t>(stream));
 }
 
-int sh_spiral_conv_p3_grp_ok(int B, int S, int Cg, int Nout, int g_L) {
-    if (!(Cg % 32 == 0 || (Cg == 16 && p3_geom(S, Cg, Nout).nt <= 2))) return 0;
-    return p3_shape_ok(B, S, Cg, Nout) && p3_resident_ok(S, Cg, Nout) && p3_geom(S, Cg, Nout).nt <= 4 && S < 255 && g_L > 0 && g_L <= 64;
-}
+int sh_spiral_conv_p3_grp_ok(int B, int S, int Cg, int Nout, int g_L) { return p3_choice_of(B, S, Cg, Nout, P3_GRP_LIST, g_L).form == P3_GROUPED; }
 
-// members per group the kernel of this shape is built for (the host groups accordingly): four while their accumulators leave room
-// for the load ring (<= 2 channel tiles per workgroup), two with four tiles; 0: the shape is not taken
-int sh_spiral_conv_p3_grp_members(int B, int S, int Cg, int Nout) {
-    if (!sh_spiral_conv_p3_grp_ok(B, S, Cg, Nout, 1)) return 0;
-    return p3_geom(S, Cg, Nout).nt <= 2 ? 4 : 2;
-}
+// members per group the kernel of this shape is built for (the host groups accordingly; p3_grp_members); 0: the shape is not taken
+int sh_spiral_conv_p3_grp_members(int B, int S, int Cg, int Nout) { return p3_choice_of(B, S, Cg, Nout, P3_GRP_LIST, 1).members; }
 
 // does grouping pay for this launch?  Measured (profiles/r06_kernel_experiments.txt item 12, 6890 vertices x 64): a group is one wave
 // item of up to four rows - with fewer than ~one item per resident wave the launch loses more to its coarser, uneven items than the
 // halved gather brings (449-493 groups x 4 batch groups: +2.3 ... +4.0 us; 886-1760 x 4: -0.8 ... -8.2 us).
 int sh_spiral_conv_p3_grp_pays(int B, int n_groups) {
     constexpr int P3_GRP_MIN_ITEMS_PER_CU = 12;
-    return B >= 16 && (long)n_groups * (B / 16) >= (long)P3_GRP_MIN_ITEMS_PER_CU * p3_num_cus();
+    return B >= 16 && (long)n_groups * (B / 16) >= (long)P3_GRP_MIN_ITEMS_PER_CU * sh_num_cus();
 }
 
 int sh_spiral_conv_p3_grp(const void* xp, const int32_t* g_rows, const uint32_t* g_pos, const int32_t* g_out, int n_groups, int g_L,
@@ -1334,7 +1292,8 @@ int sh_spiral_conv_p3_grp(const void* xp, const int32_t* g_rows, const uint32_t*
     SH_REQUIRE(xp && g_rows && g_pos && g_out && wfrag3, SH_ERR_INVALID_ARG, "sh_spiral_conv_p3_grp: null pointer");
     SH_REQUIRE(B > 0 && R > 0 && S > 0 && Cg > 0 && Nout > 0 && n_groups > 0, SH_ERR_INVALID_ARG, "sh_spiral_conv_p3_grp: non-positive size");
     SH_REQUIRE(act >= SH_ACT_IDENTITY && act <= SH_ACT_TANH, SH_ERR_INVALID_ARG, "sh_spiral_conv_p3_grp: unknown activation");
-    SH_REQUIRE(sh_spiral_conv_p3_grp_ok(B, S, Cg, Nout, g_L), SH_ERR_UNSUPPORTED,
+    const P3Choice c = choose_p3(B, n_groups, S, Cg, Nout, backward != 0, false, P3_GRP_LIST, g_L, p3_np(), sh_num_cus());
+    SH_REQUIRE(c.form == P3_GROUPED, SH_ERR_UNSUPPORTED,
                "sh_spiral_conv_p3_grp: B=%d S=%d gathered channels=%d output channels=%d lists of %d is not taken (resident three-plane weight, "
                "gathered channels 16 or %% 32 == 0, lists of at most 64 rows)", B, S, Cg, Nout, g_L);
     SH_REQUIRE(backward || !(yprev || yprev_planes), SH_ERR_INVALID_ARG, "sh_spiral_conv_p3_grp: yprev belongs to the backward form");
@@ -1344,42 +1303,9 @@ int sh_spiral_conv_p3_grp(const void* xp, const int32_t* g_rows, const uint32_t*
     p.yprev = yprev; p.yv_sv = yp_sv; p.yv_sb = yp_sb;
     p.B = B; p.R = R; p.S = S; p.Cg = Cg; p.Nout = Nout; p.act = act; p.zero_row = zero_row;
     p.g_rows = g_rows; p.g_pos = g_pos; p.g_out = g_out; p.g_L = g_L; p.n_grp = n_groups;
-    if (yprev_planes) {
-        SH_REQUIRE(sh_p3_bytes(1, B, Nout) && (reinterpret_cast<uintptr_t>(yprev_planes) & 15) == 0, SH_ERR_UNSUPPORTED,
-                   "sh_spiral_conv_p3_grp: B=%d channels=%d has no plane image (yprev_planes)", B, Nout);
-        p.yprev_img = static_cast<const char*>(yprev_planes);
-        p.yvi_bgb = Nout == 16 ? 1536 : (long)(Nout / 32) * 3072; p.yvi_vb = p.yvi_bgb * (B / 16);
-    }
-    const P3Geom g = p3_geom(p.S, p.Cg, p.Nout);
-    p.nks = g.nks; p.nt_tot = g.nt_tot; p.nsplit = g.nsplit; p.ncg = p.Cg / 32;
-    const int nbg = B / 16;
-    const bool c16 = Cg == 16;
-    p.x_bgb = c16 ? 1536 : (long)p.ncg * 3072; p.x_vb = p.x_bgb * nbg;
-    if (p.yp) {
-        SH_REQUIRE(p.Nout == 16 || p.Nout % 32 == 0, SH_ERR_UNSUPPORTED, "conv_p3g: a plane image has 16 or a multiple of 32 channels (%d)", p.Nout);
-        p.yp_bgb = p.Nout == 16 ? 1536 : (long)(p.Nout / 32) * 3072; p.yp_vb = p.yp_bgb * nbg;
-    }
-    SH_REQUIRE(p.y || p.yp, SH_ERR_INVALID_ARG, "conv_p3g: no output");
-    SH_REQUIRE(((reinterpret_cast<uintptr_t>(p.xp) | reinterpret_cast<uintptr_t>(p.yp) | reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.yprev) |
-                 reinterpret_cast<uintptr_t>(p.bias)) & 15) == 0 && ((p.y_sv | p.y_sb | p.yv_sv | p.yv_sb) & 3) == 0, SH_ERR_INVALID_ARG,
-               "conv_p3g: tensors must be 16-byte aligned with strides %% 4 == 0");
-    static const int np = sh_env_int("SH_P3_NP", 6, 6, 9);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int nt = g.nt;
-    // four members per group while their accumulators leave room for the load ring (<= 2 channel tiles), two beyond
-#define SH_P3G_CASE(N, GG) (backward ? (np == 9 ? launch_p3g<N, GG, true, 9>(p, st) : launch_p3g<N, GG, true, 6>(p, st)) \
-                                     : (np == 9 ? launch_p3g<N, GG, false, 9>(p, st) : launch_p3g<N, GG, false, 6>(p, st)))
-#define SH_P3G_CASE16(N) (backward ? (np == 9 ? launch_p3g<N, 4, true, 9, true>(p, st) : launch_p3g<N, 4, true, 6, true>(p, st)) \
-                                   : (np == 9 ? launch_p3g<N, 4, false, 9, true>(p, st) : launch_p3g<N, 4, false, 6, true>(p, st)))
-    if (c16 && nt == 1) return SH_P3G_CASE16(1);
-    if (c16 && nt == 2) return SH_P3G_CASE16(2);
-#undef SH_P3G_CASE16
-    if (nt == 1) return SH_P3G_CASE(1, 4);
-    if (nt == 2) return SH_P3G_CASE(2, 4);
-    if (nt == 4) return SH_P3G_CASE(4, 2);
-#undef SH_P3G_CASE
-    sh_set_error("conv_p3g: %d channel tiles per workgroup is not built", nt);
-    return SH_ERR_UNSUPPORTED;
+    if (const int rc = p3_yprev_image(p, yprev_planes, "sh_spiral_conv_p3_grp", "channels")) return rc;
+    if (const int rc = p3_prepare(p, c, "conv_p3g")) return rc;
+    return p3_launch_choice(c, p, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

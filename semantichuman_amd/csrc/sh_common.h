@@ -52,6 +52,29 @@ int sh_lds_limit(size_t& raised, size_t bytes, const char* what, K... kernels) {
     return rc;
 }
 
+// ---------------------------------------------------------------------------- grids of the resident-weight convolutions
+// compute units of the current device (256 when no device answers); read once per process
+int sh_num_cus();
+
+// Waves per workgroup and workgroups of a persistent launch whose weight (slice) stays in `lds_bytes` of LDS while its waves
+// take `work_items` items in each of `nsplit` output-channel slices (conv_p3 / p3r / p3g, conv_bf16 / bf16r).
+constexpr int SH_RESIDENT_WAVES_CU = 16;      // the kernels are built for <= 128 VGPRs: <= 16 resident waves per CU
+struct ShGrid { int waves, grid; };
+static inline ShGrid sh_resident_grid(size_t lds_bytes, long work_items, int nsplit, int num_cus) {
+    // waves per workgroup and workgroups per CU from the LDS footprint of the resident weight
+    const int per_cu = lds_bytes <= 36 * 1024 ? 4 : lds_bytes <= 76 * 1024 ? 2 : 1;
+    int nw = SH_RESIDENT_WAVES_CU / per_cu;
+    // few work items (coarse levels): as many resident waves as there are items (loads in flight per CU are what these
+    // launches live on), fewer waves per workgroup only when even one item per wave leaves waves idle
+    while (nw > 4 && (long)num_cus * per_cu * (nw >> 1) >= work_items * nsplit) nw >>= 1;
+    long groups = (work_items + nw - 1) / nw;                    // workgroups (per channel slice) that still get an item
+    const long cap = (long)num_cus * per_cu / nsplit;
+    if (groups > cap) groups = cap;
+    if (groups < 8) groups = 8;
+    groups = (groups + 7) / 8 * 8;                               // a multiple of 8 per slice -> every XCD label has all slices
+    return {nw, (int)groups * nsplit};
+}
+
 // ---------------------------------------------------------------------------- kernel timing
 // RAII: records a hipEvent pair on `st` around the launches made inside its scope (only when
 // profiling was enabled through sh_profile_enable).

@@ -31,6 +31,17 @@ int sh_raise_lds_limit(const void* const* kernels, int n, size_t bytes, const ch
     return SH_OK;
 }
 
+int sh_num_cus() {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+
 // ---- kernel timing -----------------------------------------------------------------------
 #include <mutex>
 #include <string>

@@ -32,7 +32,7 @@ from tests.p3_ref import (ACT64, DACT64, SH_ERR_UNSUPPORTED, act_slope64, arr, d
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
-RT2_TILES = 16384           # R * B / 16 from which the resident kernels take two-row tiles on a 256-CU MI355X (dispatch_p3_nt)
+RT2_TILES = 16384           # R * B / 16 from which the resident kernels take two-row tiles on a 256-CU MI355X (choose_p3)
 
 # (name, B, R, n_in, S, Cg, Nout, tags).  Forward: a layer Cin = Cg -> Cout = Nout gathering n_in rows into R; backward-data: the
 # layer Cin = Nout -> Cout = Cg over the same table (dpre has R rows, dx n_in); weight gradient: view "wA" = the forward layer,
@@ -574,7 +574,7 @@ def test_point_against_float64(sweep, name):
 
 
 def _reachable_conv_p3():
-    """conv_p3_kernel<NT, RT, C16, BWD, NP, F32R> at default settings (dispatch_p3 / dispatch_p3_nt, SH_P3_NP = 6)."""
+    """conv_p3_kernel<NT, RT, C16, BWD, NP, F32R> at default settings (choose_p3 / p3_launch_choice, SH_P3_NP = 6)."""
     out = set()
     for c16, nts in ((True, (1, 2)), (False, (1, 2, 4, 8))):
         for nt in nts:

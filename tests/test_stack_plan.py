@@ -134,7 +134,7 @@ def test_no_plane_form_without_planes3():
 
 
 def test_plane_predicates_refuse_unbuilt_tile_counts():
-    """The 16-channel plane kernels are built for one or two channel tiles per workgroup (csrc/p3_conv.hip dispatch_p3_nt)."""
+    """The 16-channel plane kernels are built for one or two channel tiles per workgroup (csrc/p3_conv.hip p3_nt_built)."""
     lib = _lib.load()
     for S in (4, 8, 9, 12, 25):
         for n in range(4, 257, 4):
