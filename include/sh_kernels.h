@@ -1290,6 +1290,59 @@ SH_API int sh_free_space_bwd(const float* x, int64_t x_sb, int rows, int n, cons
                              const float* gL, int B, float* g_x, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Free space from a rig: the term of "Depth field" for the V calibrated cameras of "Depth views" at once, with the way from the
+ * model's frame into each camera's frame inside the kernels (no reference counterpart).  Deterministic: no atomics, every output
+ * element written by one plain store; the bits depend on neither B, the padding nor the launch shape.  fp32 operations are
+ * rounded one at a time (no contraction), fp64 ones too; every division is correctly rounded.  1 <= V <= SH_DEPTH_MAX_VIEWS.
+ *
+ * sh_free_space_cameras.  pose: fp32 [B][12], scan / rig frame -> model frame, A row-major (a_00 .. a_22) then t (the layout of
+ * sh_transform_points), or NULL: the identity.  ext: fp32 [B][V][12], camera frame -> rig frame, R row-major then t_v ("Depth
+ * views").  -> cam fp32 [B][V][12] = (M | c), model frame -> camera frame, q = M x + c, M row-major (m_00 .. m_22) then c:
+ *     M = R^T A^-1,   c = -R^T (A^-1 t + t_v)
+ * in fp64 from the widened inputs, in this order, with a_i the rows of A:
+ *     k_0 = a_1 x a_2,  k_1 = a_2 x a_0,  k_2 = a_0 x a_1      (p x q)_0 = p_1 q_2 - p_2 q_1, and cyclically: two products, one difference
+ *     det = (a_00 k_00 + a_01 k_01) + a_02 k_02
+ *     I_ij = k_ji / det                                          A^-1 by the adjugate; nothing is rounded to fp32 in between
+ *     p_i  = ((I_i0 t_0 + I_i1 t_1) + I_i2 t_2) + t_v,i
+ *     M_ij = (r_0i I_0j + r_1i I_1j) + r_2i I_2j
+ *     c_i  = -((r_0i p_0 + r_1i p_1) + r_2i p_2)
+ * and each of the 12 words rounded to fp32 once.  An ext row that holds a NaN (an ABSENT camera, "Depth views"), or a body whose
+ * det is 0 or not finite, gives 12 NaN words.  One launch, one thread per (body, view).
+ *
+ * sh_free_space_views_fwd / _bwd.  x, x_sb, rows, n, v_mask, mask_sb, margin: those of sh_free_space_fwd, but x holds points of
+ * the MODEL's frame (any frame cam starts from).  cam fp32 [B][V][12]; intr fp32 [B][V][4]; cls, z, nearest [B][V][H][W]: image
+ * (b, v) is image b * V + v of an sh_depth_field call over B * V images.  For an active vertex x and every view v, ascending:
+ *     Q_i = fl(fl(fl(fl(m_i0 * x_0) + fl(m_i1 * x_1)) + fl(m_i2 * x_2)) + c_i)                          i = 0..2, the form of "Depth views"
+ * and then the case list of sh_free_space_fwd, unchanged, on (X, Y, Z) = Q with view v's intrinsics and image (one device
+ * routine serves both).  A NaN cam row gives kind SH_FS_OUTSIDE by !(Z > 0), and nothing of that view's image is read.  With an
+ * identity cam row Q == x for finite x.
+ * sh_free_space_views_fwd -> term fp32 [B][V][n], kind uint8 [B][V][n] (a masked vertex: 0 and kind 0 in every view), loss fp32
+ * [B][2] = (1 / n_act) * the sum over vertices AND views of the kind-1 terms, and of the kind-2 terms; counts int32 [B][V][4] =
+ * (n_act, #kind 1, #kind 2, #kind 4) per view (n_act is the same in every view).  The sums are fp64, in this order: thread t of
+ * 256 takes the vertices t, t + 256, ... in order and, inside a vertex, the views ascending; then the wave butterfly and the four
+ * wave sums in order; one division by n_act and one rounding to fp32 (n_act == 0: zeros).  One launch, one workgroup per body:
+ * all its threads write term and kind, one thread per vertex with a uniform loop over the views; after a barrier the first 256
+ * fold the stored terms in the order above - so the order, not the workgroup's width, makes the bits.
+ * sh_free_space_views_bwd, given the forward call's arguments, its counts and gL fp32 [B][2] -> g_x fp32 [B][rows][3],
+ * contiguous.  Per row, starting from (0, 0, 0) and for the views ascending that gave the vertex a term of kind k + 1:
+ *     w_i     = fl(fl(gL[b][k] * fl(1 / (float)n_act)) * g_i)                                         g: the camera-frame gradient of the case list
+ *     g_x[j] += fl(fl(fl(m_0j * w_0) + fl(m_1j * w_1)) + fl(m_2j * w_2))                              M^T w, one fp32 addition per view
+ * Rows without a term, masked rows and rows >= n hold zeros.  One launch, one thread per row, a uniform loop over the views.
+ * In both term kernels the body's V records (12 cam words, 4 intrinsics) are staged in LDS once per workgroup.
+ * Null pointers (v_mask, and pose for the cameras, excepted), V outside [1, SH_DEPTH_MAX_VIEWS], negative sizes, n > rows, a batch
+ * or mask stride shorter than n, a negative or NaN margin, H * W == 0 with n > 0: SH_ERR_INVALID_ARG; H or W above
+ * SH_FIELD_MAX_SIDE, B > 65535, B * V > 65535 or V * H * W > INT_MAX: SH_ERR_UNSUPPORTED; all before the device is touched.
+ * B == 0: SH_OK, nothing launched.
+ */
+SH_API int sh_free_space_cameras(const float* pose, const float* ext, int B, int V, float* cam, sh_stream_t stream);
+SH_API int sh_free_space_views_fwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                   const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb,
+                                   float margin, int B, float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream);
+SH_API int sh_free_space_views_bwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                   const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb,
+                                   float margin, const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

@@ -105,6 +105,9 @@ SIGNATURES = {
     "sh_depth_field": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "sh_free_space_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),
     "sh_free_space_bwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _I, _P, _L, c_float, _P, _P, _I, _P, _P]),
+    "sh_free_space_cameras": (c_int, [_P, _P, _I, _I, _P, _P]),
+    "sh_free_space_views_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),
+    "sh_free_space_views_bwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, c_float, _P, _P, _I, _P, _P]),
     "sh_align_ranges": (c_int, [_I, _I, c_float]),
     "sh_align_partials_bytes": (c_size_t, [_I, _I, _I, c_float]),
     "sh_align_moments": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),

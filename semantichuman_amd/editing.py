@@ -230,18 +230,26 @@ def _visibility_cache(what, visibility, visibility_every):
 
 def _free_space_term(what, field, B, free_space_weight, silhouette_weight, margin, pose, vertex_mask=None):
     """The free-space arguments of a fit, checked -> None without a field, else x_hat -> free_space_weight * free +
-    silhouette_weight * silhouette [B] (scan.free_space under `pose`, read afresh in every call, and the given vertex_mask)."""
+    silhouette_weight * silhouette [B] (scan.free_space under `pose`, read afresh in every call, and the given vertex_mask).
+    A rig field's way into its cameras (scan.free_space_cameras) is NOT read afresh: `term.pose_moved()` computes it - one launch -
+    and the caller says so before the first step and after every change of `pose`; for a one-camera field it does nothing."""
     if field is None:
         return None
     scan._check_free_space_weights(what, field, B, margin, (("free_space_weight", free_space_weight), ("silhouette_weight", silhouette_weight)))
     if pose is not None and (not isinstance(pose, scan.Pose) or len(pose) != B):
         raise ValueError("%s: free_space_pose must be a scan.Pose of %d bodies" % (what, B))
     fw, sw, margin = float(free_space_weight), float(silhouette_weight), float(margin)
+    rig = {}
 
     def term(x_hat):
-        free, silhouette = scan.free_space(x_hat, field, pose=pose, vertex_mask=vertex_mask, margin=margin)
+        free, silhouette = scan.free_space(x_hat, field, pose=pose, vertex_mask=vertex_mask, margin=margin, **rig)
         return fw * free + sw * silhouette
 
+    def pose_moved():
+        if field.views is not None:
+            rig["cameras"] = scan.free_space_cameras(field, pose)
+
+    term.pose_moved = pose_moved
     return term
 
 
@@ -276,7 +284,9 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     -> model frame) that brought the scans into the model's frame, None when the model's frame is the camera's.  A given
     vertex_mask holds for the term too; the mask of visibility= does not - the unseen vertices are the ones it is for.  Nearest-pixel sampling, no image gradient, no robust form, pinhole only.  The loss per step
     includes the term; the returned Chamfer value does not.  ValueError for a field of another batch size, a negative weight or
-    margin.
+    margin.  A rig field (scan.DepthField.from_depth(..., extrinsics=)) charges every vertex under each of the rig's cameras:
+    free_space_pose is then rig frame -> model frame, the way into the cameras is computed once before the loop
+    (scan.free_space_cameras), and a step adds one forward and one backward launch for all cameras.
     Returns (new z, chamfer [B] of the result, loss per step [steps])."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
@@ -305,6 +315,8 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
                              vis_cache=vis_cache, **rb)
 
     objective = data if extra is None else (lambda x_hat: data(x_hat) + extra(x_hat))
+    if extra is not None:
+        extra.pose_moved()                                                 # a rig field: its cameras once, the pose is fixed
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy)
     with torch.no_grad():
         if vis_cache is not None:
@@ -361,7 +373,9 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
     scan's frame): the term of every step is scan.free_space(decode(z), free_space, pose=the pose as it stands), so it follows
     every in-loop pose update.  The term moves the latents only - it does NOT move the pose: stage 1 (scan.align) and the in-loop
     pose updates are what they are without it.  The loss per step includes the term; the returned Chamfer value does not.
-    ValueError for a field of another batch size, a negative weight or margin.  No file reader."""
+    ValueError for a field of another batch size, a negative weight or margin.  A rig field (scans in the rig's frame) works the
+    same way; its cameras are recomputed - one launch - after stage 1 and after every in-loop pose update.  No file
+    reader."""
     if not isinstance(scans, scan.ScanBatch):
         scans = scan.ScanBatch(scans, z.device)
     if len(scans) != z.shape[0]:
@@ -418,11 +432,15 @@ def register_scan(model, z, z_kps, scans, parts=None, *, mode="similarity", init
                              vertex_matches=not on_surface, **rb)
 
     objective = data if extra is None else (lambda x_hat: data(x_hat) + extra(x_hat))  # `pose` is updated in place: the term reads it afresh
+    if extra is not None:
+        extra.pose_moved()                                                              # a rig field's cameras under the pose of stage 1
 
     def after_step(t):
         if (t + 1) % align_every == 0:
             state["partials"] = scan.pose_update(pose, scans, aligned, matches, mode, partials=state["partials"], surface=on_surface,
                                                  step=align_step, **rb)
+            if extra is not None:
+                extra.pose_moved()                                                      # ... and under every pose after it: one launch
 
     z_new, losses = fit_latents(model, z, z_kps, objective, parts, steps=steps, lr=lr, dummy=dummy,
                                 after_step=after_step if align_every > 0 else None)

@@ -813,7 +813,77 @@ def free_space_bwd(x, n, cls, z, nearest, intr, v_mask, mask_sb, margin, counts,
     return g
 
 
-ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                 # enum sh_robust (0: none)
+def _dense(t, device, dtype, shape):
+    return torch.is_tensor(t) and t.device == device and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+
+def free_space_cameras(ext, pose=None):
+    """sh_free_space_cameras: ext fp32 [B, V, 12] on the GPU (camera -> rig, R row-major then t: `scan.pack_extrinsics`' layout) and
+    pose fp32 [B, 12] (`Pose.packed`: scan / rig frame -> model frame) or None, the identity -> cam fp32 [B, V, 12] = (M | c), model
+    frame -> camera frame: M = R^T A^-1, c = -R^T (A^-1 t + t_v), fp64 inside, rounded once; NaN rows for an absent camera or a
+    singular pose.  One launch."""
+    who = "free_space_cameras"
+    if not (torch.is_tensor(ext) and ext.is_cuda and ext.dtype == torch.float32 and ext.dim() == 3 and ext.shape[2] == 12 and ext.is_contiguous()):
+        raise ValueError("%s: ext must be a contiguous fp32 HIP tensor [B, V, 12]" % who)
+    B, V = ext.shape[:2]
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    if pose is not None and not _dense(pose, ext.device, torch.float32, (B, 12)):
+        raise ValueError("%s: pose must be a contiguous fp32 tensor [%d, 12] on the device of ext" % (who, B))
+    cam = torch.empty((B, V, 12), dtype=torch.float32, device=ext.device)
+    check(_lib.load().sh_free_space_cameras(ptr(pose), ptr(ext), B, V, ptr(cam), stream_ptr()), "sh_" + who)
+    return cam
+
+
+def _free_space_views_args(who, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
+    """The arguments sh_free_space_views_fwd and _bwd share, checked -> (B, V, rows, their C arguments up to `margin`)."""
+    B, rows, x_sb = _points(x, who)
+    n = int(n)
+    if not 0 <= n <= rows:
+        raise ValueError("%s: n = %d exceeds the model's %d rows" % (who, n, rows))
+    if not (torch.is_tensor(cls) and cls.device == x.device and cls.dtype == torch.uint8 and cls.dim() == 4 and cls.shape[0] == B
+            and cls.is_contiguous()):
+        raise ValueError("%s: cls must be a contiguous uint8 tensor [%d, V, H, W] on the device of x" % (who, B))
+    V, H, W = cls.shape[1:]
+    if not 1 <= V <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
+    for t, dtype, shape, what in ((z, torch.float32, (B, V, H, W), "z fp32"), (nearest, torch.int32, (B, V, H, W), "nearest int32"),
+                                  (intr, torch.float32, (B, V, 4), "intr fp32"), (cam, torch.float32, (B, V, 12), "cam fp32")):
+        if not _dense(t, x.device, dtype, shape):
+            raise ValueError("%s: %s must be a contiguous tensor %s on the device of x" % (who, what, list(shape)))
+    return B, V, rows, (ptr(x), x_sb, rows, n, ptr(cam), ptr(cls), ptr(z), ptr(nearest), ptr(intr), V, H, W, ptr(v_mask), mask_sb, float(margin))
+
+
+def free_space_views_fwd(x, n, cam, cls, z, nearest, intr, v_mask=None, mask_sb=0, margin=0.0):
+    """sh_free_space_views_fwd: x [B, *, 3] model-frame points of which the first n rows are vertices, cam [B, V, 12]
+    (`free_space_cameras`), a rig's depth field (cls, z, nearest [B, V, H, W]) and intr [B, V, 4]; v_mask as in `free_space_fwd`
+    -> (term fp32 [B, V, n], kind uint8 [B, V, n], loss fp32 [B, 2] = (free space, silhouette) summed over the views, counts int32
+    [B, V, 4] = (active, kind 1, 2, 4) per view)."""
+    B, V, rows, args = _free_space_views_args("free_space_views_fwd", x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    n = int(n)
+    term = torch.empty((B, V, n), dtype=torch.float32, device=x.device)
+    kind = torch.empty((B, V, n), dtype=torch.uint8, device=x.device)
+    loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+    counts = torch.empty((B, V, 4), dtype=torch.int32, device=x.device)
+    check(_lib.load().sh_free_space_views_fwd(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_free_space_views_fwd")
+    return term, kind, loss, counts
+
+
+def free_space_views_bwd(x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
+    """sh_free_space_views_bwd: the forward call's arguments, its counts [B, V, 4] and gL fp32 [B, 2] -> g_x contiguous
+    [B, rows, 3] in the frame of x (every element written)."""
+    who = "free_space_views_bwd"
+    B, V, rows, args = _free_space_views_args(who, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    if not _dense(gL, x.device, torch.float32, (B, 2)):
+        raise ValueError("%s: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % (who, B))
+    if not _dense(counts, x.device, torch.int32, (B, V, 4)):
+        raise ValueError("%s: counts must be the forward call's int32 tensor [%d, %d, 4]" % (who, B, V))
+    g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(_lib.load().sh_free_space_views_bwd(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_" + who)
+    return g
+
+
+ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                # enum sh_robust (0: none)
 
 
 def _robust_entry(entry, robust):

@@ -35,6 +35,10 @@
   * `views_overlap(scans, depth, intrinsics, extrinsics, tol=)`, `merge_views(scans, keep, seen)`, `merge_tol=` on the two
                                      above  the rows of a rig scan that a better-placed camera also measures, found by
                                      projection (sh_depth_views_overlap), and the batch without them (sh_scan_compact)
+  * `DepthField.from_depth(..., extrinsics=)`, `free_space_cameras(field, pose)`, `free_space(x_hat, rig_field, pose=, cameras=)`
+                                     the free-space and silhouette term for all cameras of a rig at once, the way from the
+                                     model's frame into every camera's inside the kernels (sh_free_space_cameras,
+                                     sh_free_space_views_fwd / _bwd)
 
 Distances are formed from coordinate differences in fp32 (include/sh_kernels.h states the expression), never from
 |a|^2 + |b|^2 - 2ab, and no [B, N, M] matrix exists at any point.  Everything is deterministic.  `chamfer` expects scans in the
@@ -619,27 +623,42 @@ class DepthField:
     the surface, at or beyond the near end of z_range: the sensor saw through here), 1 UNKNOWN (no reading, or something nearer
     than z_range) -, `z` fp32 [B, H, W] the surface depth (0 elsewhere), `nearest` int32 [B, H, W] the nearest pixel that is not
     EMPTY as v * W + u (exact, ties to the smallest index, -1 when the image has none), `intrinsics` fp32 [B, 4] and `shape` =
-    (H, W).  `free_space` reads it; made once per image batch by `from_depth`."""
+    (H, W).  `free_space` reads it; made once per image batch by `from_depth`.
+    A RIG field (`from_depth(..., extrinsics=)`) holds the V cameras of every body: the planes are [B, V, H, W], `intrinsics`
+    [B, V, 4], `extrinsics` fp32 [B, V, 12] on the device (camera -> rig, `pack_extrinsics`' layout; a NaN row: an absent camera)
+    and `views` = V; `len` is still B and `shape` (H, W).  Without extrinsics both members are None."""
 
-    def __init__(self, cls, z, nearest, intrinsics):
-        self.cls, self.z, self.nearest, self.intrinsics = cls, z, nearest, intrinsics
-        self.shape = tuple(cls.shape[1:])
+    def __init__(self, cls, z, nearest, intrinsics, extrinsics=None):
+        self.cls, self.z, self.nearest, self.intrinsics, self.extrinsics = cls, z, nearest, intrinsics, extrinsics
+        self.views = None if extrinsics is None else int(extrinsics.shape[1])
+        self.shape = tuple(cls.shape[-2:])
 
     @classmethod
-    def from_depth(cls, depth, intrinsics, device=None, *, depth_scale=1.0, mask=None, z_range=None):
+    def from_depth(cls, depth, intrinsics, device=None, *, extrinsics=None, depth_scale=1.0, mask=None, z_range=None):
         """depth, intrinsics, depth_scale, mask, z_range and device as in `unproject_depth`, with its checks and ValueErrors (raised
         before the device is used).  Two launches, no host synchronisation.  Deterministic - the same bits for an image alone and
-        inside any batch.  RuntimeError for an image side above 16384."""
-        d, k, m, near, far = _depth_inputs("DepthField.from_depth", depth, intrinsics, mask, z_range)
+        inside any batch.  RuntimeError for an image side above 16384.
+        extrinsics: None, or a rig's camera -> rig transforms [V, 3, 4] / [B, V, 3, 4] with depth [V, H, W] / [B, V, H, W] and
+        intrinsics [4], [V, 4] or [B, V, 4] as in `unproject_depth_views` (its checks and ValueErrors): a rig field, made by the
+        same two launches over the B * V images."""
+        what = "DepthField.from_depth"
+        if extrinsics is None:
+            d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
+            d, k, m = _depth_upload(d, k, m, device)
+            return cls(*ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far), k)
+        d, k, ext, m = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
+        d, k, m, near, far = _depth_inputs(what, d, k, m, z_range)
         d, k, m = _depth_upload(d, k, m, device)
-        return cls(*ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far), k)
+        rig = tuple(ext.shape[:2])
+        planes = ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far)
+        return cls(*(p.view(rig + tuple(p.shape[-2:])) for p in planes), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device))
 
     def __len__(self):
         return self.cls.shape[0]
 
     def select(self, sl):
-        """The images `sl` (a slice) as a DepthField sharing this one's memory."""
-        return DepthField(self.cls[sl], self.z[sl], self.nearest[sl], self.intrinsics[sl])
+        """The images `sl` (a slice; of a rig field: the bodies) as a DepthField sharing this one's memory."""
+        return DepthField(self.cls[sl], self.z[sl], self.nearest[sl], self.intrinsics[sl], None if self.extrinsics is None else self.extrinsics[sl])
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
@@ -1336,6 +1355,40 @@ class _FreeSpace(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class _FreeSpaceViews(torch.autograd.Function):
+    """The rig form: x in the model's frame, cam [B, V, 12] its way into every camera's frame (a constant of the step)."""
+
+    @staticmethod
+    def forward(ctx, x, field, cam, n, v_mask, mask_sb, margin):
+        _, _, loss, counts = ops.free_space_views_fwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
+        ctx.args = (field, n, v_mask, mask_sb, margin)
+        ctx.save_for_backward(x, cam, counts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gL):
+        x, cam, counts = ctx.saved_tensors
+        field, n, v_mask, mask_sb, margin = ctx.args
+        g = ops.free_space_views_bwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
+                                     gL.to(torch.float32).contiguous())
+        return g, None, None, None, None, None, None
+
+
+def free_space_cameras(field, pose=None):
+    """The way from the model's frame into every camera of a rig field -> cam fp32 [B, V, 12] = (M | c), q = M x + c
+    (sh_free_space_cameras; include/sh_kernels.h, "Free space from a rig"): the inverse of `pose.compose(E_v)` with E_v the
+    camera's extrinsic, M = R_v^T A^-1 and c = -R_v^T (A^-1 t + t_v), formed in fp64 and rounded once.  pose: the `Pose` (rig frame
+    -> model frame) or None, the identity.  An absent camera, or a body whose A is singular, gives a NaN row: that camera sees no
+    vertex.  One launch, nothing synchronised.  What `free_space(..., cameras=)` takes when the pose stays as it is over many
+    calls.  ValueError for a field that is no rig field or a pose of another batch size."""
+    what = "free_space_cameras"
+    if not isinstance(field, DepthField) or field.views is None:
+        raise ValueError("%s: the field must be a rig field (DepthField.from_depth(..., extrinsics=))" % what)
+    if pose is not None and (not isinstance(pose, Pose) or len(pose) != len(field)):
+        raise ValueError("%s: pose must be a scan.Pose of %d bodies" % (what, len(field)))
+    return ops.free_space_cameras(field.extrinsics, None if pose is None else pose.packed.contiguous())
+
+
 def _check_free_space_weights(what, field, B, margin, weights=()):
     """The ValueErrors of the free-space arguments: a DepthField of B images, a margin and weights that are >= 0 (and not NaN)."""
     if not isinstance(field, DepthField):
@@ -1349,7 +1402,10 @@ def _check_free_space_weights(what, field, B, margin, weights=()):
             raise ValueError("%s: %s must be >= 0, got %r" % (what, name, w))
 
 
-def _free_space_args(what, x_hat, field, pose, n, vertex_mask, margin):
+def _free_space_args(what, x_hat, field, pose, n, vertex_mask, margin, cameras=None):
+    """The checks of `free_space` and `free_space_kinds` -> (x, n, v_mask, mask_sb, cam).  One camera (cam None): x is x_hat in the
+    camera's frame (`pose.to_scan_frame`, torch).  A rig field: x is x_hat as it is and cam [B, V, 12] carries it into every
+    camera's frame inside the kernels - `cameras` as given, else one `free_space_cameras` launch."""
     if not (torch.is_tensor(x_hat) and x_hat.is_cuda):
         raise RuntimeError("semantichuman_amd.scan.%s needs fp32 HIP vertices [B, rows, 3] (got %s); there is no CPU path"
                            % (what, getattr(x_hat, "device", type(x_hat))))
@@ -1361,11 +1417,20 @@ def _free_space_args(what, x_hat, field, pose, n, vertex_mask, margin):
     if not 0 < n <= rows:
         raise ValueError("%s: n = %d outside (0, %d]" % (what, n, rows))
     v_mask, mask_sb = ops._mask_arg(vertex_mask, B, n, x_hat.device)
-    x = x_hat if pose is None else pose.to_scan_frame(x_hat)
-    return x, n, v_mask, mask_sb
+    if field.views is None:
+        if cameras is not None:
+            raise ValueError("%s: cameras= goes with a rig field (DepthField.from_depth(..., extrinsics=))" % what)
+        return (x_hat if pose is None else pose.to_scan_frame(x_hat)), n, v_mask, mask_sb, None
+    if cameras is None:
+        cameras = free_space_cameras(field, pose)
+    elif not (torch.is_tensor(cameras) and cameras.device == x_hat.device and cameras.dtype == torch.float32
+              and tuple(cameras.shape) == (B, field.views, 12)):
+        raise ValueError("%s: cameras must be an fp32 tensor [%d, %d, 12] on the device of x_hat (scan.free_space_cameras), got %s"
+                         % (what, B, field.views, tuple(getattr(cameras, "shape", ()))))
+    return x_hat, n, v_mask, mask_sb, cameras.detach().contiguous()
 
 
-def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0):
+def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0, cameras=None):
     """What a one-view depth image adds to a fit beyond its points: -> (free [B], silhouette [B]), differentiable w.r.t. x_hat
     (sh_free_space_fwd / _bwd; include/sh_kernels.h, "Depth field").  x_hat [B, rows, 3] fp32 on the GPU, field: a `DepthField` of
     the same B.  Every active vertex is projected into its image (pinhole, the field's intrinsics) and reads the ONE pixel it
@@ -1380,22 +1445,36 @@ def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0)
     `pose.to_scan_frame` (plain torch, differentiable) and both values multiplied by pose.scale^2, which puts them in the units
     of x_hat, where they add to a Chamfer value.  The pose takes no gradient.
     Limits: nearest-pixel sampling - the image is read as a constant, the nearest pixel too, so there is no image gradient and
-    the value steps as a vertex crosses a pixel boundary; no robust or truncated form; pinhole without distortion; one view.
-    ValueError for a field of another batch size or a negative margin."""
-    x, n, v_mask, mask_sb = _free_space_args("free_space", x_hat, field, pose, n, vertex_mask, margin)
-    loss = _FreeSpace.apply(x, field, n, v_mask, mask_sb, float(margin))
+    the value steps as a vertex crosses a pixel boundary; no robust or truncated form; pinhole without distortion.
+    A RIG field (`DepthField.from_depth(..., extrinsics=)`; a rig of one serves a single camera): every vertex is judged by each
+    of the V cameras in turn and both values are sums over the cameras of the per-camera means (sh_free_space_views_fwd / _bwd;
+    "Free space from a rig").  x_hat stays in the model's frame: `pose` is then the Pose rig frame -> model frame (None: the
+    model's frame is the rig's), and the way into every camera's frame - the inverse of `pose.compose(E_v)` - is one small launch
+    (`free_space_cameras`) whose result the two kernels apply themselves; no torch launches for the transform.  cameras: that
+    result [B, V, 12], computed by the caller once while the pose stays as it is (`pose` is still read for its scale).  One
+    resolution per rig; an absent camera sees nothing.
+    ValueError for a field of another batch size, a negative margin, or cameras of the wrong shape or without a rig field."""
+    x, n, v_mask, mask_sb, cam = _free_space_args("free_space", x_hat, field, pose, n, vertex_mask, margin, cameras)
+    if cam is None:
+        loss = _FreeSpace.apply(x, field, n, v_mask, mask_sb, float(margin))
+    else:
+        loss = _FreeSpaceViews.apply(x, field, cam, n, v_mask, mask_sb, float(margin))
     if pose is not None:
         loss = loss * (pose.scale * pose.scale)[:, None]
     return loss[:, 0], loss[:, 1]
 
 
-def free_space_kinds(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0):
+def free_space_kinds(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0, cameras=None):
     """What `free_space` did with every vertex -> (kind uint8 [B, n]: 0 no term, 1 free space, 2 silhouette, 3 an UNKNOWN pixel,
-    4 outside the image or behind the camera; counts int32 [B, 4] = active vertices and how many of kind 1, 2 and 4).  Not
-    differentiable."""
-    x, n, v_mask, mask_sb = _free_space_args("free_space_kinds", x_hat.detach() if torch.is_tensor(x_hat) else x_hat, field, pose, n,
-                                             vertex_mask, margin)
-    _, kind, _, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, float(margin))
+    4 outside the image or behind the camera; counts int32 [B, 4] = active vertices and how many of kind 1, 2 and 4).  A rig
+    field: kind [B, V, n] and counts [B, V, 4], per camera.  Not differentiable."""
+    x, n, v_mask, mask_sb, cam = _free_space_args("free_space_kinds", x_hat.detach() if torch.is_tensor(x_hat) else x_hat, field, pose, n,
+                                                  vertex_mask, margin, cameras)
+    if cam is None:
+        _, kind, _, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, float(margin))
+    else:
+        _, kind, _, counts = ops.free_space_views_fwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb,
+                                                      float(margin))
     return kind, counts
 
 
