@@ -1271,6 +1271,9 @@ SH_API int sh_scan_compact(const float* points, const float* normals, const int3
  * sh_free_space_bwd, given the forward call's arguments, its counts and gL fp32 [B][2] -> g_x fp32 [B][rows][3], contiguous:
  *     g_x[b][i] = fl(fl(gL[b][k] * fl(1 / (float)n_act)) * g)  per component, k = 0 for kind 1 and 1 for kind 2
  * and zeros in every other row below `rows`.  One launch, one thread per row; the vertex's case list is evaluated again.
+ * Both run the kernels of "Free space from a rig" below as a rig of one camera WITHOUT a cam: the vertex is taken as it is and the
+ * gradient handed back as it is, with no products - under an identity cam 0 * inf would turn a vertex at Z = +inf into kind 4
+ * and -0 + 0 would lose the sign of a zero gradient word.  At V = 1 the layouts and the order of the sums there are the ones above.
  * Null pointers (v_mask excepted), negative sizes, n > rows, a batch or mask stride shorter than n, a negative or NaN margin,
  * H * W == 0 with n > 0: SH_ERR_INVALID_ARG; H or W above SH_FIELD_MAX_SIDE: SH_ERR_UNSUPPORTED; before the device is touched.
  * B == 0: SH_OK, nothing launched.
@@ -1329,6 +1332,9 @@ SH_API int sh_free_space_bwd(const float* x, int64_t x_sb, int rows, int n, cons
  *     g_x[j] += fl(fl(fl(m_0j * w_0) + fl(m_1j * w_1)) + fl(m_2j * w_2))                              M^T w, one fp32 addition per view
  * Rows without a term, masked rows and rows >= n hold zeros.  One launch, one thread per row, a uniform loop over the views.
  * In both term kernels the body's V records (12 cam words, 4 intrinsics) are staged in LDS once per workgroup.
+ * In the library's launch records (and the profiles made from them) these two launches read free_space_views_fwd_kernel and
+ * free_space_views_bwd_kernel: the entry point's name, not a symbol - the kernels are free_space_fwd_kernel<true> and
+ * free_space_bwd_kernel<true>, the one-camera entry points launch the <false> instantiations.
  * Null pointers (v_mask, and pose for the cameras, excepted), V outside [1, SH_DEPTH_MAX_VIEWS], negative sizes, n > rows, a batch
  * or mask stride shorter than n, a negative or NaN margin, H * W == 0 with n > 0: SH_ERR_INVALID_ARG; H or W above
  * SH_FIELD_MAX_SIDE, B > 65535, B * V > 65535 or V * H * W > INT_MAX: SH_ERR_UNSUPPORTED; all before the device is touched.

@@ -3,8 +3,10 @@
 // or for projecting onto a pixel the sensor saw through (kind 2: its offset from the ray of the nearest pixel that is not
 // empty).  The reference has no counterpart.  No search, no atomics, every output element one plain store; the per-vertex
 // expressions are the header's, each operation rounded on its own.
-// Then the same term for the V cameras of a rig in one launch per pass ("Free space from a rig"): the model -> camera maps come
-// from one small kernel, the vertices are carried into each camera's frame inside the term kernels, and one case list serves all.
+// One kernel per pass serves one camera and the V cameras of a rig ("Free space from a rig"): the model -> camera maps come from
+// one small kernel and the vertices are carried into each camera's frame inside the term kernels.  One camera is a rig of one
+// whose vertices are in the camera's frame already: V = 1 and no cam, and the kernels take the vertex and hand back the gradient
+// as they are - the rig's layouts at V = 1 are the one-camera layouts word for word, and so is the order of the sums.
 #include <climits>
 
 #include "sh_nn.h"
@@ -59,81 +61,12 @@ __device__ __forceinline__ FsTerm fs_case(const FsArgs& a, long image, const flo
     return r;
 }
 
-// One camera: the active vertex i of body b, already in the camera's frame.
-__device__ __forceinline__ FsTerm fs_term(const FsArgs& a, int b, int i) {
-    const float* p = a.x + (long)b * a.x_sb + 3L * i;
-    return fs_case(a, b, a.intr + 4L * b, p[0], p[1], p[2]);
-}
-
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
-// grid (body).  Thread t takes the vertices t, t + 256, ... in order: term and kind are stored, the two sums kept in fp64; then
-// the wave butterfly and the four wave sums in order - the order of chamfer_fwd_kernel.
-__global__ __launch_bounds__(256) void free_space_fwd_kernel(FsArgs a, float* __restrict__ term, uint8_t* __restrict__ kind,
-                                                            float* __restrict__ loss, int32_t* __restrict__ counts) {
-    __shared__ double red[2][4];
-    __shared__ int redi[4][4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const uint8_t* mb = a.v_mask ? a.v_mask + (long)b * a.mask_sb : nullptr;
-    double s1 = 0.0, s2 = 0.0;
-    int na = 0, k1 = 0, k2 = 0, k4 = 0;
-    for (int i = tid; i < a.n; i += 256) {
-        FsTerm r = {SH_FS_NONE, 0.f, 0.f, 0.f, 0.f};
-        if (!mb || mb[i] != 0) {
-            ++na;
-            r = fs_term(a, b, i);
-        }
-        term[(long)b * a.n + i] = r.term;
-        kind[(long)b * a.n + i] = (uint8_t)r.kind;
-        if (r.kind == SH_FS_FREE) { s1 += (double)r.term; ++k1; }
-        if (r.kind == SH_FS_SILHOUETTE) { s2 += (double)r.term; ++k2; }
-        k4 += r.kind == SH_FS_OUTSIDE;
-    }
-    s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
-    na = wave_sum_i(na); k1 = wave_sum_i(k1); k2 = wave_sum_i(k2); k4 = wave_sum_i(k4);
-    if ((tid & 63) == 0) {
-        const int w = tid >> 6;
-        red[0][w] = s1; red[1][w] = s2;
-        redi[0][w] = na; redi[1][w] = k1; redi[2][w] = k2; redi[3][w] = k4;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double t1 = 0.0, t2 = 0.0;
-        int c[4] = {0, 0, 0, 0};
-        for (int w = 0; w < 4; ++w) {
-            t1 += red[0][w]; t2 += red[1][w];
-            for (int j = 0; j < 4; ++j) c[j] += redi[j][w];
-        }
-        loss[2 * b] = c[0] > 0 ? (float)(t1 / (double)c[0]) : 0.f;
-        loss[2 * b + 1] = c[0] > 0 ? (float)(t2 / (double)c[0]) : 0.f;
-        for (int j = 0; j < 4; ++j) counts[4 * b + j] = c[j];
-    }
-}
-
-// grid (row tile of 256, body), thread = one row of g_x: the vertex's case list once more, its gradient times
-// fl(gL[b][k] * fl(1 / n_act)); zeros for every row without a term.
-__global__ __launch_bounds__(256) void free_space_bwd_kernel(FsArgs a, int rows, const int32_t* __restrict__ counts, const float* __restrict__ gL,
-                                                            float* __restrict__ g_x) {
-    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows) return;
-    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
-    if (i < a.n && (!a.v_mask || a.v_mask[(long)b * a.mask_sb + i] != 0)) {
-        const FsTerm r = fs_term(a, b, i);
-        if (r.kind == SH_FS_FREE || r.kind == SH_FS_SILHOUETTE) {
-            const float inv = 1.f / (float)counts[4 * b];                // n_act >= 1: this vertex is active
-            const float s = gL[2 * b + (r.kind == SH_FS_SILHOUETTE)] * inv;
-            g0 = s * r.gx; g1 = s * r.gy; g2 = s * r.gz;
-        }
-    }
-    float* o = g_x + ((long)b * rows + i) * 3;
-    o[0] = g0; o[1] = g1; o[2] = g2;
-}
-
-// ---------------------------------------------------------------------------------------------- "Free space from a rig"
 constexpr int VIEWS_NT = 1024;          // the forward workgroup: the terms are written by all of it, folded by its first 256 threads
 constexpr int VIEW_WORDS = 16;          // a view's record in LDS: the 12 words of cam (M row-major, c), then fx, fy, cx, cy
 
@@ -180,19 +113,25 @@ __global__ __launch_bounds__(64) void free_space_cameras_kernel(const float* __r
     }
 }
 
-// The body's V records into LDS (ends with a barrier): every later read of them is a broadcast.
-template <int NT>
+// The body's V records into LDS (ends with a barrier): every later read of them is a broadcast.  Without cam (CAM false) the
+// twelve words of the map are neither staged nor read.  CAM is a template parameter because a test of cam around the load keeps
+// hipcc from unrolling this loop as it does for a rig.
+template <int NT, bool CAM>
 __device__ __forceinline__ void stage_views(const FsArgs& a, const float* __restrict__ cam, int V, int b, float* sv) {
     for (int i = threadIdx.x; i < V * VIEW_WORDS; i += NT) {
         const int v = i / VIEW_WORDS, k = i - v * VIEW_WORDS;
         const long rec = (long)b * V + v;
-        sv[i] = k < 12 ? cam[12 * rec + k] : a.intr[4 * rec + (k - 12)];
+        if constexpr (CAM) sv[i] = k < 12 ? cam[12 * rec + k] : a.intr[4 * rec + (k - 12)];
+        else if (k >= 12) sv[i] = a.intr[4 * rec + (k - 12)];
     }
     __syncthreads();
 }
 
-// The header's Q = M x + c of one view's record, then the case list under that view's intrinsics and image.
+// The header's Q = M x + c of one view's record, then the case list under that view's intrinsics and image.  CAM false: x is in
+// the camera's frame already and is taken as it is - under an identity record 0 * inf would make a vertex at Z = +inf a NaN.
+template <bool CAM>
 __device__ __forceinline__ FsTerm fs_view(const FsArgs& a, const float* rec, long image, float x0, float x1, float x2) {
+    if constexpr (!CAM) return fs_case(a, image, rec + 12, x0, x1, x2);
     const float X = ((rec[0] * x0 + rec[1] * x1) + rec[2] * x2) + rec[9];
     const float Y = ((rec[3] * x0 + rec[4] * x1) + rec[5] * x2) + rec[10];
     const float Z = ((rec[6] * x0 + rec[7] * x1) + rec[8] * x2) + rec[11];
@@ -202,15 +141,17 @@ __device__ __forceinline__ FsTerm fs_view(const FsArgs& a, const float* rec, lon
 // grid (body), VIEWS_NT threads.  (1) Every thread takes vertices tid, tid + VIEWS_NT, ... and, in a uniform loop over the views,
 // stores term and kind.  (2) After the barrier the first 256 threads read them back in the header's order - thread t the vertices
 // t, t + 256, ..., the views ascending inside a vertex - into the two fp64 sums; the wave butterfly and the four wave sums as in
-// free_space_fwd_kernel.  (3) The counts are integers: per view, all threads count the stored kinds.
-__global__ __launch_bounds__(VIEWS_NT) void free_space_views_fwd_kernel(FsArgs a, const float* __restrict__ cam, int V, float* term, uint8_t* kind,
-                                                                       float* __restrict__ loss, int32_t* __restrict__ counts) {
+// chamfer_fwd_kernel.  (3) The counts are integers: per view, all threads count the stored kinds.  CAM false: cam == nullptr, one
+// camera, V = 1.  The form is a template parameter in both kernels: the rig's instantiations are the code they were before.
+template <bool CAM>
+__global__ __launch_bounds__(VIEWS_NT) void free_space_fwd_kernel(FsArgs a, const float* __restrict__ cam, int V, float* term, uint8_t* kind,
+                                                                 float* __restrict__ loss, int32_t* __restrict__ counts) {
     __shared__ float sv[SH_DEPTH_MAX_VIEWS * VIEW_WORDS];
     __shared__ double red[2][4];
     __shared__ int redi[SH_DEPTH_MAX_VIEWS][3][VIEWS_NT / 64];
     __shared__ int reda[VIEWS_NT / 64];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-    stage_views<VIEWS_NT>(a, cam, V, b, sv);
+    stage_views<VIEWS_NT, CAM>(a, cam, V, b, sv);
     const uint8_t* mb = a.v_mask ? a.v_mask + (long)b * a.mask_sb : nullptr;
     const long plane = (long)b * V * a.n;
     int na = 0;
@@ -221,7 +162,7 @@ __global__ __launch_bounds__(VIEWS_NT) void free_space_views_fwd_kernel(FsArgs a
         const float x0 = p[0], x1 = p[1], x2 = p[2];
         for (int v = 0; v < V; ++v) {                                    // uniform
             FsTerm r = {SH_FS_NONE, 0.f, 0.f, 0.f, 0.f};
-            if (active) r = fs_view(a, sv + VIEW_WORDS * v, (long)b * V + v, x0, x1, x2);
+            if (active) r = fs_view<CAM>(a, sv + VIEW_WORDS * v, (long)b * V + v, x0, x1, x2);
             term[plane + (long)v * a.n + i] = r.term;
             kind[plane + (long)v * a.n + i] = (uint8_t)r.kind;
         }
@@ -272,13 +213,15 @@ __global__ __launch_bounds__(VIEWS_NT) void free_space_views_fwd_kernel(FsArgs a
 }
 
 // grid (row tile of 256, body), thread = one row of g_x: per view the case list once more, its gradient times
-// fl(gL[b][k] * fl(1 / n_act)), carried back by M^T and added in fp32, the views ascending.
-__global__ __launch_bounds__(256) void free_space_views_bwd_kernel(FsArgs a, const float* __restrict__ cam, int V, int rows,
-                                                                  const int32_t* __restrict__ counts, const float* __restrict__ gL,
-                                                                  float* __restrict__ g_x) {
+// fl(gL[b][k] * fl(1 / n_act)), carried back by M^T and added in fp32, the views ascending.  CAM false: cam == nullptr, one camera,
+// V = 1, and that product is the row itself - through an identity record -0 + 0 would lose the sign of a zero.
+template <bool CAM>
+__global__ __launch_bounds__(256) void free_space_bwd_kernel(FsArgs a, const float* __restrict__ cam, int V, int rows,
+                                                            const int32_t* __restrict__ counts, const float* __restrict__ gL,
+                                                            float* __restrict__ g_x) {
     __shared__ float sv[SH_DEPTH_MAX_VIEWS * VIEW_WORDS];
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    stage_views<256>(a, cam, V, b, sv);
+    stage_views<256, CAM>(a, cam, V, b, sv);
     if (i >= rows) return;
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
     if (i < a.n && (!a.v_mask || a.v_mask[(long)b * a.mask_sb + i] != 0)) {
@@ -288,13 +231,17 @@ __global__ __launch_bounds__(256) void free_space_views_bwd_kernel(FsArgs a, con
         const float s_free = gL[2 * b] * inv, s_sil = gL[2 * b + 1] * inv;
         for (int v = 0; v < V; ++v) {                                    // uniform
             const float* rec = sv + VIEW_WORDS * v;
-            const FsTerm r = fs_view(a, rec, (long)b * V + v, x0, x1, x2);
+            const FsTerm r = fs_view<CAM>(a, rec, (long)b * V + v, x0, x1, x2);
             if (r.kind == SH_FS_FREE || r.kind == SH_FS_SILHOUETTE) {
                 const float s = r.kind == SH_FS_SILHOUETTE ? s_sil : s_free;
                 const float w0 = s * r.gx, w1 = s * r.gy, w2 = s * r.gz;
-                g0 += (rec[0] * w0 + rec[3] * w1) + rec[6] * w2;
-                g1 += (rec[1] * w0 + rec[4] * w1) + rec[7] * w2;
-                g2 += (rec[2] * w0 + rec[5] * w1) + rec[8] * w2;
+                if constexpr (!CAM) {
+                    g0 = w0; g1 = w1; g2 = w2;
+                } else {
+                    g0 += (rec[0] * w0 + rec[3] * w1) + rec[6] * w2;
+                    g1 += (rec[1] * w0 + rec[4] * w1) + rec[7] * w2;
+                    g2 += (rec[2] * w0 + rec[5] * w1) + rec[8] * w2;
+                }
             }
         }
     }
@@ -302,9 +249,12 @@ __global__ __launch_bounds__(256) void free_space_views_bwd_kernel(FsArgs a, con
     o[0] = g0; o[1] = g1; o[2] = g2;
 }
 
-// What both entry points ask of the arguments they share.
-int check_args(const char* who, const float* x, int64_t x_sb, int rows, int n, const uint8_t* cls, const float* z, const int32_t* nearest,
-               const float* intr, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B) {
+// What the four entry points ask of their arguments; `who` names the one that was called in every error text.  One camera:
+// rig = false, cam = nullptr and V = 1, for which the rig's limits are the one camera's own.
+int check_args(const char* who, bool rig, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+               const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B) {
+    SH_REQUIRE(!rig || cam, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(V >= 1 && V <= SH_DEPTH_MAX_VIEWS, SH_ERR_INVALID_ARG, "%s: V = %d views, must lie in [1, %d]", who, V, SH_DEPTH_MAX_VIEWS);
     SH_REQUIRE(x && cls && z && nearest && intr, SH_ERR_INVALID_ARG, "%s: null pointer", who);
     SH_REQUIRE(B >= 0 && H >= 0 && W >= 0 && rows >= 0 && n >= 0 && n <= rows, SH_ERR_INVALID_ARG,
                "%s: bad size (B %d, H %d, W %d, rows %d, n %d)", who, B, H, W, rows, n);
@@ -314,17 +264,45 @@ int check_args(const char* who, const float* x, int64_t x_sb, int rows, int n, c
     SH_REQUIRE(H <= SH_FIELD_MAX_SIDE && W <= SH_FIELD_MAX_SIDE && B <= 65535, SH_ERR_UNSUPPORTED, "%s: H and W must not exceed %d (B 65535)", who,
                SH_FIELD_MAX_SIDE);
     SH_REQUIRE((n == 0) || (H > 0 && W > 0), SH_ERR_INVALID_ARG, "%s: an empty image (H %d, W %d)", who, H, W);
+    SH_REQUIRE((long)B * V <= 65535 && (long)V * H * W <= INT_MAX, SH_ERR_UNSUPPORTED,
+               "%s: B * V must not exceed 65535 and V * H * W must fit in 31 bits (B %d, V %d, H %d, W %d)", who, B, V, H, W);
     return SH_OK;
 }
 
-// The same for the rig's two: a view count in range and a cam, then check_args, then the limits of B * V images.
-int check_views_args(const char* who, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
-                     const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B) {
-    SH_REQUIRE(cam, SH_ERR_INVALID_ARG, "%s: null pointer", who);
-    SH_REQUIRE(V >= 1 && V <= SH_DEPTH_MAX_VIEWS, SH_ERR_INVALID_ARG, "%s: V = %d views, must lie in [1, %d]", who, V, SH_DEPTH_MAX_VIEWS);
-    if (const int rc = check_args(who, x, x_sb, rows, n, cls, z, nearest, intr, H, W, v_mask, mask_sb, margin, B)) return rc;
-    SH_REQUIRE((long)B * V <= 65535 && (long)V * H * W <= INT_MAX, SH_ERR_UNSUPPORTED,
-               "%s: B * V must not exceed 65535 and V * H * W must fit in 31 bits (B %d, V %d, H %d, W %d)", who, B, V, H, W);
+// Every check and the launch of a forward entry point, and below of a backward one.  The launch record is the entry point's name
+// without the "sh_", then "_kernel"; only a rig's names V.
+int free_space_fwd(const char* who, bool rig, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                   const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B,
+                   float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream) {
+    if (const int rc = check_args(who, rig, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
+    SH_REQUIRE(term && kind && loss && counts, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (B == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
+    char views[16] = "";
+    if (rig) snprintf(views, sizeof views, " V=%d", V);
+    ShProfScope ps(st, "%s_kernel|B=%d%s n=%d H=%d W=%d", who + 3, B, views, n, H, W);
+    if (cam) SH_LAUNCH_PS(ps, free_space_fwd_kernel<true>, dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts);
+    else SH_LAUNCH_PS(ps, free_space_fwd_kernel<false>, dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts);
+    SH_CHECK_LAUNCH(who + 3);
+    return SH_OK;
+}
+
+int free_space_bwd(const char* who, bool rig, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                   const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
+                   const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream) {
+    if (const int rc = check_args(who, rig, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
+    SH_REQUIRE(counts && gL && g_x, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    if (B == 0 || rows == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
+    char views[16] = "";
+    if (rig) snprintf(views, sizeof views, " V=%d", V);
+    ShProfScope ps(st, "%s_kernel|B=%d%s rows=%d n=%d", who + 3, B, views, rows, n);
+    const dim3 grid((unsigned)sh_cdiv(rows, 256), (unsigned)B);
+    if (cam) SH_LAUNCH_PS(ps, free_space_bwd_kernel<true>, grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x);
+    else SH_LAUNCH_PS(ps, free_space_bwd_kernel<false>, grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x);
+    SH_CHECK_LAUNCH(who + 3);
     return SH_OK;
 }
 
@@ -335,29 +313,15 @@ extern "C" {
 int sh_free_space_fwd(const float* x, int64_t x_sb, int rows, int n, const uint8_t* cls, const float* z, const int32_t* nearest,
                       const float* intr, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B, float* term, uint8_t* kind,
                       float* loss, int32_t* counts, sh_stream_t stream) {
-    if (const int rc = check_args("sh_free_space_fwd", x, x_sb, rows, n, cls, z, nearest, intr, H, W, v_mask, mask_sb, margin, B)) return rc;
-    SH_REQUIRE(term && kind && loss && counts, SH_ERR_INVALID_ARG, "sh_free_space_fwd: null pointer");
-    if (B == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
-    ShProfScope ps(st, "free_space_fwd_kernel|B=%d n=%d H=%d W=%d", B, n, H, W);
-    SH_LAUNCH_PS(ps, free_space_fwd_kernel, dim3((unsigned)B), dim3(256), 0, st, a, term, kind, loss, counts);
-    SH_CHECK_LAUNCH("free_space_fwd");
-    return SH_OK;
+    return free_space_fwd("sh_free_space_fwd", false, x, x_sb, rows, n, nullptr, cls, z, nearest, intr, 1, H, W, v_mask, mask_sb, margin, B, term,
+                          kind, loss, counts, stream);
 }
 
 int sh_free_space_bwd(const float* x, int64_t x_sb, int rows, int n, const uint8_t* cls, const float* z, const int32_t* nearest,
                       const float* intr, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, const int32_t* counts,
                       const float* gL, int B, float* g_x, sh_stream_t stream) {
-    if (const int rc = check_args("sh_free_space_bwd", x, x_sb, rows, n, cls, z, nearest, intr, H, W, v_mask, mask_sb, margin, B)) return rc;
-    SH_REQUIRE(counts && gL && g_x, SH_ERR_INVALID_ARG, "sh_free_space_bwd: null pointer");
-    if (B == 0 || rows == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
-    ShProfScope ps(st, "free_space_bwd_kernel|B=%d rows=%d n=%d", B, rows, n);
-    SH_LAUNCH_PS(ps, free_space_bwd_kernel, dim3((unsigned)sh_cdiv(rows, 256), (unsigned)B), dim3(256), 0, st, a, rows, counts, gL, g_x);
-    SH_CHECK_LAUNCH("free_space_bwd");
-    return SH_OK;
+    return free_space_bwd("sh_free_space_bwd", false, x, x_sb, rows, n, nullptr, cls, z, nearest, intr, 1, H, W, v_mask, mask_sb, margin, counts,
+                          gL, B, g_x, stream);
 }
 
 int sh_free_space_cameras(const float* pose, const float* ext, int B, int V, float* cam, sh_stream_t stream) {
@@ -377,32 +341,15 @@ int sh_free_space_cameras(const float* pose, const float* ext, int B, int V, flo
 int sh_free_space_views_fwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
                             const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
                             int B, float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream) {
-    const char* who = "sh_free_space_views_fwd";
-    if (const int rc = check_views_args(who, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
-    SH_REQUIRE(term && kind && loss && counts, SH_ERR_INVALID_ARG, "%s: null pointer", who);
-    if (B == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
-    ShProfScope ps(st, "free_space_views_fwd_kernel|B=%d V=%d n=%d H=%d W=%d", B, V, n, H, W);
-    SH_LAUNCH_PS(ps, free_space_views_fwd_kernel, dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts);
-    SH_CHECK_LAUNCH("free_space_views_fwd");
-    return SH_OK;
+    return free_space_fwd("sh_free_space_views_fwd", true, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B, term,
+                          kind, loss, counts, stream);
 }
 
 int sh_free_space_views_bwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
                             const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
                             const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream) {
-    const char* who = "sh_free_space_views_bwd";
-    if (const int rc = check_views_args(who, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
-    SH_REQUIRE(counts && gL && g_x, SH_ERR_INVALID_ARG, "%s: null pointer", who);
-    if (B == 0 || rows == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const FsArgs a = {x, (long)x_sb, n, cls, z, nearest, intr, H, W, v_mask, (long)mask_sb, margin};
-    ShProfScope ps(st, "free_space_views_bwd_kernel|B=%d V=%d rows=%d n=%d", B, V, rows, n);
-    SH_LAUNCH_PS(ps, free_space_views_bwd_kernel, dim3((unsigned)sh_cdiv(rows, 256), (unsigned)B), dim3(256), 0, st, a, cam, V, rows, counts, gL,
-                 g_x);
-    SH_CHECK_LAUNCH("free_space_views_bwd");
-    return SH_OK;
+    return free_space_bwd("sh_free_space_views_bwd", true, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, counts,
+                          gL, B, g_x, stream);
 }
 
 }  // extern "C"

@@ -771,50 +771,73 @@ def depth_field(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far
     return cls, z, nearest
 
 
-def _free_space_args(who, x, n, cls, z, nearest, intr, v_mask, mask_sb, margin):
-    """The arguments sh_free_space_fwd and sh_free_space_bwd share, checked -> (B, rows, their C arguments up to `margin`)."""
+def _dense(t, device, dtype, shape):
+    return torch.is_tensor(t) and t.device == device and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+
+def _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
+    """The arguments the free-space entry points share, checked -> (B, lead, rows, their C arguments up to `margin`).  rig True: a
+    rig's field [B, V, H, W] with intr [B, V, 4] and cam [B, V, 12], lead = (B, V); rig False: one camera's [B, H, W] and [B, 4],
+    lead = (B,) - then cam is neither read nor among the arguments.  who: the public name, for the messages only."""
     B, rows, x_sb = _points(x, who)
     n = int(n)
     if not 0 <= n <= rows:
         raise ValueError("%s: n = %d exceeds the model's %d rows" % (who, n, rows))
-    if not (torch.is_tensor(cls) and cls.device == x.device and cls.dtype == torch.uint8 and cls.dim() == 3 and cls.shape[0] == B
+    if not (torch.is_tensor(cls) and cls.device == x.device and cls.dtype == torch.uint8 and cls.dim() == (4 if rig else 3) and cls.shape[0] == B
             and cls.is_contiguous()):
-        raise ValueError("%s: cls must be a contiguous uint8 tensor [%d, H, W] on the device of x" % (who, B))
-    H, W = cls.shape[1:]
-    for t, dtype, shape, what in ((z, torch.float32, (B, H, W), "z fp32"), (nearest, torch.int32, (B, H, W), "nearest int32"),
-                                  (intr, torch.float32, (B, 4), "intr fp32")):
-        if not (torch.is_tensor(t) and t.device == x.device and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+        raise ValueError("%s: cls must be a contiguous uint8 tensor [%d, %sH, W] on the device of x" % (who, B, "V, " if rig else ""))
+    lead, (H, W) = tuple(cls.shape[:-2]), cls.shape[-2:]
+    if rig and not 1 <= lead[1] <= MAX_VIEWS:
+        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, lead[1], MAX_VIEWS))
+    planes = [(z, torch.float32, lead + (H, W), "z fp32"), (nearest, torch.int32, lead + (H, W), "nearest int32"),
+              (intr, torch.float32, lead + (4,), "intr fp32")]
+    if rig:
+        planes.append((cam, torch.float32, lead + (12,), "cam fp32"))
+    for t, dtype, shape, what in planes:
+        if not _dense(t, x.device, dtype, shape):
             raise ValueError("%s: %s must be a contiguous tensor %s on the device of x" % (who, what, list(shape)))
-    return B, rows, (ptr(x), x_sb, rows, n, ptr(cls), ptr(z), ptr(nearest), ptr(intr), H, W, ptr(v_mask), mask_sb, float(margin))
+    head, field, tail = (ptr(x), x_sb, rows, n), (ptr(cls), ptr(z), ptr(nearest), ptr(intr)), (H, W, ptr(v_mask), mask_sb, float(margin))
+    if rig:
+        return B, lead, rows, head + (ptr(cam),) + field + (lead[1],) + tail
+    return B, lead, rows, head + field + tail
+
+
+def _free_space_fwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
+    """`free_space_fwd` and `free_space_views_fwd` (rig) behind one set of checks; the outputs carry the field's leading shape."""
+    who = "free_space_views_fwd" if rig else "free_space_fwd"
+    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    term = torch.empty(lead + (int(n),), dtype=torch.float32, device=x.device)
+    kind = torch.empty(lead + (int(n),), dtype=torch.uint8, device=x.device)
+    loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+    counts = torch.empty(lead + (4,), dtype=torch.int32, device=x.device)
+    check(getattr(_lib.load(), "sh_" + who)(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_" + who)
+    return term, kind, loss, counts
+
+
+def _free_space_bwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
+    """`free_space_bwd` and `free_space_views_bwd` (rig) behind one set of checks."""
+    who = "free_space_views_bwd" if rig else "free_space_bwd"
+    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+    if not _dense(gL, x.device, torch.float32, (B, 2)):
+        raise ValueError("%s: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % (who, B))
+    if rig and not _dense(counts, x.device, torch.int32, lead + (4,)):     # one camera's counts were never checked here
+        raise ValueError("%s: counts must be the forward call's int32 tensor %s" % (who, list(lead + (4,))))
+    g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
+    check(getattr(_lib.load(), "sh_" + who)(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_" + who)
+    return g
 
 
 def free_space_fwd(x, n, cls, z, nearest, intr, v_mask=None, mask_sb=0, margin=0.0):
     """sh_free_space_fwd: x [B, *, 3] camera-frame points of which the first n rows are vertices, a depth field (cls, z, nearest)
     and intr [B, 4] of the same B; v_mask uint8 [n] (mask_sb 0) or [B, n] (mask_sb n), as `_mask_arg` makes it -> (term fp32
     [B, n], kind uint8 [B, n], loss fp32 [B, 2] = (free space, silhouette), counts int32 [B, 4] = (active, kind 1, 2, 4))."""
-    B, rows, args = _free_space_args("free_space_fwd", x, n, cls, z, nearest, intr, v_mask, mask_sb, margin)
-    n = int(n)
-    term = torch.empty((B, n), dtype=torch.float32, device=x.device)
-    kind = torch.empty((B, n), dtype=torch.uint8, device=x.device)
-    loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-    counts = torch.empty((B, 4), dtype=torch.int32, device=x.device)
-    check(_lib.load().sh_free_space_fwd(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_free_space_fwd")
-    return term, kind, loss, counts
+    return _free_space_fwd(False, x, n, None, cls, z, nearest, intr, v_mask, mask_sb, margin)
 
 
 def free_space_bwd(x, n, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
     """sh_free_space_bwd: the forward call's arguments, its counts and gL fp32 [B, 2] -> g_x contiguous [B, rows, 3] (every element
     written)."""
-    B, rows, args = _free_space_args("free_space_bwd", x, n, cls, z, nearest, intr, v_mask, mask_sb, margin)
-    if not (torch.is_tensor(gL) and gL.device == x.device and gL.dtype == torch.float32 and gL.is_contiguous() and tuple(gL.shape) == (B, 2)):
-        raise ValueError("free_space_bwd: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % B)
-    g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
-    check(_lib.load().sh_free_space_bwd(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_free_space_bwd")
-    return g
-
-
-def _dense(t, device, dtype, shape):
-    return torch.is_tensor(t) and t.device == device and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+    return _free_space_bwd(False, x, n, None, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL)
 
 
 def free_space_cameras(ext, pose=None):
@@ -835,52 +858,18 @@ def free_space_cameras(ext, pose=None):
     return cam
 
 
-def _free_space_views_args(who, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
-    """The arguments sh_free_space_views_fwd and _bwd share, checked -> (B, V, rows, their C arguments up to `margin`)."""
-    B, rows, x_sb = _points(x, who)
-    n = int(n)
-    if not 0 <= n <= rows:
-        raise ValueError("%s: n = %d exceeds the model's %d rows" % (who, n, rows))
-    if not (torch.is_tensor(cls) and cls.device == x.device and cls.dtype == torch.uint8 and cls.dim() == 4 and cls.shape[0] == B
-            and cls.is_contiguous()):
-        raise ValueError("%s: cls must be a contiguous uint8 tensor [%d, V, H, W] on the device of x" % (who, B))
-    V, H, W = cls.shape[1:]
-    if not 1 <= V <= MAX_VIEWS:
-        raise ValueError("%s: V = %d views, must lie in [1, %d]" % (who, V, MAX_VIEWS))
-    for t, dtype, shape, what in ((z, torch.float32, (B, V, H, W), "z fp32"), (nearest, torch.int32, (B, V, H, W), "nearest int32"),
-                                  (intr, torch.float32, (B, V, 4), "intr fp32"), (cam, torch.float32, (B, V, 12), "cam fp32")):
-        if not _dense(t, x.device, dtype, shape):
-            raise ValueError("%s: %s must be a contiguous tensor %s on the device of x" % (who, what, list(shape)))
-    return B, V, rows, (ptr(x), x_sb, rows, n, ptr(cam), ptr(cls), ptr(z), ptr(nearest), ptr(intr), V, H, W, ptr(v_mask), mask_sb, float(margin))
-
-
 def free_space_views_fwd(x, n, cam, cls, z, nearest, intr, v_mask=None, mask_sb=0, margin=0.0):
     """sh_free_space_views_fwd: x [B, *, 3] model-frame points of which the first n rows are vertices, cam [B, V, 12]
     (`free_space_cameras`), a rig's depth field (cls, z, nearest [B, V, H, W]) and intr [B, V, 4]; v_mask as in `free_space_fwd`
     -> (term fp32 [B, V, n], kind uint8 [B, V, n], loss fp32 [B, 2] = (free space, silhouette) summed over the views, counts int32
     [B, V, 4] = (active, kind 1, 2, 4) per view)."""
-    B, V, rows, args = _free_space_views_args("free_space_views_fwd", x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
-    n = int(n)
-    term = torch.empty((B, V, n), dtype=torch.float32, device=x.device)
-    kind = torch.empty((B, V, n), dtype=torch.uint8, device=x.device)
-    loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-    counts = torch.empty((B, V, 4), dtype=torch.int32, device=x.device)
-    check(_lib.load().sh_free_space_views_fwd(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_free_space_views_fwd")
-    return term, kind, loss, counts
+    return _free_space_fwd(True, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
 
 
 def free_space_views_bwd(x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
     """sh_free_space_views_bwd: the forward call's arguments, its counts [B, V, 4] and gL fp32 [B, 2] -> g_x contiguous
     [B, rows, 3] in the frame of x (every element written)."""
-    who = "free_space_views_bwd"
-    B, V, rows, args = _free_space_views_args(who, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
-    if not _dense(gL, x.device, torch.float32, (B, 2)):
-        raise ValueError("%s: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % (who, B))
-    if not _dense(counts, x.device, torch.int32, (B, V, 4)):
-        raise ValueError("%s: counts must be the forward call's int32 tensor [%d, %d, 4]" % (who, B, V))
-    g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
-    check(_lib.load().sh_free_space_views_bwd(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_" + who)
-    return g
+    return _free_space_bwd(True, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL)
 
 
 ROBUST_FORMS = {"geman-mcclure": 1, "huber": 2}                # enum sh_robust (0: none)

@@ -642,15 +642,15 @@ class DepthField:
         intrinsics [4], [V, 4] or [B, V, 4] as in `unproject_depth_views` (its checks and ValueErrors): a rig field, made by the
         same two launches over the B * V images."""
         what = "DepthField.from_depth"
-        if extrinsics is None:
-            d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
-            d, k, m = _depth_upload(d, k, m, device)
-            return cls(*ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far), k)
-        d, k, ext, m = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
-        d, k, m, near, far = _depth_inputs(what, d, k, m, z_range)
+        ext = None
+        if extrinsics is not None:
+            depth, intrinsics, ext, mask = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
+        d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
         d, k, m = _depth_upload(d, k, m, device)
-        rig = tuple(ext.shape[:2])
         planes = ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far)
+        if ext is None:
+            return cls(*planes, k)
+        rig = tuple(ext.shape[:2])                                          # the same call over the B * V images, reshaped
         return cls(*(p.view(rig + tuple(p.shape[-2:])) for p in planes), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device))
 
     def __len__(self):
@@ -1338,29 +1338,18 @@ def _check_pair(x, scans, n, what):
 
 
 # ------------------------------------------------------------------------------------------------ free space and silhouette
+def _free_space_fwd(x, field, cam, n, v_mask, mask_sb, margin):
+    """The forward entry point on a field's planes -> (term, kind, loss, counts).  cam None: one camera, x in its frame."""
+    return ops._free_space_fwd(cam is not None, x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
+
+
 class _FreeSpace(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, field, n, v_mask, mask_sb, margin):
-        _, _, loss, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
-        ctx.args = (field, n, v_mask, mask_sb, margin)
-        ctx.save_for_backward(x, counts)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gL):
-        x, counts = ctx.saved_tensors
-        field, n, v_mask, mask_sb, margin = ctx.args
-        g = ops.free_space_bwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
-                               gL.to(torch.float32).contiguous())
-        return g, None, None, None, None, None
-
-
-class _FreeSpaceViews(torch.autograd.Function):
-    """The rig form: x in the model's frame, cam [B, V, 12] its way into every camera's frame (a constant of the step)."""
+    """x in the frame cam [B, V, 12] starts from - the model's; cam is its way into every camera's frame, a constant of the step - or,
+    cam None, in the one camera's own frame."""
 
     @staticmethod
     def forward(ctx, x, field, cam, n, v_mask, mask_sb, margin):
-        _, _, loss, counts = ops.free_space_views_fwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
+        _, _, loss, counts = _free_space_fwd(x, field, cam, n, v_mask, mask_sb, margin)
         ctx.args = (field, n, v_mask, mask_sb, margin)
         ctx.save_for_backward(x, cam, counts)
         return loss
@@ -1369,8 +1358,8 @@ class _FreeSpaceViews(torch.autograd.Function):
     def backward(ctx, gL):
         x, cam, counts = ctx.saved_tensors
         field, n, v_mask, mask_sb, margin = ctx.args
-        g = ops.free_space_views_bwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
-                                     gL.to(torch.float32).contiguous())
+        g = ops._free_space_bwd(cam is not None, x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
+                                gL.to(torch.float32).contiguous())
         return g, None, None, None, None, None, None
 
 
@@ -1455,10 +1444,7 @@ def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0,
     resolution per rig; an absent camera sees nothing.
     ValueError for a field of another batch size, a negative margin, or cameras of the wrong shape or without a rig field."""
     x, n, v_mask, mask_sb, cam = _free_space_args("free_space", x_hat, field, pose, n, vertex_mask, margin, cameras)
-    if cam is None:
-        loss = _FreeSpace.apply(x, field, n, v_mask, mask_sb, float(margin))
-    else:
-        loss = _FreeSpaceViews.apply(x, field, cam, n, v_mask, mask_sb, float(margin))
+    loss = _FreeSpace.apply(x, field, cam, n, v_mask, mask_sb, float(margin))
     if pose is not None:
         loss = loss * (pose.scale * pose.scale)[:, None]
     return loss[:, 0], loss[:, 1]
@@ -1470,11 +1456,7 @@ def free_space_kinds(x_hat, field, *, pose=None, n=None, vertex_mask=None, margi
     field: kind [B, V, n] and counts [B, V, 4], per camera.  Not differentiable."""
     x, n, v_mask, mask_sb, cam = _free_space_args("free_space_kinds", x_hat.detach() if torch.is_tensor(x_hat) else x_hat, field, pose, n,
                                                   vertex_mask, margin, cameras)
-    if cam is None:
-        _, kind, _, counts = ops.free_space_fwd(x, n, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, float(margin))
-    else:
-        _, kind, _, counts = ops.free_space_views_fwd(x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb,
-                                                      float(margin))
+    _, kind, _, counts = _free_space_fwd(x, field, cam, n, v_mask, mask_sb, float(margin))
     return kind, counts
 
 

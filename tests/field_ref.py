@@ -175,6 +175,30 @@ def gradient(kind, g, counts, gL, rows):
     return out
 
 
+def edge_rows(f):
+    """Camera-frame vertices of field f on which taking a vertex as it is and carrying it through an identity map part ways: M x
+    with M = I multiplies Z = +inf or X = -inf by the zeros of the other rows (0 * inf: a NaN, kind 4 where the case list has
+    another answer), and M^T w added to 0 turns a gradient word -0 into +0.  Z = +inf projects onto the principal point's pixel
+    whatever X and Y are; the last row stands in front of that pixel's column with X = -0: where the pixel is SURFACE its term is
+    of kind 1 with g = (0, 0, -2 e), and a negative gL makes the first two words -0."""
+    fx, fy, cx, cy = (float(t) for t in f.intr)
+    v0 = math.floor(float(F32(cy) + F32(0.5)))
+    near = 2.0 ** -3
+    return np.asarray([[0.25, -0.125, np.inf], [-np.inf, 0.1, 2.0], [np.nan, 0.1, 2.0], [-0.0, (v0 - cy) / fy * near, near]], F32)
+
+
+def edge_fields():
+    """Three 17 x 33 fields whose principal point's pixel, (u, v) = (15, 9), is of each class -> {name: Field}: "surface" all
+    SURFACE, "empty" EMPTY around the principal point with allowed pixels beyond, "none" EMPTY everywhere (no allowed pixel)."""
+    H, W, intr = 17, 33, (32.0, 16.0, 15.25, 8.5)
+    z = 1.5 + 0.01 * np.random.default_rng(2).standard_normal((H, W))
+    surface = np.full((H, W), SURFACE, np.uint8)
+    empty = surface.copy()
+    empty[7:12, 13:18] = EMPTY
+    return {"surface": field_of_classes(surface, intr, z), "empty": field_of_classes(empty, intr, z),
+            "none": field_of_classes(np.zeros((H, W), np.uint8), intr)}
+
+
 # ------------------------------------------------------------------------------------------------ the term, float64
 def terms64(x, n, f, v_mask=None, margin=0.0):
     """The term restated in float64: the same pixel rule (projection and rounding to a pixel in float64), the same cases -> (free

@@ -48,6 +48,33 @@ def test_classification():
     assert cls.tolist() == [[U, S, E, E]] and z[0, 1] == np.float32(2000) * np.float32(0.001)
 
 
+def test_reference_is_defined_where_a_vertex_taken_as_it_is_and_an_identity_map_part():
+    """R.edge_rows on a principal pixel of every class: Z = +inf keeps the case list (e = -inf: no term; an EMPTY pixel: an
+    infinite offset from the ray, or no term without an allowed pixel), X = -inf and X = NaN are outside, and the kind-1 row's zero
+    gradient words take the sign of gL.  No NaN anywhere in term, gradient or loss, and no warning."""
+    import warnings
+    want = {"surface": [R.NONE, R.OUTSIDE, R.OUTSIDE, R.FREE], "empty": [R.SILHOUETTE, R.OUTSIDE, R.OUTSIDE, R.SILHOUETTE],
+            "none": [R.NONE, R.OUTSIDE, R.OUTSIDE, R.NONE]}
+    for name, f in R.edge_fields().items():
+        kinds = want[name]
+        x = R.edge_rows(f)
+        assert np.isposinf(x[0, 2]) and np.isneginf(x[1, 0]) and np.isnan(x[2, 0]) and x[3, 0] == 0 and np.signbit(x[3, 0])
+        for gL in ((1.0, 1.0), (-2.0, -0.5)):
+            with warnings.catch_warnings():
+                warnings.simplefilter("error")
+                term, kind, g, counts = R.terms(x, len(x), f, None, 0.01)
+                gx = R.gradient(kind, g, counts, gL, len(x) + 1)
+                loss = R.losses(term, kind, counts)
+            assert kind.tolist() == kinds and counts.tolist() == [4, kinds.count(R.FREE), kinds.count(R.SILHOUETTE), 2], name
+            assert not np.isnan(term).any() and not np.isnan(gx).any() and not np.isnan(loss).any(), name
+            assert (term[kind == R.NONE] == 0).all() and (gx[:4][np.isin(kind, (R.NONE, R.OUTSIDE))] == 0).all() and (gx[-1] == 0).all()
+            if name == "surface":                                          # g = (0, 0, -2 e): the zeros carry the sign of gL[0] / n_act
+                assert term[3] > 0 and (gx[3, :2] == 0).all() and np.signbit(gx[3, :2]).tolist() == [gL[0] < 0] * 2
+                assert gx[3, 2] != 0 and np.signbit(gx[3, 2]) == (gL[0] > 0)
+            if name == "empty":                                            # Z = +inf: rx, ry and the term are infinite, nothing is 0 * inf
+                assert np.isposinf(term[0]) and np.isinf(gx[0]).all() and loss[1] == math.inf and loss[0] == 0.0
+
+
 def constructed_vertices(f, rng, n):
     """n camera-frame vertices that project at least 0.25 pixel from every pixel boundary, half of them onto SURFACE pixels (in
     front of and behind the surface, |e| > 1e-3) and half onto EMPTY ones."""

@@ -67,9 +67,10 @@ def specials(f, margin):
     ], np.float32)
 
 
-def bodies(n, rows, margin, seed):
+def bodies(n, rows, margin, seed, edge=False):
     """x float32 [3, rows, 3]: random projections over the image and a border around it, depths around the surface, with the
-    special rows spread over the bodies (rotated, so that n = 1 still meets three different ones)."""
+    special rows spread over the bodies (rotated, so that n = 1 still meets three different ones).  edge: R.edge_rows come first
+    in every body."""
     rng = np.random.default_rng(seed)
     x = np.zeros((3, rows, 3), np.float32)
     for b, f in enumerate(fields()):
@@ -78,6 +79,8 @@ def bodies(n, rows, margin, seed):
         Z = rng.uniform(1.0, 2.2, rows)
         x[b] = np.stack([(u - cx) / fx * Z, (v - cy) / fy * Z, Z], 1)
         sp = np.roll(specials_none(f) if b == 2 else specials(fields()[0], margin), -4 * b, axis=0)    # body 1: body 0's rows, as plain points
+        if edge:
+            sp = np.concatenate([R.edge_rows(f if b == 2 else fields()[0]), sp])
         k = min(len(sp), n)
         x[b, :k] = sp[:k]
     x[:, n:] = 7.0                                                         # rows >= n: never read
@@ -157,6 +160,44 @@ def test_bits_against_the_reference(n, rows, margin, masked):
         alone = run(x[b:b + 1], n, device_field(refs[b:b + 1]), None if mask is None else masks[b:b + 1].copy(), margin, gL[b:b + 1])
         for a, whole in zip(alone, got):
             assert np.array_equal(bits(a[0]), bits(whole[b]))
+
+
+@pytest.mark.parametrize("n, rows", [(1, 2), (257, 257), (600, 601)])
+def test_bits_where_an_identity_camera_would_differ(n, rows):
+    """One camera runs the rig's kernels without a cam, and that must mean the vertex as it is, not an identity record: on
+    R.edge_rows (Z = +inf over a SURFACE pixel in bodies 0 and 1 and over an EMPTY one in body 2, X = -inf, X = NaN, and a kind-1
+    term whose zero gradient words a negative gL makes -0) ops.free_space_fwd / _bwd and scan.free_space give the reference's bits."""
+    refs, margin = fields(), 0.01
+    x = bodies(n, rows, margin, seed=n, edge=True)
+    gL = np.asarray([[-1.0, 1.0], [0.5, -3.0], [-2.0, -0.25]], np.float32)
+    fld = device_field(refs)
+    got = run(x, n, fld, None, margin, gL)
+    ref = reference(x, n, refs, None, margin, gL)
+    compare(got, ref, n)
+    xd = torch.from_numpy(x).to(DEV)
+    g = ops.free_space_bwd(xd, n, fld.cls, fld.z, fld.nearest, fld.intrinsics, None, 0, margin, torch.from_numpy(got[3]).to(DEV),
+                           torch.from_numpy(gL).to(DEV))
+    assert np.array_equal(bits(g.cpu().numpy()), bits(got[4]))
+    assert np.isposinf(x[:, 0, 2]).all() and [int(r[1][0]) for r in ref] == [R.NONE] * 3           # not kind 4: 0 * inf never happened
+    if n >= 4:                                                             # the rows are all there, and are the cases they stand for
+        assert np.isneginf(x[:, 1, 0]).all() and np.isnan(x[:, 2, 0]).all() and np.signbit(x[:, 3, 0]).all()
+        assert [r[1][:4].tolist() for r in ref] == [[R.NONE, R.OUTSIDE, R.OUTSIDE, R.FREE]] * 2 + [[R.NONE, R.OUTSIDE, R.OUTSIDE, R.NONE]]
+        g0 = ref[0][3][3]
+        assert (g0[:2] == 0).all() and np.signbit(g0[:2]).all() and g0[2] > 0                     # -0, -0 under gL[0][0] < 0
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_an_infinite_silhouette_term_keeps_the_case_list(sign):
+    """Z = +inf over an EMPTY pixel that has an allowed neighbour (R.edge_fields' "empty"): kind 2 with an infinite offset from the
+    ray, so term, loss and gradient hold infinities - bitwise the reference's, no NaN; an identity record would say kind 4."""
+    f, margin = R.edge_fields()["empty"], 0.01
+    x = np.concatenate([R.edge_rows(f), np.full((1, 3), 7.0, np.float32)])[None]
+    n, gL = 4, np.asarray([[sign * 2.0, sign * 0.5]], np.float32)
+    got = run(x, n, device_field([f]), None, margin, gL)
+    ref = reference(x, n, [f], None, margin, gL)
+    compare(got, ref, n)
+    assert ref[0][1].tolist() == [R.SILHOUETTE, R.OUTSIDE, R.OUTSIDE, R.SILHOUETTE] and np.isposinf(ref[0][0][0])
+    assert np.isposinf(got[2][0, 1]) and got[2][0, 0] == 0 and np.isinf(got[4][0, 0]).all() and not np.isnan(got[4]).any()
 
 
 @functools.lru_cache(maxsize=None)
