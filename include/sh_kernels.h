@@ -1349,6 +1349,94 @@ SH_API int sh_free_space_views_bwd(const float* x, int64_t x_sb, int rows, int n
                                    float margin, const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Camera rays: lens distortion for the depth cameras of "Depth images", "Depth views", "Depth views: overlap" and "Free space from
+ * a rig" (no reference counterpart).  A depth image cannot be rectified beforehand - resampling interpolates across depth steps -
+ * so the lens lives inside the unprojection (pixel -> ray, a table made once per calibrated camera) and inside the projection
+ * (point -> pixel, evaluated in the kernels).  Deterministic: no atomics, every output element one plain store, the same bits
+ * for a camera alone and in any batch.
+ *
+ * The model is OpenCV's 8-coefficient rational one, d = (k1, k2, p1, p2, k3, k4, k5, k6) in that order, for the normalised point
+ * (a, b) = (X / Z, Y / Z).  ONE order of operations, every operation rounded on its own (no contraction), every division
+ * correctly rounded; T is fp32 in the forward model and fp64 in the inverse:
+ *     a2 = a * a;  b2 = b * b;  r2 = a2 + b2;  r4 = r2 * r2;  r6 = r4 * r2
+ *     num = ((1 + k1 * r2) + k2 * r4) + k3 * r6
+ *     den = ((1 + k4 * r2) + k5 * r4) + k6 * r6
+ *     ab = a * b
+ *     tx = (2 * p1) * ab + p2 * (r2 + 2 * a2)
+ *     ty = p1 * (r2 + 2 * b2) + (2 * p2) * ab
+ *     rad = num / den
+ *     ad = a * rad + tx;  bd = b * rad + ty
+ *     u = fx * ad + cx;   v = fy * bd + cy
+ *
+ * Forward, point -> pixel, fp32, for Z > 0:  a = fl(X / Z), b = fl(Y / Z);  !(r2 <= limit) (a NaN included): the point is
+ * OUTSIDE, whatever the polynomial would say - beyond the limit the model may fold back into the image; else (uf, vf) = (u, v)
+ * above, and the inside test and the rounding to a pixel of sh_free_space_fwd follow unchanged.
+ *
+ * Inverse, pixel -> ray: sh_camera_rays(intr fp32 [C][4], dist fp32 [C][8], C, H, W) -> rays fp32 [C][H][W][2], limit fp32 [C],
+ * complete int32 [C].  fp64 on the widened fp32 inputs.  For the sample (u, v) - a pixel centre is (u, v) integer:
+ *     xd = (u - cx) / fx;  yd = (v - cy) / fy;  (x, y) = (xd, yd)
+ *     20 times:  the terms above at (a, b) = (x, y);  s = den / num;  x = (xd - tx) * s;  y = (yd - ty) * s      (both from the old x, y)
+ *     once more the terms at (x, y), rad = num / den, and (u', v') by the last two lines above
+ *     the sample CONVERGED iff |u' - u| <= 1e-3 and |v' - v| <= 1e-3 and num > 0 and den > 0           (a NaN: not converged)
+ *     rays[c][v][u] = ((float)x, (float)y) for a converged pixel centre, else (NaN, NaN)
+ * Twenty steps is a definition, not a tuning result.  limit[c] = the largest r2 = fl(fl(xf * xf) + fl(yf * yf)), fp32 with
+ * (xf, yf) = ((float)x, (float)y) - the forward model's own r2 of a point on that ray at Z = 1 - over the converged samples: the
+ * H * W pixel centres and the image rectangle's boundary at half-pixel positions, (i - 0.5, -0.5) and (i - 0.5, H - 0.5) for
+ * i = 0 .. W, (-0.5, j - 0.5) and (W - 0.5, j - 0.5) for j = 0 .. H; 0 when no sample converged.  complete[c] = 1 iff every pixel
+ * centre has a ray.  A float maximum does not depend on its order.  Two launches: one thread per pixel centre writes the table;
+ * one workgroup per camera then folds the table and the boundary samples (which it inverts itself) into limit and complete.
+ * C == 0 or H * W == 0: SH_OK, nothing launched.  Null pointers, negative sizes: SH_ERR_INVALID_ARG; C > 65535 or H * W beyond 31
+ * bits: SH_ERR_UNSUPPORTED.
+ *
+ * The _rays entry points: their namesakes' argument lists plus the calibration, and their namesakes' contracts with these changes.
+ * rays_stride: the table images (coefficient rows, limits) per body - 1 (one camera) or V (a rig) - or 0: ONE table per camera,
+ * [1] or [V], shared by all bodies; a rig's calibration does not depend on the body.  Camera (b, v) is image b * rays_stride + v.
+ *   sh_depth_rays_count / _points, sh_depth_views_rays_count / _points (rays, rays_stride after stride): the point of a pixel is
+ *       P = (fl(ra * z), fl(rb * z), z)   with (ra, rb) = rays[..][v][u]
+ *     and the neighbours' points come from their own rays; intr is not read.  The tangent rule, the normal, "kept", the order,
+ *     the padding and the rig transform are unchanged.  No kernel tests a ray for NaN: the caller masks the pixels without a ray
+ *     (complete == 0).  All-zero coefficients agree with the pinhole entry points to rounding, not bit for bit: fl(ra * z) against
+ *     fl(fl(fl(u - cx) * z) / fx).  The tile's rays are staged in LDS with the halo, next to z, in the same bank-free layout.
+ *   sh_depth_views_rays_overlap (dist [..][8], limit [..], rays_stride after z_far): Q is projected by the forward model above.
+ *   sh_free_space_views_rays_fwd / _bwd (rays, dist, limit, rays_stride after intr): the projection is the forward model, and in
+ *     the c == 0 case (a, b) = rays[..][vq][uq], the ray of the nearest pixel that is not empty, replaces the pinhole ray; a NaN
+ *     there: kind SH_FS_NONE, no term.  rx, ry, term and g keep their expressions: the term samples the nearest pixel and has
+ *     no image gradient, so its backward pass needs no Jacobian of the lens.  cam may be NULL: one camera, V = 1, x in its frame
+ *     (sh_free_space_fwd's case).  A view's LDS record grows by the 8 coefficients and the limit.
+ * Limits: one model family - no fisheye or equidistant model -, one resolution per rig.
+ */
+SH_API int sh_camera_rays(const float* intr, const float* dist, int C, int H, int W, float* rays, float* limit, int32_t* complete,
+                          sh_stream_t stream);
+SH_API int sh_depth_rays_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W,
+                               float z_near, float z_far, float max_step, int drop_isolated, int stride, const float* rays, int rays_stride,
+                               int32_t* counts, void* workspace, size_t workspace_bytes, sh_stream_t stream);
+SH_API int sh_depth_rays_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W,
+                                float z_near, float z_far, float max_step, int drop_isolated, int stride, const float* rays, int rays_stride,
+                                const int32_t* counts, int max_count, int M, const void* workspace, size_t workspace_bytes, float* points,
+                                float* normals, int32_t* pixel, sh_stream_t stream);
+SH_API int sh_depth_views_rays_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext,
+                                     int B, int V, int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride,
+                                     const float* rays, int rays_stride, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                     sh_stream_t stream);
+SH_API int sh_depth_views_rays_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext,
+                                      int B, int V, int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride,
+                                      const float* rays, int rays_stride, const int32_t* counts, int max_count, int M, const void* workspace,
+                                      size_t workspace_bytes, float* points, float* normals, int32_t* pixel, uint8_t* view,
+                                      int32_t* view_first, sh_stream_t stream);
+SH_API int sh_depth_views_rays_overlap(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask,
+                                       const float* ext, int B, int V, int H, int W, float z_near, float z_far, const float* dist,
+                                       const float* limit, int rays_stride, const float* points, const float* normals, const uint8_t* view,
+                                       const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep, sh_stream_t stream);
+SH_API int sh_free_space_views_rays_fwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                        const int32_t* nearest, const float* intr, const float* rays, const float* dist, const float* limit,
+                                        int rays_stride, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B,
+                                        float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream);
+SH_API int sh_free_space_views_rays_bwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                        const int32_t* nearest, const float* intr, const float* rays, const float* dist, const float* limit,
+                                        int rays_stride, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
+                                        const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident dataset (autoencoder_dataset.py:26-58; main.py:209-237).  The reference loads and
  * normalises one .npy per sample in DataLoader worker processes; here the packed split is
  * normalised once on device and every batch is a row gather from the resident tensor.

@@ -108,6 +108,18 @@ SIGNATURES = {
     "sh_free_space_cameras": (c_int, [_P, _P, _I, _I, _P, _P]),
     "sh_free_space_views_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),
     "sh_free_space_views_bwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, c_float, _P, _P, _I, _P, _P]),
+    # camera rays: the namesake's arguments with the calibration inserted (include/sh_kernels.h, "Camera rays")
+    "sh_camera_rays": (c_int, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "sh_depth_rays_count": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _P, _P, c_size_t, _P]),
+    "sh_depth_rays_points": (c_int, [_P, _I, c_float, _P, _P, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _P, _I, _I, _P, c_size_t, _P, _P,
+                                     _P, _P]),
+    "sh_depth_views_rays_count": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _P, _P, c_size_t, _P]),
+    "sh_depth_views_rays_points": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, c_float, _I, _I, _P, _I, _P, _I, _I, _P,
+                                           c_size_t, _P, _P, _P, _P, _P, _P]),
+    "sh_depth_views_rays_overlap": (c_int, [_P, _I, c_float, _P, _P, _P, _I, _I, _I, _I, c_float, c_float, _P, _P, _I, _P, _P, _P, _P, _I, c_float, _P,
+                                            _P, _P]),
+    "sh_free_space_views_rays_fwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, c_float, _I, _P, _P, _P, _P, _P]),
+    "sh_free_space_views_rays_bwd": (c_int, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, c_float, _P, _P, _I, _P, _P]),
     "sh_align_ranges": (c_int, [_I, _I, c_float]),
     "sh_align_partials_bytes": (c_size_t, [_I, _I, _I, c_float]),
     "sh_align_moments": (c_int, [_P, _L, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P, _P, _P, c_float, c_float, _I, _P, c_size_t, _P]),

@@ -33,6 +33,9 @@ struct ViewArgs {
     uint8_t* view;                      // [B][M], the view a row came from, 255 in the padding
     int32_t* view_first;                // [B][V + 1]
 };
+// "Camera rays": the pixel -> ray table of a calibrated camera, fp32 [images][H][W][2]; image (b, view) is table image
+// b * stride + view, or with stride == 0 just view - one table per camera, shared by all bodies.
+struct RayArgs { const float* rays; int stride; };
 struct P3 { float x, y, z; };
 
 // bits 0, 2, 4, 6 of r -> a 4-bit number: the u of a Z-rank (its v: the same of r >> 1)
@@ -67,6 +70,24 @@ __device__ __forceinline__ P3 unproject(int u, int v, float z, float fx, float f
     return {(((float)u - cx) * z) / fx, (((float)v - cy) * z) / fy, z};
 }
 
+// The rays of the tile at (u0, v0) with its halo -> ra, rb [HALO][LROW], in the layout of zt: the same 32 lanes read the same
+// offsets of each plane, so LROW's bank reasoning holds for both.  One 8-byte read per pixel, consecutive threads consecutive
+// pixels of a row; NaN outside the image, where zt holds a NaN too and no tangent is taken.
+__device__ __forceinline__ void load_rays(const float* table, int H, int W, int u0, int v0, float* ra, float* rb) {
+    const float2* t = reinterpret_cast<const float2*>(table);
+    for (int i = threadIdx.x; i < HALO * HALO; i += NT) {
+        const int r = i / HALO, c = i - r * HALO;
+        const int u = u0 - 1 + c, v = v0 - 1 + r;
+        float2 q = {NAN, NAN};
+        if (u >= 0 && u < W && v >= 0 && v < H) q = t[(long)v * W + u];
+        ra[r * LROW + c] = q.x;
+        rb[r * LROW + c] = q.y;
+    }
+}
+
+// "Camera rays": the point of a pixel with ray (a, b) at depth z.
+__device__ __forceinline__ P3 unproject_ray(float a, float b, float z) { return {a * z, b * z, z}; }
+
 // The header's tangent rule over the lower and upper neighbour of c: hi - lo, else hi - c, else c - lo; false: none.
 __device__ __forceinline__ bool tangent(const P3& lo, bool has_lo, const P3& c, const P3& hi, bool has_hi, P3& t) {
     const P3 a = has_hi ? hi : c, b = has_lo ? lo : c;
@@ -78,11 +99,14 @@ __device__ __forceinline__ bool tangent(const P3& lo, bool has_lo, const P3& c, 
 // tile's first row (depth_scan_kernel), and the kept pixels and the body's padding are written.  VIEWS = false: an image is a
 // body.  VIEWS = true: image = body * V + view, a body's rows are its views' in turn - tile_row [B][V][tiles] is scanned per body -
 // and the emit pass moves point and normal into the rig's frame; an absent view enters as a tile of NaN: nothing kept, nothing
-// of it read.
-template <typename T, bool EMIT, bool VIEWS>
+// of it read.  RAYS: the five points come from the camera's ray table (ry), staged in LDS next to zt with the same halo, not
+// from the intrinsics, which are then not read; everything after the points is the same text.
+template <typename T, bool EMIT, bool VIEWS, bool RAYS>
 __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, ViewArgs va, int32_t* __restrict__ tile_row, const int32_t* __restrict__ counts,
-                                                  int M, float* __restrict__ points, float* __restrict__ normals, int32_t* __restrict__ pixel) {
+                                                  int M, float* __restrict__ points, float* __restrict__ normals, int32_t* __restrict__ pixel,
+                                                  RayArgs ry) {
     __shared__ float zt[HALO * LROW];
+    __shared__ float rt[RAYS ? 2 * HALO * LROW : 1];
     __shared__ int wsum[NT / 64];
     const int tile = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
     const int b = VIEWS ? img / va.V : img, view = VIEWS ? img - b * va.V : 0;
@@ -98,6 +122,11 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, ViewArgs va, int
     }
     if (present) load_tile<T>(a, img, tx * TILE, ty * TILE, zt);
     else for (int i = tid; i < HALO * LROW; i += NT) zt[i] = NAN;
+    if constexpr (RAYS) {
+        if ((EMIT || a.drop_isolated) && present)                        // uniform; the condition under which the points are formed
+            load_rays(ry.rays + 2L * a.H * a.W * (ry.stride ? (long)b * ry.stride + view : (long)view), a.H, a.W, tx * TILE, ty * TILE, rt,
+                      rt + HALO * LROW);
+    }
     __syncthreads();
     const int lu = even_bits(tid), lv = even_bits(tid >> 1);
     const int u = tx * TILE + lu, v = ty * TILE + lv;
@@ -108,15 +137,24 @@ __global__ __launch_bounds__(NT) void depth_kernel(DepthArgs a, ViewArgs va, int
     P3 p = {0.f, 0.f, 0.f};
     float nx = 0.f, ny = 0.f, nz = 0.f;
     if ((EMIT || a.drop_isolated) && present) {                          // uniform
-        const float* k = a.intr + 4L * img;
-        const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
         const float zl = zc[-1], zr = zc[1], zu = zc[-LROW], zd = zc[LROW];
-        p = unproject(u, v, z, fx, fy, cx, cy);
+        P3 pl, pr, pu, pd;
+        if constexpr (RAYS) {
+            const float* ac = rt + (lv + 1) * LROW + (lu + 1);
+            const float* bc = ac + HALO * LROW;
+            p = unproject_ray(ac[0], bc[0], z);
+            pl = unproject_ray(ac[-1], bc[-1], zl); pr = unproject_ray(ac[1], bc[1], zr);
+            pu = unproject_ray(ac[-LROW], bc[-LROW], zu); pd = unproject_ray(ac[LROW], bc[LROW], zd);
+        } else {
+            const float* k = a.intr + 4L * img;
+            const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
+            p = unproject(u, v, z, fx, fy, cx, cy);
+            pl = unproject(u - 1, v, zl, fx, fy, cx, cy); pr = unproject(u + 1, v, zr, fx, fy, cx, cy);
+            pu = unproject(u, v - 1, zu, fx, fy, cx, cy); pd = unproject(u, v + 1, zd, fx, fy, cx, cy);
+        }
         P3 dx, dy;                                                       // usable: the compare is false for a NaN on either side
-        const bool has_dx = tangent(unproject(u - 1, v, zl, fx, fy, cx, cy), fabsf(zl - z) <= a.max_step, p,
-                                    unproject(u + 1, v, zr, fx, fy, cx, cy), fabsf(zr - z) <= a.max_step, dx);
-        const bool has_dy = tangent(unproject(u, v - 1, zu, fx, fy, cx, cy), fabsf(zu - z) <= a.max_step, p,
-                                    unproject(u, v + 1, zd, fx, fy, cx, cy), fabsf(zd - z) <= a.max_step, dy);
+        const bool has_dx = tangent(pl, fabsf(zl - z) <= a.max_step, p, pr, fabsf(zr - z) <= a.max_step, dx);
+        const bool has_dy = tangent(pu, fabsf(zu - z) <= a.max_step, p, pd, fabsf(zd - z) <= a.max_step, dy);
         const double ax = dx.x, ay = dx.y, az = dx.z, bx = dy.x, by = dy.y, bz = dy.z;
         const double c0 = ay * bz - az * by, c1 = az * bx - ax * bz, c2 = ax * by - ay * bx;
         const double len2 = (c0 * c0 + c1 * c1) + c2 * c2;
@@ -223,6 +261,9 @@ struct OverlapArgs {
     const float* points; const float* normals; const uint8_t* view; const int32_t* counts;
     int M;
 };
+// "Camera rays": the distortion coefficients [images][8] and fold-back limits [images] of the cameras, images as in RayArgs.
+struct DistArgs { const float* dist; const float* limit; int stride; };
+constexpr int DIST_WORDS = 9;           // a view's record in LDS: the 8 coefficients, then the limit
 
 // The header's q of a row (point P, normal n) under the camera centre t: cos^2 / d^4 with the sign of the cosine.
 __device__ __forceinline__ float view_quality(const P3& P, const P3& n, const float* t) {
@@ -234,11 +275,13 @@ __device__ __forceinline__ float view_quality(const P3& P, const P3& n, const fl
 
 // grid (256-row chunk, body), thread = one row.  The body's V extrinsics and intrinsics are staged in LDS once per workgroup
 // (an absent view: its intrinsics are not read); every view is then a uniform loop step whose LDS reads are broadcasts.  One
-// scattered depth (and mask) read per row and other view that has the point in front of it and inside its image.
-template <typename T>
-__global__ __launch_bounds__(NT) void depth_views_overlap_kernel(OverlapArgs a, uint32_t* __restrict__ seen, uint8_t* __restrict__ keep) {
+// scattered depth (and mask) read per row and other view that has the point in front of it and inside its image.  RAYS: the
+// projection is the distorted one of "Camera rays"; a present view's coefficients and limit are staged next to sk.
+template <typename T, bool RAYS>
+__global__ __launch_bounds__(NT) void depth_views_overlap_kernel(OverlapArgs a, uint32_t* __restrict__ seen, uint8_t* __restrict__ keep, DistArgs da) {
     __shared__ float se[SH_DEPTH_MAX_VIEWS * 12];
     __shared__ float sk[SH_DEPTH_MAX_VIEWS * 4];
+    __shared__ float sd[RAYS ? SH_DEPTH_MAX_VIEWS * DIST_WORDS : 1];
     __shared__ int present[SH_DEPTH_MAX_VIEWS];
     const int b = blockIdx.y, tid = threadIdx.x;
     for (int i = tid; i < a.V * 12; i += NT) se[i] = a.ext[12L * b * a.V + i];
@@ -250,6 +293,12 @@ __global__ __launch_bounds__(NT) void depth_views_overlap_kernel(OverlapArgs a, 
         present[tid] = ok;
 #pragma unroll
         for (int k = 0; k < 4; ++k) sk[4 * tid + k] = ok ? a.intr[4L * ((long)b * a.V + tid) + k] : 0.f;
+        if constexpr (RAYS) {
+            const long cam = da.stride ? (long)b * da.stride + tid : (long)tid;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sd[DIST_WORDS * tid + k] = ok ? da.dist[8 * cam + k] : 0.f;
+            sd[DIST_WORDS * tid + 8] = ok ? da.limit[cam] : 0.f;
+        }
     }
     __syncthreads();
     const long j = (long)blockIdx.x * NT + tid;
@@ -273,8 +322,13 @@ __global__ __launch_bounds__(NT) void depth_views_overlap_kernel(OverlapArgs a, 
             const float Y = (e[1] * d0 + e[4] * d1) + e[7] * d2;
             const float Z = (e[2] * d0 + e[5] * d1) + e[8] * d2;
             if (!(Z > 0.f)) continue;                                    // a NaN included
-            const float fx = sk[4 * c], fy = sk[4 * c + 1], cx = sk[4 * c + 2], cy = sk[4 * c + 3];
-            const float uf = (X * fx) / Z + cx, vf = (Y * fy) / Z + cy;  // sh_free_space_fwd's projection, inside test and rounding
+            float uf, vf;                                                // sh_free_space_fwd's projection, inside test and rounding
+            if constexpr (RAYS) {
+                if (!camera_project(X, Y, Z, sk + 4 * c, sd + DIST_WORDS * c, sd[DIST_WORDS * c + 8], uf, vf)) continue;
+            } else {
+                const float fx = sk[4 * c], fy = sk[4 * c + 1], cx = sk[4 * c + 2], cy = sk[4 * c + 3];
+                uf = (X * fx) / Z + cx; vf = (Y * fy) / Z + cy;
+            }
             const bool inside = uf >= -0.5f && uf < (float)a.W - 0.5f && vf >= -0.5f && vf < (float)a.H - 0.5f;   // a NaN is outside
             if (!inside) continue;
             const int u = min((int)floorf(uf + 0.5f), a.W - 1), v = min((int)floorf(vf + 0.5f), a.H - 1);        // no read beyond the image whatever the rounding
@@ -381,16 +435,19 @@ int check_views(const char* who, const void* depth, int dtype, const float* intr
 }
 
 // One pass over the tiles of B bodies: of one image each (va.ext == nullptr, the record reads as before), or of va.V views each.
-template <bool EMIT, bool VIEWS>
+// With a ray table (RAYS) the record's name says so - "depth_rays_emit_kernel" - and carries the table's stride.
+template <bool EMIT, bool VIEWS, bool RAYS>
 void launch_tiles(hipStream_t st, int dtype, const DepthArgs& a, const ViewArgs& va, int B, int32_t* tile_row, const int32_t* counts, int M,
-                  float* points, float* normals, int32_t* pixel) {
-    char name[96];
-    if (VIEWS) snprintf(name, sizeof name, "%s|B=%d V=%d H=%d W=%d u16=%d", EMIT ? "depth_views_emit_kernel" : "depth_views_count_kernel", B, va.V, a.H, a.W, dtype == SH_DEPTH_U16);
+                  float* points, float* normals, int32_t* pixel, const RayArgs& ry) {
+    char name[112];
+    if (RAYS && VIEWS) snprintf(name, sizeof name, "%s|B=%d V=%d H=%d W=%d u16=%d tables=%d", EMIT ? "depth_views_rays_emit_kernel" : "depth_views_rays_count_kernel", B, va.V, a.H, a.W, dtype == SH_DEPTH_U16, ry.stride);
+    else if (RAYS) snprintf(name, sizeof name, "%s|B=%d H=%d W=%d u16=%d tables=%d", EMIT ? "depth_rays_emit_kernel" : "depth_rays_count_kernel", B, a.H, a.W, dtype == SH_DEPTH_U16, ry.stride);
+    else if (VIEWS) snprintf(name, sizeof name, "%s|B=%d V=%d H=%d W=%d u16=%d", EMIT ? "depth_views_emit_kernel" : "depth_views_count_kernel", B, va.V, a.H, a.W, dtype == SH_DEPTH_U16);
     else snprintf(name, sizeof name, "%s|B=%d H=%d W=%d u16=%d", EMIT ? "depth_emit_kernel" : "depth_count_kernel", B, a.H, a.W, dtype == SH_DEPTH_U16);
     ShProfScope ps(st, "%s", name);
     const dim3 grid((unsigned)a.tiles, (unsigned)(VIEWS ? B * va.V : B));
-    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_kernel<uint16_t, EMIT, VIEWS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel);
-    else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT, VIEWS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel);
+    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_kernel<uint16_t, EMIT, VIEWS, RAYS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel, ry);
+    else SH_LAUNCH_PS(ps, (depth_kernel<float, EMIT, VIEWS, RAYS>), grid, dim3(NT), 0, st, a, va, tile_row, counts, M, points, normals, pixel, ry);
 }
 
 // The tile rows of B bodies of `images` images each, in bytes: the workspace of both passes.
@@ -399,11 +456,18 @@ size_t tile_rows_bytes(int B, int images, int H, int W) { return (size_t)B * ima
 // Everything behind the four entry points: the checks, the workspace need, the tiles and - for the count pass - the per-body scan.
 // EMIT: the points pass, which reads counts and the workspace the count pass wrote.  VIEWS: a rig of V images per body with the
 // extrinsics ext and the outputs view and view_first; else one camera: ext, view and view_first are null and V counts as 1.
-template <bool EMIT, bool VIEWS>
+// RAYS: the "Camera rays" form with the table `rays` of rays_stride images per body (0: one table per camera for all bodies);
+// else both are null and 0.
+template <bool EMIT, bool VIEWS, bool RAYS = false>
 int depth_pass(const char* who, const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
                int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, int32_t* counts, int max_count, int M,
                void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel, uint8_t* view, int32_t* view_first,
-               sh_stream_t stream) {
+               sh_stream_t stream, const float* rays = nullptr, int rays_stride = 0) {
+    if (RAYS) {
+        SH_REQUIRE(rays, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+        SH_REQUIRE(rays_stride == 0 || rays_stride == (VIEWS ? V : 1), SH_ERR_INVALID_ARG, "%s: rays_stride = %d, must be 0 (one table per camera) or %d",
+                   who, rays_stride, VIEWS ? V : 1);
+    }
     if (const int rc = VIEWS ? check_views(who, depth, dtype, intr, ext, B, V, H, W, stride) : check_inputs(who, depth, dtype, intr, B, H, W, stride))
         return rc;
     SH_REQUIRE(counts && (!EMIT || (points && normals && pixel && (!VIEWS || (view && view_first)))), SH_ERR_INVALID_ARG, "%s: null pointer", who);
@@ -423,12 +487,37 @@ int depth_pass(const char* who, const void* depth, int dtype, float depth_scale,
     hipStream_t st = static_cast<hipStream_t>(stream);
     const DepthArgs a = {depth, intr, mask, H, W, sh_cdiv(W, TILE), tiles_of(H, W), depth_scale, z_near, z_far, max_step, drop_isolated, stride};
     int32_t* tile_row = static_cast<int32_t*>(workspace);
-    launch_tiles<EMIT, VIEWS>(st, dtype, a, ViewArgs{ext, V, view, view_first}, B, tile_row, EMIT ? counts : nullptr, M, points, normals, pixel);
+    launch_tiles<EMIT, VIEWS, RAYS>(st, dtype, a, ViewArgs{ext, V, view, view_first}, B, tile_row, EMIT ? counts : nullptr, M, points, normals, pixel,
+                                    RayArgs{rays, rays_stride});
     if (!EMIT) {
         ShProfScope ps(st, "depth_scan_kernel|B=%d tiles=%d", B, images * a.tiles);
         SH_LAUNCH_PS(ps, depth_scan_kernel, dim3((unsigned)B), dim3(NT), 0, st, tile_row, images * a.tiles, counts);
     }
     SH_CHECK_LAUNCH(who + 3);                                            // named without the "sh_", as ever
+    return SH_OK;
+}
+
+// Everything behind the two overlap entry points.  RAYS: the projection of "Camera rays" under da.
+template <bool RAYS>
+int views_overlap(const char* who, const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                  int H, int W, float z_near, float z_far, const DistArgs& da, const float* points, const float* normals, const uint8_t* view,
+                  const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep, sh_stream_t stream) {
+    if (RAYS) {
+        SH_REQUIRE(da.dist && da.limit, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+        SH_REQUIRE(da.stride == 0 || da.stride == V, SH_ERR_INVALID_ARG, "%s: rays_stride = %d, must be 0 (one record per camera) or %d", who, da.stride, V);
+    }
+    if (const int rc = check_views(who, depth, dtype, intr, ext, B, V, H, W, 1)) return rc;
+    SH_REQUIRE(points && normals && view && counts && seen && keep, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(M >= 0, SH_ERR_INVALID_ARG, "%s: negative size (M %d)", who, M);
+    SH_REQUIRE(tol >= 0.f, SH_ERR_INVALID_ARG, "%s: tol must be >= 0 (and not NaN)", who);
+    if (B == 0 || M == 0) return SH_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const OverlapArgs a = {depth, intr, mask, ext, V, H, W, depth_scale, z_near, z_far, tol, points, normals, view, counts, M};
+    ShProfScope ps(st, "%s_kernel|B=%d V=%d H=%d W=%d M=%d u16=%d", who + 3, B, V, H, W, M, dtype == SH_DEPTH_U16);
+    const dim3 grid((unsigned)compact_chunks(M), (unsigned)B);
+    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, (depth_views_overlap_kernel<uint16_t, RAYS>), grid, dim3(NT), 0, st, a, seen, keep, da);
+    else SH_LAUNCH_PS(ps, (depth_views_overlap_kernel<float, RAYS>), grid, dim3(NT), 0, st, a, seen, keep, da);
+    SH_CHECK_LAUNCH(who + 3);
     return SH_OK;
 }
 
@@ -476,21 +565,52 @@ int sh_depth_views_points(const void* depth, int dtype, float depth_scale, const
 int sh_depth_views_overlap(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
                            int H, int W, float z_near, float z_far, const float* points, const float* normals, const uint8_t* view,
                            const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep, sh_stream_t stream) {
-    const char* who = "sh_depth_views_overlap";
-    if (const int rc = check_views(who, depth, dtype, intr, ext, B, V, H, W, 1)) return rc;
-    SH_REQUIRE(points && normals && view && counts && seen && keep, SH_ERR_INVALID_ARG, "%s: null pointer", who);
-    SH_REQUIRE(M >= 0, SH_ERR_INVALID_ARG, "%s: negative size (M %d)", who, M);
-    SH_REQUIRE(tol >= 0.f, SH_ERR_INVALID_ARG, "%s: tol must be >= 0 (and not NaN)", who);
-    if (B == 0 || M == 0) return SH_OK;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const OverlapArgs a = {depth, intr, mask, ext, V, H, W, depth_scale, z_near, z_far, tol, points, normals, view, counts, M};
-    ShProfScope ps(st, "depth_views_overlap_kernel|B=%d V=%d H=%d W=%d M=%d u16=%d", B, V, H, W, M, dtype == SH_DEPTH_U16);
-    const dim3 grid((unsigned)compact_chunks(M), (unsigned)B);
-    if (dtype == SH_DEPTH_U16) SH_LAUNCH_PS(ps, depth_views_overlap_kernel<uint16_t>, grid, dim3(NT), 0, st, a, seen, keep);
-    else SH_LAUNCH_PS(ps, depth_views_overlap_kernel<float>, grid, dim3(NT), 0, st, a, seen, keep);
-    SH_CHECK_LAUNCH("depth_views_overlap");
-    return SH_OK;
+    return views_overlap<false>("sh_depth_views_overlap", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, DistArgs{nullptr, nullptr, 0},
+                                points, normals, view, counts, M, tol, seen, keep, stream);
 }
+
+int sh_depth_views_rays_overlap(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                                int H, int W, float z_near, float z_far, const float* dist, const float* limit, int rays_stride, const float* points,
+                                const float* normals, const uint8_t* view, const int32_t* counts, int M, float tol, uint32_t* seen, uint8_t* keep,
+                                sh_stream_t stream) {
+    return views_overlap<true>("sh_depth_views_rays_overlap", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far,
+                               DistArgs{dist, limit, rays_stride}, points, normals, view, counts, M, tol, seen, keep, stream);
+}
+
+int sh_depth_rays_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
+                        float z_far, float max_step, int drop_isolated, int stride, const float* rays, int rays_stride, int32_t* counts,
+                        void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    return depth_pass<false, false, true>("sh_depth_rays_count", depth, dtype, depth_scale, intr, mask, nullptr, B, 0, H, W, z_near, z_far, max_step,
+                                          drop_isolated, stride, counts, 0, 0, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          stream, rays, rays_stride);
+}
+
+int sh_depth_rays_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, int B, int H, int W, float z_near,
+                         float z_far, float max_step, int drop_isolated, int stride, const float* rays, int rays_stride, const int32_t* counts,
+                         int max_count, int M, const void* workspace, size_t workspace_bytes, float* points, float* normals, int32_t* pixel,
+                         sh_stream_t stream) {
+    return depth_pass<true, false, true>("sh_depth_rays_points", depth, dtype, depth_scale, intr, mask, nullptr, B, 0, H, W, z_near, z_far, max_step,
+                                         drop_isolated, stride, const_cast<int32_t*>(counts), max_count, M, const_cast<void*>(workspace), workspace_bytes,
+                                         points, normals, pixel, nullptr, nullptr, stream, rays, rays_stride);
+}
+
+int sh_depth_views_rays_count(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                              int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, const float* rays,
+                              int rays_stride, int32_t* counts, void* workspace, size_t workspace_bytes, sh_stream_t stream) {
+    return depth_pass<false, true, true>("sh_depth_views_rays_count", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, max_step,
+                                         drop_isolated, stride, counts, 0, 0, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         stream, rays, rays_stride);
+}
+
+int sh_depth_views_rays_points(const void* depth, int dtype, float depth_scale, const float* intr, const uint8_t* mask, const float* ext, int B, int V,
+                               int H, int W, float z_near, float z_far, float max_step, int drop_isolated, int stride, const float* rays,
+                               int rays_stride, const int32_t* counts, int max_count, int M, const void* workspace, size_t workspace_bytes,
+                               float* points, float* normals, int32_t* pixel, uint8_t* view, int32_t* view_first, sh_stream_t stream) {
+    return depth_pass<true, true, true>("sh_depth_views_rays_points", depth, dtype, depth_scale, intr, mask, ext, B, V, H, W, z_near, z_far, max_step,
+                                        drop_isolated, stride, const_cast<int32_t*>(counts), max_count, M, const_cast<void*>(workspace), workspace_bytes,
+                                        points, normals, pixel, view, view_first, stream, rays, rays_stride);
+}
+
 
 size_t sh_scan_compact_workspace(int B, int M) { return B <= 0 || M < 0 ? 0 : (size_t)B * compact_chunks(M) * sizeof(int32_t); }
 

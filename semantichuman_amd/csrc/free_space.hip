@@ -9,6 +9,7 @@
 // as they are - the rig's layouts at V = 1 are the one-camera layouts word for word, and so is the order of the sums.
 #include <climits>
 
+#include "sh_depth.h"
 #include "sh_nn.h"
 
 #pragma clang fp contract(off)          // the header's expressions, in the whole file
@@ -23,13 +24,24 @@ struct FsArgs {
     float margin;
 };
 struct FsTerm { int kind; float term, gx, gy, gz; };
+// "Camera rays": the ray tables [images][H][W][2], coefficients [images][8] and limits [images] of the field's cameras; camera
+// (b, v) is image b * stride + v, or with stride == 0 just v - one calibration per camera, shared by all bodies.
+struct FsRays { const float* rays; const float* dist; const float* limit; int stride; };
 
 // The header's case list for a camera-frame point (X, Y, Z) under the intrinsics k = (fx, fy, cx, cy) and image `image` of the field.
-__device__ __forceinline__ FsTerm fs_case(const FsArgs& a, long image, const float* k, float X, float Y, float Z) {
+// DIST, "Camera rays": k is followed by the camera's 8 coefficients and its limit, the projection is the distorted one, and the
+// silhouette ray is read from `table`, the camera's ray table; a NaN there: no term.
+template <bool DIST>
+__device__ __forceinline__ FsTerm fs_case(const FsArgs& a, long image, const float* k, float X, float Y, float Z, const float* table) {
     const float fx = k[0], fy = k[1], cx = k[2], cy = k[3];
     FsTerm r = {SH_FS_OUTSIDE, 0.f, 0.f, 0.f, 0.f};
     if (!(Z > 0.f)) return r;                                            // a NaN included
-    const float uf = (X * fx) / Z + cx, vf = (Y * fy) / Z + cy;
+    float uf, vf;
+    if constexpr (DIST) {
+        if (!camera_project(X, Y, Z, k, k + 4, k[12], uf, vf)) return r;
+    } else {
+        uf = (X * fx) / Z + cx; vf = (Y * fy) / Z + cy;
+    }
     const bool inside = uf >= -0.5f && uf < (float)a.W - 0.5f && vf >= -0.5f && vf < (float)a.H - 0.5f;   // a NaN is outside
     if (!inside) return r;
     const int u = min((int)floorf(uf + 0.5f), a.W - 1), v = min((int)floorf(vf + 0.5f), a.H - 1);        // the min never binds: no read beyond the image whatever the rounding
@@ -47,13 +59,20 @@ __device__ __forceinline__ FsTerm fs_case(const FsArgs& a, long image, const flo
         const int q = a.nearest[px];
         if (q >= 0) {
             const int vq = q / a.W, uq = q - vq * a.W;
-            const float ra = ((float)uq - cx) / fx, rb = ((float)vq - cy) / fy;
-            const float rx = X - ra * Z, ry = Y - rb * Z;
-            r.kind = SH_FS_SILHOUETTE;
-            r.term = rx * rx + ry * ry;
-            r.gx = 2.f * rx;
-            r.gy = 2.f * ry;
-            r.gz = -2.f * (ra * rx + rb * ry);
+            float ra, rb;
+            if constexpr (DIST) {
+                ra = table[2L * q]; rb = table[2L * q + 1];
+            } else {
+                ra = ((float)uq - cx) / fx; rb = ((float)vq - cy) / fy;
+            }
+            if (!DIST || (ra == ra && rb == rb)) {
+                const float rx = X - ra * Z, ry = Y - rb * Z;
+                r.kind = SH_FS_SILHOUETTE;
+                r.term = rx * rx + ry * ry;
+                r.gx = 2.f * rx;
+                r.gy = 2.f * ry;
+                r.gz = -2.f * (ra * rx + rb * ry);
+            }
         }
     } else {
         r.kind = SH_FS_UNKNOWN;
@@ -69,6 +88,8 @@ __device__ __forceinline__ int wave_sum_i(int v) {
 
 constexpr int VIEWS_NT = 1024;          // the forward workgroup: the terms are written by all of it, folded by its first 256 threads
 constexpr int VIEW_WORDS = 16;          // a view's record in LDS: the 12 words of cam (M row-major, c), then fx, fy, cx, cy
+constexpr int DIST_VIEW_WORDS = 25;     // "Camera rays": then the 8 coefficients and the limit
+constexpr int view_words(bool dist) { return dist ? DIST_VIEW_WORDS : VIEW_WORDS; }
 
 // grid (cdiv(B * V, 64)), thread = one (body, view): the header's fp64 expressions, in its order.
 __global__ __launch_bounds__(64) void free_space_cameras_kernel(const float* __restrict__ pose, const float* __restrict__ ext, int BV, int V,
@@ -116,12 +137,18 @@ __global__ __launch_bounds__(64) void free_space_cameras_kernel(const float* __r
 // The body's V records into LDS (ends with a barrier): every later read of them is a broadcast.  Without cam (CAM false) the
 // twelve words of the map are neither staged nor read.  CAM is a template parameter because a test of cam around the load keeps
 // hipcc from unrolling this loop as it does for a rig.
-template <int NT, bool CAM>
-__device__ __forceinline__ void stage_views(const FsArgs& a, const float* __restrict__ cam, int V, int b, float* sv) {
-    for (int i = threadIdx.x; i < V * VIEW_WORDS; i += NT) {
-        const int v = i / VIEW_WORDS, k = i - v * VIEW_WORDS;
+template <int NT, bool CAM, bool DIST>
+__device__ __forceinline__ void stage_views(const FsArgs& a, const float* __restrict__ cam, int V, int b, float* sv, const FsRays& fr) {
+    constexpr int WORDS = view_words(DIST);
+    for (int i = threadIdx.x; i < V * WORDS; i += NT) {
+        const int v = i / WORDS, k = i - v * WORDS;
         const long rec = (long)b * V + v;
-        if constexpr (CAM) sv[i] = k < 12 ? cam[12 * rec + k] : a.intr[4 * rec + (k - 12)];
+        if constexpr (DIST) {
+            const long c = fr.stride ? (long)b * fr.stride + v : (long)v;
+            if (k >= 16) sv[i] = k < 24 ? fr.dist[8 * c + (k - 16)] : fr.limit[c];
+            else if (k >= 12) sv[i] = a.intr[4 * rec + (k - 12)];
+            else if (CAM) sv[i] = cam[12 * rec + k];
+        } else if constexpr (CAM) sv[i] = k < 12 ? cam[12 * rec + k] : a.intr[4 * rec + (k - 12)];
         else if (k >= 12) sv[i] = a.intr[4 * rec + (k - 12)];
     }
     __syncthreads();
@@ -129,13 +156,20 @@ __device__ __forceinline__ void stage_views(const FsArgs& a, const float* __rest
 
 // The header's Q = M x + c of one view's record, then the case list under that view's intrinsics and image.  CAM false: x is in
 // the camera's frame already and is taken as it is - under an identity record 0 * inf would make a vertex at Z = +inf a NaN.
-template <bool CAM>
-__device__ __forceinline__ FsTerm fs_view(const FsArgs& a, const float* rec, long image, float x0, float x1, float x2) {
-    if constexpr (!CAM) return fs_case(a, image, rec + 12, x0, x1, x2);
+template <bool CAM, bool DIST>
+__device__ __forceinline__ FsTerm fs_view(const FsArgs& a, const float* rec, long image, float x0, float x1, float x2, const float* table) {
+    if constexpr (!CAM) return fs_case<DIST>(a, image, rec + 12, x0, x1, x2, table);
     const float X = ((rec[0] * x0 + rec[1] * x1) + rec[2] * x2) + rec[9];
     const float Y = ((rec[3] * x0 + rec[4] * x1) + rec[5] * x2) + rec[10];
     const float Z = ((rec[6] * x0 + rec[7] * x1) + rec[8] * x2) + rec[11];
-    return fs_case(a, image, rec + 12, X, Y, Z);
+    return fs_case<DIST>(a, image, rec + 12, X, Y, Z, table);
+}
+
+// The ray table of camera (b, v) under fr (nullptr without one).
+template <bool DIST>
+__device__ __forceinline__ const float* fs_table(const FsArgs& a, const FsRays& fr, int b, int v) {
+    if constexpr (!DIST) return nullptr;
+    return fr.rays + 2L * a.H * a.W * (fr.stride ? (long)b * fr.stride + v : (long)v);
 }
 
 // grid (body), VIEWS_NT threads.  (1) Every thread takes vertices tid, tid + VIEWS_NT, ... and, in a uniform loop over the views,
@@ -143,15 +177,16 @@ __device__ __forceinline__ FsTerm fs_view(const FsArgs& a, const float* rec, lon
 // t, t + 256, ..., the views ascending inside a vertex - into the two fp64 sums; the wave butterfly and the four wave sums as in
 // chamfer_fwd_kernel.  (3) The counts are integers: per view, all threads count the stored kinds.  CAM false: cam == nullptr, one
 // camera, V = 1.  The form is a template parameter in both kernels: the rig's instantiations are the code they were before.
-template <bool CAM>
+template <bool CAM, bool DIST>
 __global__ __launch_bounds__(VIEWS_NT) void free_space_fwd_kernel(FsArgs a, const float* __restrict__ cam, int V, float* term, uint8_t* kind,
-                                                                 float* __restrict__ loss, int32_t* __restrict__ counts) {
-    __shared__ float sv[SH_DEPTH_MAX_VIEWS * VIEW_WORDS];
+                                                                 float* __restrict__ loss, int32_t* __restrict__ counts, FsRays fr) {
+    constexpr int WORDS = view_words(DIST);
+    __shared__ float sv[SH_DEPTH_MAX_VIEWS * WORDS];
     __shared__ double red[2][4];
     __shared__ int redi[SH_DEPTH_MAX_VIEWS][3][VIEWS_NT / 64];
     __shared__ int reda[VIEWS_NT / 64];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-    stage_views<VIEWS_NT, CAM>(a, cam, V, b, sv);
+    stage_views<VIEWS_NT, CAM, DIST>(a, cam, V, b, sv, fr);
     const uint8_t* mb = a.v_mask ? a.v_mask + (long)b * a.mask_sb : nullptr;
     const long plane = (long)b * V * a.n;
     int na = 0;
@@ -162,7 +197,7 @@ __global__ __launch_bounds__(VIEWS_NT) void free_space_fwd_kernel(FsArgs a, cons
         const float x0 = p[0], x1 = p[1], x2 = p[2];
         for (int v = 0; v < V; ++v) {                                    // uniform
             FsTerm r = {SH_FS_NONE, 0.f, 0.f, 0.f, 0.f};
-            if (active) r = fs_view<CAM>(a, sv + VIEW_WORDS * v, (long)b * V + v, x0, x1, x2);
+            if (active) r = fs_view<CAM, DIST>(a, sv + WORDS * v, (long)b * V + v, x0, x1, x2, fs_table<DIST>(a, fr, b, v));
             term[plane + (long)v * a.n + i] = r.term;
             kind[plane + (long)v * a.n + i] = (uint8_t)r.kind;
         }
@@ -215,13 +250,14 @@ __global__ __launch_bounds__(VIEWS_NT) void free_space_fwd_kernel(FsArgs a, cons
 // grid (row tile of 256, body), thread = one row of g_x: per view the case list once more, its gradient times
 // fl(gL[b][k] * fl(1 / n_act)), carried back by M^T and added in fp32, the views ascending.  CAM false: cam == nullptr, one camera,
 // V = 1, and that product is the row itself - through an identity record -0 + 0 would lose the sign of a zero.
-template <bool CAM>
+template <bool CAM, bool DIST>
 __global__ __launch_bounds__(256) void free_space_bwd_kernel(FsArgs a, const float* __restrict__ cam, int V, int rows,
                                                             const int32_t* __restrict__ counts, const float* __restrict__ gL,
-                                                            float* __restrict__ g_x) {
-    __shared__ float sv[SH_DEPTH_MAX_VIEWS * VIEW_WORDS];
+                                                            float* __restrict__ g_x, FsRays fr) {
+    constexpr int WORDS = view_words(DIST);
+    __shared__ float sv[SH_DEPTH_MAX_VIEWS * WORDS];
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    stage_views<256, CAM>(a, cam, V, b, sv);
+    stage_views<256, CAM, DIST>(a, cam, V, b, sv, fr);
     if (i >= rows) return;
     float g0 = 0.f, g1 = 0.f, g2 = 0.f;
     if (i < a.n && (!a.v_mask || a.v_mask[(long)b * a.mask_sb + i] != 0)) {
@@ -230,8 +266,8 @@ __global__ __launch_bounds__(256) void free_space_bwd_kernel(FsArgs a, const flo
         const float inv = 1.f / (float)counts[4L * b * V];              // n_act >= 1: this vertex is active
         const float s_free = gL[2 * b] * inv, s_sil = gL[2 * b + 1] * inv;
         for (int v = 0; v < V; ++v) {                                    // uniform
-            const float* rec = sv + VIEW_WORDS * v;
-            const FsTerm r = fs_view<CAM>(a, rec, (long)b * V + v, x0, x1, x2);
+            const float* rec = sv + WORDS * v;
+            const FsTerm r = fs_view<CAM, DIST>(a, rec, (long)b * V + v, x0, x1, x2, fs_table<DIST>(a, fr, b, v));
             if (r.kind == SH_FS_FREE || r.kind == SH_FS_SILHOUETTE) {
                 const float s = r.kind == SH_FS_SILHOUETTE ? s_sil : s_free;
                 const float w0 = s * r.gx, w1 = s * r.gy, w2 = s * r.gz;
@@ -269,12 +305,21 @@ int check_args(const char* who, bool rig, const float* x, int64_t x_sb, int rows
     return SH_OK;
 }
 
+// "Camera rays": what the two _rays entry points ask of the calibration (fr null: the pinhole entry points, nothing to ask).
+int check_rays(const char* who, const FsRays* fr, int V) {
+    if (!fr) return SH_OK;
+    SH_REQUIRE(fr->rays && fr->dist && fr->limit, SH_ERR_INVALID_ARG, "%s: null pointer", who);
+    SH_REQUIRE(fr->stride == 0 || fr->stride == V, SH_ERR_INVALID_ARG, "%s: rays_stride = %d, must be 0 (one table per camera) or %d", who, fr->stride, V);
+    return SH_OK;
+}
+
 // Every check and the launch of a forward entry point, and below of a backward one.  The launch record is the entry point's name
 // without the "sh_", then "_kernel"; only a rig's names V.
 int free_space_fwd(const char* who, bool rig, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
                    const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B,
-                   float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream) {
+                   float* term, uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream, const FsRays* fr = nullptr) {
     if (const int rc = check_args(who, rig, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
+    if (const int rc = check_rays(who, fr, V)) return rc;
     SH_REQUIRE(term && kind && loss && counts, SH_ERR_INVALID_ARG, "%s: null pointer", who);
     if (B == 0) return SH_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -282,16 +327,20 @@ int free_space_fwd(const char* who, bool rig, const float* x, int64_t x_sb, int 
     char views[16] = "";
     if (rig) snprintf(views, sizeof views, " V=%d", V);
     ShProfScope ps(st, "%s_kernel|B=%d%s n=%d H=%d W=%d", who + 3, B, views, n, H, W);
-    if (cam) SH_LAUNCH_PS(ps, free_space_fwd_kernel<true>, dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts);
-    else SH_LAUNCH_PS(ps, free_space_fwd_kernel<false>, dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts);
+    const FsRays none = {nullptr, nullptr, nullptr, 0};
+    if (fr && cam) SH_LAUNCH_PS(ps, (free_space_fwd_kernel<true, true>), dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts, *fr);
+    else if (fr) SH_LAUNCH_PS(ps, (free_space_fwd_kernel<false, true>), dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts, *fr);
+    else if (cam) SH_LAUNCH_PS(ps, (free_space_fwd_kernel<true, false>), dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts, none);
+    else SH_LAUNCH_PS(ps, (free_space_fwd_kernel<false, false>), dim3((unsigned)B), dim3(VIEWS_NT), 0, st, a, cam, V, term, kind, loss, counts, none);
     SH_CHECK_LAUNCH(who + 3);
     return SH_OK;
 }
 
 int free_space_bwd(const char* who, bool rig, const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
                    const int32_t* nearest, const float* intr, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
-                   const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream) {
+                   const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream, const FsRays* fr = nullptr) {
     if (const int rc = check_args(who, rig, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B)) return rc;
+    if (const int rc = check_rays(who, fr, V)) return rc;
     SH_REQUIRE(counts && gL && g_x, SH_ERR_INVALID_ARG, "%s: null pointer", who);
     if (B == 0 || rows == 0) return SH_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -300,8 +349,11 @@ int free_space_bwd(const char* who, bool rig, const float* x, int64_t x_sb, int 
     if (rig) snprintf(views, sizeof views, " V=%d", V);
     ShProfScope ps(st, "%s_kernel|B=%d%s rows=%d n=%d", who + 3, B, views, rows, n);
     const dim3 grid((unsigned)sh_cdiv(rows, 256), (unsigned)B);
-    if (cam) SH_LAUNCH_PS(ps, free_space_bwd_kernel<true>, grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x);
-    else SH_LAUNCH_PS(ps, free_space_bwd_kernel<false>, grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x);
+    const FsRays none = {nullptr, nullptr, nullptr, 0};
+    if (fr && cam) SH_LAUNCH_PS(ps, (free_space_bwd_kernel<true, true>), grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x, *fr);
+    else if (fr) SH_LAUNCH_PS(ps, (free_space_bwd_kernel<false, true>), grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x, *fr);
+    else if (cam) SH_LAUNCH_PS(ps, (free_space_bwd_kernel<true, false>), grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x, none);
+    else SH_LAUNCH_PS(ps, (free_space_bwd_kernel<false, false>), grid, dim3(256), 0, st, a, cam, V, rows, counts, gL, g_x, none);
     SH_CHECK_LAUNCH(who + 3);
     return SH_OK;
 }
@@ -350,6 +402,29 @@ int sh_free_space_views_bwd(const float* x, int64_t x_sb, int rows, int n, const
                             const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream) {
     return free_space_bwd("sh_free_space_views_bwd", true, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, counts,
                           gL, B, g_x, stream);
+}
+
+// "Camera rays": the pair above under a lens model.  cam may be NULL: one camera, V = 1, x in its frame.
+int sh_free_space_views_rays_fwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                 const int32_t* nearest, const float* intr, const float* rays, const float* dist, const float* limit,
+                                 int rays_stride, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin, int B, float* term,
+                                 uint8_t* kind, float* loss, int32_t* counts, sh_stream_t stream) {
+    const char* who = "sh_free_space_views_rays_fwd";
+    SH_REQUIRE(cam || V == 1, SH_ERR_INVALID_ARG, "%s: without cam there is one camera, V = %d", who, V);
+    const FsRays fr = {rays, dist, limit, rays_stride};
+    return free_space_fwd(who, cam != nullptr, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, B, term, kind, loss, counts,
+                          stream, &fr);
+}
+
+int sh_free_space_views_rays_bwd(const float* x, int64_t x_sb, int rows, int n, const float* cam, const uint8_t* cls, const float* z,
+                                 const int32_t* nearest, const float* intr, const float* rays, const float* dist, const float* limit,
+                                 int rays_stride, int V, int H, int W, const uint8_t* v_mask, int64_t mask_sb, float margin,
+                                 const int32_t* counts, const float* gL, int B, float* g_x, sh_stream_t stream) {
+    const char* who = "sh_free_space_views_rays_bwd";
+    SH_REQUIRE(cam || V == 1, SH_ERR_INVALID_ARG, "%s: without cam there is one camera, V = %d", who, V);
+    const FsRays fr = {rays, dist, limit, rays_stride};
+    return free_space_bwd(who, cam != nullptr, x, x_sb, rows, n, cam, cls, z, nearest, intr, V, H, W, v_mask, mask_sb, margin, counts, gL, B, g_x, stream,
+                          &fr);
 }
 
 }  // extern "C"

@@ -25,6 +25,29 @@ __device__ __forceinline__ bool depth_valid(T raw, float z, float z_near, float 
     return z > 0.f && z < INFINITY && z_near <= z && z <= z_far && depth_raw_ok(raw) && (!m || m[p] != 0);
 }
 
+// "Camera rays", the forward model: a camera-frame point with Z > 0 -> (uf, vf) under k = (fx, fy, cx, cy), the coefficients
+// d = (k1, k2, p1, p2, k3, k4, k5, k6) and the fold-back limit, every operation in fp32 and rounded on its own, in the header's
+// order.  false: the point lies beyond the limit (a NaN included) and is outside whatever the polynomial would say.  The one
+// text of it for free_space.hip and depth.hip.
+__device__ __forceinline__ bool camera_project(float X, float Y, float Z, const float* k, const float* d, float limit, float& uf, float& vf) {
+#pragma clang fp contract(off)
+    const float a = X / Z, b = Y / Z;
+    const float a2 = a * a, b2 = b * b;
+    const float r2 = a2 + b2;
+    if (!(r2 <= limit)) return false;
+    const float r4 = r2 * r2;
+    const float r6 = r4 * r2;
+    const float num = ((1.f + d[0] * r2) + d[1] * r4) + d[4] * r6;
+    const float den = ((1.f + d[5] * r2) + d[6] * r4) + d[7] * r6;
+    const float rad = num / den;
+    const float ab = a * b;
+    const float tx = (2.f * d[2]) * ab + d[3] * (r2 + 2.f * a2);
+    const float ty = d[2] * (r2 + 2.f * b2) + (2.f * d[3]) * ab;
+    uf = k[0] * (a * rad + tx) + k[2];
+    vf = k[1] * (b * rad + ty) + k[3];
+    return true;
+}
+
 // What every depth entry point asks of the inputs they share; `who` names the caller in the message.
 static inline int depth_check_inputs(const char* who, const void* depth, int dtype, const float* intr, int B, int H, int W) {
     SH_REQUIRE(dtype == SH_DEPTH_F32 || dtype == SH_DEPTH_U16, SH_ERR_INVALID_ARG, "%s: unknown depth dtype %d", who, dtype);

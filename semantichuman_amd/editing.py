@@ -282,7 +282,7 @@ def fit_scan(model, z, z_kps, scans, parts=None, *, steps=200, lr=1e-2, trunc=No
     saw through, or projecting outside the body's silhouette, are pushed back - the data term a one-view fit lacks for the half
     of the body that visibility= only removes (two launches per step).  free_space_pose: the scan.Pose (camera frame
     -> model frame) that brought the scans into the model's frame, None when the model's frame is the camera's.  A given
-    vertex_mask holds for the term too; the mask of visibility= does not - the unseen vertices are the ones it is for.  Nearest-pixel sampling, no image gradient, no robust form, pinhole only.  The loss per step
+    vertex_mask holds for the term too; the mask of visibility= does not - the unseen vertices are the ones it is for.  Nearest-pixel sampling, no image gradient, no robust form; a field made with distortion= is read through its lens model (scan.free_space).  The loss per step
     includes the term; the returned Chamfer value does not.  ValueError for a field of another batch size, a negative weight or
     margin.  A rig field (scan.DepthField.from_depth(..., extrinsics=)) charges every vertex under each of the rig's cameras:
     free_space_pose is then rig frame -> model frame, the way into the cameras is computed once before the loop

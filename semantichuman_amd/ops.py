@@ -611,27 +611,73 @@ def _depth_args(who, rig, depth, intr, ext, mask, depth_scale, z_near, z_far, ma
                         + (H, W, float(z_near), float(z_far), float(max_step), int(bool(drop_isolated)), stride))
 
 
+def _rays_arg(who, rays, B, V, H, W, device):
+    """rays: None, or the calibration of "Camera rays" as (table fp32 [..., H, W, 2], dist fp32 [..., 8], limit fp32 [...]) with the
+    leading shape [1] or [B] for one camera per body (V = 0), [V] or [B, V] for a rig: without the batch axis ONE table per
+    camera serves every body -> (table, dist, limit, rays_stride), checked; rays_stride 0: shared."""
+    if rays is None:
+        return None
+    table, dist, limit = rays
+    per = max(V, 1)
+    shared, own = ((V,) if V else (1,)), ((B, V) if V else (B,))
+    lead = tuple(limit.shape) if torch.is_tensor(limit) else None
+    if lead not in (shared, own) or not (_dense(table, device, torch.float32, lead + (H, W, 2)) and _dense(dist, device, torch.float32, lead + (8,))
+                                         and _dense(limit, device, torch.float32, lead)):
+        raise ValueError("%s: rays must be contiguous fp32 tensors (table %s, dist %s, limit %s) on the images' device, or the same with a leading "
+                         "batch axis of %d" % (who, list(shared + (H, W, 2)), list(shared + (8,)), list(shared), B))
+    return table, dist, limit, (0 if lead == shared and lead != own else per)
+
+
+def camera_rays(intr, dist, H, W):
+    """sh_camera_rays: intr fp32 [C, 4], dist fp32 [C, 8] on the GPU -> (rays fp32 [C, H, W, 2]: the pixel -> ray table, (NaN, NaN)
+    where the inverse did not converge; limit fp32 [C]: the fold-back guard of the forward model; complete int32 [C]).  Two
+    launches, nothing synchronised."""
+    who = "camera_rays"
+    if not (torch.is_tensor(intr) and intr.is_cuda and intr.dtype == torch.float32 and intr.dim() == 2 and intr.shape[1] == 4 and intr.is_contiguous()):
+        raise ValueError("%s: intr must be a contiguous fp32 HIP tensor [C, 4]" % who)
+    C, H, W = intr.shape[0], int(H), int(W)
+    if not _dense(dist, intr.device, torch.float32, (C, 8)):
+        raise ValueError("%s: dist must be a contiguous fp32 tensor [%d, 8] on the device of intr" % (who, C))
+    if H < 0 or W < 0:
+        raise ValueError("%s: negative image size (%d, %d)" % (who, H, W))
+    rays = torch.empty((C, H, W, 2), dtype=torch.float32, device=intr.device)
+    limit = torch.zeros((C,), dtype=torch.float32, device=intr.device)
+    complete = torch.ones((C,), dtype=torch.int32, device=intr.device)
+    check(_lib.load().sh_camera_rays(ptr(intr), ptr(dist), C, H, W, ptr(rays), ptr(limit), ptr(complete), stream_ptr()), "sh_" + who)
+    return rays, limit, complete
+
+
 def _depth_workspace(lib, B, V, H, W):
     """Bytes of the tile rows the count pass leaves for the points pass; V = 0: one camera."""
     return lib.sh_depth_views_workspace(B, V, H, W) if V else lib.sh_depth_workspace(B, H, W)
 
 
-def _depth_count(who, rig, depth, *args):
-    """`depth_count` and `depth_views_count` (rig): args as `_depth_args` takes them after depth."""
+def _depth_entry(lib, rig, rays, what):
+    """The entry point of the pass `what` ("count" / "points"): the rig's or one camera's, the "Camera rays" form with a table."""
+    return getattr(lib, "sh_depth%s%s_%s" % ("_views" if rig else "", "_rays" if rays else "", what))
+
+
+def _depth_count(who, rig, depth, *args, rays=None):
+    """`depth_count` and `depth_views_count` (rig): args as `_depth_args` takes them after depth; rays as `_rays_arg` takes it."""
     B, V, H, W, cargs = _depth_args(who, rig, depth, *args)
+    rays = _rays_arg(who, rays, B, V, H, W, depth.device)
+    if rays:
+        cargs += (ptr(rays[0]), rays[3])
     lib = _lib.load()
     counts = torch.empty((B,), dtype=torch.int32, device=depth.device)
     nbytes = _depth_workspace(lib, B, V, H, W)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
-    entry = lib.sh_depth_views_count if rig else lib.sh_depth_count
-    check(entry(*cargs, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_" + who)
+    check(_depth_entry(lib, rig, rays, "count")(*cargs, ptr(counts), ptr(ws), nbytes, stream_ptr()), "sh_" + who)
     return counts, ws
 
 
-def _depth_points(who, rig, counts, workspace, M, max_count, depth, *args):
+def _depth_points(who, rig, counts, workspace, M, max_count, depth, *args, rays=None):
     """`depth_points` and `depth_views_points` (rig): args as `_depth_args` takes them after depth; a rig's view and view_first are
-    appended to the outputs."""
+    appended to the outputs; rays as `_rays_arg` takes it."""
     B, V, H, W, cargs = _depth_args(who, rig, depth, *args)
+    rays = _rays_arg(who, rays, B, V, H, W, depth.device)
+    if rays:
+        cargs += (ptr(rays[0]), rays[3])
     M, max_count = int(M), int(max_count)
     counted = "depth_views_count" if rig else "depth_count"
     if not (torch.is_tensor(counts) and counts.device == depth.device and counts.dtype == torch.int32 and counts.is_contiguous()
@@ -647,43 +693,43 @@ def _depth_points(who, rig, counts, workspace, M, max_count, depth, *args):
     outs = (points, torch.empty_like(points), torch.empty((B, max(M, 0)), dtype=torch.int32, device=depth.device))
     if rig:
         outs += (torch.empty((B, max(M, 0)), dtype=torch.uint8, device=depth.device), torch.empty((B, V + 1), dtype=torch.int32, device=depth.device))
-    entry = lib.sh_depth_views_points if rig else lib.sh_depth_points
-    check(entry(*cargs, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), *[ptr(t) for t in outs], stream_ptr()), "sh_" + who)
+    check(_depth_entry(lib, rig, rays, "points")(*cargs, ptr(counts), max_count, M, ptr(workspace), workspace.numel(), *[ptr(t) for t in outs],
+                                                 stream_ptr()), "sh_" + who)
     return outs
 
 
-def depth_count(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False, stride=1):
+def depth_count(depth, intr, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False, stride=1, rays=None):
     """sh_depth_count: depth [B, H, W] fp32 or 16-bit words on the device, intr fp32 [B, 4] = (fx, fy, cx, cy), mask uint8
     [B, H, W] or None -> (counts int32 [B], the kept pixels per body; the workspace sh_depth_points reads, the first row of every
-    16 x 16 tile).  Nothing is synchronised."""
-    return _depth_count("depth_count", False, depth, intr, None, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    16 x 16 tile).  Nothing is synchronised.  rays: None, or the calibration of "Camera rays" (`_rays_arg`): sh_depth_rays_count."""
+    return _depth_count("depth_count", False, depth, intr, None, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride, rays=rays)
 
 
 def depth_points(depth, intr, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf,
-                 drop_isolated=False, stride=1):
+                 drop_isolated=False, stride=1, rays=None):
     """sh_depth_points: the inputs and options of the `depth_count` call that made (counts, workspace), a width M and the largest
     count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the camera's frame, normals fp32 [B, M, 3] - a
     zero row: unknown -, pixel int32 [B, M] = v * W + u), rows in tile / Z-order; beyond a body's count zeros, zeros and -1."""
     return _depth_points("depth_points", False, counts, workspace, M, max_count, depth, intr, None, mask, depth_scale, z_near, z_far, max_step,
-                         drop_isolated, stride)
+                         drop_isolated, stride, rays=rays)
 
 
 def depth_views_count(depth, intr, ext, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, max_step=math.inf, drop_isolated=False,
-                      stride=1):
+                      stride=1, rays=None):
     """sh_depth_views_count: depth [B, V, H, W] fp32 or 16-bit words on the device, intr fp32 [B, V, 4], ext fp32 [B, V, 12] (camera ->
     rig, R row-major then t; a NaN row: the view is absent), mask uint8 [B, V, H, W] or None -> (counts int32 [B], the kept pixels
     per body over its views; the workspace sh_depth_views_points reads).  Nothing is synchronised."""
-    return _depth_count("depth_views_count", True, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride)
+    return _depth_count("depth_views_count", True, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step, drop_isolated, stride, rays=rays)
 
 
 def depth_views_points(depth, intr, ext, counts, workspace, M, max_count, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf,
-                       max_step=math.inf, drop_isolated=False, stride=1):
+                       max_step=math.inf, drop_isolated=False, stride=1, rays=None):
     """sh_depth_views_points: the inputs and options of the `depth_views_count` call that made (counts, workspace), a width M and the
     largest count as the caller read it (M >= max_count) -> (points fp32 [B, M, 3] in the rig's frame, normals fp32 [B, M, 3],
     pixel int32 [B, M] = v * W + u in the row's view, view uint8 [B, M], view_first int32 [B, V + 1]); rows view-major, tile /
     Z-order inside a view; beyond a body's count zeros, zeros, -1 and 255."""
     return _depth_points("depth_views_points", True, counts, workspace, M, max_count, depth, intr, ext, mask, depth_scale, z_near, z_far, max_step,
-                         drop_isolated, stride)
+                         drop_isolated, stride, rays=rays)
 
 
 def _rig_rows(who, B, M, device, **planes):
@@ -699,14 +745,16 @@ def _rig_rows(who, B, M, device, **planes):
 _SEEN = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
 
 
-def depth_views_overlap(depth, intr, ext, points, normals, view, counts, tol, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf):
+def depth_views_overlap(depth, intr, ext, points, normals, view, counts, tol, mask=None, depth_scale=1.0, z_near=-math.inf, z_far=math.inf, rays=None):
     """sh_depth_views_overlap: the images, calibration and range of the `depth_views_count` / `depth_views_points` calls that made the
     packed rows (points, normals fp32 [B, M, 3], view uint8 [B, M], counts int32 [B]) and a depth tolerance tol >= 0 -> (seen int32
     [B, M] read as unsigned: bit c set where camera c measures the row's surface point within tol, the row's own bit always; keep
     uint8 [B, M]: 0 where an observing camera is better placed - larger cos / d^2 under the row's normal, the lower index on a
-    tie); zeros in the padding.  One launch, nothing synchronised."""
+    tie); zeros in the padding.  One launch, nothing synchronised.  rays: None, or the calibration of "Camera rays"
+    (`_rays_arg`): sh_depth_views_rays_overlap, the projection under the lens model."""
     who = "depth_views_overlap"
     B, V, H, W, cargs = _depth_args(who, True, depth, intr, ext, mask, depth_scale, z_near, z_far, math.inf, False, 1)
+    rays = _rays_arg(who, rays, B, V, H, W, depth.device)
     tol = float(tol)
     if not tol >= 0:
         raise ValueError("%s: tol must be >= 0, got %r" % (who, tol))
@@ -717,8 +765,11 @@ def depth_views_overlap(depth, intr, ext, points, normals, view, counts, tol, ma
         raise ValueError("%s: counts must be the int32 tensor [%d] of the packed rows" % (who, B))
     seen = torch.empty((B, M), dtype=torch.int32, device=depth.device)
     keep = torch.empty((B, M), dtype=torch.uint8, device=depth.device)
-    check(_lib.load().sh_depth_views_overlap(*cargs[:12], ptr(points), ptr(normals), ptr(view), ptr(counts), M, tol, ptr(seen), ptr(keep),
-                                             stream_ptr()), "sh_" + who)
+    lib, cal = _lib.load(), ()
+    if rays:
+        cal = (ptr(rays[1]), ptr(rays[2]), rays[3])
+    check((lib.sh_depth_views_rays_overlap if rays else lib.sh_depth_views_overlap)(*cargs[:12], *cal, ptr(points), ptr(normals), ptr(view), ptr(counts),
+                                                                                    M, tol, ptr(seen), ptr(keep), stream_ptr()), "sh_" + who)
     return seen, keep
 
 
@@ -775,7 +826,7 @@ def _dense(t, device, dtype, shape):
     return torch.is_tensor(t) and t.device == device and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
 
 
-def _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
+def _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, rays=None):
     """The arguments the free-space entry points share, checked -> (B, lead, rows, their C arguments up to `margin`).  rig True: a
     rig's field [B, V, H, W] with intr [B, V, 4] and cam [B, V, 12], lead = (B, V); rig False: one camera's [B, H, W] and [B, 4],
     lead = (B,) - then cam is neither read nor among the arguments.  who: the public name, for the messages only."""
@@ -797,33 +848,43 @@ def _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb
         if not _dense(t, x.device, dtype, shape):
             raise ValueError("%s: %s must be a contiguous tensor %s on the device of x" % (who, what, list(shape)))
     head, field, tail = (ptr(x), x_sb, rows, n), (ptr(cls), ptr(z), ptr(nearest), ptr(intr)), (H, W, ptr(v_mask), mask_sb, float(margin))
+    if rays is not None:                                                # "Camera rays": one entry-point pair, cam NULL for one camera
+        rays = _rays_arg(who, rays, B, lead[1] if rig else 0, H, W, x.device)
+        return B, lead, rows, head + (ptr(cam if rig else None),) + field + (ptr(rays[0]), ptr(rays[1]), ptr(rays[2]), rays[3], lead[1] if rig else 1) + tail
     if rig:
         return B, lead, rows, head + (ptr(cam),) + field + (lead[1],) + tail
     return B, lead, rows, head + field + tail
 
 
-def _free_space_fwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin):
-    """`free_space_fwd` and `free_space_views_fwd` (rig) behind one set of checks; the outputs carry the field's leading shape."""
-    who = "free_space_views_fwd" if rig else "free_space_fwd"
-    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+def _free_space_entry(rig, rays, what):
+    """-> (the public name for the messages, the entry point's): with a calibration the _views_rays_ pair serves both."""
+    who = "free_space_views_" + what if rig else "free_space_" + what
+    return who, "sh_free_space_views_rays_" + what if rays is not None else "sh_" + who
+
+
+def _free_space_fwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, rays=None):
+    """`free_space_fwd` and `free_space_views_fwd` (rig) behind one set of checks; the outputs carry the field's leading shape.
+    rays: None, or the calibration of "Camera rays" (`_rays_arg`): sh_free_space_views_rays_fwd."""
+    who, entry = _free_space_entry(rig, rays, "fwd")
+    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, rays)
     term = torch.empty(lead + (int(n),), dtype=torch.float32, device=x.device)
     kind = torch.empty(lead + (int(n),), dtype=torch.uint8, device=x.device)
     loss = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     counts = torch.empty(lead + (4,), dtype=torch.int32, device=x.device)
-    check(getattr(_lib.load(), "sh_" + who)(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), "sh_" + who)
+    check(getattr(_lib.load(), entry)(*args, B, ptr(term), ptr(kind), ptr(loss), ptr(counts), stream_ptr()), entry)
     return term, kind, loss, counts
 
 
-def _free_space_bwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL):
-    """`free_space_bwd` and `free_space_views_bwd` (rig) behind one set of checks."""
-    who = "free_space_views_bwd" if rig else "free_space_bwd"
-    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin)
+def _free_space_bwd(rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, counts, gL, rays=None):
+    """`free_space_bwd` and `free_space_views_bwd` (rig) behind one set of checks; rays as in `_free_space_fwd`."""
+    who, entry = _free_space_entry(rig, rays, "bwd")
+    B, lead, rows, args = _free_space_args(who, rig, x, n, cam, cls, z, nearest, intr, v_mask, mask_sb, margin, rays)
     if not _dense(gL, x.device, torch.float32, (B, 2)):
         raise ValueError("%s: gL must be a contiguous fp32 tensor [%d, 2] on the device of x" % (who, B))
     if rig and not _dense(counts, x.device, torch.int32, lead + (4,)):     # one camera's counts were never checked here
         raise ValueError("%s: counts must be the forward call's int32 tensor %s" % (who, list(lead + (4,))))
     g = torch.empty((B, rows, 3), dtype=torch.float32, device=x.device)
-    check(getattr(_lib.load(), "sh_" + who)(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), "sh_" + who)
+    check(getattr(_lib.load(), entry)(*args, ptr(counts), ptr(gL), B, ptr(g), stream_ptr()), entry)
     return g
 
 

@@ -274,7 +274,9 @@ class ScanBatch:
         merge_tol: None, or - a rig only - a depth tolerance >= 0: the rows that a better-placed camera also measures within it are
         dropped before the batch is made, `merge_views(scans, *views_overlap(scans, ..., tol=merge_tol))` on the batch described
         above with the images still resident, and `seen` is kept.  That costs TWO host synchronisations instead of one: the kept
-        counts are read as well.  ValueError for a merge_tol without extrinsics, negative or NaN."""
+        counts are read as well.  ValueError for a merge_tol without extrinsics, negative or NaN.
+        distortion= (among the options): the lens, as in `unproject_depth` / `unproject_depth_views`; it works together with
+        merge_tol.  A ready `CameraRays` launches nothing more than the default path does."""
         if extrinsics is not None:
             rows = _unproject_depth_views(depth, intrinsics, extrinsics, device=device, merge_tol=merge_tol, **options)
             points, normals, pixel, view, view_first, counts, host_counts, ext = rows[:8]
@@ -344,6 +346,143 @@ def _intrinsics_arg(what, intrinsics, shapes):
     return k
 
 
+# ------------------------------------------------------------------------------------------------ lens distortion
+def _distortion_arg(what, distortion, leads):
+    """OpenCV coefficients (k1, k2, p1, p2[, k3[, k4, k5, k6]]) - 4, 5 or 8 per camera, with a leading shape among `leads` - as a
+    float32 array lead + (8,), shorter sets zero-padded in OpenCV's order; else ValueError."""
+    try:
+        c = np.asarray(distortion.detach().cpu().numpy() if torch.is_tensor(distortion) else distortion, dtype=np.float64)
+    except (ValueError, TypeError):
+        c = None
+    if c is None or c.ndim < 1 or c.shape[-1] not in (4, 5, 8):
+        raise ValueError("%s: distortion must hold 4, 5 or 8 coefficients per camera (k1, k2, p1, p2, k3, k4, k5, k6), got %s"
+                         % (what, "shape %s" % (c.shape,) if c is not None else type(distortion).__name__))
+    if c.shape[:-1] not in leads:
+        raise ValueError("%s: distortion of shape %s does not match the cameras: its leading shape must be one of %s"
+                         % (what, c.shape, ", ".join(str(list(l)) for l in leads)))
+    if not np.isfinite(c).all():
+        raise ValueError("%s: distortion coefficients must be finite" % what)
+    out = np.zeros(c.shape[:-1] + (8,), np.float32)
+    out[..., :c.shape[-1]] = c
+    return out
+
+
+class CameraRays:
+    """A calibrated camera's lens, resident on the device (sh_camera_rays; include/sh_kernels.h, "Camera rays"): `rays` fp32
+    lead + [H, W, 2], every pixel's ray (x, y) - the pixel sees along (x, y, 1) -, (NaN, NaN) where the model cannot be inverted;
+    `limit` fp32 lead, the largest x^2 + y^2 the forward model is trusted to (beyond it a point is outside the image: the model
+    may fold back); `coeffs` fp32 lead + [8] in OpenCV's order, `intrinsics` fp32 lead + [4]; `complete` (a host bool): every
+    pixel of every camera has a ray; `shape` = (H, W).  lead is (), [V] or [B, V] ([B] for one camera per body).  Made by
+    `camera_rays`; what distortion= takes for a fixed camera over many calls."""
+
+    def __init__(self, rays, limit, coeffs, intrinsics, complete, host):
+        self.rays, self.limit, self.coeffs, self.intrinsics, self.complete = rays, limit, coeffs, intrinsics, bool(complete)
+        self.shape = tuple(rays.shape[-3:-1])
+        self._host = host                                                   # (intrinsics, coefficients) float32 numpy, as uploaded
+
+    @property
+    def lead(self):
+        return tuple(self.limit.shape)
+
+    def select(self, sl):
+        """The bodies `sl` (a slice) of tables with a batch axis, sharing memory."""
+        return CameraRays(self.rays[sl], self.limit[sl], self.coeffs[sl], self.intrinsics[sl], self.complete, tuple(h[sl] for h in self._host))
+
+    def _planes(self, lead):
+        """(table, coefficients, limit) as contiguous tensors of leading shape `lead` (the same number of cameras)."""
+        H, W = self.shape
+        return (self.rays.reshape(lead + (H, W, 2)).contiguous(), self.coeffs.reshape(lead + (8,)).contiguous(), self.limit.reshape(lead).contiguous())
+
+
+def camera_rays(intrinsics, distortion, shape, device=None):
+    """The lens of calibrated depth cameras as ray tables -> `CameraRays` (sh_camera_rays; include/sh_kernels.h, "Camera rays").
+    intrinsics: (fx, fy, cx, cy) as [4], [V, 4] or [B, V, 4]; distortion: OpenCV's rational model (k1, k2, p1, p2, k3, k4, k5, k6),
+    4, 5 or 8 coefficients per camera (shorter sets are zero-padded in that order) as [k], [V, k] or [B, V, k]; the two leading
+    shapes broadcast.  shape = (H, W); device: None is the default HIP device.  Per pixel centre the model is inverted by 20
+    fixed-point steps in fp64 and checked by one forward evaluation: a pixel whose reprojection misses by more than 1e-3 pixel
+    has no ray (NaN) - the wrappers that take the result then mask it.  Two launches per call and ONE host synchronisation, to
+    read `complete`.  Deterministic: the same bits for a camera alone and among others.  ValueError (before the device is used)
+    for a wrong coefficient count, shapes that do not broadcast, non-finite values or fx / fy that are not positive."""
+    what = "camera_rays"
+    try:
+        H, W = (int(v) for v in shape)
+    except (ValueError, TypeError):
+        H = W = -1
+    if H < 1 or W < 1:
+        raise ValueError("%s: shape must be (H, W) with both at least 1, got %r" % (what, shape))
+    try:
+        k = np.asarray(intrinsics.detach().cpu().numpy() if torch.is_tensor(intrinsics) else intrinsics, dtype=np.float64)
+    except (ValueError, TypeError):
+        k = None
+    if k is None or k.ndim not in (1, 2, 3) or k.shape[-1] != 4:
+        raise ValueError("%s: intrinsics must be (fx, fy, cx, cy) as [4], [V, 4] or [B, V, 4]" % what)
+    if not np.isfinite(k).all() or not (k[..., :2] > 0).all():
+        raise ValueError("%s: fx and fy must be finite and positive, cx and cy finite" % what)
+    n = np.shape(distortion.detach().cpu().numpy() if torch.is_tensor(distortion) else distortion)
+    try:
+        lead = np.broadcast_shapes(k.shape[:-1], tuple(n[:-1]))
+    except ValueError:
+        raise ValueError("%s: distortion of shape %s does not match the cameras: intrinsics of shape %s" % (what, tuple(n), k.shape)) from None
+    if len(lead) > 2:
+        raise ValueError("%s: distortion of shape %s does not match the cameras: at most [B, V, k]" % (what, tuple(n)))
+    c = _distortion_arg(what, distortion, (tuple(n[:-1]),))
+    return _camera_rays(np.broadcast_to(k.astype(np.float32), lead + (4,)).copy(), np.broadcast_to(c, lead + (8,)).copy(), H, W, device)
+
+
+def _camera_rays(k, c, H, W, device):
+    """`camera_rays` on checked float32 arrays lead + (4,) and lead + (8,)."""
+    lead = k.shape[:-1]
+    k, c = np.array(k, np.float32), np.array(c, np.float32)                            # own, writable copies: they are kept
+    dev = torch.device(device if device is not None else "cuda")
+    kd, cd = torch.from_numpy(k.reshape(-1, 4)).to(dev), torch.from_numpy(c.reshape(-1, 8)).to(dev)
+    rays, limit, complete = ops.camera_rays(kd, cd, H, W)
+    return CameraRays(rays.view(lead + (H, W, 2)), limit.view(lead), cd.view(lead + (8,)), kd.view(lead + (4,)),
+                      bool(complete.min().item()) if complete.numel() else True, (k, c))          # the one synchronisation
+
+
+def _calibration(what, distortion, k, B, V, H, W, device):
+    """distortion= of the depth wrappers -> None, or (CameraRays, lead): the cameras of B bodies of V views each (V = 0: one
+    camera per body) whose intrinsics are k float32 [B * max(V, 1), 4]; lead is the leading shape ops takes - [1] / [V] when one
+    table per camera serves every body, [B] / [B, V] otherwise.  Coefficients: a table per camera when neither they nor the
+    intrinsics differ between the bodies, else per body.  A ready CameraRays must fit: ValueError for another image size,
+    camera count or intrinsics.  Nothing is launched for a ready one; for coefficients the device is used only after the checks."""
+    if distortion is None:
+        return None
+    per = max(V, 1)
+    shared, own = ((V,) if V else (1,)), ((B, V) if V else (B,))
+    kk = k.reshape(B, per, 4)
+    if isinstance(distortion, CameraRays):
+        cr = distortion
+        if cr.shape != (H, W):
+            raise ValueError("%s: the CameraRays is of %d x %d images, the depth of %d x %d" % ((what,) + cr.shape + (H, W)))
+        if cr.lead == shared or (per == 1 and cr.lead == ()):
+            lead = shared
+        elif cr.lead == own:
+            lead = own
+        else:
+            raise ValueError("%s: the CameraRays holds cameras %s, the images need %s or %s" % (what, list(cr.lead), list(shared), list(own)))
+        if not np.array_equal(np.broadcast_to(cr._host[0].reshape(-1, per, 4), (B, per, 4)), kk):
+            raise ValueError("%s: the CameraRays was made for other intrinsics" % what)
+        return cr, lead
+    c = _distortion_arg(what, distortion, ((), (V,), (B, V)) if V else ((), (B,)))
+    c = np.broadcast_to(c[:, None] if V == 0 and c.ndim == 2 else c, (B, per, 8))
+    if (kk == kk[:1]).all() and (c == c[:1]).all():
+        return _camera_rays(np.ascontiguousarray(kk[0].reshape(shared + (4,))), np.ascontiguousarray(c[0].reshape(shared + (8,))), H, W, device), shared
+    return _camera_rays(np.ascontiguousarray(kk.reshape(own + (4,))), np.ascontiguousarray(c.reshape(own + (8,))), H, W, device), own
+
+
+def _ray_mask(cal, m, B, V, H, W):
+    """The mask rule: with an incomplete table "this pixel has a ray" is ANDed into the mask m (uint8 [B * max(V, 1), H, W] or None)
+    with torch ops before the validity rules run in the kernels, which never test a ray."""
+    cr, lead = cal
+    if cr.complete:
+        return m
+    per = max(V, 1)
+    has = ~torch.isnan(cr.rays.reshape(-1, per, H, W, 2)[..., 0])                        # [1 or B, per, H, W]
+    has = has.expand(B, per, H, W).reshape(B * per, H, W).to(torch.uint8)
+    return has.contiguous() if m is None else (m & has).contiguous()
+
+
 def _depth_inputs(what, depth, intrinsics, mask, z_range):
     """The checks `unproject_depth` and `DepthField.from_depth` share, nothing moved to the device yet -> (depth [B, H, W] fp32 or
     int16 words, intrinsics float32 numpy [B, 4], mask [B, H, W] or None, near, far)."""
@@ -393,40 +532,50 @@ def _depth_upload(d, k, m, device):
 
 
 def _depth_rows(what, depth, intrinsics, ext=None, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                device=None, merge_tol=None):
+                device=None, merge_tol=None, distortion=None):
     """`unproject_depth` (ext None), with the counts as the host read them as a fifth result - and what `unproject_depth_views`
     shares with it: `_depth_inputs` and the checks of max_step and stride - every ValueError before the device is used -, then
     upload, count, read the counts once, points.  ext: a rig's float32 [B, V, 12] - depth, intrinsics and mask then hold an image
     per row, body-major, and ops.depth_views_points' results come first.  merge_tol (a rig only, checked by the caller): the rows
-    are merged with the resident images (`_merge_rows`: a second synchronisation) and `seen` is an eighth result."""
+    are merged with the resident images (`_merge_rows`: a second synchronisation) and `seen` is an eighth result.  distortion: None
+    - the launches and bits of ever -, or the lens (`_calibration`): the "Camera rays" forms of the same launches."""
     d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
     step = math.inf if max_step is None else float(max_step)
     if not step >= 0:
         raise ValueError("%s: max_step must be None or >= 0, got %r" % (what, max_step))
     if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
         raise ValueError("%s: stride must be an integer >= 1, got %r" % (what, stride))
+    B, V = (d.shape[0], 0) if ext is None else tuple(ext.shape[:2])
+    dev = device if device is not None or not d.is_cuda else d.device
+    cal = _calibration(what, distortion, k, B, V, d.shape[-2], d.shape[-1], dev)
     d, k, m = _depth_upload(d, k, m, device)
+    rays = {}
+    if cal is not None:
+        m = _ray_mask(cal, m, B, V, d.shape[-2], d.shape[-1])
+        rays = dict(rays=cal[0]._planes(cal[1]))
     lead, count, points = (d, k), ops.depth_count, ops.depth_points
     if ext is not None:
         rig = tuple(ext.shape[:2])
         lead = (d.view(rig + tuple(d.shape[-2:])), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device))
         m = None if m is None else m.view(lead[0].shape)
         count, points = ops.depth_views_count, ops.depth_views_points
-    opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride))
+    opts = dict(mask=m, depth_scale=depth_scale, z_near=near, z_far=far, max_step=step, drop_isolated=drop_isolated, stride=int(stride), **rays)
     counts, ws = count(*lead, **opts)
     host_counts = counts.cpu().numpy()                                                  # the one synchronisation
     most = int(host_counts.max())
     rows = points(*lead, counts, ws, max(most, 1), most, **opts)
     if merge_tol is None:
         return rows + (counts, host_counts)
-    seen, keep = ops.depth_views_overlap(*lead, rows[0], rows[1], rows[3], counts, merge_tol, mask=m, depth_scale=depth_scale, z_near=near, z_far=far)
+    seen, keep = ops.depth_views_overlap(*lead, rows[0], rows[1], rows[3], counts, merge_tol, mask=m, depth_scale=depth_scale, z_near=near, z_far=far,
+                                         **rays)
     return _merge_rows(rows[0], rows[1], rows[2], rows[3], counts, rig[1], keep, seen)
 
 
-def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None):
+def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1, device=None,
+                    distortion=None):
     """Depth images -> scans (sh_depth_count, sh_depth_points; include/sh_kernels.h, "Depth images").  depth: a host array or a
     tensor [B, H, W] or [H, W], fp32 or 16-bit unsigned words (a tensor of int16 is read as such words); z = raw * depth_scale.
-    intrinsics: (fx, fy, cx, cy) as [4] or [B, 4], pinhole, no distortion.  A pixel is valid when z is finite and positive, lies
+    intrinsics: (fx, fy, cx, cy) as [4] or [B, 4]; without distortion= an ideal pinhole.  A pixel is valid when z is finite and positive, lies
     in z_range = (near, far) if given, is not the word 0, and mask (bool or integer, the depth's shape) is non-zero there.  Its
     point is ((u - cx) z / fx, (v - cy) z / fy, z) in the camera's frame.  Its normal comes from its grid neighbours - central
     differences where both are usable, one-sided where one is; a neighbour is usable when valid and within max_step in depth
@@ -439,8 +588,18 @@ def unproject_depth(depth, intrinsics, *, depth_scale=1.0, mask=None, z_range=No
     and -1.  Rows are in 16 x 16 tile order, Z-order inside a tile: neighbours in memory are neighbours on the surface.  One host
     synchronisation, to read the counts: a packing-time operation.  Deterministic - the same bits for an image alone and inside
     any batch.  Not differentiable.  ValueError for wrong shapes or dtypes, fx / fy not finite and positive, stride < 1 or a
-    negative max_step."""
-    return _depth_rows("unproject_depth", depth, intrinsics, None, depth_scale, mask, z_range, max_step, drop_isolated, stride, device)[:4]
+    negative max_step.
+    distortion: None - the launches and bits described above -, or the camera's lens (include/sh_kernels.h, "Camera rays"): OpenCV
+    coefficients (k1, k2, p1, p2, k3, k4, k5, k6), 4, 5 or 8 of them as [k] or [B, k], or a ready `CameraRays` (`camera_rays`) -
+    the form for a fixed camera over many calls, no ray launch then; coefficients cost the two launches and the synchronisation
+    of `camera_rays` per call.  A pixel's point is then (x z, y z, z) with (x, y) its ray from the table, and its neighbours'
+    points come from theirs (sh_depth_rays_count / _points); everything else is as above.  A pixel the lens model cannot be
+    inverted at has no ray and counts as masked.  All-zero coefficients take this path too and agree with the pinhole result to
+    rounding, not bit for bit: x z against ((u - cx) z) / fx.  ValueError (before the device is used) for a wrong coefficient
+    count, a shape that does not match the cameras, non-finite coefficients, or a CameraRays of another image size, camera count
+    or intrinsics."""
+    return _depth_rows("unproject_depth", depth, intrinsics, None, depth_scale, mask, z_range, max_step, drop_isolated, stride, device,
+                       distortion=distortion)[:4]
 
 
 def pack_extrinsics(extrinsics, what="extrinsics"):
@@ -503,19 +662,19 @@ def _rig_inputs(what, depth, intrinsics, extrinsics, mask):
 
 
 def _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                           device=None, merge_tol=None):
+                           device=None, merge_tol=None, distortion=None):
     """`unproject_depth_views`, with the counts as the host read them and the extrinsics float32 [B, V, 12] as two more results -
     and, with a merge_tol, `seen` as a ninth.  Every ValueError is raised before the device is used."""
     what = "unproject_depth_views"
     if merge_tol is not None:
         merge_tol = _check_merge_tol(what, merge_tol)
     d, k, ext, m = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
-    rows = _depth_rows(what, d, k, ext, depth_scale, m, z_range, max_step, drop_isolated, stride, device, merge_tol)
+    rows = _depth_rows(what, d, k, ext, depth_scale, m, z_range, max_step, drop_isolated, stride, device, merge_tol, distortion)
     return rows[:7] + (ext,) + rows[7:]
 
 
 def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mask=None, z_range=None, max_step=None, drop_isolated=False, stride=1,
-                          device=None, merge_tol=None):
+                          device=None, merge_tol=None, distortion=None):
     """The depth cameras of a rig -> ONE scan per body in the rig's frame (sh_depth_views_count, sh_depth_views_points;
     include/sh_kernels.h, "Depth views").  depth: [B, V, H, W], or [V, H, W] with extrinsics that have no batch axis (B = 1); fp32 or
     16-bit words as in `unproject_depth`, and depth_scale, mask (the depth's shape), z_range, max_step, drop_isolated and stride
@@ -532,9 +691,13 @@ def unproject_depth_views(depth, intrinsics, extrinsics, *, depth_scale=1.0, mas
     negative max_step, or extrinsics that are no rigid transforms.
     merge_tol: None - nothing more is launched -, or a depth tolerance >= 0 (ValueError when negative or NaN): the rows that a
     better-placed camera also measures within it are dropped (`views_overlap`, `merge_views`) and the six results are the merged
-    ones.  That costs TWO host synchronisations instead of one: the kept counts are read as well."""
+    ones.  That costs TWO host synchronisations instead of one: the kept counts are read as well.
+    distortion: None, or the cameras' lenses as in `unproject_depth` - coefficients [k], [V, k] or [B, V, k], or a ready
+    `CameraRays` of [V] or [B, V] cameras: the points come from the ray tables (sh_depth_views_rays_count / _points) and, with a
+    merge_tol, the overlap pass projects through the lens model (sh_depth_views_rays_overlap).  A calibration that does not differ
+    between the bodies is ONE table per camera, whatever B.  One resolution per rig."""
     points, normals, pixel, view, view_first, counts = _unproject_depth_views(depth, intrinsics, extrinsics, depth_scale, mask, z_range, max_step,
-                                                                              drop_isolated, stride, device, merge_tol)[:6]
+                                                                              drop_isolated, stride, device, merge_tol, distortion)[:6]
     return points, normals, pixel, view, counts, view_first
 
 
@@ -561,7 +724,7 @@ def _rig_batch(what, scans):
     return scans.view_first.shape[1] - 1
 
 
-def views_overlap(scans, depth, intrinsics, extrinsics, *, tol, depth_scale=1.0, mask=None, z_range=None):
+def views_overlap(scans, depth, intrinsics, extrinsics, *, tol, depth_scale=1.0, mask=None, z_range=None, distortion=None):
     """Which rows of a rig batch a better-placed camera also measures (sh_depth_views_overlap; include/sh_kernels.h, "Depth views:
     overlap").  scans: the rig batch `ScanBatch.from_depth(depth, intrinsics, device, extrinsics=extrinsics, ...)` made from THESE
     images - depth, intrinsics, extrinsics, depth_scale, mask and z_range as given there (max_step, drop_isolated and stride are
@@ -572,7 +735,9 @@ def views_overlap(scans, depth, intrinsics, extrinsics, *, tol, depth_scale=1.0,
     -> (keep bool [B, M]: False where another camera keeps the row, and in the padding; seen int32 [B, M] read as unsigned: bit c
     set where camera c observes the row, its own bit always).  One launch, nothing synchronised; fp32 throughout, deterministic.
     ValueError (before the device is used) for scans that are no rig batch or of another B or V, a tol that is negative or NaN,
-    and what `unproject_depth_views` refuses in the images."""
+    and what `unproject_depth_views` refuses in the images.
+    distortion: None, or the lenses given to `from_depth` (`unproject_depth_views`): every point is projected through the lens
+    model, and a point beyond a camera's fold-back limit is not observed by it (sh_depth_views_rays_overlap)."""
     what = "views_overlap"
     V = _rig_batch(what, scans)
     tol = _check_merge_tol(what, tol, "tol")
@@ -580,12 +745,17 @@ def views_overlap(scans, depth, intrinsics, extrinsics, *, tol, depth_scale=1.0,
     if ext.shape[:2] != (len(scans), V):
         raise ValueError("%s: the scans hold %d bodies x %d views, the extrinsics %d x %d" % ((what, len(scans), V) + ext.shape[:2]))
     d, k, m, near, far = _depth_inputs(what, d, k, m, z_range)
-    d, k, m = _depth_upload(d, k, m, scans.points.device)
     rig = tuple(ext.shape[:2])
+    cal = _calibration(what, distortion, k, rig[0], rig[1], d.shape[-2], d.shape[-1], scans.points.device)
+    d, k, m = _depth_upload(d, k, m, scans.points.device)
+    rays = {}
+    if cal is not None:
+        m = _ray_mask(cal, m, rig[0], rig[1], d.shape[-2], d.shape[-1])
+        rays = dict(rays=cal[0]._planes(cal[1]))
     d = d.view(rig + tuple(d.shape[-2:]))
     seen, keep = ops.depth_views_overlap(d, k.view(rig + (4,)), torch.from_numpy(ext).to(d.device), scans.points, scans.normals, scans.view,
                                          scans.counts, tol, mask=None if m is None else m.view(d.shape), depth_scale=depth_scale, z_near=near,
-                                         z_far=far)
+                                         z_far=far, **rays)
     return keep.bool(), seen
 
 
@@ -626,39 +796,59 @@ class DepthField:
     (H, W).  `free_space` reads it; made once per image batch by `from_depth`.
     A RIG field (`from_depth(..., extrinsics=)`) holds the V cameras of every body: the planes are [B, V, H, W], `intrinsics`
     [B, V, 4], `extrinsics` fp32 [B, V, 12] on the device (camera -> rig, `pack_extrinsics`' layout; a NaN row: an absent camera)
-    and `views` = V; `len` is still B and `shape` (H, W).  Without extrinsics both members are None."""
+    and `views` = V; `len` is still B and `shape` (H, W).  Without extrinsics both members are None.
+    `rays`: None, or the cameras' lenses as a `CameraRays` (`from_depth(..., distortion=)`): `free_space` then projects through the
+    lens model and takes the silhouette rays from the tables."""
 
-    def __init__(self, cls, z, nearest, intrinsics, extrinsics=None):
+    def __init__(self, cls, z, nearest, intrinsics, extrinsics=None, rays=None, rays_lead=None):
         self.cls, self.z, self.nearest, self.intrinsics, self.extrinsics = cls, z, nearest, intrinsics, extrinsics
+        self.rays, self._rays_lead = rays, rays_lead
         self.views = None if extrinsics is None else int(extrinsics.shape[1])
         self.shape = tuple(cls.shape[-2:])
 
     @classmethod
-    def from_depth(cls, depth, intrinsics, device=None, *, extrinsics=None, depth_scale=1.0, mask=None, z_range=None):
+    def from_depth(cls, depth, intrinsics, device=None, *, extrinsics=None, depth_scale=1.0, mask=None, z_range=None, distortion=None):
         """depth, intrinsics, depth_scale, mask, z_range and device as in `unproject_depth`, with its checks and ValueErrors (raised
         before the device is used).  Two launches, no host synchronisation.  Deterministic - the same bits for an image alone and
         inside any batch.  RuntimeError for an image side above 16384.
         extrinsics: None, or a rig's camera -> rig transforms [V, 3, 4] / [B, V, 3, 4] with depth [V, H, W] / [B, V, H, W] and
         intrinsics [4], [V, 4] or [B, V, 4] as in `unproject_depth_views` (its checks and ValueErrors): a rig field, made by the
-        same two launches over the B * V images."""
+        same two launches over the B * V images.
+        distortion: None, or the lenses as in `unproject_depth` / `unproject_depth_views` (their checks and ValueErrors).  The
+        field's planes live in pixel space and are made by the same two launches; the table is kept as `rays`, and a pixel
+        without a ray is classified as a masked one is."""
         what = "DepthField.from_depth"
         ext = None
         if extrinsics is not None:
             depth, intrinsics, ext, mask = _rig_inputs(what, depth, intrinsics, extrinsics, mask)
         d, k, m, near, far = _depth_inputs(what, depth, intrinsics, mask, z_range)
+        B, V = (d.shape[0], 0) if ext is None else tuple(ext.shape[:2])
+        cal = _calibration(what, distortion, k, B, V, d.shape[-2], d.shape[-1], device if device is not None or not d.is_cuda else d.device)
         d, k, m = _depth_upload(d, k, m, device)
+        if cal is not None:
+            m = _ray_mask(cal, m, B, V, d.shape[-2], d.shape[-1])
+        lens = {} if cal is None else dict(rays=cal[0], rays_lead=cal[1])
         planes = ops.depth_field(d, k, mask=m, depth_scale=depth_scale, z_near=near, z_far=far)
         if ext is None:
-            return cls(*planes, k)
+            return cls(*planes, k, **lens)
         rig = tuple(ext.shape[:2])                                          # the same call over the B * V images, reshaped
-        return cls(*(p.view(rig + tuple(p.shape[-2:])) for p in planes), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device))
+        return cls(*(p.view(rig + tuple(p.shape[-2:])) for p in planes), k.view(rig + (4,)), torch.from_numpy(ext).to(d.device), **lens)
 
     def __len__(self):
         return self.cls.shape[0]
 
     def select(self, sl):
         """The images `sl` (a slice; of a rig field: the bodies) as a DepthField sharing this one's memory."""
-        return DepthField(self.cls[sl], self.z[sl], self.nearest[sl], self.intrinsics[sl], None if self.extrinsics is None else self.extrinsics[sl])
+        out = DepthField(self.cls[sl], self.z[sl], self.nearest[sl], self.intrinsics[sl], None if self.extrinsics is None else self.extrinsics[sl])
+        if self.rays is not None:                                           # tables per body are cut with them; one table per camera is shared
+            per_body = self._rays_lead == ((len(self), self.views) if self.views else (len(self),)) and self.rays.lead == self._rays_lead
+            out.rays = self.rays.select(sl) if per_body else self.rays
+            out._rays_lead = (len(out),) + self._rays_lead[1:] if per_body else self._rays_lead
+        return out
+
+    def _lens(self):
+        """What ops takes as rays=: None, or (table, coefficients, limit)."""
+        return None if self.rays is None else self.rays._planes(self._rays_lead)
 
 
 def nearest(q, t, q_count=None, t_count=None, t_mask=None, chunks=0):
@@ -1340,7 +1530,8 @@ def _check_pair(x, scans, n, what):
 # ------------------------------------------------------------------------------------------------ free space and silhouette
 def _free_space_fwd(x, field, cam, n, v_mask, mask_sb, margin):
     """The forward entry point on a field's planes -> (term, kind, loss, counts).  cam None: one camera, x in its frame."""
-    return ops._free_space_fwd(cam is not None, x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin)
+    return ops._free_space_fwd(cam is not None, x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin,
+                               rays=field._lens())
 
 
 class _FreeSpace(torch.autograd.Function):
@@ -1359,7 +1550,7 @@ class _FreeSpace(torch.autograd.Function):
         x, cam, counts = ctx.saved_tensors
         field, n, v_mask, mask_sb, margin = ctx.args
         g = ops._free_space_bwd(cam is not None, x, n, cam, field.cls, field.z, field.nearest, field.intrinsics, v_mask, mask_sb, margin, counts,
-                                gL.to(torch.float32).contiguous())
+                                gL.to(torch.float32).contiguous(), rays=field._lens())
         return g, None, None, None, None, None, None
 
 
@@ -1422,7 +1613,7 @@ def _free_space_args(what, x_hat, field, pose, n, vertex_mask, margin, cameras=N
 def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0, cameras=None):
     """What a one-view depth image adds to a fit beyond its points: -> (free [B], silhouette [B]), differentiable w.r.t. x_hat
     (sh_free_space_fwd / _bwd; include/sh_kernels.h, "Depth field").  x_hat [B, rows, 3] fp32 on the GPU, field: a `DepthField` of
-    the same B.  Every active vertex is projected into its image (pinhole, the field's intrinsics) and reads the ONE pixel it
+    the same B.  Every active vertex is projected into its image (the field's intrinsics; its lens, if it has one) and reads the ONE pixel it
     falls into:
       * a SURFACE pixel whose depth, less `margin`, lies behind the vertex: the vertex stands in space the sensor saw through -
         it adds (z - margin - Z)^2 to `free`;
@@ -1434,7 +1625,10 @@ def free_space(x_hat, field, *, pose=None, n=None, vertex_mask=None, margin=0.0,
     `pose.to_scan_frame` (plain torch, differentiable) and both values multiplied by pose.scale^2, which puts them in the units
     of x_hat, where they add to a Chamfer value.  The pose takes no gradient.
     Limits: nearest-pixel sampling - the image is read as a constant, the nearest pixel too, so there is no image gradient and
-    the value steps as a vertex crosses a pixel boundary; no robust or truncated form; pinhole without distortion.
+    the value steps as a vertex crosses a pixel boundary; no robust or truncated form.  A field made with distortion= (`field.rays`)
+    is read through its lens model - the rational model of "Camera rays", no fisheye or equidistant model: the vertex is projected
+    by the forward model, a vertex beyond the fold-back limit is outside, the silhouette ray comes from the table (a pixel without
+    a ray: no term), and the gradient needs no Jacobian of the lens (sh_free_space_views_rays_fwd / _bwd).
     A RIG field (`DepthField.from_depth(..., extrinsics=)`; a rig of one serves a single camera): every vertex is judged by each
     of the V cameras in turn and both values are sums over the cameras of the per-camera means (sh_free_space_views_fwd / _bwd;
     "Free space from a rig").  x_hat stays in the model's frame: `pose` is then the Pose rig frame -> model frame (None: the
